@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- ResNet-50 f32, batch 32 per GPU, on the HIP backend (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W [--config f32|int8] [--lanes L] [--chains C] [--via-runner]
+    python bench.py --gpus N --steps K --warmup W [--config f32|int8] [--lanes L] [--chains C] [--via-runner] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes the outputs of the last timed step when
+`--dump-outputs DIR` is given (DIR/logits.npy, float32: the logits of the batch that step ran; rank r > 0 writes logits_rank<r>.npy) and prints the
+line (`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, ...).  The inputs are seeded, so two runs with the same arguments see the
+same weights and batches.  Every other measurement -- the one-batch latencies, the PCIe-inclusive pass, the instrumented roofline pass, the co-run and
+per-shape tables, the CPU baselines and the secondary configs -- runs only with `--full`, as described below.
 
 `--gpus N` always means N ranks, one per GPU: without a launcher the script spawns them itself (torch.distributed.run);
 under a launcher it refuses to run when WORLD_SIZE != N.  `--config int8` runs the dynamically quantized graph
@@ -19,7 +25,7 @@ steps (both synchronisation points cover every stream of every lane); `ms_per_st
 data-path collective (weak scaling: 32 images per GPU); the only collective is the one-time RCCL broadcast of the model's weight arena from rank 0.
 
 Rank 0 prints ONE COMPACT JSON line (at most 4096 bytes: `compact_line`; the driver keeps a bounded tail of stdout, and round 5's 23 KB line came back
-unparsed) as the LAST thing on stdout: the contract fields, `roofline` -- f32: achieved / frac = the conv FLOPs of one batch over the TIMED step (every kernel
+unparsed) as the LAST thing on stdout: the contract fields and, with `--full`, `roofline` -- f32: achieved / frac = the conv FLOPs of one batch over the TIMED step (every kernel
 and gap included) with the dominant kernel's stand-alone figures (HIP events per launch, an instrumented eager pass outside the timed region) as
 `dominant_kernel` -- plus, under lanes, `dominant_kernel.co_run`: the dominant layer family on `lanes` streams at once, the state a launch of the timed schedule
 runs in and the way the lanes plan's entries were chosen (rten_amd/workloads/corun.py) -- and its HBM traffic from the committed PMC pass when that pass ran the same launch plan; int8: the dominant kernel against the HBM peak plus
@@ -192,6 +198,13 @@ def emit(out, args, key=None):
         print(f"bench.py: could not write {path}: {e}", file=sys.stderr)
     sys.stdout.flush()
     print(compact_line(out, rel), flush=True)
+
+
+def dump_outputs(path, rank, logits):
+    """--dump-outputs: what a caller of the timed path received in the last timed step (the logits of its batch), as float32 .npy."""
+    os.makedirs(path, exist_ok=True)
+    name = "logits" if rank == 0 else f"logits_rank{rank}"
+    np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(logits, dtype=np.float32))
 
 
 def cpu_baseline(specs, weights, budget_s=12.0):
@@ -401,9 +414,9 @@ def secondary_configs():
     res = {}
     # the latency-optimal f32 schedule beside the throughput one: ONE replica running the batch as 4 sub-batch chains (round 4's schedule, its own committed
     # plan), in a process of its own (idle lane streams beside the four chains cost it 25 %: 3.5 vs 2.7-2.8 ms)
-    jobs = (("resnet50_f32_b32_4chains_1lane", [os.path.join(root, "bench.py"), "--chains", "4", "--lanes", "1", "--no-secondary", "--no-cpu-baseline", "--no-shapes",
+    jobs = (("resnet50_f32_b32_4chains_1lane", [os.path.join(root, "bench.py"), "--full", "--chains", "4", "--lanes", "1", "--no-secondary", "--no-cpu-baseline", "--no-shapes",
                                                 "--detail-file", os.path.join(root, "gpurun_out", "bench_detail_f32_4chains.json")]),
-            ("resnet50_int8_b32", [os.path.join(root, "bench.py"), "--config", "int8", "--no-secondary"]),
+            ("resnet50_int8_b32", [os.path.join(root, "bench.py"), "--full", "--config", "int8", "--no-secondary"]),
             ("bert_base_f32_b32_s128", [os.path.join(root, "tools", "bench_bert.py")]),
             ("resnet50_f32_b1_latency", [os.path.join(root, "tools", "bench_resnet50_b1.py")]),
             ("resnet50_int8_b1_latency", [os.path.join(root, "tools", "bench_resnet50_b1.py"), "--config", "int8"]))
@@ -722,6 +735,10 @@ def run_via_executor(args):
             dist.barrier()
             dist.destroy_process_group()
         return 3
+    if args.dump_outputs:  # the lane that ran the last timed step (every lane holds the logits of its last batch)
+        l_last = (args.steps - 1) % lanes
+        op_l, os_l = models[l_last].output(0)
+        dump_outputs(args.dump_outputs, rank, DeviceTensor(lane_ctx[l_last], os_l, np.float32, ptr=op_l, keepalive=models[l_last]).numpy())
 
     # ---- per-step join (a latency figure: every step waits for all chains) beside the free-running throughput figure above
     def one_batch_alone(m):
@@ -740,10 +757,10 @@ def run_via_executor(args):
             m.run()  # ONE replica, joined on the caller's stream every step, host not blocked: no overlap between steps
         m.sync()
         return float(np.median(lat)), (time.perf_counter() - t1) / min(args.steps, 20) * 1e3
-    p50, joined_ms = one_batch_alone(model)
+    p50, joined_ms = one_batch_alone(model) if args.full else (None, None)
     lanes_plan_alone = None
     one_plan = os.path.join(ROOT, "profiles", "plans", "f32_1chain.json")
-    if not int8 and lanes > 1 and chains == 1 and world == 1 and not DRY and plan_path == default_plan and plan_text and os.path.exists(one_plan):
+    if args.full and not int8 and lanes > 1 and chains == 1 and world == 1 and not DRY and plan_path == default_plan and plan_text and os.path.exists(one_plan):
         # The lanes plan is chosen for company (round 6: per layer under co-run): ONE replica running it alone is slower than one replica under the plan a single
         # replica is given (3.4-3.6 vs 2.9 ms).  "One batch on one replica with nothing beside it" -- `ms_per_step_joined_every_step` / `p50_latency_ms`, the
         # figures of rounds 4-5 -- is therefore measured on a one-replica model under ITS plan (f32_1chain.json), loaded here beside the idle lanes; the lanes
@@ -767,7 +784,7 @@ def run_via_executor(args):
 
     # ---- PCIe-inclusive rate (the reference's Model::run takes host tensors): batch uploaded and logits downloaded every step.  Never `value`.
     pcie_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         t1 = time.perf_counter()
         for _ in range(min(args.steps, 20)):
             xt.upload(x)
@@ -779,7 +796,7 @@ def run_via_executor(args):
     step_ms = elapsed / args.steps * 1e3
     gflop = (resnet50.conv_flops_per_image() + 2 * 2048 * 1000) / 1e9
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         rep = model.profile_pass(max(1, min(args.steps, 10)))  # serialised, eager, HIP events per launch: per-kernel detail, outside the timed region
         nrep = max(1, min(args.steps, 10))
         tot_ms = sum(r["ms"] for r in rep)
@@ -856,7 +873,7 @@ def run_via_executor(args):
         global_batch = BATCH_PER_GPU * world
         out = {"metric": f"inferences/sec, ResNet-50 {'int8 (dynamically quantized)' if int8 else 'f32'} batch 32 per GPU", "value": round(global_batch * args.steps / elapsed, 2),
                "unit": "inferences/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(step_ms, 4),
-               "ms_per_step_joined_every_step": round(joined_ms, 4), "p50_latency_ms": round(p50, 4),
+               **({"ms_per_step_joined_every_step": round(joined_ms, 4), "p50_latency_ms": round(p50, 4)} if p50 is not None else {}),
                **({"lanes_plan_alone": lanes_plan_alone} if lanes_plan_alone else {}),
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8 x i8 -> i32 (f32 between layers)" if int8 else "f32",
                "data": "recording (no device: control-flow test)" if DRY else "synthetic",
@@ -894,13 +911,13 @@ def run_via_executor(args):
             out["config"]["quantized_output_launches"] = sorted(p.get("qout", []))
             out["config"]["quantized_output_by_recomputation"] = sorted(p.get("qout2", []))
             out["config"]["quantize_on_load_layers"] = sorted(p.get("fused_dql", []))
-        if world == 1 and not args.no_cpu_baseline and not DRY:
+        if world == 1 and args.full and not args.no_cpu_baseline and not DRY:
             out["cpu_baseline"] = cpu_baseline_int8(resnet50.conv_specs(), weights) if int8 else cpu_baseline(resnet50.conv_specs(), weights)
             if not int8:
                 out["cpu_baseline"]["other_cpu_implementation"] = torch_cpu_reference(resnet50.conv_specs(), weights)
         else:
             out["cpu_baseline"] = None
-        if world == 1 and not args.no_secondary and not int8 and not DRY:
+        if world == 1 and args.full and not args.no_secondary and not int8 and not DRY:
             out["secondary"] = secondary_configs()
             four = out["secondary"].get("resnet50_f32_b32_4chains_1lane") or {}
             if "p50_latency_ms" in four:
@@ -968,6 +985,11 @@ def parse_args():
                          "1 when --chains is given).  A throughput schedule: `p50_latency_ms` stays the latency of ONE batch on one replica")
     ap.add_argument("--no-shapes", action="store_true", help="f32: skip the stand-alone per-shape table (`roofline.shapes`)")
     ap.add_argument("--detail-file", default=None, help="where the full record goes (default gpurun_out/bench_detail[_<config>].json); the printed line stays compact")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement: one-batch latencies, the PCIe-inclusive pass, the instrumented roofline "
+                         "pass, the co-run and per-shape tables, the CPU baselines and the secondary configs (off by default: a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last timed step (the logits of its batch) as DIR/logits.npy, float32")
     ap.add_argument("--recording-test", action="store_true",
                     help="control-flow test mode (tests/test_bench_world8.py): together with RTEN_BENCH_RECORDING=1, launches are recorded instead of issued")
     return ap.parse_args()
@@ -1214,21 +1236,23 @@ def run_via_runner(args):
             print(f"bench.py: a quantized-output launch gave up waiting for its grid (workgroups not all resident) {where}: results are void", file=sys.stderr)
             sys.exit(3)
     check_qout("during the timed steps")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, net.logits.numpy())
 
     # ---- p50 latency per batch (separate pass, host-timed per step)
     lat = []
-    for _ in range(min(args.steps, 20)):
+    for _ in range(min(args.steps, 20) if args.full else 0):
         t1 = time.perf_counter()
         net.run()
         ctx.sync()
         lat.append((time.perf_counter() - t1) * 1e3)
-    p50 = float(np.median(lat))
+    p50 = float(np.median(lat)) if lat else None
     check_qout("during the latency pass")
 
     # ---- PCIe-inclusive rate (the reference's Model::run takes host tensors): the same K steps with the batch uploaded
     #      from host memory and the logits downloaded every step.  Reported beside `value`, never as `value`.
     pcie_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         t1 = time.perf_counter()
         for _ in range(min(args.steps, 20)):
             net.x.upload(x)
@@ -1240,7 +1264,7 @@ def run_via_runner(args):
     # ---- roofline of the dominant kernel: instrumented eager pass over the same K steps (HIP events per launch
     #      on the backend's stream).  Kept out of the timed region so `value` is not perturbed.
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         rep = net.profile_pass(args.steps)  # serialised launches (chain after chain): clean per-kernel durations
         tot_ms = sum(r["ms"] for r in rep)
         if int8:
@@ -1345,7 +1369,7 @@ def run_via_runner(args):
         out = {
             "metric": metric,
             "value": round(value, 2), "unit": "inferences/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "p50_latency_ms": round(p50, 4),
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4), **({"p50_latency_ms": round(p50, 4)} if p50 is not None else {}),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8 x i8 -> i32 (f32 between layers)" if int8 else "f32",
             "data": "recording (no device: control-flow test)" if DRY else "synthetic",
             "config": {"workload": workload, "path": "runner",
@@ -1371,13 +1395,13 @@ def run_via_runner(args):
             out["config"]["quantized_output_launches"] = sorted(set(net.qout_next) - net._qout_off) if net.fused_qout else []
             out["config"]["int8_pad_mode"] = ("RAW0_I8 -- ASSUMPTION: padded taps of an integer convolution hold raw 0 after the u8->i8 shift, the x86 reference's im2col behaviour "
                                               "(rten-gemm/src/im2col.rs:340-358, SURVEY App. C.1); unpinned by a reference-held vector; ZERO_POINT / RAW0_U8 are the other modes of the ABI")
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if n_gpus == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_int8(net.specs, weights) if int8 else cpu_baseline(net.specs, weights)
             if not int8:
                 out["cpu_baseline"]["other_cpu_implementation"] = torch_cpu_reference(net.specs, weights)
         else:
             out["cpu_baseline"] = None
-        if n_gpus == 1 and world == 1 and not args.no_secondary and not int8:
+        if n_gpus == 1 and world == 1 and args.full and not args.no_secondary and not int8:
             out["secondary"] = secondary_configs()
         emit(out, args, key=args.config + "_runner")
     if DRY:

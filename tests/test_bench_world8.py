@@ -84,7 +84,7 @@ def test_eight_rank_bench_control_flow(config):
     """... and the same for `--via-runner` (the Python runner: the A/B path)."""
     from rten_amd import lib as L
     from rten_amd.workloads import resnet50, resnet50_int8
-    r = _run(8, config, 29611 if config == "int8" else 29613, extra=("--via-runner",))
+    r = _run(8, config, 29611 if config == "int8" else 29613, extra=("--via-runner", "--full"))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line, j = _line_and_detail(r)  # rank 0 prints ONE line
     assert line["config"]["path"] == "runner"
@@ -126,3 +126,36 @@ def test_world_size_mismatch_is_refused_in_recording_mode_too():
     env.update(RTEN_BENCH_RECORDING="1", WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", PYTHONPATH=ROOT)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--config", "int8", "--recording-test"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and "refusing to report" in r.stderr
+
+
+@pytest.mark.parametrize("path", ["executor", "runner"])
+def test_plain_run_times_the_steps_only_and_dumps_the_outputs(path, tmp_path):
+    """A plain run sets up, warms up, times the steps, writes the logits of the last timed step (--dump-outputs) and prints the line; the one-batch
+    latency, PCIe-inclusive and instrumented passes (and the CPU baselines and secondary configs) run only with --full."""
+    import re
+
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(RTEN_BENCH_RECORDING="1", PYTHONPATH=ROOT + os.pathsep + env.get("PYTHONPATH", ""), OMP_NUM_THREADS="1")
+    launches = {}
+    for full in (False, True):
+        out = tmp_path / ("full" if full else "plain")
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--recording-test",
+               "--detail-file", str(out / "detail.json"), "--dump-outputs", str(out)]
+        cmd += (["--via-runner"] if path == "runner" else []) + (["--full", "--no-cpu-baseline", "--no-secondary"] if full else [])
+        r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and len(lines[0]) <= 4096, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert {"metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype"} <= set(line) and line["steps"] == 3 and line["warmup"] == 1
+        assert line["config"]["path"] == path and line["cpu_baseline"] is None and "secondary" not in line
+        assert ("p50_latency_ms" in line) == full
+        logits = np.load(out / "logits.npy")
+        assert logits.dtype == np.float32 and logits.shape == (32, 1000)
+        m = re.search(r"\[recording\] rank 0 seed 1234 shard \[0\]\.\.\+32 graph_launch (\d+)", r.stderr)
+        assert m, r.stderr[-2000:]
+        launches[full] = int(m.group(1))
+    # graph launches on the first lane's (executor: lanes round robin) / the main context's (runner: every step) stream: warm-up + timed steps, nothing more
+    assert launches[False] == (1 + 1 if path == "executor" else 1 + 3)
+    assert launches[True] > launches[False]

@@ -1,15 +1,16 @@
 #!/bin/bash
-# Shorter GPU session: GPU parity tests + bench with the per-layer table (no rocprof).
-# Usage: gpurun --timeout 1500 -- 'bash tools/gpu/quick.sh <tag> [pytest -k expr]'
+# Shorter GPU session: GPU parity tests + the full bench record (no rocprof).
+# Usage: OUT=<results dir> bash tools/gpu/quick.sh <tag> [pytest -k expr]
 TAG=${1:-q}
 KEXPR=${2:-}
-mkdir -p gpurun_out
+OUT=${OUT:?set OUT to the directory the results go to}
+mkdir -p $OUT
 export TMPDIR=/tmp
 if [ -n "$KEXPR" ]; then
-  timeout 900 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider -k "$KEXPR" > gpurun_out/${TAG}_pytest_gpu.log 2>&1
+  timeout 900 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider -k "$KEXPR" > $OUT/${TAG}_pytest_gpu.log 2>&1
 else
-  timeout 1200 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider > gpurun_out/${TAG}_pytest_gpu.log 2>&1
+  timeout 1200 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider > $OUT/${TAG}_pytest_gpu.log 2>&1
 fi
-echo "pytest rc=$?" >> gpurun_out/${TAG}_pytest_gpu.log
-timeout 900 python bench.py --layer-table --save-plan gpurun_out/${TAG}_plan.json > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err; echo "bench rc=$?" >> gpurun_out/${TAG}_bench.err
-tail -15 gpurun_out/${TAG}_pytest_gpu.log; head -c 2500 gpurun_out/${TAG}_bench.json; tail -5 gpurun_out/${TAG}_bench.err
+echo "pytest rc=$?" >> $OUT/${TAG}_pytest_gpu.log
+timeout 900 python bench.py --full --layer-table --save-plan $OUT/${TAG}_plan.json --detail-file $OUT/${TAG}_bench_detail.json > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?" >> $OUT/${TAG}_bench.err
+tail -15 $OUT/${TAG}_pytest_gpu.log; head -c 2500 $OUT/${TAG}_bench.json; tail -5 $OUT/${TAG}_bench.err
