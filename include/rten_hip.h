@@ -159,6 +159,18 @@ int32_t rten_hip_calc_output_size_and_padding(int32_t in_h, int32_t in_w, int32_
 #define RTEN_HIP_ACT_NONE 0
 #define RTEN_HIP_ACT_RELU 1 /* Relu, src/ops/unary_elementwise.rs:611-613 */
 #define RTEN_HIP_ACT_GELU 2 /* Gelu, rten-vecmath/src/erf.rs:61-76 */
+/* The kinds below are reached only through the activation arguments (act_kind, act_alpha, act_beta) of rten_hip_activation_f32,
+ * rten_hip_gemm_f32_act and rten_hip_conv2d_f32_act, which take every kind; desc.act of rten_hip_gemm_f32 keeps NONE / RELU / GELU.
+ * Unused parameters are ignored; any other kind is RTEN_HIP_ERR_INVALID_VALUE.  rten-vecmath/src/exp.rs:201-275, relu.rs:13-25,
+ * src/ops/unary_elementwise.rs:248-303,437-471. */
+#define RTEN_HIP_ACT_SIGMOID 3      /* 1 / (1 + exp(-x)) */
+#define RTEN_HIP_ACT_SILU 4         /* x / (1 + exp(-x)) */
+#define RTEN_HIP_ACT_SWISH 5        /* x * sigmoid(alpha * x) */
+#define RTEN_HIP_ACT_HARD_SIGMOID 6 /* clamp(alpha * x + beta, 0, 1) */
+#define RTEN_HIP_ACT_HARD_SWISH 7   /* x * clamp(x / 6 + 0.5, 0, 1) */
+#define RTEN_HIP_ACT_CLIP 8         /* alpha = min, beta = max (Clamp trait: NaN -> min; min > max -> max) */
+#define RTEN_HIP_ACT_LEAKY_RELU 9   /* x < 0 ? alpha * x : x */
+#define RTEN_HIP_ACT_ELU 10         /* x >= 0 ? x : alpha * (exp(x) - 1) */
 
 typedef struct {
     int32_t m, n, k;
@@ -179,6 +191,9 @@ typedef struct {
 
 int32_t rten_hip_gemm_f32(rten_hip_ctx *ctx, const rten_hip_gemm_desc *desc, const float *a, const float *b,
                           const float *bias, float *c);
+/* rten_hip_gemm_f32 with any RTEN_HIP_ACT_* activation applied after the bias in the epilogue.  desc->act must be RTEN_HIP_ACT_NONE. */
+int32_t rten_hip_gemm_f32_act(rten_hip_ctx *ctx, const rten_hip_gemm_desc *desc, const float *a, const float *b,
+                              const float *bias, int32_t act_kind, float act_alpha, float act_beta, float *c);
 /* One-row products (m == 1, per batch element): the reference takes its vector-matrix kernels when A has one row and B is not
  * prepacked (rten-gemm/src/lib.rs:668-747, 876-891; kernels/simd_generic.rs:14-197), and their accumulation order is not the
  * blocked GEMM's (depth blocks of 8 or 512, 16-lane partial sums for transposed B, unfused scalar loops for the columns left over
@@ -251,6 +266,11 @@ int32_t rten_hip_conv2d_f32_prepack(rten_hip_ctx *ctx, const rten_hip_conv2d_des
 int32_t rten_hip_conv2d_f32(rten_hip_ctx *ctx, const rten_hip_conv2d_desc *desc, const float *x, const float *w,
                             int32_t weights_packed, const float *bias, const float *residual, uint32_t flags,
                             float *y);
+/* rten_hip_conv2d_f32 with any RTEN_HIP_ACT_* activation applied after the bias and the residual Add.  flags must not carry
+ * RTEN_HIP_CONV_RELU (pass RTEN_HIP_ACT_RELU instead). */
+int32_t rten_hip_conv2d_f32_act(rten_hip_ctx *ctx, const rten_hip_conv2d_desc *desc, const float *x, const float *w,
+                                int32_t weights_packed, const float *bias, const float *residual, uint32_t flags,
+                                int32_t act_kind, float act_alpha, float act_beta, float *y);
 
 /* Two pointwise convolutions in ONE launch (v8): y1 = act1(conv1x1(x, w1) + bias1 [+ residual]), y2 = act2(conv1x1(y1, w2) + bias2) -- an expand
  * layer of a bottleneck block and the reduce layer of the next block (src/ops/conv.rs:248-284 twice).  y1 is written as always; the second
@@ -412,6 +432,10 @@ int32_t rten_hip_erf_f32(rten_hip_ctx *ctx, int64_t n, const float *x, float *y)
 /* Tanh (rten-vecmath/src/tanh.rs:12-72: odd polynomial below 0.55, (exp(2|x|) - 1) / (exp(2|x|) + 1) above, 1 from 9.02), bit-identical to the reference's
  * AVX-512 / AVX2 form (sign handled as bit operations: tanh(+0) = -0 there). */
 int32_t rten_hip_tanh_f32(rten_hip_ctx *ctx, int64_t n, const float *x, float *y);
+/* y = act(x) for any RTEN_HIP_ACT_* kind (Sigmoid, Silu, Swish, HardSigmoid, HardSwish, Clip, LeakyRelu, Elu, and Relu / Gelu);
+ * bit-identical to the reference's element-wise operators.  y may equal x. */
+int32_t rten_hip_activation_f32(rten_hip_ctx *ctx, int32_t act_kind, float act_alpha, float act_beta, int64_t n, const float *x,
+                                float *y);
 /* y[i] = a[i] + b[i % b_len] (b_len == n: same shape; b_len < n: trailing-dims broadcast) */
 int32_t rten_hip_add_f32(rten_hip_ctx *ctx, int64_t n, const float *a, const float *b, int64_t b_len, float *y);
 int32_t rten_hip_mul_f32(rten_hip_ctx *ctx, int64_t n, const float *a, const float *b, int64_t b_len, float *y);

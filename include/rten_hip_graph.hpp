@@ -985,6 +985,7 @@ class Graph {
         for (size_t i = 0; i < steps_.size(); i++) {
             Step &A = steps_[i];
             if (!A.conv || A.removed || !opt_.pairs.count(A.name) || A.out.empty() || A.out[0] < 0 || A.in.size() < 4) continue;
+            if (A.conv->act.kind != RTEN_HIP_ACT_NONE) continue; // the pair kernel's epilogues know Relu only
             // B: a Conv step reading A's output (constant weights, no residual).  A stage's last block has two such readers -- the next stage's reduce layer and its
             // strided shortcut layer: the one whose attributes fit the kernel (1x1, unit stride, no padding, one group) is taken, whichever comes first in the graph
             auto unit_pointwise = [&](const Step &c) {
@@ -996,7 +997,8 @@ class Graph {
             Step *Bp = nullptr;
             for (size_t k = i + 1; k < steps_.size(); k++) {
                 Step &c = steps_[k];
-                if (c.conv && !c.removed && c.in.size() >= 4 && c.in[0] == A.out[0] && c.in[3] < 0 && c.in[1] >= 0 && consts_.count(c.in[1]) && (c.in[2] < 0 || consts_.count(c.in[2]))) {
+                if (c.conv && !c.removed && c.in.size() >= 4 && c.in[0] == A.out[0] && c.in[3] < 0 && c.in[1] >= 0 && consts_.count(c.in[1]) && (c.in[2] < 0 || consts_.count(c.in[2])) &&
+                    c.conv->act.kind == RTEN_HIP_ACT_NONE) {
                     if (!Bp) Bp = &c;
                     if (unit_pointwise(c)) { Bp = &c; break; }
                 }
@@ -1016,7 +1018,7 @@ class Graph {
                 for (auto &st : steps_) if (!st.removed) for (int id : st.in) if (id == A.in[3]) readers++;
                 for (size_t k = 0; k < i && readers == 1; k++) {
                     Step &c = steps_[k];
-                    if (c.conv && !c.removed && !c.out.empty() && c.out[0] == A.in[3] && c.in.size() >= 4 && c.in[3] < 0 && !c.conv->fuse_relu && c.in[1] >= 0 && consts_.count(c.in[1]) &&
+                    if (c.conv && !c.removed && !c.out.empty() && c.out[0] == A.in[3] && c.in.size() >= 4 && c.in[3] < 0 && !c.conv->fuse_relu && c.conv->act.kind == RTEN_HIP_ACT_NONE && c.in[1] >= 0 && consts_.count(c.in[1]) &&
                         (c.in[2] < 0 || consts_.count(c.in[2])) && (pd = packed_lookup(c.name)) != nullptr) { Dp = &c; break; }
                 }
             }
@@ -1350,6 +1352,7 @@ class Graph {
     // ---- canonicalisation of exporter idioms, on the ONNX node list (the reference does these in its graph optimiser, so its
     //      numerics are the FUSED operators' numerics -- they are applied whether or not the backend's own epilogue fusions are on):
     //   * Constant nodes become initializers (`Constant` -> constant node, rten-onnx loader);
+    //   * x * Sigmoid(x) -> Silu, x * Sigmoid(alpha * x) -> Swish                          (SiluFusion / SwishFusion, fusions.rs:567-615)
     //   * x * (Erf(x / sqrt(2) | x * (1 / sqrt(2))) + 1) * 0.5                              -> Gelu               (GeluFusion, optimize/fusions.rs:407-430)
     //   * (x - ReduceMean(x)) / Sqrt(eps + ReduceMean(Pow(x - ReduceMean(x), 2))) * scale [+ bias], means over the last axis
     //                                                                                      -> LayerNormalization (fusions.rs:674-747)
@@ -1410,6 +1413,40 @@ class Graph {
             }
             return axes.size() == 1 && axes[0] == -1;
         };
+        // ---- Silu / Swish: x * Sigmoid(x) -> Silu, x * Sigmoid(alpha * x) -> Swish(alpha), either operand order (SiluFusion / SwishFusion,
+        //      optimize/fusions.rs:567-615, run before GeluFusion).  Silu divides where the pair multiplies by a reciprocal: the bits change.
+        for (size_t i = 0; i < m.nodes.size(); i++) {
+            onnx::Node &mul = m.nodes[i];
+            if (mul.op_type != "Mul" || mul.inputs.size() != 2) continue;
+            for (int k = 0; k < 2; k++) {
+                onnx::Node *sig = node_of(mul.inputs[(size_t)k], "Sigmoid");
+                if (!sig || sig->inputs.size() != 1) continue;
+                const std::string x = mul.inputs[(size_t)(1 - k)];
+                onnx::Node f;
+                onnx::Node *scale = nullptr;
+                if (sig->inputs[0] == x) {
+                    f.op_type = "Silu";
+                } else {
+                    scale = node_of(sig->inputs[0], "Mul");
+                    float alpha = 0.f;
+                    if (!scale || scale->inputs.size() != 2) continue;
+                    const int j = scale->inputs[0] == x ? 0 : (scale->inputs[1] == x ? 1 : -1);
+                    if (j < 0 || !scalar(scale->inputs[(size_t)(1 - j)], alpha)) continue;
+                    f.op_type = "Swish";
+                    onnx::Attr a;
+                    a.name = "alpha"; a.type = 1; a.f = alpha;
+                    f.attrs = {a};
+                }
+                f.name = mul.name.empty() ? (f.op_type == "Silu" ? "silu" : "swish") : mul.name;
+                f.inputs = {x};
+                f.outputs = mul.outputs;
+                sig->op_type.clear();
+                if (scale) scale->op_type.clear();
+                mul = f;
+                index();
+                break;
+            }
+        }
         const float sqrt2 = std::sqrt(2.0f);
         for (size_t i = 0; i < m.nodes.size(); i++) {
             onnx::Node &last = m.nodes[i];
@@ -1528,6 +1565,46 @@ class Graph {
             return it == producer.end() || it->second < at;
         };
         auto other_input = [&](const onnx::Node &n, const std::string &v) { return n.inputs[0] == v ? n.inputs[1] : n.inputs[0]; };
+        // An activation node as the kernels' RTEN_HIP_ACT_* kind and parameters, with the reference's attribute defaults (onnx_registry.rs:1132,1228,1275,1999);
+        // Clip's min / max come from its opset-6 attributes (promoted to inputs, onnx_registry.rs:887-897) or from constant scalar inputs (an empty name or a
+        // missing input: f32::MIN / f32::MAX).  False: not one of these, or a Clip whose bounds are run-time values.
+        auto activation_of = [&](const onnx::Node &n, Activation &a) -> bool {
+            a = Activation();
+            if (n.op_type == "Sigmoid") a.kind = RTEN_HIP_ACT_SIGMOID;
+            else if (n.op_type == "Silu") a.kind = RTEN_HIP_ACT_SILU;
+            else if (n.op_type == "Swish") { a.kind = RTEN_HIP_ACT_SWISH; a.alpha = n.get_float("alpha", 1.f); }
+            else if (n.op_type == "HardSigmoid") { a.kind = RTEN_HIP_ACT_HARD_SIGMOID; a.alpha = n.get_float("alpha", 0.2f); a.beta = n.get_float("beta", 0.5f); }
+            else if (n.op_type == "HardSwish") a.kind = RTEN_HIP_ACT_HARD_SWISH;
+            else if (n.op_type == "LeakyRelu") { a.kind = RTEN_HIP_ACT_LEAKY_RELU; a.alpha = n.get_float("alpha", 0.01f); }
+            else if (n.op_type == "Elu") { a.kind = RTEN_HIP_ACT_ELU; a.alpha = n.get_float("alpha", 1.f); }
+            else if (n.op_type == "Clip") {
+                a.kind = RTEN_HIP_ACT_CLIP; a.alpha = -FLT_MAX; a.beta = FLT_MAX;
+                for (int k = 1; k <= 2; k++) {
+                    const char *an = k == 1 ? "min" : "max";
+                    const bool has_in = n.inputs.size() > (size_t)k && !n.inputs[(size_t)k].empty();
+                    if (n.attr(an) && has_in) throw GraphError("Clip " + n.name + ": input " + std::to_string(k) + " specified as both attribute and input");
+                    float v;
+                    if (n.attr(an)) v = n.get_float(an, 0.f);
+                    else if (!has_in) continue;
+                    else {
+                        if (!is_const(n.inputs[(size_t)k])) return false;
+                        const Tensor &t = consts_.at(ids_.at(n.inputs[(size_t)k]));
+                        if (t.len() != 1 || t.dtype() != DType::F32) return false;
+                        v = t.to_host<float>()[0];
+                    }
+                    (k == 1 ? a.alpha : a.beta) = v;
+                }
+            } else return false;
+            return true;
+        };
+        // the sole consumer of v if it is an activation activation_of takes (and not a graph output); -1 otherwise
+        auto sole_activation = [&](const std::string &v, Activation &a) -> long {
+            if (graph_outs.count(v)) return -1;
+            auto it = users.find(v);
+            if (it == users.end() || it->second.size() != 1 || dead_ptr->at(it->second[0])) return -1;
+            const onnx::Node &u = m.nodes[it->second[0]];
+            return u.inputs.size() >= 1 && u.inputs[0] == v && activation_of(u, a) ? (long)it->second[0] : -1;
+        };
 
         // ---- attention pre-pass (TransposeFusion + MatMulScale + AddSoftmax of the reference, taken one step further):
         //   q_lin -> Reshape[0,0,h,d] -> Transpose(0,2,1,3) -+
@@ -1755,6 +1832,9 @@ class Graph {
                     }
                     long r = sole_user(out_name, "Relu");
                     if (r >= 0) { op->fuse_relu = true; dead[(size_t)r] = true; out_name = m.nodes[(size_t)r].outputs[0]; fused_away_++; st.pos = (size_t)r; }
+                    Activation act;
+                    const long ac = op->fuse_relu ? -1 : sole_activation(out_name, act);
+                    if (ac >= 0) { op->act = act; dead[(size_t)ac] = true; out_name = m.nodes[(size_t)ac].outputs[0]; fused_away_++; st.pos = (size_t)ac; }
                 }
                 while (st.in.size() < 3) st.in.push_back(-1);
                 st.in.push_back(residual.empty() ? -1 : id_of(residual));
@@ -1763,7 +1843,8 @@ class Graph {
                     const Tensor &w = consts_.at(ids_.at(n.inputs[1]));
                     if (w.ndim() == 4) packed = packed_for(n.name.empty() ? n.outputs.at(0) : n.name, [&] { return op->prepack(ctx_, w); });
                 }
-                st.kind_name = std::string("Conv") + (residual.empty() ? "" : "+Add") + (op->fuse_relu ? "+Relu" : "");
+                st.kind_name = std::string("Conv") + (residual.empty() ? "" : "+Add") + (op->fuse_relu ? "+Relu" : "") +
+                               (op->act.kind != RTEN_HIP_ACT_NONE ? std::string("+") + activation_name(op->act.kind) : "");
                 st.conv = op;
                 // The Add's other operand is used as the kernel's residual only when it has exactly the conv's output shape
                 // (the kernel indexes it with the output's strides).  Its shape is a run-time fact (no shape inference here), and
@@ -1780,9 +1861,10 @@ class Graph {
                             same = res->shape() == std::vector<int64_t>{d.n, d.o, d.out_h, d.out_w};
                         }
                         if (!same) {
-                            Conv plain = *op; plain.fuse_relu = false;
+                            Conv plain = *op; plain.fuse_relu = false; plain.act = Activation();
                             OutputList y = plain.run_packed(c, {in[0], in[1], in.size() > 2 ? in[2] : nullptr}, packed);
                             OutputList sum = Add().run(c, {&y[0], res});
+                            if (op->act.kind != RTEN_HIP_ACT_NONE) return ActivationOp(op->act.kind, op->act.alpha, op->act.beta).run(c, {&sum[0]});
                             return op->fuse_relu ? Relu().run(c, {&sum[0]}) : std::move(sum);
                         }
                     }
@@ -1963,10 +2045,17 @@ class Graph {
                             if (r >= 0) { op->act = RTEN_HIP_ACT_RELU; dead[(size_t)r] = true; fused_away_++; out_name = m.nodes[(size_t)r].outputs[0]; st.pos = (size_t)r; }
                         }
                     }
+                    Activation act;
+                    const long ac = op->act == RTEN_HIP_ACT_NONE ? sole_activation(out_name, act) : -1;
+                    if (ac >= 0) {
+                        op->act = act.kind; op->act_alpha = act.alpha; op->act_beta = act.beta;
+                        dead[(size_t)ac] = true; fused_away_++; out_name = m.nodes[(size_t)ac].outputs[0]; st.pos = (size_t)ac;
+                    }
                 }
                 st.in.resize(2);
                 st.in.push_back(bias.empty() ? -1 : id_of(bias));
-                st.kind_name = std::string(op->alpha != 1.f || !bias.empty() ? "FusedMatMul" : "MatMul") + (op->act == RTEN_HIP_ACT_GELU ? "+Gelu" : op->act == RTEN_HIP_ACT_RELU ? "+Relu" : "");
+                st.kind_name = std::string(op->alpha != 1.f || !bias.empty() || op->act > RTEN_HIP_ACT_GELU ? "FusedMatMul" : "MatMul") +
+                               (op->act != RTEN_HIP_ACT_NONE ? std::string("+") + activation_name(op->act) : "");
                 auto plan = std::make_shared<GemmPlan>();
                 st.gemm_plan = plan;
                 st.run = [op, plan](Context &c, const InputList &in) {
@@ -2018,6 +2107,17 @@ class Graph {
                 st.batch_coupled = op->axis == 0;
                 const std::string nm = st.name;
                 st.run = [this, op, nm](Context &c, const InputList &in) { note_axis("LayerNormalization", nm, op->axis, require(in, 0)); return op->run(c, in); };
+            } else if (n.op_type == "Sigmoid" || n.op_type == "Silu" || n.op_type == "Swish" || n.op_type == "HardSigmoid" || n.op_type == "HardSwish" ||
+                       n.op_type == "LeakyRelu" || n.op_type == "Elu" || n.op_type == "Clip") {
+                Activation act;
+                if (activation_of(n, act)) { // parameters fixed at load time: one rten_hip_activation_f32 launch, nothing read back per run
+                    auto op = std::make_shared<ActivationOp>(act.kind, act.alpha, act.beta);
+                    st.in.resize(1);
+                    st.run = [op](Context &c, const InputList &in) { return op->run(c, in); };
+                } else { // Clip with run-time bounds
+                    auto op = std::make_shared<Clip>();
+                    st.run = [op](Context &c, const InputList &in) { return op->run(c, in); };
+                }
             } else if (n.op_type == "Gelu" && n.attr("approximate") && n.attr("approximate")->s != "none") {
                 throw GraphError("Gelu " + st.name + ": approximate=\"" + n.attr("approximate")->s + "\" is not supported");
             } else if (n.op_type == "MaxPool" || n.op_type == "AveragePool") {

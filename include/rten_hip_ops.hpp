@@ -16,6 +16,7 @@
 // is no CPU fallback: without a gfx950 device `Context` throws.  Header only; C++17.
 #pragma once
 #include <algorithm>
+#include <cfloat>
 #include <cstdint>
 #include <cstring>
 #include <functional>
@@ -307,6 +308,18 @@ class PlanScope { // applies a plan around one call and restores the automatic p
     int32_t saved_[8] = {};
 };
 
+// ------------------------------------------------------------------------------------------------ activations with parameters
+// An element-wise activation (RTEN_HIP_ACT_* kind and its parameters): the standalone operators below, and the epilogue that
+// Conv / FusedMatMul apply after their bias (and residual).
+struct Activation {
+    int32_t kind = RTEN_HIP_ACT_NONE;
+    float alpha = 0.f, beta = 0.f;
+};
+inline const char *activation_name(int32_t kind) {
+    static const char *n[] = {"", "Relu", "Gelu", "Sigmoid", "Silu", "Swish", "HardSigmoid", "HardSwish", "Clip", "LeakyRelu", "Elu"};
+    return kind >= 0 && kind <= RTEN_HIP_ACT_ELU ? n[kind] : "?";
+}
+
 // ------------------------------------------------------------------------------------------------ Conv
 struct Conv : Operator {
     GemmPlan plan;
@@ -315,6 +328,7 @@ struct Conv : Operator {
     Padding padding;
     std::vector<int> strides{1, 1};
     bool fuse_relu = false; // backend fusion of the following Relu; a 4th input is the residual Add operand
+    Activation act;         // backend fusion of another following activation (Sigmoid, Silu, Clip, ...); exclusive with fuse_relu
 
     const char *name() const override { return "Conv"; }
     int max_inputs() const override { return 4; }
@@ -376,10 +390,16 @@ struct Conv : Operator {
         const rten_hip_conv2d_desc d = geometry(x.shape(), w.shape());
         if (bias && bias->size(0) != d.o) throw OpError(OpError::IncompatibleInputShapes, "bias.size(0) != out_channels");
         Tensor y(ctx, {d.n, d.o, d.out_h, d.out_w}, DType::F32);
+        if (fuse_relu && act.kind != RTEN_HIP_ACT_NONE) throw OpError(OpError::InvalidValue, "Conv: fuse_relu and act are exclusive");
         const uint32_t flags = (fuse_relu ? RTEN_HIP_CONV_RELU : 0u) | (residual ? RTEN_HIP_CONV_RESIDUAL : 0u);
         PlanScope scope(ctx, plan);
-        ctx.check(rten_hip_conv2d_f32(ctx.raw(), &d, (const float *)x.ptr(), (const float *)(packed_weight ? packed_weight->ptr() : w.ptr()),
-                                      packed_weight ? 1 : 0, (const float *)vp(bias), (const float *)vp(residual), flags, (float *)y.ptr()));
+        const float *wp = (const float *)(packed_weight ? packed_weight->ptr() : w.ptr());
+        if (act.kind != RTEN_HIP_ACT_NONE)
+            ctx.check(rten_hip_conv2d_f32_act(ctx.raw(), &d, (const float *)x.ptr(), wp, packed_weight ? 1 : 0, (const float *)vp(bias), (const float *)vp(residual), flags,
+                                              act.kind, act.alpha, act.beta, (float *)y.ptr()));
+        else
+            ctx.check(rten_hip_conv2d_f32(ctx.raw(), &d, (const float *)x.ptr(), wp, packed_weight ? 1 : 0, (const float *)vp(bias), (const float *)vp(residual), flags,
+                                          (float *)y.ptr()));
         OutputList out;
         out.push_back(std::move(y));
         return out;
@@ -550,7 +570,9 @@ inline int64_t prod(const std::vector<int64_t> &v, size_t b, size_t e) {
     return p;
 }
 // numpy.matmul shape rules (src/ops/matmul.rs:208-385); contiguous inputs; b_transposed folds transB into strides
-inline Tensor matmul(Context &ctx, const Tensor &a, const Tensor &b, const Tensor *bias, float alpha, int act, bool b_transposed) {
+// act: RTEN_HIP_ACT_NONE / RELU / GELU in the descriptor; any other kind (with act_alpha / act_beta) through rten_hip_gemm_f32_act
+inline Tensor matmul(Context &ctx, const Tensor &a, const Tensor &b, const Tensor *bias, float alpha, int act, bool b_transposed, float act_alpha = 0.f,
+                     float act_beta = 0.f) {
     std::vector<int64_t> as = a.shape(), bs = b.shape();
     if (as.empty() || bs.empty()) throw OpError(OpError::InvalidValue, "Inputs must have >= 1 dimensions");
     const bool a_vec = as.size() == 1, b_vec = bs.size() == 1;
@@ -576,7 +598,8 @@ inline Tensor matmul(Context &ctx, const Tensor &a, const Tensor &b, const Tenso
     if (y.len() > 0) {
         rten_hip_gemm_desc d{};
         d.k = (int)k; d.n = (int)n; d.a_rs = k; d.a_cs = 1; d.b_rs = b_transposed ? 1 : n; d.b_cs = b_transposed ? k : 1; d.ldc = n;
-        d.alpha = alpha; d.beta = 0.f; d.bias_kind = bias ? RTEN_HIP_BIAS_PER_COL : RTEN_HIP_BIAS_NONE; d.act = act;
+        const bool ext = act > RTEN_HIP_ACT_GELU;
+        d.alpha = alpha; d.beta = 0.f; d.bias_kind = bias ? RTEN_HIP_BIAS_PER_COL : RTEN_HIP_BIAS_NONE; d.act = ext ? RTEN_HIP_ACT_NONE : act;
         if (na > 1 && nb == 1) { // matmul.rs:266-297: one [A*M, K] x [K, N] product
             d.m = (int)(na * m); d.batch = 1;
         } else {
@@ -584,7 +607,11 @@ inline Tensor matmul(Context &ctx, const Tensor &a, const Tensor &b, const Tenso
             if ((na != 1 && na != batch) || (nb != 1 && nb != batch)) throw OpError(OpError::UnsupportedValue, "partial batch broadcasting is not supported by the device path");
             d.m = (int)m; d.batch = (int)batch; d.a_bs = na > 1 ? m * k : 0; d.b_bs = nb > 1 ? k * n : 0; d.c_bs = m * n;
         }
-        ctx.check(rten_hip_gemm_f32(ctx.raw(), &d, (const float *)a.ptr(), (const float *)b.ptr(), (const float *)vp(bias), (float *)y.ptr()));
+        if (ext)
+            ctx.check(rten_hip_gemm_f32_act(ctx.raw(), &d, (const float *)a.ptr(), (const float *)b.ptr(), (const float *)vp(bias), act, act_alpha, act_beta,
+                                            (float *)y.ptr()));
+        else
+            ctx.check(rten_hip_gemm_f32(ctx.raw(), &d, (const float *)a.ptr(), (const float *)b.ptr(), (const float *)vp(bias), (float *)y.ptr()));
     }
     if (a_vec) oshape.erase(oshape.end() - 2);
     if (b_vec) oshape.pop_back();
@@ -603,9 +630,10 @@ struct MatMul : Operator { // src/ops/matmul.rs:387-428
     }
 };
 
-struct FusedMatMul : Operator { // src/ops/matmul.rs:455-510: MatMul + per-column bias + alpha (act: backend fusion of the following Gelu / Relu)
+struct FusedMatMul : Operator { // src/ops/matmul.rs:455-510: MatMul + per-column bias + alpha (act: backend fusion of the following activation)
     float alpha = 1.f;
-    int act = RTEN_HIP_ACT_NONE;
+    int act = RTEN_HIP_ACT_NONE; // any RTEN_HIP_ACT_* kind
+    float act_alpha = 0.f, act_beta = 0.f;
     bool transpose_b = false;
     const char *name() const override { return "FusedMatMul"; }
     int max_inputs() const override { return 3; }
@@ -613,7 +641,7 @@ struct FusedMatMul : Operator { // src/ops/matmul.rs:455-510: MatMul + per-colum
         const Tensor *bias = get(in, 2);
         if (bias && bias->ndim() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 1 dims");
         OutputList out;
-        out.push_back(detail::matmul(ctx, want(require(in, 0), DType::F32, "float32"), want(require(in, 1), DType::F32, "float32"), bias, alpha, act, transpose_b));
+        out.push_back(detail::matmul(ctx, want(require(in, 0), DType::F32, "float32"), want(require(in, 1), DType::F32, "float32"), bias, alpha, act, transpose_b, act_alpha, act_beta));
         return out;
     }
 };
@@ -885,6 +913,57 @@ struct UnaryOp : Operator {
 struct Relu : UnaryOp<rten_hip_relu_f32> { Relu() : UnaryOp("Relu") {} };
 struct Gelu : UnaryOp<rten_hip_gelu_f32> { Gelu() : UnaryOp("Gelu") {} };
 struct Erf : UnaryOp<rten_hip_erf_f32> { Erf() : UnaryOp("Erf") {} };
+
+// Sigmoid, Silu, Swish, HardSigmoid, HardSwish, LeakyRelu, Elu (rten-vecmath/src/exp.rs:201-275, relu.rs:13-25, src/ops/unary_elementwise.rs:437-471):
+// one parameterised kernel, rten_hip_activation_f32
+inline Tensor run_activation(Context &ctx, const Tensor &x, const Activation &a) {
+    if (x.dtype() != DType::F32) throw OpError(OpError::UnsupportedType, "expected float32 tensor");
+    Tensor y(ctx, x.shape(), DType::F32);
+    if (x.len()) ctx.check(rten_hip_activation_f32(ctx.raw(), a.kind, a.alpha, a.beta, x.len(), (const float *)x.ptr(), (float *)y.ptr()));
+    return y;
+}
+struct ActivationOp : Operator {
+    Activation act;
+    ActivationOp(int32_t kind, float alpha = 0.f, float beta = 0.f) { act.kind = kind; act.alpha = alpha; act.beta = beta; }
+    const char *name() const override { return activation_name(act.kind); }
+    int max_inputs() const override { return 1; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        OutputList out;
+        out.push_back(run_activation(ctx, require(in, 0), act));
+        return out;
+    }
+};
+struct Sigmoid : ActivationOp { Sigmoid() : ActivationOp(RTEN_HIP_ACT_SIGMOID) {} };
+struct Silu : ActivationOp { Silu() : ActivationOp(RTEN_HIP_ACT_SILU) {} };
+struct Swish : ActivationOp { explicit Swish(float alpha = 1.f) : ActivationOp(RTEN_HIP_ACT_SWISH, alpha) {} };
+struct HardSigmoid : ActivationOp { explicit HardSigmoid(float alpha = 0.2f, float beta = 0.5f) : ActivationOp(RTEN_HIP_ACT_HARD_SIGMOID, alpha, beta) {} };
+struct HardSwish : ActivationOp { HardSwish() : ActivationOp(RTEN_HIP_ACT_HARD_SWISH) {} };
+struct LeakyRelu : ActivationOp { explicit LeakyRelu(float alpha = 0.01f) : ActivationOp(RTEN_HIP_ACT_LEAKY_RELU, alpha) {} };
+struct Elu : ActivationOp { explicit Elu(float alpha = 1.f) : ActivationOp(RTEN_HIP_ACT_ELU, alpha) {} };
+
+// Clip(x, min?, max?) through the reference's Clamp trait (unary_elementwise.rs:248-303): a missing bound is f32::MIN / f32::MAX.
+// f32 only; the bounds are scalars (read back to the host).
+struct Clip : Operator {
+    const char *name() const override { return "Clip"; }
+    int max_inputs() const override { return 3; }
+    static float bound(const Tensor *t, float dflt) {
+        if (!t) return dflt;
+        if (t->len() != 1) throw OpError(OpError::InvalidValue, "Clip: min / max must be scalars");
+        if (t->dtype() != DType::F32) throw OpError(OpError::UnsupportedType, "Clip: expected float32 bounds");
+        return t->to_host<float>()[0];
+    }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0);
+        if (x.dtype() != DType::F32) throw OpError(OpError::UnsupportedType, "Clip: only float32 tensors are supported");
+        Activation a;
+        a.kind = RTEN_HIP_ACT_CLIP;
+        a.alpha = bound(get(in, 1), -FLT_MAX);
+        a.beta = bound(get(in, 2), FLT_MAX);
+        OutputList out;
+        out.push_back(run_activation(ctx, x, a));
+        return out;
+    }
+};
 
 template <int32_t (*FN)(rten_hip_ctx *, int64_t, const float *, const float *, int64_t, float *), int OPCODE>
 struct BinaryOp : Operator { // binary_elementwise.rs:58-170,476-495: numpy broadcasting
@@ -2025,6 +2104,14 @@ class OpRegistry {
         r.register_op<Relu>("Relu");
         r.register_op<Gelu>("Gelu");
         r.register_op<Erf>("Erf");
+        r.register_op<Sigmoid>("Sigmoid");
+        r.register_op<Silu>("Silu");
+        r.register_op<Swish>("Swish");
+        r.register_op<HardSigmoid>("HardSigmoid");
+        r.register_op<HardSwish>("HardSwish");
+        r.register_op<Clip>("Clip");
+        r.register_op<LeakyRelu>("LeakyRelu");
+        r.register_op<Elu>("Elu");
         r.register_op<Add>("Add");
         r.register_op<Mul>("Mul");
         r.register_op<Sub>("Sub");

@@ -12,7 +12,7 @@ namespace {
 template <int KH, int KW> // > 0: compile-time window with all taps' loads issued first; 0: runtime window
 __global__ __launch_bounds__(256) void depthwise_conv2d_f32_kernel(const rten_hip_conv2d_desc d, const float *__restrict__ x, const float *__restrict__ w,
                                                                    int w_stride, const float *__restrict__ bias, const float *__restrict__ residual,
-                                                                   int relu, float *__restrict__ y) {
+                                                                   int act, float act_a, float act_b, float *__restrict__ y) {
     const int plane = d.out_h * d.out_w;
     const int o = blockIdx.y * 256 + threadIdx.x;
     if (o >= plane) return;
@@ -52,7 +52,8 @@ __global__ __launch_bounds__(256) void depthwise_conv2d_f32_kernel(const rten_hi
     }
     const long long oi = (long long)nc * plane + o;
     if (residual) acc = acc + residual[oi]; // the Add node that follows (binary_elementwise.rs:476-495)
-    if (relu) acc = vm::relu(acc);
+    if (act == RTEN_HIP_ACT_RELU) acc = vm::relu(acc);
+    else if (act != RTEN_HIP_ACT_NONE) acc = vm::activation(act, acc, act_a, act_b);
     y[oi] = acc;
 }
 
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(256) void depthwise_conv2d_f32_kernel(const rten_hi
 // the workgroups.
 template <int SH>
 __global__ __launch_bounds__(256) void depthwise3x3_y4_kernel(const rten_hip_conv2d_desc d, const float *__restrict__ x, const float *__restrict__ w, int w_stride,
-                                                             const float *__restrict__ bias, const float *__restrict__ residual, int relu, float *__restrict__ y) {
+                                                             const float *__restrict__ bias, const float *__restrict__ residual, int act, float act_a, float act_b, float *__restrict__ y) {
     constexpr int NROW = 3 * SH + 3;
     const int hq = (d.out_h + 3) >> 2, items = hq * d.out_w;
     const int q = blockIdx.y * 256 + threadIdx.x;
@@ -98,7 +99,8 @@ __global__ __launch_bounds__(256) void depthwise3x3_y4_kernel(const rten_hip_con
                 if (rok[j * SH + ky] && cok[kx]) acc = __fadd_rn(acc, __fmul_rn(xv[j * SH + ky][kx], wv[ky * 3 + kx]));
         const long long oi = o0 + (long long)(oy0 + j) * d.out_w;
         if (residual) acc = acc + residual[oi];
-        if (relu) acc = vm::relu(acc);
+        if (act == RTEN_HIP_ACT_RELU) acc = vm::relu(acc);
+        else if (act != RTEN_HIP_ACT_NONE) acc = vm::activation(act, acc, act_a, act_b);
         y[oi] = acc;
     }
 }
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(256) void depthwise3x3_y4_kernel(const rten_hip_con
 // 16 bytes).  Each output replays the reference's sequence (accumulator = bias; per in-bounds tap in (k_y, k_x) order one rounded multiply and one add;
 // padding taps not visited: conv/depthwise.rs:95-146): same bits.
 __global__ __launch_bounds__(256) void depthwise3x3s1_stream_kernel(const rten_hip_conv2d_desc d, const float *__restrict__ x, const float *__restrict__ w, int w_stride,
-                                                                   const float *__restrict__ bias, const float *__restrict__ residual, int relu, float *__restrict__ y,
+                                                                   const float *__restrict__ bias, const float *__restrict__ residual, int act, float act_a, float act_b, float *__restrict__ y,
                                                                    long long total) {
     const int kq = d.w >> 2, rgs = (d.out_h + 3) >> 2;
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -174,9 +176,11 @@ __global__ __launch_bounds__(256) void depthwise3x3s1_stream_kernel(const rten_h
             const float4 rr = *reinterpret_cast<const float4 *>(residual + oi);
             acc[0] = acc[0] + rr.x; acc[1] = acc[1] + rr.y; acc[2] = acc[2] + rr.z; acc[3] = acc[3] + rr.w;
         }
-        if (relu) {
+        if (act == RTEN_HIP_ACT_RELU) {
 #pragma unroll
             for (int i = 0; i < 4; i++) acc[i] = vm::relu(acc[i]);
+        } else if (act != RTEN_HIP_ACT_NONE) {
+            vm::activation_n<4>(act, acc, act_a, act_b);
         }
         *reinterpret_cast<float4 *>(y + oi) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     }
@@ -187,12 +191,13 @@ __global__ __launch_bounds__(256) void depthwise3x3s1_stream_kernel(const rten_h
 // Called by rten_hip_conv2d_f32 for groups == C == O geometries (weights OIHW [C,1,kh,kw], or the prepacked form whose
 // per-group K x 4 block holds the taps at stride 4).
 int32_t rten_depthwise_conv2d_f32(rten_hip_ctx *ctx, const rten_hip_conv2d_desc *d, const float *x, const float *w, int32_t weights_packed, const float *bias,
-                                  const float *residual, uint32_t flags, float *y) {
+                                  const float *residual, uint32_t flags, const RtenAct &act, float *y) {
     const long long planes = (long long)d->n * d->c, plane = (long long)d->out_h * d->out_w;
     if (planes > 0x7fffffffLL || plane > 65535LL * 256 || (long long)d->h * d->w > 0x7fffffffLL)
         return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "depthwise conv: plane too large");
     const dim3 grid((unsigned)planes, (unsigned)((plane + 255) / 256));
-    const int ws = weights_packed ? 4 : 1, relu = (flags & RTEN_HIP_CONV_RELU) ? 1 : 0;
+    const int ws = weights_packed ? 4 : 1, ak = act.kind;
+    const float aa = act.alpha, ab = act.beta;
     const float *res = (flags & RTEN_HIP_CONV_RESIDUAL) ? residual : nullptr;
     ProfScope ps(ctx, "depthwise_conv2d_f32", 2.0 * planes * plane * d->kh * d->kw, 4.0 * (planes * (double)d->h * d->w + planes * (double)plane));
     // the streaming form: 3 x 3, stride 1, dilation 1, one padding column on either side, rows of whole 16-byte groups (RTEN_HIP_DEBUG bit 0x100000: the round-4 kernel, A/B)
@@ -201,7 +206,7 @@ int32_t rten_depthwise_conv2d_f32(rten_hip_ctx *ctx, const rten_hip_conv2d_desc 
                         !(ctx->debug & 0x100000);
     if (stream) {
         const long long threads = planes * (long long)(d->w / 4) * ((d->out_h + 3) / 4);
-        hipLaunchKernelGGL(depthwise3x3s1_stream_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, *d, x, w, ws, bias, res, relu, y, threads);
+        hipLaunchKernelGGL(depthwise3x3s1_stream_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, *d, x, w, ws, bias, res, ak, aa, ab, y, threads);
         RTEN_LAUNCH_CHECK(ctx, "depthwise3x3s1_stream_kernel launch");
         return RTEN_HIP_OK;
     }
@@ -209,11 +214,11 @@ int32_t rten_depthwise_conv2d_f32(rten_hip_ctx *ctx, const rten_hip_conv2d_desc 
     if (y4) {
         const long long items = (long long)((d->out_h + 3) / 4) * d->out_w;
         const dim3 grid4((unsigned)planes, (unsigned)((items + 255) / 256));
-        if (d->stride_h == 1) hipLaunchKernelGGL((depthwise3x3_y4_kernel<1>), grid4, dim3(256), 0, ctx->stream, *d, x, w, ws, bias, res, relu, y);
-        else hipLaunchKernelGGL((depthwise3x3_y4_kernel<2>), grid4, dim3(256), 0, ctx->stream, *d, x, w, ws, bias, res, relu, y);
-    } else if (d->kh == 3 && d->kw == 3) hipLaunchKernelGGL((depthwise_conv2d_f32_kernel<3, 3>), grid, dim3(256), 0, ctx->stream, *d, x, w, ws, bias, res, relu, y);
-    else if (d->kh == 5 && d->kw == 5) hipLaunchKernelGGL((depthwise_conv2d_f32_kernel<5, 5>), grid, dim3(256), 0, ctx->stream, *d, x, w, ws, bias, res, relu, y);
-    else hipLaunchKernelGGL((depthwise_conv2d_f32_kernel<0, 0>), grid, dim3(256), 0, ctx->stream, *d, x, w, ws, bias, res, relu, y);
+        if (d->stride_h == 1) hipLaunchKernelGGL((depthwise3x3_y4_kernel<1>), grid4, dim3(256), 0, ctx->stream, *d, x, w, ws, bias, res, ak, aa, ab, y);
+        else hipLaunchKernelGGL((depthwise3x3_y4_kernel<2>), grid4, dim3(256), 0, ctx->stream, *d, x, w, ws, bias, res, ak, aa, ab, y);
+    } else if (d->kh == 3 && d->kw == 3) hipLaunchKernelGGL((depthwise_conv2d_f32_kernel<3, 3>), grid, dim3(256), 0, ctx->stream, *d, x, w, ws, bias, res, ak, aa, ab, y);
+    else if (d->kh == 5 && d->kw == 5) hipLaunchKernelGGL((depthwise_conv2d_f32_kernel<5, 5>), grid, dim3(256), 0, ctx->stream, *d, x, w, ws, bias, res, ak, aa, ab, y);
+    else hipLaunchKernelGGL((depthwise_conv2d_f32_kernel<0, 0>), grid, dim3(256), 0, ctx->stream, *d, x, w, ws, bias, res, ak, aa, ab, y);
     RTEN_LAUNCH_CHECK(ctx, "depthwise_conv2d_f32_kernel launch");
     return RTEN_HIP_OK;
 }

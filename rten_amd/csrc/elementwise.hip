@@ -53,6 +53,27 @@ __global__ __launch_bounds__(EW_THREADS) void unary_kernel(int64_t n, const floa
     }
 }
 
+// Parameterised activation (RTEN_HIP_ACT_*, vm::activation): one instantiation per kind, the parameters ride in SGPRs.
+// No __restrict__: y may equal x (each element is read before it is written, by the same lane).
+template <int KIND>
+__global__ __launch_bounds__(EW_THREADS) void activation_kernel(int64_t n, const float *x, float *y, float a, float b, int vec) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (vec) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = tid; i < n4; i += stride) {
+            f32x4 v = reinterpret_cast<const f32x4 *>(x)[i];
+            f32x4 r;
+#pragma unroll
+            for (int k = 0; k < 4; k++) r[k] = vm::activation(KIND, v[k], a, b);
+            reinterpret_cast<f32x4 *>(y)[i] = r;
+        }
+        for (int64_t i = (n4 << 2) + tid; i < n; i += stride) y[i] = vm::activation(KIND, x[i], a, b);
+    } else {
+        for (int64_t i = tid; i < n; i += stride) y[i] = vm::activation(KIND, x[i], a, b);
+    }
+}
+
 enum BinaryOp { B_ADD, B_MUL, B_SUB, B_DIV };
 
 template <int OP>
@@ -223,6 +244,27 @@ RTEN_EXPORT int32_t rten_hip_erf_f32(rten_hip_ctx *ctx, int64_t n, const float *
 }
 RTEN_EXPORT int32_t rten_hip_tanh_f32(rten_hip_ctx *ctx, int64_t n, const float *x, float *y) {
     return run_unary<U_TANH>(ctx, n, x, y, "tanh_f32");
+}
+RTEN_EXPORT int32_t rten_hip_activation_f32(rten_hip_ctx *ctx, int32_t act_kind, float act_alpha, float act_beta, int64_t n, const float *x,
+                                            float *y) {
+    RTEN_CHECK_CTX(ctx);
+    if (!rten_act_valid(act_kind)) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "activation: unknown kind");
+    if (n < 0) return RTEN_HIP_ERR_INVALID_VALUE;
+    if (n == 0) return RTEN_HIP_OK;
+    if (!x || !y) return RTEN_HIP_ERR_INVALID_VALUE;
+    const int vec = al16(x) && al16(y);
+    const dim3 grid(ew_blocks(vec ? n / 4 : n));
+    const float a = act_alpha, b = act_beta;
+    ProfScope ps(ctx, "activation_f32", 0.0, 8.0 * n);
+    switch (act_kind) {
+#define RTEN_ACT_CASE(K) case K: hipLaunchKernelGGL((activation_kernel<K>), grid, dim3(EW_THREADS), 0, ctx->stream, n, x, y, a, b, vec); break;
+    RTEN_ACT_CASE(RTEN_HIP_ACT_NONE) RTEN_ACT_CASE(RTEN_HIP_ACT_RELU) RTEN_ACT_CASE(RTEN_HIP_ACT_GELU) RTEN_ACT_CASE(RTEN_HIP_ACT_SIGMOID)
+    RTEN_ACT_CASE(RTEN_HIP_ACT_SILU) RTEN_ACT_CASE(RTEN_HIP_ACT_SWISH) RTEN_ACT_CASE(RTEN_HIP_ACT_HARD_SIGMOID) RTEN_ACT_CASE(RTEN_HIP_ACT_HARD_SWISH)
+    RTEN_ACT_CASE(RTEN_HIP_ACT_CLIP) RTEN_ACT_CASE(RTEN_HIP_ACT_LEAKY_RELU) RTEN_ACT_CASE(RTEN_HIP_ACT_ELU)
+#undef RTEN_ACT_CASE
+    }
+    RTEN_LAUNCH_CHECK(ctx, "activation_f32");
+    return RTEN_HIP_OK;
 }
 RTEN_EXPORT int32_t rten_hip_add_f32(rten_hip_ctx *ctx, int64_t n, const float *a, const float *b, int64_t b_len,
                                      float *y) {

@@ -979,6 +979,8 @@ __device__ __forceinline__ void store_out16(const GemmArgs &p, f32x4v (&val)[TM2
             } else if (p.act == RTEN_HIP_ACT_GELU) {
 #pragma unroll
                 for (int r = 0; r < 4; r++) v[r] = vm::gelu(v[r]);
+            } else if (p.act != RTEN_HIP_ACT_NONE) {
+                vm::activation_n<4>(p.act, v, p.act_a, p.act_b);
             }
 #pragma unroll
             for (int r = 0; r < 4; r++) {
@@ -2061,7 +2063,7 @@ __global__ __launch_bounds__(2 * NTHREADS, 2) void igemm_f32_ws_kernel(const Gem
         const int mb = m0 + wm0 + 4 * half, nb0 = n0 + wn0 + l31;
         if constexpr (MULTI_KC) { // launched only for K > 256: at least two depth blocks
             fold_next<TM, TN>(p, acc, tot);
-            store_out<TM, TN>(p, tot, mb, nb0, c_zoff);
+            store_out<TM, TN, false>(p, tot, mb, nb0, c_zoff); // (acc and tot live: no room for the activations past Gelu, see launch_cfg)
         } else {
             fold_first<TM, TN>(p, z, acc, acc, mb, nb0, c_zoff);
             store_out<TM, TN>(p, acc, mb, nb0, c_zoff);
@@ -2307,6 +2309,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void igemm_f32_thin_kernel(const GemmA
     } else if (p.act == RTEN_HIP_ACT_GELU) {
 #pragma unroll
         for (int r = 0; r < 4; r++) v[r] = vm::gelu(v[r]);
+    } else if (p.act != RTEN_HIP_ACT_NONE) {
+        vm::activation_n<4>(p.act, v, p.act_a, p.act_b);
     }
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -2594,6 +2598,7 @@ int32_t launch_cfg(rten_hip_ctx *ctx, GemmArgs &a, int Z) {
         }
         TRACE_ASSIGN(a, gx * (unsigned)Z);
         if constexpr (kDma) {
+            if (pipe == 2 && mode == 1 && a.act > RTEN_HIP_ACT_GELU) pipe = 1; // the multi-block warp-specialised kernel's epilogue stops at Gelu: the three-stage kernel
             if (pipe == 2) {
                 snprintf(kname, sizeof kname, "igemm_f32_ws_kernel<%d,%d,%d,%s>", BM, BN, BL, mode == 1 ? "true" : "false");
                 ProfScope ps(ctx, kname, fl, by);
@@ -2874,13 +2879,23 @@ RTEN_EXPORT int32_t rten_hip_set_gemm_order(rten_hip_ctx *ctx, int32_t order) {
 }
 
 namespace {
-int32_t gemm_f32_entry(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b, const float *bias, float *c, bool allow_gemv);
+int32_t gemm_f32_entry(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b, const float *bias, float *c, bool allow_gemv,
+                       const RtenAct *act = nullptr);
 }
 
 RTEN_EXPORT int32_t rten_hip_gemm_f32(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b,
                                       const float *bias, float *c) {
     RTEN_CHECK_CTX(ctx);
     return gemm_f32_entry(ctx, d, a, b, bias, c, ctx->gemv_order != 0);
+}
+
+RTEN_EXPORT int32_t rten_hip_gemm_f32_act(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b,
+                                          const float *bias, int32_t act_kind, float act_alpha, float act_beta, float *c) {
+    RTEN_CHECK_CTX(ctx);
+    if (d && d->act != RTEN_HIP_ACT_NONE) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "gemm_act: desc.act must be NONE");
+    if (!rten_act_valid(act_kind)) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "gemm_act: unknown activation kind");
+    const RtenAct act = {act_kind, act_alpha, act_beta};
+    return gemm_f32_entry(ctx, d, a, b, bias, c, ctx->gemv_order != 0, &act);
 }
 
 int32_t rten_gemm_f32_blocked(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b, const float *bias, float *c) {
@@ -2927,7 +2942,8 @@ int32_t launch_smallm(rten_hip_ctx *ctx, GemmArgs &a, const rten_hip_gemm_desc *
     return RTEN_HIP_OK;
 }
 
-int32_t gemm_f32_entry(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b, const float *bias, float *c, bool allow_gemv) {
+int32_t gemm_f32_entry(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b, const float *bias, float *c, bool allow_gemv,
+                       const RtenAct *act) {
     if (!d) return RTEN_HIP_ERR_INVALID_VALUE;
     if (d->m < 0 || d->n < 0 || d->k < 0 || d->batch < 0)
         return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "gemm: negative dimension");
@@ -2939,7 +2955,7 @@ int32_t gemm_f32_entry(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const flo
     if (d->a_rs < 0 || d->a_cs < 0 || d->b_rs < 0 || d->b_cs < 0)
         return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "gemm: negative strides are not supported");
     // one row, B not prepacked: the reference takes its gemv kernels, whose accumulation order is not the blocked one (lib.rs:876-891)
-    if (allow_gemv && d->m == 1 && d->k > 0) return rten_gemv_f32(ctx, d, a, b, bias, c);
+    if (allow_gemv && d->m == 1 && d->k > 0) return rten_gemv_f32(ctx, d, a, b, bias, act, c);
 
     GemmArgs g = {};
     g.A = a ? a : c; g.B = b ? b : c; g.C = c; g.bias = bias; g.res = nullptr;
@@ -2952,6 +2968,7 @@ int32_t gemm_f32_entry(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const flo
     g.Pn = d->n;
     g.alpha = d->alpha; g.beta = d->beta;
     g.bias_kind = d->bias_kind; g.act = d->act;
+    if (act) { g.act = act->kind; g.act_a = act->alpha; g.act_b = act->beta; }
     g.a_dir_m = (d->a_rs == 1 && d->a_cs != 1) ? 1 : 0;
     g.b_dir_n = (d->b_cs == 1 || d->b_rs != 1) ? 1 : 0;
     const long long ab = extent_bytes(d->m, d->a_rs, d->k, d->a_cs), bb = extent_bytes(d->k, d->b_rs, d->n, d->b_cs);
@@ -3035,9 +3052,9 @@ const i32x2 *get_im2col_lut(rten_hip_ctx *ctx, int Cg, int kh, int kw, int dy, i
 bool rten_small_c_conv_f32_supported(const rten_hip_conv2d_desc *d, int weights_packed, const float *residual);
 int32_t rten_small_c_conv_f32(rten_hip_ctx *ctx, const rten_hip_conv2d_desc *d, const float *x, const float *w_packed, const float *bias, uint32_t flags, float *y);
 
-// depthwise.hip
+// depthwise.hip (flags: RTEN_HIP_CONV_RESIDUAL only; the activation is `act`)
 int32_t rten_depthwise_conv2d_f32(rten_hip_ctx *ctx, const rten_hip_conv2d_desc *d, const float *x, const float *w, int32_t weights_packed, const float *bias,
-                                  const float *residual, uint32_t flags, float *y);
+                                  const float *residual, uint32_t flags, const RtenAct &act, float *y);
 
 RTEN_EXPORT size_t rten_hip_conv2d_f32_packed_bytes(const rten_hip_conv2d_desc *d) {
     if (!d || d->groups <= 0) return 0;
@@ -3062,10 +3079,10 @@ RTEN_EXPORT int32_t rten_hip_conv2d_f32_prepack(rten_hip_ctx *ctx, const rten_hi
     return RTEN_HIP_OK;
 }
 
-RTEN_EXPORT int32_t rten_hip_conv2d_f32(rten_hip_ctx *ctx, const rten_hip_conv2d_desc *d, const float *x, const float *w,
-                                        int32_t weights_packed, const float *bias, const float *residual,
-                                        uint32_t flags, float *y) {
-    RTEN_CHECK_CTX(ctx);
+namespace {
+// `act`: the epilogue activation (flags' RTEN_HIP_CONV_RELU already folded into it)
+int32_t conv2d_f32_impl(rten_hip_ctx *ctx, const rten_hip_conv2d_desc *d, const float *x, const float *w, int32_t weights_packed, const float *bias,
+                        const float *residual, uint32_t flags, const RtenAct &act, float *y) {
     int32_t rc = check_conv_desc(ctx, d);
     if (rc) return rc;
     if (!x || !w || !y) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "conv: NULL operand");
@@ -3075,12 +3092,15 @@ RTEN_EXPORT int32_t rten_hip_conv2d_f32(rten_hip_ctx *ctx, const rten_hip_conv2d
     {   // dispatch order of conv_impl (conv.rs:248-284): the pointwise GEMM first (groups == 1 only), then depthwise
         const bool pw = d->kh == 1 && d->kw == 1 && d->groups == 1 && d->stride_h == 1 && d->stride_w == 1 && d->dil_h == 1 && d->dil_w == 1 &&
                         d->pads[0] == 0 && d->pads[1] == 0 && d->pads[2] == 0 && d->pads[3] == 0;
-        if (!pw && d->c == d->o && d->groups == d->c) return rten_depthwise_conv2d_f32(ctx, d, x, w, weights_packed, bias, residual, flags, y);
+        if (!pw && d->c == d->o && d->groups == d->c) return rten_depthwise_conv2d_f32(ctx, d, x, w, weights_packed, bias, residual, flags, act, y);
     }
+    // the stem kernel's epilogue knows Relu only: other activations take the generic forms
+    const uint32_t stem_flags = (flags & ~RTEN_HIP_CONV_RELU) | (act.kind == RTEN_HIP_ACT_RELU ? RTEN_HIP_CONV_RELU : 0u);
     // variant 32 (also what -1 = automatic picks there): 3-channel 7x7 stride-2 convolutions (a ResNet stem) as a direct implicit GEMM over an image patch in LDS
     // (gemm_f32_stem.hip); same bits
-    if ((ctx->gemm_variant_override == 32 || ctx->gemm_variant_override < 0) && aligned16(w) && rten_small_c_conv_f32_supported(d, weights_packed, (flags & RTEN_HIP_CONV_RESIDUAL) ? residual : nullptr))
-        return rten_small_c_conv_f32(ctx, d, x, w, bias, flags, y);
+    if ((ctx->gemm_variant_override == 32 || ctx->gemm_variant_override < 0) && act.kind <= RTEN_HIP_ACT_RELU && aligned16(w) &&
+        rten_small_c_conv_f32_supported(d, weights_packed, (flags & RTEN_HIP_CONV_RESIDUAL) ? residual : nullptr))
+        return rten_small_c_conv_f32(ctx, d, x, w, bias, stem_flags, y);
     const int Cg = d->c / d->groups, Og = d->o / d->groups, Og4 = (Og + 3) & ~3;
     const int K = Cg * d->kh * d->kw;
     const int P = d->out_h * d->out_w;
@@ -3112,7 +3132,7 @@ RTEN_EXPORT int32_t rten_hip_conv2d_f32(rten_hip_ctx *ctx, const rten_hip_conv2d
     g.Pn = P;
     g.alpha = 1.f; g.beta = 0.f;
     g.bias_kind = bias ? RTEN_HIP_BIAS_PER_ROW : RTEN_HIP_BIAS_NONE;
-    g.act = (flags & RTEN_HIP_CONV_RELU) ? RTEN_HIP_ACT_RELU : RTEN_HIP_ACT_NONE;
+    g.act = act.kind; g.act_a = act.alpha; g.act_b = act.beta;
 
     const bool pointwise = d->kh == 1 && d->kw == 1 && d->stride_h == 1 && d->stride_w == 1 && d->pads[0] == 0 &&
                            d->pads[1] == 0 && d->pads[2] == 0 && d->pads[3] == 0; // conv.rs:250-258 (dilation is moot)
@@ -3135,6 +3155,25 @@ RTEN_EXPORT int32_t rten_hip_conv2d_f32(rten_hip_ctx *ctx, const rten_hip_conv2d
     g.b_dir_n = 1;
     g.debug = ctx->debug;
     return dispatch(ctx, g, d->groups, al, bl);
+}
+} // namespace
+
+RTEN_EXPORT int32_t rten_hip_conv2d_f32(rten_hip_ctx *ctx, const rten_hip_conv2d_desc *d, const float *x, const float *w,
+                                        int32_t weights_packed, const float *bias, const float *residual,
+                                        uint32_t flags, float *y) {
+    RTEN_CHECK_CTX(ctx);
+    const RtenAct act = {(flags & RTEN_HIP_CONV_RELU) ? RTEN_HIP_ACT_RELU : RTEN_HIP_ACT_NONE, 0.f, 0.f};
+    return conv2d_f32_impl(ctx, d, x, w, weights_packed, bias, residual, flags, act, y);
+}
+
+RTEN_EXPORT int32_t rten_hip_conv2d_f32_act(rten_hip_ctx *ctx, const rten_hip_conv2d_desc *d, const float *x, const float *w,
+                                            int32_t weights_packed, const float *bias, const float *residual,
+                                            uint32_t flags, int32_t act_kind, float act_alpha, float act_beta, float *y) {
+    RTEN_CHECK_CTX(ctx);
+    if (flags & RTEN_HIP_CONV_RELU) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "conv_act: pass Relu as the activation, not as a flag");
+    if (!rten_act_valid(act_kind)) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "conv_act: unknown activation kind");
+    const RtenAct act = {act_kind, act_alpha, act_beta};
+    return conv2d_f32_impl(ctx, d, x, w, weights_packed, bias, residual, flags, act, y);
 }
 
 #ifdef RTEN_TRACE

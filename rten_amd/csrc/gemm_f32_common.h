@@ -61,7 +61,8 @@ struct GemmArgs {
     float alpha, beta;
     int bias_kind, act;
     int tiles_m, tiles_n;
-    int a_dir_m, b_dir_n; // scalar loaders: lanes run along m / n (1) or along k (0)
+    short a_dir_m, b_dir_n; // scalar loaders: lanes run along m / n (1) or along k (0) (16 bits each: with act_a / act_b the block still spans 5 cache lines)
+    float act_a;            // activation parameters (RTEN_HIP_ACT_SWISH .. ELU; act_b after n_lo)
     int H, W, OW, sy, sx, pt, pl; // im2col geometry
     int KH, KW, dy, dx;           // kernel taps / dilation (B_IM2COL_TAPS validity masks)
     int debug; // ablation switches for tuning runs (RTEN_HIP_DEBUG): 1 = skip the in-loop DMA, 2 = skip the MFMAs, 4 = skip the epilogue
@@ -73,6 +74,7 @@ struct GemmArgs {
     int split_t1, split_s, split_g, split_slots, split_ntail;
     int order; // bit 0: tiles walk n fastest (default m fastest); bit 1: split workgroups walk tiles fastest, K groups slowest
     int n_lo;  // thin-tile kernel: first column of its share (the whole-round tiles of the same call cover [0, n_lo))
+    float act_b;
 #ifdef RTEN_TRACE
     unsigned long long *trace_buf; // NULL: off
     unsigned trace_cap;
@@ -184,7 +186,8 @@ __device__ __forceinline__ void fold_next(const GemmArgs &p, f32x16 (&acc)[TM][T
 // Residual Add, activation and the NCHW / row-major store of finished values.  Buffer loads/stores with 32-bit
 // offsets: the lane part (column, first row of the block) is one VGPR per block, the register's row rides in the
 // scalar offset; rows >= M / columns >= N get an out-of-range lane offset (store dropped, load returns 0).
-template <int TM, int TN>
+// EXT = false: NONE / RELU / GELU only (for a kernel with no register room for the other kinds; its launcher never routes them to it).
+template <int TM, int TN, bool EXT = true>
 __device__ __forceinline__ void store_out(const GemmArgs &p, f32x16 (&val)[TM][TN], int mb, int nb0, long long c_zoff) {
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void *)(p.C + c_zoff), 0, 0x7ffffffc, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void *)((p.res ? p.res : p.C) + c_zoff), 0, 0x7ffffffc, 0x00020000);
@@ -218,6 +221,8 @@ __device__ __forceinline__ void store_out(const GemmArgs &p, f32x16 (&val)[TM][T
             } else if (p.act == RTEN_HIP_ACT_GELU) {
 #pragma unroll
                 for (int r = 0; r < 16; r++) v[r] = vm::gelu(v[r]);
+            } else if (EXT && p.act != RTEN_HIP_ACT_NONE) {
+                vm::activation_n<16>(p.act, v, p.act_a, p.act_b);
             }
 #pragma unroll
             for (int r = 0; r < 16; r++) {

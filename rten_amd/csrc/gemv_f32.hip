@@ -25,6 +25,7 @@ struct GemvArgs {
     int batch_inner;
     float alpha, beta;
     int bias_kind, act, col_block;
+    float act_a, act_b;
 };
 
 __device__ __forceinline__ float finish(const GemvArgs &p, float o, int col) {
@@ -32,6 +33,7 @@ __device__ __forceinline__ float finish(const GemvArgs &p, float o, int col) {
     else if (p.bias_kind == RTEN_HIP_BIAS_PER_COL) o = o + p.bias[col];
     if (p.act == RTEN_HIP_ACT_RELU) o = vm::relu(o);
     else if (p.act == RTEN_HIP_ACT_GELU) o = vm::gelu(o);
+    else if (p.act != RTEN_HIP_ACT_NONE) o = vm::activation(p.act, o, p.act_a, p.act_b);
     return o;
 }
 
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(256) void gemv_transposed_kernel(const GemvArgs p) 
 } // namespace
 
 // Called by rten_hip_gemm_f32 for m == 1, k > 0 when the context's gemv order is on.
-int32_t rten_gemv_f32(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b, const float *bias, float *c) {
+int32_t rten_gemv_f32(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b, const float *bias, const RtenAct *act, float *c) {
     GemvArgs g = {};
     g.A = a; g.B = b; g.bias = bias; g.C = c;
     g.N = d->n; g.K = d->k;
@@ -130,6 +132,7 @@ int32_t rten_gemv_f32(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const floa
     g.batch_inner = d->batch_inner;
     g.alpha = d->alpha; g.beta = d->beta;
     g.bias_kind = d->bias_kind; g.act = d->act;
+    if (act) { g.act = act->kind; g.act_a = act->alpha; g.act_b = act->beta; }
     long long cb = 128;
     if (ctx->gemv_threads > 0) {
         cb = ((long long)d->n + ctx->gemv_threads - 1) / ctx->gemv_threads;

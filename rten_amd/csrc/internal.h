@@ -85,8 +85,14 @@ int32_t rten_check_hip(rten_hip_ctx *ctx, hipError_t e, const char *what);
 void *rten_scratch(rten_hip_ctx *ctx, size_t bytes);
 // non-zero: the context's sticky device fault as an error (see rten_hip_ctx::fault_host)
 int32_t rten_check_fault(rten_hip_ctx *ctx);
-// gemv_f32.hip: the m == 1 product in the reference's gemv order (called by rten_hip_gemm_f32)
-int32_t rten_gemv_f32(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b, const float *bias, float *c);
+// An epilogue activation: RTEN_HIP_ACT_* kind and its two parameters (the act_kind / act_alpha / act_beta arguments of the C ABI)
+struct RtenAct {
+    int32_t kind;
+    float alpha, beta;
+};
+inline bool rten_act_valid(int32_t kind) { return kind >= RTEN_HIP_ACT_NONE && kind <= RTEN_HIP_ACT_ELU; }
+// gemv_f32.hip: the m == 1 product in the reference's gemv order (called by rten_hip_gemm_f32); `act` (NULL: desc->act) is the epilogue activation
+int32_t rten_gemv_f32(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b, const float *bias, const RtenAct *act, float *c);
 // gemm_f32.hip: rten_hip_gemm_f32 without the gemv dispatch (operators whose reference form is not a gemm_impl call on unpacked operands)
 int32_t rten_gemm_f32_blocked(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b, const float *bias, float *c);
 void *rten_aux_scratch(rten_hip_ctx *ctx, size_t bytes);

@@ -6,8 +6,12 @@
 //   ReducedRangeExp  rten-vecmath/src/exp.rs:140-190
 //   Exp              rten-vecmath/src/exp.rs:59-132
 //   Erf, Gelu        rten-vecmath/src/erf.rs:21-76
+//   Sigmoid, Silu, Swish, Elu   rten-vecmath/src/exp.rs:201-275
+//   LeakyRelu        rten-vecmath/src/relu.rs:13-25
+//   HardSigmoid, HardSwish, Clip   src/ops/unary_elementwise.rs:248-303,437-471
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../../include/rten_hip.h"
 
 namespace vm {
 
@@ -114,5 +118,84 @@ __device__ __forceinline__ float tanh(float x) {
 
 // Relu: f32::max(x, 0) -- NaN -> 0 (unary_elementwise.rs:611-613)
 __device__ __forceinline__ float relu(float x) { return fmaxf(x, 0.f); }
+
+// Sigmoid: 1 / (1 + exp(-x)) -- the reciprocal is an IEEE division (rten-simd/src/ops.rs:639)
+__device__ __forceinline__ float sigmoid(float x) { return 1.0f / (1.0f + exp_full(-x)); }
+
+// Silu: x / (1 + exp(-x)), one division (not x * sigmoid(x))
+__device__ __forceinline__ float silu(float x) { return x / (1.0f + exp_full(-x)); }
+
+// Swish(alpha): x * sigmoid(x * alpha)
+__device__ __forceinline__ float swish(float x, float alpha) { return x * sigmoid(x * alpha); }
+
+// Elu(alpha): x >= 0 ? x : alpha * (exp(x) - 1)
+__device__ __forceinline__ float elu(float x, float alpha) {
+    const float e = alpha * (exp_full(x) - 1.0f);
+    return x >= 0.f ? x : e;
+}
+
+// LeakyRelu(alpha): x < 0 ? x * alpha : x
+__device__ __forceinline__ float leaky_relu(float x, float alpha) { return x < 0.f ? x * alpha : x; }
+
+// f32::clamp(x, 0, 1): NaN and -0 pass through
+__device__ __forceinline__ float clamp01(float x) {
+    x = x < 0.f ? 0.f : x;
+    return x > 1.0f ? 1.0f : x;
+}
+
+// HardSigmoid(alpha, beta): clamp(alpha * x + beta, 0, 1), multiply and add rounded separately
+__device__ __forceinline__ float hard_sigmoid(float x, float alpha, float beta) { return clamp01(alpha * x + beta); }
+
+// HardSwish: x * clamp(x / 6 + 0.5, 0, 1) with 1/6 rounded to f32 first
+__device__ __forceinline__ float hard_swish(float x) { return x * clamp01((1.0f / 6.0f) * x + 0.5f); }
+
+// Clip(min, max) through the generic Clamp trait (unary_elementwise.rs:248-303), not f32::clamp: NaN becomes `lo`, lo > hi gives hi
+__device__ __forceinline__ float clip(float x, float lo, float hi) {
+    const float y = x > lo ? x : lo;
+    return y < hi ? y : hi;
+}
+
+// One activation by runtime kind (RTEN_HIP_ACT_*) with its two parameters.  NONE and unknown kinds pass x through.
+__device__ __forceinline__ float activation(int kind, float x, float a, float b) {
+    switch (kind) {
+    case RTEN_HIP_ACT_RELU: return relu(x);
+    case RTEN_HIP_ACT_GELU: return gelu(x);
+    case RTEN_HIP_ACT_SIGMOID: return sigmoid(x);
+    case RTEN_HIP_ACT_SILU: return silu(x);
+    case RTEN_HIP_ACT_SWISH: return swish(x, a);
+    case RTEN_HIP_ACT_HARD_SIGMOID: return hard_sigmoid(x, a, b);
+    case RTEN_HIP_ACT_HARD_SWISH: return hard_swish(x);
+    case RTEN_HIP_ACT_CLIP: return clip(x, a, b);
+    case RTEN_HIP_ACT_LEAKY_RELU: return leaky_relu(x, a);
+    case RTEN_HIP_ACT_ELU: return elu(x, a);
+    default: return x;
+    }
+}
+
+// vm::activation over the first N elements of v: the kind is tested once, outside the element loop, so an epilogue pays one
+// uniform branch per block and straight-line code per kind.  NONE and unknown kinds leave v unchanged.
+template <int N, typename V>
+__device__ __forceinline__ void activation_n(int kind, V &v, float a, float b) {
+#define VM_ACT_LOOP(EXPR)                          \
+    _Pragma("unroll") for (int r = 0; r < N; r++) { \
+        const float x = v[r];                      \
+        v[r] = EXPR;                               \
+    }                                              \
+    break;
+    switch (kind) {
+    case RTEN_HIP_ACT_RELU: VM_ACT_LOOP(relu(x))
+    case RTEN_HIP_ACT_GELU: VM_ACT_LOOP(gelu(x))
+    case RTEN_HIP_ACT_SIGMOID: VM_ACT_LOOP(sigmoid(x))
+    case RTEN_HIP_ACT_SILU: VM_ACT_LOOP(silu(x))
+    case RTEN_HIP_ACT_SWISH: VM_ACT_LOOP(swish(x, a))
+    case RTEN_HIP_ACT_HARD_SIGMOID: VM_ACT_LOOP(hard_sigmoid(x, a, b))
+    case RTEN_HIP_ACT_HARD_SWISH: VM_ACT_LOOP(hard_swish(x))
+    case RTEN_HIP_ACT_CLIP: VM_ACT_LOOP(clip(x, a, b))
+    case RTEN_HIP_ACT_LEAKY_RELU: VM_ACT_LOOP(leaky_relu(x, a))
+    case RTEN_HIP_ACT_ELU: VM_ACT_LOOP(elu(x, a))
+    default: break;
+    }
+#undef VM_ACT_LOOP
+}
 
 } // namespace vm

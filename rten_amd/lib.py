@@ -18,6 +18,8 @@ ERR_INVALID_VALUE, ERR_INCOMPATIBLE_SHAPES, ERR_UNSUPPORTED, ERR_HIP, ERR_NO_DEV
 
 BIAS_NONE, BIAS_PER_ROW, BIAS_PER_COL = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
+# act_kind of rten_hip_activation_f32 / rten_hip_gemm_f32_act / rten_hip_conv2d_f32_act (which also take the three above)
+ACT_SIGMOID, ACT_SILU, ACT_SWISH, ACT_HARD_SIGMOID, ACT_HARD_SWISH, ACT_CLIP, ACT_LEAKY_RELU, ACT_ELU = 3, 4, 5, 6, 7, 8, 9, 10
 CONV_RELU, CONV_RESIDUAL = 1, 2
 PAD_ZERO_POINT, PAD_RAW0_I8, PAD_RAW0_U8 = 0, 1, 2
 MODEL_RECEIVE_WEIGHTS = 1  # rten_hip_model_load_ex flag
@@ -118,6 +120,7 @@ PROTOTYPES = {
     "rten_hip_calc_output_size_and_padding": (_I32, [_I32] * 7 + [C.POINTER(_I32), _I32, _I32, _I32, C.POINTER(_I32),
                                                                  C.POINTER(_I32), C.POINTER(C.c_char_p)]),
     "rten_hip_gemm_f32": (_I32, [_VP, C.POINTER(GemmDesc), _VP, _VP, _VP, _VP]),
+    "rten_hip_gemm_f32_act": (_I32, [_VP, C.POINTER(GemmDesc), _VP, _VP, _VP, _I32, C.c_float, C.c_float, _VP]),
     "rten_hip_set_gemv_order": (_I32, [_VP, _I32, _I32]),
     "rten_hip_gemm_int8": (_I32, [_VP, C.POINTER(GemmInt8Desc), _VP, _VP, _VP, _VP, _VP, _VP]),
     "rten_hip_gemm_int8_packed_bytes": (_SZ, [_I32, _I32]),
@@ -130,6 +133,7 @@ PROTOTYPES = {
     "rten_hip_conv2d_f32_packed_bytes": (_SZ, [C.POINTER(Conv2dDesc)]),
     "rten_hip_conv2d_f32_prepack": (_I32, [_VP, C.POINTER(Conv2dDesc), _VP, _VP]),
     "rten_hip_conv2d_f32": (_I32, [_VP, C.POINTER(Conv2dDesc), _VP, _VP, _I32, _VP, _VP, _U32, _VP]),
+    "rten_hip_conv2d_f32_act": (_I32, [_VP, C.POINTER(Conv2dDesc), _VP, _VP, _I32, _VP, _VP, _U32, _I32, C.c_float, C.c_float, _VP]),
     "rten_hip_conv2d_f32_pair_supported": (_I32, [C.POINTER(Conv2dDesc), C.POINTER(Conv2dDesc)]),
     "rten_hip_conv2d_f32_pair": (_I32, [_VP, C.POINTER(Conv2dDesc), _VP, _VP, _VP, _VP, _U32, _VP, C.POINTER(Conv2dDesc), _VP, _VP, _U32, _VP]),
     "rten_hip_conv2d_f32_pair_shortcut_supported": (_I32, [C.POINTER(Conv2dDesc), C.POINTER(Conv2dDesc), C.POINTER(Conv2dDesc)]),
@@ -157,6 +161,7 @@ PROTOTYPES = {
     "rten_hip_add_layer_norm_f32": (_I32, [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _F32, _F32, _F32, _VP]),
     "rten_hip_batch_norm_f32": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _F32, _VP]),
     "rten_hip_relu_f32": (_I32, [_VP, _I64, _VP, _VP]),
+    "rten_hip_activation_f32": (_I32, [_VP, _I32, C.c_float, C.c_float, _I64, _VP, _VP]),
     "rten_hip_gelu_f32": (_I32, [_VP, _I64, _VP, _VP]),
     "rten_hip_erf_f32": (_I32, [_VP, _I64, _VP, _VP]),
     "rten_hip_tanh_f32": (_I32, [_VP, _I64, _VP, _VP]),

@@ -111,14 +111,16 @@ class Operator:
 class Conv(Operator):
     """src/ops/conv.rs:367-403.  inputs: X [N,C,H,W] (or [N,C,W]), W [O,C/g,kh,kw], bias [O]?
     Extra (backend fusion of the following graph ops): `fuse_relu`, and a 4th input =
-    residual tensor added before the Relu."""
+    residual tensor added before the Relu.  `act`: another following activation (an activation operator
+    instance such as Sigmoid(), Clip(0, 6), HardSwish()) applied in the epilogue instead; exclusive with fuse_relu."""
 
-    def __init__(self, groups=1, dilations=(1, 1), padding=(0, 0, 0, 0), strides=(1, 1), fuse_relu=False):
+    def __init__(self, groups=1, dilations=(1, 1), padding=(0, 0, 0, 0), strides=(1, 1), fuse_relu=False, act=None):
         self.groups = groups
         self.dilations = list(dilations)
         self.padding = padding
         self.strides = list(strides)
         self.fuse_relu = fuse_relu
+        self.act = act
         self._packed = {}
 
     def max_inputs(self):
@@ -176,7 +178,7 @@ class Conv(Operator):
             raise InvalidValue("expected 1 stride value")
         if len(self.dilations) != 1:
             raise InvalidValue("expected 1 dilation value")
-        op = Conv(self.groups, [1, self.dilations[0]], pad2, [1, self.strides[0]], self.fuse_relu)
+        op = Conv(self.groups, [1, self.dilations[0]], pad2, [1, self.strides[0]], self.fuse_relu, self.act)
         n, c, wd = x.shape
         return op, x.view((n, c, 1, wd)), w.view((w.shape[0], w.shape[1], 1, w.shape[2]))
 
@@ -196,8 +198,15 @@ class Conv(Operator):
         y = out if out is not None else DeviceTensor(ctx, (d.n, d.o, d.out_h, d.out_w), np.float32)
         flags = (L.CONV_RELU if self.fuse_relu else 0) | (L.CONV_RESIDUAL if residual is not None else 0)
         wt = packed_weight if packed_weight is not None else w
-        ctx.call("rten_hip_conv2d_f32", C.byref(d), x.vp, wt.vp, 1 if packed_weight is not None else 0, _vp(bias),
-                 _vp(residual), flags, y.vp)
+        if self.act is not None:
+            if self.fuse_relu:
+                raise InvalidValue("Conv: fuse_relu and act are exclusive")
+            kind, alpha, beta = _activation_args(self.act)
+            ctx.call("rten_hip_conv2d_f32_act", C.byref(d), x.vp, wt.vp, 1 if packed_weight is not None else 0, _vp(bias),
+                     _vp(residual), flags, kind, alpha, beta, y.vp)
+        else:
+            ctx.call("rten_hip_conv2d_f32", C.byref(d), x.vp, wt.vp, 1 if packed_weight is not None else 0, _vp(bias),
+                     _vp(residual), flags, y.vp)
         return [y]
 
 
@@ -335,7 +344,11 @@ def _broadcast_shapes(a, b):
 
 def _matmul(ctx, a: DeviceTensor, b: DeviceTensor, bias=None, alpha=None, act=L.ACT_NONE, b_transposed=False):
     """numpy.matmul rules, src/ops/matmul.rs:208-385.  Contiguous inputs; `b_transposed` reads B as
-    [..., N, K] (TransformInputs / transB folded into strides, matmul.rs:47-48, fusions.rs:1066)."""
+    [..., N, K] (TransformInputs / transB folded into strides, matmul.rs:47-48, fusions.rs:1066).
+    `act`: L.ACT_NONE / ACT_RELU / ACT_GELU, or an activation operator instance (rten_hip_gemm_f32_act)."""
+    ext = None
+    if act is not None and not isinstance(act, int):
+        ext, act = _activation_args(act), L.ACT_NONE
     ash, bsh = list(a.shape), list(b.shape)
     if len(ash) < 1 or len(bsh) < 1:
         raise InvalidValue("Inputs must have >= 1 dimensions")
@@ -369,7 +382,10 @@ def _matmul(ctx, a: DeviceTensor, b: DeviceTensor, bias=None, alpha=None, act=L.
             d = L.gemm_desc(m, n, k, k, 1, b_rs, b_cs, n, batch, m * k if na > 1 else 0, k * n if nb > 1 else 0, m * n,
                             alpha=alpha if alpha is not None else 1.0,
                             bias_kind=L.BIAS_PER_COL if bias is not None else L.BIAS_NONE, act=act)
-        ctx.call("rten_hip_gemm_f32", C.byref(d), a.vp, b.vp, _vp(bias), y.vp)
+        if ext is not None:
+            ctx.call("rten_hip_gemm_f32_act", C.byref(d), a.vp, b.vp, _vp(bias), ext[0], ext[1], ext[2], y.vp)
+        else:
+            ctx.call("rten_hip_gemm_f32", C.byref(d), a.vp, b.vp, _vp(bias), y.vp)
     if a_vec:
         out_shape.pop(-2)
     if b_vec:
@@ -378,7 +394,10 @@ def _matmul(ctx, a: DeviceTensor, b: DeviceTensor, bias=None, alpha=None, act=L.
 
 
 class MatMul(Operator):
-    """src/ops/matmul.rs:387-428"""
+    """src/ops/matmul.rs:387-428.  `act` (backend fusion extra): an activation operator instance applied in the epilogue."""
+
+    def __init__(self, act=None):
+        self.act = act
 
     def max_inputs(self):
         return 2
@@ -386,12 +405,12 @@ class MatMul(Operator):
     def run(self, ctx, inputs):
         a = _want(_require(inputs, 0), np.float32)
         b = _want(_require(inputs, 1), np.float32)
-        return [_matmul(ctx, a, b)]
+        return [_matmul(ctx, a, b, act=self.act if self.act is not None else L.ACT_NONE)]
 
 
 class FusedMatMul(Operator):
     """src/ops/matmul.rs:455-510: MatMul + bias (per column) + alpha.  `act` is a backend fusion extra
-    (GELU epilogue for the BERT FFN)."""
+    (GELU epilogue for the BERT FFN): L.ACT_NONE / ACT_RELU / ACT_GELU or an activation operator instance."""
 
     def __init__(self, alpha=None, act=L.ACT_NONE, transpose_b=False):
         self.alpha = alpha
@@ -853,6 +872,102 @@ class Gelu(_Unary):
 
 class Erf(_Unary):
     fn = "rten_hip_erf_f32"
+
+
+class _Activation(Operator):
+    """Element-wise activation with parameters (rten_hip_activation_f32; rten-vecmath/src/exp.rs:201-275, relu.rs:13-25,
+    src/ops/unary_elementwise.rs:248-303,437-471).  An instance is also what Conv / MatMul / FusedMatMul take as `act`."""
+    kind = L.ACT_NONE
+
+    def __init__(self, alpha=0.0, beta=0.0):
+        self.alpha = alpha
+        self.beta = beta
+
+    def max_inputs(self):
+        return 1
+
+    def run(self, ctx, inputs, in_place=False):
+        x = _require(inputs, 0)
+        if x.dtype != np.float32:
+            raise OpError("UnsupportedType", "expected float32 tensor")
+        y = x if in_place else DeviceTensor(ctx, x.shape, np.float32)
+        ctx.call("rten_hip_activation_f32", *_activation_args(self), x.size, x.vp, y.vp)
+        return [y]
+
+
+def _activation_args(act):
+    """(kind, alpha, beta) of an activation operator instance."""
+    if not isinstance(act, _Activation):
+        raise InvalidValue(f"expected an activation operator, got {act!r}")
+    return act.kind, float(act.alpha), float(act.beta)
+
+
+class Sigmoid(_Activation):
+    kind = L.ACT_SIGMOID
+
+
+class Silu(_Activation):
+    kind = L.ACT_SILU
+
+
+class Swish(_Activation):
+    kind = L.ACT_SWISH
+
+    def __init__(self, alpha=1.0):
+        super().__init__(alpha)
+
+
+class HardSigmoid(_Activation):
+    kind = L.ACT_HARD_SIGMOID
+
+    def __init__(self, alpha=0.2, beta=0.5):
+        super().__init__(alpha, beta)
+
+
+class HardSwish(_Activation):
+    kind = L.ACT_HARD_SWISH
+
+
+class LeakyRelu(_Activation):
+    kind = L.ACT_LEAKY_RELU
+
+    def __init__(self, alpha=0.01):
+        super().__init__(alpha)
+
+
+class Elu(_Activation):
+    kind = L.ACT_ELU
+
+    def __init__(self, alpha=1.0):
+        super().__init__(alpha)
+
+
+F32_MAX = float(np.finfo(np.float32).max)
+
+
+class Clip(_Activation):
+    """Clip(x, min, max) through the reference's Clamp trait: a missing bound is f32::MIN / f32::MAX, NaN becomes min.
+    Bounds given as constructor arguments, or as scalar inputs 1 / 2 (read back to the host)."""
+    kind = L.ACT_CLIP
+
+    def __init__(self, min=None, max=None):
+        super().__init__(-F32_MAX if min is None else min, F32_MAX if max is None else max)
+
+    def max_inputs(self):
+        return 3
+
+    def run(self, ctx, inputs, in_place=False):
+        lo, hi = _get(inputs, 1), _get(inputs, 2)
+        if lo is None and hi is None:
+            return super().run(ctx, inputs, in_place)
+
+        def bound(t, dflt):
+            if t is None:
+                return dflt
+            if t.size != 1:
+                raise InvalidValue("Clip: min / max must be scalars")
+            return float(t.numpy().reshape(-1)[0])
+        return Clip(bound(lo, self.alpha), bound(hi, self.beta)).run(ctx, inputs[:1], in_place)
 
 
 class _Binary(Operator):

@@ -89,6 +89,11 @@ def main():
     n_ffn = 4096 * 3072
     hbm("Gelu", f"n={n_ffn}", (lambda: ctx.call("rten_hip_gelu_f32", n_ffn, x.vp, y.vp)), 8.0 * n_ffn)
     hbm("Erf", f"n={n_ffn}", (lambda: ctx.call("rten_hip_erf_f32", n_ffn, x.vp, y.vp)), 8.0 * n_ffn)
+    # the parameterised activation kernel, every kind, at 12.6 M elements (rten_hip_activation_f32)
+    for name, kind, a, b in (("Sigmoid", L.ACT_SIGMOID, 0.0, 0.0), ("Silu", L.ACT_SILU, 0.0, 0.0), ("Swish", L.ACT_SWISH, 1.702, 0.0),
+                             ("HardSigmoid", L.ACT_HARD_SIGMOID, 0.2, 0.5), ("HardSwish", L.ACT_HARD_SWISH, 0.0, 0.0), ("Clip", L.ACT_CLIP, 0.0, 6.0),
+                             ("LeakyRelu", L.ACT_LEAKY_RELU, 0.01, 0.0), ("Elu", L.ACT_ELU, 1.0, 0.0)):
+        hbm(f"activation {name}", f"n={n_ffn}", (lambda kind=kind, a=a, b=b: ctx.call("rten_hip_activation_f32", kind, a, b, n_ffn, x.vp, y.vp)), 8.0 * n_ffn)
     r, c = 32 * 12 * 128, 128
     hbm("Softmax", f"rows={r} cols={c}", (lambda: ctx.call("rten_hip_softmax_f32", r, c, x.vp, None, 1, 1, 0, y.vp)), 8.0 * r * c)
     r, c = 4096, 768
@@ -118,6 +123,37 @@ def main():
     ydw = empty((32, cdw, 56, 56))
     ddw = L.Conv2dDesc(32, cdw, 56, 56, cdw, 3, 3, (C.c_int32 * 4)(1, 1, 1, 1), 1, 1, 1, 1, cdw, 56, 56)
     hbm("Conv depthwise 3x3", f"32x{cdw}x56x56", (lambda: ctx.call("rten_hip_conv2d_f32", C.byref(ddw), xdw.vp, wdw.vp, 0, bdw.vp, None, 0, ydw.vp)), 8.0 * 32 * cdw * 56 * 56)
+    # fused activation epilogue vs the same convolution with none, and vs convolution + the standalone kernel: the depthwise 3x3 above and a
+    # MobileNet pointwise convolution (32 x 96 x 112 x 112 -> 24)
+    ndw = 32 * cdw * 56 * 56
+    hbm("Conv depthwise 3x3 + Clip(0, 6) fused", f"32x{cdw}x56x56",
+        (lambda: ctx.call("rten_hip_conv2d_f32_act", C.byref(ddw), xdw.vp, wdw.vp, 0, bdw.vp, None, 0, L.ACT_CLIP, 0.0, 6.0, ydw.vp)), 8.0 * ndw)
+    hbm("Conv depthwise 3x3 + Silu fused", f"32x{cdw}x56x56",
+        (lambda: ctx.call("rten_hip_conv2d_f32_act", C.byref(ddw), xdw.vp, wdw.vp, 0, bdw.vp, None, 0, L.ACT_SILU, 0.0, 0.0, ydw.vp)), 8.0 * ndw)
+    hbm("Conv depthwise 3x3, then standalone Silu", f"32x{cdw}x56x56",
+        (lambda: (ctx.call("rten_hip_conv2d_f32", C.byref(ddw), xdw.vp, wdw.vp, 0, bdw.vp, None, 0, ydw.vp),
+                  ctx.call("rten_hip_activation_f32", L.ACT_SILU, 0.0, 0.0, ndw, ydw.vp, ydw.vp))), 8.0 * ndw)
+    dpw = L.Conv2dDesc(32, 96, 112, 112, 24, 1, 1, (C.c_int32 * 4)(0, 0, 0, 0), 1, 1, 1, 1, 1, 112, 112)
+    xpw, bpw = dev(rng.standard_normal((32, 96, 112, 112), dtype=np.float32)), dev(np.zeros(24, np.float32))
+    wpw = empty((ctx.lib.rten_hip_conv2d_f32_packed_bytes(C.byref(dpw)) // 4,))
+    ctx.call("rten_hip_conv2d_f32_prepack", C.byref(dpw), dev(rng.standard_normal((24, 96, 1, 1), dtype=np.float32)).vp, wpw.vp)
+    ypw = empty((32, 24, 112, 112))
+    npw_in, npw_out = 32 * 96 * 112 * 112, 32 * 24 * 112 * 112
+    for label, kind, a, b in (("no activation", L.ACT_NONE, 0.0, 0.0), ("+ Clip(0, 6) fused", L.ACT_CLIP, 0.0, 6.0), ("+ Silu fused", L.ACT_SILU, 0.0, 0.0)):
+        hbm(f"Conv pointwise {label}", "32x96x112x112 -> 24",
+            (lambda kind=kind, a=a, b=b: ctx.call("rten_hip_conv2d_f32_act", C.byref(dpw), xpw.vp, wpw.vp, 1, bpw.vp, None, 0, kind, a, b, ypw.vp)),
+            4.0 * (npw_in + npw_out))
+    hbm("Conv pointwise, then standalone Silu", "32x96x112x112 -> 24",
+        (lambda: (ctx.call("rten_hip_conv2d_f32", C.byref(dpw), xpw.vp, wpw.vp, 1, bpw.vp, None, 0, ypw.vp),
+                  ctx.call("rten_hip_activation_f32", L.ACT_SILU, 0.0, 0.0, npw_out, ypw.vp, ypw.vp))), 4.0 * (npw_in + npw_out))
+    # the SwiGLU gate projection of a decoder MLP: 4096 x 768 x 3072 with Silu in the epilogue
+    xs, ws = dev(rng.standard_normal((4096, 768), dtype=np.float32)), dev(rng.standard_normal((768, 3072), dtype=np.float32))
+    ys = empty((4096, 3072))
+    gsd = L.gemm_desc(4096, 3072, 768, 768, 1, 3072, 1, 3072)
+    mfma("FusedMatMul+Silu", "4096x768x3072", (lambda: ctx.call("rten_hip_gemm_f32_act", C.byref(gsd), xs.vp, ws.vp, None, L.ACT_SILU, 0.0, 0.0, ys.vp)),
+         2.0 * 4096 * 768 * 3072, F32_PEAK_TF, "TFLOP/s")
+    mfma("MatMul (no activation, same shape)", "4096x768x3072", (lambda: ctx.call("rten_hip_gemm_f32", C.byref(gsd), xs.vp, ws.vp, None, ys.vp)),
+         2.0 * 4096 * 768 * 3072, F32_PEAK_TF, "TFLOP/s")
     xct, wct, bct = dev(rng.standard_normal((32, 64, 28, 28), dtype=np.float32)), dev(rng.standard_normal((64, 32, 4, 4), dtype=np.float32)), dev(np.zeros(32, np.float32))
     yct = empty((32, 32, 56, 56))
     dct = L.Conv2dDesc(32, 64, 28, 28, 32, 4, 4, (C.c_int32 * 4)(1, 1, 1, 1), 2, 2, 1, 1, 1, 56, 56)

@@ -110,7 +110,7 @@ int main(int argc, char **argv) {
             if (c.nodes.size() != m.nodes.size()) {
                 std::map<std::string, int> chist;
                 for (auto &n : c.nodes) chist[n.op_type]++;
-                std::printf("  canonical form (Constant nodes, Gelu / LayerNormalization patterns): %zu nodes:", c.nodes.size());
+                std::printf("  canonical form (Constant nodes, Silu / Swish / Gelu / LayerNormalization patterns): %zu nodes:", c.nodes.size());
                 for (auto &h : chist) std::printf(" %s x%d", h.first.c_str(), h.second);
                 std::printf("\n");
             }

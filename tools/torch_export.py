@@ -11,6 +11,7 @@ Test and tooling infrastructure only: nothing under rten_amd/ imports this.
     python tools/torch_export.py encoder /tmp/bert_base_torch.onnx     # BERT-base sized encoder in plain torch.nn, batch 32 x 128
     python tools/torch_export.py bert /tmp/bert_torch.onnx             # transformers.BertModel, random init, 2 layers (its mask
                                                                        # subgraph needs NonZero / Where / Expand: not loadable yet)
+    python tools/torch_export.py mobile /tmp/mobile_torch.onnx         # small MobileNetV2 / V3 / EfficientNet-style network (activations)
 """
 from __future__ import annotations
 
@@ -171,6 +172,59 @@ def bert_onnx(model, batch=2, seq=128) -> bytes:
                         ["last_hidden_state"])
 
 
+def mobile_module(width: int = 1, seed: int = 0):
+    """A small MobileNetV2 / V3 / EfficientNet-style network whose exported graph holds every activation the backend runs:
+    ReLU6 (Clip with min / max attributes), Hardswish, a Hardsigmoid squeeze-excite gate, SiLU (Sigmoid + Mul), a Sigmoid
+    squeeze-excite gate, QuickGELU x * sigmoid(1.702 x) (Swish), LeakyReLU and ELU.  The squeezes are AdaptiveAvgPool2d(1)
+    (GlobalAveragePool).  `width` scales the channel counts."""
+    import torch
+    from torch import nn
+    torch.manual_seed(seed)
+    c1, c2, c3 = 16 * width, 24 * width, 32 * width
+
+    class SE(nn.Module):
+        def __init__(self, c, r, inner, gate):
+            super().__init__()
+            self.pool, self.fc1, self.act, self.fc2, self.gate = nn.AdaptiveAvgPool2d(1), nn.Conv2d(c, r, 1), inner, nn.Conv2d(r, c, 1), gate
+
+        def forward(self, x):
+            return x * self.gate(self.fc2(self.act(self.fc1(self.pool(x)))))
+
+    class QuickGelu(nn.Module):
+        def forward(self, x):
+            return x * torch.sigmoid(1.702 * x)
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.body = nn.Sequential(
+                nn.Conv2d(3, c1, 3, 2, 1), nn.ReLU6(),                               # stem, MobileNetV2
+                nn.Conv2d(c1, c1, 3, 1, 1, groups=c1), nn.Hardswish(),               # depthwise, MobileNetV3
+                SE(c1, 8, nn.ReLU(), nn.Hardsigmoid()),
+                nn.Conv2d(c1, c2, 1), nn.SiLU(),                                     # pointwise, EfficientNet
+                nn.Conv2d(c2, c2, 3, 2, 1, groups=c2), nn.SiLU(),
+                SE(c2, 8, nn.SiLU(), nn.Sigmoid()),
+                nn.Conv2d(c2, c3, 1), nn.LeakyReLU(0.1),
+                nn.Conv2d(c3, c3, 3, 1, 1), nn.ELU(),
+                QuickGelu(),
+                nn.Conv2d(c3, c3, 1), nn.ReLU6(),
+                nn.AdaptiveAvgPool2d(1), nn.Flatten(), nn.Linear(c3, 10))
+            for m in self.modules():  # small weights: activations stay in the interesting range of every function
+                if isinstance(m, nn.Conv2d):
+                    nn.init.normal_(m.weight, 0.0, 0.7 / (m.weight[0].numel() ** 0.5))
+
+        def forward(self, x):
+            return self.body(x)
+
+    return Net().eval()
+
+
+def mobile_onnx(model=None, image: int = 32) -> bytes:
+    import torch
+    model = model if model is not None else mobile_module()
+    return export_bytes(model, (torch.zeros(2, 3, image, image),), ["x"], ["logits"], {"x": {0: "batch"}, "logits": {0: "batch"}})
+
+
 if __name__ == "__main__":
     kind, path = sys.argv[1], sys.argv[2]
     if kind == "resnet50":
@@ -180,6 +234,8 @@ if __name__ == "__main__":
         from rten_amd.workloads import bert as Bw
         cfg = Bw.BertConfig()
         data = encoder_onnx(cfg, Bw.make_weights(cfg), 32, 128)
+    elif kind == "mobile":
+        data = mobile_onnx()
     else:
         data = bert_onnx(bert_module())
     open(path, "wb").write(data)
