@@ -489,6 +489,23 @@ int32_t rten_hip_gather_axis_b32(rten_hip_ctx *ctx, int64_t outer, int64_t axis_
 /* rows x row_elems 4-byte elements from src (row pitch src_pitch elements) to dst (row pitch dst_pitch >= row_elems): one piece of a Concat
  * (src/ops/concat.rs:108) written into its slot of the output. */
 int32_t rten_hip_copy_rows_b32(rten_hip_ctx *ctx, int64_t rows, int64_t row_elems, const void *src, int64_t src_pitch, void *dst, int64_t dst_pitch);
+/* Resize / Upsample (src/ops/resize.rs:48-243): `planes` contiguous f32 planes of in_h x in_w -> out_h x out_w (y contiguous), the NCHW form the
+ * host operators reshape every supported rank to.  inv_scale_y / inv_scale_x map output to input coordinates (1 / scale, or in / out for sizes).
+ * Bit-identical to the reference: input_coord per coordinate mode, clamp to [0, len - 1] (NaN stays NaN: align_corners with an output length of 1
+ * is 0 / 0, nearest then reads index 0 and linear gives NaN), the nearest modes' rounding, lerp = (1 - w) * a + w * b along x, then along y.
+ * An unknown mode / coord_mode / nearest_mode is RTEN_HIP_ERR_INVALID_VALUE (nearest_mode is checked in linear mode too). */
+#define RTEN_HIP_RESIZE_MODE_NEAREST 0
+#define RTEN_HIP_RESIZE_MODE_LINEAR 1 /* bilinear; the loaders map `cubic` here, as the reference does */
+#define RTEN_HIP_RESIZE_COORD_HALF_PIXEL 0
+#define RTEN_HIP_RESIZE_COORD_ASYMMETRIC 1
+#define RTEN_HIP_RESIZE_COORD_ALIGN_CORNERS 2
+#define RTEN_HIP_RESIZE_COORD_PYTORCH_HALF_PIXEL 3
+#define RTEN_HIP_RESIZE_NEAREST_ROUND_PREFER_FLOOR 0
+#define RTEN_HIP_RESIZE_NEAREST_ROUND_PREFER_CEIL 1
+#define RTEN_HIP_RESIZE_NEAREST_FLOOR 2
+#define RTEN_HIP_RESIZE_NEAREST_CEIL 3
+int32_t rten_hip_resize_f32(rten_hip_ctx *ctx, int32_t mode, int32_t coord_mode, int32_t nearest_mode, int64_t planes, int64_t in_h, int64_t in_w,
+                            int64_t out_h, int64_t out_w, float inv_scale_y, float inv_scale_x, const float *x, float *y);
 /* 1 while a graph capture is active on `ctx` (rten_hip_graph_begin .. _end): host code must not upload from host memory then -- the copy would be
  * recorded with the host pointer and re-read at every replay. */
 int32_t rten_hip_capture_active(rten_hip_ctx *ctx);

@@ -2164,6 +2164,10 @@ class Graph {
                 st.batch_coupled = op->axis == 0;
                 const std::string nm = st.name;
                 st.run = [this, op, nm](Context &c, const InputList &in) { note_axis("Softmax", nm, op->axis, require(in, 0)); return op->run(c, in); };
+            } else if (n.op_type == "Resize" || n.op_type == "Upsample") {
+                make_resize_step(st, n);
+            } else if (n.op_type == "Split") {
+                make_split_step(st, n);
             } else if (n.op_type == "Flatten" || n.op_type == "Reshape" || n.op_type == "Squeeze" || n.op_type == "Unsqueeze" || n.op_type == "Identity" ||
                        n.op_type == "Dropout") {
                 make_view_step(st, n, m);
@@ -2381,6 +2385,98 @@ class Graph {
             return true;
         }
         return false;
+    }
+
+    // Resize (opset 10: [X, scales]; 11+: [X, roi, scales, sizes]) and Upsample (opset 7: the `scales` attribute; 9: input 1) with the attributes the
+    // reference reads (onnx_registry.rs:1721-1810).  Scales / sizes are host values at run time (constants or shape arithmetic): nothing is read back,
+    // and the step is one rten_hip_resize_f32 launch (a device copy when nothing is resized), so it is capture-safe.
+    void make_resize_step(Step &st, const onnx::Node &n) {
+        const std::string kind = n.op_type, name = st.name;
+        std::shared_ptr<Resize> op = kind == "Upsample" ? std::make_shared<Upsample>() : std::make_shared<Resize>();
+        auto str_attr = [&](const char *a, const std::string &dflt) { const onnx::Attr *at = n.attr(a); return at ? at->s : dflt; };
+        const std::string mode = str_attr("mode", "nearest");
+        if (mode == "nearest") op->mode = RTEN_HIP_RESIZE_MODE_NEAREST;
+        else if (mode == "linear" || (kind == "Resize" && mode == "cubic")) op->mode = RTEN_HIP_RESIZE_MODE_LINEAR; // cubic: linear, as the reference does
+        else throw GraphError(kind + " " + name + ": mode \"" + mode + "\" is not supported");
+        size_t scales_at = 1; // the scales input (sizes follow it in opset 11+)
+        if (kind == "Resize") {
+            if (n.get_int("antialias", 0) != 0 || n.get_int("exclude_outside", 0) != 0 || n.get_float("extrapolation_value", 0.f) != 0.f ||
+                n.get_float("cubic_coeff_a", -0.75f) != -0.75f || str_attr("keep_aspect_ratio_policy", "stretch") != "stretch")
+                throw GraphError("Resize " + name + ": antialias, exclude_outside, extrapolation_value, cubic_coeff_a and keep_aspect_ratio_policy must keep their defaults");
+            static const std::map<std::string, int32_t> coords = {{"half_pixel", RTEN_HIP_RESIZE_COORD_HALF_PIXEL}, {"asymmetric", RTEN_HIP_RESIZE_COORD_ASYMMETRIC},
+                                                                  {"align_corners", RTEN_HIP_RESIZE_COORD_ALIGN_CORNERS},
+                                                                  {"pytorch_half_pixel", RTEN_HIP_RESIZE_COORD_PYTORCH_HALF_PIXEL}};
+            static const std::map<std::string, int32_t> nearest = {{"round_prefer_floor", RTEN_HIP_RESIZE_NEAREST_ROUND_PREFER_FLOOR},
+                                                                   {"round_prefer_ceil", RTEN_HIP_RESIZE_NEAREST_ROUND_PREFER_CEIL},
+                                                                   {"floor", RTEN_HIP_RESIZE_NEAREST_FLOOR}, {"ceil", RTEN_HIP_RESIZE_NEAREST_CEIL}};
+            const std::string cm = str_attr("coordinate_transformation_mode", "half_pixel"), nm = str_attr("nearest_mode", "round_prefer_floor");
+            if (!coords.count(cm)) throw GraphError("Resize " + name + ": coordinate_transformation_mode \"" + cm + "\" is not supported");
+            if (!nearest.count(nm)) throw GraphError("Resize " + name + ": nearest_mode \"" + nm + "\" is not supported");
+            op->coord_mode = coords.at(cm);
+            op->nearest_mode = nearest.at(nm);
+            if (n.inputs.size() == 2) { // the opset-10 form [X, scales], which PyTorch's exporter also writes under later opsets: Upsample's coordinates
+                op->coord_mode = RTEN_HIP_RESIZE_COORD_ASYMMETRIC;
+                op->nearest_mode = RTEN_HIP_RESIZE_NEAREST_FLOOR;
+            } else scales_at = 2;
+        }
+        const onnx::Attr *sa = kind == "Upsample" ? n.attr("scales") : nullptr;
+        const std::vector<float> attr_scales = sa ? sa->floats : std::vector<float>();
+        if (sa) st.in.resize(1);
+        // a constant scales / sizes operand of length 1 or 2 means a 1-D / 2-D input, whose dim 0 is resampled
+        int64_t rank = sa ? (int64_t)attr_scales.size() : -1;
+        for (size_t k = scales_at; !sa && rank < 0 && k < n.inputs.size() && k <= scales_at + 1; k++) {
+            auto it = n.inputs[k].empty() ? ids_.end() : ids_.find(n.inputs[k]);
+            if (it != ids_.end() && consts_.count(it->second) && consts_.at(it->second).len() > 0) rank = consts_.at(it->second).len();
+        }
+        st.batch_coupled = rank == 1 || rank == 2;
+        const bool two_input = scales_at == 1;
+        st.run = [this, op, kind, name, sa_given = sa != nullptr, attr_scales, scales_at, two_input](Context &c, const InputList &in) {
+            const Tensor &x = require(in, 0);
+            ResizeTarget t;
+            if (sa_given) t.s = attr_scales;
+            else {
+                const Tensor *s = get(in, scales_at), *z = two_input ? nullptr : get(in, scales_at + 1);
+                for (const Tensor *v : {s, z})
+                    if (v && v->len() && !v->host())
+                        throw OpError(OpError::UnsupportedValue, kind + ": scales / sizes must be constants or computable from the input shapes (they depend on device data)");
+                t = two_input ? Resize::scales_target(require(in, 1)) : Resize::target(s, z);
+            }
+            OutputList o;
+            o.push_back(op->resize(c, x, t));
+            if (x.ndim() <= 2 && o[0].shape() != x.shape() && runtime_coupled_.empty()) runtime_coupled_ = kind + " \"" + name + "\" (resizes dim 0)";
+            return o;
+        };
+    }
+
+    // Split (onnx_registry.rs:1962-1972): the `split` attribute (opset < 13), the split input (13+) or `num_outputs` (18+), else the node's output count.
+    // Host values split on the host (shape arithmetic); 4-byte device tensors are one strided copy per piece.
+    void make_split_step(Step &st, const onnx::Node &n) {
+        auto op = std::make_shared<Split>();
+        op->axis = (int)n.get_int("axis", 0);
+        op->num_outputs = n.attr("num_outputs") ? n.get_int("num_outputs", 0) : -1;
+        op->node_outputs = (int64_t)n.outputs.size();
+        const onnx::Attr *sa = n.attr("split");
+        const std::vector<int64_t> attr_split = sa ? sa->ints : std::vector<int64_t>();
+        if (sa) st.in.resize(1);
+        st.batch_coupled = op->axis == 0;
+        std::vector<std::shared_ptr<HostCache>> caches;
+        for (size_t k = 0; k < n.outputs.size(); k++) caches.push_back(std::make_shared<HostCache>());
+        const std::string name = st.name;
+        st.run = [this, op, sa_given = sa != nullptr, attr_split, caches, name](Context &c, const InputList &in) {
+            const Tensor &x = require(in, 0);
+            note_axis("Split", name, op->axis, x);
+            const int a = resolve_axis(op->axis, x.ndim());
+            const Tensor *s = sa_given ? nullptr : get(in, 1);
+            const std::vector<int64_t> sizes = sa_given ? attr_split : host_ints(s, "Split: the split input");
+            OutputList o;
+            const auto pieces = op->pieces(x.size(a), sa_given || s ? &sizes : nullptr);
+            for (size_t k = 0; k < pieces.size(); k++) {
+                const std::vector<SliceRange> r = Split::piece_ranges(x, a, pieces[k]);
+                if (x.host() && k < caches.size()) o.push_back(materialize(c, hostops::slice(*x.host(), r), *caches[k]));
+                else o.push_back(slice_tensor(c, x, r));
+            }
+            return o;
+        };
     }
 
     // Shape-only operators: the output aliases the input's buffer (src/ops/layout.rs reshapes in place when it can).

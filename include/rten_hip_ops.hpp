@@ -12,11 +12,13 @@
 //   * MaxPool, AveragePool, GlobalAveragePool      src/ops/pooling.rs:174-521
 //   * DynamicQuantizeLinear                        src/ops/quantize.rs:352-436
 //   * Einsum, ReduceSum                            src/ops/einsum.rs:21-692, src/ops/reduce.rs:414-520,1126-1165
+//   * Resize, Upsample, Split                      src/ops/resize.rs:273-652, src/ops/split.rs:34-136
 // Validation runs on the host before any launch; arithmetic is done by librten_hip.so on device-resident tensors.  There
 // is no CPU fallback: without a gfx950 device `Context` throws.  Header only; C++17.
 #pragma once
 #include <algorithm>
 #include <cfloat>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <functional>
@@ -1599,6 +1601,152 @@ inline Tensor concat_tensors(Context &ctx, const InputList &in, int axis) {
     return y;
 }
 
+// ------------------------------------------------------------------------------------------------ Resize / Upsample / Split
+// Resize's target (src/ops/resize.rs:20-27): a scale (f32) or an output size (i32) per input dim.
+struct ResizeTarget {
+    bool scales = true;
+    std::vector<float> s;
+    std::vector<int64_t> n;
+};
+// calc_output_size (resize.rs:273-308): size = floor(in * scale) in f32 (`as i32` saturates, NaN -> 0) and inv_scale = 1 / scale, or size and in / size
+inline void resize_geometry(const std::vector<int64_t> &in, const ResizeTarget &t, std::vector<int64_t> &sizes, std::vector<float> &inv) {
+    if ((t.scales ? t.s.size() : t.n.size()) != in.size()) throw OpError(OpError::IncompatibleInputShapes, "scales/sizes length should equal input rank");
+    sizes.assign(in.size(), 0);
+    inv.assign(in.size(), 0.f);
+    for (size_t i = 0; i < in.size(); i++) {
+        if (t.scales) {
+            const float f = std::floor((float)in[i] * t.s[i]);
+            sizes[i] = f != f ? 0 : f >= 2147483648.f ? INT32_MAX : f < -2147483648.f ? INT32_MIN : (int64_t)f;
+            inv[i] = 1.f / t.s[i];
+        } else {
+            const int32_t o = (int32_t)t.n[i];
+            sizes[i] = o;
+            inv[i] = (float)in[i] / (float)o;
+        }
+    }
+    for (int64_t v : sizes) if (v < 0) throw OpError(OpError::InvalidValue, "scales/sizes must be positive");
+}
+
+// Resize (resize.rs:470-606): f32 only; the input is viewed as [planes, H, W] (resize_impl, resize.rs:334-408) and resampled by rten_hip_resize_f32.
+struct Resize : Operator {
+    int32_t mode = RTEN_HIP_RESIZE_MODE_NEAREST, coord_mode = RTEN_HIP_RESIZE_COORD_HALF_PIXEL, nearest_mode = RTEN_HIP_RESIZE_NEAREST_ROUND_PREFER_FLOOR;
+    const char *name() const override { return "Resize"; }
+    int max_inputs() const override { return 4; }
+    // inputs X, roi (read by tf_crop_and_resize only, which the loader refuses), scales, sizes
+    OutputList run(Context &ctx, const InputList &in) const override {
+        OutputList out;
+        out.push_back(resize(ctx, require(in, 0), target(get(in, 2), get(in, 3))));
+        return out;
+    }
+    // target_from_scale_size_inputs (resize.rs:312-325, 496-507): an absent or empty tensor is missing.  Values come from the tensor's host mirror
+    // when it has one (constants, shape arithmetic), else they are read back.
+    static ResizeTarget target(const Tensor *scales, const Tensor *sizes) {
+        const bool has_s = scales && scales->len(), has_n = sizes && sizes->len();
+        if (has_s && scales->ndim() != 1) throw OpError(OpError::InvalidValue, "scales must have 1 dims");
+        if (has_n && sizes->ndim() != 1) throw OpError(OpError::InvalidValue, "sizes must have 1 dims");
+        if (has_s) return scales_target(*scales);
+        if (!has_n) throw OpError(OpError::MissingInputs, "");
+        want(*sizes, DType::I32, "int32");
+        ResizeTarget t;
+        t.scales = false;
+        if (sizes->host()) t.n = sizes->host()->i;
+        else for (int32_t v : sizes->to_host<int32_t>()) t.n.push_back(v);
+        return t;
+    }
+    static ResizeTarget scales_target(const Tensor &scales) {
+        if (scales.ndim() != 1) throw OpError(OpError::InvalidValue, "scales must have 1 dims");
+        want(scales, DType::F32, "float32");
+        ResizeTarget t;
+        t.s = scales.host() ? scales.host()->f : scales.to_host<float>();
+        return t;
+    }
+    Tensor resize(Context &ctx, const Tensor &x_in, const ResizeTarget &t) const {
+        const Tensor &x = want(x_in, DType::F32, "float32");
+        std::vector<int64_t> os;
+        std::vector<float> inv;
+        resize_geometry(x.shape(), t, os, inv);
+        const std::vector<int64_t> &is = x.shape();
+        if (os == is) { // nothing resized: a copy, whatever the scales were (resize.rs:352)
+            Tensor y(ctx, os, DType::F32);
+            if (y.bytes()) ctx.check(rten_hip_memcpy_d2d(ctx.raw(), y.ptr(), x.ptr(), y.bytes()));
+            return y;
+        }
+        int64_t planes = 1, ih = 1, iw = 1, oh = 1, ow = 1;
+        float sy = 1.f, sx = 1.f; // an axis the input is expanded along is not resized: scale 1
+        const size_t nd = is.size();
+        if (nd == 4 && is[0] == os[0] && is[1] == os[1]) { planes = is[0] * is[1]; ih = is[2]; iw = is[3]; oh = os[2]; ow = os[3]; sy = inv[2]; sx = inv[3]; }
+        else if (nd == 3 && is[0] == os[0] && is[1] == os[1]) { planes = is[0] * is[1]; iw = is[2]; ow = os[2]; sx = inv[2]; } // NCW (tried first)
+        else if (nd == 3 && is[0] == os[0]) { planes = is[0]; ih = is[1]; iw = is[2]; oh = os[1]; ow = os[2]; sy = inv[1]; sx = inv[2]; } // NHW
+        else if (nd == 2) { ih = is[0]; iw = is[1]; oh = os[0]; ow = os[1]; sy = inv[0]; sx = inv[1]; }
+        else if (nd == 1) { iw = is[0]; ow = os[0]; sx = inv[0]; }
+        else throw OpError(OpError::UnsupportedValue, "Only 1D to 4D inputs are supported with up to two resized dimensions");
+        Tensor y(ctx, os, DType::F32);
+        if (y.len())
+            ctx.check(rten_hip_resize_f32(ctx.raw(), mode, coord_mode, nearest_mode, planes, ih, iw, oh, ow, sy, sx, (const float *)x.ptr(), (float *)y.ptr()));
+        return y;
+    }
+};
+
+// Upsample (resize.rs:610-652): the deprecated form of Resize -- scales required (input 1), asymmetric coordinates, floor.
+struct Upsample : Resize {
+    Upsample() { coord_mode = RTEN_HIP_RESIZE_COORD_ASYMMETRIC; nearest_mode = RTEN_HIP_RESIZE_NEAREST_FLOOR; }
+    const char *name() const override { return "Upsample"; }
+    int max_inputs() const override { return 2; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        OutputList out;
+        out.push_back(resize(ctx, require(in, 0), scales_target(require(in, 1))));
+        return out;
+    }
+};
+
+// Split (src/ops/split.rs:34-136) of 4-byte tensors, one strided copy per piece: the sizes of input 1 (the opset < 13 `split` attribute arrives
+// there too), else `num_outputs` (opset 18), else the node's output count, as equal chunks of ceil(dim / n) -- the last piece is smaller, and there
+// may be fewer than n pieces (5 split 4 ways gives 3).
+struct Split : Operator {
+    int axis = 0;
+    int64_t num_outputs = -1; // < 0: the attribute is absent
+    int64_t node_outputs = 1; // outputs of the graph node (ctx.outputs().len() in the reference)
+    const char *name() const override { return "Split"; }
+    int max_inputs() const override { return 2; }
+    // (start, length) along the axis of every piece
+    std::vector<std::pair<int64_t, int64_t>> pieces(int64_t dim, const std::vector<int64_t> *sizes) const {
+        std::vector<std::pair<int64_t, int64_t>> p;
+        if (sizes) {
+            for (int64_t s : *sizes) if (s < 0) throw OpError(OpError::InvalidValue, "Split sizes must be >= 0");
+            int64_t start = 0;
+            for (int64_t s : *sizes) { p.push_back({start, s}); start += s; }
+            if (start != dim) throw OpError(OpError::InvalidValue, "Split sizes do not sum to dimension size");
+            return p;
+        }
+        const int64_t n = num_outputs >= 0 ? num_outputs : node_outputs;
+        if (n == 0) throw OpError(OpError::InvalidValue, "num_outputs must be > 0");
+        if (n > dim) throw OpError(OpError::InvalidValue, "num_outputs exceeds dim size");
+        const int64_t chunk = (dim + n - 1) / n;
+        for (int64_t s = 0; s < dim; s += chunk) p.push_back({s, std::min(chunk, dim - s)});
+        return p;
+    }
+    static std::vector<SliceRange> piece_ranges(const Tensor &x, int a, const std::pair<int64_t, int64_t> &pc) {
+        std::vector<SliceRange> r;
+        for (int d = 0; d < x.ndim(); d++) r.push_back({0, x.size(d), 1});
+        r[(size_t)a] = {pc.first, pc.second, 1};
+        return r;
+    }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0);
+        const int a = resolve_axis(axis, x.ndim());
+        const Tensor *s = get(in, 1);
+        std::vector<int64_t> sizes;
+        if (s) {
+            want(*s, DType::I32, "int32");
+            if (s->host()) sizes = s->host()->i;
+            else for (int32_t v : s->to_host<int32_t>()) sizes.push_back(v);
+        }
+        OutputList out;
+        for (auto &pc : pieces(x.size(a), s ? &sizes : nullptr)) out.push_back(slice_tensor(ctx, x, piece_ranges(x, a, pc)));
+        return out;
+    }
+};
+
 // ------------------------------------------------------------------------------------------------ Einsum / ReduceSum
 // src/ops/einsum.rs:21-692, rten-shape-inference/src/einsum_parser.rs:68-275, src/ops/reduce.rs:414-520,1101-1165.
 // The reference walks a path of two-term steps over permuted TensorViews and copies where a kernel wants contiguous data.
@@ -2129,6 +2277,9 @@ class OpRegistry {
         r.register_op<ReduceSum>("ReduceSum");
         r.register_op<ReduceMean>("ReduceMean");
         r.register_op<Einsum>("Einsum");
+        r.register_op<Resize>("Resize");
+        r.register_op<Upsample>("Upsample");
+        r.register_op<Split>("Split");
         return r;
     }
 

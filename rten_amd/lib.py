@@ -20,6 +20,10 @@ BIAS_NONE, BIAS_PER_ROW, BIAS_PER_COL = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 # act_kind of rten_hip_activation_f32 / rten_hip_gemm_f32_act / rten_hip_conv2d_f32_act (which also take the three above)
 ACT_SIGMOID, ACT_SILU, ACT_SWISH, ACT_HARD_SIGMOID, ACT_HARD_SWISH, ACT_CLIP, ACT_LEAKY_RELU, ACT_ELU = 3, 4, 5, 6, 7, 8, 9, 10
+# mode / coord_mode / nearest_mode of rten_hip_resize_f32 (RTEN_HIP_RESIZE_*)
+RESIZE_MODE_NEAREST, RESIZE_MODE_LINEAR = 0, 1
+RESIZE_COORD_HALF_PIXEL, RESIZE_COORD_ASYMMETRIC, RESIZE_COORD_ALIGN_CORNERS, RESIZE_COORD_PYTORCH_HALF_PIXEL = 0, 1, 2, 3
+RESIZE_NEAREST_ROUND_PREFER_FLOOR, RESIZE_NEAREST_ROUND_PREFER_CEIL, RESIZE_NEAREST_FLOOR, RESIZE_NEAREST_CEIL = 0, 1, 2, 3
 CONV_RELU, CONV_RESIDUAL = 1, 2
 PAD_ZERO_POINT, PAD_RAW0_I8, PAD_RAW0_U8 = 0, 1, 2
 MODEL_RECEIVE_WEIGHTS = 1  # rten_hip_model_load_ex flag
@@ -175,6 +179,7 @@ PROTOTYPES = {
     "rten_hip_elementwise_nd": (_I32, [_VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _I32]),
     "rten_hip_gather_axis_b32": (_I32, [_VP, _I64, _I64, _I64, _I64, _VP, _VP, _VP]),
     "rten_hip_copy_rows_b32": (_I32, [_VP, _I64, _I64, _VP, _I64, _VP, _I64]),
+    "rten_hip_resize_f32": (_I32, [_VP, _I32, _I32, _I32, _I64, _I64, _I64, _I64, _I64, C.c_float, C.c_float, _VP, _VP]),
     "rten_hip_capture_active": (_I32, [_VP]),
     "rten_hip_reduce_sum_strided_f32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_reduce_mean_strided_f32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),

@@ -1258,6 +1258,176 @@ class Einsum(Operator):
         return [E.einsum(ctx, xs, self.equation)]
 
 
+# ------------------------------------------------------------------------------------------ Resize / Upsample / Split
+RESIZE_MODES = {"nearest": L.RESIZE_MODE_NEAREST, "linear": L.RESIZE_MODE_LINEAR}
+RESIZE_COORDS = {"half_pixel": L.RESIZE_COORD_HALF_PIXEL, "asymmetric": L.RESIZE_COORD_ASYMMETRIC, "align_corners": L.RESIZE_COORD_ALIGN_CORNERS,
+                 "pytorch_half_pixel": L.RESIZE_COORD_PYTORCH_HALF_PIXEL}
+RESIZE_NEAREST = {"round_prefer_floor": L.RESIZE_NEAREST_ROUND_PREFER_FLOOR, "round_prefer_ceil": L.RESIZE_NEAREST_ROUND_PREFER_CEIL,
+                  "floor": L.RESIZE_NEAREST_FLOOR, "ceil": L.RESIZE_NEAREST_CEIL}
+
+
+def _host_values(t):
+    """A scales / sizes / split operand: a numpy array or list as given, a DeviceTensor read back."""
+    return t.numpy() if isinstance(t, DeviceTensor) else np.asarray(t)
+
+
+def _optional_operand(t, dtype, what):
+    """get_optional_input (src/ops/resize.rs:496-507): an absent or empty tensor is missing; otherwise a 1-D operand."""
+    if t is None:
+        return None
+    a = _host_values(t)
+    if a.size == 0:
+        return None
+    if a.ndim != 1:
+        raise InvalidValue(f"{what} must have 1 dims")
+    return a.astype(dtype)
+
+
+def resize_geometry(in_shape, scales=None, sizes=None):
+    """calc_output_size (src/ops/resize.rs:273-308): (output sizes, f32 inverse scales).  size = floor(in * scale) in f32 (`as i32` saturates,
+    NaN -> 0) with inv_scale = 1 / scale, or the given size with in / size."""
+    target = scales if scales is not None else sizes
+    if len(target) != len(in_shape):
+        raise IncompatibleInputShapes("scales/sizes length should equal input rank")
+    out, inv = [], []
+    with np.errstate(all="ignore"):
+        for d, n in enumerate(in_shape):
+            if scales is not None:
+                s = np.float32(scales[d])
+                f = np.floor(np.float32(n) * s)
+                out.append(0 if np.isnan(f) else int(max(min(f, 2 ** 31 - 1), -(2 ** 31))))
+                inv.append(np.float32(1) / s)
+            else:
+                o = int(np.int32(sizes[d]))
+                out.append(o)
+                inv.append(np.float32(n) / np.float32(o))
+    if any(v < 0 for v in out):
+        raise InvalidValue("scales/sizes must be positive")
+    return out, inv
+
+
+def _resize_planes(in_shape, out, inv):
+    """resize_impl (src/ops/resize.rs:334-408): the [planes, H, W] view (planes, in_h, in_w, out_h, out_w, inv_y, inv_x); an axis the input is
+    expanded along has scale 1."""
+    s, o, one = tuple(in_shape), tuple(out), np.float32(1)
+    if len(s) == 4 and s[:2] == o[:2]:
+        return s[0] * s[1], s[2], s[3], o[2], o[3], inv[2], inv[3]
+    if len(s) == 3 and s[:2] == o[:2]:  # NCW, tried before NHW
+        return s[0] * s[1], 1, s[2], 1, o[2], one, inv[2]
+    if len(s) == 3 and s[0] == o[0]:  # NHW
+        return s[0], s[1], s[2], o[1], o[2], inv[1], inv[2]
+    if len(s) == 2:
+        return 1, s[0], s[1], o[0], o[1], inv[0], inv[1]
+    if len(s) == 1:
+        return 1, 1, s[0], 1, o[0], one, inv[0]
+    raise UnsupportedValue("Only 1D to 4D inputs are supported with up to two resized dimensions")
+
+
+def _enum(v, table):
+    return table[v] if isinstance(v, str) else int(v)
+
+
+class Resize(Operator):
+    """src/ops/resize.rs:470-606 (rten_hip_resize_f32): inputs X (f32), roi (read by tf_crop_and_resize only, which is unsupported), scales (f32) or
+    sizes (i32); an absent or empty scales / sizes is missing.  An output of the input's shape is a copy, whatever the scales."""
+
+    def __init__(self, mode="nearest", coord_mode="half_pixel", nearest_mode="round_prefer_floor"):
+        self.mode, self.coord_mode, self.nearest_mode = mode, coord_mode, nearest_mode
+
+    def max_inputs(self):
+        return 4
+
+    def run(self, ctx, inputs):
+        x = _require(inputs, 0)
+        scales = _optional_operand(_get(inputs, 2), np.float32, "scales")
+        sizes = _optional_operand(_get(inputs, 3), np.int32, "sizes")
+        if scales is None and sizes is None:
+            raise MissingInputs
+        return [self.resize(ctx, x, scales=scales, sizes=None if scales is not None else sizes)]
+
+    def resize(self, ctx, x, scales=None, sizes=None):
+        x = _want(x, np.float32)
+        out, inv = resize_geometry(x.shape, scales, sizes)
+        if tuple(out) == tuple(x.shape):  # nothing resized (resize.rs:352)
+            y = DeviceTensor(ctx, out, np.float32)
+            if x.size:
+                ctx.call("rten_hip_memcpy_d2d", y.vp, x.vp, C.c_size_t(4 * x.size))
+            return y
+        planes, ih, iw, oh, ow, sy, sx = _resize_planes(x.shape, out, inv)
+        y = DeviceTensor(ctx, out, np.float32)
+        if y.size:
+            ctx.call("rten_hip_resize_f32", _enum(self.mode, RESIZE_MODES), _enum(self.coord_mode, RESIZE_COORDS), _enum(self.nearest_mode, RESIZE_NEAREST),
+                     planes, ih, iw, oh, ow, float(sy), float(sx), x.vp, y.vp)
+        return y
+
+
+class Upsample(Resize):
+    """src/ops/resize.rs:610-652: the deprecated form of Resize -- scales (input 1) required, asymmetric coordinates, floor."""
+
+    def __init__(self, mode="nearest"):
+        super().__init__(mode, "asymmetric", "floor")
+
+    def max_inputs(self):
+        return 2
+
+    def run(self, ctx, inputs):
+        x = _require(inputs, 0)
+        scales = _host_values(_require(inputs, 1))
+        if scales.ndim != 1:
+            raise InvalidValue("scales must have 1 dims")
+        return [self.resize(ctx, x, scales=scales.astype(np.float32))]
+
+
+class Split(Operator):
+    """src/ops/split.rs:34-136 on 4-byte tensors (one rten_hip_copy_strided_b32 per piece): the sizes of input 1, else `num_outputs`, else the
+    node's output count as equal chunks of ceil(dim / n) -- the last piece is smaller, and there may be fewer than n pieces (5 split 4 ways
+    gives 3)."""
+
+    def __init__(self, axis=0, num_outputs=None, node_outputs=1):
+        self.axis, self.num_outputs, self.node_outputs = axis, num_outputs, node_outputs
+
+    def max_inputs(self):
+        return 2
+
+    def pieces(self, dim, sizes=None):
+        """(start, length) along the axis of every piece."""
+        if sizes is not None:
+            sizes = [int(s) for s in sizes]
+            if any(s < 0 for s in sizes):
+                raise InvalidValue("Split sizes must be >= 0")
+            if sum(sizes) != dim:
+                raise InvalidValue("Split sizes do not sum to dimension size")
+            return [(sum(sizes[:k]), s) for k, s in enumerate(sizes)]
+        n = self.node_outputs if self.num_outputs is None else self.num_outputs
+        if n == 0:
+            raise InvalidValue("num_outputs must be > 0")
+        if n > dim:
+            raise InvalidValue("num_outputs exceeds dim size")
+        chunk = -(-dim // n)
+        return [(a, min(chunk, dim - a)) for a in range(0, dim, chunk)]
+
+    def run(self, ctx, inputs):
+        x = _require(inputs, 0)
+        nd = len(x.shape)
+        ax = _resolve_axis(nd, self.axis)
+        s = _get(inputs, 1)
+        pieces = self.pieces(x.shape[ax], None if s is None else _host_values(s).reshape(-1))
+        if x.dtype.itemsize != 4:
+            raise UnsupportedType
+        if nd > 6:
+            raise UnsupportedValue("Split: more than 6 dims on the device path")
+        strides = [int(np.prod(x.shape[d + 1:], dtype=np.int64)) for d in range(nd)]
+        outs = []
+        for start, length in pieces:
+            shape = list(x.shape)
+            shape[ax] = length
+            y = DeviceTensor(ctx, shape, x.dtype)
+            if y.size:
+                ctx.call("rten_hip_copy_strided_b32", nd, (C.c_int64 * nd)(*shape), (C.c_int64 * nd)(*strides), C.c_void_p(x.ptr + 4 * start * strides[ax]), y.vp)
+            outs.append(y)
+        return outs
+
+
 class OpRegistry:
     """Mirror of OpRegistry (src/op_registry.rs:25-72): op_type -> operator class for the hot path."""
 
@@ -1269,7 +1439,8 @@ class OpRegistry:
         r = cls()
         for op in (Conv, ConvTranspose, ConvInteger, ConvIntegerToFloat, MatMul, FusedMatMul, Gemm, MatMulInteger, MatMulIntegerToFloat, MatMulNBits,
                    Softmax, AddSoftmax, LayerNormalization, BatchNormalization, Relu, Gelu, Erf, Add, Mul, Sub, Div, Transpose, MaxPool,
-                   AveragePool, GlobalAveragePool, Flatten, DynamicQuantizeLinear, Attention, Gather, ReduceSum, ReduceMean, Einsum):
+                   AveragePool, GlobalAveragePool, Flatten, DynamicQuantizeLinear, Attention, Gather, ReduceSum, ReduceMean, Einsum, Resize, Upsample,
+                   Split):
             r.register_op(op)
         return r
 

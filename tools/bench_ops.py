@@ -146,6 +146,26 @@ def main():
     hbm("Conv pointwise, then standalone Silu", "32x96x112x112 -> 24",
         (lambda: (ctx.call("rten_hip_conv2d_f32", C.byref(dpw), xpw.vp, wpw.vp, 1, bpw.vp, None, 0, ypw.vp),
                   ctx.call("rten_hip_activation_f32", L.ACT_SILU, 0.0, 0.0, npw_out, ypw.vp, ypw.vp))), 4.0 * (npw_in + npw_out))
+    # Resize (rten_hip_resize_f32) at the sizes detectors and segmenters run it: YOLO's nearest 2x upsamplings at batch 32, a bilinear 2x
+    # upsampling, DeepLab's logit upsampling (65 -> 513, pytorch_half_pixel); each beside a device copy that moves the same bytes (in + out)
+    for label, (n_, c_, h_, w_), (oh_, ow_), mode, coord in (
+            ("Resize nearest 2x", (32, 256, 40, 40), (80, 80), L.RESIZE_MODE_NEAREST, L.RESIZE_COORD_ASYMMETRIC),
+            ("Resize nearest 2x", (32, 512, 20, 20), (40, 40), L.RESIZE_MODE_NEAREST, L.RESIZE_COORD_ASYMMETRIC),
+            ("Resize linear half_pixel 2x", (32, 256, 64, 64), (128, 128), L.RESIZE_MODE_LINEAR, L.RESIZE_COORD_HALF_PIXEL),
+            ("Resize linear pytorch_half_pixel (DeepLab logits)", (8, 21, 65, 65), (513, 513), L.RESIZE_MODE_LINEAR, L.RESIZE_COORD_PYTORCH_HALF_PIXEL)):
+        if not want(label) and not want("copy, " + label):
+            continue
+        n_in, n_out = n_ * c_ * h_ * w_, n_ * c_ * oh_ * ow_
+        xr, yr = dev(rng.standard_normal(n_in, dtype=np.float32)), empty((n_out,))
+        shape = f"{n_}x{c_}x{h_}x{w_} -> {oh_}x{ow_}"
+        hbm(label, shape, (lambda xr=xr, yr=yr, n_=n_, c_=c_, h_=h_, w_=w_, oh_=oh_, ow_=ow_, mode=mode, coord=coord: ctx.call(
+            "rten_hip_resize_f32", mode, coord, L.RESIZE_NEAREST_FLOOR, n_ * c_, h_, w_, oh_, ow_, h_ / oh_, w_ / ow_, xr.vp, yr.vp)), 4.0 * (n_in + n_out))
+        half = 2 * (n_in + n_out)  # bytes copied: read + write = the resize's input + output bytes
+        del xr
+        src = empty((half // 4,))
+        hbm(f"copy, {label} (reference point)", f"{half} B", (lambda src=src, yr=yr, half=half: ctx.call("rten_hip_memcpy_d2d", yr.vp, src.vp, C.c_size_t(half))),
+            4.0 * (n_in + n_out))
+        del src, yr
     # the SwiGLU gate projection of a decoder MLP: 4096 x 768 x 3072 with Silu in the epilogue
     xs, ws = dev(rng.standard_normal((4096, 768), dtype=np.float32)), dev(rng.standard_normal((768, 3072), dtype=np.float32))
     ys = empty((4096, 3072))

@@ -12,6 +12,7 @@ Test and tooling infrastructure only: nothing under rten_amd/ imports this.
     python tools/torch_export.py bert /tmp/bert_torch.onnx             # transformers.BertModel, random init, 2 layers (its mask
                                                                        # subgraph needs NonZero / Where / Expand: not loadable yet)
     python tools/torch_export.py mobile /tmp/mobile_torch.onnx         # small MobileNetV2 / V3 / EfficientNet-style network (activations)
+    python tools/torch_export.py yolo /tmp/yolo_torch.onnx             # small YOLOv8-style detector (Split, Resize, SPPF, DFL head)
 """
 from __future__ import annotations
 
@@ -225,6 +226,87 @@ def mobile_onnx(model=None, image: int = 32) -> bytes:
     return export_bytes(model, (torch.zeros(2, 3, image, image),), ["x"], ["logits"], {"x": {0: "batch"}, "logits": {0: "batch"}})
 
 
+def yolo_module(seed: int = 0, reg_max: int = 8, classes: int = 4):
+    """A small YOLOv8-style detector (the Ultralytics layout with BatchNorm folded): Conv + SiLU blocks, C2f blocks (a channel Split, a
+    bottleneck, Concat), SPPF (three 5x5 stride-1 max-pools), a top-down path of two nearest 2x upsamplings each followed by a Concat, and a DFL
+    box head (Reshape, Transpose, Softmax over axis 1, a 1x1 Conv whose weights are the bin indices) beside a Sigmoid class head.  The channel
+    splits are torch.split with constant sizes (`chunk` does not export through export_bytes)."""
+    import torch
+    from torch import nn
+    torch.manual_seed(seed)
+
+    class Conv(nn.Module):
+        def __init__(self, ci, co, k=1, s=1):
+            super().__init__()
+            self.conv, self.act = nn.Conv2d(ci, co, k, s, k // 2), nn.SiLU()
+
+        def forward(self, x):
+            return self.act(self.conv(x))
+
+    class Bottleneck(nn.Module):
+        def __init__(self, c, shortcut):
+            super().__init__()
+            self.cv1, self.cv2, self.add = Conv(c, c, 3), Conv(c, c, 3), shortcut
+
+        def forward(self, x):
+            y = self.cv2(self.cv1(x))
+            return x + y if self.add else y
+
+    class C2f(nn.Module):
+        def __init__(self, ci, co, shortcut=True):
+            super().__init__()
+            self.c = co // 2
+            self.cv1, self.cv2, self.m = Conv(ci, 2 * self.c), Conv(3 * self.c, co), Bottleneck(self.c, shortcut)
+
+        def forward(self, x):
+            a, b = torch.split(self.cv1(x), [self.c, self.c], 1)
+            return self.cv2(torch.cat([a, b, self.m(b)], 1))
+
+    class SPPF(nn.Module):
+        def __init__(self, ci, co):
+            super().__init__()
+            self.cv1, self.cv2, self.pool = Conv(ci, ci // 2), Conv(ci // 2 * 4, co), nn.MaxPool2d(5, 1, 2)
+
+        def forward(self, x):
+            x = self.cv1(x)
+            y1 = self.pool(x)
+            y2 = self.pool(y1)
+            return self.cv2(torch.cat([x, y1, y2, self.pool(y2)], 1))
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.stem, self.d1, self.d2 = Conv(3, 8, 3, 2), Conv(8, 16, 3, 2), Conv(16, 32, 3, 2)
+            self.c2f1, self.d3, self.sppf = C2f(32, 32), Conv(32, 64, 3, 2), SPPF(64, 64)
+            self.up = nn.Upsample(scale_factor=2, mode="nearest")
+            self.c2f2, self.c2f3 = C2f(64 + 32, 32, False), C2f(32 + 16, 16, False)
+            self.box, self.cls = nn.Conv2d(16, 4 * reg_max, 1), nn.Conv2d(16, classes, 1)
+            self.dfl = nn.Conv2d(reg_max, 1, 1, bias=False)
+            for m in self.modules():  # small weights: activations stay in the interesting range of SiLU / Softmax
+                if isinstance(m, nn.Conv2d):
+                    nn.init.normal_(m.weight, 0.0, 1.0 / (m.weight[0].numel() ** 0.5))
+            self.dfl.weight.data[:] = torch.arange(reg_max, dtype=torch.float32).view(1, reg_max, 1, 1)
+
+        def forward(self, x):
+            p3 = self.d1(self.stem(x))   # stride 4
+            p4 = self.c2f1(self.d2(p3))  # stride 8
+            p5 = self.sppf(self.d3(p4))  # stride 16
+            h4 = self.c2f2(torch.cat([self.up(p5), p4], 1))
+            h3 = self.c2f3(torch.cat([self.up(h4), p3], 1))
+            b, _, hh, ww = h3.shape
+            box = self.box(h3).view(b, 4, reg_max, hh * ww).transpose(2, 1).softmax(1)  # DFL: [b, bins, 4, anchors]
+            box = self.dfl(box).view(b, 4, hh * ww)
+            return torch.cat([box, self.cls(h3).view(b, classes, hh * ww).sigmoid()], 1)
+
+    return Net().eval()
+
+
+def yolo_onnx(model=None, image: int = 64) -> bytes:
+    import torch
+    model = model if model is not None else yolo_module()
+    return export_bytes(model, (torch.zeros(2, 3, image, image),), ["x"], ["y"], {"x": {0: "batch"}, "y": {0: "batch"}})
+
+
 if __name__ == "__main__":
     kind, path = sys.argv[1], sys.argv[2]
     if kind == "resnet50":
@@ -236,6 +318,8 @@ if __name__ == "__main__":
         data = encoder_onnx(cfg, Bw.make_weights(cfg), 32, 128)
     elif kind == "mobile":
         data = mobile_onnx()
+    elif kind == "yolo":
+        data = yolo_onnx()
     else:
         data = bert_onnx(bert_module())
     open(path, "wb").write(data)
