@@ -520,6 +520,30 @@ int32_t rten_hip_reduce_sum_strided_f32(rten_hip_ctx *ctx, int32_t n_outer, cons
 int32_t rten_hip_reduce_mean_strided_f32(rten_hip_ctx *ctx, int32_t n_outer, const int64_t *outer_shape, const int64_t *outer_strides,
                                          int32_t n_inner, const int64_t *inner_shape, const int64_t *inner_strides,
                                          const float *x, float *y);
+/* The selection family on strided views, float32 (RTEN_HIP_DT_F32) and int32 (RTEN_HIP_DT_I32) elements; kept dims and reduced dims as for
+ * rten_hip_reduce_sum_strided_f32 (<= 6 + 6, element strides, nothing is packed); no host read-back, capture-safe.
+ * ReduceMax / ReduceMin (reduce_max / reduce_min, src/ops/reduce.rs:414-520,876-1044): y[r] = extreme of the slice; a NaN anywhere in the slice gives
+ * the canonical quiet NaN; when the extreme is zero and zeros of both signs occur, +0 for max and -0 for min; an empty slice gives the identity
+ * (-inf / +inf, INT32_MIN / INT32_MAX).  y has x's element type. */
+#define RTEN_HIP_SELECT_MAX 0
+#define RTEN_HIP_SELECT_MIN 1
+int32_t rten_hip_reduce_minmax_strided(rten_hip_ctx *ctx, int32_t op, int32_t dtype, int32_t n_outer, const int64_t *outer_shape,
+                                       const int64_t *outer_strides, int32_t n_inner, const int64_t *inner_shape, const int64_t *inner_strides,
+                                       const void *x, void *y);
+/* ArgMax / ArgMin along one axis (arg_max / arg_min, src/ops/reduce.rs:64-215): Iterator::max_by with cmp_nan_greater -- the index of the FIRST NaN of
+ * the lane if it holds one (ArgMin too), otherwise of the LAST element equal to the extreme (+0 == -0).  axis_len == 0 is RTEN_HIP_ERR_INVALID_VALUE
+ * "Cannot select index from empty sequence". */
+int32_t rten_hip_arg_minmax_strided(rten_hip_ctx *ctx, int32_t op, int32_t dtype, int32_t n_outer, const int64_t *outer_shape,
+                                    const int64_t *outer_strides, int64_t axis_len, int64_t axis_stride, const void *x, int32_t *y);
+/* TopK along one axis (topk, src/ops/reduce.rs:1236-1356): per lane the k first (value, index) pairs in the order "NaN greater than every number whatever
+ * `largest` says; larger (largest != 0) or smaller value first; equal values by ascending index; several NaNs by ascending index", always sorted.
+ * The output lane of kept-dims coordinate c starts at sum(c[d] * outer_out_strides[d]) and steps by out_axis_stride, in `values` (x's element type,
+ * the input's own bits) and in `indices`.  k < 0: RTEN_HIP_ERR_INVALID_VALUE "k must be positive"; k > axis_len: "k > dimension size"; k == 0 writes
+ * nothing; k > 4096: RTEN_HIP_ERR_UNSUPPORTED.  A lane of up to 8192 elements is sorted by one workgroup; a longer one in chunks whose first k are merged
+ * (candidate lists in the context's scratch buffer). */
+int32_t rten_hip_topk_strided(rten_hip_ctx *ctx, int32_t largest, int32_t dtype, int32_t n_outer, const int64_t *outer_shape,
+                              const int64_t *outer_strides, const int64_t *outer_out_strides, int64_t axis_len, int64_t axis_stride, int64_t k,
+                              const void *x, void *values, int32_t *indices, int64_t out_axis_stride);
 /* y[(i / inner) ...] += bias[c]: per-channel bias add for NCHW tensors ([1,O,1,1] constant Add) */
 int32_t rten_hip_add_channel_bias_f32(rten_hip_ctx *ctx, int32_t n, int32_t c, int64_t inner, const float *x,
                                       const float *bias, float *y);

@@ -496,6 +496,42 @@ inline HostVal nonzero(const HostVal &x) { // src/ops/non_zero.rs: [rank, count]
     for (int d = 0; d < nd; d++) for (size_t c = 0; c < cols.size(); c++) out.i[(size_t)d * cols.size() + c] = cols[c][(size_t)d];
     return out;
 }
+// ReduceMax / ReduceMin of a host value over sorted unique `axes` (shape arithmetic sometimes takes the extreme of a shape vector): NaN propagates, an empty
+// slice gives the identity (src/ops/reduce.rs:414-520, 876-1044)
+inline HostVal reduce_minmax(const HostVal &x, const std::vector<int> &axes, bool keep_dims, bool min) {
+    const size_t nd = x.shape.size();
+    std::vector<int64_t> kept_stride(nd, 0);
+    HostVal y;
+    y.is_float = x.is_float;
+    int64_t acc = 1;
+    for (size_t d = nd; d-- > 0;) {
+        const bool red = std::find(axes.begin(), axes.end(), (int)d) != axes.end();
+        if (!red) { kept_stride[d] = acc; acc *= x.shape[d]; }
+    }
+    for (size_t d = 0; d < nd; d++) {
+        const bool red = std::find(axes.begin(), axes.end(), (int)d) != axes.end();
+        if (!red) y.shape.push_back(x.shape[d]);
+        else if (keep_dims) y.shape.push_back(1);
+    }
+    const float fid = min ? std::numeric_limits<float>::infinity() : -std::numeric_limits<float>::infinity();
+    const int64_t iid = min ? std::numeric_limits<int32_t>::max() : std::numeric_limits<int32_t>::min();
+    if (x.is_float) y.f.assign((size_t)acc, fid); else y.i.assign((size_t)acc, iid);
+    std::vector<int64_t> idx(nd, 0);
+    for (int64_t e = 0, n = x.len(); e < n; e++) {
+        int64_t o = 0;
+        for (size_t d = 0; d < nd; d++) o += idx[d] * kept_stride[d];
+        if (x.is_float) {
+            float &a = y.f[(size_t)o];
+            const float b = x.f[(size_t)e];
+            if (a != a) {} else if (b != b) a = std::numeric_limits<float>::quiet_NaN(); else a = min ? std::min(a, b) : std::max(a, b);
+        } else {
+            int64_t &a = y.i[(size_t)o];
+            a = min ? std::min(a, x.i[(size_t)e]) : std::max(a, x.i[(size_t)e]);
+        }
+        for (size_t d = nd; d-- > 0;) { if (++idx[d] < x.shape[d]) break; idx[d] = 0; }
+    }
+    return y;
+}
 } // namespace hostops
 
 // ======================================================================================================== executor
@@ -2158,6 +2194,58 @@ class Graph {
                 st.batch_coupled = op->axes.empty() ? !op->noop_with_empty_axes : std::count(op->axes.begin(), op->axes.end(), 0) != 0; // sums over dim 0
                 const std::string kind = n.op_type, nm = st.name;
                 st.run = [this, op, kind, nm](Context &c, const InputList &in) { for (int a : op->axes) note_axis(kind, nm, a, require(in, 0)); return op->run(c, in); };
+            } else if (n.op_type == "ReduceMax" || n.op_type == "ReduceMin") {
+                auto op = std::make_shared<ReduceMax>();
+                op->min = n.op_type == "ReduceMin";
+                op->keep_dims = n.get_int("keepdims", 1) != 0;
+                op->noop_with_empty_axes = n.get_int("noop_with_empty_axes", 0) != 0;
+                op->axes = n.get_ints("axes", {});
+                if (n.inputs.size() > 1 && !n.inputs[1].empty()) { // opset >= 18: axes as a (constant) input
+                    auto it = ids_.find(n.inputs[1]);
+                    if (it == ids_.end() || !consts_.count(it->second)) throw GraphError(n.op_type + " " + st.name + ": the axes input must be a constant");
+                    for (int32_t v : consts_.at(it->second).to_host<int32_t>()) op->axes.push_back(v);
+                    st.in.resize(1);
+                }
+                st.batch_coupled = op->axes.empty() ? !op->noop_with_empty_axes : std::count(op->axes.begin(), op->axes.end(), 0) != 0; // reduces over dim 0
+                const std::string kind = n.op_type, nm = st.name;
+                auto cache = std::make_shared<HostCache>();
+                st.run = [this, op, kind, nm, cache](Context &c, const InputList &in) {
+                    const Tensor &x = require(in, 0);
+                    for (int a : op->axes) note_axis(kind, nm, a, x);
+                    if (x.host() && x.ndim() > 0 && !(op->axes.empty() && op->noop_with_empty_axes)) { // shape arithmetic: on the host
+                        OutputList o;
+                        o.push_back(materialize(c, hostops::reduce_minmax(*x.host(), resolve_axes(op->axes, x.ndim()), op->keep_dims, op->min), *cache));
+                        return o;
+                    }
+                    return op->run(c, in);
+                };
+            } else if (n.op_type == "ArgMax" || n.op_type == "ArgMin") {
+                if (n.get_int("select_last_index", 0) != 0) throw GraphError(n.op_type + " " + st.name + ": select_last_index is not supported"); // onnx_registry.rs:769
+                auto op = std::make_shared<ArgMax>();
+                op->min = n.op_type == "ArgMin";
+                op->axis = (int)n.get_int("axis", 0);
+                op->keep_dims = n.get_int("keepdims", 1) != 0;
+                st.batch_coupled = op->axis == 0;
+                const std::string kind = n.op_type, nm = st.name;
+                st.run = [this, op, kind, nm](Context &c, const InputList &in) { note_axis(kind, nm, op->axis, require(in, 0)); return op->run(c, in); };
+            } else if (n.op_type == "TopK") {
+                auto op = std::make_shared<TopK>();
+                op->axis = (int)n.get_int("axis", -1);
+                op->largest = n.get_int("largest", 1) != 0;
+                op->sorted = n.get_int("sorted", 1) != 0;
+                if (n.inputs.size() < 2 || n.inputs[1].empty()) throw GraphError("TopK " + st.name + ": the K input is missing");
+                // K is read on the host (no read-back, so the step may be captured): an initializer, a Constant, or shape arithmetic the executor evaluates
+                // on the host.  A graph input is device data at run time: refused here; any other device-computed K is refused by the step when it runs.
+                for (auto &gi : m.inputs)
+                    if (gi.name == n.inputs[1] && !is_const(gi.name))
+                        throw GraphError("TopK " + st.name + ": K must be a constant or computable from the input shapes (it is the graph input \"" + gi.name + "\", device data at run time)");
+                st.batch_coupled = op->axis == 0;
+                const std::string nm = st.name;
+                st.run = [this, op, nm](Context &c, const InputList &in) {
+                    note_axis("TopK", nm, op->axis, require(in, 0));
+                    host_ints(&require(in, 1), "TopK: K"); // throws unless K carries a host value
+                    return op->run(c, in);
+                };
             } else if (n.op_type == "Softmax") {
                 auto op = std::make_shared<Softmax>();
                 op->axis = (int)n.get_int("axis", -1);

@@ -836,6 +836,15 @@ inline int resolve_axis(int axis, int ndim) { // resolve_axis (src/ops/mod.rs): 
     if (a < 0 || a >= ndim) throw OpError(OpError::InvalidValue, "Axis is invalid");
     return a;
 }
+// resolve_axes (src/ops/mod.rs:259-271): negative axes from the end, sorted, unique; none given = all
+inline std::vector<int> resolve_axes(const std::vector<int> &axes, int nd) {
+    std::vector<int> ax;
+    if (axes.empty()) for (int d = 0; d < nd; d++) ax.push_back(d);
+    for (int a : axes) ax.push_back(resolve_axis(a, nd));
+    std::sort(ax.begin(), ax.end());
+    ax.erase(std::unique(ax.begin(), ax.end()), ax.end());
+    return ax;
+}
 
 struct Softmax : Operator { // src/ops/norm.rs:825-840 (last-axis lanes contiguous: other axes need a transpose first)
     int axis = -1;
@@ -1941,8 +1950,8 @@ inline Shape broadcast(const Shape &a, const Shape &b, const char *msg) {
     return o;
 }
 
-inline Tensor materialize(Context &ctx, const View &v) { // to_tensor / to_contiguous / expand_to
-    Tensor y(ctx, v.shape, DType::F32);
+inline Tensor materialize(Context &ctx, const View &v, DType dt = DType::F32) { // to_tensor / to_contiguous / expand_to (any 4-byte element type)
+    Tensor y(ctx, v.shape, dt);
     if (y.len()) {
         Shape ms; std::vector<Shape> mst;
         merge_axes(v.shape, {v.strides}, ms, mst);
@@ -2174,11 +2183,7 @@ struct ReduceSum : Operator { // src/ops/reduce.rs:1126-1165 (f32); axes as the 
         const int nd = x.ndim();
         OutputList out;
         if ((axes.empty() && noop_with_empty_axes) || nd == 0) { out.push_back(E::materialize(ctx, E::View::of(x))); return out; }
-        std::vector<int> ax;
-        if (axes.empty()) for (int d = 0; d < nd; d++) ax.push_back(d);
-        for (int a : axes) ax.push_back(resolve_axis(a, nd));
-        std::sort(ax.begin(), ax.end());
-        ax.erase(std::unique(ax.begin(), ax.end()), ax.end()); // resolve_axes, src/ops/mod.rs:259-271
+        const std::vector<int> ax = resolve_axes(axes, nd);
         Tensor y = E::reduce_sum(ctx, E::View::of(x), ax, mean);
         if (keep_dims) {
             std::vector<int64_t> s = x.shape();
@@ -2192,6 +2197,154 @@ struct ReduceSum : Operator { // src/ops/reduce.rs:1126-1165 (f32); axes as the 
 
 struct ReduceMean : ReduceSum { // src/ops/reduce.rs:523-580: Sum / len per slice
     ReduceMean() { mean = true; }
+};
+
+// ------------------------------------------------------------------------------------------------ selection family
+// ReduceMax / ReduceMin / ArgMax / ArgMin / TopK (src/ops/reduce.rs:64-215, 876-1044, 1236-1356) of float32 and int32 tensors; index outputs are int32.
+// The kernels (rten_amd/csrc/select.hip) read the view in place through its strides and never report back to the host.
+namespace select_detail {
+inline int32_t abi_dtype(const Tensor &x) { // map_value_view!(.., [FloatTensor, Int32Tensor], ..)
+    if (x.dtype() == DType::F32) return RTEN_HIP_DT_F32;
+    if (x.dtype() == DType::I32) return RTEN_HIP_DT_I32;
+    throw OpError(OpError::UnsupportedType, "");
+}
+// an int32 operand the host reads (axes, K): its host copy when it has one, a read-back otherwise (a graph executor refuses that case before it gets here)
+inline std::vector<int64_t> host_ints(const Tensor &t) {
+    want(t, DType::I32, "int32");
+    if (t.host()) return t.host()->i;
+    std::vector<int64_t> v;
+    for (int32_t e : t.to_host<int32_t>()) v.push_back(e);
+    return v;
+}
+// kept / reduced dims of `v` as the merged shape + stride lists the ABI takes
+struct Split2 { einsum_detail::Shape kshape, mo, mi; std::vector<einsum_detail::Shape> mos, mis; };
+inline Split2 split_dims(const einsum_detail::View &v, const std::vector<int> &axes) {
+    namespace E = einsum_detail;
+    Split2 r;
+    E::Shape kst, rs, rst;
+    for (int d = 0; d < v.nd(); d++) {
+        const bool red = std::find(axes.begin(), axes.end(), d) != axes.end();
+        (red ? rs : r.kshape).push_back(v.shape[(size_t)d]);
+        (red ? rst : kst).push_back(v.strides[(size_t)d]);
+    }
+    E::merge_axes(r.kshape, {kst}, r.mo, r.mos);
+    E::merge_axes(rs, {rst}, r.mi, r.mis);
+    if (r.mo.size() > 6 || r.mi.size() > 6) throw OpError(OpError::UnsupportedValue, "more than 6 non-mergeable dims are not supported by the device path");
+    return r;
+}
+} // namespace select_detail
+
+struct ReduceMax : Operator { // src/ops/reduce.rs:977-1044; axes as the attribute or the second input
+    std::vector<int> axes;
+    bool keep_dims = true, noop_with_empty_axes = false, min = false;
+    const char *name() const override { return min ? "ReduceMin" : "ReduceMax"; }
+    int max_inputs() const override { return 2; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        namespace E = einsum_detail;
+        namespace S = select_detail;
+        const Tensor &x = require(in, 0);
+        std::vector<int> given = axes;
+        if (const Tensor *a = get(in, 1)) { given.clear(); for (int64_t e : S::host_ints(*a)) given.push_back((int)e); }
+        const int32_t dt = S::abi_dtype(x);
+        const int nd = x.ndim();
+        OutputList out;
+        if (given.empty() && noop_with_empty_axes) { out.push_back(E::materialize(ctx, E::View::of(x), x.dtype())); return out; }
+        if (nd == 0) { // a 0-d input returns itself (reduce.rs:425-428)
+            for (int a : given) resolve_axis(a, 0);
+            out.push_back(E::materialize(ctx, E::View::of(x), x.dtype()));
+            return out;
+        }
+        const std::vector<int> ax = resolve_axes(given, nd);
+        const E::View v = E::View::of(x);
+        const S::Split2 d = S::split_dims(v, ax);
+        Tensor y(ctx, d.kshape, x.dtype());
+        if (y.len())
+            ctx.check(rten_hip_reduce_minmax_strided(ctx.raw(), min ? RTEN_HIP_SELECT_MIN : RTEN_HIP_SELECT_MAX, dt, (int)d.mo.size(), d.mo.data(), d.mos[0].data(),
+                                                     (int)d.mi.size(), d.mi.data(), d.mis[0].data(), v.p, y.ptr()));
+        if (keep_dims) {
+            std::vector<int64_t> s = x.shape();
+            for (int a : ax) s[(size_t)a] = 1;
+            y.reshape(s);
+        }
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+
+struct ReduceMin : ReduceMax { // src/ops/reduce.rs:907-975
+    ReduceMin() { min = true; }
+};
+
+struct ArgMax : Operator { // src/ops/reduce.rs:64-160: the FIRST NaN of a lane that holds one, otherwise the LAST element equal to the extreme
+    int axis = 0;
+    bool keep_dims = true, min = false;
+    const char *name() const override { return min ? "ArgMin" : "ArgMax"; }
+    int max_inputs() const override { return 1; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        namespace E = einsum_detail;
+        namespace S = select_detail;
+        const Tensor &x = require(in, 0);
+        const int32_t dt = S::abi_dtype(x);
+        const int a = resolve_axis(axis, x.ndim());
+        if (x.size(a) == 0) throw OpError(OpError::InvalidValue, "Cannot select index from empty sequence");
+        const E::View v = E::View::of(x);
+        const S::Split2 d = S::split_dims(v, {a});
+        Tensor y(ctx, d.kshape, DType::I32);
+        if (y.len())
+            ctx.check(rten_hip_arg_minmax_strided(ctx.raw(), min ? RTEN_HIP_SELECT_MIN : RTEN_HIP_SELECT_MAX, dt, (int)d.mo.size(), d.mo.data(), d.mos[0].data(),
+                                                  v.shape[(size_t)a], v.strides[(size_t)a], v.p, (int32_t *)y.ptr()));
+        if (keep_dims) {
+            std::vector<int64_t> s = x.shape();
+            s[(size_t)a] = 1;
+            y.reshape(s);
+        }
+        OutputList out;
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+
+struct ArgMin : ArgMax { // src/ops/reduce.rs:162-215
+    ArgMin() { min = true; }
+};
+
+// TopK (src/ops/reduce.rs:1236-1356): inputs X, K (int32 scalar or one element); outputs values and int32 indices.  NaN is greater than every number
+// whatever `largest` says, equal values come by ascending index, the result is always sorted (`sorted` = 0 leaves the order unspecified in the reference).
+struct TopK : Operator {
+    int axis = -1;
+    bool largest = true, sorted = true;
+    const char *name() const override { return "TopK"; }
+    int max_inputs() const override { return 2; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        namespace E = einsum_detail;
+        namespace S = select_detail;
+        const Tensor &x = require(in, 0);
+        const std::vector<int64_t> kv = S::host_ints(require(in, 1));
+        if (kv.size() != 1) throw OpError(OpError::InvalidValue, "Expected scalar value");
+        const int64_t k = kv[0];
+        if (k < 0) throw OpError(OpError::InvalidValue, "k must be positive");
+        const int32_t dt = S::abi_dtype(x);
+        const int a = resolve_axis(axis, x.ndim());
+        std::vector<int64_t> oshape = x.shape();
+        oshape[(size_t)a] = k;
+        OutputList out;
+        out.emplace_back(ctx, oshape, x.dtype());
+        out.emplace_back(ctx, oshape, DType::I32);
+        if (k == 0) return out;
+        if (k > x.size(a)) throw OpError(OpError::InvalidValue, "k > dimension size");
+        if (out[0].len()) {
+            const E::View v = E::View::of(x), ov = E::View::of(out[0]);
+            E::Shape ks, kst, kost, mo;
+            std::vector<E::Shape> mos;
+            for (int d = 0; d < v.nd(); d++)
+                if (d != a) { ks.push_back(v.shape[(size_t)d]); kst.push_back(v.strides[(size_t)d]); kost.push_back(ov.strides[(size_t)d]); }
+            E::merge_axes(ks, {kst, kost}, mo, mos);
+            if (mo.size() > 6) throw OpError(OpError::UnsupportedValue, "more than 6 non-mergeable dims are not supported by the device path");
+            ctx.check(rten_hip_topk_strided(ctx.raw(), largest ? 1 : 0, dt, (int)mo.size(), mo.data(), mos[0].data(), mos[1].data(), v.shape[(size_t)a],
+                                            v.strides[(size_t)a], k, v.p, out[0].ptr(), (int32_t *)out[1].ptr(), ov.strides[(size_t)a]));
+        }
+        return out;
+    }
 };
 
 struct Einsum : Operator { // src/ops/einsum.rs:21-108
@@ -2280,6 +2433,11 @@ class OpRegistry {
         r.register_op<Resize>("Resize");
         r.register_op<Upsample>("Upsample");
         r.register_op<Split>("Split");
+        r.register_op<ReduceMax>("ReduceMax");
+        r.register_op<ReduceMin>("ReduceMin");
+        r.register_op<ArgMax>("ArgMax");
+        r.register_op<ArgMin>("ArgMin");
+        r.register_op<TopK>("TopK");
         return r;
     }
 

@@ -192,10 +192,10 @@ def _merge_axes(shape, *stride_sets):
     return [n for n, _ in merged], [[st[k] for _, st in merged] for k in range(len(stride_sets))]
 
 
-def materialize(ctx, v: View, shape=None) -> DeviceTensor:
-    """to_tensor / to_contiguous / expand_to: a contiguous tensor of `shape` (default: the view's own shape)."""
+def materialize(ctx, v: View, shape=None, dtype=np.float32) -> DeviceTensor:
+    """to_tensor / to_contiguous / expand_to: a contiguous tensor of `shape` (default: the view's own shape); `dtype`: any 4-byte element type."""
     v = v if shape is None else v.expanded(shape)
-    out = DeviceTensor(ctx, v.shape, np.float32)
+    out = DeviceTensor(ctx, v.shape, dtype)
     if v.size:
         msh, (mst,) = _merge_axes(v.shape, v.strides)
         if len(msh) > 6:

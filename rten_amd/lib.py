@@ -183,6 +183,9 @@ PROTOTYPES = {
     "rten_hip_capture_active": (_I32, [_VP]),
     "rten_hip_reduce_sum_strided_f32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_reduce_mean_strided_f32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
+    "rten_hip_reduce_minmax_strided": (_I32, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
+    "rten_hip_arg_minmax_strided": (_I32, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _I64, _VP, _VP]),
+    "rten_hip_topk_strided": (_I32, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _I64]),
     "rten_hip_conv_transpose_output_size": (_I32, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP]),
     "rten_hip_conv_transpose2d_f32": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "rten_hip_matmul_nbits_f32": (_I32, [_VP, _I64, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),

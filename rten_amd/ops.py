@@ -1208,6 +1208,16 @@ class Gather(Operator):
         return [out]
 
 
+def resolve_axes(nd, axes):
+    """resolve_axes (src/ops/mod.rs:259-271): negative axes count from the end, the result is sorted and unique."""
+    out = []
+    for a in axes:
+        if a < -nd or a >= nd:
+            raise InvalidValue("Axis is invalid")
+        out.append(a + nd if a < 0 else a)
+    return sorted(set(out))
+
+
 class ReduceSum(Operator):
     """src/ops/reduce.rs:1126-1165 (f32): axes attribute or second input already resolved by the caller into `axes`;
     the slice of every output element is summed in place through the view's strides, 16-lane vecmath::Sum order."""
@@ -1225,12 +1235,7 @@ class ReduceSum(Operator):
         nd = len(x.shape)
         if not self.axes and self.noop_with_empty_axes:
             return [E.materialize(ctx, E.View(x))]
-        axes = []
-        for a in (self.axes if self.axes else range(nd)):
-            if a < -nd or a >= nd:
-                raise InvalidValue("Axis is invalid")
-            axes.append(a + nd if a < 0 else a)
-        axes = sorted(set(axes))  # resolve_axes sorts and dedups (src/ops/mod.rs:259-271)
+        axes = resolve_axes(nd, self.axes if self.axes else range(nd))
         y = E.reduce_sum(ctx, E.View(x), axes, mean=self.mean) if nd else E.materialize(ctx, E.View(x))  # rank 0: Sum = Mean = x (slice of one)
         if self.keep_dims:
             y = y.reshape([1 if d in axes else x.shape[d] for d in range(nd)])
@@ -1240,6 +1245,156 @@ class ReduceSum(Operator):
 class ReduceMean(ReduceSum):
     """src/ops/reduce.rs:523-580: vecmath::Sum(slice) / len(slice) as f32 (an empty slice gives NaN)."""
     mean = True
+
+
+# ------------------------------------------------------------------------------------------ selection family
+SELECT_MAX, SELECT_MIN = 0, 1  # RTEN_HIP_SELECT_*
+_DT = {np.dtype(np.float32): 0, np.dtype(np.int32): 1}  # RTEN_HIP_DT_F32 / _I32
+
+
+def _select_view(x):
+    """(view, ABI dtype) of a float32 / int32 operand: a DeviceTensor, or an einsum.View of one (permuted / sliced: reduced in place)."""
+    from . import einsum as E
+    v = x if isinstance(x, E.View) else E.View(x)
+    if v.t.dtype not in _DT:
+        raise UnsupportedType
+    return v, _DT[v.t.dtype]
+
+
+def _host_ints(v):
+    """A host-side int32 operand (axes, K): numpy array, list or int -> flat list of ints; None stays None."""
+    return None if v is None else [int(a) for a in np.asarray(v).reshape(-1)]
+
+
+def _kept_and_reduced(v, axes):
+    from . import einsum as E
+    keep = [d for d in range(len(v.shape)) if d not in axes]
+    osh, (ost,) = E._merge_axes([v.shape[d] for d in keep], [v.strides[d] for d in keep])
+    ish, (ist,) = E._merge_axes([v.shape[d] for d in axes], [v.strides[d] for d in axes])
+    if len(osh) > 6 or len(ish) > 6:
+        raise UnsupportedValue("more than 6 non-mergeable dims are not supported by the device path")
+    return keep, osh, ost, ish, ist
+
+
+class ReduceMax(Operator):
+    """src/ops/reduce.rs:977-1044 (float32 and int32): axes attribute or host-side second input; a NaN in a slice gives NaN; an empty slice gives
+    the identity (-inf / i32::MIN; ReduceMin: +inf / i32::MAX).  The slice is read in place through the view's strides."""
+    op = SELECT_MAX
+
+    def __init__(self, axes=None, keep_dims=True, noop_with_empty_axes=False):
+        self.axes, self.keep_dims, self.noop_with_empty_axes = axes, keep_dims, noop_with_empty_axes
+
+    def max_inputs(self):
+        return 2
+
+    def run(self, ctx, inputs):
+        from . import einsum as E
+        v, dt = _select_view(_require(inputs, 0))
+        axes = _host_ints(_get(inputs, 1))
+        axes = list(self.axes) if axes is None and self.axes is not None else axes
+        nd = len(v.shape)
+        copy = lambda: [E.materialize(ctx, v, dtype=v.t.dtype)]
+        if not axes and self.noop_with_empty_axes:
+            return copy()
+        if nd == 0:
+            resolve_axes(0, axes or [])
+            return copy()  # a 0-d input returns itself (reduce.rs:425-428)
+        axes = resolve_axes(nd, axes if axes else range(nd))
+        keep, osh, ost, ish, ist = _kept_and_reduced(v, axes)
+        y = DeviceTensor(ctx, [v.shape[d] for d in keep], v.t.dtype)
+        if y.size:
+            ctx.call("rten_hip_reduce_minmax_strided", self.op, dt, len(osh), E._i64(osh), E._i64(ost), len(ish), E._i64(ish), E._i64(ist), v.t.vp, y.vp)
+        if self.keep_dims:
+            y = y.reshape([1 if d in axes else v.shape[d] for d in range(nd)])
+        return [y]
+
+
+class ReduceMin(ReduceMax):
+    """src/ops/reduce.rs:907-975."""
+    op = SELECT_MIN
+
+
+class ArgMax(Operator):
+    """src/ops/reduce.rs:64-160: int32 index along `axis` following Iterator::max_by with cmp_nan_greater -- the FIRST NaN if the lane holds
+    one, otherwise the LAST element equal to the extreme.  select_last_index != 0 is refused as by the reference's loader (onnx_registry.rs:769)."""
+    op = SELECT_MAX
+
+    def __init__(self, axis=0, keep_dims=True, select_last_index=0):
+        if select_last_index:
+            raise UnsupportedValue("select_last_index is not supported")
+        self.axis, self.keep_dims = axis, keep_dims
+
+    def max_inputs(self):
+        return 1
+
+    def run(self, ctx, inputs):
+        from . import einsum as E
+        v, dt = _select_view(_require(inputs, 0))
+        nd = len(v.shape)
+        if self.axis < -nd or self.axis >= nd:
+            raise InvalidValue("Axis is invalid")
+        ax = self.axis + nd if self.axis < 0 else self.axis
+        if v.shape[ax] == 0:
+            raise InvalidValue("Cannot select index from empty sequence")
+        keep, osh, ost, _, _ = _kept_and_reduced(v, [ax])
+        y = DeviceTensor(ctx, [v.shape[d] for d in keep], np.int32)
+        if y.size:
+            ctx.call("rten_hip_arg_minmax_strided", self.op, dt, len(osh), E._i64(osh), E._i64(ost), v.shape[ax], v.strides[ax], v.t.vp, y.vp)
+        if self.keep_dims:
+            y = y.reshape([1 if d == ax else v.shape[d] for d in range(nd)])
+        return [y]
+
+
+class ArgMin(ArgMax):
+    """src/ops/reduce.rs:162-215."""
+    op = SELECT_MIN
+
+
+class TopK(Operator):
+    """src/ops/reduce.rs:1236-1356: inputs X, K (host-side int32 scalar or 1-element vector); outputs values (X's type) and int32 indices.  NaN is
+    greater than every number whatever `largest` says; equal values by ascending index.  The result is always sorted (with sorted == 0 the reference
+    leaves an unspecified order of the same pairs)."""
+
+    def __init__(self, axis=-1, largest=True, sorted=True):
+        self.axis, self.largest, self.sorted = axis, largest, sorted
+
+    def max_inputs(self):
+        return 2
+
+    def run(self, ctx, inputs):
+        from . import einsum as E
+        v, dt = _select_view(_require(inputs, 0))
+        kv = _host_ints(_require(inputs, 1))
+        if len(kv) != 1:
+            raise InvalidValue("Expected scalar value")
+        k = kv[0]
+        if k < 0:
+            raise InvalidValue("k must be positive")
+        nd = len(v.shape)
+        axis = -1 if self.axis is None else self.axis
+        if axis < -nd or axis >= nd:
+            raise InvalidValue("Axis is invalid")
+        ax = axis + nd if axis < 0 else axis
+        out_shape = [k if d == ax else v.shape[d] for d in range(nd)]
+        values, indices = DeviceTensor(ctx, out_shape, v.t.dtype), DeviceTensor(ctx, out_shape, np.int32)
+        if k == 0:
+            return [values, indices]
+        if k > v.shape[ax]:
+            raise InvalidValue("k > dimension size")
+        if values.size:
+            ov = E.View(values)
+            keep = [d for d in range(nd) if d != ax]
+            osh, (ost, oost) = E._merge_axes([v.shape[d] for d in keep], [v.strides[d] for d in keep], [ov.strides[d] for d in keep])
+            if len(osh) > 6:
+                raise UnsupportedValue("more than 6 non-mergeable dims are not supported by the device path")
+            try:
+                ctx.call("rten_hip_topk_strided", 1 if self.largest else 0, dt, len(osh), E._i64(osh), E._i64(ost), E._i64(oost), v.shape[ax], v.strides[ax],
+                         k, v.t.vp, values.vp, indices.vp, ov.strides[ax])
+            except L.HipError as e:
+                if e.code == L.ERR_UNSUPPORTED:
+                    raise UnsupportedValue(e.msg)
+                raise
+        return [values, indices]
 
 
 class Einsum(Operator):
@@ -1440,7 +1595,7 @@ class OpRegistry:
         for op in (Conv, ConvTranspose, ConvInteger, ConvIntegerToFloat, MatMul, FusedMatMul, Gemm, MatMulInteger, MatMulIntegerToFloat, MatMulNBits,
                    Softmax, AddSoftmax, LayerNormalization, BatchNormalization, Relu, Gelu, Erf, Add, Mul, Sub, Div, Transpose, MaxPool,
                    AveragePool, GlobalAveragePool, Flatten, DynamicQuantizeLinear, Attention, Gather, ReduceSum, ReduceMean, Einsum, Resize, Upsample,
-                   Split):
+                   Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK):
             r.register_op(op)
         return r
 

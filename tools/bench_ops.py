@@ -219,6 +219,33 @@ def main():
     yc = empty((3072,))
     hbm("ReduceSum strided axis", "4096x3072 -> 3072", (lambda: ctx.call("rten_hip_reduce_sum_strided_f32", 1, i64(3072), i64(1), 1, i64(4096), i64(3072), xc.vp, yc.vp)),
         4.0 * (4096 * 3072 + 3072))
+    # ---- the selection family (rten_amd/csrc/select.hip): ReduceMax on the two ReduceSum shapes above (its yardstick is the ReduceSum row of the same run),
+    # ArgMax over the channels of a segmentation map and over logits rows, a whole-tensor ReduceMax (yardstick: a device copy of the input's size), TopK.
+    # bytes = input once + output once.
+    hbm("ReduceMax last axis", "49152x128", (lambda: ctx.call("rten_hip_reduce_minmax_strided", 0, 0, 1, i64(49152), i64(128), 1, i64(128), i64(1), xr.vp, yr.vp)),
+        4.0 * (49152 * 128 + 49152))
+    hbm("ReduceMax strided axis", "4096x3072 -> 3072", (lambda: ctx.call("rten_hip_reduce_minmax_strided", 0, 0, 1, i64(3072), i64(1), 1, i64(4096), i64(3072), xc.vp, yc.vp)),
+        4.0 * (4096 * 3072 + 3072))
+    xs = dev(rng.standard_normal((1, 21, 512, 512), dtype=np.float32))
+    ys = empty((512 * 512,), np.int32)
+    hbm("ArgMax over channels", "1x21x512x512", (lambda: ctx.call("rten_hip_arg_minmax_strided", 0, 0, 1, i64(512 * 512), i64(1), 21, 512 * 512, xs.vp, ys.vp)),
+        4.0 * (21 * 512 * 512 + 512 * 512))
+    hbm("copy, ArgMax over channels' size (reference point)", f"{4 * 21 * 512 * 512} B",
+        (lambda: ctx.call("rten_hip_memcpy_d2d", xc.vp, xs.vp, C.c_size_t(4 * 21 * 512 * 512))), 8.0 * 21 * 512 * 512)
+    xl = dev(rng.standard_normal((32, 1000), dtype=np.float32))
+    yl = empty((32,), np.int32)
+    hbm("ArgMax last axis", "32x1000", (lambda: ctx.call("rten_hip_arg_minmax_strided", 0, 0, 1, i64(32), i64(1000), 1000, 1, xl.vp, yl.vp)), 4.0 * (32 * 1000 + 32))
+    hbm("copy, ArgMax last axis' size (reference point)", f"{4 * 32 * 1000} B", (lambda: ctx.call("rten_hip_memcpy_d2d", xc.vp, xl.vp, C.c_size_t(4 * 32 * 1000))), 8.0 * 32 * 1000)
+    nw = 32 * 64 * 112 * 112
+    xw = dev(rng.standard_normal((nw,), dtype=np.float32))
+    xw2 = empty((nw,))
+    hbm("ReduceMax whole tensor", "32x64x112x112", (lambda: ctx.call("rten_hip_reduce_minmax_strided", 0, 0, 0, i64(), i64(), 1, i64(nw), i64(1), xw.vp, yl.vp)), 4.0 * (nw + 1))
+    hbm("copy, ReduceMax whole tensor's size (reference point)", f"{4 * nw} B", (lambda: ctx.call("rten_hip_memcpy_d2d", xw2.vp, xw.vp, C.c_size_t(4 * nw))), 8.0 * nw)
+    for (lanes_t, len_t, k_t, shape_t) in ((32, 1000, 5, "32x1000, k=5"), (8, 8400, 300, "8x8400, k=300"), (1, 151936, 50, "1x151936, k=50"), (32 * 128, 128, 8, "32x128x128, k=8")):
+        xt = dev(rng.standard_normal((lanes_t, len_t), dtype=np.float32))
+        vt, it = empty((lanes_t, k_t)), empty((lanes_t, k_t), np.int32)
+        hbm("TopK", shape_t, (lambda xt=xt, vt=vt, it=it, lanes_t=lanes_t, len_t=len_t, k_t=k_t: ctx.call(
+            "rten_hip_topk_strided", 1, 0, 1, i64(lanes_t), i64(len_t), i64(k_t), len_t, 1, k_t, xt.vp, vt.vp, it.vp, 1)), 4.0 * lanes_t * len_t)
     Be, Se, He, De = 32, 128, 12, 64
     qe, ke, ve = (dev(rng.standard_normal((Be, Se, He, De), dtype=np.float32)) for _ in range(3))
     pe = dev(rng.standard_normal((Be, He, Se, Se), dtype=np.float32))

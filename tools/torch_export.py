@@ -13,6 +13,9 @@ Test and tooling infrastructure only: nothing under rten_amd/ imports this.
                                                                        # subgraph needs NonZero / Where / Expand: not loadable yet)
     python tools/torch_export.py mobile /tmp/mobile_torch.onnx         # small MobileNetV2 / V3 / EfficientNet-style network (activations)
     python tools/torch_export.py yolo /tmp/yolo_torch.onnx             # small YOLOv8-style detector (Split, Resize, SPPF, DFL head)
+    python tools/torch_export.py classifier_topk /tmp/cls_topk.onnx    # the mobile network + softmax(-1) + topk(5)
+    python tools/torch_export.py segment_argmax /tmp/seg_argmax.onnx   # mobile features + class conv + bilinear interpolate + argmax(1)
+    python tools/torch_export.py yolo_filter /tmp/yolo_filter.onnx     # the detector + scores.max(1) + topk over anchors + Gather by index
 """
 from __future__ import annotations
 
@@ -307,6 +310,92 @@ def yolo_onnx(model=None, image: int = 64) -> bytes:
     return export_bytes(model, (torch.zeros(2, 3, image, image),), ["x"], ["y"], {"x": {0: "batch"}, "y": {0: "batch"}})
 
 
+def classifier_topk_module(seed: int = 0):
+    """The mobile network as an ImageNet-style classifier that finishes in the graph: softmax(-1), then topk(5).  Outputs: the probabilities (the
+    pre-selection tensor), the five values and their indices."""
+    import torch
+    from torch import nn
+    body = mobile_module(seed=seed)
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.body = body
+
+        def forward(self, x):
+            probs = self.body(x).softmax(-1)
+            values, indices = torch.topk(probs, 5)
+            return probs, values, indices
+
+    return Net().eval()
+
+
+def classifier_topk_onnx(model=None, image: int = 32) -> bytes:
+    import torch
+    model = model if model is not None else classifier_topk_module()
+    names = ["probs", "values", "indices"]
+    return export_bytes(model, (torch.zeros(2, 3, image, image),), ["x"], names, {n: {0: "batch"} for n in ["x"] + names})
+
+
+def segment_argmax_module(seed: int = 0, classes: int = 21):
+    """A DeepLab-style segmentation head on the mobile network's features: a 1x1 class convolution at stride 4, bilinear interpolation back to the
+    input size, argmax over the (strided) channel axis.  Outputs: the class map [b, classes, h, w] (the pre-selection tensor) and the labels [b, h, w]."""
+    import torch
+    from torch import nn
+    import torch.nn.functional as F
+    features = mobile_module(seed=seed).body[:8]  # through the second squeeze-excite block: 24 channels at stride 4
+    torch.manual_seed(seed + 1)
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.features, self.head = features, nn.Conv2d(24, classes, 1)
+
+        def forward(self, x):
+            logits = F.interpolate(self.head(self.features(x)), size=x.shape[2:], mode="bilinear", align_corners=False)
+            return logits, logits.argmax(1)
+
+    return Net().eval()
+
+
+def segment_argmax_onnx(model=None, image: int = 32) -> bytes:
+    import torch
+    model = model if model is not None else segment_argmax_module()
+    names = ["logits", "labels"]
+    return export_bytes(model, (torch.zeros(2, 3, image, image),), ["x"], names, {n: {0: "batch"} for n in ["x"] + names})
+
+
+def yolo_filter_module(seed: int = 0, keep: int = 20, classes: int = 4, batch: int = 2):
+    """The YOLO-style detector with the usual score filter in the graph: the best class score of every anchor (`scores.max(1)`: ReduceMax + ArgMax), the
+    `keep` best anchors (TopK over the anchor axis), and their boxes / classes fetched by the returned indices (per image `index_select`: Gather along the
+    anchor axis).  Outputs: the detector's own [b, 4 + classes, anchors] tensor (pre-selection), the per-anchor confidence, the kept scores, their anchor
+    indices, the kept boxes [b, 4, keep] and classes [b, keep].  The batch is static (the gathers are per image)."""
+    import torch
+    from torch import nn
+    body = yolo_module(seed=seed, classes=classes)
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.body = body
+
+        def forward(self, x):
+            y = self.body(x)
+            conf, cls = y[:, 4:, :].max(1)
+            top, idx = conf.topk(keep, dim=1)
+            boxes = torch.stack([torch.index_select(y[i, :4, :], 1, idx[i]) for i in range(batch)], 0)
+            kept_cls = torch.stack([torch.index_select(cls[i], 0, idx[i]) for i in range(batch)], 0)
+            return y, conf, top, idx, boxes, kept_cls
+
+    return Net().eval()
+
+
+def yolo_filter_onnx(model=None, image: int = 64, batch: int = 2) -> bytes:
+    import torch
+    model = model if model is not None else yolo_filter_module(batch=batch)
+    return export_bytes(model, (torch.zeros(batch, 3, image, image),), ["x"], ["y", "conf", "top", "idx", "boxes", "classes"])
+
+
 if __name__ == "__main__":
     kind, path = sys.argv[1], sys.argv[2]
     if kind == "resnet50":
@@ -320,6 +409,12 @@ if __name__ == "__main__":
         data = mobile_onnx()
     elif kind == "yolo":
         data = yolo_onnx()
+    elif kind == "classifier_topk":
+        data = classifier_topk_onnx()
+    elif kind == "segment_argmax":
+        data = segment_argmax_onnx()
+    elif kind == "yolo_filter":
+        data = yolo_filter_onnx()
     else:
         data = bert_onnx(bert_module())
     open(path, "wb").write(data)
