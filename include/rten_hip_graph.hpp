@@ -5,11 +5,14 @@
 //   * onnx::parse        rten-onnx/src/onnx.rs (hand-rolled protobuf reader, same subset: ModelProto / GraphProto /
 //                        NodeProto / AttributeProto / TensorProto / ValueInfoProto), src/model/onnx_loader.rs
 //                        (int64 initializers are narrowed to int32 at load, onnx_loader.rs:332-339).
-//   * Graph::compile     Graph::prepack_weights (src/graph.rs:488-562: constant conv weights are staged once) and the
-//                        fusion passes that touch this backend's operators (src/optimize/fusions.rs):
-//                        Conv (+ Add residual) (+ Relu); ConvInteger -> Cast -> Mul(scale) (= ConvIntegerToFloat,
-//                        fusions.rs:1012-1058) (+ Add bias [1,O,1,1]) (+ Add residual) (+ Relu); MatMulInteger -> Cast -> Mul
-//                        (= MatMulIntegerToFloat); Reshape / Flatten / Squeeze / Unsqueeze / Identity as views.
+//   * Graph::compile     Graph::prepack_weights (src/graph.rs:488-562: constant conv weights are staged once; prepacked_weight) and the
+//                        fusion passes that touch this backend's operators (src/optimize/fusions.rs), each in one member:
+//                        make_conv_step: Conv (+ Add residual) (+ Relu | activation); make_conv_integer_step: ConvInteger -> Cast -> Mul(scale)
+//                        (= ConvIntegerToFloat, fusions.rs:1012-1058) (+ Add bias [1,O,1,1]) (+ Add residual) (+ Relu); make_matmul_integer_step:
+//                        MatMulInteger -> Cast -> Mul (= MatMulIntegerToFloat); make_matmul_step: MatMul (+ scalar Mul / Div) (+ Add bias)
+//                        (+ Gelu | Relu | activation) (= FusedMatMul); make_add_norm_step: Add -> LayerNormalization, Add -> Softmax;
+//                        plan_attention / emit_attention: the attention subgraph as MultiHeadSdpa; make_view_step: Reshape / Flatten / Squeeze /
+//                        Unsqueeze / Identity as views.  compile() itself is the table of contents: it walks the nodes and dispatches to these.
 //   * Graph::run         Graph::run_plan (src/graph.rs:1139-1231): operators run sequentially in plan order, values are
 //                        reference counted and their buffers go back to the pool when the last consumer has run
 //                        (buffer_pool.rs); here every value stays in HBM between operators -- only graph inputs and
@@ -884,6 +887,19 @@ class Graph {
         return fused;
     }
 
+    // ---- what the step-level passes below ask of steps_
+    bool is_graph_output(int id) const {
+        for (auto &o : outputs_) if (ids_.at(o.name) == id) return true;
+        return false;
+    }
+    void index_steps(std::map<int, size_t> &producer, std::map<int, std::vector<size_t>> &consumers) const {
+        for (size_t i = 0; i < steps_.size(); i++) {
+            for (int id : steps_[i].out) if (id >= 0) producer[id] = i;
+            for (int id : steps_[i].in) if (id >= 0) consumers[id].push_back(i);
+        }
+    }
+    void erase_removed_steps() { steps_.erase(std::remove_if(steps_.begin(), steps_.end(), [](const Step &st) { return st.removed; }), steps_.end()); }
+
     // The staged int8 pipeline at graph level.  A DynamicQuantizeLinear whose codes feed only int8
     // convolutions of one padding geometry writes them straight into the kernel's staged layout; if its input is the f32
     // output of a fused ConvIntegerToFloat step or of a MaxPool, that launch accumulates the min/max the quantizer needs
@@ -891,19 +907,14 @@ class Graph {
     void plan_int8_staging() {
         std::map<int, size_t> producer;
         std::map<int, std::vector<size_t>> consumers;
-        for (size_t i = 0; i < steps_.size(); i++) {
-            for (int id : steps_[i].out) if (id >= 0) producer[id] = i;
-            for (int id : steps_[i].in) if (id >= 0) consumers[id].push_back(i);
-        }
+        index_steps(producer, consumers);
         struct Pending { size_t dql; size_t producer; };
         std::vector<Pending> want_stats;
         for (size_t i = 0; i < steps_.size(); i++) {
             Step &dq = steps_[i];
             if (dq.kind_name != "DynamicQuantizeLinear" || dq.out.size() < 3 || dq.out[0] < 0 || dq.i8) continue;
-            bool graph_out = false;
-            for (auto &o : outputs_) if (ids_.at(o.name) == dq.out[0]) graph_out = true;
             const auto &users = consumers[dq.out[0]];
-            if (graph_out || users.empty()) continue;
+            if (is_graph_output(dq.out[0]) || users.empty()) continue;
             bool ok = true;
             const Step *first = nullptr;
             for (size_t u : users) {
@@ -920,7 +931,7 @@ class Graph {
             op->kernel = consts_.at(first->in[1]).shape();
             for (size_t u : users) steps_[u].i8->sg.x_staged = true;
             dq.kind_name = "DynamicQuantizeLinear(staged)";
-            dq.run = [op](Context &c, const InputList &in) { return op->run(c, in); };
+            run_plainly(dq, op);
             dq.dql_staged = op;
             staged_dql_++;
             // fold the following Mul(y_scale, constant scalar) nodes -- one per convolution that reads the codes -- into the quantizer (same f32
@@ -931,9 +942,7 @@ class Graph {
                 if (mu.kind_name != "Mul" || mu.in.size() != 2 || mu.removed) continue;
                 const int other = mu.in[0] == dq.out[1] ? mu.in[1] : mu.in[0];
                 if (other == dq.out[1] || !consts_.count(other) || consts_.at(other).len() != 1 || consts_.at(other).dtype() != DType::F32) continue;
-                bool is_out = false;
-                for (auto &o : outputs_) if (ids_.at(o.name) == mu.out[0]) is_out = true;
-                if (is_out) continue;
+                if (is_graph_output(mu.out[0])) continue;
                 op->mul_by.push_back(&consts_.at(other));
                 dq.out.push_back(mu.out[0]);
                 mu.removed = true;
@@ -945,7 +954,7 @@ class Graph {
                 want_stats.push_back({i, p->second});
         }
         // (indices into steps_ stay valid until here; drop the absorbed Mul steps last)
-        struct Eraser { std::vector<Step> &v; ~Eraser() { v.erase(std::remove_if(v.begin(), v.end(), [](const Step &s) { return s.removed; }), v.end()); } } eraser{steps_};
+        struct Eraser { Graph &g; ~Eraser() { g.erase_removed_steps(); } } eraser{*this};
         if (want_stats.empty()) return;
         const size_t sb = rten_hip_minmax_stats_bytes();
         std::map<size_t, size_t> block_of; // producer step -> block
@@ -978,8 +987,7 @@ class Graph {
         ctx_.check(rten_hip_grid_sync_reset(ctx_.raw(), sync_arena_->ptr(), (int32_t)edges.size()));
         for (size_t e = 0; e < edges.size(); e++) {
             Step &P = steps_[edges[e].producer], &D = steps_[edges[e].dql];
-            bool keep = consumers[D.in[0]].size() > 1;
-            for (auto &o : outputs_) if (ids_.at(o.name) == D.in[0]) keep = true;
+            const bool keep = consumers[D.in[0]].size() > 1 || is_graph_output(D.in[0]);
             const bool recompute = !opt_.qout.count(P.name); // (listed under "qout2" only: no exchange block is used)
             void *sync = recompute ? nullptr : (char *)sync_arena_->ptr() + gb * e;
             auto state = P.i8;
@@ -1049,8 +1057,7 @@ class Graph {
             Step *Dp = nullptr;
             const Tensor *pd = nullptr;
             if (opt_.pair_shortcuts.count(A.name) && A.in[3] >= 0) {
-                size_t readers = 0;
-                for (auto &o : outputs_) if (ids_.at(o.name) == A.in[3]) readers += 2;
+                size_t readers = is_graph_output(A.in[3]) ? 2 : 0; // (a graph output is never the one reader's alone)
                 for (auto &st : steps_) if (!st.removed) for (int id : st.in) if (id == A.in[3]) readers++;
                 for (size_t k = 0; k < i && readers == 1; k++) {
                     Step &c = steps_[k];
@@ -1125,7 +1132,7 @@ class Graph {
             conv_pairs_++;
             if (Dp) { Dp->removed = true; fused_away_++; conv_pairs_++; A.kind_name = Dp->kind_name + "+" + A.kind_name; }
         }
-        steps_.erase(std::remove_if(steps_.begin(), steps_.end(), [](const Step &st) { return st.removed; }), steps_.end());
+        erase_removed_steps();
     }
     // Opt-in per layer (Options::fused_dql, the runner's `fused_layers`): a pointwise ConvIntegerToFloat step whose input comes from a staged
     // quantizer with producer statistics reads the quantizer's f32 INPUT and quantizes in its own operand loader (rten_hip_conv2d_int8_dql:
@@ -1134,7 +1141,8 @@ class Graph {
     void plan_dql_loaders() {
         if (opt_.fused_dql.empty()) return;
         std::map<int, size_t> producer;
-        for (size_t i = 0; i < steps_.size(); i++) for (int id : steps_[i].out) if (id >= 0) producer[id] = i;
+        std::map<int, std::vector<size_t>> consumers;
+        index_steps(producer, consumers);
         for (size_t i = 0; i < steps_.size(); i++) {
             Step &cs = steps_[i];
             if (!cs.i8 || !cs.i8->to_float || cs.i8->qout_producer || !opt_.fused_dql.count(cs.name) || !cs.i8->sg.x_staged || !cs.i8->sg.packed_weight || !cs.i8->sg.packed_weight->len()) continue;
@@ -1198,10 +1206,10 @@ class Graph {
                 if (&st == &D || st.removed) continue;
                 for (int id : st.in) for (int o : D.out) if (id >= 0 && id == o) read = true;
             }
-            for (auto &o : outputs_) for (int oid : D.out) if (ids_.at(o.name) == oid) read = true;
+            for (int oid : D.out) if (is_graph_output(oid)) read = true;
             if (!read) { D.removed = true; fused_away_++; }
         }
-        steps_.erase(std::remove_if(steps_.begin(), steps_.end(), [](const Step &st) { return st.removed; }), steps_.end());
+        erase_removed_steps();
     }
     uint64_t graph_ = 0;
     std::vector<Tensor> captured_outputs_;
@@ -1505,8 +1513,6 @@ class Graph {
                 scale->op_type.clear(); erf->op_type.clear(); add->op_type.clear(); mul->op_type.clear();
                 last = g;
                 index();
-            } else if (last.op_type == "Add" || last.op_type == "Mul") {
-                continue;
             }
         }
         for (size_t i = 0; i < m.nodes.size(); i++) { // ---- LayerNormalization: anchored at the scaling Mul
@@ -1564,349 +1570,355 @@ class Graph {
         return m;
     }
 
-    // ---- compile: constants, fusion, steps, liveness
+    // ---- what the fusion matchers ask of the ONNX node list.  `dead`: nodes an earlier step has taken.  A fused step runs at the position of the LAST node it
+    //      absorbs (st.pos), where -- the node list being topologically sorted -- every operand of every absorbed node is already available.
+    struct Nodes {
+        Graph &g;
+        const onnx::Model &m;
+        std::map<std::string, std::vector<size_t>> users; // consumers of every value
+        std::map<std::string, size_t> producer;
+        std::set<std::string> graph_outs; // graph outputs count as a use: they must not be fused away
+        std::vector<bool> dead;
+        Nodes(Graph &g_, const onnx::Model &m_) : g(g_), m(m_), dead(m_.nodes.size(), false) {
+            for (size_t i = 0; i < m.nodes.size(); i++) {
+                for (auto &s : m.nodes[i].inputs) if (!s.empty()) users[s].push_back(i);
+                for (auto &s : m.nodes[i].outputs) if (!s.empty()) producer[s] = i;
+            }
+            for (auto &o : m.outputs) graph_outs.insert(o.name);
+        }
+        const onnx::Node &operator[](long i) const { return m.nodes[(size_t)i]; }
+        // the one live node reading v, unless v is a graph output; -1 otherwise
+        long sole_reader(const std::string &v) const {
+            if (graph_outs.count(v)) return -1;
+            auto it = users.find(v);
+            if (it == users.end() || it->second.size() != 1 || dead.at(it->second[0])) return -1;
+            return (long)it->second[0];
+        }
+        long sole_user(const std::string &v, const char *op) const { const long u = sole_reader(v); return u >= 0 && m.nodes[(size_t)u].op_type == op ? u : -1; }
+        // the sole consumer of v if it is an activation activation_of takes (and not a graph output); -1 otherwise
+        long sole_activation(const std::string &v, Activation &a) const {
+            const long u = sole_reader(v);
+            if (u < 0) return -1;
+            const onnx::Node &un = m.nodes[(size_t)u];
+            return un.inputs.size() >= 1 && un.inputs[0] == v && g.activation_of(un, a) ? u : -1;
+        }
+        // the live `op` node producing v, if v has one reader and is not a graph output; -1 otherwise
+        long made_by(const std::string &v, const char *op) const {
+            auto it = producer.find(v);
+            if (it == producer.end() || dead[it->second] || m.nodes[it->second].op_type != op || graph_outs.count(v)) return -1;
+            auto us = users.find(v);
+            return us != users.end() && us->second.size() == 1 ? (long)it->second : -1;
+        }
+        // An Add of two operator outputs is claimed by the LATER producer only (its other operand exists before that producer runs), so two
+        // convolutions feeding one Add (projection shortcut + main branch) do not both absorb it.
+        bool ready_before(const std::string &v, size_t at) const { auto it = producer.find(v); return it == producer.end() || it->second < at; }
+        const std::string &other_input(const onnx::Node &n, const std::string &v) const { return n.inputs[0] == v ? n.inputs[1] : n.inputs[0]; }
+        // `node` becomes part of step `st`: it gets no step of its own, the step produces its output and runs where it stood
+        void absorb(Step &st, size_t node, std::string &out_name) { dead[node] = true; g.fused_away_++; out_name = m.nodes[node].outputs[0]; st.pos = node; }
+    };
+
+    // ---- small questions every step builder asks
+    bool is_const(const std::string &v) const { auto it = ids_.find(v); return it != ids_.end() && consts_.count(it->second) != 0; }
+    const Tensor &const_of(const std::string &v) const { return consts_.at(ids_.at(v)); }
+    bool const_f32_scalar(const std::string &v, float &out) const {
+        if (!is_const(v)) return false;
+        const Tensor &t = const_of(v);
+        if (t.len() != 1 || t.dtype() != DType::F32) return false;
+        out = t.to_host<float>()[0];
+        return true;
+    }
+    static std::string label_of(const onnx::Node &n) { return n.name.empty() ? n.outputs.at(0) : n.name; }
+    template <class Op> static void run_plainly(Step &st, std::shared_ptr<Op> op) { st.run = [op](Context &c, const InputList &in) { return op->run(c, in); }; }
+    // Graph::prepack_weights (src/graph.rs:488-562): a constant weight (input 1) is staged once at load, under the node's label.  `rank`: the one weight rank
+    // the operator packs (0: any).  Null: nothing was packed, the step stages its weight per run
+    template <class Op> const Tensor *prepacked_weight(const onnx::Node &n, Op &op, bool eligible, int rank) {
+        if (!opt_.prepack || !is_const(n.inputs.at(1)) || !eligible) return nullptr;
+        const Tensor &w = const_of(n.inputs[1]);
+        return rank && w.ndim() != rank ? nullptr : packed_for(label_of(n), [&] { return op.prepack(ctx_, w); });
+    }
+    // A constant weight zero point (input 3 of ConvInteger / MatMulInteger) that is all zeros (what ort-quantize writes for symmetric weights) is no zero
+    // point: dropped at load, the kernel then takes its single-row-term epilogue (integer algebra: the dropped terms are exact zeros).  Measured: 28.1 ->
+    // 24.7 us on the dominant launch of the int8 graph -- the whole gap between this executor and the hand-planned runner, which never passed one.
+    void drop_zero_zero_point(Step &st) {
+        if (!opt_.fuse || st.in[3] < 0 || !consts_.count(st.in[3])) return;
+        const Tensor &z = consts_.at(st.in[3]);
+        bool all_zero = z.len() > 0 && (z.dtype() == DType::I8 || z.dtype() == DType::U8);
+        if (all_zero) for (uint8_t b : z.to_host<uint8_t>()) if (b) { all_zero = false; break; }
+        if (all_zero) st.in[3] = -1;
+    }
+    // (ConvInteger | MatMulInteger) -> Cast(to float) -> Mul(scale): takes the two followers and names the scale.  False: the graph has no such tail
+    bool absorb_cast_and_scale(Step &st, Nodes &nodes, std::string &out_name, std::string &scale) {
+        const long cast = opt_.fuse ? nodes.sole_user(out_name, "Cast") : -1;
+        const long mul = cast >= 0 && nodes[cast].get_int("to", 0) == onnx::FLOAT ? nodes.sole_user(nodes[cast].outputs[0], "Mul") : -1;
+        if (mul < 0) return false;
+        scale = nodes.other_input(nodes[mul], nodes[cast].outputs[0]);
+        nodes.absorb(st, (size_t)cast, out_name);
+        nodes.absorb(st, (size_t)mul, out_name);
+        return true;
+    }
+    // keepdims / noop_with_empty_axes / axes of a Reduce* node; axes come from the attribute or (ReduceSum: opset >= 13, the others: opset >= 18) from a constant input
+    template <class Op> void read_reduce_attrs(Step &st, const onnx::Node &n, Op &op) {
+        op.keep_dims = n.get_int("keepdims", 1) != 0;
+        op.noop_with_empty_axes = n.get_int("noop_with_empty_axes", 0) != 0;
+        op.axes = n.get_ints("axes", {});
+        if (n.inputs.size() > 1 && !n.inputs[1].empty()) {
+            if (!is_const(n.inputs[1])) throw GraphError(n.op_type + " " + st.name + ": the axes input must be a constant");
+            for (int32_t v : const_of(n.inputs[1]).to_host<int32_t>()) op.axes.push_back(v);
+            st.in.resize(1);
+        }
+        st.batch_coupled = op.axes.empty() ? !op.noop_with_empty_axes : std::count(op.axes.begin(), op.axes.end(), 0) != 0; // reduces over dim 0
+    }
+    // An activation node as the kernels' RTEN_HIP_ACT_* kind and parameters, with the reference's attribute defaults (onnx_registry.rs:1132,1228,1275,1999);
+    // Clip's min / max come from its opset-6 attributes (promoted to inputs, onnx_registry.rs:887-897) or from constant scalar inputs (an empty name or a
+    // missing input: f32::MIN / f32::MAX).  False: not one of these, or a Clip whose bounds are run-time values.
+    bool activation_of(const onnx::Node &n, Activation &a) const {
+        a = Activation();
+        if (n.op_type == "Sigmoid") a.kind = RTEN_HIP_ACT_SIGMOID;
+        else if (n.op_type == "Silu") a.kind = RTEN_HIP_ACT_SILU;
+        else if (n.op_type == "Swish") { a.kind = RTEN_HIP_ACT_SWISH; a.alpha = n.get_float("alpha", 1.f); }
+        else if (n.op_type == "HardSigmoid") { a.kind = RTEN_HIP_ACT_HARD_SIGMOID; a.alpha = n.get_float("alpha", 0.2f); a.beta = n.get_float("beta", 0.5f); }
+        else if (n.op_type == "HardSwish") a.kind = RTEN_HIP_ACT_HARD_SWISH;
+        else if (n.op_type == "LeakyRelu") { a.kind = RTEN_HIP_ACT_LEAKY_RELU; a.alpha = n.get_float("alpha", 0.01f); }
+        else if (n.op_type == "Elu") { a.kind = RTEN_HIP_ACT_ELU; a.alpha = n.get_float("alpha", 1.f); }
+        else if (n.op_type == "Clip") {
+            a.kind = RTEN_HIP_ACT_CLIP; a.alpha = -FLT_MAX; a.beta = FLT_MAX;
+            for (int k = 1; k <= 2; k++) {
+                const char *an = k == 1 ? "min" : "max";
+                const bool has_in = n.inputs.size() > (size_t)k && !n.inputs[(size_t)k].empty();
+                if (n.attr(an) && has_in) throw GraphError("Clip " + n.name + ": input " + std::to_string(k) + " specified as both attribute and input");
+                float v = 0.f;
+                if (n.attr(an)) v = n.get_float(an, 0.f);
+                else if (!has_in) continue;
+                else if (!const_f32_scalar(n.inputs[(size_t)k], v)) return false;
+                (k == 1 ? a.alpha : a.beta) = v;
+            }
+        } else return false;
+        return true;
+    }
+
+    // ---- attention pre-pass (TransposeFusion + MatMulScale + AddSoftmax of the reference, taken one step further):
+    //   q_lin -> Reshape[0,0,h,d] -> Transpose(0,2,1,3) -+
+    //   k_lin -> Reshape[0,0,h,d] -> Transpose(0,2,3,1) -+> MatMul -> (Div | Mul scalar) -> Add(mask) -> Softmax(-1) -+
+    //   v_lin -> Reshape[0,0,h,d] -> Transpose(0,2,1,3) ------------------------------------------------------------+> MatMul -> Transpose(0,2,1,3) -> Reshape[0,0,H]
+    // becomes one MultiHeadSdpa step over the [B, S, H] projections; if the three projections are MatMul(x, W) + Add(b)
+    // of one input with constant weights, they become one GEMM against [Wq | Wk | Wv] whose column blocks the
+    // attention kernel reads in place (bit-identical: every output element is the same k-ordered dot product).
+    // lead0 / lead1: leading dims when the Reshapes spell them out ([B, S, h, d], as PyTorch's exporter writes a static-shape
+    // `view`) instead of copying them ([0, 0, h, d]); checked against the projections at run time (0 = copied)
+    struct Attn { std::string q, k, v, mask, out, x; int heads = 0; float scale = 1.f; bool merged = false; int wqkv = -1, bqkv = -1; int64_t hidden = 0; int lead0 = 0, lead1 = 0; int head_dim = 0;
+                  std::string lead_check; }; // a run-time Reshape target (dynamic-axes export): its leading dims are checked against the projection's when the step runs
+    // The matcher: every match is keyed by the node where its step runs (the final Reshape); the nodes it covers are dead from here on.
+    std::map<size_t, Attn> plan_attention(Nodes &nodes) {
+        const onnx::Model &m = nodes.m;
+        std::map<size_t, Attn> attn_at;
+        auto const_i32 = [&](const std::string &v, std::vector<int32_t> &out) {
+            if (!is_const(v) || const_of(v).dtype() != DType::I32) return false;
+            out = const_of(v).to_host<int32_t>();
+            return true;
+        };
+        auto leading_ok = [](const std::vector<int32_t> &shp, Attn &at, bool first) { // [0, 0, ..] or one explicit [B, S, ..] throughout
+            if ((shp[0] == 0) != (shp[1] == 0) || shp[0] < 0 || shp[1] < 0) return false;
+            if (first) { at.lead0 = shp[0]; at.lead1 = shp[1]; return true; }
+            return at.lead0 == shp[0] && at.lead1 == shp[1];
+        };
+        // The target of a head-split / head-merge Reshape: a constant, or -- exports with dynamic axes -- Concat(dim 0, dim 1, [h | -1], [d]) whose leading
+        // entries are computed from a Shape at run time and whose trailing entries are constants.  The run-time form reads as [0, 0, ..] ("copy the
+        // projection's leading dims"); `dyn` names the Concat's output so that the fused step can check that claim against its host value.
+        auto reshape_target = [&](const onnx::Node &rn, std::vector<int32_t> &shp, std::string &dyn) {
+            dyn.clear();
+            if (rn.inputs.size() < 2) return false;
+            if (const_i32(rn.inputs[1], shp)) return true;
+            const long c = nodes.made_by(rn.inputs[1], "Concat");
+            if (c < 0 || nodes[c].get_int("axis", 0) != 0 || nodes[c].inputs.size() < 3) return false;
+            const onnx::Node &cn = nodes[c];
+            shp.assign(cn.inputs.size(), 0);
+            for (size_t k = 0; k < cn.inputs.size(); k++) {
+                std::vector<int32_t> one;
+                if (k < 2) { if (is_const(cn.inputs[k])) return false; continue; } // (a half-constant leading pair is not this idiom)
+                if (!const_i32(cn.inputs[k], one) || one.size() != 1) return false;
+                shp[k] = one[0];
+            }
+            dyn = rn.inputs[1];
+            return true;
+        };
+        // value -> (Reshape[0,0,h,d] node, Transpose node) feeding it with the given perm; returns the projection's name
+        auto split_heads = [&](const std::string &v, std::vector<int> perm, Attn &at, bool first, std::vector<size_t> &covered) -> std::string {
+            int &heads = at.heads;
+            const long t = nodes.made_by(v, "Transpose");
+            if (t < 0 || nodes[t].get_ints("perm", {}) != perm) return "";
+            const long r = nodes.made_by(nodes[t].inputs[0], "Reshape");
+            std::vector<int32_t> shp;
+            std::string dyn;
+            // [.., .., h, d] or [.., .., -1, d]: transformers' exporter spells the head COUNT as -1 (hidden / d, resolved when the step runs)
+            if (r < 0 || !reshape_target(nodes[r], shp, dyn) || shp.size() != 4 || (shp[2] <= 0 && !(shp[2] == -1 && shp[3] > 0)) || !leading_ok(shp, at, first)) return "";
+            if (first) at.lead_check = dyn;
+            if (heads && heads != shp[2]) return "";
+            // one head size for q, k and v (the kernel's d == dv); -1 ("the rest") is accepted only if all three say so
+            if (heads && at.head_dim != shp[3]) return "";
+            heads = shp[2];
+            at.head_dim = shp[3];
+            covered.push_back((size_t)t); covered.push_back((size_t)r);
+            return nodes[r].inputs[0];
+        };
+        // a projection written as MatMul(x, W constant [K, N]) + Add(b constant [N]), either operand order
+        struct Lin { long mm = -1, add = -1; std::string x, w, b; };
+        auto linear = [&](const std::string &v) {
+            Lin l;
+            const long a = nodes.made_by(v, "Add");
+            if (a < 0) return l;
+            for (int side = 0; side < 2; side++) {
+                const std::string &mmv = nodes[a].inputs[(size_t)side], &bv = nodes[a].inputs[(size_t)(1 - side)];
+                const long mmi = nodes.made_by(mmv, "MatMul");
+                if (mmi < 0 || !is_const(bv) || !is_const(nodes[mmi].inputs[1])) continue;
+                const Tensor &w = const_of(nodes[mmi].inputs[1]), &b = const_of(bv);
+                if (w.ndim() != 2 || b.ndim() != 1 || b.len() != w.size(1) || w.dtype() != DType::F32 || b.dtype() != DType::F32) continue;
+                l.mm = mmi; l.add = a; l.x = nodes[mmi].inputs[0]; l.w = nodes[mmi].inputs[1]; l.b = bv;
+                return l;
+            }
+            return l;
+        };
+        for (size_t i = 0; i < m.nodes.size(); i++) {
+            const onnx::Node &mm = m.nodes[i];
+            if (nodes.dead[i] || mm.op_type != "MatMul" || mm.inputs.size() != 2) continue;
+            Attn at;
+            std::vector<size_t> covered{i};
+            at.q = split_heads(mm.inputs[0], {0, 2, 1, 3}, at, true, covered);
+            at.k = at.q.empty() ? "" : split_heads(mm.inputs[1], {0, 2, 3, 1}, at, false, covered);
+            if (at.k.empty()) continue;
+            std::string cur = mm.outputs[0];
+            for (const char *sop : {"Div", "Mul"}) {
+                const long d = nodes.sole_user(cur, sop);
+                float cv = 0.f;
+                if (d < 0 || nodes[d].inputs[0] != cur || at.scale != 1.f || !const_f32_scalar(nodes[d].inputs[1], cv)) continue;
+                at.scale = std::string(sop) == "Div" ? 1.0f / cv : cv;
+                covered.push_back((size_t)d);
+                cur = nodes[d].outputs[0];
+            }
+            const long add = nodes.sole_user(cur, "Add");
+            if (add >= 0) { at.mask = nodes.other_input(nodes[add], cur); covered.push_back((size_t)add); cur = nodes[add].outputs[0]; }
+            const long sm = nodes.sole_user(cur, "Softmax");
+            const int64_t sm_axis = sm < 0 ? 0 : nodes[sm].get_int("axis", -1);
+            if (sm < 0 || (sm_axis != -1 && sm_axis != 3)) continue; // the scores are 4-D here: PyTorch's exporter writes the last axis as 3
+            covered.push_back((size_t)sm);
+            cur = nodes[sm].outputs[0];
+            const long pv = nodes.sole_user(cur, "MatMul");
+            if (pv < 0 || nodes[pv].inputs[0] != cur) continue;
+            covered.push_back((size_t)pv);
+            at.v = split_heads(nodes[pv].inputs[1], {0, 2, 1, 3}, at, false, covered);
+            if (at.v.empty()) continue;
+            const long tr = nodes.sole_user(nodes[pv].outputs[0], "Transpose");
+            if (tr < 0 || nodes[tr].get_ints("perm", {}) != std::vector<int>{0, 2, 1, 3}) continue;
+            const long rs = nodes.sole_user(nodes[tr].outputs[0], "Reshape");
+            std::vector<int32_t> shp;
+            std::string dyn_out;
+            if (rs < 0 || !reshape_target(nodes[rs], shp, dyn_out) || shp.size() != 3 || !leading_ok(shp, at, false)) continue;
+            covered.push_back((size_t)tr); covered.push_back((size_t)rs);
+            at.out = nodes[rs].outputs[0];
+            if (!at.mask.empty() && !nodes.ready_before(at.mask, i + 1)) continue; // mask must exist before the scores
+            if (!at.mask.empty() && is_const(at.mask)) { // a constant mask with a head axis is outside the kernel's forms: leave the graph unfused
+                const Tensor &mk = const_of(at.mask);
+                if (mk.dtype() != DType::F32 || mk.ndim() > 4 || (mk.ndim() == 4 && mk.size(1) != 1) || (mk.ndim() == 3 && mk.size(0) != 1)) continue;
+            }
+            // optional: one GEMM for the three projections
+            const Lin lq = linear(at.q), lk = linear(at.k), lv = linear(at.v);
+            const bool one_input = lq.mm >= 0 && lk.mm >= 0 && lv.mm >= 0 && lq.x == lk.x && lq.x == lv.x;
+            if (one_input && const_of(lq.w).shape() == const_of(lk.w).shape() && const_of(lq.w).shape() == const_of(lv.w).shape()) {
+                const Tensor &wq = const_of(lq.w), &wk = const_of(lk.w), &wv = const_of(lv.w);
+                const int64_t K = wq.size(0), Nn = wq.size(1);
+                const std::vector<float> hq = wq.to_host<float>(), hk = wk.to_host<float>(), hv = wv.to_host<float>();
+                std::vector<float> wcat((size_t)(K * 3 * Nn)), bcat;
+                for (int64_t r = 0; r < K; r++) {
+                    std::copy(hq.begin() + r * Nn, hq.begin() + (r + 1) * Nn, wcat.begin() + r * 3 * Nn);
+                    std::copy(hk.begin() + r * Nn, hk.begin() + (r + 1) * Nn, wcat.begin() + r * 3 * Nn + Nn);
+                    std::copy(hv.begin() + r * Nn, hv.begin() + (r + 1) * Nn, wcat.begin() + r * 3 * Nn + 2 * Nn);
+                }
+                for (const std::string *bn : {&lq.b, &lk.b, &lv.b}) { const std::vector<float> hb = const_of(*bn).to_host<float>(); bcat.insert(bcat.end(), hb.begin(), hb.end()); }
+                at.wqkv = id_of("__qkv_w." + std::to_string(i));
+                at.bqkv = id_of("__qkv_b." + std::to_string(i));
+                add_const(at.wqkv, [&] { return Tensor::from_host<float>(ctx_, {K, 3 * Nn}, wcat.data()); });
+                add_const(at.bqkv, [&] { return Tensor::from_host<float>(ctx_, {3 * Nn}, bcat.data()); });
+                at.merged = true; at.x = lq.x; at.hidden = Nn;
+                for (long d : {lq.mm, lq.add, lk.mm, lk.add, lv.mm, lv.add}) covered.push_back((size_t)d);
+            }
+            for (size_t d : covered) nodes.dead[d] = true;
+            fused_away_ += covered.size() - (at.merged ? 2 : 1);
+            attn_at[(size_t)rs] = at;
+        }
+        return attn_at;
+    }
+    // The step(s) of one match, at node `pos`: MultiHeadSdpa, after one FusedMatMul for the three projections when they were merged.
+    void emit_attention(const Attn &at, size_t pos) {
+        auto op = std::make_shared<MultiHeadSdpa>();
+        op->heads = at.heads; op->head_dim = at.head_dim; op->scale = at.scale; op->flush_nans_to_zero = false;
+        Step st;
+        st.pos = pos;
+        st.name = at.out;
+        st.kind_name = at.merged ? "MultiHeadSdpa(QKV column blocks)" : "MultiHeadSdpa";
+        if (at.merged) {
+            auto lin = std::make_shared<FusedMatMul>();
+            Step pj;
+            pj.pos = pos;
+            pj.name = at.out + ".qkv";
+            pj.kind_name = "FusedMatMul(QKV)";
+            pj.in = {id_of(at.x), at.wqkv, at.bqkv};
+            const int qkv = id_of("__qkv." + at.out);
+            pj.out = {qkv};
+            auto plan = std::make_shared<GemmPlan>();
+            pj.gemm_plan = plan;
+            pj.run = [lin, plan](Context &c, const InputList &in) { PlanScope scope(c, *plan); return lin->run(c, in); };
+            steps_.push_back(std::move(pj));
+            op->q_rs = op->k_rs = op->v_rs = 3 * at.hidden; op->width = at.hidden;
+            op->q_off = 0; op->k_off = at.hidden; op->v_off = 2 * at.hidden;
+            st.in = {qkv, qkv, qkv, at.mask.empty() ? -1 : id_of(at.mask)};
+        } else {
+            st.in = {id_of(at.q), id_of(at.k), id_of(at.v), at.mask.empty() ? -1 : id_of(at.mask)};
+        }
+        st.out = {id_of(at.out)};
+        if (!at.lead_check.empty()) st.in.push_back(id_of(at.lead_check)); // (5th operand: the run-time Reshape target, a host value)
+        const int lead0 = at.lead0, lead1 = at.lead1;
+        st.run = [op, lead0, lead1](Context &c, const InputList &in) {
+            if (lead0 && (require(in, 0).ndim() != 3 || require(in, 0).size(0) != lead0 || require(in, 0).size(1) != lead1))
+                throw OpError(OpError::InvalidValue, "fused attention: the graph's Reshape spells out leading dims that differ from the projection's");
+            if (in.size() > 4 && in[4]) { // the Reshape target the graph computes at run time must say what the fusion assumed: [B, S, ..] of the projection
+                const std::vector<int64_t> tgt = host_ints(in[4], "fused attention: the head-split Reshape's target");
+                if (require(in, 0).ndim() != 3 || tgt.size() != 4 || tgt[0] != require(in, 0).size(0) || tgt[1] != require(in, 0).size(1))
+                    throw OpError(OpError::InvalidValue, "fused attention: the graph's Reshape target differs from the projection's leading dims");
+                return op->run(c, InputList(in.begin(), in.begin() + 4));
+            }
+            return op->run(c, in);
+        };
+        steps_.push_back(std::move(st));
+    }
+
+    // ---- compile: constants, the attention pre-pass, one step per remaining node (the make_*_step members below, each with the followers it absorbs), then
+    //      the step-level passes and liveness
     void compile(const onnx::Model &m_in) {
-        const onnx::Model m_canonical = canonicalize(m_in);
-        const onnx::Model &m = m_canonical;
+        const onnx::Model m = canonicalize(m_in);
         inputs_ = m.inputs;
         outputs_ = m.outputs;
         for (auto &t : m.initializers) add_const(id_of(t.name), [&] { return upload(t); });
         for (auto &in : m.inputs) id_of(in.name);
 
-        const size_t N = m.nodes.size();
-        // consumers of every value (graph outputs count as a use: they must not be fused away)
-        std::map<std::string, std::vector<size_t>> users;
-        std::map<std::string, size_t> producer;
-        for (size_t i = 0; i < N; i++) {
-            for (auto &s : m.nodes[i].inputs) if (!s.empty()) users[s].push_back(i);
-            for (auto &s : m.nodes[i].outputs) if (!s.empty()) producer[s] = i;
-        }
-        std::set<std::string> graph_outs;
-        for (auto &o : m.outputs) graph_outs.insert(o.name);
-        std::vector<bool> dead(N, false);
-        const std::vector<bool> *dead_ptr = &dead;
-        auto sole_user = [&](const std::string &v, const char *op) -> long {
-            if (graph_outs.count(v)) return -1;
-            auto it = users.find(v);
-            if (it == users.end() || it->second.size() != 1 || dead_ptr->at(it->second[0])) return -1;
-            return m.nodes[it->second[0]].op_type == op ? (long)it->second[0] : -1;
-        };
-        auto is_const = [&](const std::string &v) { auto it = ids_.find(v); return it != ids_.end() && consts_.count(it->second) != 0; };
-        // A fused step runs at the position of the LAST node it absorbs (st.pos), where -- the node list being
-        // topologically sorted -- every operand of every absorbed node is already available.  An Add of two operator
-        // outputs is claimed by the LATER producer only (its other operand exists before that producer runs), so two
-        // convolutions feeding one Add (projection shortcut + main branch) do not both absorb it.
-        auto ready_before = [&](const std::string &v, size_t at) {
-            auto it = producer.find(v);
-            return it == producer.end() || it->second < at;
-        };
-        auto other_input = [&](const onnx::Node &n, const std::string &v) { return n.inputs[0] == v ? n.inputs[1] : n.inputs[0]; };
-        // An activation node as the kernels' RTEN_HIP_ACT_* kind and parameters, with the reference's attribute defaults (onnx_registry.rs:1132,1228,1275,1999);
-        // Clip's min / max come from its opset-6 attributes (promoted to inputs, onnx_registry.rs:887-897) or from constant scalar inputs (an empty name or a
-        // missing input: f32::MIN / f32::MAX).  False: not one of these, or a Clip whose bounds are run-time values.
-        auto activation_of = [&](const onnx::Node &n, Activation &a) -> bool {
-            a = Activation();
-            if (n.op_type == "Sigmoid") a.kind = RTEN_HIP_ACT_SIGMOID;
-            else if (n.op_type == "Silu") a.kind = RTEN_HIP_ACT_SILU;
-            else if (n.op_type == "Swish") { a.kind = RTEN_HIP_ACT_SWISH; a.alpha = n.get_float("alpha", 1.f); }
-            else if (n.op_type == "HardSigmoid") { a.kind = RTEN_HIP_ACT_HARD_SIGMOID; a.alpha = n.get_float("alpha", 0.2f); a.beta = n.get_float("beta", 0.5f); }
-            else if (n.op_type == "HardSwish") a.kind = RTEN_HIP_ACT_HARD_SWISH;
-            else if (n.op_type == "LeakyRelu") { a.kind = RTEN_HIP_ACT_LEAKY_RELU; a.alpha = n.get_float("alpha", 0.01f); }
-            else if (n.op_type == "Elu") { a.kind = RTEN_HIP_ACT_ELU; a.alpha = n.get_float("alpha", 1.f); }
-            else if (n.op_type == "Clip") {
-                a.kind = RTEN_HIP_ACT_CLIP; a.alpha = -FLT_MAX; a.beta = FLT_MAX;
-                for (int k = 1; k <= 2; k++) {
-                    const char *an = k == 1 ? "min" : "max";
-                    const bool has_in = n.inputs.size() > (size_t)k && !n.inputs[(size_t)k].empty();
-                    if (n.attr(an) && has_in) throw GraphError("Clip " + n.name + ": input " + std::to_string(k) + " specified as both attribute and input");
-                    float v;
-                    if (n.attr(an)) v = n.get_float(an, 0.f);
-                    else if (!has_in) continue;
-                    else {
-                        if (!is_const(n.inputs[(size_t)k])) return false;
-                        const Tensor &t = consts_.at(ids_.at(n.inputs[(size_t)k]));
-                        if (t.len() != 1 || t.dtype() != DType::F32) return false;
-                        v = t.to_host<float>()[0];
-                    }
-                    (k == 1 ? a.alpha : a.beta) = v;
-                }
-            } else return false;
-            return true;
-        };
-        // the sole consumer of v if it is an activation activation_of takes (and not a graph output); -1 otherwise
-        auto sole_activation = [&](const std::string &v, Activation &a) -> long {
-            if (graph_outs.count(v)) return -1;
-            auto it = users.find(v);
-            if (it == users.end() || it->second.size() != 1 || dead_ptr->at(it->second[0])) return -1;
-            const onnx::Node &u = m.nodes[it->second[0]];
-            return u.inputs.size() >= 1 && u.inputs[0] == v && activation_of(u, a) ? (long)it->second[0] : -1;
-        };
-
-        // ---- attention pre-pass (TransposeFusion + MatMulScale + AddSoftmax of the reference, taken one step further):
-        //   q_lin -> Reshape[0,0,h,d] -> Transpose(0,2,1,3) -+
-        //   k_lin -> Reshape[0,0,h,d] -> Transpose(0,2,3,1) -+> MatMul -> (Div | Mul scalar) -> Add(mask) -> Softmax(-1) -+
-        //   v_lin -> Reshape[0,0,h,d] -> Transpose(0,2,1,3) ------------------------------------------------------------+> MatMul -> Transpose(0,2,1,3) -> Reshape[0,0,H]
-        // becomes one MultiHeadSdpa step over the [B, S, H] projections; if the three projections are MatMul(x, W) + Add(b)
-        // of one input with constant weights, they become one GEMM against [Wq | Wk | Wv] whose column blocks the
-        // attention kernel reads in place (bit-identical: every output element is the same k-ordered dot product).
-        // lead0 / lead1: leading dims when the Reshapes spell them out ([B, S, h, d], as PyTorch's exporter writes a static-shape
-        // `view`) instead of copying them ([0, 0, h, d]); checked against the projections at run time (0 = copied)
-        struct Attn { std::string q, k, v, mask, out, x; int heads = 0; float scale = 1.f; bool merged = false; int wqkv = -1, bqkv = -1; int64_t hidden = 0; int lead0 = 0, lead1 = 0; int head_dim = 0;
-                      std::string lead_check; }; // a run-time Reshape target (dynamic-axes export): its leading dims are checked against the projection's when the step runs
-        std::map<size_t, Attn> attn_at;
-        if (opt_.fuse) {
-            auto single_use = [&](const std::string &v) { auto it = users.find(v); return !graph_outs.count(v) && it != users.end() && it->second.size() == 1; };
-            auto made_by = [&](const std::string &v, const char *op) -> long {
-                auto it = producer.find(v);
-                return it != producer.end() && !dead[it->second] && m.nodes[it->second].op_type == op && single_use(v) ? (long)it->second : -1;
-            };
-            auto const_i32 = [&](const std::string &v, std::vector<int32_t> &out) {
-                if (!is_const(v)) return false;
-                const Tensor &t = consts_.at(ids_.at(v));
-                if (t.dtype() != DType::I32) return false;
-                out = t.to_host<int32_t>();
-                return true;
-            };
-            // value -> (Reshape[0,0,h,d] node, Transpose node) feeding it with the given perm; returns the projection's name
-            auto leading_ok = [](const std::vector<int32_t> &shp, Attn &at, bool first) { // [0, 0, ..] or one explicit [B, S, ..] throughout
-                if ((shp[0] == 0) != (shp[1] == 0) || shp[0] < 0 || shp[1] < 0) return false;
-                if (first) { at.lead0 = shp[0]; at.lead1 = shp[1]; return true; }
-                return at.lead0 == shp[0] && at.lead1 == shp[1];
-            };
-            // The target of a head-split / head-merge Reshape: a constant, or -- exports with dynamic axes -- Concat(dim 0, dim 1, [h | -1], [d]) whose leading
-            // entries are computed from a Shape at run time and whose trailing entries are constants.  The run-time form reads as [0, 0, ..] ("copy the
-            // projection's leading dims"); `dyn` names the Concat's output so that the fused step can check that claim against its host value.
-            auto reshape_target = [&](const onnx::Node &rn, std::vector<int32_t> &shp, std::string &dyn) {
-                dyn.clear();
-                if (rn.inputs.size() < 2) return false;
-                if (const_i32(rn.inputs[1], shp)) return true;
-                const long c = made_by(rn.inputs[1], "Concat");
-                if (c < 0 || m.nodes[(size_t)c].get_int("axis", 0) != 0 || m.nodes[(size_t)c].inputs.size() < 3) return false;
-                const onnx::Node &cn = m.nodes[(size_t)c];
-                shp.assign(cn.inputs.size(), 0);
-                for (size_t k = 0; k < cn.inputs.size(); k++) {
-                    std::vector<int32_t> one;
-                    if (k < 2) { if (is_const(cn.inputs[k])) return false; continue; } // (a half-constant leading pair is not this idiom)
-                    if (!const_i32(cn.inputs[k], one) || one.size() != 1) return false;
-                    shp[k] = one[0];
-                }
-                dyn = rn.inputs[1];
-                return true;
-            };
-            auto split_heads = [&](const std::string &v, std::vector<int> perm, Attn &at, bool first, std::vector<size_t> &nodes) -> std::string {
-                int &heads = at.heads;
-                const long t = made_by(v, "Transpose");
-                if (t < 0 || m.nodes[(size_t)t].get_ints("perm", {}) != perm) return "";
-                const long r = made_by(m.nodes[(size_t)t].inputs[0], "Reshape");
-                std::vector<int32_t> shp;
-                std::string dyn;
-                // [.., .., h, d] or [.., .., -1, d]: transformers' exporter spells the head COUNT as -1 (hidden / d, resolved when the step runs)
-                if (r < 0 || !reshape_target(m.nodes[(size_t)r], shp, dyn) || shp.size() != 4 || (shp[2] <= 0 && !(shp[2] == -1 && shp[3] > 0)) || !leading_ok(shp, at, first)) return "";
-                if (first) at.lead_check = dyn;
-                if (heads && heads != shp[2]) return "";
-                // one head size for q, k and v (the kernel's d == dv); -1 ("the rest") is accepted only if all three say so
-                if (heads && at.head_dim != shp[3]) return "";
-                heads = shp[2];
-                at.head_dim = shp[3];
-                nodes.push_back((size_t)t); nodes.push_back((size_t)r);
-                return m.nodes[(size_t)r].inputs[0];
-            };
-            for (size_t i = 0; i < N; i++) {
-                const onnx::Node &mm = m.nodes[i];
-                if (dead[i] || mm.op_type != "MatMul" || mm.inputs.size() != 2) continue;
-                Attn at;
-                std::vector<size_t> nodes{i};
-                at.q = split_heads(mm.inputs[0], {0, 2, 1, 3}, at, true, nodes);
-                at.k = at.q.empty() ? "" : split_heads(mm.inputs[1], {0, 2, 3, 1}, at, false, nodes);
-                if (at.k.empty()) continue;
-                std::string cur = mm.outputs[0];
-                for (const char *sop : {"Div", "Mul"}) {
-                    const long d = sole_user(cur, sop);
-                    if (d < 0 || m.nodes[(size_t)d].inputs[0] != cur || !is_const(m.nodes[(size_t)d].inputs[1])) continue;
-                    const Tensor &c = consts_.at(ids_.at(m.nodes[(size_t)d].inputs[1]));
-                    if (c.len() != 1 || c.dtype() != DType::F32 || at.scale != 1.f) continue;
-                    const float cv = c.to_host<float>()[0];
-                    at.scale = std::string(sop) == "Div" ? 1.0f / cv : cv;
-                    nodes.push_back((size_t)d);
-                    cur = m.nodes[(size_t)d].outputs[0];
-                }
-                const long add = sole_user(cur, "Add");
-                if (add >= 0) { at.mask = other_input(m.nodes[(size_t)add], cur); nodes.push_back((size_t)add); cur = m.nodes[(size_t)add].outputs[0]; }
-                const long sm = sole_user(cur, "Softmax");
-                const int64_t sm_axis = sm < 0 ? 0 : m.nodes[(size_t)sm].get_int("axis", -1);
-                if (sm < 0 || (sm_axis != -1 && sm_axis != 3)) continue; // the scores are 4-D here: PyTorch's exporter writes the last axis as 3
-                nodes.push_back((size_t)sm);
-                cur = m.nodes[(size_t)sm].outputs[0];
-                const long pv = sole_user(cur, "MatMul");
-                if (pv < 0 || m.nodes[(size_t)pv].inputs[0] != cur) continue;
-                nodes.push_back((size_t)pv);
-                at.v = split_heads(m.nodes[(size_t)pv].inputs[1], {0, 2, 1, 3}, at, false, nodes);
-                if (at.v.empty()) continue;
-                const long tr = sole_user(m.nodes[(size_t)pv].outputs[0], "Transpose");
-                if (tr < 0 || m.nodes[(size_t)tr].get_ints("perm", {}) != std::vector<int>{0, 2, 1, 3}) continue;
-                const long rs = sole_user(m.nodes[(size_t)tr].outputs[0], "Reshape");
-                std::vector<int32_t> shp;
-                std::string dyn_out;
-                if (rs < 0 || !reshape_target(m.nodes[(size_t)rs], shp, dyn_out) || shp.size() != 3 || !leading_ok(shp, at, false)) continue;
-                nodes.push_back((size_t)tr); nodes.push_back((size_t)rs);
-                at.out = m.nodes[(size_t)rs].outputs[0];
-                if (!at.mask.empty() && producer.count(at.mask) && producer[at.mask] > i) continue; // mask must exist before the scores
-                if (!at.mask.empty() && is_const(at.mask)) { // a constant mask with a head axis is outside the kernel's forms: leave the graph unfused
-                    const Tensor &mk = consts_.at(ids_.at(at.mask));
-                    if (mk.dtype() != DType::F32 || mk.ndim() > 4 || (mk.ndim() == 4 && mk.size(1) != 1) || (mk.ndim() == 3 && mk.size(0) != 1)) continue;
-                }
-                // optional: one GEMM for the three projections
-                struct Lin { long mm = -1, add = -1; std::string x, w, b; };
-                auto linear = [&](const std::string &v) {
-                    Lin l;
-                    const long a = made_by(v, "Add");
-                    if (a < 0) return l;
-                    for (int side = 0; side < 2; side++) {
-                        const std::string &mmv = m.nodes[(size_t)a].inputs[(size_t)side], &bv = m.nodes[(size_t)a].inputs[(size_t)(1 - side)];
-                        const long mmi = made_by(mmv, "MatMul");
-                        if (mmi < 0 || !is_const(bv) || !is_const(m.nodes[(size_t)mmi].inputs[1])) continue;
-                        const Tensor &w = consts_.at(ids_.at(m.nodes[(size_t)mmi].inputs[1])), &b = consts_.at(ids_.at(bv));
-                        if (w.ndim() != 2 || b.ndim() != 1 || b.len() != w.size(1) || w.dtype() != DType::F32 || b.dtype() != DType::F32) continue;
-                        l.mm = mmi; l.add = a; l.x = m.nodes[(size_t)mmi].inputs[0]; l.w = m.nodes[(size_t)mmi].inputs[1]; l.b = bv;
-                        return l;
-                    }
-                    return l;
-                };
-                const Lin lq = linear(at.q), lk = linear(at.k), lv = linear(at.v);
-                if (lq.mm >= 0 && lk.mm >= 0 && lv.mm >= 0 && lq.x == lk.x && lq.x == lv.x) {
-                    const Tensor &wq = consts_.at(ids_.at(lq.w)), &wk = consts_.at(ids_.at(lk.w)), &wv = consts_.at(ids_.at(lv.w));
-                    if (wq.shape() == wk.shape() && wq.shape() == wv.shape()) {
-                        const int64_t K = wq.size(0), Nn = wq.size(1);
-                        const std::vector<float> hq = wq.to_host<float>(), hk = wk.to_host<float>(), hv = wv.to_host<float>();
-                        std::vector<float> wcat((size_t)(K * 3 * Nn)), bcat;
-                        for (int64_t r = 0; r < K; r++) {
-                            std::copy(hq.begin() + r * Nn, hq.begin() + (r + 1) * Nn, wcat.begin() + r * 3 * Nn);
-                            std::copy(hk.begin() + r * Nn, hk.begin() + (r + 1) * Nn, wcat.begin() + r * 3 * Nn + Nn);
-                            std::copy(hv.begin() + r * Nn, hv.begin() + (r + 1) * Nn, wcat.begin() + r * 3 * Nn + 2 * Nn);
-                        }
-                        for (const std::string *bn : {&lq.b, &lk.b, &lv.b}) { const std::vector<float> hb = consts_.at(ids_.at(*bn)).to_host<float>(); bcat.insert(bcat.end(), hb.begin(), hb.end()); }
-                        at.wqkv = id_of("__qkv_w." + std::to_string(i));
-                        at.bqkv = id_of("__qkv_b." + std::to_string(i));
-                        add_const(at.wqkv, [&] { return Tensor::from_host<float>(ctx_, {K, 3 * Nn}, wcat.data()); });
-                        add_const(at.bqkv, [&] { return Tensor::from_host<float>(ctx_, {3 * Nn}, bcat.data()); });
-                        at.merged = true; at.x = lq.x; at.hidden = Nn;
-                        for (long d : {lq.mm, lq.add, lk.mm, lk.add, lv.mm, lv.add}) nodes.push_back((size_t)d);
-                    }
-                }
-                for (size_t d : nodes) dead[d] = true;
-                fused_away_ += nodes.size() - (at.merged ? 2 : 1);
-                attn_at[(size_t)rs] = at;
-            }
-        }
-
-        for (size_t i = 0; i < N; i++) {
+        Nodes nodes(*this, m);
+        const std::map<size_t, Attn> attn_at = opt_.fuse ? plan_attention(nodes) : std::map<size_t, Attn>();
+        for (size_t i = 0; i < m.nodes.size(); i++) {
             auto af = attn_at.find(i);
-            if (af != attn_at.end()) {
-                const Attn &at = af->second;
-                auto op = std::make_shared<MultiHeadSdpa>();
-                op->heads = at.heads; op->head_dim = at.head_dim; op->scale = at.scale; op->flush_nans_to_zero = false;
-                Step st;
-                st.pos = i;
-                st.name = at.out;
-                st.kind_name = at.merged ? "MultiHeadSdpa(QKV column blocks)" : "MultiHeadSdpa";
-                if (at.merged) {
-                    auto lin = std::make_shared<FusedMatMul>();
-                    Step pj;
-                    pj.pos = i;
-                    pj.name = at.out + ".qkv";
-                    pj.kind_name = "FusedMatMul(QKV)";
-                    pj.in = {id_of(at.x), at.wqkv, at.bqkv};
-                    pj.out = {id_of("__qkv." + at.out)};
-                    auto plan = std::make_shared<GemmPlan>();
-                    pj.gemm_plan = plan;
-                    pj.run = [lin, plan](Context &c, const InputList &in) { PlanScope scope(c, *plan); return lin->run(c, in); };
-                    steps_.push_back(std::move(pj));
-                    const int qkv = id_of("__qkv." + at.out);
-                    op->q_rs = op->k_rs = op->v_rs = 3 * at.hidden; op->width = at.hidden;
-                    op->q_off = 0; op->k_off = at.hidden; op->v_off = 2 * at.hidden;
-                    st.in = {qkv, qkv, qkv, at.mask.empty() ? -1 : id_of(at.mask)};
-                } else {
-                    st.in = {id_of(at.q), id_of(at.k), id_of(at.v), at.mask.empty() ? -1 : id_of(at.mask)};
-                }
-                st.out = {id_of(at.out)};
-                if (!at.lead_check.empty()) st.in.push_back(id_of(at.lead_check)); // (5th operand: the run-time Reshape target, a host value)
-                const int lead0 = at.lead0, lead1 = at.lead1;
-                st.run = [op, lead0, lead1](Context &c, const InputList &in) {
-                    if (lead0 && (require(in, 0).ndim() != 3 || require(in, 0).size(0) != lead0 || require(in, 0).size(1) != lead1))
-                        throw OpError(OpError::InvalidValue, "fused attention: the graph's Reshape spells out leading dims that differ from the projection's");
-                    if (in.size() > 4 && in[4]) { // the Reshape target the graph computes at run time must say what the fusion assumed: [B, S, ..] of the projection
-                        const std::vector<int64_t> tgt = host_ints(in[4], "fused attention: the head-split Reshape's target");
-                        if (require(in, 0).ndim() != 3 || tgt.size() != 4 || tgt[0] != require(in, 0).size(0) || tgt[1] != require(in, 0).size(1))
-                            throw OpError(OpError::InvalidValue, "fused attention: the graph's Reshape target differs from the projection's leading dims");
-                        return op->run(c, InputList(in.begin(), in.begin() + 4));
-                    }
-                    return op->run(c, in);
-                };
-                steps_.push_back(std::move(st));
-                continue;
-            }
-            if (dead[i]) continue;
+            if (af != attn_at.end()) { emit_attention(af->second, i); continue; }
+            if (nodes.dead[i]) continue;
             const onnx::Node &n = m.nodes[i];
             // contrib operators this backend carries live in com.microsoft (onnx_registry.rs registers them under that domain)
             const bool contrib = n.domain == "com.microsoft" && n.op_type == "MatMulNBits";
             if (!n.domain.empty() && n.domain != "ai.onnx" && !contrib) throw GraphError("node " + n.name + ": operator domain " + n.domain + " is not supported");
             Step st;
-            st.name = n.name.empty() ? n.outputs.at(0) : n.name;
+            st.name = label_of(n);
             st.kind_name = n.op_type;
             st.pos = i;
             for (auto &s : n.inputs) st.in.push_back(id_of(s));
-            std::string out_name = n.outputs.at(0);
+            std::string out_name = n.outputs.at(0); // becomes the output of the last node the step absorbs
 
-            if (n.op_type == "Conv") {
-                auto op = std::make_shared<Conv>(conv_attrs(n));
-                std::string residual;
-                if (opt_.fuse) {
-                    long a = sole_user(out_name, "Add");
-                    if (a >= 0 && m.nodes[(size_t)a].inputs.size() == 2) {
-                        const std::string other = other_input(m.nodes[(size_t)a], out_name);
-                        if (other != out_name && ready_before(other, i)) { residual = other; dead[(size_t)a] = true; out_name = m.nodes[(size_t)a].outputs[0]; fused_away_++; st.pos = (size_t)a; }
-                    }
-                    long r = sole_user(out_name, "Relu");
-                    if (r >= 0) { op->fuse_relu = true; dead[(size_t)r] = true; out_name = m.nodes[(size_t)r].outputs[0]; fused_away_++; st.pos = (size_t)r; }
-                    Activation act;
-                    const long ac = op->fuse_relu ? -1 : sole_activation(out_name, act);
-                    if (ac >= 0) { op->act = act; dead[(size_t)ac] = true; out_name = m.nodes[(size_t)ac].outputs[0]; fused_away_++; st.pos = (size_t)ac; }
-                }
-                while (st.in.size() < 3) st.in.push_back(-1);
-                st.in.push_back(residual.empty() ? -1 : id_of(residual));
-                const Tensor *packed = nullptr;
-                if (opt_.prepack && is_const(n.inputs.at(1)) && op->groups == 1) {
-                    const Tensor &w = consts_.at(ids_.at(n.inputs[1]));
-                    if (w.ndim() == 4) packed = packed_for(n.name.empty() ? n.outputs.at(0) : n.name, [&] { return op->prepack(ctx_, w); });
-                }
-                st.kind_name = std::string("Conv") + (residual.empty() ? "" : "+Add") + (op->fuse_relu ? "+Relu" : "") +
-                               (op->act.kind != RTEN_HIP_ACT_NONE ? std::string("+") + activation_name(op->act.kind) : "");
-                st.conv = op;
-                // The Add's other operand is used as the kernel's residual only when it has exactly the conv's output shape
-                // (the kernel indexes it with the output's strides).  Its shape is a run-time fact (no shape inference here), and
-                // it may be a constant or any broadcasting operand -- e.g. the exporter's explicit bias Add([1,O,1,1]) -- so a
-                // mismatch runs the operators as the graph spells them: Conv, broadcasting Add, Relu.  (The constant is NOT
-                // routed to the conv's bias input: the GEMM adds a bias after the first depth block, the graph adds it last.)
-                st.run = [op, packed](Context &c, const InputList &in) {
-                    const Tensor *res = in.size() > 3 ? in[3] : nullptr;
-                    if (res) {
-                        const Tensor &x = require(in, 0), &w = require(in, 1);
-                        bool same = res->dtype() == DType::F32 && x.ndim() == 4 && w.ndim() == 4; // 1-D convs with an Add: always unfused
-                        if (same) {
-                            const rten_hip_conv2d_desc d = op->geometry(x.shape(), w.shape());
-                            same = res->shape() == std::vector<int64_t>{d.n, d.o, d.out_h, d.out_w};
-                        }
-                        if (!same) {
-                            Conv plain = *op; plain.fuse_relu = false; plain.act = Activation();
-                            OutputList y = plain.run_packed(c, {in[0], in[1], in.size() > 2 ? in[2] : nullptr}, packed);
-                            OutputList sum = Add().run(c, {&y[0], res});
-                            if (op->act.kind != RTEN_HIP_ACT_NONE) return ActivationOp(op->act.kind, op->act.alpha, op->act.beta).run(c, {&sum[0]});
-                            return op->fuse_relu ? Relu().run(c, {&sum[0]}) : std::move(sum);
-                        }
-                    }
-                    return op->run_packed(c, in, packed);
-                };
-            } else if (n.op_type == "ConvTranspose") {
+            const std::string &kind = n.op_type;
+            if (kind == "Conv") make_conv_step(st, n, nodes, out_name);
+            else if (kind == "ConvTranspose") {
                 auto op = std::make_shared<ConvTranspose>();
                 op->groups = (int)n.get_int("group", 1);
                 op->strides = n.get_ints("strides", {1, 1});
@@ -1914,360 +1926,53 @@ class Graph {
                 op->output_padding = n.get_ints("output_padding", {});
                 op->padding = padding_of(n, "ConvTranspose");
                 if (n.attr("output_shape")) throw GraphError("ConvTranspose " + st.name + ": the output_shape attribute is not supported");
-                st.run = [op](Context &c, const InputList &in) { return op->run(c, in); };
-            } else if (n.op_type == "MatMulNBits") { // com.microsoft contrib op (onnx_registry reads bits / block_size / accuracy_level)
+                run_plainly(st, op);
+            } else if (kind == "MatMulNBits") { // com.microsoft contrib op (onnx_registry reads bits / block_size / accuracy_level)
                 auto op = std::make_shared<MatMulNBits>();
                 op->bits = (int)n.get_int("bits", 4);
                 op->block_size = n.get_int("block_size", 32);
                 op->accuracy_level = (int)n.get_int("accuracy_level", 0);
-                st.run = [op](Context &c, const InputList &in) { return op->run(c, in); };
-            } else if (n.op_type == "ConvInteger") {
-                auto op = std::make_shared<ConvInteger>();
-                op->conv = conv_attrs(n);
-                std::string scale, bias, residual;
-                bool relu = false;
-                long cast = opt_.fuse ? sole_user(out_name, "Cast") : -1;
-                long mul = cast >= 0 && m.nodes[(size_t)cast].get_int("to", 0) == onnx::FLOAT ? sole_user(m.nodes[(size_t)cast].outputs[0], "Mul") : -1;
-                if (mul >= 0) {
-                    // ConvIntegerToFloat: the Mul's other operand must be a single scale available before the conv runs
-                    const std::string sc = other_input(m.nodes[(size_t)mul], m.nodes[(size_t)cast].outputs[0]);
-                    {
-                        scale = sc;
-                        dead[(size_t)cast] = dead[(size_t)mul] = true;
-                        fused_away_ += 2;
-                        out_name = m.nodes[(size_t)mul].outputs[0];
-                        st.pos = (size_t)mul;
-                        long add = sole_user(out_name, "Add");
-                        if (add >= 0) { // Add(bias constant [1, O, 1, 1])
-                            const std::string b = other_input(m.nodes[(size_t)add], out_name);
-                            if (is_const(b)) {
-                                const Tensor &bt = consts_.at(ids_.at(b));
-                                if (bt.ndim() == 4 && bt.size(0) == 1 && bt.size(2) == 1 && bt.size(3) == 1) {
-                                    bias = b; dead[(size_t)add] = true; fused_away_++; out_name = m.nodes[(size_t)add].outputs[0]; st.pos = (size_t)add;
-                                }
-                            }
-                        }
-                        long add2 = bias.empty() ? -1 : sole_user(out_name, "Add");
-                        if (add2 >= 0) {
-                            const std::string other = other_input(m.nodes[(size_t)add2], out_name);
-                            if (other != out_name && ready_before(other, i)) { residual = other; dead[(size_t)add2] = true; fused_away_++; out_name = m.nodes[(size_t)add2].outputs[0]; st.pos = (size_t)add2; }
-                        }
-                        long r = sole_user(out_name, "Relu");
-                        if (r >= 0) { relu = true; dead[(size_t)r] = true; fused_away_++; out_name = m.nodes[(size_t)r].outputs[0]; st.pos = (size_t)r; }
-                    }
-                }
-                while (st.in.size() < 4) st.in.push_back(-1);
-                // A constant weight zero point that is all zeros (what ort-quantize writes for symmetric weights) is no zero point: dropped at load, the
-                // kernel then takes its single-row-term epilogue (integer algebra: the dropped terms are exact zeros).  Measured: 28.1 -> 24.7 us on the
-                // dominant launch of the int8 graph -- the whole gap between this executor and the hand-planned runner, which never passed one.
-                if (opt_.fuse && st.in[3] >= 0 && consts_.count(st.in[3])) {
-                    const Tensor &z = consts_.at(st.in[3]);
-                    bool all_zero = z.len() > 0 && (z.dtype() == DType::I8 || z.dtype() == DType::U8);
-                    if (all_zero) for (uint8_t b : z.to_host<uint8_t>()) if (b) { all_zero = false; break; }
-                    if (all_zero) st.in[3] = -1;
-                }
-                st.in.push_back(scale.empty() ? -1 : id_of(scale));
-                st.in.push_back(bias.empty() ? -1 : id_of(bias));
-                st.in.push_back(residual.empty() ? -1 : id_of(residual));
-                if (!scale.empty()) st.kind_name = std::string("ConvIntegerToFloat") + (bias.empty() ? "" : "+bias") + (residual.empty() ? "" : "+Add") + (relu ? "+Relu" : "");
-                auto state = std::make_shared<I8Conv>();
-                state->op = op;
-                state->to_float = !scale.empty();
-                if (opt_.prepack && is_const(n.inputs.at(1)) && op->conv.groups == 1) {
-                    const Tensor &w = consts_.at(ids_.at(n.inputs[1]));
-                    if (w.ndim() == 4) state->sg.packed_weight = packed_for(n.name.empty() ? n.outputs.at(0) : n.name, [&] { return op->prepack(ctx_, w); });
-                }
-                st.i8 = state;
-                // ConvIntegerToFloatFusion (fusions.rs:1012-1058) fuses only a scale of shape [] or [1] and leaves every other graph
-                // as ConvInteger -> Cast -> Mul.  Shapes are run-time facts here, so the step decides per run: a scalar f32 scale
-                // (or a per-output-channel [1,O,1,1] / [O,1,1] one, which the kernel applies exactly as Cast -> Mul would) with a
-                // bias of O channels and a residual of the output's shape takes the fused kernel; anything else runs the
-                // operators as the graph spells them.
-                state->relu = relu;
-                st.run = [state, relu](Context &c, const InputList &in) {
-                    const Tensor *scale = in[4], *bias = in[5], *residual = in[6];
-                    if (!scale) return state->op->run_staged(c, InputList(in.begin(), in.begin() + 4), nullptr, nullptr, nullptr, false, state->sg);
-                    bool per_channel = false;
-                    const bool fused = i8_fused_form(*state, in, per_channel);
-                    if (fused) return state->op->run_staged(c, InputList(in.begin(), in.begin() + 4), scale, bias, residual, relu, state->sg, per_channel);
-                    ConvInteger::Staging sg = state->sg;
-                    sg.stats_out = nullptr; // statistics are accumulated by the float epilogue only
-                    OutputList acc = state->op->run_staged(c, InputList(in.begin(), in.begin() + 4), nullptr, nullptr, nullptr, false, sg);
-                    Cast cast; cast.to = DType::F32;
-                    OutputList f = cast.run(c, {&acc[0]});
-                    OutputList y = Mul().run(c, {&f[0], scale});
-                    if (bias) y = Add().run(c, {&y[0], bias});
-                    if (residual) y = Add().run(c, {&y[0], residual});
-                    if (relu) y = Relu().run(c, {&y[0]});
-                    return y;
-                };
-            } else if (n.op_type == "MatMulInteger") {
-                auto op = std::make_shared<MatMulInteger>();
-                std::string scale;
-                long cast = opt_.fuse ? sole_user(out_name, "Cast") : -1;
-                long mul = cast >= 0 && m.nodes[(size_t)cast].get_int("to", 0) == onnx::FLOAT ? sole_user(m.nodes[(size_t)cast].outputs[0], "Mul") : -1;
-                if (mul >= 0) {
-                    const std::string sc = other_input(m.nodes[(size_t)mul], m.nodes[(size_t)cast].outputs[0]);
-                    scale = sc; dead[(size_t)cast] = dead[(size_t)mul] = true; fused_away_ += 2; out_name = m.nodes[(size_t)mul].outputs[0]; st.pos = (size_t)mul;
-                }
-                while (st.in.size() < 4) st.in.push_back(-1);
-                if (opt_.fuse && st.in[3] >= 0 && consts_.count(st.in[3])) { // an all-zero constant RHS zero point: dropped (see ConvInteger)
-                    const Tensor &z = consts_.at(st.in[3]);
-                    bool all_zero = z.len() > 0 && (z.dtype() == DType::I8 || z.dtype() == DType::U8);
-                    if (all_zero) for (uint8_t b : z.to_host<uint8_t>()) if (b) { all_zero = false; break; }
-                    if (all_zero) st.in[3] = -1;
-                }
-                st.in.push_back(scale.empty() ? -1 : id_of(scale));
-                if (!scale.empty()) st.kind_name = "MatMulIntegerToFloat";
-                // Graph::prepack_weights (src/graph.rs:488-562): a constant RHS is staged once at load (PackedBMatrix)
-                const Tensor *packed = nullptr;
-                if (opt_.prepack && is_const(n.inputs.at(1))) {
-                    const Tensor &w = consts_.at(ids_.at(n.inputs.at(1)));
-                    packed = packed_for(n.name.empty() ? n.outputs.at(0) : n.name, [&] { return op->prepack(ctx_, w); });
-                }
-                // MatMulIntegerToFloatFusion (fusions.rs:960-1009) needs a scale of rank <= 1; the operator then needs length 1 or N.
-                // Decided per run (shapes are run-time facts); otherwise MatMulInteger -> Cast -> Mul as the graph spells it.
-                st.run = [op, packed](Context &c, const InputList &in) {
-                    const Tensor *scale = in[4];
-                    if (scale) {
-                        const Tensor &b = require(in, 1);
-                        const int64_t ncols = b.ndim() > 1 ? b.size(b.ndim() - 1) : 1;
-                        const bool ok = scale->dtype() == DType::F32 && scale->ndim() <= 1 && (scale->len() == 1 || scale->len() == ncols);
-                        if (!ok) {
-                            OutputList acc = op->run_scaled(c, InputList(in.begin(), in.begin() + 4), nullptr, packed);
-                            Cast cast; cast.to = DType::F32;
-                            OutputList f = cast.run(c, {&acc[0]});
-                            return Mul().run(c, {&f[0], scale});
-                        }
-                    }
-                    return op->run_scaled(c, InputList(in.begin(), in.begin() + 4), scale, packed);
-                };
-            } else if (n.op_type == "Gemm") {
+                run_plainly(st, op);
+            } else if (kind == "ConvInteger") make_conv_integer_step(st, n, nodes, out_name);
+            else if (kind == "MatMulInteger") make_matmul_integer_step(st, n, nodes, out_name);
+            else if (kind == "Gemm") {
                 auto op = std::make_shared<Gemm>();
                 op->alpha = n.get_float("alpha", 1.f); op->beta = n.get_float("beta", 1.f);
                 op->transpose_a = n.get_int("transA", 0) != 0; op->transpose_b = n.get_int("transB", 0) != 0;
                 auto plan = std::make_shared<GemmPlan>();
                 st.gemm_plan = plan;
                 st.run = [op, plan](Context &c, const InputList &in) { PlanScope scope(c, *plan); return op->run(c, in); };
-            } else if (n.op_type == "MatMul") {
-                // MatMul (+ Mul / Div by a constant scalar = alpha, MatMulScale fusion) (+ Add of a constant 1-D bias,
-                // MatMulAddFusion) (+ Gelu / Relu as the GEMM epilogue): FusedMatMul (src/ops/matmul.rs:455-510)
-                auto op = std::make_shared<FusedMatMul>();
-                std::string bias;
-                auto const_scalar = [&](const std::string &v, float &out) {
-                    if (!is_const(v)) return false;
-                    const Tensor &t = consts_.at(ids_.at(v));
-                    if (t.len() != 1 || t.dtype() != DType::F32) return false;
-                    out = t.to_host<float>()[0];
-                    return true;
-                };
-                if (opt_.fuse) {
-                    for (const char *sop : {"Div", "Mul"}) {
-                        long d = sole_user(out_name, sop);
-                        float c = 0.f;
-                        if (d >= 0 && m.nodes[(size_t)d].inputs[0] == out_name && const_scalar(m.nodes[(size_t)d].inputs[1], c) && op->alpha == 1.f) {
-                            op->alpha = std::string(sop) == "Div" ? 1.0f / c : c;
-                            dead[(size_t)d] = true; fused_away_++; out_name = m.nodes[(size_t)d].outputs[0]; st.pos = (size_t)d;
-                        }
-                    }
-                    long a = op->alpha == 1.f ? sole_user(out_name, "Add") : -1;
-                    if (a >= 0) {
-                        const std::string other = other_input(m.nodes[(size_t)a], out_name);
-                        if (is_const(other) && consts_.at(ids_.at(other)).ndim() == 1 && consts_.at(ids_.at(other)).dtype() == DType::F32) {
-                            bias = other; dead[(size_t)a] = true; fused_away_++; out_name = m.nodes[(size_t)a].outputs[0]; st.pos = (size_t)a;
-                            long g = sole_user(out_name, "Gelu");
-                            if (g >= 0 && !m.nodes[(size_t)g].attr("approximate")) { op->act = RTEN_HIP_ACT_GELU; dead[(size_t)g] = true; fused_away_++; out_name = m.nodes[(size_t)g].outputs[0]; st.pos = (size_t)g; }
-                            long r = g < 0 ? sole_user(out_name, "Relu") : -1;
-                            if (r >= 0) { op->act = RTEN_HIP_ACT_RELU; dead[(size_t)r] = true; fused_away_++; out_name = m.nodes[(size_t)r].outputs[0]; st.pos = (size_t)r; }
-                        }
-                    }
-                    Activation act;
-                    const long ac = op->act == RTEN_HIP_ACT_NONE ? sole_activation(out_name, act) : -1;
-                    if (ac >= 0) {
-                        op->act = act.kind; op->act_alpha = act.alpha; op->act_beta = act.beta;
-                        dead[(size_t)ac] = true; fused_away_++; out_name = m.nodes[(size_t)ac].outputs[0]; st.pos = (size_t)ac;
-                    }
-                }
-                st.in.resize(2);
-                st.in.push_back(bias.empty() ? -1 : id_of(bias));
-                st.kind_name = std::string(op->alpha != 1.f || !bias.empty() || op->act > RTEN_HIP_ACT_GELU ? "FusedMatMul" : "MatMul") +
-                               (op->act != RTEN_HIP_ACT_NONE ? std::string("+") + activation_name(op->act) : "");
-                auto plan = std::make_shared<GemmPlan>();
-                st.gemm_plan = plan;
-                st.run = [op, plan](Context &c, const InputList &in) {
-                    const Tensor *bias = in[2];
-                    if (bias && bias->len() != require(in, 1).size(require(in, 1).ndim() - 1)) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast bias to output shape");
-                    PlanScope scope(c, *plan);
-                    return op->run(c, in);
-                };
-            } else if (n.op_type == "Add" && opt_.fuse && sole_user(out_name, "LayerNormalization") >= 0 &&
-                       m.nodes[(size_t)sole_user(out_name, "LayerNormalization")].get_int("axis", -1) == -1 &&
-                       m.nodes[(size_t)sole_user(out_name, "LayerNormalization")].inputs[0] == out_name) {
-                // Add(residual) -> LayerNormalization(last axis) as one kernel
-                const long ln = sole_user(out_name, "LayerNormalization");
-                const onnx::Node &lnn = m.nodes[(size_t)ln];
-                auto fused = std::make_shared<AddLayerNormalization>();
-                fused->epsilon = lnn.get_float("epsilon", 1e-5f);
-                auto plain = std::make_shared<LayerNormalization>();
-                plain->epsilon = fused->epsilon;
-                dead[(size_t)ln] = true; fused_away_++; out_name = lnn.outputs[0]; st.pos = (size_t)ln;
-                st.in.push_back(id_of(lnn.inputs.at(1)));
-                st.in.push_back(lnn.inputs.size() > 2 ? id_of(lnn.inputs[2]) : -1);
-                st.kind_name = "Add+LayerNormalization";
-                st.run = [fused, plain](Context &c, const InputList &in) {
-                    if (require(in, 0).shape() == require(in, 1).shape()) return fused->run(c, in);
-                    OutputList sum = Add().run(c, {in[0], in[1]}); // broadcasting Add: separate kernels
-                    return plain->run(c, {&sum[0], in[2], in[3]});
-                };
-            } else if (n.op_type == "Add" && opt_.fuse && sole_user(out_name, "Softmax") >= 0 &&
-                       m.nodes[(size_t)sole_user(out_name, "Softmax")].get_int("axis", -1) == -1) {
-                // Add -> Softmax(last axis) = AddSoftmax (src/ops/attention.rs:94-156)
-                const long sm = sole_user(out_name, "Softmax");
-                dead[(size_t)sm] = true; fused_away_++; out_name = m.nodes[(size_t)sm].outputs[0]; st.pos = (size_t)sm;
-                st.kind_name = "AddSoftmax";
-                st.run = [](Context &c, const InputList &in) {
-                    const Tensor &a = require(in, 0), &b = require(in, 1);
-                    AddSoftmax fused;
-                    try {
-                        return a.len() >= b.len() ? fused.run(c, {&a, &b}) : fused.run(c, {&b, &a});
-                    } catch (const OpError &e) { // a broadcast the fused kernel does not cover: Add, then Softmax
-                        if (e.kind != OpError::IncompatibleInputShapes) throw;
-                        OutputList sum = Add().run(c, in);
-                        return Softmax().run(c, {&sum[0]});
-                    }
-                };
-            } else if (n.op_type == "LayerNormalization") {
+            } else if (kind == "MatMul") make_matmul_step(st, n, nodes, out_name);
+            else if (kind == "Add" && opt_.fuse && make_add_norm_step(st, n, nodes, out_name)) {} // (any other Add takes the generic path below)
+            else if (kind == "LayerNormalization") {
                 auto op = std::make_shared<LayerNormalization>();
                 op->axis = (int)n.get_int("axis", -1);
                 op->epsilon = n.get_float("epsilon", 1e-5f);
                 st.batch_coupled = op->axis == 0;
                 const std::string nm = st.name;
                 st.run = [this, op, nm](Context &c, const InputList &in) { note_axis("LayerNormalization", nm, op->axis, require(in, 0)); return op->run(c, in); };
-            } else if (n.op_type == "Sigmoid" || n.op_type == "Silu" || n.op_type == "Swish" || n.op_type == "HardSigmoid" || n.op_type == "HardSwish" ||
-                       n.op_type == "LeakyRelu" || n.op_type == "Elu" || n.op_type == "Clip") {
-                Activation act;
-                if (activation_of(n, act)) { // parameters fixed at load time: one rten_hip_activation_f32 launch, nothing read back per run
-                    auto op = std::make_shared<ActivationOp>(act.kind, act.alpha, act.beta);
-                    st.in.resize(1);
-                    st.run = [op](Context &c, const InputList &in) { return op->run(c, in); };
-                } else { // Clip with run-time bounds
-                    auto op = std::make_shared<Clip>();
-                    st.run = [op](Context &c, const InputList &in) { return op->run(c, in); };
-                }
-            } else if (n.op_type == "Gelu" && n.attr("approximate") && n.attr("approximate")->s != "none") {
+            } else if (kind == "Sigmoid" || kind == "Silu" || kind == "Swish" || kind == "HardSigmoid" || kind == "HardSwish" || kind == "LeakyRelu" || kind == "Elu" || kind == "Clip")
+                make_activation_step(st, n);
+            else if (kind == "Gelu" && n.attr("approximate") && n.attr("approximate")->s != "none")
                 throw GraphError("Gelu " + st.name + ": approximate=\"" + n.attr("approximate")->s + "\" is not supported");
-            } else if (n.op_type == "MaxPool" || n.op_type == "AveragePool") {
-                std::vector<int> k = n.get_ints("kernel_shape", {});
-                if (k.size() != 2) throw GraphError(n.op_type + " " + st.name + ": kernel_shape must have 2 values");
-                const std::vector<int> strides = n.get_ints("strides", {1, 1});
-                const Padding pad = padding_of(n, n.op_type.c_str());
-                const bool ceil = n.get_int("ceil_mode", 0) != 0;
-                if (n.outputs.size() > 1 && !n.outputs[1].empty()) throw GraphError("MaxPool " + st.name + ": the Indices output is not supported");
-                if (n.op_type == "MaxPool") {
-                    auto op = std::make_shared<MaxPool>();
-                    op->kernel_size = k; op->strides = strides; op->padding = pad; op->ceil_mode = ceil;
-                    st.run = [op](Context &c, const InputList &in) { return op->run(c, in); };
-                    st.maxpool = op;
-                } else {
-                    auto op = std::make_shared<AveragePool>();
-                    op->kernel_size = k; op->strides = strides; op->padding = pad; op->ceil_mode = ceil;
-                    op->count_include_pad = n.get_int("count_include_pad", 0) != 0;
-                    st.run = [op](Context &c, const InputList &in) { return op->run(c, in); };
-                }
-            } else if (n.op_type == "Einsum") {
+            else if (kind == "MaxPool" || kind == "AveragePool") make_pool_step(st, n);
+            else if (kind == "Einsum") {
                 auto op = std::make_shared<Einsum>();
                 if (!n.attr("equation")) throw GraphError("Einsum " + st.name + ": the equation attribute is missing");
                 op->equation = n.attr("equation")->s;
-                st.run = [op](Context &c, const InputList &in) { return op->run(c, in); };
-            } else if (n.op_type == "ReduceSum" || n.op_type == "ReduceMean") {
-                auto op = std::make_shared<ReduceSum>();
-                op->mean = n.op_type == "ReduceMean";
-                op->keep_dims = n.get_int("keepdims", 1) != 0;
-                op->noop_with_empty_axes = n.get_int("noop_with_empty_axes", 0) != 0;
-                op->axes = n.get_ints("axes", {});
-                if (n.inputs.size() > 1 && !n.inputs[1].empty()) { // opset >= 13: axes as a (constant) input
-                    auto it = ids_.find(n.inputs[1]);
-                    if (it == ids_.end() || !consts_.count(it->second)) throw GraphError(n.op_type + " " + st.name + ": the axes input must be a constant");
-                    for (int32_t v : consts_.at(it->second).to_host<int32_t>()) op->axes.push_back(v);
-                    st.in.resize(1);
-                }
-                st.batch_coupled = op->axes.empty() ? !op->noop_with_empty_axes : std::count(op->axes.begin(), op->axes.end(), 0) != 0; // sums over dim 0
-                const std::string kind = n.op_type, nm = st.name;
-                st.run = [this, op, kind, nm](Context &c, const InputList &in) { for (int a : op->axes) note_axis(kind, nm, a, require(in, 0)); return op->run(c, in); };
-            } else if (n.op_type == "ReduceMax" || n.op_type == "ReduceMin") {
-                auto op = std::make_shared<ReduceMax>();
-                op->min = n.op_type == "ReduceMin";
-                op->keep_dims = n.get_int("keepdims", 1) != 0;
-                op->noop_with_empty_axes = n.get_int("noop_with_empty_axes", 0) != 0;
-                op->axes = n.get_ints("axes", {});
-                if (n.inputs.size() > 1 && !n.inputs[1].empty()) { // opset >= 18: axes as a (constant) input
-                    auto it = ids_.find(n.inputs[1]);
-                    if (it == ids_.end() || !consts_.count(it->second)) throw GraphError(n.op_type + " " + st.name + ": the axes input must be a constant");
-                    for (int32_t v : consts_.at(it->second).to_host<int32_t>()) op->axes.push_back(v);
-                    st.in.resize(1);
-                }
-                st.batch_coupled = op->axes.empty() ? !op->noop_with_empty_axes : std::count(op->axes.begin(), op->axes.end(), 0) != 0; // reduces over dim 0
-                const std::string kind = n.op_type, nm = st.name;
-                auto cache = std::make_shared<HostCache>();
-                st.run = [this, op, kind, nm, cache](Context &c, const InputList &in) {
-                    const Tensor &x = require(in, 0);
-                    for (int a : op->axes) note_axis(kind, nm, a, x);
-                    if (x.host() && x.ndim() > 0 && !(op->axes.empty() && op->noop_with_empty_axes)) { // shape arithmetic: on the host
-                        OutputList o;
-                        o.push_back(materialize(c, hostops::reduce_minmax(*x.host(), resolve_axes(op->axes, x.ndim()), op->keep_dims, op->min), *cache));
-                        return o;
-                    }
-                    return op->run(c, in);
-                };
-            } else if (n.op_type == "ArgMax" || n.op_type == "ArgMin") {
-                if (n.get_int("select_last_index", 0) != 0) throw GraphError(n.op_type + " " + st.name + ": select_last_index is not supported"); // onnx_registry.rs:769
-                auto op = std::make_shared<ArgMax>();
-                op->min = n.op_type == "ArgMin";
-                op->axis = (int)n.get_int("axis", 0);
-                op->keep_dims = n.get_int("keepdims", 1) != 0;
-                st.batch_coupled = op->axis == 0;
-                const std::string kind = n.op_type, nm = st.name;
-                st.run = [this, op, kind, nm](Context &c, const InputList &in) { note_axis(kind, nm, op->axis, require(in, 0)); return op->run(c, in); };
-            } else if (n.op_type == "TopK") {
-                auto op = std::make_shared<TopK>();
-                op->axis = (int)n.get_int("axis", -1);
-                op->largest = n.get_int("largest", 1) != 0;
-                op->sorted = n.get_int("sorted", 1) != 0;
-                if (n.inputs.size() < 2 || n.inputs[1].empty()) throw GraphError("TopK " + st.name + ": the K input is missing");
-                // K is read on the host (no read-back, so the step may be captured): an initializer, a Constant, or shape arithmetic the executor evaluates
-                // on the host.  A graph input is device data at run time: refused here; any other device-computed K is refused by the step when it runs.
-                for (auto &gi : m.inputs)
-                    if (gi.name == n.inputs[1] && !is_const(gi.name))
-                        throw GraphError("TopK " + st.name + ": K must be a constant or computable from the input shapes (it is the graph input \"" + gi.name + "\", device data at run time)");
-                st.batch_coupled = op->axis == 0;
-                const std::string nm = st.name;
-                st.run = [this, op, nm](Context &c, const InputList &in) {
-                    note_axis("TopK", nm, op->axis, require(in, 0));
-                    host_ints(&require(in, 1), "TopK: K"); // throws unless K carries a host value
-                    return op->run(c, in);
-                };
-            } else if (n.op_type == "Softmax") {
-                auto op = std::make_shared<Softmax>();
-                op->axis = (int)n.get_int("axis", -1);
-                st.batch_coupled = op->axis == 0;
-                const std::string nm = st.name;
-                st.run = [this, op, nm](Context &c, const InputList &in) { note_axis("Softmax", nm, op->axis, require(in, 0)); return op->run(c, in); };
-            } else if (n.op_type == "Resize" || n.op_type == "Upsample") {
-                make_resize_step(st, n);
-            } else if (n.op_type == "Split") {
-                make_split_step(st, n);
-            } else if (n.op_type == "Flatten" || n.op_type == "Reshape" || n.op_type == "Squeeze" || n.op_type == "Unsqueeze" || n.op_type == "Identity" ||
-                       n.op_type == "Dropout") {
-                make_view_step(st, n, m);
-            } else if (make_layout_step(st, n)) {
+                run_plainly(st, op);
+            } else if (kind == "ReduceSum" || kind == "ReduceMean" || kind == "ReduceMax" || kind == "ReduceMin") make_reduce_step(st, n);
+            else if (kind == "ArgMax" || kind == "ArgMin" || kind == "TopK" || kind == "Softmax") make_select_step(st, n);
+            else if (kind == "Resize" || kind == "Upsample") make_resize_step(st, n);
+            else if (kind == "Split") make_split_step(st, n);
+            else if (kind == "Flatten" || kind == "Reshape" || kind == "Squeeze" || kind == "Unsqueeze" || kind == "Identity" || kind == "Dropout") make_view_step(st, n);
+            else if (make_layout_step(st, n)) {
                 // Shape / ConstantOfShape / NonZero / Range / Slice / Concat / Expand / Where / comparisons / logic / integer arithmetic / Cast / Gather /
                 // Transpose: host-evaluated when their operands are host values, device kernels otherwise
             } else {
                 static const OpRegistry reg = OpRegistry::with_all_ops();
-                if (!reg.contains(n.op_type))
-                    throw GraphError("node " + st.name + ": operator " + n.op_type + " is not available on the HIP backend (no CPU fallback)");
-                std::shared_ptr<Operator> op(reg.create(n.op_type).release());
-                st.run = [op](Context &c, const InputList &in) { return op->run(c, in); };
+                if (!reg.contains(kind)) throw GraphError("node " + st.name + ": operator " + kind + " is not available on the HIP backend (no CPU fallback)");
+                run_plainly(st, std::shared_ptr<Operator>(reg.create(kind).release()));
             }
             st.out.push_back(id_of(out_name));
             for (size_t k = 1; k < n.outputs.size(); k++) st.out.push_back(n.outputs[k].empty() ? -1 : id_of(n.outputs[k]));
@@ -2280,6 +1985,305 @@ class Graph {
         if (opt_.fuse) { plan_int8_staging(); plan_dql_loaders(); plan_conv_pairs(); }
         for (auto &st : steps_) if (st.kind_name.find("DynamicQuantizeLinear") != std::string::npos) st.batch_coupled = true; // min / max over the whole tensor
         plan_liveness();
+    }
+
+    // Conv (+ Add residual) (+ Relu, or one activation activation_of takes)
+    void make_conv_step(Step &st, const onnx::Node &n, Nodes &nodes, std::string &out_name) {
+        auto op = std::make_shared<Conv>(conv_attrs(n));
+        const size_t at = st.pos;
+        std::string residual;
+        if (opt_.fuse) {
+            const long a = nodes.sole_user(out_name, "Add");
+            if (a >= 0 && nodes[a].inputs.size() == 2) {
+                const std::string other = nodes.other_input(nodes[a], out_name);
+                if (other != out_name && nodes.ready_before(other, at)) { residual = other; nodes.absorb(st, (size_t)a, out_name); }
+            }
+            const long r = nodes.sole_user(out_name, "Relu");
+            if (r >= 0) { op->fuse_relu = true; nodes.absorb(st, (size_t)r, out_name); }
+            Activation act;
+            const long ac = op->fuse_relu ? -1 : nodes.sole_activation(out_name, act);
+            if (ac >= 0) { op->act = act; nodes.absorb(st, (size_t)ac, out_name); }
+        }
+        while (st.in.size() < 3) st.in.push_back(-1);
+        st.in.push_back(residual.empty() ? -1 : id_of(residual));
+        const Tensor *packed = prepacked_weight(n, *op, op->groups == 1, 4);
+        st.kind_name = std::string("Conv") + (residual.empty() ? "" : "+Add") + (op->fuse_relu ? "+Relu" : "") +
+                       (op->act.kind != RTEN_HIP_ACT_NONE ? std::string("+") + activation_name(op->act.kind) : "");
+        st.conv = op;
+        // The Add's other operand is used as the kernel's residual only when it has exactly the conv's output shape
+        // (the kernel indexes it with the output's strides).  Its shape is a run-time fact (no shape inference here), and
+        // it may be a constant or any broadcasting operand -- e.g. the exporter's explicit bias Add([1,O,1,1]) -- so a
+        // mismatch runs the operators as the graph spells them: Conv, broadcasting Add, Relu.  (The constant is NOT
+        // routed to the conv's bias input: the GEMM adds a bias after the first depth block, the graph adds it last.)
+        st.run = [op, packed](Context &c, const InputList &in) {
+            const Tensor *res = in.size() > 3 ? in[3] : nullptr;
+            if (res) {
+                const Tensor &x = require(in, 0), &w = require(in, 1);
+                bool same = res->dtype() == DType::F32 && x.ndim() == 4 && w.ndim() == 4; // 1-D convs with an Add: always unfused
+                if (same) {
+                    const rten_hip_conv2d_desc d = op->geometry(x.shape(), w.shape());
+                    same = res->shape() == std::vector<int64_t>{d.n, d.o, d.out_h, d.out_w};
+                }
+                if (!same) {
+                    Conv plain = *op; plain.fuse_relu = false; plain.act = Activation();
+                    OutputList y = plain.run_packed(c, {in[0], in[1], in.size() > 2 ? in[2] : nullptr}, packed);
+                    OutputList sum = Add().run(c, {&y[0], res});
+                    if (op->act.kind != RTEN_HIP_ACT_NONE) return ActivationOp(op->act.kind, op->act.alpha, op->act.beta).run(c, {&sum[0]});
+                    return op->fuse_relu ? Relu().run(c, {&sum[0]}) : std::move(sum);
+                }
+            }
+            return op->run_packed(c, in, packed);
+        };
+    }
+    // ConvInteger -> Cast -> Mul(scale) (= ConvIntegerToFloat) (+ Add bias constant [1, O, 1, 1]) (+ Add residual) (+ Relu)
+    void make_conv_integer_step(Step &st, const onnx::Node &n, Nodes &nodes, std::string &out_name) {
+        auto op = std::make_shared<ConvInteger>();
+        op->conv = conv_attrs(n);
+        const size_t at = st.pos;
+        std::string scale, bias, residual;
+        bool relu = false;
+        // ConvIntegerToFloat: the Mul's other operand must be a single scale available before the conv runs
+        if (absorb_cast_and_scale(st, nodes, out_name, scale)) {
+            const long add = nodes.sole_user(out_name, "Add");
+            if (add >= 0) { // Add(bias constant [1, O, 1, 1])
+                const std::string b = nodes.other_input(nodes[add], out_name);
+                if (is_const(b)) {
+                    const Tensor &bt = const_of(b);
+                    if (bt.ndim() == 4 && bt.size(0) == 1 && bt.size(2) == 1 && bt.size(3) == 1) { bias = b; nodes.absorb(st, (size_t)add, out_name); }
+                }
+            }
+            const long add2 = bias.empty() ? -1 : nodes.sole_user(out_name, "Add");
+            if (add2 >= 0) {
+                const std::string other = nodes.other_input(nodes[add2], out_name);
+                if (other != out_name && nodes.ready_before(other, at)) { residual = other; nodes.absorb(st, (size_t)add2, out_name); }
+            }
+            const long r = nodes.sole_user(out_name, "Relu");
+            if (r >= 0) { relu = true; nodes.absorb(st, (size_t)r, out_name); }
+        }
+        while (st.in.size() < 4) st.in.push_back(-1);
+        drop_zero_zero_point(st);
+        st.in.push_back(scale.empty() ? -1 : id_of(scale));
+        st.in.push_back(bias.empty() ? -1 : id_of(bias));
+        st.in.push_back(residual.empty() ? -1 : id_of(residual));
+        if (!scale.empty()) st.kind_name = std::string("ConvIntegerToFloat") + (bias.empty() ? "" : "+bias") + (residual.empty() ? "" : "+Add") + (relu ? "+Relu" : "");
+        auto state = std::make_shared<I8Conv>();
+        state->op = op;
+        state->to_float = !scale.empty();
+        state->sg.packed_weight = prepacked_weight(n, *op, op->conv.groups == 1, 4);
+        st.i8 = state;
+        // ConvIntegerToFloatFusion (fusions.rs:1012-1058) fuses only a scale of shape [] or [1] and leaves every other graph
+        // as ConvInteger -> Cast -> Mul.  Shapes are run-time facts here, so the step decides per run: a scalar f32 scale
+        // (or a per-output-channel [1,O,1,1] / [O,1,1] one, which the kernel applies exactly as Cast -> Mul would) with a
+        // bias of O channels and a residual of the output's shape takes the fused kernel; anything else runs the
+        // operators as the graph spells them.
+        state->relu = relu;
+        st.run = [state, relu](Context &c, const InputList &in) {
+            const Tensor *scale = in[4], *bias = in[5], *residual = in[6];
+            if (!scale) return state->op->run_staged(c, InputList(in.begin(), in.begin() + 4), nullptr, nullptr, nullptr, false, state->sg);
+            bool per_channel = false;
+            const bool fused = i8_fused_form(*state, in, per_channel);
+            if (fused) return state->op->run_staged(c, InputList(in.begin(), in.begin() + 4), scale, bias, residual, relu, state->sg, per_channel);
+            ConvInteger::Staging sg = state->sg;
+            sg.stats_out = nullptr; // statistics are accumulated by the float epilogue only
+            OutputList acc = state->op->run_staged(c, InputList(in.begin(), in.begin() + 4), nullptr, nullptr, nullptr, false, sg);
+            Cast cast; cast.to = DType::F32;
+            OutputList f = cast.run(c, {&acc[0]});
+            OutputList y = Mul().run(c, {&f[0], scale});
+            if (bias) y = Add().run(c, {&y[0], bias});
+            if (residual) y = Add().run(c, {&y[0], residual});
+            if (relu) y = Relu().run(c, {&y[0]});
+            return y;
+        };
+    }
+    // MatMulInteger -> Cast -> Mul(scale) (= MatMulIntegerToFloat)
+    void make_matmul_integer_step(Step &st, const onnx::Node &n, Nodes &nodes, std::string &out_name) {
+        auto op = std::make_shared<MatMulInteger>();
+        std::string scale;
+        absorb_cast_and_scale(st, nodes, out_name, scale);
+        while (st.in.size() < 4) st.in.push_back(-1);
+        drop_zero_zero_point(st);
+        st.in.push_back(scale.empty() ? -1 : id_of(scale));
+        if (!scale.empty()) st.kind_name = "MatMulIntegerToFloat";
+        const Tensor *packed = prepacked_weight(n, *op, true, 0); // a constant RHS (PackedBMatrix)
+        // MatMulIntegerToFloatFusion (fusions.rs:960-1009) needs a scale of rank <= 1; the operator then needs length 1 or N.
+        // Decided per run (shapes are run-time facts); otherwise MatMulInteger -> Cast -> Mul as the graph spells it.
+        st.run = [op, packed](Context &c, const InputList &in) {
+            const Tensor *scale = in[4];
+            if (scale) {
+                const Tensor &b = require(in, 1);
+                const int64_t ncols = b.ndim() > 1 ? b.size(b.ndim() - 1) : 1;
+                const bool ok = scale->dtype() == DType::F32 && scale->ndim() <= 1 && (scale->len() == 1 || scale->len() == ncols);
+                if (!ok) {
+                    OutputList acc = op->run_scaled(c, InputList(in.begin(), in.begin() + 4), nullptr, packed);
+                    Cast cast; cast.to = DType::F32;
+                    OutputList f = cast.run(c, {&acc[0]});
+                    return Mul().run(c, {&f[0], scale});
+                }
+            }
+            return op->run_scaled(c, InputList(in.begin(), in.begin() + 4), scale, packed);
+        };
+    }
+    // MatMul (+ Mul / Div by a constant scalar = alpha, MatMulScale fusion) (+ Add of a constant 1-D bias,
+    // MatMulAddFusion) (+ Gelu / Relu as the GEMM epilogue): FusedMatMul (src/ops/matmul.rs:455-510)
+    void make_matmul_step(Step &st, const onnx::Node &, Nodes &nodes, std::string &out_name) {
+        auto op = std::make_shared<FusedMatMul>();
+        std::string bias;
+        if (opt_.fuse) {
+            for (const char *sop : {"Div", "Mul"}) {
+                const long d = nodes.sole_user(out_name, sop);
+                float c = 0.f;
+                if (d >= 0 && nodes[d].inputs[0] == out_name && const_f32_scalar(nodes[d].inputs[1], c) && op->alpha == 1.f) {
+                    op->alpha = std::string(sop) == "Div" ? 1.0f / c : c;
+                    nodes.absorb(st, (size_t)d, out_name);
+                }
+            }
+            const long a = op->alpha == 1.f ? nodes.sole_user(out_name, "Add") : -1;
+            if (a >= 0) {
+                const std::string other = nodes.other_input(nodes[a], out_name);
+                if (is_const(other) && const_of(other).ndim() == 1 && const_of(other).dtype() == DType::F32) {
+                    bias = other;
+                    nodes.absorb(st, (size_t)a, out_name);
+                    const long g = nodes.sole_user(out_name, "Gelu");
+                    if (g >= 0 && !nodes[g].attr("approximate")) { op->act = RTEN_HIP_ACT_GELU; nodes.absorb(st, (size_t)g, out_name); }
+                    const long r = g < 0 ? nodes.sole_user(out_name, "Relu") : -1;
+                    if (r >= 0) { op->act = RTEN_HIP_ACT_RELU; nodes.absorb(st, (size_t)r, out_name); }
+                }
+            }
+            Activation act;
+            const long ac = op->act == RTEN_HIP_ACT_NONE ? nodes.sole_activation(out_name, act) : -1;
+            if (ac >= 0) { op->act = act.kind; op->act_alpha = act.alpha; op->act_beta = act.beta; nodes.absorb(st, (size_t)ac, out_name); }
+        }
+        st.in.resize(2);
+        st.in.push_back(bias.empty() ? -1 : id_of(bias));
+        st.kind_name = std::string(op->alpha != 1.f || !bias.empty() || op->act > RTEN_HIP_ACT_GELU ? "FusedMatMul" : "MatMul") +
+                       (op->act != RTEN_HIP_ACT_NONE ? std::string("+") + activation_name(op->act) : "");
+        auto plan = std::make_shared<GemmPlan>();
+        st.gemm_plan = plan;
+        st.run = [op, plan](Context &c, const InputList &in) {
+            const Tensor *bias = in[2];
+            if (bias && bias->len() != require(in, 1).size(require(in, 1).ndim() - 1)) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast bias to output shape");
+            PlanScope scope(c, *plan);
+            return op->run(c, in);
+        };
+    }
+    // The two fused forms of Add, tried before the generic path.  False: this Add is neither.
+    bool make_add_norm_step(Step &st, const onnx::Node &, Nodes &nodes, std::string &out_name) {
+        const long ln = nodes.sole_user(out_name, "LayerNormalization");
+        if (ln >= 0 && nodes[ln].get_int("axis", -1) == -1 && nodes[ln].inputs[0] == out_name) {
+            // Add(residual) -> LayerNormalization(last axis) as one kernel
+            const onnx::Node &lnn = nodes[ln];
+            auto fused = std::make_shared<AddLayerNormalization>();
+            fused->epsilon = lnn.get_float("epsilon", 1e-5f);
+            auto plain = std::make_shared<LayerNormalization>();
+            plain->epsilon = fused->epsilon;
+            nodes.absorb(st, (size_t)ln, out_name);
+            st.in.push_back(id_of(lnn.inputs.at(1)));
+            st.in.push_back(lnn.inputs.size() > 2 ? id_of(lnn.inputs[2]) : -1);
+            st.kind_name = "Add+LayerNormalization";
+            st.run = [fused, plain](Context &c, const InputList &in) {
+                if (require(in, 0).shape() == require(in, 1).shape()) return fused->run(c, in);
+                OutputList sum = Add().run(c, {in[0], in[1]}); // broadcasting Add: separate kernels
+                return plain->run(c, {&sum[0], in[2], in[3]});
+            };
+            return true;
+        }
+        const long sm = nodes.sole_user(out_name, "Softmax");
+        if (sm >= 0 && nodes[sm].get_int("axis", -1) == -1) {
+            // Add -> Softmax(last axis) = AddSoftmax (src/ops/attention.rs:94-156)
+            nodes.absorb(st, (size_t)sm, out_name);
+            st.kind_name = "AddSoftmax";
+            st.run = [](Context &c, const InputList &in) {
+                const Tensor &a = require(in, 0), &b = require(in, 1);
+                AddSoftmax fused;
+                try {
+                    return a.len() >= b.len() ? fused.run(c, {&a, &b}) : fused.run(c, {&b, &a});
+                } catch (const OpError &e) { // a broadcast the fused kernel does not cover: Add, then Softmax
+                    if (e.kind != OpError::IncompatibleInputShapes) throw;
+                    OutputList sum = Add().run(c, in);
+                    return Softmax().run(c, {&sum[0]});
+                }
+            };
+            return true;
+        }
+        return false;
+    }
+    void make_activation_step(Step &st, const onnx::Node &n) {
+        Activation act;
+        if (activation_of(n, act)) { // parameters fixed at load time: one rten_hip_activation_f32 launch, nothing read back per run
+            st.in.resize(1);
+            run_plainly(st, std::make_shared<ActivationOp>(act.kind, act.alpha, act.beta));
+        } else run_plainly(st, std::make_shared<Clip>()); // Clip with run-time bounds
+    }
+    void make_pool_step(Step &st, const onnx::Node &n) {
+        std::vector<int> k = n.get_ints("kernel_shape", {});
+        if (k.size() != 2) throw GraphError(n.op_type + " " + st.name + ": kernel_shape must have 2 values");
+        const std::vector<int> strides = n.get_ints("strides", {1, 1});
+        const Padding pad = padding_of(n, n.op_type.c_str());
+        const bool ceil = n.get_int("ceil_mode", 0) != 0;
+        if (n.outputs.size() > 1 && !n.outputs[1].empty()) throw GraphError("MaxPool " + st.name + ": the Indices output is not supported");
+        auto finish = [&](auto op) { op->kernel_size = k; op->strides = strides; op->padding = pad; op->ceil_mode = ceil; run_plainly(st, op); return op; };
+        if (n.op_type == "MaxPool") st.maxpool = finish(std::make_shared<MaxPool>());
+        else finish(std::make_shared<AveragePool>())->count_include_pad = n.get_int("count_include_pad", 0) != 0;
+    }
+    // ReduceSum / ReduceMean, and ReduceMax / ReduceMin (which shape arithmetic sometimes applies to a shape vector: those run on the host)
+    void make_reduce_step(Step &st, const onnx::Node &n) {
+        const std::string kind = n.op_type, nm = st.name;
+        if (kind == "ReduceSum" || kind == "ReduceMean") {
+            auto op = std::make_shared<ReduceSum>();
+            op->mean = kind == "ReduceMean";
+            read_reduce_attrs(st, n, *op);
+            st.run = [this, op, kind, nm](Context &c, const InputList &in) { for (int a : op->axes) note_axis(kind, nm, a, require(in, 0)); return op->run(c, in); };
+            return;
+        }
+        auto op = std::make_shared<ReduceMax>();
+        op->min = kind == "ReduceMin";
+        read_reduce_attrs(st, n, *op);
+        auto cache = std::make_shared<HostCache>();
+        st.run = [this, op, kind, nm, cache](Context &c, const InputList &in) {
+            const Tensor &x = require(in, 0);
+            for (int a : op->axes) note_axis(kind, nm, a, x);
+            if (x.host() && x.ndim() > 0 && !(op->axes.empty() && op->noop_with_empty_axes)) { // shape arithmetic: on the host
+                OutputList o;
+                o.push_back(materialize(c, hostops::reduce_minmax(*x.host(), resolve_axes(op->axes, x.ndim()), op->keep_dims, op->min), *cache));
+                return o;
+            }
+            return op->run(c, in);
+        };
+    }
+    // ArgMax / ArgMin, TopK and Softmax: one axis each, noted per run in case it resolves to dim 0
+    void make_select_step(Step &st, const onnx::Node &n) {
+        const std::string kind = n.op_type, nm = st.name;
+        if (kind == "ArgMax" || kind == "ArgMin") {
+            if (n.get_int("select_last_index", 0) != 0) throw GraphError(kind + " " + st.name + ": select_last_index is not supported"); // onnx_registry.rs:769
+            auto op = std::make_shared<ArgMax>();
+            op->min = kind == "ArgMin";
+            op->axis = (int)n.get_int("axis", 0);
+            op->keep_dims = n.get_int("keepdims", 1) != 0;
+            st.batch_coupled = op->axis == 0;
+            st.run = [this, op, kind, nm](Context &c, const InputList &in) { note_axis(kind, nm, op->axis, require(in, 0)); return op->run(c, in); };
+        } else if (kind == "TopK") {
+            auto op = std::make_shared<TopK>();
+            op->axis = (int)n.get_int("axis", -1);
+            op->largest = n.get_int("largest", 1) != 0;
+            op->sorted = n.get_int("sorted", 1) != 0;
+            if (n.inputs.size() < 2 || n.inputs[1].empty()) throw GraphError("TopK " + st.name + ": the K input is missing");
+            // K is read on the host (no read-back, so the step may be captured): an initializer, a Constant, or shape arithmetic the executor evaluates
+            // on the host.  A graph input is device data at run time: refused here; any other device-computed K is refused by the step when it runs.
+            for (auto &gi : inputs_)
+                if (gi.name == n.inputs[1] && !is_const(gi.name))
+                    throw GraphError("TopK " + st.name + ": K must be a constant or computable from the input shapes (it is the graph input \"" + gi.name + "\", device data at run time)");
+            st.batch_coupled = op->axis == 0;
+            st.run = [this, op, nm](Context &c, const InputList &in) {
+                note_axis("TopK", nm, op->axis, require(in, 0));
+                host_ints(&require(in, 1), "TopK: K"); // throws unless K carries a host value
+                return op->run(c, in);
+            };
+        } else {
+            auto op = std::make_shared<Softmax>();
+            op->axis = (int)n.get_int("axis", -1);
+            st.batch_coupled = op->axis == 0;
+            st.run = [this, op, nm](Context &c, const InputList &in) { note_axis("Softmax", nm, op->axis, require(in, 0)); return op->run(c, in); };
+        }
     }
 
     // Layout / logic operators around the hot path (src/ops/layout.rs, slice.rs, concat.rs, gather.rs, convert.rs, binary_elementwise.rs, non_zero.rs,
@@ -2512,10 +2516,8 @@ class Graph {
         if (sa) st.in.resize(1);
         // a constant scales / sizes operand of length 1 or 2 means a 1-D / 2-D input, whose dim 0 is resampled
         int64_t rank = sa ? (int64_t)attr_scales.size() : -1;
-        for (size_t k = scales_at; !sa && rank < 0 && k < n.inputs.size() && k <= scales_at + 1; k++) {
-            auto it = n.inputs[k].empty() ? ids_.end() : ids_.find(n.inputs[k]);
-            if (it != ids_.end() && consts_.count(it->second) && consts_.at(it->second).len() > 0) rank = consts_.at(it->second).len();
-        }
+        for (size_t k = scales_at; !sa && rank < 0 && k < n.inputs.size() && k <= scales_at + 1; k++)
+            if (is_const(n.inputs[k]) && const_of(n.inputs[k]).len() > 0) rank = const_of(n.inputs[k]).len();
         st.batch_coupled = rank == 1 || rank == 2;
         const bool two_input = scales_at == 1;
         st.run = [this, op, kind, name, sa_given = sa != nullptr, attr_scales, scales_at, two_input](Context &c, const InputList &in) {
@@ -2568,21 +2570,18 @@ class Graph {
     }
 
     // Shape-only operators: the output aliases the input's buffer (src/ops/layout.rs reshapes in place when it can).
-    void make_view_step(Step &st, const onnx::Node &n, const onnx::Model &m) {
-        (void)m;
+    void make_view_step(Step &st, const onnx::Node &n) {
         const std::string kind = n.op_type;
         const int axis = (int)n.get_int("axis", 1);
         std::vector<int64_t> spec; // Reshape target / (Un)Squeeze axes from a constant input (opset >= 13) or the attribute
         bool have_spec = false;
         bool runtime_spec = false; // the shape / axes operand is computed by the graph (shape arithmetic): read from its host value at run time
         if (n.inputs.size() > 1 && !n.inputs[1].empty()) {
-            auto it = ids_.find(n.inputs[1]);
-            if (it == ids_.end() || !consts_.count(it->second)) {
+            if (!is_const(n.inputs[1])) {
                 runtime_spec = true;
                 st.in.resize(2);
             } else {
-                const Tensor &t = consts_.at(it->second);
-                for (int32_t v : t.to_host<int32_t>()) spec.push_back(v);
+                for (int32_t v : const_of(n.inputs[1]).to_host<int32_t>()) spec.push_back(v);
                 st.in.resize(1);
             }
             have_spec = true;
