@@ -1373,23 +1373,32 @@ class Graph {
         };
     }
 
-    static Padding padding_of(const onnx::Node &n, const char *op) {
+    // `spatial`: the number of spatial axes the node's attributes are written for (2, or 1 for a 1-D convolution)
+    static Padding padding_of(const onnx::Node &n, const char *op, size_t spatial = 2) {
         const onnx::Attr *ap = n.attr("auto_pad");
         if (ap && !ap->s.empty() && ap->s != "NOTSET") {
             if (ap->s == "SAME_UPPER") return Padding::Same();
-            if (ap->s == "VALID") return Padding::Fixed({0, 0, 0, 0});
+            if (ap->s == "VALID") return Padding::Fixed(std::vector<int>(2 * spatial, 0));
             throw GraphError(std::string(op) + " " + n.name + ": auto_pad " + ap->s + " is not supported");
         }
-        std::vector<int> p = n.get_ints("pads", {0, 0, 0, 0});
-        if (p.size() != 4) throw GraphError(std::string(op) + " " + n.name + ": only 2-D spatial operators are supported");
-        return Padding::Fixed({p[0], p[1], p[2], p[3]}); // ONNX [top, left, bottom, right] == the reference's order
+        std::vector<int> p = n.get_ints("pads", std::vector<int>(2 * spatial, 0));
+        if (p.size() != 2 * spatial)
+            throw GraphError(std::string(op) + " " + n.name + (spatial == 1 ? ": a 1-D operator takes 2 pad values" : ": only 2-D spatial operators are supported"));
+        return Padding::Fixed(p); // ONNX [top, left, bottom, right] == the reference's order; 1-D: [begin, end]
     }
-    static Conv conv_attrs(const onnx::Node &n) {
+    // A 1-D Conv node keeps one-axis attributes, defaults included: the operator expands a [N, C, W] input to 2-D itself (src/ops/conv.rs:142-182) and
+    // asks for exactly these lengths.  `weight_rank`: the rank of a constant weight (3 decides for 1-D, 4 for 2-D); 0, a run-time weight: an
+    // attribute of one-axis length (kernel_shape / strides / dilations of one value, pads of two) decides.
+    static Conv conv_attrs(const onnx::Node &n, int weight_rank = 0) {
         Conv c;
+        const bool hinted = n.get_ints("kernel_shape", {}).size() == 1 || n.get_ints("strides", {}).size() == 1 || n.get_ints("dilations", {}).size() == 1 ||
+                            n.get_ints("pads", {}).size() == 2;
+        const bool one_d = weight_rank ? weight_rank == 3 : hinted;
+        const std::vector<int> ones(one_d ? 1 : 2, 1);
         c.groups = (int)n.get_int("group", 1);
-        c.dilations = n.get_ints("dilations", {1, 1});
-        c.strides = n.get_ints("strides", {1, 1});
-        c.padding = padding_of(n, "Conv");
+        c.dilations = n.get_ints("dilations", ones);
+        c.strides = n.get_ints("strides", ones);
+        c.padding = padding_of(n, "Conv", one_d ? 1 : 2);
         return c;
     }
 
@@ -1989,7 +1998,7 @@ class Graph {
 
     // Conv (+ Add residual) (+ Relu, or one activation activation_of takes)
     void make_conv_step(Step &st, const onnx::Node &n, Nodes &nodes, std::string &out_name) {
-        auto op = std::make_shared<Conv>(conv_attrs(n));
+        auto op = std::make_shared<Conv>(conv_attrs(n, n.inputs.size() > 1 && is_const(n.inputs[1]) ? const_of(n.inputs[1]).ndim() : 0));
         const size_t at = st.pos;
         std::string residual;
         if (opt_.fuse) {
@@ -2131,9 +2140,14 @@ class Graph {
         if (opt_.fuse) {
             for (const char *sop : {"Div", "Mul"}) {
                 const long d = nodes.sole_user(out_name, sop);
+                const bool div = std::string(sop) == "Div";
                 float c = 0.f;
-                if (d >= 0 && nodes[d].inputs[0] == out_name && const_f32_scalar(nodes[d].inputs[1], c) && op->alpha == 1.f) {
-                    op->alpha = std::string(sop) == "Div" ? 1.0f / c : c;
+                if (d < 0 || nodes[d].inputs.size() != 2 || op->alpha != 1.f) continue;
+                // the product on the left and the scalar on the right, or -- Mul only -- the other way round (get_scale_factor, fusions.rs:884-906)
+                const bool right = nodes[d].inputs[0] == out_name && const_f32_scalar(nodes[d].inputs[1], c);
+                const bool left = !right && !div && nodes[d].inputs[1] == out_name && const_f32_scalar(nodes[d].inputs[0], c);
+                if (right || left) {
+                    op->alpha = div ? 1.0f / c : c;
                     nodes.absorb(st, (size_t)d, out_name);
                 }
             }
@@ -2195,12 +2209,15 @@ class Graph {
             st.run = [](Context &c, const InputList &in) {
                 const Tensor &a = require(in, 0), &b = require(in, 1);
                 AddSoftmax fused;
+                const Tensor &x = a.len() >= b.len() ? a : b, &addend = a.len() >= b.len() ? b : a;
+                auto unfused = [&] { OutputList sum = Add().run(c, in); return Softmax().run(c, {&sum[0]}); };
+                // an addend of higher rank gives the sum that rank -- [R, C] + [1, 1, C] is [1, R, C] -- which the fused kernel's output, shaped like x, is not
+                if (addend.ndim() > x.ndim()) return unfused();
                 try {
-                    return a.len() >= b.len() ? fused.run(c, {&a, &b}) : fused.run(c, {&b, &a});
+                    return fused.run(c, {&x, &addend});
                 } catch (const OpError &e) { // a broadcast the fused kernel does not cover: Add, then Softmax
                     if (e.kind != OpError::IncompatibleInputShapes) throw;
-                    OutputList sum = Add().run(c, in);
-                    return Softmax().run(c, {&sum[0]});
+                    return unfused();
                 }
             };
             return true;

@@ -1,0 +1,1135 @@
+"""Seeded generator of small adversarial ONNX graphs for the graph executor (include/rten_hip_graph.hpp), and a node-by-node interpreter of them.
+
+A graph is assembled from MOTIFS -- one fusable pattern of Graph::compile each, optionally carrying one SPOILER that must disable or reroute the
+fusion -- joined by inert glue.  `ROWS` is the table of (motif, variant) pairs; every row has one hand-written minimal graph (`hand_case`) and occurs
+again inside the random graphs of `make_case(seed)`.  Each motif records in `Case.expect` what the executor's plan must look like: how many nodes the
+fusion passes fold away (`folded`) and the kinds of the fused steps (`kinds`).
+
+`evaluate(case, binding, fused)` walks the node list once and evaluates every node by itself on the CPU oracle (oracle/ref.py, oracle/einsum.py), the
+numpy restatements in tests/ (select_rules.py, test_gpu_activations.np_act) or plain numpy (single IEEE operations and layout ops are exact): no buffer
+reuse, no views, no reordering.  Its semantics are the reference's.  The executor's own fusions are bit-identical to the operators they replace, so
+they need no rule here; the reference's optimiser changes arithmetic in two places, and the interpreter applies those rules exactly where the
+reference's pattern matches (`_reference_matmul_fusions`):
+  * MatMulAddFusion  (src/optimize/fusions.rs:806-847): Add(MatMul(a, b), bias) with a constant rank-1 bias -> FusedMatMul(a, b, bias); the GEMM adds
+    the bias after the FIRST depth block of 256 (rten-gemm/src/lib.rs:876-891), not after the last, so K > 256 rounds differently;
+  * MatMulScaleFusion (src/optimize/fusions.rs:855-960): Mul(MatMul, c), Mul(c, MatMul) or Div(MatMul, c) with a constant scalar c -> FusedMatMul with
+    alpha = c or 1 / c; alpha is applied per depth block and a division becomes a multiplication by the rounded reciprocal.
+With fused=False (the executor's --no-fuse mode) every node is evaluated as the graph spells it; cases where the two differ are exactly the MatMul
+motif's (`Case.expect["modes_differ"]` says so).
+  * A fused bias whose length is not N: the reference's FusedMatMul reaches gemm's WrongBiasSize ("bias vector length is incorrect",
+    rten-gemm/src/lib.rs:809-816) through an unwrap (src/ops/matmul.rs:361-374), i.e. it does not run the graph; the executor reports
+    IncompatibleInputShapes "Cannot broadcast bias to output shape".  Pinned as an expected error of the fused modes.
+
+`evaluate64` is an independent float64 evaluation (numpy / torch-CPU only, nothing shared with oracle/) used by tests/test_graph_fuzz_oracle.py.
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from rten_amd import onnx_writer as ow  # noqa: E402
+
+F = np.float32
+N_SEEDS = 64          # the committed random corpus: make_case(0) .. make_case(N_SEEDS - 1)
+MAX_ELEMS = 1 << 16   # no tensor of a generated graph is larger
+
+ACT_KINDS = ("Sigmoid", "Silu", "Swish", "HardSigmoid", "HardSwish", "LeakyRelu", "Elu", "Clip")
+# kinds of fused steps as Graph::compile names them; plain operators are not listed in Case.expect["kinds"]
+FUSED_PREFIXES = ("FusedMatMul", "AddSoftmax", "ConvIntegerToFloat", "MatMulIntegerToFloat")
+
+
+def is_fused_kind(kind):
+    return "+" in kind or kind.startswith(FUSED_PREFIXES)
+
+
+class Case:
+    def __init__(self, name):
+        self.name = name
+        self.nodes = []          # dicts: op, inputs, outputs, attrs, name
+        self.inits = {}          # name -> ndarray (insertion order = file order)
+        self.input_specs = []    # (name, declared dims)
+        self.bindings = [{}]     # one dict of named numpy inputs per run; more than one when a dynamic axis is bound at several sizes
+        self.outputs = []        # ordered graph output names (a name may occur twice)
+        self.expect = {"rows": [], "folded": 0, "kinds": [], "error": None, "modes_differ": None}
+        self.onnx = b""
+
+    @property
+    def inputs(self):
+        return self.bindings[0]
+
+
+# ------------------------------------------------------------------------------------------------ node-by-node evaluation (f32, the oracle)
+def _act32(op, x, attrs, consts):
+    from rten_amd import lib as L
+    from tests.test_gpu_activations import np_act, FMAX
+    if op == "Relu":
+        return np_act(L.ACT_RELU, x)
+    if op == "Gelu":
+        return np_act(L.ACT_GELU, x)
+    if op == "Sigmoid":
+        return np_act(L.ACT_SIGMOID, x)
+    if op == "Silu":
+        return np_act(L.ACT_SILU, x)
+    if op == "Swish":
+        return np_act(L.ACT_SWISH, x, attrs.get("alpha", 1.0))
+    if op == "HardSigmoid":
+        return np_act(L.ACT_HARD_SIGMOID, x, attrs.get("alpha", 0.2), attrs.get("beta", 0.5))
+    if op == "HardSwish":
+        return np_act(L.ACT_HARD_SWISH, x)
+    if op == "LeakyRelu":
+        return np_act(L.ACT_LEAKY_RELU, x, attrs.get("alpha", 0.01))
+    if op == "Elu":
+        return np_act(L.ACT_ELU, x, attrs.get("alpha", 1.0))
+    if op == "Clip":
+        lo = consts[0] if consts and consts[0] is not None else -FMAX
+        hi = consts[1] if len(consts) > 1 and consts[1] is not None else FMAX
+        return np_act(L.ACT_CLIP, x, float(lo), float(hi))
+    raise KeyError(op)
+
+
+def _conv_geometry(x, w, attrs):
+    """(x4, w4, pads4, strides2, dilations2, one_d) of a 1-D or 2-D Conv / ConvInteger node."""
+    one_d = x.ndim == 3
+    nsp = 1 if one_d else 2
+    pads = list(attrs.get("pads", [0] * (2 * nsp)))
+    strides = list(attrs.get("strides", [1] * nsp))
+    dil = list(attrs.get("dilations", [1] * nsp))
+    if one_d:  # src/ops/conv.rs:142-182: a 1-D convolution is the 2-D one on [N, C, 1, L]
+        return x[:, :, None, :], w[:, :, None, :], (0, pads[0], 0, pads[1]), (1, strides[0]), (1, dil[0]), True
+    return x, w, tuple(pads), tuple(strides), tuple(dil), False
+
+
+def _slice_np(x, starts, ends, axes, steps):
+    sl = [slice(None)] * x.ndim
+    for s, e, a, st in zip(starts, ends, axes, steps):
+        sl[int(a)] = slice(int(s), int(e), int(st))
+    return np.ascontiguousarray(x[tuple(sl)])
+
+
+def _layout_op(op, ins, attrs):
+    """Operators that only move or index data, shared by both evaluators' callers through plain numpy (exact in any precision)."""
+    x = ins[0]
+    if op == "Identity":
+        return [x.copy()]
+    if op == "Reshape":
+        shape = [x.shape[i] if d == 0 else int(d) for i, d in enumerate(np.asarray(ins[1]).ravel())]
+        return [x.reshape(shape)]
+    if op == "Flatten":
+        a = attrs.get("axis", 1)
+        a = a + x.ndim if a < 0 else a
+        return [x.reshape(int(np.prod(x.shape[:a], dtype=np.int64)), -1)]
+    if op == "Squeeze":
+        return [np.squeeze(x, tuple(int(a) for a in np.asarray(ins[1]).ravel()))]
+    if op == "Unsqueeze":
+        y = x
+        nd = x.ndim + np.asarray(ins[1]).size
+        for a in sorted(int(a) % nd for a in np.asarray(ins[1]).ravel()):
+            y = np.expand_dims(y, a)
+        return [y]
+    if op == "Transpose":
+        return [np.ascontiguousarray(np.transpose(x, attrs.get("perm")))]
+    if op == "Concat":
+        return [np.concatenate(ins, axis=attrs["axis"])]
+    if op == "Slice":
+        n = len(ins[1])
+        axes = ins[3] if len(ins) > 3 and ins[3] is not None else np.arange(n)
+        steps = ins[4] if len(ins) > 4 and ins[4] is not None else np.ones(n, np.int64)
+        return [_slice_np(x, ins[1], ins[2], axes, steps)]
+    if op == "Split":
+        cuts = np.cumsum(np.asarray(ins[1]).ravel())[:-1]
+        return [np.ascontiguousarray(p) for p in np.split(x, cuts, axis=attrs.get("axis", 0))]
+    if op == "Shape":
+        return [np.array(x.shape, np.int64)]
+    if op == "Gather":
+        return [np.take(x, np.asarray(ins[1]), axis=attrs.get("axis", 0))]
+    return None
+
+
+LAYOUT_OPS = ("Identity", "Reshape", "Flatten", "Squeeze", "Unsqueeze", "Transpose", "Concat", "Slice", "Split", "Shape", "Gather")
+
+
+def eval_node(node, ins):
+    """One node on the f32 oracle.  `ins`: the input arrays (None for an omitted optional input).  Returns the list of outputs."""
+    from oracle import einsum as OE
+    from oracle import ref
+    from tests import select_rules as SR
+    op, attrs = node["op"], node["attrs"]
+    if op in LAYOUT_OPS:
+        return _layout_op(op, ins, attrs)
+    x = ins[0]
+    with np.errstate(all="ignore"):
+        if op in ("Add", "Sub", "Mul", "Div"):  # one correctly rounded IEEE operation per element: numpy is exact
+            fn = {"Add": np.add, "Sub": np.subtract, "Mul": np.multiply, "Div": np.divide}[op]
+            return [np.asarray(fn(ins[0], ins[1]), ins[0].dtype)]
+        if op == "Conv":
+            x4, w4, pads, strides, dil, one_d = _conv_geometry(x, ins[1], attrs)
+            y = ref.conv2d_f32(x4, w4, ins[2] if len(ins) > 2 else None, pads=pads, strides=strides, dilations=dil, groups=attrs.get("group", 1))
+            return [y[:, :, 0, :] if one_d else y]
+        if op == "ConvInteger":
+            x4, w4, pads, strides, dil, _ = _conv_geometry(x, ins[1], attrs)
+            assert not any(pads), "the corpus keeps int8 convolutions unpadded"
+            wzp = ins[3] if len(ins) > 3 and ins[3] is not None else None
+            return [ref.conv2d_int8(x4, w4, x_zp=int(ins[2]), w_zp=wzp, pads=pads, strides=strides, dilations=dil, groups=attrs.get("group", 1))]
+        if op == "Cast":
+            assert attrs["to"] == ow.FLOAT
+            return [x.astype(F)]
+        if op == "DynamicQuantizeLinear":
+            q, s, z = ref.dynamic_quantize_linear(x)
+            return [q, np.asarray(s, F), np.asarray(z, np.uint8)]
+        if op == "MatMul":
+            return [ref.matmul_f32(ins[0], ins[1])]
+        if op == "FusedMatMul":  # only ever made by _reference_matmul_fusions
+            return [ref.matmul_f32(ins[0], ins[1], alpha=attrs.get("alpha", 1.0), bias=ins[2] if len(ins) > 2 else None)]
+        if op == "Gemm":
+            a = ins[0].T if attrs.get("transA", 0) else ins[0]
+            b = ins[1].T if attrs.get("transB", 0) else ins[1]
+            if len(ins) > 2 and ins[2] is not None:
+                c = np.broadcast_to(ins[2], (a.shape[0], b.shape[1])).astype(F)
+                return [ref.gemm_f32(a, b, c=c, alpha=attrs.get("alpha", 1.0), beta=attrs.get("beta", 1.0))]
+            return [ref.gemm_f32(a, b, alpha=attrs.get("alpha", 1.0), beta=0.0)]
+        if op == "LayerNormalization":
+            a = attrs.get("axis", -1)
+            a = a + x.ndim if a < 0 else a
+            cols = int(np.prod(x.shape[a:], dtype=np.int64))
+            bias = ins[2].reshape(-1) if len(ins) > 2 and ins[2] is not None else None
+            return [ref.layer_norm(x.reshape(-1, cols), ins[1].reshape(-1), bias, eps=attrs.get("epsilon", 1e-5)).reshape(x.shape)]
+        if op == "Softmax":
+            a = attrs.get("axis", -1)
+            return [np.ascontiguousarray(np.moveaxis(ref.softmax(np.ascontiguousarray(np.moveaxis(x, a, -1))), -1, a))]
+        if op == "MaxPool":
+            return [ref.max_pool(x, attrs["kernel_shape"], attrs.get("strides", [1, 1]), attrs.get("pads", [0, 0, 0, 0]))]
+        if op == "AveragePool":
+            return [ref.average_pool(x, attrs["kernel_shape"], attrs.get("strides", [1, 1]), attrs.get("pads", [0, 0, 0, 0]))]
+        if op == "GlobalAveragePool":
+            return [ref.global_average_pool(x)]
+        if op == "ReduceSum":
+            return [OE.reduce_sum(x, [int(a) for a in ins[1]], bool(attrs.get("keepdims", 1)))]
+        if op == "ReduceMean":
+            return [OE.reduce_mean(x, list(attrs["axes"]), bool(attrs.get("keepdims", 1)))]
+        if op == "Tanh":
+            return [ref.tanh(x)]
+        if op == "ArgMax":
+            return [SR.arg_minmax(x, attrs.get("axis", 0), bool(attrs.get("keepdims", 1)), "max")]
+        if op == "TopK":
+            v, i = SR.topk(x, int(np.asarray(ins[1]).ravel()[0]), attrs.get("axis", -1), bool(attrs.get("largest", 1)))
+            return [v, i]
+        return [_act32(op, x, attrs, ins[1:])]
+
+
+def _users(case):
+    users = {}
+    for i, n in enumerate(case.nodes):
+        for s in n["inputs"]:
+            if s:
+                users.setdefault(s, []).append(i)
+    return users
+
+
+def _scalar_const(case, name):
+    a = case.inits.get(name)
+    return None if a is None or a.dtype != F or a.size != 1 else F(a.reshape(-1)[0])
+
+
+def _reference_matmul_fusions(case):
+    """{node index: replacement} for the two arithmetic-changing fusions of the reference (module docstring).  A replacement is ("skip",) for an
+    absorbed MatMul or (alpha, bias name or None, a, b) for the Mul / Div / Add that becomes the FusedMatMul's output."""
+    users, outs = _users(case), set(case.outputs)
+    producer = {o: i for i, n in enumerate(case.nodes) for o in n["outputs"]}
+    plan = {}
+    for i, n in enumerate(case.nodes):
+        if n["op"] != "MatMul":
+            continue
+        y = n["outputs"][0]
+        if y in outs or len(users.get(y, [])) != 1:  # a fusion never removes a value somebody else reads
+            continue
+        u = case.nodes[users[y][0]]
+        a, b = n["inputs"]
+        if u["op"] in ("Mul", "Div"):  # fusions.rs:884-906: Mul takes the scalar on either side, Div on the right only
+            lhs, rhs = u["inputs"]
+            c = _scalar_const(case, rhs) if lhs == y else (_scalar_const(case, lhs) if u["op"] == "Mul" else None)
+            if c is None or lhs == rhs:
+                continue
+            alpha = F(1.0) / c if u["op"] == "Div" else c
+            if alpha == F(1.0):  # fusions.rs:951-954
+                continue
+            plan[i], plan[users[y][0]] = ("skip",), (float(alpha), None, a, b)
+        elif u["op"] == "Add":  # fusions.rs:815-846
+            other = u["inputs"][1] if u["inputs"][0] == y else u["inputs"][0]
+            if other in case.inits and case.inits[other].ndim == 1 and other not in producer and other != y:
+                plan[i], plan[users[y][0]] = ("skip",), (1.0, other, a, b)
+    return plan
+
+
+class ExpectedError(Exception):
+    """The graph must be refused with this message (Case.expect["error"])."""
+
+
+def evaluate(case, binding=0, fused=True):
+    """{value name: ndarray} of every value of the graph, node by node.  fused=False: the --no-fuse expectation."""
+    vals = dict(case.inits)
+    vals.update(case.bindings[binding])
+    plan = _reference_matmul_fusions(case) if fused else {}
+    for i, n in enumerate(case.nodes):
+        r = plan.get(i)
+        if r == ("skip",):
+            continue
+        if r is not None:
+            alpha, bias, a, b = r
+            if bias is not None and vals[bias].size != vals[b].shape[-1]:
+                raise ExpectedError("Cannot broadcast bias to output shape")
+            node = {"op": "FusedMatMul", "attrs": {"alpha": alpha}}
+            out = eval_node(node, [vals[a], vals[b]] + ([vals[bias]] if bias is not None else []))
+        else:
+            out = eval_node(n, [vals[s] if s else None for s in n["inputs"]])
+        for name, v in zip(n["outputs"], out):
+            if name:
+                vals[name] = v
+    return vals
+
+
+# ------------------------------------------------------------------------------------------------ independent float64 evaluation
+def evaluate64(case, binding=0, teacher=None):
+    """Every value in float64 with numpy / torch-CPU only.  Integer-valued results (u8 codes, zero points, indices) cannot be carried in a
+    different precision: they are computed here for the comparison and then replaced by `teacher`'s (the f32 interpreter's) values, so that one
+    rounding tie does not spread.  Returns (values, ties): ties[name] is a boolean mask of the elements of an integer output whose float64
+    decision is within `TIE_MARGIN` of flipping."""
+    import torch
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64))
+    vals, ties = {}, {}
+    for k, v in list(case.inits.items()) + list(case.bindings[binding].items()):
+        vals[k] = v.astype(np.float64) if v.dtype == F else v
+    for n in case.nodes:
+        op, attrs = n["op"], n["attrs"]
+        ins = [vals[s] if s else None for s in n["inputs"]]
+        x = ins[0]
+        with np.errstate(all="ignore"):
+            if op in LAYOUT_OPS:
+                out = _layout_op(op, ins, attrs)
+            elif op in ("Add", "Sub", "Mul", "Div"):
+                out = [{"Add": np.add, "Sub": np.subtract, "Mul": np.multiply, "Div": np.divide}[op](ins[0], ins[1])]
+            elif op in ("Conv", "ConvInteger"):
+                w = ins[1].astype(np.float64)
+                xx = x.astype(np.float64)
+                if op == "ConvInteger":
+                    xx = xx - float(ins[2])
+                    if len(ins) > 3 and ins[3] is not None:
+                        w = w - np.asarray(ins[3], np.float64).reshape(-1, *([1] * (w.ndim - 1)))
+                nsp = x.ndim - 2
+                pads = list(attrs.get("pads", [0] * (2 * nsp)))
+                xp = np.pad(xx, [(0, 0), (0, 0)] + [(pads[k], pads[k + nsp]) for k in range(nsp)])
+                conv = torch.nn.functional.conv1d if nsp == 1 else torch.nn.functional.conv2d
+                b = T(ins[2]) if op == "Conv" and len(ins) > 2 and ins[2] is not None else None
+                y = conv(T(xp), T(w), b, stride=tuple(attrs.get("strides", [1] * nsp)), dilation=tuple(attrs.get("dilations", [1] * nsp)), groups=attrs.get("group", 1)).numpy()
+                out = [np.rint(y).astype(np.int32) if op == "ConvInteger" else y]
+            elif op == "Cast":
+                out = [x.astype(np.float64)]
+            elif op == "DynamicQuantizeLinear":  # the ONNX definition
+                lo, hi = min(0.0, float(x.min())), max(0.0, float(x.max()))
+                s = (hi - lo) / 255.0
+                zf = np.clip(-lo / s, 0, 255) if s else 0.0
+                z = np.rint(zf)
+                qf = x / s + z if s else np.zeros_like(x)
+                out = [np.clip(np.rint(qf), 0, 255).astype(np.uint8), np.float64(s), np.uint8(z)]
+                ties[n["outputs"][0]] = np.abs(np.abs(qf - np.floor(qf)) - 0.5) < TIE_MARGIN * (1.0 + np.abs(qf))
+                ties[n["outputs"][2]] = np.asarray(abs(abs(zf - np.floor(zf)) - 0.5) < TIE_MARGIN * (1.0 + abs(zf)))
+            elif op == "MatMul":
+                out = [np.matmul(ins[0], ins[1])]
+            elif op == "Gemm":
+                a = ins[0].T if attrs.get("transA", 0) else ins[0]
+                b = ins[1].T if attrs.get("transB", 0) else ins[1]
+                y = attrs.get("alpha", 1.0) * (a @ b)
+                out = [y + attrs.get("beta", 1.0) * ins[2] if len(ins) > 2 and ins[2] is not None else y]
+            elif op == "LayerNormalization":
+                a = attrs.get("axis", -1) % x.ndim
+                ax = tuple(range(a, x.ndim))
+                mu = x.mean(axis=ax, keepdims=True)
+                var = ((x - mu) ** 2).mean(axis=ax, keepdims=True)
+                y = (x - mu) / np.sqrt(var + float(F(attrs.get("epsilon", 1e-5)))) * ins[1].reshape(x.shape[a:])
+                out = [y + ins[2].reshape(x.shape[a:]) if len(ins) > 2 and ins[2] is not None else y]
+            elif op == "Softmax":
+                a = attrs.get("axis", -1)
+                e = np.exp(x - x.max(axis=a, keepdims=True))
+                out = [e / e.sum(axis=a, keepdims=True)]
+            elif op in ("MaxPool", "AveragePool"):
+                k, s, p = attrs["kernel_shape"], attrs.get("strides", [1, 1]), attrs.get("pads", [0, 0, 0, 0])
+                assert p[0] == p[2] and p[1] == p[3]
+                if op == "MaxPool":
+                    out = [torch.nn.functional.max_pool2d(T(x), tuple(k), tuple(s), (p[0], p[1])).numpy()]
+                else:
+                    out = [torch.nn.functional.avg_pool2d(T(x), tuple(k), tuple(s), (p[0], p[1]), count_include_pad=False).numpy()]
+            elif op == "GlobalAveragePool":
+                out = [x.mean(axis=tuple(range(2, x.ndim)), keepdims=True)]
+            elif op == "ReduceSum":
+                out = [x.sum(axis=tuple(int(a) for a in ins[1]), keepdims=bool(attrs.get("keepdims", 1)))]
+            elif op == "ReduceMean":
+                out = [x.mean(axis=tuple(attrs["axes"]), keepdims=bool(attrs.get("keepdims", 1)))]
+            elif op == "Tanh":
+                out = [np.tanh(x)]
+            elif op == "ArgMax":
+                a = attrs.get("axis", 0)
+                srt = np.sort(x, axis=a)
+                gap = np.take(srt, [-1], axis=a) - np.take(srt, [-2], axis=a)
+                idx = np.expand_dims(np.argmax(x, axis=a), a).astype(np.int32)
+                ties[n["outputs"][0]] = gap < TIE_MARGIN if attrs.get("keepdims", 1) else np.squeeze(gap < TIE_MARGIN, a)
+                out = [idx if attrs.get("keepdims", 1) else np.squeeze(idx, a)]
+            elif op == "TopK":
+                k, a = int(np.asarray(ins[1]).ravel()[0]), attrs.get("axis", -1)
+                order = np.argsort(-x if attrs.get("largest", 1) else x, axis=a, kind="stable")
+                srt = np.take_along_axis(x, order, axis=a)
+                gaps = np.abs(np.diff(srt, axis=a))
+                pad = [(0, 0)] * x.ndim
+                pad[a] = (1, 0)
+                near_prev = np.pad(gaps, pad, constant_values=np.inf) < TIE_MARGIN
+                pad[a] = (0, 1)
+                near_next = np.pad(gaps, pad, constant_values=np.inf) < TIE_MARGIN
+                tie = np.take(near_prev | near_next, np.arange(k), axis=a)
+                out = [np.take(srt, np.arange(k), axis=a), np.take(order, np.arange(k), axis=a).astype(np.int32)]
+                ties[n["outputs"][1]] = tie
+            else:
+                one = 1.0
+                sig = lambda v: one / (one + np.exp(-v))
+                if op == "Relu":
+                    out = [np.fmax(x, 0.0)]  # f32::max semantics (rten-vecmath/src/relu.rs): Relu(NaN) = 0
+                elif op == "Gelu":
+                    out = [0.5 * x * (1.0 + torch.erf(T(x) / np.sqrt(2.0)).numpy())]
+                elif op == "Sigmoid":
+                    out = [sig(x)]
+                elif op == "Silu":
+                    out = [x * sig(x)]
+                elif op == "Swish":
+                    out = [x * sig(x * float(F(attrs.get("alpha", 1.0))))]
+                elif op == "HardSigmoid":
+                    out = [np.clip(float(F(attrs.get("alpha", 0.2))) * x + float(F(attrs.get("beta", 0.5))), 0.0, 1.0)]
+                elif op == "HardSwish":
+                    out = [x * np.clip(x / 6.0 + 0.5, 0.0, 1.0)]
+                elif op == "LeakyRelu":
+                    out = [np.where(x < 0, x * float(F(attrs.get("alpha", 0.01))), x)]
+                elif op == "Elu":
+                    out = [np.where(x >= 0, x, float(F(attrs.get("alpha", 1.0))) * (np.exp(x) - 1.0))]
+                elif op == "Clip":
+                    lo = ins[1] if len(ins) > 1 and ins[1] is not None else -np.inf
+                    hi = ins[2] if len(ins) > 2 and ins[2] is not None else np.inf
+                    out = [np.minimum(np.maximum(x, lo), hi)]
+                else:
+                    raise KeyError(op)
+        for name, v in zip(n["outputs"], out):
+            if not name:
+                continue
+            v = np.asarray(v)
+            if v.dtype.kind in "iu" and teacher is not None and op not in LAYOUT_OPS:
+                vals[name + "#f64"] = v
+                v = teacher[name]
+            vals[name] = v
+    return vals, ties
+
+
+F64_BOUND = 8.5e-6  # |f32 oracle - float64| / (1 + |float64|) over the corpus stays below this (measured in tests/test_graph_fuzz_oracle.py)
+TIE_MARGIN = F64_BOUND  # a float64 decision (rounding, arg-max, top-k order) closer than this to flipping is not compared
+
+
+# ------------------------------------------------------------------------------------------------ builder
+class Builder:
+    """Builds a Case node by node; every node is evaluated at once on the f32 oracle so that later nodes can be shaped after its result."""
+
+    def __init__(self, name, seed):
+        self.case = Case(name)
+        self.rng = np.random.default_rng(seed)
+        self.v = {}       # name -> ndarray, first binding
+        self.made_by = {}  # name -> op type of the producing node
+        self.k = 0
+        self.alt = None   # optional second binding: {input name: ndarray}
+
+    def fresh(self, stem):
+        self.k += 1
+        return f"{stem}{self.k}"
+
+    def data(self, shape, scale=1.0):
+        """U[-scale, scale) float32."""
+        return ((self.rng.random(shape, dtype=np.float32) * F(2.0) - F(1.0)) * F(scale)).astype(F)
+
+    def inp(self, shape, dims=None, arr=None):
+        name = self.fresh("in")
+        a = self.data(shape) if arr is None else arr
+        self.case.input_specs.append((name, list(dims if dims is not None else a.shape)))
+        self.case.bindings[0][name] = a
+        self.v[name] = a
+        self.made_by[name] = "input"
+        return name
+
+    def const(self, arr, stem="c"):
+        name = self.fresh(stem)
+        a = np.asarray(arr)
+        self.case.inits[name] = a
+        self.v[name] = a
+        return name
+
+    def cf(self, shape, scale=1.0):
+        return self.const(self.data(shape, scale))
+
+    def ci(self, values):
+        return self.const(np.asarray(values, np.int64), "i")
+
+    def node(self, op, inputs, nout=1, outputs=None, **attrs):
+        outs = outputs or [self.fresh(op.lower()[:4] + "_") for _ in range(nout)]
+        n = {"op": op, "inputs": list(inputs), "outputs": list(outs), "attrs": attrs, "name": self.fresh("n_" + op)}
+        res = eval_node(n, [self.v[s] if s else None for s in inputs])
+        assert len(res) >= len(outs), (op, len(res))
+        for o, r in zip(outs, res):
+            if o:
+                assert r.size <= MAX_ELEMS, (op, r.shape)
+                self.v[o] = r
+                self.made_by[o] = op
+        self.case.nodes.append(n)
+        return outs[0] if len(outs) == 1 else outs
+
+    def out(self, name):
+        self.case.outputs.append(name)
+
+    def row(self, row, folded=0, kinds=()):
+        e = self.case.expect
+        e["rows"].append(row)
+        e["folded"] += folded
+        e["kinds"] += list(kinds)
+
+    def finish(self):
+        c = self.case
+        assert c.outputs, c.name
+        elem = {np.dtype(np.float32): ow.FLOAT, np.dtype(np.uint8): ow.UINT8, np.dtype(np.int8): ow.INT8, np.dtype(np.int32): ow.INT32, np.dtype(np.int64): ow.INT64}
+        nodes = [ow.node(n["op"], n["inputs"], n["outputs"], name=n["name"], **n["attrs"]) for n in c.nodes]
+        ins = [ow.value_info(name, elem[c.bindings[0][name].dtype], dims) for name, dims in c.input_specs]
+        outs = [ow.value_info(o, elem[self.v[o].dtype], list(self.v[o].shape) if self.alt is None else []) for o in c.outputs]
+        c.onnx = ow.model(nodes, ins, outs, [ow.tensor(k, a) for k, a in c.inits.items()], name=c.name)
+        if self.alt is not None:
+            c.bindings.append(self.alt)
+        c.expect["kinds"] = sorted(c.expect["kinds"])
+        return c
+
+
+# ------------------------------------------------------------------------------------------------ motifs
+# Every motif takes the builder, a variant name and a float32 source value of any shape (it derives its own operand from it with inert operators, so
+# motifs chain), emits its nodes, records its row and returns the values a later motif or a graph output may read.
+
+def _to4d(b, src, c, hw):
+    """[1, c, hw, hw] f32 derived from `src` (flatten, slice or tile by Concat, reshape): nothing here is a fusion head or tail."""
+    need = c * hw * hw
+    flat = b.node("Reshape", [src, b.ci([-1])])
+    while b.v[flat].size < need:
+        flat = b.node("Concat", [flat, flat], axis=0)
+    cut = b.node("Slice", [flat, b.ci([0]), b.ci([need]), b.ci([0]), b.ci([1])])
+    return b.node("Reshape", [cut, b.ci([1, c, hw, hw])])
+
+
+def _to2d(b, src, m, k):
+    need = m * k
+    flat = b.node("Reshape", [src, b.ci([-1])])
+    while b.v[flat].size < need:
+        flat = b.node("Concat", [flat, flat], axis=0)
+    cut = b.node("Slice", [flat, b.ci([0]), b.ci([need]), b.ci([0]), b.ci([1])])
+    return b.node("Reshape", [cut, b.ci([m, k])])
+
+
+def m_conv(b, variant, src):
+    r = b.rng
+    C, O, HW = 4, 4, int(r.integers(5, 9))
+    row = "conv/" + variant
+    if variant == "conv1d_add":
+        flat = _to2d(b, src, 1, 4 * 12)
+        x = b.node("Reshape", [flat, b.ci([1, 4, 12])])
+        res = b.node("Sub", [x, b.cf((1, 4, 12))])
+        y = b.node("Conv", [x, b.cf((4, 4, 3), 0.4), b.cf((4,))], kernel_shape=[3], pads=[1, 1], strides=[1], dilations=[1])
+        s = b.node("Add", [y, res])
+        z = b.node("Relu", [s])
+        b.row(row, 2, ["Conv+Add+Relu"])  # the step claims both; a 1-D convolution then runs them as separate launches
+        return [z]
+    if variant == "conv1d_default_attrs":  # no attribute at all: the constant weight's rank says that the node is 1-D
+        flat = _to2d(b, src, 1, 4 * 12)
+        x = b.node("Reshape", [flat, b.ci([1, 4, 12])])
+        z = b.node("Relu", [b.node("Conv", [x, b.cf((4, 4, 3), 0.4), b.cf((4,))])])
+        b.row(row, 1, ["Conv+Relu"])
+        return [z]
+    x = _to4d(b, src, C, HW)
+    groups = {"grouped": 2, "depthwise": 4}.get(variant, 1)
+    k = int(r.choice([1, 3]))
+    w = b.cf((O, C // groups, k, k), 0.4)
+    bias = b.cf((O,))
+    conv = lambda xin, ww=w: b.node("Conv", [xin, ww, bias], kernel_shape=[k, k], pads=[k // 2] * 4, strides=[1, 1], group=groups)
+    if variant in ("res_ready", "grouped", "depthwise"):
+        res = b.node("Sub", [x, b.cf((1, C, HW, HW))])
+        y = conv(x)
+        s = b.node("Add", [y, res] if r.integers(2) else [res, y])
+        z = b.node("Relu", [s])
+        b.row(row, 2, ["Conv+Add+Relu"])
+        return [z]
+    if variant == "res_after":  # the residual's producer stands after the convolution: ready_before is false, nothing is claimed
+        y = conv(x)
+        res = b.node("Sub", [x, b.cf((1, C, HW, HW))])
+        s = b.node("Add", [y, res])
+        z = b.node("Relu", [s])
+        b.row(row, 0)
+        return [z]
+    if variant == "two_convs_one_add":  # only the later convolution claims the Add
+        y1 = conv(x)
+        y2 = conv(x, b.cf((O, C, k, k), 0.4))
+        s = b.node("Add", [y1, y2])
+        z = b.node("Relu", [s])
+        b.row(row, 2, ["Conv+Add+Relu"])
+        return [z]
+    if variant == "add_same":
+        y = conv(x)
+        s = b.node("Add", [y, y])
+        z = b.node("Relu", [s])
+        b.row(row, 0)
+        return [z]
+    if variant in ("res_const_1o11", "res_const_o11", "res_scalar"):  # claimed at load, run as Conv, broadcasting Add, Relu
+        shape = {"res_const_1o11": (1, O, 1, 1), "res_const_o11": (O, 1, 1), "res_scalar": ()}[variant]
+        y = conv(x)
+        s = b.node("Add", [y, b.cf(shape)])
+        z = b.node("Relu", [s])
+        b.row(row, 2, ["Conv+Add+Relu"])
+        return [z]
+    if variant == "out_second_reader":
+        y = conv(x)
+        z = b.node("Relu", [y])
+        t = b.node("Sub", [y, b.cf((1, O, 1, 1))])
+        b.row(row, 0)
+        return [z, t]
+    if variant == "out_is_graph_output":
+        y = conv(x)
+        b.out(y)
+        z = b.node("Relu", [y])
+        b.row(row, 0)
+        return [z]
+    if variant == "add_is_output_relu_after":
+        res = b.node("Sub", [x, b.cf((1, C, HW, HW))])
+        y = conv(x)
+        s = b.node("Add", [y, res])
+        b.out(s)
+        z = b.node("Relu", [s])
+        b.row(row, 1, ["Conv+Add"])
+        return [z]
+    if variant == "relu":
+        z = b.node("Relu", [conv(x)])
+        b.row(row, 1, ["Conv+Relu"])
+        return [z]
+    assert variant.startswith("act_"), variant
+    kind = variant[4:]
+    y = conv(x)
+    attrs, extra = {}, []
+    if kind == "Swish":
+        attrs = {"alpha": 1.702}
+    elif kind == "HardSigmoid":
+        attrs = {"alpha": 0.25, "beta": 0.5}
+    elif kind in ("LeakyRelu", "Elu"):
+        attrs = {"alpha": 0.3}
+    elif kind == "Clip":
+        extra = [b.const(np.array(-0.25, F)), b.const(np.array(0.5, F))]
+    z = b.node(kind, [y] + extra, **attrs)
+    b.row(row, 1, ["Conv+" + kind])
+    return [z]
+
+
+CONV_VARIANTS = ["res_ready", "res_after", "two_convs_one_add", "add_same", "res_const_1o11", "res_const_o11", "res_scalar", "conv1d_add",
+                 "out_second_reader", "out_is_graph_output", "add_is_output_relu_after", "relu", "grouped", "depthwise"] + ["act_" + k for k in ACT_KINDS]
+
+
+def m_matmul(b, variant, src):
+    r = b.rng
+    row = "matmul/" + variant
+    big_k = variant.endswith("_k300")
+    base = variant[:-5] if big_k else variant
+    K = 300 if big_k else int(r.choice([24, 64, 256]))
+    M, N = int(r.integers(2, 7)), int(r.choice([8, 20, 33]))
+    if base == "one_row_bias":
+        M = 1
+    a = _to2d(b, src, M, K)
+    if base == "batched_3d_bias":
+        a2 = _to2d(b, src, 3 * M, K)
+        a = b.node("Reshape", [a2, b.ci([3, M, K])])
+    w = b.cf((K, N), 0.3)
+    if base == "div_left":  # a product of non-negative factors stays away from zero, where c / y is ill-conditioned
+        a, w = b.node("Mul", [a, a]), b.const(np.abs(b.v[w]) + F(0.05))
+    y = b.node("MatMul", [a, w])
+    differ = "the reference's FusedMatMul rounds differently from MatMul followed by the scalar operator / the bias Add (tests/graph_fuzz.py docstring)"
+    if base in ("mul_right_pow2", "mul_right_np2", "div_right_pow2", "div_right_np2", "mul_left_np2"):
+        c = b.const(np.array({"pow2": 0.125, "np2": 0.3}[base.rsplit("_", 1)[1]], F).reshape(() if r.integers(2) else (1,)))
+        op = "Div" if base.startswith("div") else "Mul"
+        z = b.node(op, [c, y] if base == "mul_left_np2" else [y, c])
+        b.row(row, 1, ["FusedMatMul"])
+        if "np2" in base:
+            b.case.expect["modes_differ"] = differ
+        return [z]
+    if base == "div_left":  # c / MatMul is no scaling of the product
+        z = b.node("Div", [b.const(np.array(0.3, F)), y])
+        b.row(row, 0)
+        return [z]
+    if base == "div_then_mul":  # the Div becomes alpha, the Mul stays
+        d = b.node("Div", [y, b.const(np.array(3.0, F))])
+        z = b.node("Mul", [d, b.const(np.array(0.7, F))])
+        b.row(row, 1, ["FusedMatMul"])
+        b.case.expect["modes_differ"] = differ
+        return [z]
+    if base in ("bias_1d", "one_row_bias", "batched_3d_bias", "bias_1d_left"):
+        bias = b.cf((N,))
+        s = b.node("Add", [bias, y] if base == "bias_1d_left" else [y, bias])
+        b.row(row, 1, ["FusedMatMul"])
+        b.case.expect["modes_differ"] = differ
+        return [s]
+    if base in ("bias_gelu", "bias_relu", "bias_act"):
+        s = b.node("Add", [y, b.cf((N,))])
+        kind = {"bias_gelu": "Gelu", "bias_relu": "Relu", "bias_act": str(r.choice(["Sigmoid", "Silu", "HardSwish", "Elu"]))}[base]
+        z = b.node(kind, [s])
+        b.row(row, 2, ["FusedMatMul+" + kind])
+        b.case.expect["modes_differ"] = differ
+        return [z]
+    if base == "act_no_bias":
+        z = b.node("Sigmoid", [y])
+        b.row(row, 1, ["FusedMatMul+Sigmoid"])
+        return [z]
+    if base == "bias_1xn":  # a [1, N] constant is no bias vector: MatMul, Add
+        s = b.node("Add", [y, b.cf((1, N))])
+        b.row(row, 0)
+        return [s]
+    if base == "bias_nonconst":
+        bias = b.node("Sub", [b.cf((N,)), b.cf((N,))])
+        s = b.node("Add", [y, bias])
+        b.row(row, 0)
+        return [s]
+    if base == "bias_len_mismatch":  # a constant [1]: the Add broadcasts it, the FusedMatMul refuses it
+        s = b.node("Add", [y, b.cf((1,))])
+        b.row(row, 1, ["FusedMatMul"])
+        b.case.expect["error"] = {"fused": "Cannot broadcast bias to output shape", "nofuse": None}
+        return [s]
+    if base == "read_twice":
+        s = b.node("Add", [y, b.cf((N,))])
+        t = b.node("Sub", [y, b.cf((N,))])
+        b.row(row, 0)
+        return [s, t]
+    raise KeyError(variant)
+
+
+MATMUL_VARIANTS = ["mul_right_pow2", "mul_right_np2", "div_right_pow2", "div_right_np2", "mul_left_np2", "div_left", "div_then_mul", "bias_1d", "bias_1d_left",
+                   "bias_1d_k300", "mul_right_np2_k300", "mul_left_np2_k300", "bias_gelu", "bias_relu", "bias_act", "bias_gelu_k300", "act_no_bias", "bias_1xn",
+                   "bias_nonconst", "bias_len_mismatch", "batched_3d_bias", "one_row_bias", "one_row_bias_k300", "read_twice"]
+
+
+def m_gemm(b, variant, src):
+    r = b.rng
+    M, K, N = int(r.integers(2, 6)), int(r.choice([16, 300])), int(r.choice([8, 21]))
+    if variant == "one_row":
+        M = 1
+    ta, tb = variant in ("trans_a", "trans_ab"), variant in ("trans_b", "trans_ab", "alpha_beta_matrix")
+    a = _to2d(b, src, K, M) if ta else _to2d(b, src, M, K)
+    w = b.cf((N, K) if tb else (K, N), 0.3)
+    attrs = {"transA": int(ta), "transB": int(tb)}
+    ins = [a, w]
+    if variant == "alpha_beta_matrix":
+        attrs.update(alpha=0.5, beta=0.75)
+        ins.append(b.cf((M, N)))
+    elif variant != "no_c":
+        ins.append(b.cf((N,)))
+    y = b.node("Gemm", ins, **attrs)
+    b.row("gemm/" + variant, 0)
+    return [y]
+
+
+GEMM_VARIANTS = ["vector_c", "trans_a", "trans_b", "trans_ab", "alpha_beta_matrix", "no_c", "one_row"]
+
+
+def m_add_ln(b, variant, src):
+    r = b.rng
+    R, Cc = int(r.integers(2, 6)), int(r.choice([10, 64, 100]))
+    row = "add_ln/" + variant
+    if variant == "add_out_is_scale":  # the Add's result is read twice by the LayerNormalization: not a sole reader
+        x = _to2d(b, src, 1, Cc)
+        x1 = b.node("Reshape", [x, b.ci([Cc])])
+        s = b.node("Add", [x1, b.cf((Cc,))])
+        y = b.node("LayerNormalization", [s, s], axis=-1, epsilon=1e-5)
+        b.row(row, 0)
+        return [y]
+    x = _to2d(b, src, 2 * R, Cc)
+    x = b.node("Reshape", [x, b.ci([2, R, Cc])])
+    gamma, beta = b.cf((Cc,)), b.cf((Cc,))
+    if variant == "axis_other":  # LayerNormalization over the two trailing axes: Add, LayerNormalization
+        s = b.node("Add", [x, b.cf((2, R, Cc))])
+        y = b.node("LayerNormalization", [s, b.cf((R, Cc)), b.cf((R, Cc))], axis=1, epsilon=1e-5)
+        b.row(row, 0)
+        return [y]
+    other = b.cf((Cc,)) if variant == "bcast_add" else b.cf((2, R, Cc))
+    s = b.node("Add", [x, other] if r.integers(2) else [other, x])
+    y = b.node("LayerNormalization", [s, gamma] + ([] if variant == "no_bias" else [beta]), axis=-1, epsilon=1e-12 if r.integers(2) else 1e-5)
+    if variant == "add_is_output":
+        b.out(s)
+        b.row(row, 0)
+    else:
+        b.row(row, 1, ["Add+LayerNormalization"])
+    return [y]
+
+
+ADD_LN_VARIANTS = ["axis_last", "axis_other", "bcast_add", "add_out_is_scale", "no_bias", "add_is_output"]
+
+
+def m_add_softmax(b, variant, src):
+    r = b.rng
+    R, Cc = int(r.integers(2, 6)), int(r.choice([7, 32, 130]))
+    row = "add_softmax/" + variant
+    x = _to2d(b, src, 3 * R, Cc)
+    x = b.node("Reshape", [x, b.ci([3, R, Cc])])
+    if variant == "other_axis":
+        s = b.node("Add", [x, b.cf((3, R, Cc))])
+        y = b.node("Softmax", [s], axis=1)
+        b.row(row, 0)
+        return [y]
+    if variant == "last_axis":
+        s = b.node("Add", [x, b.cf((3, R, Cc))])
+    elif variant == "small_first":  # the step swaps the operands
+        s = b.node("Add", [b.cf((Cc,)), x])
+    elif variant == "bcast_both":  # [3, R, Cc] + [3, 1, Cc] is outside the fused kernel's forms; [3, 1, Cc] + [1, R, Cc] broadcasts both ways
+        x1 = b.node("Slice", [x, b.ci([0]), b.ci([1]), b.ci([1]), b.ci([1])])
+        s = b.node("Add", [x1, b.cf((1, R, Cc))])
+    elif variant == "addend_of_higher_rank":  # [R, Cc] + [1, 1, Cc] is [1, R, Cc]: the sum takes the ADDEND's rank, so the fused kernel (output shaped like x) is not taken
+        x2 = b.node("Reshape", [b.node("Slice", [x, b.ci([0]), b.ci([1]), b.ci([0]), b.ci([1])]), b.ci([R, Cc])])
+        s = b.node("Add", [x2, b.cf((1, 1, Cc))])
+    elif variant == "neg_inf_row":  # one row of the mask is all -inf: that row of the result is NaN
+        mask = np.zeros((3, R, Cc), F)
+        mask[1, 0, :] = -np.inf
+        mask[2, R - 1, ::2] = -np.inf
+        s = b.node("Add", [x, b.const(mask)])
+    else:
+        raise KeyError(variant)
+    y = b.node("Softmax", [s], axis=-1)
+    b.row(row, 1, ["AddSoftmax"])
+    return [y]
+
+
+ADD_SOFTMAX_VARIANTS = ["last_axis", "other_axis", "small_first", "bcast_both", "neg_inf_row", "addend_of_higher_rank"]
+
+
+def m_views(b, variant, src):
+    r = b.rng
+    row = "views/" + variant
+    A, B_ = int(r.integers(2, 5)), int(r.choice([6, 16, 40]))
+    x = _to2d(b, src, A, B_)
+    base = b.node("Sub", [x, b.cf((A, B_))])  # a pooled buffer of A * B_ floats
+    if variant.startswith("chain"):
+        depth = int(variant[5:])
+        ops = [("Reshape", lambda v: [v, b.ci([1, A, B_])], {}), ("Flatten", lambda v: [v], {"axis": 2}), ("Unsqueeze", lambda v: [v, b.ci([0, 3])], {}),
+               ("Squeeze", lambda v: [v, b.ci([0])], {})]
+        v = base
+        for d in range(depth):
+            op, mk, attrs = ops[d] if d < 4 else ops[0]
+            v = b.node(op, mk(v), **attrs)
+            if d % 2 == 0:
+                v = b.node("Identity", [v])
+        y = b.node("Mul", [v, b.cf(b.v[v].shape)])
+        b.row(row)
+        return [y]
+    if variant == "of_graph_input":
+        g = b.inp((A, B_))
+        v = b.node("Reshape", [g, b.ci([B_, A])])
+        y = b.node("Sub", [v, b.cf((B_, A))])
+        b.out(v)
+        b.row(row)
+        return [y]
+    if variant == "of_initializer":
+        v = b.node("Reshape", [b.cf((A, B_)), b.ci([B_, A])])
+        b.out(v)
+        xt = b.node("Reshape", [base, b.ci([B_, A])])
+        y = b.node("Mul", [v, xt])
+        b.row(row)
+        return [y]
+    if variant == "view_is_output":
+        v = b.node("Flatten", [base], axis=0)
+        b.out(v)
+        y = b.node("Tanh", [base])
+        b.row(row)
+        return [y]
+    if variant == "output_listed_twice":
+        y = b.node("Tanh", [base])
+        b.out(y)
+        b.out(y)
+        v = b.node("Reshape", [y, b.ci([-1])])
+        b.out(v)
+        b.out(v)
+        b.row(row)
+        return [b.node("Sub", [y, b.cf((B_,))])]
+    if variant == "input_is_output":
+        g = b.inp((A, B_))
+        b.out(g)
+        b.row(row)
+        return [b.node("Mul", [g, base])]
+    if variant == "read_after_base_dies":
+        # v aliases `base`; Tanh is base's last other reader; `again` then asks the pool for a buffer of base's size while v is still to be read
+        v = b.node("Reshape", [base, b.ci([B_, A])])
+        t = b.node("Tanh", [base])
+        again = b.node("Sub", [t, b.cf((A, B_))])
+        more = b.node("Mul", [again, b.cf((A, B_))])
+        w = b.node("Mul", [v, b.cf((B_, A))])
+        b.out(w)
+        b.row(row)
+        return [more]
+    if variant == "view_of_view_after_base_dies":
+        v1 = b.node("Reshape", [base, b.ci([B_, A])])
+        v2 = b.node("Unsqueeze", [v1, b.ci([0])])
+        t = b.node("Tanh", [v1])  # v1's last reader: its hold on base goes, v2's must stay
+        again = b.node("Sub", [t, b.cf((B_, A))])
+        more = b.node("Mul", [again, b.cf((B_, A))])
+        w = b.node("Mul", [v2, b.cf((1, B_, A))])
+        b.out(w)
+        b.row(row)
+        return [more]
+    if variant == "unread_view":
+        b.node("Reshape", [base, b.ci([-1])])
+        y = b.node("Tanh", [base])
+        b.row(row)
+        return [b.node("Sub", [y, b.cf((A, B_))])]
+    if variant == "add_v_v":
+        v = b.node("Reshape", [base, b.ci([B_, A])])
+        y = b.node("Add", [v, v])
+        b.row(row)
+        return [y]
+    if variant == "split_second_unread":
+        h = B_ // 2
+        p0, _ = b.node("Split", [base, b.ci([h, B_ - h])], nout=2, axis=1)
+        b.row(row)
+        return [b.node("Sub", [p0, b.cf((A, h))])]
+    if variant == "topk_indices_unread":
+        vals, _ = b.node("TopK", [base, b.ci([3])], nout=2, axis=-1, largest=1)
+        b.row(row)
+        return [b.node("Sub", [vals, b.cf((A, 3))])]
+    if variant == "topk_values_unread":
+        _, idx = b.node("TopK", [base, b.ci([3])], nout=2, axis=-1, largest=1)
+        b.out(idx)
+        am = b.node("ArgMax", [base], axis=1, keepdims=0)
+        b.out(am)
+        b.row(row)
+        return [b.node("Tanh", [base])]
+    if variant == "dql_scale_unread":
+        x4 = _to4d(b, base, 4, 5)
+        q, _, zp = b.node("DynamicQuantizeLinear", [x4], nout=3)
+        wq = b.const(b.rng.integers(-64, 65, (3, 4, 1, 1)).astype(np.int8))
+        acc = b.node("ConvInteger", [q, wq, zp], kernel_shape=[1, 1])
+        b.out(acc)
+        b.out(q)
+        b.row(row)
+        return [b.node("Tanh", [x4])]
+    raise KeyError(variant)
+
+
+VIEW_VARIANTS = ["chain2", "chain3", "chain4", "of_graph_input", "of_initializer", "view_is_output", "output_listed_twice", "input_is_output", "read_after_base_dies",
+                 "view_of_view_after_base_dies", "unread_view", "add_v_v", "split_second_unread", "topk_indices_unread", "topk_values_unread", "dql_scale_unread"]
+
+
+def m_int8(b, variant, src):
+    """DynamicQuantizeLinear -> ConvInteger -> Cast -> Mul(x_scale * w_scale) (+ Add bias [1,O,1,1]) (+ Add residual) (+ Relu), small and unpadded."""
+    r = b.rng
+    row = "int8/" + variant
+    C, O, HW = 4, 4, 6
+    x = _to4d(b, src, C, HW)
+    zero = b.const(np.zeros((), np.int8))
+    q, xs, xz = b.node("DynamicQuantizeLinear", [x], nout=3)
+
+    def chain(k, per_channel=False, bias=True, residual=None, relu=False):
+        wq = b.const(r.integers(-64, 65, (O, C, k, k)).astype(np.int8))
+        ws = b.const((r.random((1, O, 1, 1), dtype=np.float32) * F(0.02) + F(0.005)) if per_channel else np.array(0.0123, F))
+        acc = b.node("ConvInteger", [q, wq, xz, zero], kernel_shape=[k, k], pads=[0, 0, 0, 0], strides=[1, 1])
+        accf = b.node("Cast", [acc], to=ow.FLOAT)
+        sc = b.node("Mul", [xs, ws])
+        y = b.node("Mul", [accf, sc])
+        folded, kind = 2 + (0 if per_channel else 1), "ConvIntegerToFloat"  # Cast, Mul; the scalar scale product moves into the staged quantizer
+        if bias:
+            y = b.node("Add", [y, b.cf((1, O, 1, 1))])
+            folded, kind = folded + 1, kind + "+bias"
+        if residual is not None:
+            y = b.node("Add", [y, residual])
+            folded, kind = folded + 1, kind + "+Add"
+        if relu:
+            y = b.node("Relu", [y])
+            folded, kind = folded + 1, kind + "+Relu"
+        return y, folded, kind
+    if variant in ("scalar_scale", "per_channel_scale"):
+        y, f, k = chain(1, per_channel=variant == "per_channel_scale", relu=True)
+        b.row(row, f, [k])
+        return [y]
+    if variant == "residual_relu":
+        res = b.node("Sub", [x, b.cf((1, C, HW, HW))])
+        y, f, k = chain(1, residual=res, relu=True)
+        b.row(row, f, [k])
+        return [y]
+    if variant == "one_quantizer_two_convs":  # two convolutions of one geometry read the codes; the scale feeds two Mul nodes
+        y1, f1, k1 = chain(1, relu=True)
+        y2, f2, k2 = chain(1, bias=False)
+        b.row(row, f1 + f2, [k1, k2])
+        return [b.node("Sub", [y1, y2])]
+    if variant == "quantizer_input_read_elsewhere":
+        y, f, k = chain(3)
+        b.out(x)
+        t = b.node("Tanh", [x])
+        b.row(row, f, [k])
+        return [y, t]
+    if variant == "scale_read_by_second_mul":  # x_scale also scales an f32 tensor: that Mul is no scale product
+        y, f, k = chain(1)
+        t = b.node("Mul", [x, xs])
+        b.row(row, f, [k])
+        return [y, t]
+    raise KeyError(variant)
+
+
+INT8_VARIANTS = ["scalar_scale", "per_channel_scale", "residual_relu", "one_quantizer_two_convs", "quantizer_input_read_elsewhere", "scale_read_by_second_mul"]
+
+MOTIFS = {"conv": (m_conv, CONV_VARIANTS), "matmul": (m_matmul, MATMUL_VARIANTS), "gemm": (m_gemm, GEMM_VARIANTS), "add_ln": (m_add_ln, ADD_LN_VARIANTS),
+          "add_softmax": (m_add_softmax, ADD_SOFTMAX_VARIANTS), "views": (m_views, VIEW_VARIANTS), "int8": (m_int8, INT8_VARIANTS)}
+HAND_ONLY_ROWS = ["shape/dynamic_batch_reshape", "conv/conv1d_default_attrs"]  # rows that have a minimal graph only, outside the seeds' walk of the table
+ROWS = [f"{m}/{v}" for m, (_, vs) in MOTIFS.items() for v in vs] + HAND_ONLY_ROWS
+
+
+# ------------------------------------------------------------------------------------------------ glue
+# Inert operators only: nothing here is a fusion head (Conv, MatMul, Add, ConvInteger) and a fusion tail (Relu, an activation, Gelu, scalar Mul / Div,
+# Add, LayerNormalization, Softmax, Cast) is emitted only behind a value that no head produced.
+HEADS = ("Conv", "MatMul", "ConvInteger", "MatMulInteger", "Add", "Gemm")
+
+
+def glue(b, src):
+    r = b.rng
+    x = b.v[src]
+    choices = ["sub_bcast", "mul_bcast", "tanh", "transpose", "concat_slice", "split", "reduce"]
+    if x.ndim == 4 and x.shape[2] >= 4 and x.shape[3] >= 4:
+        choices += ["maxpool", "avgpool"]
+    if b.made_by.get(src) not in HEADS + ("Mul", "Div", "Cast"):  # (a scalar Mul / Div may have become a FusedMatMul's result, which takes an activation)
+        choices += ["activation", "relu"]
+    pick = str(r.choice(choices))
+    if pick in ("sub_bcast", "mul_bcast"):
+        shape = list(x.shape)
+        for d in range(len(shape)):
+            if r.integers(2):
+                shape[d] = 1
+        shape = shape[int(r.integers(0, len(shape) + 1)) if shape else 0:] if r.integers(2) else shape
+        if int(np.prod(shape, dtype=np.int64)) == 1 and pick == "mul_bcast":
+            shape = list(x.shape)  # never a scalar Mul: that is the MatMul motif's tail
+        c = b.cf(tuple(shape))
+        op = "Sub" if pick == "sub_bcast" else "Mul"
+        return b.node(op, [src, c] if r.integers(2) else [c, src])
+    if pick == "tanh":
+        return b.node("Tanh", [src])
+    if pick == "transpose" and x.ndim >= 2:
+        return b.node("Transpose", [src], perm=[int(p) for p in r.permutation(x.ndim)])
+    if pick == "concat_slice" and x.ndim >= 1 and x.size * 2 <= MAX_ELEMS:
+        ax = int(r.integers(x.ndim))
+        cat = b.node("Concat", [src, b.node("Tanh", [src])], axis=ax)
+        n = b.v[cat].shape[ax]
+        lo = int(r.integers(0, n // 2))
+        return b.node("Slice", [cat, b.ci([lo]), b.ci([lo + n // 2 + 1]), b.ci([ax]), b.ci([1])])
+    if pick == "split" and x.ndim >= 1:
+        ax = int(np.argmax(x.shape))
+        n = x.shape[ax]
+        if n >= 2:
+            parts = b.node("Split", [src, b.ci([n // 2, n - n // 2])], nout=2, axis=ax)
+            return parts[int(r.integers(2))] if r.integers(2) else b.node("Concat", [parts[1], parts[0]], axis=ax)
+    if pick == "reduce" and x.ndim >= 2 and x.size >= 16:
+        ax = int(r.integers(x.ndim))
+        if r.integers(2):
+            return b.node("ReduceSum", [src, b.ci([ax])], keepdims=1)
+        return b.node("ReduceMean", [src], axes=[ax], keepdims=int(r.integers(2)) if x.ndim > 2 else 1)
+    if pick == "maxpool":
+        return b.node("MaxPool", [src], kernel_shape=[2, 2], strides=[2, 2], pads=[0, 0, 0, 0])
+    if pick == "avgpool":
+        return b.node("AveragePool", [src], kernel_shape=[3, 3], strides=[1, 1], pads=[1, 1, 1, 1])
+    if pick == "activation":
+        return b.node(str(r.choice(["Sigmoid", "HardSwish", "Elu", "LeakyRelu"])), [src])
+    if pick == "relu":
+        return b.node("Relu", [src])
+    return b.node("Sub", [src, b.cf(x.shape)])
+
+
+def _link(b, src, prev):
+    """`src` shifted by the mean of `prev` (ReduceMean over every axis, broadcasting Sub): the next motif's operand depends on the previous result."""
+    mean = b.node("ReduceMean", [prev], axes=list(range(b.v[prev].ndim)), keepdims=1)
+    return b.node("Sub", [src, b.node("Reshape", [mean, b.ci([1])])])
+
+
+def hand_case(row):
+    """The minimal graph of one table row: an input, the motif, its results as outputs."""
+    if row == "shape/dynamic_batch_reshape":
+        return shape_case()
+    motif, variant = row.split("/", 1)
+    b = Builder("hand_" + row.replace("/", "_"), seed=1 + ROWS.index(row))
+    src = b.inp((4, 96))
+    for o in MOTIFS[motif][0](b, variant, src):
+        b.out(o)
+    return b.finish()
+
+
+def shape_case():
+    """Shape -> Gather -> Unsqueeze -> Concat -> Reshape around a Conv + Relu, with the leading axis dynamic and bound at 2 and at 3."""
+    b = Builder("hand_shape_dynamic_batch_reshape", seed=977)
+    x = b.inp((2, 3, 6, 6), dims=["batch", 3, 6, 6])
+    y = b.node("Relu", [b.node("Conv", [x, b.cf((4, 3, 3, 3), 0.4), b.cf((4,))], kernel_shape=[3, 3], pads=[1, 1, 1, 1], strides=[1, 1])])
+    shp = b.node("Shape", [y])
+    n = b.node("Gather", [shp, b.const(np.array(0, np.int64), "i")], axis=0)
+    n1 = b.node("Unsqueeze", [n, b.ci([0])])
+    tgt = b.node("Concat", [n1, b.ci([-1])], axis=0)
+    flat = b.node("Reshape", [y, tgt])
+    z = b.node("Add", [b.node("MatMul", [flat, b.cf((4 * 36, 10), 0.2)]), b.cf((10,))])
+    b.out(z)
+    b.out(flat)
+    b.row("shape/dynamic_batch_reshape", 2, ["Conv+Relu", "FusedMatMul"])
+    b.case.expect["modes_differ"] = "FusedMatMul bias position"
+    b.alt = {x: Builder("alt", 978).data((3, 3, 6, 6))}
+    return b.finish()
+
+
+def make_case(seed):
+    """A random graph of 6-30 nodes: the one or two table rows the seed stands for plus motifs drawn at random, each reading the graph input shifted by
+    the previous motif's result, with glue in between and behind; deterministic from the seed alone."""
+    motif_rows = ROWS[:-len(HAND_ONLY_ROWS)]
+    forced = [motif_rows[k].split("/", 1) for k in range(seed % N_SEEDS, len(motif_rows), N_SEEDS)]  # every row occurs in the random corpus too
+    for attempt in range(64):
+        b = Builder(f"seed{seed}", seed=(seed << 8) + attempt)
+        r = b.rng
+        src = b.inp((int(r.integers(6, 10)), 320))
+        picks = [forced[k] for k in r.permutation(len(forced))]
+        prev, results = None, []
+        while picks or (len(b.case.nodes) < 14 and r.integers(3)):
+            motif, variant = picks.pop(0) if picks else (str(r.choice(list(MOTIFS))), None)
+            fn, variants = MOTIFS[motif]
+            variant = variant or str(r.choice([v for v in variants if v != "bias_len_mismatch"]))  # an expected error ends the run: only where the seed asks
+            cur = src if prev is None else _link(b, src, prev)
+            if len(b.case.nodes) < 12 and r.integers(2):
+                cur = glue(b, cur)
+            outs = fn(b, variant, cur)
+            results += outs
+            prev = next((o for o in outs if b.v[o].dtype == F), prev)
+        for o in results:
+            if b.v[o].dtype == F and len(b.case.nodes) < 27 and r.integers(2):
+                o = glue(b, o)
+            if o not in b.case.outputs:
+                b.out(o)
+        if 6 <= len(b.case.nodes) <= 30:
+            return b.finish()
+    raise AssertionError(f"seed {seed}: no graph of 6-30 nodes in 64 attempts")
+
+
+def corpus():
+    """Every case of the committed corpus: one hand-written graph per table row, then the random seeds."""
+    return [hand_case(r) for r in ROWS] + [make_case(s) for s in range(N_SEEDS)]
+
+
+PROBE = os.path.join(ROOT, "tests", "cpp", "_build", "graph_outputs_outlive_run")
+
+
+def build_outlive_probe():
+    """tests/cpp/graph_outputs_outlive_run.cpp: runs a graph, reuses the pool, THEN reads the outputs (the CLI reads them first)."""
+    import subprocess
+    from rten_amd import lib as L
+    L.load()
+    src = os.path.join(ROOT, "tests", "cpp", "graph_outputs_outlive_run.cpp")
+    deps = [src] + [os.path.join(ROOT, "include", h) for h in ("rten_hip_graph.hpp", "rten_hip_ops.hpp", "rten_hip_safetensors.hpp", "rten_hip.h")]
+    os.makedirs(os.path.dirname(PROBE), exist_ok=True)
+    if not os.path.exists(PROBE) or os.path.getmtime(PROBE) < max(os.path.getmtime(d) for d in deps):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", PROBE,
+                               "-L" + os.path.join(ROOT, "rten_amd"), "-lrten_hip", "-Wl,-rpath,$ORIGIN/../../../rten_amd",
+                               "-Wl,-rpath," + os.path.join(ROOT, "rten_amd"), "-Wl,-rpath,/opt/rocm/lib"])
+    return PROBE

@@ -1,0 +1,152 @@
+"""The graph fuzzer's generator and interpreter (tests/graph_fuzz.py), checked without a device: determinism, the C++ loader reads every graph,
+every row of the motif / spoiler table occurs, and the f32 interpreter agrees with an independent float64 evaluation."""
+import collections
+
+import numpy as np
+import pytest
+
+from tests import graph_fuzz as gf
+from tests.test_graph_executor import run_cli
+
+
+@pytest.fixture(scope="module")
+def corpus():
+    return gf.corpus()
+
+
+def test_same_seed_same_bytes():
+    for seed in (0, 1, 17, gf.N_SEEDS - 1):
+        a, b = gf.make_case(seed), gf.make_case(seed)
+        assert a.onnx == b.onnx and a.outputs == b.outputs and a.expect == b.expect
+        for k in a.inputs:
+            assert np.array_equal(a.inputs[k], b.inputs[k])
+    assert gf.make_case(1).onnx != gf.make_case(2).onnx
+    row = gf.ROWS[3]
+    assert gf.hand_case(row).onnx == gf.hand_case(row).onnx
+
+
+def test_corpus_shape(corpus):
+    assert len(corpus) == len(gf.ROWS) + gf.N_SEEDS and gf.N_SEEDS >= 64
+    assert len({c.name for c in corpus}) == len(corpus)
+    for c in corpus[len(gf.ROWS):]:
+        assert 6 <= len(c.nodes) <= 30, (c.name, len(c.nodes))
+    vals_seen = 0
+    for c in corpus:
+        for k in range(len(c.bindings)):
+            try:
+                vals = gf.evaluate(c, k, fused=False)
+            except gf.ExpectedError:
+                continue
+            for name, v in vals.items():
+                assert v.size <= gf.MAX_ELEMS, (c.name, name, v.shape)
+                vals_seen += 1
+    assert vals_seen > 2000
+
+
+def test_every_table_row_occurs(corpus):
+    """Computed from Case.expect: a row dropped from the generator (or from ROWS' source tables) fails here."""
+    table = {"conv": 23, "matmul": 24, "gemm": 7, "add_ln": 6, "add_softmax": 6, "views": 16, "int8": 6, "shape": 1}
+    assert collections.Counter(r.split("/")[0] for r in gf.ROWS) == table
+    hand = collections.Counter(r for c in corpus[:len(gf.ROWS)] for r in c.expect["rows"])
+    rand = collections.Counter(r for c in corpus[len(gf.ROWS):] for r in c.expect["rows"])
+    assert [r for r in gf.ROWS if hand[r] != 1] == []                                       # one minimal graph per row
+    assert [r for r in gf.ROWS if not rand[r] and r not in gf.HAND_ONLY_ROWS] == []         # and each motif row inside a random graph too
+    # the spoilers the table names, by what they must do to the plan
+    by_row = {c.expect["rows"][0]: c.expect for c in corpus[:len(gf.ROWS)]}
+    must_not_fuse = ["conv/res_after", "conv/add_same", "conv/out_second_reader", "conv/out_is_graph_output", "matmul/div_left", "matmul/bias_1xn",
+                     "matmul/bias_nonconst", "matmul/read_twice", "add_ln/axis_other", "add_ln/add_out_is_scale", "add_ln/add_is_output", "add_softmax/other_axis"]
+    for r in must_not_fuse:
+        assert by_row[r]["folded"] == 0 and by_row[r]["kinds"] == [], r
+    assert by_row["conv/add_is_output_relu_after"] == dict(by_row["conv/add_is_output_relu_after"], folded=1, kinds=["Conv+Add"])
+    assert by_row["conv/two_convs_one_add"]["kinds"] == ["Conv+Add+Relu"] and by_row["matmul/div_then_mul"]["folded"] == 1
+    assert by_row["matmul/bias_len_mismatch"]["error"] == {"fused": "Cannot broadcast bias to output shape", "nofuse": None}
+    assert sorted(k.split("+")[1] for r, e in by_row.items() if r.startswith("conv/act_") for k in e["kinds"]) == sorted(gf.ACT_KINDS)
+    assert sum(1 for c in corpus if len(c.bindings) == 2) >= 1                              # the dynamic axis bound at two sizes
+    assert sum(1 for c in corpus if len(c.outputs) != len(set(c.outputs))) >= 1             # an output listed twice
+    assert sum(1 for c in corpus if set(c.outputs) & set(c.inputs)) >= 1                    # a graph input returned as an output
+
+
+def test_cpp_loader_parses_every_graph(corpus, tmp_path):
+    """... and the load-time canonicalisation (Silu / Swish / Gelu / LayerNormalization idioms) finds nothing to rewrite: the plan the cases predict
+    is the plan of the nodes as written."""
+    for c in corpus:
+        p = tmp_path / "m.onnx"
+        p.write_bytes(c.onnx)
+        out = run_cli("--parse-only", str(p), timeout=60)
+        assert out.returncode == 0, (c.name, out.stderr)
+        assert f"{len(c.nodes)} nodes, {len(c.inits)} initializers" in out.stdout, (c.name, out.stdout)
+        assert "canonical form" not in out.stdout, (c.name, out.stdout)
+        for name, dims in c.input_specs:
+            assert f"input  {name}:" in out.stdout, (c.name, name)
+
+
+def test_fused_and_unfused_expectations_differ_only_where_the_case_says(corpus):
+    for c in corpus:
+        if c.expect["error"]:
+            with pytest.raises(gf.ExpectedError, match=c.expect["error"]["fused"]):
+                gf.evaluate(c, 0, fused=True)
+            gf.evaluate(c, 0, fused=False)
+            continue
+        a, b = gf.evaluate(c, 0, fused=True), gf.evaluate(c, 0, fused=False)
+        same = all(np.array_equal(a[o], b[o], equal_nan=True) for o in c.outputs)
+        assert same or c.expect["modes_differ"], c.name
+    assert sum(1 for c in corpus if c.expect["modes_differ"]) >= 10
+
+
+def test_interpreter_against_independent_float64(corpus):
+    """Every float value of every graph, f32 oracle against float64: deviation = |f32 - f64| / (1 + |f64|).
+
+    Measured over this corpus: worst deviation 2.13e-6 (matmul/div_right_np2: a K = 256 product divided by 0.3); the values that the fused
+    expectation computes differently (FusedMatMul with alpha, the bias position) deviate by 2.13e-6 at most as well.  The bound is 4x that,
+    gf.F64_BOUND = 8.5e-6 -- the corpus is fixed, only libm varies.  Integer outputs (u8 codes and zero points, ArgMax / TopK indices) are compared
+    where the float64 decision is not within the same bound of a tie; fewer than 1% of them may be left out on that ground."""
+    worst, worst_at, worst_fused = 0.0, None, 0.0
+    ints = skipped = 0
+    for c in corpus:
+        for k in range(len(c.bindings)):
+            teacher = gf.evaluate(c, k, fused=False)
+            v64, ties = gf.evaluate64(c, k, teacher=teacher)
+            for n in c.nodes:
+                for o in n["outputs"]:
+                    if not o:
+                        continue
+                    got = teacher[o]
+                    if got.dtype == np.float32:
+                        want = v64[o]
+                        assert got.shape == want.shape and want.dtype == np.float64, (c.name, n["op"], o)
+                        assert np.array_equal(np.isnan(got), np.isnan(want)), (c.name, n["op"], o)
+                        fin = np.isfinite(want)
+                        assert np.array_equal(got[~fin & ~np.isnan(want)], want[~fin & ~np.isnan(want)]), (c.name, n["op"], o)
+                        if fin.any():
+                            d = float((np.abs(got[fin].astype(np.float64) - want[fin]) / (1.0 + np.abs(want[fin]))).max())
+                            if d > worst:
+                                worst, worst_at = d, (c.name, n["op"], o)
+                    elif o + "#f64" in v64:
+                        want = v64[o + "#f64"]
+                        assert got.shape == want.shape, (c.name, n["op"], o)
+                        tie = np.broadcast_to(ties.get(o, np.zeros((), bool)), got.shape)
+                        ints += got.size
+                        skipped += int(tie.sum())
+                        assert np.array_equal(got[~tie].astype(np.int64), want[~tie].astype(np.int64)), (c.name, n["op"], o)
+            # ... and the interpreter's arithmetic-changing rules (FusedMatMul with alpha, the bias position): every float value of the FUSED
+            # expectation against the same float64 values, same bound
+            try:
+                fused = gf.evaluate(c, k, fused=True)
+            except gf.ExpectedError:
+                continue
+            for o, got in fused.items():
+                if got.dtype != np.float32 or o not in v64 or np.array_equal(got, teacher[o], equal_nan=True):  # (only what the rules changed)
+                    continue
+                want = v64[o]
+                assert got.shape == want.shape and np.array_equal(np.isnan(got), np.isnan(want)), (c.name, "fused", o)
+                fin = np.isfinite(want)
+                if fin.any():
+                    d = float((np.abs(got[fin].astype(np.float64) - want[fin]) / (1.0 + np.abs(want[fin]))).max())
+                    worst_fused = max(worst_fused, d)
+                    if d > worst:
+                        worst, worst_at = d, (c.name, "fused", o)
+    print(f"worst deviation of the fused expectation {worst_fused:.3e}")
+    assert worst_fused > 0.0
+    print(f"worst f32 / float64 deviation {worst:.3e} at {worst_at}; {skipped} of {ints} integer elements near a tie")
+    assert worst <= gf.F64_BOUND, (worst, worst_at)  # measured 2.13e-6, bound 4x = 8.5e-6
+    assert ints > 1000 and skipped < 0.01 * ints, (skipped, ints)
