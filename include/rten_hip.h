@@ -556,6 +556,33 @@ int32_t rten_hip_conv_transpose_output_size(int32_t in_h, int32_t in_w, int32_t 
                                             int32_t out_pads[4], const char **msg);
 int32_t rten_hip_conv_transpose2d_f32(rten_hip_ctx *ctx, const rten_hip_conv2d_desc *desc, const float *x, const float *w, const float *bias, float *y);
 
+/* ---- GRU / LSTM: src/ops/rnn.rs:138-328 (gru), :413-597 (lstm) ----
+ * One recurrent layer.  X [seq, batch, input] (read through the element strides x_ss / x_bs of its first two dims, 0 = contiguous; the last dim is
+ * contiguous), W [dirs, G * hidden, input], R [dirs, G * hidden, hidden], B [dirs, 2 * G * hidden] or NULL (input biases, then recurrent biases),
+ * initial_h / initial_c [dirs, batch, hidden] or NULL (zeros); G = 3 gates in the order update, reset, hidden (GRU), 4 in the order input, output,
+ * forget, cell (LSTM).  Outputs, each of which may be NULL (not written): Y [seq, dirs, batch, hidden], Y_h and Y_c [dirs, batch, hidden].
+ * direction: RTEN_HIP_RNN_*; direction 1 of a bidirectional layer and `reverse` walk the sequence backwards.  The reference's arithmetic one rounded operation at a
+ * time (sigmoid / tanh are the vecmath functions, also for the LSTM's tanh(c), where the reference calls the host's libm); products in its depth-blocked
+ * order, and in its one-row order when batch == 1 and seq < 5 (PREPACK_MIN_SEQ_LEN: unpacked operands) under rten_hip_set_gemv_order.  The input
+ * projection of all time steps is one GEMM launch; workspace comes from the context's auxiliary scratch; nothing is read back (capture-safe once the
+ * scratch has its size).  GRU with linear_before_reset == 0: RTEN_HIP_ERR_UNSUPPORTED "`linear_before_reset=0` is not supported". */
+#define RTEN_HIP_RNN_FORWARD 0
+#define RTEN_HIP_RNN_REVERSE 1
+#define RTEN_HIP_RNN_BIDIRECTIONAL 2
+int32_t rten_hip_gru_f32(rten_hip_ctx *ctx, int32_t seq, int32_t batch, int32_t input, int32_t hidden, int32_t direction, int32_t linear_before_reset,
+                         int64_t x_ss, int64_t x_bs, const float *x, const float *w, const float *r, const float *b, const float *initial_h, float *y,
+                         float *y_h);
+int32_t rten_hip_lstm_f32(rten_hip_ctx *ctx, int32_t seq, int32_t batch, int32_t input, int32_t hidden, int32_t direction, int64_t x_ss, int64_t x_bs,
+                          const float *x, const float *w, const float *r, const float *b, const float *initial_h, const float *initial_c, float *y,
+                          float *y_h, float *y_c);
+/* Recurrent path (tuning knob, sticky, default 0; part of rten_hip_tuning_save / _restore): 0 = automatic (today: the composed path everywhere -- the fused kernel has not been timed against it yet, docs/KERNELS.md 4.6), 1 = composed (per time step and direction the
+ * f32 GEMM for h.R^T plus one gate kernel), 2 = the fused kernel (one launch walks every time step: a workgroup owns 16 batch rows of one direction, h in
+ * LDS, h.R^T as 16x16x4 MFMA chains in the same order) or RTEN_HIP_ERR_UNSUPPORTED where it does not cover the call: hidden > RTEN_HIP_RNN_FUSED_MAX_HIDDEN
+ * (a register limit: a wave keeps the accumulators, the step's projection and the biases of 2 x 16 hidden units x all gates; twice as many spill),
+ * or the one-row case above.  Same bits on every path. */
+#define RTEN_HIP_RNN_FUSED_MAX_HIDDEN 256
+int32_t rten_hip_set_rnn_path(rten_hip_ctx *ctx, int32_t mode);
+
 /* ---- MatMulNBits (com.microsoft contrib op): src/ops/matmul/contrib.rs:21-106, rten-gemm/src/block_quant.rs:61-141 (vector x
  * matrix), rten-gemm/src/packing.rs:229-318 (dequantise-while-packing for the ordinary GEMM) ----
  * a [batch][rows][k] f32; b_quant [n][k / block_size][block_size / 2] packed 4-bit (even element low nibble), zero point 8;
@@ -691,7 +718,7 @@ int32_t rten_hip_model_output(rten_hip_model *model, int32_t i, const void **dev
 int32_t rten_hip_model_destroy(rten_hip_model *model);
 
 /* ---- tuning knobs are sticky per context.  save / restore snapshot all of them (GEMM variant override, split-K plan, tile order, gemv order and its
- * thread assumption, int8 path, attention path): code that changes knobs around its own launches on a context it does not own restores the owner's
+ * thread assumption, int8 path, attention path, recurrent path): code that changes knobs around its own launches on a context it does not own restores the owner's
  * settings, not the defaults. */
 int32_t rten_hip_tuning_save(rten_hip_ctx *ctx, int32_t state[8]);
 int32_t rten_hip_tuning_restore(rten_hip_ctx *ctx, const int32_t state[8]);

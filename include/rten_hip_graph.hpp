@@ -53,6 +53,7 @@ struct Attr {
     std::string s;
     std::vector<float> floats;
     std::vector<int64_t> ints;
+    std::vector<std::string> strings;
     TensorProto t;
 };
 struct Node {
@@ -171,6 +172,7 @@ inline Attr parse_attr(Reader r) {
         else if (f == 5 && w == 2) a.t = parse_tensor(r.sub());
         else if (f == 7) r.repeated(w, 5, [&](Reader &q) { const uint32_t b = q.fixed32(); float v; std::memcpy(&v, &b, 4); a.floats.push_back(v); });
         else if (f == 8) r.repeated(w, 0, [&](Reader &q) { a.ints.push_back((int64_t)q.varint()); });
+        else if (f == 9 && w == 2) a.strings.push_back(r.str());
         else if (f == 20 && w == 0) a.type = (int)r.varint();
         else r.skip(w);
     }
@@ -799,6 +801,48 @@ class Graph {
             }
         }
         return result;
+    }
+
+    // What a GRU / LSTM node asks for, read as onnx_registry.rs:1214-1226,1306-1370 reads it: activations other than the defaults, activation_alpha / _beta,
+    // clip != 0, layout != 0 and input_forget != 0 are load errors that name the node; so are GRU's linear_before_reset=0 (the operator refuses it,
+    // rnn.rs:153-158: no point in loading such a model), a peephole input, and a sequence_lens input (the reference reads it and ignores it: refusing is the
+    // safe reading, and exporters leave it empty for unpacked input).  Needs no device.
+    struct RnnNode {
+        bool lstm = false;
+        RnnDirection direction = RnnDirection::Forward;
+        int64_t hidden_size = 0;
+        unsigned output_mask = 0; // bit i: output i is named
+    };
+    static RnnNode read_rnn_node(const onnx::Node &n, const std::string &label) {
+        const std::string kind = n.op_type, where = kind + " " + label + ": ";
+        RnnNode a;
+        a.lstm = kind == "LSTM";
+        if (!n.attr("hidden_size")) throw GraphError(where + "the hidden_size attribute is missing");
+        a.hidden_size = n.get_int("hidden_size", 0);
+        if (const onnx::Attr *d = n.attr("direction")) {
+            if (d->s == "forward") a.direction = RnnDirection::Forward;
+            else if (d->s == "reverse") a.direction = RnnDirection::Reverse;
+            else if (d->s == "bidirectional") a.direction = RnnDirection::Bidirectional;
+            else throw GraphError(where + "direction=\"" + d->s + "\" is not supported");
+        }
+        const size_t dirs = a.direction == RnnDirection::Bidirectional ? 2 : 1;
+        for (const char *nm : {"activation_alpha", "activation_beta"})
+            if (const onnx::Attr *p = n.attr(nm)) if (!p->floats.empty()) throw GraphError(where + nm + " is not supported");
+        if (const onnx::Attr *p = n.attr("activations")) {
+            static const std::vector<std::string> gru_acts = {"Sigmoid", "Tanh"}, lstm_acts = {"Sigmoid", "Tanh", "Tanh"};
+            const std::vector<std::string> &defaults = a.lstm ? lstm_acts : gru_acts;
+            bool ok = p->strings.empty() || p->strings.size() == defaults.size() * dirs;
+            for (size_t i = 0; ok && i < p->strings.size(); i++) ok = p->strings[i] == defaults[i % defaults.size()];
+            if (!ok) throw GraphError(where + "activations other than the defaults are not supported");
+        }
+        if (n.get_float("clip", 0.f) != 0.f) throw GraphError(where + "clip is not supported");
+        if (n.get_int("layout", 0) != 0) throw GraphError(where + "layout=" + std::to_string(n.get_int("layout", 0)) + " is not supported");
+        if (a.lstm && n.get_int("input_forget", 0) != 0) throw GraphError(where + "input_forget is not supported");
+        if (!a.lstm && n.get_int("linear_before_reset", 0) == 0) throw GraphError(where + "`linear_before_reset=0` is not supported");
+        if (n.inputs.size() > 4 && !n.inputs[4].empty()) throw GraphError(where + "a sequence_lens input is not supported (the reference ignores it)");
+        if (a.lstm && n.inputs.size() > 7 && !n.inputs[7].empty()) throw GraphError(where + "a peephole input (P) is not supported");
+        for (size_t k = 0; k < n.outputs.size() && k < (a.lstm ? 3u : 2u); k++) if (!n.outputs[k].empty()) a.output_mask |= 1u << k;
+        return a;
     }
 
   private:
@@ -1974,6 +2018,7 @@ class Graph {
             else if (kind == "ArgMax" || kind == "ArgMin" || kind == "TopK" || kind == "Softmax") make_select_step(st, n);
             else if (kind == "Resize" || kind == "Upsample") make_resize_step(st, n);
             else if (kind == "Split") make_split_step(st, n);
+            else if (kind == "GRU" || kind == "LSTM") make_rnn_step(st, n);
             else if (kind == "Flatten" || kind == "Reshape" || kind == "Squeeze" || kind == "Unsqueeze" || kind == "Identity" || kind == "Dropout") make_view_step(st, n);
             else if (make_layout_step(st, n)) {
                 // Shape / ConstantOfShape / NonZero / Range / Slice / Concat / Expand / Where / comparisons / logic / integer arithmetic / Cast / Gather /
@@ -2584,6 +2629,21 @@ class Graph {
             }
             return o;
         };
+    }
+
+    // GRU / LSTM: attributes through read_rnn_node (public: what the reference refuses at load is refused here, device or not); unnamed outputs are not
+    // computed.  Rows of the batch are independent (not batch_coupled); the workspace is the context's auxiliary scratch, sized by the warm-up run before a capture.
+    void make_rnn_step(Step &st, const onnx::Node &n) {
+        const RnnNode a = read_rnn_node(n, st.name);
+        if (a.lstm) {
+            auto op = std::make_shared<LSTM>();
+            op->direction = a.direction; op->hidden_size = a.hidden_size; op->output_mask = a.output_mask;
+            run_plainly(st, op);
+        } else {
+            auto op = std::make_shared<GRU>();
+            op->direction = a.direction; op->hidden_size = a.hidden_size; op->output_mask = a.output_mask; op->linear_before_reset = true;
+            run_plainly(st, op);
+        }
     }
 
     // Shape-only operators: the output aliases the input's buffer (src/ops/layout.rs reshapes in place when it can).

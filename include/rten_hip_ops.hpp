@@ -2373,6 +2373,77 @@ struct Einsum : Operator { // src/ops/einsum.rs:21-108
     }
 };
 
+// ------------------------------------------------------------------------------------------------ recurrent layers (src/ops/rnn.rs)
+enum class RnnDirection { Forward = RTEN_HIP_RNN_FORWARD, Reverse = RTEN_HIP_RNN_REVERSE, Bidirectional = RTEN_HIP_RNN_BIDIRECTIONAL };
+
+namespace rnn_detail {
+// static_dims! (src/operator.rs:210-241)
+inline const Tensor &dims(const Tensor &t, int nd, const char *what, const char *names = nullptr) {
+    if (t.ndim() != nd) throw OpError(OpError::InvalidValue, std::string(what) + " must have " + std::to_string(nd) + " dims" + (names ? " (" + std::string(names) + ")" : ""));
+    return want(t, DType::F32, "float32");
+}
+// Y [seq, dirs, batch, hidden], Y_h (, Y_c) [dirs, batch, hidden]; an output the mask leaves out is an empty Tensor and is not computed
+inline OutputList outputs(Context &ctx, const Tensor &x, int64_t hidden, RnnDirection dir, int n_out, unsigned mask) {
+    const int64_t dirs = dir == RnnDirection::Bidirectional ? 2 : 1;
+    OutputList out;
+    for (int i = 0; i < n_out; i++) {
+        if (!(mask >> i & 1)) { out.emplace_back(); continue; }
+        if (i == 0) out.emplace_back(ctx, std::vector<int64_t>{x.size(0), dirs, x.size(1), hidden}, DType::F32);
+        else out.emplace_back(ctx, std::vector<int64_t>{dirs, x.size(1), hidden}, DType::F32);
+    }
+    return out;
+}
+} // namespace rnn_detail
+
+// GRU (src/ops/rnn.rs:107-383): inputs X, W, R, B?, sequence_lens? (ignored, as in the reference), initial_h?; gate order update, reset, hidden.
+// `output_mask` bit i = compute output i (Y, Y_h): a graph node may leave outputs unnamed.
+struct GRU : Operator {
+    RnnDirection direction = RnnDirection::Forward;
+    int64_t hidden_size = 0; // inferred from W, as in the reference
+    bool linear_before_reset = false;
+    unsigned output_mask = 3;
+    const char *name() const override { return "GRU"; }
+    int max_inputs() const override { return 6; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        if (!linear_before_reset) throw OpError(OpError::UnsupportedValue, "`linear_before_reset=0` is not supported");
+        const Tensor &x = rnn_detail::dims(require(in, 0), 3, "input", "seq, batch, input");
+        const Tensor &w = rnn_detail::dims(require(in, 1), 3, "weights", "dir, hidden x 3, input");
+        const Tensor &r = rnn_detail::dims(require(in, 2), 3, "recurrent_weights");
+        const Tensor *b = get(in, 3), *h0 = get(in, 5);
+        if (b) rnn_detail::dims(*b, 2, "bias", "dir, hidden x 6");
+        if (h0) rnn_detail::dims(*h0, 3, "initial_hidden");
+        const int64_t hidden = w.size(1) / 3;
+        OutputList out = rnn_detail::outputs(ctx, x, hidden, direction, 2, output_mask);
+        ctx.check(rten_hip_gru_f32(ctx.raw(), (int32_t)x.size(0), (int32_t)x.size(1), (int32_t)x.size(2), (int32_t)hidden, (int32_t)direction, 1, 0, 0, (const float *)x.ptr(), (const float *)w.ptr(), (const float *)r.ptr(), (const float *)vp(b), (const float *)vp(h0),
+                                   (float *)out[0].ptr(), (float *)out[1].ptr()));
+        return out;
+    }
+};
+
+// LSTM (src/ops/rnn.rs:385-660): inputs X, W, R, B?, sequence_lens? (ignored), initial_h?, initial_c?; gate order input, output, forget, cell; outputs Y, Y_h, Y_c.
+struct LSTM : Operator {
+    RnnDirection direction = RnnDirection::Forward;
+    int64_t hidden_size = 0;
+    unsigned output_mask = 7;
+    const char *name() const override { return "LSTM"; }
+    int max_inputs() const override { return 7; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = rnn_detail::dims(require(in, 0), 3, "input", "seq, batch, input");
+        const Tensor &w = rnn_detail::dims(require(in, 1), 3, "weights", "dir, hidden x 4, input");
+        const Tensor &r = rnn_detail::dims(require(in, 2), 3, "recurrent_weights", "dir, hidden x 4, hidden");
+        if (w.size(1) % 4 != 0) throw OpError(OpError::InvalidValue, "weights dim 1 must be 4 * hidden_size");
+        const Tensor *b = get(in, 3), *h0 = get(in, 5), *c0 = get(in, 6);
+        if (b) { rnn_detail::dims(*b, 2, "bias"); if (b->size(1) % 8 != 0) throw OpError(OpError::InvalidValue, "bias dim 1 must be 8 * hidden_size"); }
+        if (h0) rnn_detail::dims(*h0, 3, "initial_hidden");
+        if (c0) rnn_detail::dims(*c0, 3, "initial_cell");
+        const int64_t hidden = w.size(1) / 4;
+        OutputList out = rnn_detail::outputs(ctx, x, hidden, direction, 3, output_mask);
+        ctx.check(rten_hip_lstm_f32(ctx.raw(), (int32_t)x.size(0), (int32_t)x.size(1), (int32_t)x.size(2), (int32_t)hidden, (int32_t)direction, 0, 0, (const float *)x.ptr(), (const float *)w.ptr(), (const float *)r.ptr(), (const float *)vp(b), (const float *)vp(h0),
+                                    (const float *)vp(c0), (float *)out[0].ptr(), (float *)out[1].ptr(), (float *)out[2].ptr()));
+        return out;
+    }
+};
+
 // ------------------------------------------------------------------------------------------------ registry (src/op_registry.rs:25-72)
 class OpRegistry {
   public:
@@ -2438,6 +2509,8 @@ class OpRegistry {
         r.register_op<ArgMax>("ArgMax");
         r.register_op<ArgMin>("ArgMin");
         r.register_op<TopK>("TopK");
+        r.register_op<GRU>("GRU");
+        r.register_op<LSTM>("LSTM");
         return r;
     }
 

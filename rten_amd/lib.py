@@ -18,6 +18,9 @@ ERR_INVALID_VALUE, ERR_INCOMPATIBLE_SHAPES, ERR_UNSUPPORTED, ERR_HIP, ERR_NO_DEV
 
 BIAS_NONE, BIAS_PER_ROW, BIAS_PER_COL = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
+RNN_FORWARD, RNN_REVERSE, RNN_BIDIRECTIONAL = 0, 1, 2
+RNN_PATH_AUTO, RNN_PATH_COMPOSED, RNN_PATH_FUSED = 0, 1, 2  # rten_hip_set_rnn_path
+RNN_FUSED_MAX_HIDDEN = 256
 # act_kind of rten_hip_activation_f32 / rten_hip_gemm_f32_act / rten_hip_conv2d_f32_act (which also take the three above)
 ACT_SIGMOID, ACT_SILU, ACT_SWISH, ACT_HARD_SIGMOID, ACT_HARD_SWISH, ACT_CLIP, ACT_LEAKY_RELU, ACT_ELU = 3, 4, 5, 6, 7, 8, 9, 10
 # mode / coord_mode / nearest_mode of rten_hip_resize_f32 (RTEN_HIP_RESIZE_*)
@@ -204,6 +207,9 @@ PROTOTYPES = {
     "rten_hip_set_int8_path": (_I32, [_VP, _I32]),
     "rten_hip_set_int8_tile": (_I32, [_VP, _I32, C.POINTER(C.c_int32)]),
     "rten_hip_set_sdpa_path": (_I32, [_VP, _I32]),
+    "rten_hip_gru_f32": (_I32, [_VP] + [_I32] * 6 + [_I64, _I64] + [_VP] * 7),
+    "rten_hip_lstm_f32": (_I32, [_VP] + [_I32] * 5 + [_I64, _I64] + [_VP] * 9),
+    "rten_hip_set_rnn_path": (_I32, [_VP, _I32]),
     # the plan executor behind the C ABI (csrc/graph_abi.cpp)
     "rten_hip_model_load": (_I32, [_VP, _VP, _SZ, C.c_char_p, _I32, _I32, C.POINTER(_VP)]),
     "rten_hip_model_load_ex": (_I32, [_VP, _VP, _SZ, C.c_char_p, _I32, _U32, C.POINTER(_VP)]),

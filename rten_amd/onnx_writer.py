@@ -60,7 +60,7 @@ def tensor(name: str, arr) -> bytes:
 
 def attr(name: str, value) -> bytes:
     """AttributeProto: name = 1, f = 2, i = 3, s = 4, t = 5, floats = 7, ints = 8, type = 20
-    (AttributeType FLOAT = 1, INT = 2, STRING = 3, TENSOR = 4, FLOATS = 6, INTS = 7)."""
+    (AttributeType FLOAT = 1, INT = 2, STRING = 3, TENSOR = 4, FLOATS = 6, INTS = 7), strings = 9 (STRINGS = 8)."""
     out = _str(1, name)
     if isinstance(value, bool) or isinstance(value, (int, np.integer)):
         return out + _vi(3, int(value)) + _vi(20, 2)
@@ -71,6 +71,8 @@ def attr(name: str, value) -> bytes:
     if isinstance(value, np.ndarray):
         return out + _ld(5, tensor("", value)) + _vi(20, 4)
     value = list(value)
+    if value and all(isinstance(v, str) for v in value):
+        return out + b"".join(_ld(9, v.encode()) for v in value) + _vi(20, 8)
     if all(isinstance(v, (int, np.integer)) for v in value):
         return out + b"".join(_vi(8, int(v)) for v in value) + _vi(20, 7)
     return out + b"".join(_key(7, 5) + struct.pack("<f", float(v)) for v in value) + _vi(20, 6)

@@ -1583,6 +1583,102 @@ class Split(Operator):
         return outs
 
 
+RNN_DIRECTIONS = {"forward": L.RNN_FORWARD, "reverse": L.RNN_REVERSE, "bidirectional": L.RNN_BIDIRECTIONAL}
+
+
+def _rnn_dims(t, ndim, what, names=None):
+    """static_dims! (src/operator.rs:210-241): "<name> must have N dims (<names>)"."""
+    if len(t.shape) != ndim:
+        raise InvalidValue(f"{what} must have {ndim} dims" + (f" ({names})" if names else ""))
+    return _want(t, np.float32)
+
+
+class _Recurrent(Operator):
+    """What GRU and LSTM share (src/ops/rnn.rs): the direction attribute, output allocation and the C-ABI call.  `outputs` selects which of
+    Y, Y_h (, Y_c) are computed: an entry that is False comes back as None (a graph node may leave outputs unnamed)."""
+
+    GATES = 0
+
+    def _direction(self):
+        if self.direction not in RNN_DIRECTIONS:
+            raise InvalidValue(f"unknown direction {self.direction!r}")
+        return RNN_DIRECTIONS[self.direction]
+
+    def _launch(self, ctx, symbol, x, operands, n_out, outputs):
+        seq, batch, n_in = x.shape
+        dirs = 2 if self.direction == "bidirectional" else 1
+        hidden = operands[0].shape[1] // self.GATES
+        want = list(outputs) if outputs is not None else [True] * n_out
+        shapes = [(seq, dirs, batch, hidden)] + [(dirs, batch, hidden)] * (n_out - 1)
+        outs = [DeviceTensor(ctx, sh, np.float32) if w else None for sh, w in zip(shapes, want)]
+        geometry = [seq, batch, n_in, hidden, self._direction()] + ([1] if self.GATES == 3 else []) + [0, 0]  # (GRU: linear_before_reset; X contiguous)
+        try:
+            ctx.call(symbol, *geometry, x.vp, *[_vp(t) for t in operands], *[_vp(t) for t in outs])
+        except L.HipError as e:
+            if e.code == L.ERR_UNSUPPORTED:
+                raise UnsupportedValue(e.msg)
+            raise
+        return outs
+
+
+class GRU(_Recurrent):
+    """src/ops/rnn.rs:107-383.  Inputs X [seq, batch, input], W [dirs, 3 * hidden, input], R [dirs, 3 * hidden, hidden], B [dirs, 6 * hidden]
+    (optional), sequence_lens (ignored, as in the reference), initial_h [dirs, batch, hidden] (optional); gate order update, reset, hidden.
+    Outputs Y [seq, dirs, batch, hidden] and Y_h [dirs, batch, hidden]."""
+
+    GATES = 3
+
+    def __init__(self, direction="forward", hidden_size=0, linear_before_reset=False):
+        self.direction, self.hidden_size, self.linear_before_reset = direction, hidden_size, linear_before_reset
+
+    def max_inputs(self):
+        return 6
+
+    def run(self, ctx, inputs, outputs=None):
+        if not self.linear_before_reset:
+            raise UnsupportedValue("`linear_before_reset=0` is not supported")
+        x = _rnn_dims(_require(inputs, 0), 3, "input", "seq, batch, input")
+        w = _rnn_dims(_require(inputs, 1), 3, "weights", "dir, hidden x 3, input")
+        r = _rnn_dims(_require(inputs, 2), 3, "recurrent_weights")
+        b, h0 = _get(inputs, 3), _get(inputs, 5)
+        if b is not None:
+            _rnn_dims(b, 2, "bias", "dir, hidden x 6")
+        if h0 is not None:
+            _rnn_dims(h0, 3, "initial_hidden")
+        return self._launch(ctx, "rten_hip_gru_f32", x, [w, r, b, h0], 2, outputs)
+
+
+class LSTM(_Recurrent):
+    """src/ops/rnn.rs:385-660.  Inputs X, W [dirs, 4 * hidden, input], R [dirs, 4 * hidden, hidden], B [dirs, 8 * hidden] (optional), sequence_lens
+    (ignored), initial_h, initial_c [dirs, batch, hidden] (optional); gate order input, output, forget, cell.  Outputs Y, Y_h, Y_c.  tanh(c) in
+    h = o * tanh(c) is the vecmath tanh (the reference calls the host's libm there: docs/KERNELS.md)."""
+
+    GATES = 4
+
+    def __init__(self, direction="forward", hidden_size=0):
+        self.direction, self.hidden_size = direction, hidden_size
+
+    def max_inputs(self):
+        return 7
+
+    def run(self, ctx, inputs, outputs=None):
+        x = _rnn_dims(_require(inputs, 0), 3, "input", "seq, batch, input")
+        w = _rnn_dims(_require(inputs, 1), 3, "weights", "dir, hidden x 4, input")
+        r = _rnn_dims(_require(inputs, 2), 3, "recurrent_weights", "dir, hidden x 4, hidden")
+        if w.shape[1] % 4 != 0:
+            raise InvalidValue("weights dim 1 must be 4 * hidden_size")
+        b, h0, c0 = _get(inputs, 3), _get(inputs, 5), _get(inputs, 6)
+        if b is not None:
+            _rnn_dims(b, 2, "bias")
+            if b.shape[1] % 8 != 0:
+                raise InvalidValue("bias dim 1 must be 8 * hidden_size")
+        if h0 is not None:
+            _rnn_dims(h0, 3, "initial_hidden")
+        if c0 is not None:
+            _rnn_dims(c0, 3, "initial_cell")
+        return self._launch(ctx, "rten_hip_lstm_f32", x, [w, r, b, h0, c0], 3, outputs)
+
+
 class OpRegistry:
     """Mirror of OpRegistry (src/op_registry.rs:25-72): op_type -> operator class for the hot path."""
 
@@ -1595,7 +1691,7 @@ class OpRegistry:
         for op in (Conv, ConvTranspose, ConvInteger, ConvIntegerToFloat, MatMul, FusedMatMul, Gemm, MatMulInteger, MatMulIntegerToFloat, MatMulNBits,
                    Softmax, AddSoftmax, LayerNormalization, BatchNormalization, Relu, Gelu, Erf, Add, Mul, Sub, Div, Transpose, MaxPool,
                    AveragePool, GlobalAveragePool, Flatten, DynamicQuantizeLinear, Attention, Gather, ReduceSum, ReduceMean, Einsum, Resize, Upsample,
-                   Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK):
+                   Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK, GRU, LSTM):
             r.register_op(op)
         return r
 

@@ -288,6 +288,31 @@ def main():
             mfma(f"sdpa general ({label})", f"b={B2} h={H2} s={S2} t={T2} d={D2}", fn, 4.0 * B2 * H2 * S2 * T2 * D2, F32_PEAK_TF, "TFLOP/s")
             ctx.call("rten_hip_set_sdpa_path", 0)
 
+    # ---- recurrent layers at a text-recogniser size (bidirectional, 128 columns, 256 features, hidden 256), batch 32 and batch 1: the time-persistent
+    #      fused kernel against per-step launches (f32 GEMM + gate kernel).  Each row also carries us per time step.
+    for lstm in (False, True):
+        for batch in (32, 1):
+            seq, n_in, hid, G = 128, 256, 256, 4 if lstm else 3
+            xr = dev(rng.standard_normal((seq, batch, n_in), dtype=np.float32))
+            wr = dev(rng.standard_normal((2, G * hid, n_in), dtype=np.float32) / 16)
+            rr = dev(rng.standard_normal((2, G * hid, hid), dtype=np.float32) / 16)
+            br = dev(rng.standard_normal((2, 2 * G * hid), dtype=np.float32) / 4)
+            yr, yh, yc = empty((seq, 2, batch, hid)), empty((2, batch, hid)), empty((2, batch, hid))
+            geo = (seq, batch, n_in, hid, L.RNN_BIDIRECTIONAL)
+            for path, label in ((L.RNN_PATH_FUSED, "fused: one launch walks all steps"), (L.RNN_PATH_COMPOSED, "composed: GEMM + gate kernel per step")):
+                def fn(lstm=lstm, geo=geo, xr=xr, wr=wr, rr=rr, br=br, yr=yr, yh=yh, yc=yc):
+                    if lstm:
+                        ctx.call("rten_hip_lstm_f32", *geo, 0, 0, xr.vp, wr.vp, rr.vp, br.vp, None, None, yr.vp, yh.vp, yc.vp)
+                    else:
+                        ctx.call("rten_hip_gru_f32", *geo, 1, 0, 0, xr.vp, wr.vp, rr.vp, br.vp, None, yr.vp, yh.vp)
+                ctx.call("rten_hip_set_rnn_path", path)
+                before = len(rows)
+                mfma(f"{'LSTM' if lstm else 'GRU'} bidirectional ({label})", f"seq={seq} batch={batch} input={n_in} hidden={hid}", fn,
+                     2.0 * 2 * seq * batch * G * hid * (n_in + hid), F32_PEAK_TF, "TFLOP/s")
+                ctx.call("rten_hip_set_rnn_path", L.RNN_PATH_AUTO)
+                for row in rows[before:]:
+                    row["us_per_step"] = round(row["us"] / seq, 2)
+
     # ---- int8 GEMM / conv (u8 activations x i8 weights)
     for (m, k, n) in ((4096, 768, 768), (4096, 768, 3072)):
         a = dev(rng.integers(0, 255, (m, k)).astype(np.uint8)); w = dev(rng.integers(-127, 127, (k, n)).astype(np.int8))

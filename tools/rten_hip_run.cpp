@@ -16,7 +16,7 @@
 //     -t, --timing           per-operator table (each operator followed by a sync)
 //     --tune                 time the candidate launch plans of every f32 convolution at load and keep the fastest
 //     --graph                capture one run into a hipGraph and replay it for the timed runs
-//     --parse-only           print the model summary and exit (needs no GPU)
+//     --parse-only           print the model summary (and check the attributes of GRU / LSTM nodes as the loader does) and exit (needs no GPU)
 //     --safetensors-info F   list the tensors of a Safetensors file (with --save-outputs: re-write it); no model, no GPU
 //
 // There is no CPU fallback: without an MI355X the tool reports BackendUnavailable and exits 2.
@@ -115,6 +115,12 @@ int main(int argc, char **argv) {
                 std::printf("\n");
             }
         }
+        for (auto &n : Graph::canonical_form(m).nodes) // recurrent layers: what the loader would refuse is refused here too (needs no GPU)
+            if (n.domain.empty() || n.domain == "ai.onnx") if (n.op_type == "GRU" || n.op_type == "LSTM") {
+                const Graph::RnnNode a = Graph::read_rnn_node(n, n.name.empty() ? n.outputs.at(0) : n.name);
+                std::printf("  recurrent step %s \"%s\": %s, hidden_size %" PRId64 "\n", n.op_type.c_str(), n.name.c_str(),
+                            a.direction == RnnDirection::Bidirectional ? "bidirectional" : a.direction == RnnDirection::Reverse ? "reverse" : "forward", a.hidden_size);
+            }
         if (parse_only) return 0;
 
         Context ctx(0);

@@ -16,6 +16,8 @@ Test and tooling infrastructure only: nothing under rten_amd/ imports this.
     python tools/torch_export.py classifier_topk /tmp/cls_topk.onnx    # the mobile network + softmax(-1) + topk(5)
     python tools/torch_export.py segment_argmax /tmp/seg_argmax.onnx   # mobile features + class conv + bilinear interpolate + argmax(1)
     python tools/torch_export.py yolo_filter /tmp/yolo_filter.onnx     # the detector + scores.max(1) + topk over anchors + Gather by index
+    python tools/torch_export.py recognizer_gru /tmp/rec_gru.onnx      # text-recogniser shape: Conv2d + ReLU, columns as time steps, bidirectional
+    python tools/torch_export.py recognizer_lstm /tmp/rec_lstm.onnx    #   GRU / LSTM, Linear head (dynamic batch and width)
 """
 from __future__ import annotations
 
@@ -396,6 +398,44 @@ def yolo_filter_onnx(model=None, image: int = 64, batch: int = 2) -> bytes:
     return export_bytes(model, (torch.zeros(batch, 3, image, image),), ["x"], ["y", "conf", "top", "idx", "boxes", "classes"])
 
 
+def recognizer_module(kind: str = "gru", bidirectional: bool = True, layers: int = 1, seed: int = 0, height: int = 8, channels: int = 4, hidden: int = 20,
+                      classes: int = 11, batch_first: bool = False):
+    """A text recogniser in the shape of `ocrs`: Conv2d + ReLU over a [b, 1, height, w] line image, every image column a time step
+    (`permute(3, 0, 1, 2).flatten(2)` -> [w, b, channels * height]), `layers` uni- or bidirectional nn.GRU / nn.LSTM layers, a Linear head over
+    the classes -- [w, b, classes], or [b, w, classes] with `batch_first` (a trailing permute: what the model ABI's dim-0 batch slices need).  The exporter writes one GRU / LSTM node per layer (linear_before_reset=1, empty sequence_lens, initial states from Expand /
+    ConstantOfShape) between Transpose / Reshape / Shape arithmetic."""
+    import torch
+    from torch import nn
+    torch.manual_seed(seed)
+    rnn_cls = {"gru": nn.GRU, "lstm": nn.LSTM}[kind]
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.conv = nn.Conv2d(1, channels, 3, padding=1)
+            self.rnn = rnn_cls(channels * height, hidden, num_layers=layers, bidirectional=bidirectional)
+            self.head = nn.Linear(hidden * (2 if bidirectional else 1), classes)
+
+        def forward(self, x):
+            f = torch.relu(self.conv(x)).permute(3, 0, 1, 2).flatten(2)
+            y, _ = self.rnn(f)
+            y = self.head(y)
+            return y.permute(1, 0, 2) if batch_first else y
+
+    net = Net().eval()
+    net.batch_first = batch_first  # (recognizer_onnx names the dynamic output axes by it)
+    return net
+
+
+def recognizer_onnx(model=None, kind: str = "gru", bidirectional: bool = True, layers: int = 1, seed: int = 0, batch: int = 2, width: int = 12,
+                    height: int = 8, dynamic: bool = True) -> bytes:
+    import torch
+    model = model if model is not None else recognizer_module(kind, bidirectional, layers, seed, height=height)
+    y_axes = {0: "batch", 1: "width"} if getattr(model, "batch_first", False) else {0: "width", 1: "batch"}
+    axes = {"x": {0: "batch", 3: "width"}, "y": y_axes} if dynamic else None
+    return export_bytes(model, (torch.zeros(batch, 1, height, width),), ["x"], ["y"], axes)
+
+
 if __name__ == "__main__":
     kind, path = sys.argv[1], sys.argv[2]
     if kind == "resnet50":
@@ -415,6 +455,8 @@ if __name__ == "__main__":
         data = segment_argmax_onnx()
     elif kind == "yolo_filter":
         data = yolo_filter_onnx()
+    elif kind in ("recognizer_gru", "recognizer_lstm"):
+        data = recognizer_onnx(kind=kind.split("_")[1])
     else:
         data = bert_onnx(bert_module())
     open(path, "wb").write(data)
