@@ -1,6 +1,7 @@
-// Shared pieces of the f32 GEMM / implicit-GEMM translation units (gemm_f32.hip: the 4-wave tile kernels and every host-side launch plan;
-// gemm_f32_wave.hip: the one-wave-per-tile kernel family): kernel-argument block, buffer-load helpers, the reference's fold / epilogue
-// (rten-gemm/src/lib.rs:1008-1013,1221-1255; simd_generic.rs:378-414), the exact split-K last-arrival fold and the -DRTEN_TRACE stamps.
+// Shared pieces of the f32 GEMM / implicit-GEMM translation units (gemm_f32.hip: every host-side launch plan and the entry points;
+// gemm_f32_<family>.hip: one kernel family each behind one rten_launch_gemm_f32_<family> function, declared in internal.h):
+// kernel-argument block, buffer-load helpers, the reference's fold / epilogue (rten-gemm/src/lib.rs:1008-1013,1221-1255;
+// simd_generic.rs:378-414), the exact split-K last-arrival fold, the -DRTEN_TRACE stamps and the launchers' tile switch.
 // Everything here has internal linkage (anonymous namespace): each translation unit compiles its own copy.
 #pragma once
 #include "internal.h"
@@ -20,6 +21,8 @@ namespace {
 constexpr int BK = 16;             // k-tile depth
 constexpr int KC_TILES = 256 / BK; // reference depth block (kc = 256 for f32)
 constexpr int NTHREADS = 256;
+constexpr int MAX_NSTAGE = 6;      // deepest LDS ring of any kernel: the im2col table is padded for its look-ahead
+constexpr int LBK = 32;            // k-tile depth of the lean kernel (its plan takes K % LBK == 0 only)
 // Ablation switches (RTEN_HIP_DEBUG bits) exist only in -DRTEN_ABLATE tuning builds: a runtime test inside the K loop
 // costs the production kernels accumulator copies and exec-mask branches.
 #ifdef RTEN_ABLATE
@@ -102,6 +105,89 @@ __device__ __forceinline__ f32x4 coherent_load4(__amdgpu_buffer_rsrc_t r, unsign
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 17));
 }
 
+
+// ---- prologue pieces the tile kernels share: pure functions of scalars and the argument block (the k-loops stay with each kernel).
+
+// XCD-chunked workgroup -> tile map.  Workgroup ids are dealt round-robin to the eight XCDs (each with a private L2); XCD x = id & 7 gets the
+// x-th contiguous chunk of nt / 8 (+ 1) tiles and walks it in id order, so the tiles an XCD works on at one time share a B panel.
+__device__ __forceinline__ int xcd_chunked_tile(int id, int nt) {
+    const int xcd = id & 7, q = nt >> 3, r = nt & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
+}
+
+// Batch slice z of the operands (z -> (z / batch_inner, z % batch_inner) for a two-level batch) and a buffer descriptor over one.
+// Kernarg / blockIdx derived only: the descriptors stay in SGPRs, no waterfall loops.
+struct BatchSlice { const float *A, *B; long long c_zoff; };
+__device__ __forceinline__ BatchSlice batch_slice(const GemmArgs &p, int z) {
+    int zo = z, zi = 0;
+    if (p.batch_inner > 1) { zo = z / p.batch_inner; zi = z - zo * p.batch_inner; }
+    return {p.A + (long long)zo * p.a_bs + (long long)zi * p.a_bsi, p.B + (long long)zo * p.b_bs + (long long)zi * p.b_bsi,
+            (long long)zo * p.c_bs + (long long)zi * p.c_bsi};
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t slice_rsrc(const float *base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)bytes, 0x00020000);
+}
+
+// Loop-invariant LDS-DMA source offsets of a tile's A rows [m0, m0 + BM) and dense B columns [n0, n0 + BN), k-tile 0: wave w issues the
+// dwordx4 instructions q = w * N + j, instruction q covers the flat tile range [q * 256, q * 256 + 256) floats.  OOB = lanes outside
+// the operand (the hardware range check returns 0).  A_K4: one instruction is 64 rows x one k-quad, a_kq = its first local k (k-tail test).
+template <int BM, int NA> // k-major A (A_M4)
+__device__ __forceinline__ void dma_a_offsets_m4(const GemmArgs &p, int m0, int wave, int lane, unsigned (&a_voff)[NA]) {
+#pragma unroll
+    for (int j = 0; j < NA; j++) {
+        const int f = (wave * NA + j) * 256 + lane * 4;
+        const int k = f / BM, m = m0 + f % BM;
+        // rows >= K lie past the end of the [K][M4] buffer (hardware range check); columns >= M4 must not wrap
+        a_voff[j] = m < (int)p.a_cs ? (unsigned)(((long long)k * p.a_cs + m) * 4) : OOB;
+    }
+}
+template <int BM, int AL, int NA> // A_M4 or A_K4
+__device__ __forceinline__ void dma_a_offsets(const GemmArgs &p, int m0, int wave, int lane, unsigned (&a_voff)[NA], int (&a_kq)[NA]) {
+    if constexpr (AL == A_M4) {
+        dma_a_offsets_m4<BM, NA>(p, m0, wave, lane, a_voff);
+    } else {
+#pragma unroll
+        for (int j = 0; j < NA; j++) {
+            const int q = wave * NA + j, kq = q / (BM / 64), m = m0 + (q % (BM / 64)) * 64 + lane;
+            a_kq[j] = kq * 4;
+            a_voff[j] = m < p.M ? (unsigned)(((long long)m * p.a_rs + kq * 4) * 4) : OOB;
+        }
+    }
+}
+template <int BN, int NBV>
+__device__ __forceinline__ void dma_b_offsets(const GemmArgs &p, int n0, int wave, int lane, unsigned (&b_voff)[NBV], int (&b_krow)[NBV]) {
+#pragma unroll
+    for (int j = 0; j < NBV; j++) {
+        const int f = (wave * NBV + j) * 256 + lane * 4;
+        const int k = f / BN, n = n0 + f % BN;
+        const int nn = n < p.N ? n : 0;
+        const int nb = nn / p.Pn, np = nn - nb * p.Pn;
+        b_krow[j] = k;
+        b_voff[j] = n < p.N ? (unsigned)(((long long)k * p.b_rs + (long long)nb * p.b_ns + np) * 4) : OOB;
+    }
+}
+
+// im2col set-up of output column n (a gather instruction covers one k row x 64 columns: a lane sees one column per 64 of the tile):
+// iy0 / ix0 = input row / column of tap (0, 0) (iy0 far out of range for n >= N), pix = element offset of that tap in the batch slice.
+// TAPS: inv = the column's padding mask -- bit t set = tap t falls outside the image; bit 31 always set (k-tail rows).
+template <bool TAPS>
+__device__ __forceinline__ void im2col_column(const GemmArgs &p, int n, int &iy0, int &ix0, int &pix, unsigned &inv) {
+    const bool ok = n < p.N;
+    const int nn = ok ? n : 0;
+    const int nb = nn / p.Pn, np = nn - nb * p.Pn;
+    const int oy = np / p.OW, ox = np - oy * p.OW;
+    iy0 = ok ? oy * p.sy - p.pt : -0x40000000;
+    ix0 = ox * p.sx - p.pl;
+    pix = (int)((long long)nb * p.b_ns) + (oy * p.sy - p.pt) * p.W + ix0;
+    if constexpr (TAPS) {
+        unsigned colbad = 0; // bit kx set: column tap kx falls outside the image
+        for (int kx = 0; kx < p.KW; kx++) colbad |= ((unsigned)(ix0 + kx * p.dx) >= (unsigned)p.W ? 1u : 0u) << kx;
+        const unsigned allbad = (1u << p.KW) - 1u;
+        unsigned m = 0x80000000u;
+        for (int ky = 0; ky < p.KH; ky++) m |= ((unsigned)(iy0 + ky * p.dy) >= (unsigned)p.H ? allbad : colbad) << (ky * p.KW);
+        inv = m;
+    }
+}
 
 // ---- fold / epilogue helpers shared by all kernels.  Every uniform condition (alpha/beta form, bias kind,
 // residual, activation) is tested ONCE per 32x32 accumulator block around straight-line code, and the block's 16
@@ -234,6 +320,130 @@ __device__ __forceinline__ void store_out(const GemmArgs &p, f32x16 (&val)[TM][T
 }
 
 
+// ---- the same fold / epilogue for kernels whose accumulators are v_mfma_f32_16x16x4_f32 blocks (the 16x16x4, persistent and small-M kernels).
+// Accumulator element r of block (i, j): row mb + 16 i + r, column nb0 + 16 j.
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+
+template <int TM2, int TN2>
+__device__ __forceinline__ void fold_first16(const GemmArgs &p, int z, f32x4v (&acc)[TM2][TN2], f32x4v (&out)[TM2][TN2], int mb, int nb0, long long c_zoff) {
+    const __amdgpu_buffer_rsrc_t rsBias = __builtin_amdgcn_make_buffer_rsrc((void *)((p.bias ? p.bias : p.C) + (long long)z * p.bias_bs), 0, 0x7ffffffc, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void *)(p.C + c_zoff), 0, 0x7ffffffc, 0x00020000);
+#pragma unroll
+    for (int i = 0; i < TM2; i++) {
+        const int mrow = mb + i * 16;
+        float brow[4];
+        if (p.bias_kind == RTEN_HIP_BIAS_PER_ROW) {
+#pragma unroll
+            for (int r = 0; r < 4; r++) brow[r] = buf_load1(rsBias, mrow + r < p.M ? (unsigned)(mrow + r) << 2 : OOB, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < TN2; j++) {
+            const int n = nb0 + j * 16;
+            const bool cok = n < p.N;
+            f32x4v v = acc[i][j];
+            if (p.beta == 0.f) {
+                if (p.alpha != 1.f) {
+#pragma unroll
+                    for (int r = 0; r < 4; r++) v[r] = v[r] * p.alpha;
+                }
+            } else {
+                const int nn = cok ? n : 0;
+                const int nb = nn / p.Pn, np = nn - nb * p.Pn;
+                const unsigned col = (unsigned)((long long)nb * p.c_ns + np);
+                float cin[4];
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int m = mrow + r;
+                    cin[r] = buf_load1(rsC, (m < p.M && cok) ? (col + (unsigned)m * (unsigned)p.c_rs) << 2 : OOB, 0);
+                }
+                if (p.beta == 1.f && p.alpha == 1.f) {
+#pragma unroll
+                    for (int r = 0; r < 4; r++) v[r] = cin[r] + v[r];
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; r++) v[r] = vm::fma(v[r], p.alpha, cin[r] * p.beta);
+                }
+            }
+            if (p.bias_kind == RTEN_HIP_BIAS_PER_ROW) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) v[r] = v[r] + brow[r];
+            } else if (p.bias_kind == RTEN_HIP_BIAS_PER_COL) {
+                const float bcol = buf_load1(rsBias, cok ? (unsigned)n << 2 : OOB, 0);
+#pragma unroll
+                for (int r = 0; r < 4; r++) v[r] = v[r] + bcol;
+            }
+            out[i][j] = v;
+        }
+    }
+}
+
+template <int TM2, int TN2>
+__device__ __forceinline__ void fold_next16(const GemmArgs &p, f32x4v (&acc)[TM2][TN2], f32x4v (&tot)[TM2][TN2]) {
+#pragma unroll
+    for (int i = 0; i < TM2; i++)
+#pragma unroll
+        for (int j = 0; j < TN2; j++) {
+            if (p.alpha == 1.f) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) tot[i][j][r] = tot[i][j][r] + acc[i][j][r];
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; r++) tot[i][j][r] = vm::fma(acc[i][j][r], p.alpha, tot[i][j][r]);
+            }
+        }
+}
+
+template <int TM2, int TN2>
+__device__ __forceinline__ void store_out16(const GemmArgs &p, f32x4v (&val)[TM2][TN2], int mb, int nb0, long long c_zoff) {
+    const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void *)(p.C + c_zoff), 0, 0x7ffffffc, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void *)((p.res ? p.res : p.C) + c_zoff), 0, 0x7ffffffc, 0x00020000);
+    const bool has_res = p.res != nullptr;
+    const unsigned rs4 = (unsigned)p.c_rs << 2;
+#pragma unroll
+    for (int j = 0; j < TN2; j++) {
+        const int n = nb0 + j * 16;
+        const bool cok = n < p.N;
+        const int nn = cok ? n : 0;
+        const int nb = nn / p.Pn, np = nn - nb * p.Pn;
+        const unsigned col = (unsigned)((long long)nb * p.c_ns + np);
+        unsigned voff[TM2][4];
+        float rr[TM2][4];
+#pragma unroll
+        for (int i = 0; i < TM2; i++) {
+            const int mrow = mb + i * 16;
+            const unsigned base = cok ? (col + (unsigned)mrow * (unsigned)p.c_rs) << 2 : OOB;
+#pragma unroll
+            for (int r = 0; r < 4; r++) voff[i][r] = mrow + r < p.M ? base : OOB;
+            if (has_res) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) rr[i][r] = buf_load1(rsR, voff[i][r], (unsigned)r * rs4);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < TM2; i++) {
+            f32x4v v = val[i][j];
+            if (has_res) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) v[r] = v[r] + rr[i][r];
+            }
+            if (p.act == RTEN_HIP_ACT_RELU) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) v[r] = vm::relu(v[r]);
+            } else if (p.act == RTEN_HIP_ACT_GELU) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) v[r] = vm::gelu(v[r]);
+            } else if (p.act != RTEN_HIP_ACT_NONE) {
+                vm::activation_n<4>(p.act, v, p.act_a, p.act_b);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float x = v[r];
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, x), rsC, (int)voff[i][r], (int)((unsigned)r * rs4), 0);
+            }
+        }
+    }
+}
+
 // Split-K, last arrival folds: a producer workgroup that has parked its depth blocks in the slab announces itself on the
 // tile's counter; the workgroup that finds all the others already there replays the unsplit fold over the slots in
 // depth-block order (exactly what igemm_f32_fixup_kernel does: first block beta * C + bias, later blocks separate adds, then
@@ -291,6 +501,37 @@ __device__ __forceinline__ void split_finish(const GemmArgs &p, int z, int tile,
     if (threadIdx.x == 0) p.split_counters[(long long)z * p.split_ntail + ti] = 0u;
 }
 
+// Split-K producer side of the slab: park the raw accumulators of one depth block as slot `slot` of the tile -- the image split_finish and the
+// fixup kernel read back: [wave wq][block i * TN + j][quad][lane] float4.
+template <int BM, int BN, int TM, int TN>
+__device__ __forceinline__ void split_park(const GemmArgs &p, int z, int tile, int wq, int lane, f32x16 (&v)[TM][TN], int slot) {
+    int loff = wq * (TM * TN * 16 * 64) + lane * 4;
+    asm volatile("" : "+v"(loff)); // keep the address math at the use (not hoisted across the K loop)
+    float *base = p.slab + (((long long)z * p.split_ntail + (tile - p.split_t1)) * p.split_slots + slot) * (long long)(BM * BN) + loff;
+    if (p.split_counters) { // folded in this launch, possibly on another XCD: write through (see coherent_store4)
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(base - loff), 0, BM * BN * 4, 0x00020000);
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+#pragma unroll
+            for (int j = 0; j < TN; j++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    f32x4 o = {v[i][j][4 * q], v[i][j][4 * q + 1], v[i][j][4 * q + 2], v[i][j][4 * q + 3]};
+                    coherent_store4(rs, (unsigned)(loff + ((i * TN + j) * 4 + q) * 256) * 4u, o);
+                }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < TM; i++)
+#pragma unroll
+        for (int j = 0; j < TN; j++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                f32x4 o = {v[i][j][4 * q], v[i][j][4 * q + 1], v[i][j][4 * q + 2], v[i][j][4 * q + 3]};
+                *(f32x4 *)(base + ((i * TN + j) * 4 + q) * 256) = o;
+            }
+}
+
 #ifdef RTEN_TRACE
 __device__ __forceinline__ void trace_write(const GemmArgs &p, unsigned kid, int tile, int grp, unsigned trips, const unsigned long long (&t)[6], unsigned long long cycles, unsigned long long ticks) {
     if (threadIdx.x != 0 || p.trace_buf == nullptr) return;
@@ -323,9 +564,29 @@ inline void trace_assign(GemmArgs &a, unsigned workgroups) {
     g_trace_host.next += workgroups;
 }
 #define TRACE_ASSIGN(a, n) trace_assign(a, n)
+#define TRACED_ARGS(a, args, n) GemmArgs a = *static_cast<const GemmArgs *>(args); trace_assign(a, n) // a launcher's own copy carries the slots
 #else
 #define TRACE_ASSIGN(a, n)
+#define TRACED_ARGS(a, args, n) const GemmArgs &a = *static_cast<const GemmArgs *>(args)
 #endif
+
+inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; } // host: may a 16-byte loader start here
+
+// host, the launchers (their contracts are stated once, in internal.h): a (tile shape, operand layout) the planner never sends to a family,
+// and the run-time tile shape as a type T for f (T::bm, T::bn); each launcher then switches over the layouts its family has kernels for.
+inline int32_t not_covered(rten_hip_ctx *ctx, const char *family) {
+    return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "internal: %s called with a tile shape / operand layout it does not cover", family);
+}
+template <int BM, int BN> struct Tile { static constexpr int bm = BM, bn = BN; };
+template <class F>
+int32_t switch_tile(rten_hip_ctx *ctx, const char *family, int bm, int bn, F &&f) {
+    if (bm == 128 && bn == 128) return f(Tile<128, 128>());
+    if (bm == 128 && bn == 64) return f(Tile<128, 64>());
+    if (bm == 64 && bn == 128) return f(Tile<64, 128>());
+    if (bm == 64 && bn == 64) return f(Tile<64, 64>());
+    return not_covered(ctx, family);
+}
+constexpr int layouts(int al, int bl) { return al * 8 + bl; } // one switch key for an (ALoad, BLoad) pair
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {

@@ -89,12 +89,7 @@ __global__ __launch_bounds__(256, ((K1 + (DS ? 64 : 0)) * 64 + 64 * M2 + 64 * BN
     const int l31 = lane & 31, half = lane >> 5;
     const int wq = t >> 6, wm = wq >> 1, wn = wq & 1;
 
-    int tile;
-    {   // workgroups of one XCD take a contiguous range of column tiles (as the GEMM kernels do)
-        const int id = blockIdx.x, nt = (int)gridDim.x;
-        const int xcd = id & 7, q = nt >> 3, r = nt & 7;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-    }
+    const int tile = xcd_chunked_tile(blockIdx.x, (int)gridDim.x); // workgroups of one XCD take a contiguous range of column tiles (as the GEMM kernels do)
     const int n0 = tile * BN;
     const int nch = p.M1 >> 6;
 

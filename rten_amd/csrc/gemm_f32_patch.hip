@@ -1,7 +1,7 @@
 // 3x3 convolutions (stride 1, padding 1, dilation 1) whose B operand is staged as IMAGE PATCHES: the "patch" family of the f32 implicit-GEMM
 // kernels (gfx950).
 //
-// Replaces the same reference code as gemm_f32.hip (rten-gemm/src/lib.rs:794-1093, kernels/simd_generic.rs:285-414, the virtual im2col of
+// Replaces the same reference code as the other gemm_f32_*.hip families (see gemm_f32.hip: rten-gemm/src/lib.rs:794-1093, kernels/simd_generic.rs:285-414, the virtual im2col of
 // rten-gemm/src/im2col.rs:56-212 and conv_impl, src/ops/conv.rs:124-365) for A = prepacked k-major weights [K][M], B = the im2col matrix of a
 // 3x3 / stride 1 / padding 1 convolution.
 //
@@ -58,9 +58,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void igemm_f32_patch_kernel(const Gemm
 
     int tile, grp = -1;
     {
-        const int id = blockIdx.x, nt = (int)gridDim.x;
-        const int xcd = id & 7, q = nt >> 3, r = nt & 7; // XCD-chunked: each XCD (private L2) walks a contiguous run of tiles sharing a B panel
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
+        tile = xcd_chunked_tile(blockIdx.x, (int)gridDim.x);
         if constexpr (SPLIT) {
             const int rr = tile;
             if (p.order & 2) { grp = rr / p.split_ntail; tile = p.split_t1 + rr - grp * p.split_ntail; }
@@ -70,13 +68,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void igemm_f32_patch_kernel(const Gemm
     const int bm = (p.order & 1) ? tile / p.tiles_n : tile % p.tiles_m, bn = (p.order & 1) ? tile % p.tiles_n : tile / p.tiles_m;
     const int m0 = bm * 64, n0 = bn * 64;
 
-    int zo = z, zi = 0;
-    if (p.batch_inner > 1) { zo = z / p.batch_inner; zi = z - zo * p.batch_inner; }
-    const float *Ab = p.A + (long long)zo * p.a_bs + (long long)zi * p.a_bsi;
-    const float *Bb = p.B + (long long)zo * p.b_bs + (long long)zi * p.b_bsi;
-    const long long c_zoff = (long long)zo * p.c_bs + (long long)zi * p.c_bsi;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void *)Ab, 0, (int)p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void *)Bb, 0, (int)p.b_bytes, 0x00020000);
+    const BatchSlice zs = batch_slice(p, z);
+    const long long c_zoff = zs.c_zoff;
+    const __amdgpu_buffer_rsrc_t rsA = slice_rsrc(zs.A, p.a_bytes), rsB = slice_rsrc(zs.B, p.b_bytes);
 
     // ---- A: instruction `wave` of round 0 covers rows 4 wave .. 4 wave + 3 of the [18][64] tile; round 1 (rows 16, 17) is wave 0's
     unsigned a_voff0, a_voff1;
@@ -147,26 +141,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void igemm_f32_patch_kernel(const Gemm
     zero_acc();
     const int mb = m0 + wm0 + 4 * half, nb0 = n0 + wn0 + l31;
 
-    // raw accumulator image of this tile in the split-K slab: [wave][quad][lane] float4 (the 4-wave kernels' image: split_finish<64, 64, 1, 1>)
-    [[maybe_unused]] auto store_raw = [&](int slot) {
-        int loff = wave * 1024 + lane * 4;
-        asm volatile("" : "+v"(loff));
-        float *base = p.slab + (((long long)z * p.split_ntail + (tile - p.split_t1)) * p.split_slots + slot) * (long long)(64 * 64);
-        if (p.split_counters) { // folded in this launch, possibly on another XCD: write through (see coherent_store4)
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, 64 * 64 * 4, 0x00020000);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                f32x4 o = {acc[0][0][4 * q], acc[0][0][4 * q + 1], acc[0][0][4 * q + 2], acc[0][0][4 * q + 3]};
-                coherent_store4(rs, (unsigned)(loff + q * 256) * 4u, o);
-            }
-            return;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            f32x4 o = {acc[0][0][4 * q], acc[0][0][4 * q + 1], acc[0][0][4 * q + 2], acc[0][0][4 * q + 3]};
-            *(f32x4 *)(base + loff + q * 256) = o;
-        }
-    };
+    [[maybe_unused]] auto store_raw = [&](int slot) { split_park<64, 64, 1, 1>(p, z, tile, wave, lane, acc, slot); }; // (read back by split_finish<64, 64, 1, 1>)
     // the reference starts a new depth block at k = 256 j: fold (or park) the block that ends there
     [[maybe_unused]] auto block_boundary = [&](int k) {
         if constexpr (SPLIT) {
@@ -274,9 +249,9 @@ int32_t launch_patch(rten_hip_ctx *ctx, const GemmArgs &a, const PatchGeom &g, d
 
 // Does the patch family cover this launch?  3x3 taps, stride 1, padding 1 (top / left; the output is as large as the input), dilation 1, K a whole
 // number of channel pairs, and every tile's window of the virtual image stack fits a patch slot.  On success `*geom_out` (opaque to the caller) holds
-// what the launch needs; called by the launch plans of gemm_f32.hip (launch_cfg<64, 64, A_M4, B_IM2COL*>) with that translation unit's GemmArgs.
+// what the launch needs; called by the launch plans of gemm_f32.hip (launch_cfg with 64x64 tiles, k-major A and an im2col B) with that translation unit's GemmArgs.
 int32_t rten_launch_gemm_f32_patch(rten_hip_ctx *ctx, const void *args, unsigned grid_x, unsigned grid_z, int mode) {
-    GemmArgs a = *static_cast<const GemmArgs *>(args);
+    TRACED_ARGS(a, args, grid_x * grid_z);
     if (!(a.KH == 3 && a.KW == 3 && a.sy == 1 && a.sx == 1 && a.dy == 1 && a.dx == 1 && a.pt == 1 && a.pl == 1 && a.OW == a.W && a.Pn == a.H * a.W && a.K % PK == 0 &&
           a.K >= PK && a.N > 0 && a.b_ns > 0))
         return RTEN_HIP_ERR_UNSUPPORTED;
@@ -304,7 +279,6 @@ int32_t rten_launch_gemm_f32_patch(rten_hip_ctx *ctx, const void *args, unsigned
     }
     const int np = (int)((ext + 64 * G - 1) / (64 * G));
     const dim3 grid(grid_x, grid_z);
-    TRACE_ASSIGN(a, grid_x * grid_z);
     if (x4) {
         if (np <= 1) return launch_patch<4, 1>(ctx, a, g, grid, mode);
         if (np == 2) return launch_patch<4, 2>(ctx, a, g, grid, mode);

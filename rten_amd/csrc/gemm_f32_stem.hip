@@ -47,12 +47,7 @@ __global__ __launch_bounds__(256, 2) void conv_small_c_f32_kernel(const StemArgs
     const int l31 = lane & 31, half = lane >> 5;
     const int wq = t >> 6;
 
-    int tile;
-    {   // workgroups of one XCD take a contiguous range of tiles
-        const int id = blockIdx.x, nt = (int)gridDim.x;
-        const int xcd = id & 7, q = nt >> 3, r = nt & 7;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-    }
+    const int tile = xcd_chunked_tile(blockIdx.x, (int)gridDim.x); // workgroups of one XCD take a contiguous range of tiles
     const int per_img = p.tiles_x * p.tiles_y;
     const int img = tile / per_img, tr = tile - img * per_img;
     const int ty = tr / p.tiles_x, tx = tr - ty * p.tiles_x;

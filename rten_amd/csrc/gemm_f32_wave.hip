@@ -1,6 +1,6 @@
 // One wave = one workgroup = one 64x64 output tile: the "wave tile" family of the f32 implicit-GEMM kernels (gfx950).
 //
-// Replaces the same reference code as gemm_f32.hip (rten-gemm/src/lib.rs:794-1093, kernels/simd_generic.rs:285-414, the virtual im2col of
+// Replaces the same reference code as the other gemm_f32_*.hip families (see gemm_f32.hip: rten-gemm/src/lib.rs:794-1093, kernels/simd_generic.rs:285-414, the virtual im2col of
 // rten-gemm/src/im2col.rs:56-212 and conv_impl, src/ops/conv.rs:124-365) for the convolution operand layouts: A = prepacked k-major weights
 // [K][M], B = dense two-level activations (1x1 / stride 1) or the im2col gather.
 //
@@ -14,7 +14,7 @@
 //     synchronisation) and halves the fragment traffic (2 + 2 ds_read_b32 feed 4 MFMAs).  Probe: 142 TF/s on a dense k-loop at two waves per
 //     SIMD (0.93 of the pipe) against 130 for the 4-wave form.
 //
-// Numerics: exactly those of gemm_f32.hip (same fold_first / fold_next / store_out, same depth-block boundaries, same exact split-K with the
+// Numerics: exactly those of the 4-wave families (same fold_first / fold_next / store_out, same depth-block boundaries, same exact split-K with the
 // last-arrival fold) -- bit-identical to the oracle; the variant sweeps in tests/ run this family next to the others.
 #include "gemm_f32_common.h"
 
@@ -54,9 +54,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TMW == 2 ? 2
 
     int tile, grp = -1; // grp >= 0: this wave computes one K group of a split tile
     {
-        const int id = blockIdx.x, nt = (int)gridDim.x;
-        const int xcd = id & 7, q = nt >> 3, r = nt & 7; // XCD-chunked: each XCD (private L2) walks a contiguous run of tiles sharing a B panel
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
+        tile = xcd_chunked_tile(blockIdx.x, (int)gridDim.x); // each XCD (private L2) walks a contiguous run of tiles sharing a B panel
         if constexpr (SPLIT) {
             const int rr = tile;
             if (p.order & 2) { grp = rr / p.split_ntail; tile = p.split_t1 + rr - grp * p.split_ntail; }
@@ -66,24 +64,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TMW == 2 ? 2
     const int bm = (p.order & 1) ? tile / p.tiles_n : tile % p.tiles_m, bn = (p.order & 1) ? tile % p.tiles_n : tile / p.tiles_m;
     const int m0 = bm * BMW, n0 = bn * BNW;
 
-    int zo = z, zi = 0;
-    if (p.batch_inner > 1) { zo = z / p.batch_inner; zi = z - zo * p.batch_inner; }
-    const float *Ab = p.A + (long long)zo * p.a_bs + (long long)zi * p.a_bsi;
-    const float *Bb = p.B + (long long)zo * p.b_bs + (long long)zi * p.b_bsi;
-    const long long c_zoff = (long long)zo * p.c_bs + (long long)zi * p.c_bsi;
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void *)Ab, 0, (int)p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void *)Bb, 0, (int)p.b_bytes, 0x00020000);
+    const BatchSlice zs = batch_slice(p, z);
+    const long long c_zoff = zs.c_zoff;
+    const __amdgpu_buffer_rsrc_t rsA = slice_rsrc(zs.A, p.a_bytes), rsB = slice_rsrc(zs.B, p.b_bytes);
     const int nk = (p.K + BKW - 1) / BKW;
 
     // ---- loop-invariant DMA source offsets: instruction j covers the flat tile range [j*256, j*256+256) floats (dwordx4: 4 k rows x 64)
     unsigned a_voff[NA];
-#pragma unroll
-    for (int j = 0; j < NA; j++) {
-        const int f = j * 256 + lane * 4;
-        const int k = f / BMW, m = m0 + f % BMW;
-        // rows >= K lie past the end of the [K][M4] buffer (hardware range check); columns >= M4 must not wrap
-        a_voff[j] = m < (int)p.a_cs ? (unsigned)(((long long)k * p.a_cs + m) * 4) : OOB;
-    }
+    dma_a_offsets_m4<BMW, NA>(p, m0, 0, lane, a_voff); // (one wave issues the whole tile)
     const unsigned a_kstep = (unsigned)(BKW * p.a_cs * 4);
 
     [[maybe_unused]] unsigned b_voff[BL == B_N4 ? NBV : 1];
@@ -92,33 +80,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TMW == 2 ? 2
     [[maybe_unused]] int im_iy0 = 0, im_ix0 = 0, im_pix = 0;
     [[maybe_unused]] unsigned im_inv = 0; // TAPS: bit t set = tap t of this lane's pixel is padding; bit 31 always set (k-tail rows)
     if constexpr (BL == B_N4) {
-#pragma unroll
-        for (int j = 0; j < NBV; j++) {
-            const int f = j * 256 + lane * 4;
-            const int k = f / BNW, n = n0 + f % BNW;
-            const int nn = n < p.N ? n : 0;
-            const int nb = nn / p.Pn, np = nn - nb * p.Pn;
-            b_krow[j] = k;
-            b_voff[j] = n < p.N ? (unsigned)(((long long)k * p.b_rs + (long long)nb * p.b_ns + np) * 4) : OOB;
-        }
+        dma_b_offsets<BNW, NBV>(p, n0, 0, lane, b_voff, b_krow);
         b_kstep = (unsigned)(BKW * p.b_rs * 4);
     } else {
-        const int n = n0 + lane; // a gather instruction covers one k row x 64 columns: a lane sees ONE column
-        const bool ok = n < p.N;
-        const int nn = ok ? n : 0;
-        const int nb = nn / p.Pn, np = nn - nb * p.Pn;
-        const int oy = np / p.OW, ox = np - oy * p.OW;
-        im_iy0 = ok ? oy * p.sy - p.pt : -0x40000000;
-        im_ix0 = ox * p.sx - p.pl;
-        im_pix = (int)((long long)nb * p.b_ns) + (oy * p.sy - p.pt) * p.W + im_ix0;
-        if constexpr (TAPS) {
-            unsigned colbad = 0; // bit kx set: column tap kx falls outside the image
-            for (int kx = 0; kx < p.KW; kx++) colbad |= ((unsigned)(im_ix0 + kx * p.dx) >= (unsigned)p.W ? 1u : 0u) << kx;
-            const unsigned allbad = (1u << p.KW) - 1u;
-            unsigned inv = 0x80000000u;
-            for (int ky = 0; ky < p.KH; ky++) inv |= ((unsigned)(im_iy0 + ky * p.dy) >= (unsigned)p.H ? allbad : colbad) << (ky * p.KW);
-            im_inv = inv;
-        }
+        im2col_column<TAPS>(p, n0 + lane, im_iy0, im_ix0, im_pix, im_inv); // a gather instruction covers one k row x 64 columns: a lane sees ONE column
     }
 
     // im2col LUT entries (scalar loads) for the tile whose DMA is issued NEXT: all BKW rows belong to this wave
@@ -213,34 +178,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TMW == 2 ? 2
         __builtin_amdgcn_iglp_opt(0);
     };
 
-    // raw accumulator image of this tile in the split-K slab: [i][j][quad][lane] float4 (= the 4-wave kernels' [wave][quad][lane] image)
-    [[maybe_unused]] auto store_raw = [&](f32x16 (&v)[TM][TN], int slot) {
-        int loff = lane * 4;
-        asm volatile("" : "+v"(loff)); // keep the address math at the use (not hoisted across the K loop)
-        float *base = p.slab + (((long long)z * p.split_ntail + (tile - p.split_t1)) * p.split_slots + slot) * (long long)(BMW * BNW) + loff;
-        if (p.split_counters) { // folded in this launch, possibly on another XCD: write through (see coherent_store4)
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(base - loff), 0, BMW * BNW * 4, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < TM; i++)
-#pragma unroll
-                for (int j = 0; j < TN; j++)
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        f32x4 o = {v[i][j][4 * q], v[i][j][4 * q + 1], v[i][j][4 * q + 2], v[i][j][4 * q + 3]};
-                        coherent_store4(rs, (unsigned)(loff + ((i * TN + j) * 4 + q) * 256) * 4u, o);
-                    }
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < TM; i++)
-#pragma unroll
-            for (int j = 0; j < TN; j++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    f32x4 o = {v[i][j][4 * q], v[i][j][4 * q + 1], v[i][j][4 * q + 2], v[i][j][4 * q + 3]};
-                    *(f32x4 *)(base + ((i * TN + j) * 4 + q) * 256) = o;
-                }
-    };
+    [[maybe_unused]] auto store_raw = [&](f32x16 (&v)[TM][TN], int slot) { split_park<BMW, BNW, TM, TN>(p, z, tile, 0, lane, v, slot); }; // (one wave: the 4-wave image with wq = 0)
 
     // ---- software pipeline: NST - 1 k-tiles in flight behind the one being multiplied.  No barrier anywhere: the ring is this wave's own,
     // a stage is refilled only after the MFMAs that read it have been issued (in order) and their fragments consumed.
@@ -338,11 +276,10 @@ int32_t launch_mode(rten_hip_ctx *ctx, const GemmArgs &a, dim3 grid, int mode, i
 
 } // namespace
 
-// Called by the launch plans of gemm_f32.hip (launch_cfg<64, 64, A_M4, BL>): `args` is that translation unit's GemmArgs (same header, same layout).
+// Called by the launch plans of gemm_f32.hip (launch_cfg with 64x64 tiles and k-major A): `args` is that translation unit's GemmArgs (same header, same layout).
 int32_t rten_launch_gemm_f32_wave(rten_hip_ctx *ctx, const void *args, unsigned grid_x, unsigned grid_z, int bl, int mode, int flavour) {
-    GemmArgs a = *static_cast<const GemmArgs *>(args);
+    TRACED_ARGS(a, args, grid_x * grid_z);
     const dim3 grid(grid_x, grid_z);
-    TRACE_ASSIGN(a, grid_x * grid_z);
     switch (bl) {
     case B_N4: return launch_mode<B_N4>(ctx, a, grid, mode, flavour);
     case B_IM2COL_TAPS: return launch_mode<B_IM2COL_TAPS>(ctx, a, grid, mode, flavour);

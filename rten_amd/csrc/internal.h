@@ -97,7 +97,31 @@ int32_t rten_gemv_f32(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const floa
 // gemm_f32.hip: rten_hip_gemm_f32 without the gemv dispatch (operators whose reference form is not a gemm_impl call on unpacked operands)
 int32_t rten_gemm_f32_blocked(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b, const float *bias, float *c);
 void *rten_aux_scratch(rten_hip_ctx *ctx, size_t bytes);
-// gemm_f32_wave.hip: one launch of the wave-tile kernels; `args` = the caller's GemmArgs (gemm_f32_common.h)
+// The f32 GEMM kernel families, one translation unit each (gemm_f32_<family>.hip), launched by the plans of gemm_f32.hip.  `args` = the caller's
+// GemmArgs (gemm_f32_common.h); bm x bn = tile shape, al / bl = operand layouts (ALoad / BLoad), mode = 0 one depth block, 1 several, 2 split-K
+// producer; flops / bytes = the launch's share of the call for the profiler.  Each launcher names, brackets (ProfScope) and checks its launch.
+int32_t rten_launch_gemm_f32_reg(rten_hip_ctx *ctx, const void *args, unsigned grid_x, unsigned grid_z, int bm, int bn, int al, int bl, int mode,
+                                 double flops, double bytes);
+// mode 3 = whole tiles + split-K producers in one launch; nst = LDS stages (2: 64x64 tiles only, 3, 4); mfk = fragments-first issue (three stages)
+int32_t rten_launch_gemm_f32_dma(rten_hip_ctx *ctx, const void *args, unsigned grid_x, unsigned grid_z, int bm, int bn, int al, int bl, int mode, int nst,
+                                 int mfk, size_t dyn_lds, double flops, double bytes);
+// the ordered fold of a split-K launch whose producers did not fold (no arrival counters): one wave per tile quadrant
+int32_t rten_launch_gemm_f32_fixup(rten_hip_ctx *ctx, const void *args, unsigned grid_x, unsigned grid_z, int bm, int bn, double bytes);
+int32_t rten_launch_gemm_f32_dma16(rten_hip_ctx *ctx, const void *args, unsigned grid_x, unsigned grid_z, int bm, int bn, int al, int bl, int mode,
+                                   double flops, double bytes);
+// form: 0 = 32x32x2 MFMAs, 1 = fragments-first issue, 2 = 16x16x4 MFMAs; dyn_lds = untouched dynamic LDS that fixes the workgroups per compute unit
+int32_t rten_launch_gemm_f32_pers(rten_hip_ctx *ctx, const void *args, unsigned grid_x, unsigned grid_z, int bm, int bn, int al, int bl, int form,
+                                  int dyn_lds, double flops, double bytes);
+// 64x64 tiles, prepacked weights; bl = B_N4 or B_IM2COL_TAPS; nst = LDS stages (3, 4, 5); dyn_lds as for the persistent family
+int32_t rten_launch_gemm_f32_lean(rten_hip_ctx *ctx, const void *args, unsigned grid_x, int bl, int nst, int dyn_lds, double flops, double bytes);
+// k-major A only; mode 0 / 1 (no split-K form), and a mode 1 launch takes activations up to Gelu only: the planner sends the others to the three-stage LDS-DMA kernel
+int32_t rten_launch_gemm_f32_ws(rten_hip_ctx *ctx, const void *args, unsigned grid_x, unsigned grid_z, int bm, int bn, int bl, int mode, double flops,
+                                double bytes);
+// `args` with n_lo and the 16-row tile count set; prepacked weights; multi = K > 256
+int32_t rten_launch_gemm_f32_thin(rten_hip_ctx *ctx, const void *args, unsigned grid_x, int bl, int multi, double flops, double bytes);
+// one batch, M <= 64 (`args` filled for the call `d`); RTEN_HIP_ERR_UNSUPPORTED when the call is not its shape
+int32_t rten_launch_gemm_f32_smallm(rten_hip_ctx *ctx, const void *args, const rten_hip_gemm_desc *d, const float *a, const float *b);
+// gemm_f32_wave.hip: one launch of the wave-tile kernels
 int32_t rten_launch_gemm_f32_wave(rten_hip_ctx *ctx, const void *args, unsigned grid_x, unsigned grid_z, int bl, int mode, int flavour);
 // gemm_f32_patch.hip: 3x3 / stride 1 / padding 1 convolutions with B staged as image patches; RTEN_HIP_ERR_UNSUPPORTED when the launch is not covered
 int32_t rten_launch_gemm_f32_patch(rten_hip_ctx *ctx, const void *args, unsigned grid_x, unsigned grid_z, int mode);

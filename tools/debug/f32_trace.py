@@ -1,7 +1,8 @@
-"""Wall-clock timeline of every workgroup of one ResNet-50 f32 step (batch 32), from a -DRTEN_TRACE build of gemm_f32.hip.
+"""Wall-clock timeline of every workgroup of one ResNet-50 f32 step (batch 32), from a -DRTEN_TRACE build of every gemm_f32*.hip
+(the flag changes the GemmArgs layout they share, so all of them are rebuilt with it).
 
-    cd rten_amd/csrc && hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -DRTEN_TRACE -c gemm_f32.hip -o /tmp/tr/gemm_f32_trace.o
-    cd .. && hipcc --offload-arch=gfx950 -shared -fPIC -o _ab/trace.so $(ls _build/*.o | grep -v gemm_f32.o) /tmp/tr/gemm_f32_trace.o
+    cd rten_amd/csrc && for f in gemm_f32*.hip; do hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -DRTEN_TRACE -c $f -o /tmp/tr/${f%.hip}.o & done; wait
+    cd .. && hipcc --offload-arch=gfx950 -shared -fPIC -o _ab/trace.so $(ls _build/*.o | grep -v /gemm_f32) /tmp/tr/gemm_f32*.o
     RTEN_HIP_LIBRARY=$PWD/rten_amd/_ab/trace.so python tools/debug/f32_trace.py [--chains 4] [--out gpurun_out/f32_trace]     (GPU box)
 
 Every workgroup of igemm_f32_dma_kernel appends {kernel id, compute unit, s_memrealtime at entry / prologue issued / first k-tile landed /
