@@ -424,6 +424,31 @@ int32_t rten_hip_add_layer_norm_f32(rten_hip_ctx *ctx, int64_t rows, int32_t col
 int32_t rten_hip_batch_norm_f32(rten_hip_ctx *ctx, int32_t n, int32_t c, int64_t inner, const float *x,
                                 const float *scale, const float *bias, const float *mean, const float *var,
                                 float epsilon, float *y);
+/* The same with an activation on the result: y = act(batch_norm(x)); act_kind / act_alpha / act_beta as for rten_hip_activation_f32 (every RTEN_HIP_ACT_* kind,
+ * any other is RTEN_HIP_ERR_INVALID_VALUE).  The activation sees the f32 value the plain form stores, so the result has the bits of BatchNormalization followed
+ * by the activation operator; RTEN_HIP_ACT_NONE is rten_hip_batch_norm_f32. */
+int32_t rten_hip_batch_norm_f32_act(rten_hip_ctx *ctx, int32_t n, int32_t c, int64_t inner, const float *x, const float *scale, const float *bias,
+                                    const float *mean, const float *var, float epsilon, int32_t act_kind, float act_alpha, float act_beta, float *y);
+
+/* ---- InstanceNormalization: src/ops/norm.rs:320-365 (normalize_each over the N*C slices, norm.rs:103-189) + rten-vecmath/src/normalize.rs:112-127 ----
+ * x, y [n][c][inner]; scale, bias [c].  Per slice r = b*c + ch: mean = Sum(row) / inner, var = SumSquareSub(row, mean) / inner (both in the reference's
+ * 16-lane fold_unroll<4> order, divisions in f32), s = scale[ch] / sqrtf(var + epsilon), y = act(fma(x - mean, s, bias[ch])).  The activation arguments
+ * are those of rten_hip_activation_f32.  y may equal x.  n*c == 0 or inner == 0 launches nothing.  No scratch, no atomics: the call can be captured. */
+int32_t rten_hip_instance_norm_f32(rten_hip_ctx *ctx, int32_t n, int32_t c, int64_t inner, const float *x, const float *scale, const float *bias,
+                                   float epsilon, int32_t act_kind, float act_alpha, float act_beta, float *y);
+/* InstanceNormalization path (tuning knob, sticky, default 0; part of rten_hip_tuning_save / _restore): 0 = automatic (slices of at most 1024 elements: one
+ * wave per slice, the slice in registers; longer ones: the streaming form -- the resident form has not been timed against it yet, docs/KERNELS.md 4.7),
+ * 1 = streaming (one workgroup per slice: one wave reduces from memory, all waves normalise; any length), 2 = resident (the workgroup holds the slice in
+ * LDS: one read and one write per element) for slices of at most RTEN_HIP_INSTANCE_NORM_RESIDENT_MAX elements, streaming above that (never an error).
+ * Same bits on every path. */
+#define RTEN_HIP_INSTANCE_NORM_RESIDENT_MAX 32768
+int32_t rten_hip_set_instance_norm_path(rten_hip_ctx *ctx, int32_t mode);
+
+/* ---- LogSoftmax: rten-vecmath/src/softmax.rs:131-174 ----
+ * Over the last axis of a [rows][cols] view: max (f32::MIN start), sum of ReducedRangeExp(x - max) in rten_hip_softmax_f32's order,
+ * y = (x - max) - ln(sum) as two subtractions.  ln(sum) is the f64 logarithm of the f32 sum rounded to f32 (the reference calls the host's libm logf,
+ * which is not correctly rounded: docs/KERNELS.md 4.7).  y may equal x. */
+int32_t rten_hip_log_softmax_f32(rten_hip_ctx *ctx, int64_t rows, int32_t cols, const float *x, float *y);
 
 /* ---- element-wise: src/ops/unary_elementwise.rs:399-420,611-613; binary_elementwise.rs:476-495 ---- */
 int32_t rten_hip_relu_f32(rten_hip_ctx *ctx, int64_t n, const float *x, float *y);

@@ -11,6 +11,7 @@
 //                        (= ConvIntegerToFloat, fusions.rs:1012-1058) (+ Add bias [1,O,1,1]) (+ Add residual) (+ Relu); make_matmul_integer_step:
 //                        MatMulInteger -> Cast -> Mul (= MatMulIntegerToFloat); make_matmul_step: MatMul (+ scalar Mul / Div) (+ Add bias)
 //                        (+ Gelu | Relu | activation) (= FusedMatMul); make_add_norm_step: Add -> LayerNormalization, Add -> Softmax;
+//                        make_norm_step: InstanceNormalization | BatchNormalization (+ Relu | activation), LogSoftmax;
 //                        plan_attention / emit_attention: the attention subgraph as MultiHeadSdpa; make_view_step: Reshape / Flatten / Squeeze /
 //                        Unsqueeze / Identity as views.  compile() itself is the table of contents: it walks the nodes and dispatches to these.
 //   * Graph::run         Graph::run_plan (src/graph.rs:1139-1231): operators run sequentially in plan order, values are
@@ -843,6 +844,47 @@ class Graph {
         if (a.lstm && n.inputs.size() > 7 && !n.inputs[7].empty()) throw GraphError(where + "a peephole input (P) is not supported");
         for (size_t k = 0; k < n.outputs.size() && k < (a.lstm ? 3u : 2u); k++) if (!n.outputs[k].empty()) a.output_mask |= 1u << k;
         return a;
+    }
+
+    // What an InstanceNormalization / BatchNormalization / LogSoftmax node asks for, read as onnx_registry.rs:830-842,1254-1257,1289-1292 reads it.
+    // BatchNormalization: training_mode != 0 and spatial != 1 are load errors that name the node, momentum is ignored, and a named output beyond Y
+    // (running_mean, running_var, saved_mean, saved_var: training only, norm.rs:249-256) is refused like MaxPool's Indices.  Needs no device.
+    struct NormNode {
+        std::optional<float> epsilon; // absent: the operator's default (1e-5)
+        int axis = -1;                // LogSoftmax
+    };
+    static NormNode read_norm_node(const onnx::Node &n, const std::string &label) {
+        const std::string kind = n.op_type, where = kind + " " + label + ": ";
+        NormNode a;
+        if (n.attr("epsilon")) a.epsilon = n.get_float("epsilon", 1e-5f);
+        if (kind == "BatchNormalization") {
+            if (n.get_int("training_mode", 0) != 0) throw GraphError(where + "training_mode=" + std::to_string(n.get_int("training_mode", 0)) + " is not supported");
+            if (n.get_int("spatial", 1) != 1) throw GraphError(where + "spatial=" + std::to_string(n.get_int("spatial", 1)) + " is not supported");
+            static const char *outs[] = {"Y", "running_mean", "running_var", "saved_mean", "saved_var"};
+            for (size_t k = 1; k < n.outputs.size(); k++)
+                if (!n.outputs[k].empty()) throw GraphError(where + "the " + (k < 5 ? outs[k] : "extra") + " output is not supported");
+        } else if (kind == "LogSoftmax") a.axis = (int)n.get_int("axis", -1);
+        return a;
+    }
+    // The step name the loader gives norm node `i` of a canonical model when fusion is on -- "InstanceNormalization+Relu", "BatchNormalization+Sigmoid", ... --
+    // from the node list alone (the rule of make_norm_step: the sole reader of the output is a Relu or an activation with load-time parameters), for
+    // rten_hip_run --parse-only, which has no device to build a plan on.
+    static std::string norm_step_name(const onnx::Model &m, size_t i) {
+        const onnx::Node &n = m.nodes.at(i);
+        const std::string &v = n.outputs.at(0);
+        if (n.op_type == "LogSoftmax") return n.op_type;
+        for (auto &o : m.outputs) if (o.name == v) return n.op_type;
+        const onnx::Node *reader = nullptr;
+        size_t readers = 0;
+        for (auto &u : m.nodes) for (auto &in : u.inputs) if (in == v) { readers++; reader = &u; }
+        if (readers != 1 || reader->inputs[0] != v) return n.op_type;
+        if (reader->op_type == "Relu") return n.op_type + "+Relu";
+        Activation act;
+        auto scalar = [&m](const std::string &name, float &) {
+            for (auto &t : m.initializers) if (t.name == name) return t.data_type == 1 && detail::prod(t.dims, 0, t.dims.size()) == 1;
+            return false;
+        };
+        return activation_of(*reader, act, scalar) ? n.op_type + "+" + activation_name(act.kind) : n.op_type;
     }
 
   private:
@@ -1725,6 +1767,10 @@ class Graph {
     // Clip's min / max come from its opset-6 attributes (promoted to inputs, onnx_registry.rs:887-897) or from constant scalar inputs (an empty name or a
     // missing input: f32::MIN / f32::MAX).  False: not one of these, or a Clip whose bounds are run-time values.
     bool activation_of(const onnx::Node &n, Activation &a) const {
+        return activation_of(n, a, [this](const std::string &v, float &out) { return const_f32_scalar(v, out); });
+    }
+    // (`scalar`: the value of a constant f32 scalar by name, false if it is not one -- the loader's constants, or the initializers of a model that is only parsed)
+    static bool activation_of(const onnx::Node &n, Activation &a, const std::function<bool(const std::string &, float &)> &scalar) {
         a = Activation();
         if (n.op_type == "Sigmoid") a.kind = RTEN_HIP_ACT_SIGMOID;
         else if (n.op_type == "Silu") a.kind = RTEN_HIP_ACT_SILU;
@@ -1742,7 +1788,7 @@ class Graph {
                 float v = 0.f;
                 if (n.attr(an)) v = n.get_float(an, 0.f);
                 else if (!has_in) continue;
-                else if (!const_f32_scalar(n.inputs[(size_t)k], v)) return false;
+                else if (!scalar(n.inputs[(size_t)k], v)) return false;
                 (k == 1 ? a.alpha : a.beta) = v;
             }
         } else return false;
@@ -2019,6 +2065,7 @@ class Graph {
             else if (kind == "Resize" || kind == "Upsample") make_resize_step(st, n);
             else if (kind == "Split") make_split_step(st, n);
             else if (kind == "GRU" || kind == "LSTM") make_rnn_step(st, n);
+            else if (kind == "InstanceNormalization" || kind == "BatchNormalization" || kind == "LogSoftmax") make_norm_step(st, n, nodes, out_name);
             else if (kind == "Flatten" || kind == "Reshape" || kind == "Squeeze" || kind == "Unsqueeze" || kind == "Identity" || kind == "Dropout") make_view_step(st, n);
             else if (make_layout_step(st, n)) {
                 // Shape / ConstantOfShape / NonZero / Range / Slice / Concat / Expand / Where / comparisons / logic / integer arithmetic / Cast / Gather /
@@ -2312,6 +2359,43 @@ class Graph {
             return op->run(c, in);
         };
     }
+    // InstanceNormalization / BatchNormalization (+ Relu, or one activation activation_of takes: the activation sees the f32 value the unfused node would
+    // store, so the pair keeps its bits) and LogSoftmax.  BatchNormalization is NOT folded into a preceding Conv: that would change bits against the
+    // reference.  Rows of the batch are independent for the two normalisations; LogSoftmax is coupled exactly when its axis resolves to dim 0.
+    void make_norm_step(Step &st, const onnx::Node &n, Nodes &nodes, std::string &out_name) {
+        const NormNode a = read_norm_node(n, st.name);
+        const std::string kind = n.op_type, nm = st.name;
+        if (kind == "LogSoftmax") {
+            auto op = std::make_shared<LogSoftmax>();
+            op->axis = a.axis;
+            st.batch_coupled = op->axis == 0;
+            st.run = [this, op, nm](Context &c, const InputList &in) { note_axis("LogSoftmax", nm, op->axis, require(in, 0)); return op->run(c, in); };
+            return;
+        }
+        Activation act;
+        if (opt_.fuse) {
+            const long r = nodes.sole_user(out_name, "Relu");
+            if (r >= 0) { act.kind = RTEN_HIP_ACT_RELU; nodes.absorb(st, (size_t)r, out_name); }
+            else {
+                Activation follower;
+                const long ac = nodes.sole_activation(out_name, follower);
+                if (ac >= 0) { act = follower; nodes.absorb(st, (size_t)ac, out_name); }
+            }
+        }
+        if (act.kind != RTEN_HIP_ACT_NONE) st.kind_name = kind + "+" + activation_name(act.kind);
+        if (kind == "InstanceNormalization") {
+            auto op = std::make_shared<InstanceNormalization>();
+            op->epsilon = a.epsilon;
+            op->act = act;
+            run_plainly(st, op);
+        } else {
+            auto op = std::make_shared<BatchNormalization>();
+            op->epsilon = a.epsilon.value_or(1e-5f);
+            op->act = act;
+            run_plainly(st, op);
+        }
+    }
+
     // ArgMax / ArgMin, TopK and Softmax: one axis each, noted per run in case it resolves to dim 0
     void make_select_step(Step &st, const onnx::Node &n) {
         const std::string kind = n.op_type, nm = st.name;

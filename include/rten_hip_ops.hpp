@@ -17,6 +17,7 @@
 // is no CPU fallback: without a gfx950 device `Context` throws.  Header only; C++17.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -26,6 +27,7 @@
 #include <memory>
 #include <mutex>
 #include <numeric>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -877,6 +879,106 @@ struct Softmax : Operator { // src/ops/norm.rs:825-840 (last-axis lanes contiguo
         const int64_t cols = x.size(a), rows = cols ? x.len() / cols : 0;
         Tensor y(ctx, x.shape(), DType::F32);
         if (x.len()) ctx.check(rten_hip_softmax_f32(ctx.raw(), rows, (int)cols, (const float *)x.ptr(), nullptr, 1, 1, 0, (float *)y.ptr()));
+        OutputList out;
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+
+// LogSoftmax (src/ops/norm.rs:695-800 over rten-vecmath/src/softmax.rs:131-174): Softmax's route, any axis.
+struct LogSoftmax : Operator {
+    int axis = -1;
+    const char *name() const override { return "LogSoftmax"; }
+    int max_inputs() const override { return 1; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = want(require(in, 0), DType::F32, "float32");
+        const int a = resolve_axis(axis, x.ndim());
+        OutputList out;
+        if (a != x.ndim() - 1) {
+            const int nd = x.ndim();
+            if (nd > 6) throw OpError(OpError::UnsupportedValue, "LogSoftmax over a non-last axis of more than 6 dims is not supported by the device path");
+            std::vector<int32_t> fwd, back((size_t)nd);
+            for (int i = 0; i < nd; i++) if (i != a) fwd.push_back(i);
+            fwd.push_back(a);
+            for (int i = 0; i < nd; i++) back[(size_t)fwd[(size_t)i]] = i;
+            std::vector<int64_t> tshape;
+            for (int i = 0; i < nd; i++) tshape.push_back(x.size(fwd[(size_t)i]));
+            Tensor t(ctx, tshape, DType::F32), y(ctx, x.shape(), DType::F32);
+            if (x.len()) {
+                const int64_t cols = x.size(a), rows = x.len() / cols;
+                ctx.check(rten_hip_transpose_b32(ctx.raw(), nd, x.shape().data(), fwd.data(), x.ptr(), t.ptr()));
+                ctx.check(rten_hip_log_softmax_f32(ctx.raw(), rows, (int)cols, (const float *)t.ptr(), (float *)t.ptr())); // in place: a wave stores a row after its last read of it
+                ctx.check(rten_hip_transpose_b32(ctx.raw(), nd, tshape.data(), back.data(), t.ptr(), y.ptr()));
+            }
+            out.push_back(std::move(y));
+            return out;
+        }
+        const int64_t cols = x.size(a), rows = cols ? x.len() / cols : 0;
+        Tensor y(ctx, x.shape(), DType::F32);
+        if (x.len()) ctx.check(rten_hip_log_softmax_f32(ctx.raw(), rows, (int)cols, (const float *)x.ptr(), (float *)y.ptr()));
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+
+// BatchNormalization, inference form (src/ops/norm.rs:194-318): inputs X [N, C, ...] (a 1-D input has C = 1), scale, bias, mean, var [C].
+// `act`: backend fusion of the following activation (the bits of the two operators in sequence).
+struct BatchNormalization : Operator {
+    float epsilon = 1e-5f;
+    Activation act;
+    const char *name() const override { return "BatchNormalization"; }
+    int max_inputs() const override { return 5; }
+    // the shape checks alone (the loader runs them on shapes): {n, channels, inner}
+    static std::array<int64_t, 3> geometry(const std::vector<int64_t> &xs, int64_t scale0, int64_t bias0, int64_t mean0, int64_t var0) {
+        if (xs.empty()) throw OpError(OpError::InvalidValue, "Input must have at least 1 dim");
+        const int64_t channels = xs.size() >= 2 ? xs[1] : 1;
+        if (scale0 != channels) throw OpError(OpError::IncompatibleInputShapes, "scale.size(0) != channels");
+        if (bias0 != channels) throw OpError(OpError::IncompatibleInputShapes, "bias.size(0) != channels");
+        if (mean0 != channels) throw OpError(OpError::IncompatibleInputShapes, "mean.size(0) != channels");
+        if (var0 != channels) throw OpError(OpError::IncompatibleInputShapes, "var.size(0) != channels");
+        const int64_t n = xs[0];
+        return {n, channels, xs.size() >= 2 ? detail::prod(xs, 2, xs.size()) : 1};
+    }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = want(require(in, 0), DType::F32, "float32");
+        const Tensor *p[4];
+        for (int i = 0; i < 4; i++) {
+            p[i] = &want(require(in, (size_t)i + 1), DType::F32, "float32");
+            if (p[i]->ndim() != 1) throw OpError(OpError::InvalidValue, "expected a vector"); // (NdTensorView<f32, 1> conversion)
+        }
+        const auto g = geometry(x.shape(), p[0]->size(0), p[1]->size(0), p[2]->size(0), p[3]->size(0));
+        Tensor y(ctx, x.shape(), DType::F32);
+        if (x.len())
+            ctx.check(rten_hip_batch_norm_f32_act(ctx.raw(), (int32_t)g[0], (int32_t)g[1], g[2], (const float *)x.ptr(), (const float *)p[0]->ptr(), (const float *)p[1]->ptr(),
+                                                  (const float *)p[2]->ptr(), (const float *)p[3]->ptr(), epsilon, act.kind, act.alpha, act.beta, (float *)y.ptr()));
+        OutputList out;
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+
+// InstanceNormalization (src/ops/norm.rs:320-395): inputs X [N, C, ...], scale [C], bias [C]; epsilon absent = 1e-5.  `act` as above.
+struct InstanceNormalization : Operator {
+    std::optional<float> epsilon;
+    Activation act;
+    const char *name() const override { return "InstanceNormalization"; }
+    int max_inputs() const override { return 3; }
+    static std::array<int64_t, 3> geometry(const std::vector<int64_t> &xs, int64_t scale0, int64_t bias0) {
+        if (xs.size() < 2) throw OpError(OpError::InvalidValue, "expected input with >= 2 dims");
+        if (scale0 != xs[1]) throw OpError(OpError::InvalidValue, "scale length should match channel count");
+        if (bias0 != xs[1]) throw OpError(OpError::InvalidValue, "bias length should match channel count");
+        return {xs[0], xs[1], detail::prod(xs, 2, xs.size())};
+    }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = want(require(in, 0), DType::F32, "float32");
+        const Tensor &scale = want(require(in, 1), DType::F32, "float32");
+        const Tensor &bias = want(require(in, 2), DType::F32, "float32");
+        if (scale.ndim() != 1 || bias.ndim() != 1) throw OpError(OpError::InvalidValue, "expected a vector");
+        const auto g = geometry(x.shape(), scale.size(0), bias.size(0));
+        Tensor y(ctx, x.shape(), DType::F32);
+        if (x.len())
+            ctx.check(rten_hip_instance_norm_f32(ctx.raw(), (int32_t)g[0], (int32_t)g[1], g[2], (const float *)x.ptr(), (const float *)scale.ptr(), (const float *)bias.ptr(),
+                                                 epsilon.value_or(1e-5f), act.kind, act.alpha, act.beta, (float *)y.ptr()));
         OutputList out;
         out.push_back(std::move(y));
         return out;
@@ -2472,7 +2574,10 @@ class OpRegistry {
         r.register_op<MatMulInteger>("MatMulInteger");
         r.register_op<MatMulNBits>("MatMulNBits");
         r.register_op<Softmax>("Softmax");
+        r.register_op<LogSoftmax>("LogSoftmax");
         r.register_op<LayerNormalization>("LayerNormalization");
+        r.register_op<BatchNormalization>("BatchNormalization");
+        r.register_op<InstanceNormalization>("InstanceNormalization");
         r.register_op<Relu>("Relu");
         r.register_op<Gelu>("Gelu");
         r.register_op<Erf>("Erf");

@@ -415,13 +415,13 @@ RTEN_EXPORT int32_t rten_hip_graph_destroy(rten_hip_ctx *ctx, uint64_t graph) {
 }
 
 // Snapshot / restore of every sticky tuning knob of a context (GEMM variant override, split-K plan, tile order, gemv order + thread
-// assumption, int8 path, attention path, recurrent path): a library-level caller that changes knobs around its own launches -- the plan executor on a
+// assumption, int8 path, attention path, recurrent path, instance-normalisation path): a library-level caller that changes knobs around its own launches -- the plan executor on a
 // BORROWED context -- puts back what the owner had set instead of the defaults.
 RTEN_EXPORT int32_t rten_hip_tuning_save(rten_hip_ctx *ctx, int32_t state[8]) {
     RTEN_CHECK_CTX(ctx);
     if (!state) return RTEN_HIP_ERR_INVALID_VALUE;
     state[0] = ctx->gemm_variant_override; state[1] = ctx->split_mode; state[2] = ctx->split_s; state[3] = ctx->tile_order;
-    state[4] = ctx->gemv_order; state[5] = (int32_t)ctx->gemv_threads; state[6] = ctx->int8_path; state[7] = ctx->sdpa_path | (ctx->rnn_path << 8); // (two small knobs share the last slot: the array's length is part of the ABI)
+    state[4] = ctx->gemv_order; state[5] = (int32_t)ctx->gemv_threads; state[6] = ctx->int8_path; state[7] = ctx->sdpa_path | (ctx->rnn_path << 8) | (ctx->instance_norm_path << 16); // (three small knobs share the last slot: the array's length is part of the ABI)
     return RTEN_HIP_OK;
 }
 RTEN_EXPORT int32_t rten_hip_tuning_restore(rten_hip_ctx *ctx, const int32_t state[8]) {
@@ -438,6 +438,7 @@ RTEN_EXPORT int32_t rten_hip_tuning_restore(rten_hip_ctx *ctx, const int32_t sta
     ctx->int8_path = state[6];
     ctx->sdpa_path = state[7] & 0xff;
     ctx->rnn_path = (state[7] >> 8) & 0xff;
+    ctx->instance_norm_path = (state[7] >> 16) & 0xff;
     return first;
 }
 

@@ -130,22 +130,6 @@ __global__ __launch_bounds__(EW_THREADS) void cast_scale_kernel(int64_t n, const
     }
 }
 
-// y = fma(x - mean_c, scale_c / sqrt(var_c + eps), bias_c)  (norm.rs:146 + normalize.rs:112-127)
-__global__ __launch_bounds__(EW_THREADS) void batch_norm_kernel(int64_t total, int c, int64_t inner,
-                                                                const float *__restrict__ x,
-                                                                const float *__restrict__ scale,
-                                                                const float *__restrict__ bias,
-                                                                const float *__restrict__ mean,
-                                                                const float *__restrict__ var, float eps,
-                                                                float *__restrict__ y) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const int ch = (int)((i / inner) % c);
-        const float ssr = scale[ch] / sqrtf(var[ch] + eps);
-        y[i] = vm::fma(x[i] - mean[ch], ssr, bias[ch]);
-    }
-}
-
 // out[i, :] = table[ids[i], :]  (Gather axis 0; out-of-range ids are clamped after host validation)
 __global__ __launch_bounds__(EW_THREADS) void gather_rows_kernel(int64_t n_ids, int row_len, int table_rows,
                                                                  const float *__restrict__ table,
@@ -385,19 +369,11 @@ RTEN_EXPORT int32_t rten_hip_cast_scale(rten_hip_ctx *ctx, int64_t n, const int3
     return RTEN_HIP_OK;
 }
 
+// (the kernel lives in norm.hip: BatchNormalization with an activation on the result; NONE passes the value through)
 RTEN_EXPORT int32_t rten_hip_batch_norm_f32(rten_hip_ctx *ctx, int32_t n, int32_t c, int64_t inner, const float *x,
                                             const float *scale, const float *bias, const float *mean,
                                             const float *var, float epsilon, float *y) {
-    RTEN_CHECK_CTX(ctx);
-    if (n < 0 || c <= 0 || inner < 0) return RTEN_HIP_ERR_INVALID_VALUE;
-    const int64_t total = (int64_t)n * c * inner;
-    if (total == 0) return RTEN_HIP_OK;
-    if (!x || !scale || !bias || !mean || !var || !y) return RTEN_HIP_ERR_INVALID_VALUE;
-    ProfScope ps(ctx, "batch_norm_f32", 0.0, 8.0 * total);
-    hipLaunchKernelGGL(batch_norm_kernel, dim3(ew_blocks(total)), dim3(EW_THREADS), 0, ctx->stream, total, c, inner, x,
-                       scale, bias, mean, var, epsilon, y);
-    RTEN_LAUNCH_CHECK(ctx, "batch_norm_kernel");
-    return RTEN_HIP_OK;
+    return rten_hip_batch_norm_f32_act(ctx, n, c, inner, x, scale, bias, mean, var, epsilon, RTEN_HIP_ACT_NONE, 0.f, 0.f, y);
 }
 
 RTEN_EXPORT int32_t rten_hip_gather_rows_f32(rten_hip_ctx *ctx, int64_t n_ids, int32_t row_len, int32_t table_rows,

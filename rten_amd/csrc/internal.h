@@ -55,6 +55,7 @@ struct rten_hip_ctx {
     int num_cus = 256;
     int sdpa_path = 0;  // 0 automatic (fused attention kernel when it covers the shape), 1 composed path only
     int rnn_path = 0;   // GRU / LSTM: 0 automatic, 1 composed path only (per-step GEMM + gate kernel), 2 the time-persistent fused kernel or an error (rnn.hip)
+    int instance_norm_path = 0; // InstanceNormalization: 0 automatic, 1 streaming form, 2 LDS-resident form where the slice fits, else streaming (norm.hip)
     int int8_path = 0;  // 0 automatic (fast staging path when it covers the call), 1 generic kernel only
     int int8_tile = -1; // rten_hip_set_int8_tile: -1 = per-shape rule, 0..3 = 128x128 / 128x64 / 64x128 / 64x64
     int tile_order = 0; // workgroup -> tile order bits (rten_hip_set_gemm_order)

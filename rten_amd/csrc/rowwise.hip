@@ -17,40 +17,13 @@
 #include <type_traits>
 
 #include "internal.h"
+#include "rowreduce.h" // lane_bcast, simd16_reduce: the reduction order, shared with norm.hip
 #include "vecmath.h"
 
 namespace {
 
 constexpr int ROWS_PER_BLOCK = 4;
 constexpr int MAX_CH = 16; // register-resident rows up to 1024 columns
-
-__device__ __forceinline__ float lane_bcast(float v, int src_lane) { return __shfl(v, src_lane, 64); }
-
-// fold_unroll<4> order (sum.rs:27-33,110-127).  kind 0: sum x ; kind 1: sum (x-off)^2 via mul_add.
-// `get(i)` returns element i (i < n).  All lanes return the same total.
-template <int KIND, typename Get>
-__device__ __forceinline__ float simd16_reduce(Get get, int n, float off, int lane) {
-    auto f = [&](float acc, float x) -> float {
-        if constexpr (KIND == 0) return acc + x;
-        else { const float d = x - off; return vm::fma(d, d, acc); }
-    };
-    float acc = 0.f;
-    const int full4 = n / 64;
-    for (int c = 0; c < full4; c++) acc = f(acc, get(c * 64 + lane));
-    // acc0 += acc1; += acc2; += acc3  (lanes 0..15 hold the running vector)
-    float a = acc;
-    a = a + lane_bcast(acc, (lane & 15) + 16);
-    a = a + lane_bcast(acc, (lane & 15) + 32);
-    a = a + lane_bcast(acc, (lane & 15) + 48);
-    int i0 = full4 * 64;
-    const int l = lane & 15;
-    for (; i0 + 16 <= n; i0 += 16) a = f(a, get(i0 + l));
-    if (i0 + l < n) a = f(a, get(i0 + l)); // masked tail: other lanes keep their value
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; k++) s = s + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), k));
-    return s;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Softmax: max (f32::MIN start), e = ReducedRangeExp(x - max), sum in single-accumulator 16-lane order

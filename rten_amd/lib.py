@@ -21,6 +21,8 @@ ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 RNN_FORWARD, RNN_REVERSE, RNN_BIDIRECTIONAL = 0, 1, 2
 RNN_PATH_AUTO, RNN_PATH_COMPOSED, RNN_PATH_FUSED = 0, 1, 2  # rten_hip_set_rnn_path
 RNN_FUSED_MAX_HIDDEN = 256
+INSTANCE_NORM_PATH_AUTO, INSTANCE_NORM_PATH_STREAMING, INSTANCE_NORM_PATH_RESIDENT = 0, 1, 2  # rten_hip_set_instance_norm_path
+INSTANCE_NORM_RESIDENT_MAX = 32768  # RTEN_HIP_INSTANCE_NORM_RESIDENT_MAX: longest slice (elements) the resident form holds
 # act_kind of rten_hip_activation_f32 / rten_hip_gemm_f32_act / rten_hip_conv2d_f32_act (which also take the three above)
 ACT_SIGMOID, ACT_SILU, ACT_SWISH, ACT_HARD_SIGMOID, ACT_HARD_SWISH, ACT_CLIP, ACT_LEAKY_RELU, ACT_ELU = 3, 4, 5, 6, 7, 8, 9, 10
 # mode / coord_mode / nearest_mode of rten_hip_resize_f32 (RTEN_HIP_RESIZE_*)
@@ -167,6 +169,10 @@ PROTOTYPES = {
     "rten_hip_layer_norm_f32": (_I32, [_VP, _I64, _I32, _VP, _VP, _VP, _F32, _F32, _F32, _VP]),
     "rten_hip_add_layer_norm_f32": (_I32, [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _F32, _F32, _F32, _VP]),
     "rten_hip_batch_norm_f32": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _F32, _VP]),
+    "rten_hip_batch_norm_f32_act": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _F32, _I32, _F32, _F32, _VP]),
+    "rten_hip_instance_norm_f32": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _F32, _I32, _F32, _F32, _VP]),
+    "rten_hip_set_instance_norm_path": (_I32, [_VP, _I32]),
+    "rten_hip_log_softmax_f32": (_I32, [_VP, _I64, _I32, _VP, _VP]),
     "rten_hip_relu_f32": (_I32, [_VP, _I64, _VP, _VP]),
     "rten_hip_activation_f32": (_I32, [_VP, _I32, C.c_float, C.c_float, _I64, _VP, _VP]),
     "rten_hip_gelu_f32": (_I32, [_VP, _I64, _VP, _VP]),

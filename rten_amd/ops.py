@@ -822,10 +822,12 @@ class LayerNormalization(Operator):
 
 
 class BatchNormalization(Operator):
-    """src/ops/norm.rs:194-290.  inputs: X, scale, bias, mean, var"""
+    """src/ops/norm.rs:194-290.  inputs: X, scale, bias, mean, var.  Extra: `act`, an activation operator instance (Relu(), Sigmoid(),
+    Clip(0, 6), ...) applied to the result in the same launch (the bits of the two operators in sequence)."""
 
-    def __init__(self, epsilon=1e-5):
+    def __init__(self, epsilon=1e-5, act=None):
         self.epsilon = epsilon
+        self.act = act
 
     def max_inputs(self):
         return 5
@@ -842,7 +844,84 @@ class BatchNormalization(Operator):
         n = x.shape[0]
         inner = x.size // max(n * chans, 1)
         y = DeviceTensor(ctx, x.shape, np.float32)
-        ctx.call("rten_hip_batch_norm_f32", n, chans, inner, x.vp, scale.vp, bias.vp, mean.vp, var.vp, self.epsilon, y.vp)
+        if self.act is None:
+            ctx.call("rten_hip_batch_norm_f32", n, chans, inner, x.vp, scale.vp, bias.vp, mean.vp, var.vp, self.epsilon, y.vp)
+        else:
+            ctx.call("rten_hip_batch_norm_f32_act", n, chans, inner, x.vp, scale.vp, bias.vp, mean.vp, var.vp, self.epsilon, *_norm_act_args(self.act), y.vp)
+        return [y]
+
+
+def _norm_act_args(act):
+    """(kind, alpha, beta) of the `act` of a normalisation operator: None, Relu() / Gelu() or a parameterised activation instance."""
+    if act is None:
+        return L.ACT_NONE, 0.0, 0.0
+    if isinstance(act, Relu):
+        return L.ACT_RELU, 0.0, 0.0
+    if isinstance(act, Gelu):
+        return L.ACT_GELU, 0.0, 0.0
+    return _activation_args(act)
+
+
+class InstanceNormalization(Operator):
+    """src/ops/norm.rs:320-395.  inputs: X [N, C, ...], scale [C], bias [C].  epsilon None = the ONNX default 1e-5.  Extra: `act` as for
+    BatchNormalization."""
+
+    def __init__(self, epsilon=None, act=None):
+        self.epsilon = epsilon
+        self.act = act
+
+    def max_inputs(self):
+        return 3
+
+    def run(self, ctx, inputs, in_place=False):
+        x = _want(_require(inputs, 0), np.float32)
+        scale = _want(_require(inputs, 1), np.float32)
+        bias = _want(_require(inputs, 2), np.float32)
+        if len(x.shape) < 2:
+            raise InvalidValue("expected input with >= 2 dims")
+        n, chans = x.shape[0], x.shape[1]
+        if len(scale.shape) != 1 or scale.shape[0] != chans:
+            raise InvalidValue("scale length should match channel count")
+        if len(bias.shape) != 1 or bias.shape[0] != chans:
+            raise InvalidValue("bias length should match channel count")
+        inner = int(np.prod(x.shape[2:], dtype=np.int64))
+        eps = 1e-5 if self.epsilon is None else self.epsilon
+        y = x if in_place else DeviceTensor(ctx, x.shape, np.float32)
+        ctx.call("rten_hip_instance_norm_f32", n, chans, inner, x.vp, scale.vp, bias.vp, eps, *_norm_act_args(self.act), y.vp)
+        return [y]
+
+
+class LogSoftmax(Operator):
+    """src/ops/norm.rs:695-800 (log_softmax over normalize_lanes, rten-vecmath/src/softmax.rs:131-174); any axis, a non-last one by the route Softmax takes."""
+
+    def __init__(self, axis=-1):
+        self.axis = axis
+
+    def max_inputs(self):
+        return 1
+
+    def run(self, ctx, inputs):
+        x = _want(_require(inputs, 0), np.float32)
+        nd = len(x.shape)
+        ax = _resolve_axis(nd, self.axis)
+        if ax != nd - 1:
+            if nd > 6:
+                raise UnsupportedValue("LogSoftmax over a non-last axis of more than 6 dims is not supported by the device path")
+            fwd = [i for i in range(nd) if i != ax] + [ax]
+            back = [fwd.index(i) for i in range(nd)]
+            tshape = [x.shape[i] for i in fwd]
+            t, y = DeviceTensor(ctx, tshape, np.float32), DeviceTensor(ctx, x.shape, np.float32)
+            if x.size:
+                cols = x.shape[ax]
+                i64 = lambda v: (C.c_int64 * len(v))(*v)
+                i32 = lambda v: (C.c_int32 * len(v))(*v)
+                ctx.call("rten_hip_transpose_b32", nd, i64(list(x.shape)), i32(fwd), x.vp, t.vp)
+                ctx.call("rten_hip_log_softmax_f32", x.size // cols, cols, t.vp, t.vp)  # in place: a wave stores a row only after its last read of it
+                ctx.call("rten_hip_transpose_b32", nd, i64(tshape), i32(back), t.vp, y.vp)
+            return [y]
+        y = DeviceTensor(ctx, x.shape, np.float32)
+        cols = x.shape[-1]
+        ctx.call("rten_hip_log_softmax_f32", x.size // max(cols, 1), cols, x.vp, y.vp)
         return [y]
 
 
@@ -1689,7 +1768,7 @@ class OpRegistry:
     def with_all_ops(cls):
         r = cls()
         for op in (Conv, ConvTranspose, ConvInteger, ConvIntegerToFloat, MatMul, FusedMatMul, Gemm, MatMulInteger, MatMulIntegerToFloat, MatMulNBits,
-                   Softmax, AddSoftmax, LayerNormalization, BatchNormalization, Relu, Gelu, Erf, Add, Mul, Sub, Div, Transpose, MaxPool,
+                   Softmax, LogSoftmax, AddSoftmax, LayerNormalization, BatchNormalization, InstanceNormalization, Relu, Gelu, Erf, Add, Mul, Sub, Div, Transpose, MaxPool,
                    AveragePool, GlobalAveragePool, Flatten, DynamicQuantizeLinear, Attention, Gather, ReduceSum, ReduceMean, Einsum, Resize, Upsample,
                    Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK, GRU, LSTM):
             r.register_op(op)

@@ -117,6 +117,31 @@ def main():
         (lambda: ctx.call("rten_hip_max_pool2d_f32_stats", C.byref(pd), x.vp, y.vp, st.vp)), 4.0 * (n_in + n_out))
     hbm("GlobalAveragePool", "32x2048x7x7", (lambda: ctx.call("rten_hip_global_average_pool_f32", 32 * 2048, 49, x.vp, y.vp)), 4.0 * 32 * 2048 * 50)
 
+    # InstanceNormalization (few, long slices) on every path, BatchNormalization with a fused activation, LogSoftmax -- each beside a device copy of the
+    # same bytes (the rate a launch of that size can reach at all)
+    def copy_row(what, n_el):
+        hbm(f"copy, {what} (reference point)", f"{4 * n_el} B", (lambda: ctx.call("rten_hip_memcpy_d2d", y.vp, x.vp, C.c_size_t(4 * n_el))), 8.0 * n_el)
+
+    for n, c, h, w in ((8, 64, 128, 128), (1, 32, 512, 512), (32, 256, 32, 32)):
+        sc_c, bi_c = dev(rng.standard_normal(c, dtype=np.float32)), dev(rng.standard_normal(c, dtype=np.float32))
+        for pname, path in (("streaming", L.INSTANCE_NORM_PATH_STREAMING), ("resident", L.INSTANCE_NORM_PATH_RESIDENT), ("auto", L.INSTANCE_NORM_PATH_AUTO)):
+            if want("InstanceNormalization"):
+                ctx.call("rten_hip_set_instance_norm_path", path)
+            hbm(f"InstanceNormalization ({pname})", f"{n}x{c}x{h}x{w}",
+                (lambda n=n, c=c, h=h, w=w, sc_c=sc_c, bi_c=bi_c: ctx.call("rten_hip_instance_norm_f32", n, c, h * w, x.vp, sc_c.vp, bi_c.vp, 1e-5, L.ACT_RELU, 0.0, 0.0, y.vp)),
+                8.0 * n * c * h * w)
+        ctx.call("rten_hip_set_instance_norm_path", L.INSTANCE_NORM_PATH_AUTO)
+        copy_row(f"InstanceNormalization {n}x{c}x{h}x{w}", n * c * h * w)
+    bn_c = 256
+    bn_p = [dev(np.abs(rng.standard_normal(bn_c, dtype=np.float32)) + 0.5) for _ in range(4)]
+    hbm("batch_norm_f32_act (Relu)", "32x256x56x56",
+        (lambda: ctx.call("rten_hip_batch_norm_f32_act", 32, bn_c, 56 * 56, x.vp, *[t.vp for t in bn_p], 1e-5, L.ACT_RELU, 0.0, 0.0, y.vp)), 8.0 * n_act)
+    hbm("batch_norm_f32", "32x256x56x56", (lambda: ctx.call("rten_hip_batch_norm_f32", 32, bn_c, 56 * 56, x.vp, *[t.vp for t in bn_p], 1e-5, y.vp)), 8.0 * n_act)
+    copy_row("batch_norm 32x256x56x56", n_act)
+    for r, c in ((4096, 97), (64, 32000)):
+        hbm("LogSoftmax", f"rows={r} cols={c}", (lambda r=r, c=c: ctx.call("rten_hip_log_softmax_f32", r, c, x.vp, y.vp)), 8.0 * r * c)
+        copy_row(f"LogSoftmax {r}x{c}", r * c)
+
     # depthwise 3x3 (MobileNet-style: 32 x 144 x 56 x 56) and a 2x upsampling ConvTranspose (32 x 64 x 28 x 28 -> 32 x 32 x 56 x 56, 4x4 / 2)
     cdw = 144
     xdw, wdw, bdw = dev(rng.standard_normal((32, cdw, 56, 56), dtype=np.float32)), dev(rng.standard_normal((cdw, 1, 3, 3), dtype=np.float32)), dev(np.zeros(cdw, np.float32))

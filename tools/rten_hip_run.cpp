@@ -16,7 +16,7 @@
 //     -t, --timing           per-operator table (each operator followed by a sync)
 //     --tune                 time the candidate launch plans of every f32 convolution at load and keep the fastest
 //     --graph                capture one run into a hipGraph and replay it for the timed runs
-//     --parse-only           print the model summary (and check the attributes of GRU / LSTM nodes as the loader does) and exit (needs no GPU)
+//     --parse-only           print the model summary (and check the attributes of GRU / LSTM and normalisation nodes as the loader does) and exit (needs no GPU)
 //     --safetensors-info F   list the tensors of a Safetensors file (with --save-outputs: re-write it); no model, no GPU
 //
 // There is no CPU fallback: without an MI355X the tool reports BackendUnavailable and exits 2.
@@ -121,6 +121,16 @@ int main(int argc, char **argv) {
                 std::printf("  recurrent step %s \"%s\": %s, hidden_size %" PRId64 "\n", n.op_type.c_str(), n.name.c_str(),
                             a.direction == RnnDirection::Bidirectional ? "bidirectional" : a.direction == RnnDirection::Reverse ? "reverse" : "forward", a.hidden_size);
             }
+        {
+            const onnx::Model c = Graph::canonical_form(m); // normalisation nodes: the loader's attribute and output checks, and the step each becomes with fusion on
+            for (size_t i = 0; i < c.nodes.size(); i++) {
+                const onnx::Node &n = c.nodes[i];
+                if (!(n.domain.empty() || n.domain == "ai.onnx") || !(n.op_type == "InstanceNormalization" || n.op_type == "BatchNormalization" || n.op_type == "LogSoftmax")) continue;
+                const Graph::NormNode a = Graph::read_norm_node(n, n.name.empty() ? n.outputs.at(0) : n.name);
+                if (n.op_type == "LogSoftmax") std::printf("  norm step LogSoftmax \"%s\": axis %d\n", n.name.c_str(), a.axis);
+                else std::printf("  norm step %s \"%s\": epsilon %g\n", (fuse ? Graph::norm_step_name(c, i) : n.op_type).c_str(), n.name.c_str(), (double)a.epsilon.value_or(1e-5f));
+            }
+        }
         if (parse_only) return 0;
 
         Context ctx(0);

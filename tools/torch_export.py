@@ -18,6 +18,9 @@ Test and tooling infrastructure only: nothing under rten_amd/ imports this.
     python tools/torch_export.py yolo_filter /tmp/yolo_filter.onnx     # the detector + scores.max(1) + topk over anchors + Gather by index
     python tools/torch_export.py recognizer_gru /tmp/rec_gru.onnx      # text-recogniser shape: Conv2d + ReLU, columns as time steps, bidirectional
     python tools/torch_export.py recognizer_lstm /tmp/rec_lstm.onnx    #   GRU / LSTM, Linear head (dynamic batch and width)
+    python tools/torch_export.py recognizer_ctc /tmp/rec_ctc.onnx      # the GRU recogniser with its log_softmax head (LogSoftmax)
+    python tools/torch_export.py generator /tmp/generator.onnx         # image-to-image generator: Conv / InstanceNorm2d / ReLU, residual blocks, ConvTranspose, Tanh
+    python tools/torch_export.py preact /tmp/preact.onnx               # pre-activation blocks (BN -> ReLU -> Conv): BatchNormalization nodes that survive export
 """
 from __future__ import annotations
 
@@ -399,11 +402,12 @@ def yolo_filter_onnx(model=None, image: int = 64, batch: int = 2) -> bytes:
 
 
 def recognizer_module(kind: str = "gru", bidirectional: bool = True, layers: int = 1, seed: int = 0, height: int = 8, channels: int = 4, hidden: int = 20,
-                      classes: int = 11, batch_first: bool = False):
+                      classes: int = 11, batch_first: bool = False, log_softmax: bool = False):
     """A text recogniser in the shape of `ocrs`: Conv2d + ReLU over a [b, 1, height, w] line image, every image column a time step
     (`permute(3, 0, 1, 2).flatten(2)` -> [w, b, channels * height]), `layers` uni- or bidirectional nn.GRU / nn.LSTM layers, a Linear head over
     the classes -- [w, b, classes], or [b, w, classes] with `batch_first` (a trailing permute: what the model ABI's dim-0 batch slices need).  The exporter writes one GRU / LSTM node per layer (linear_before_reset=1, empty sequence_lens, initial states from Expand /
-    ConstantOfShape) between Transpose / Reshape / Shape arithmetic."""
+    ConstantOfShape) between Transpose / Reshape / Shape arithmetic.  `log_softmax`: the model's real head, log_softmax(dim=-1) over the classes (what a
+    CTC decoder reads): one LogSoftmax node."""
     import torch
     from torch import nn
     torch.manual_seed(seed)
@@ -420,6 +424,8 @@ def recognizer_module(kind: str = "gru", bidirectional: bool = True, layers: int
             f = torch.relu(self.conv(x)).permute(3, 0, 1, 2).flatten(2)
             y, _ = self.rnn(f)
             y = self.head(y)
+            if log_softmax:
+                y = torch.log_softmax(y, dim=-1)
             return y.permute(1, 0, 2) if batch_first else y
 
     net = Net().eval()
@@ -434,6 +440,91 @@ def recognizer_onnx(model=None, kind: str = "gru", bidirectional: bool = True, l
     y_axes = {0: "batch", 1: "width"} if getattr(model, "batch_first", False) else {0: "width", 1: "batch"}
     axes = {"x": {0: "batch", 3: "width"}, "y": y_axes} if dynamic else None
     return export_bytes(model, (torch.zeros(batch, 1, height, width),), ["x"], ["y"], axes)
+
+
+def generator_module(seed: int = 0, width: int = 8):
+    """A small image-to-image generator in the shape of the CycleGAN / fast-style-transfer nets: Conv -> InstanceNorm2d(affine) -> ReLU down path (one
+    stride-2 stage), two residual blocks with InstanceNorm, a ConvTranspose up path, Tanh.  Zero padding only (no Pad node).  Every
+    nn.InstanceNorm2d exports as one InstanceNormalization node; those followed by a ReLU fuse with it in the executor."""
+    import torch
+    from torch import nn
+    torch.manual_seed(seed)
+    c1, c2 = width, 2 * width
+
+    class Res(nn.Module):
+        def __init__(self, c):
+            super().__init__()
+            self.body = nn.Sequential(nn.Conv2d(c, c, 3, 1, 1), nn.InstanceNorm2d(c, affine=True), nn.ReLU(), nn.Conv2d(c, c, 3, 1, 1), nn.InstanceNorm2d(c, affine=True))
+
+        def forward(self, x):
+            return x + self.body(x)
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.body = nn.Sequential(
+                nn.Conv2d(3, c1, 3, 1, 1), nn.InstanceNorm2d(c1, affine=True), nn.ReLU(),
+                nn.Conv2d(c1, c2, 3, 2, 1), nn.InstanceNorm2d(c2, affine=True), nn.ReLU(),
+                Res(c2), Res(c2),
+                nn.ConvTranspose2d(c2, c1, 3, 2, 1, output_padding=1), nn.InstanceNorm2d(c1, affine=True), nn.ReLU(),
+                nn.Conv2d(c1, 3, 3, 1, 1), nn.Tanh())
+            for m in self.modules():  # distinct scale / bias per channel: a channel mix-up cannot cancel
+                if isinstance(m, nn.InstanceNorm2d):
+                    nn.init.uniform_(m.weight, 0.5, 1.5)
+                    nn.init.uniform_(m.bias, -0.5, 0.5)
+
+        def forward(self, x):
+            return self.body(x)
+
+    return Net().eval()
+
+
+def generator_onnx(model=None, image: int = 16, batch: int = 2, dynamic: bool = True) -> bytes:
+    import torch
+    model = model if model is not None else generator_module()
+    axes = {"x": {0: "batch"}, "y": {0: "batch"}} if dynamic else None
+    return export_bytes(model, (torch.zeros(batch, 3, image, image),), ["x"], ["y"], axes)
+
+
+def preact_module(seed: int = 0, classes: int = 5):
+    """A pre-activation network (BN -> ReLU -> Conv, the order of ResNet-v2 / DenseNet) whose BatchNormalization nodes survive export: the exporter
+    folds a BatchNorm only into a convolution directly before it.  Here one follows a convolution whose output is also the residual, one follows a
+    pool (with a LeakyReLU), and a BatchNorm1d sits in the head in front of the Linear layer."""
+    import torch
+    from torch import nn
+    torch.manual_seed(seed)
+
+    def randomise(bn):  # running statistics and affine parameters away from their (0, 1, 1, 0) initial values
+        nn.init.uniform_(bn.weight, 0.5, 1.5)
+        nn.init.uniform_(bn.bias, -0.5, 0.5)
+        bn.running_mean.uniform_(-0.5, 0.5)
+        bn.running_var.uniform_(0.5, 2.0)
+        return bn
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.stem = nn.Conv2d(3, 8, 3, 1, 1)
+            self.bn1, self.conv1 = randomise(nn.BatchNorm2d(8)), nn.Conv2d(8, 8, 3, 1, 1)
+            self.pool = nn.MaxPool2d(2)
+            self.bn2, self.act2, self.conv2 = randomise(nn.BatchNorm2d(8)), nn.LeakyReLU(0.1), nn.Conv2d(8, 12, 1)
+            self.bn3, self.fc = randomise(nn.BatchNorm1d(12)), nn.Linear(12, classes)
+
+        def forward(self, x):
+            y = self.stem(x)
+            y = y + self.conv1(torch.relu(self.bn1(y)))
+            y = self.conv2(self.act2(self.bn2(self.pool(y))))
+            y = torch.flatten(nn.functional.adaptive_avg_pool2d(y, 1), 1)
+            return self.fc(self.bn3(y))
+
+    return Net().eval()
+
+
+def preact_onnx(model=None, image: int = 16, batch: int = 2, dynamic: bool = True) -> bytes:
+    import torch
+    model = model if model is not None else preact_module()
+    axes = {"x": {0: "batch"}, "logits": {0: "batch"}} if dynamic else None
+    return export_bytes(model, (torch.zeros(batch, 3, image, image),), ["x"], ["logits"], axes)
 
 
 if __name__ == "__main__":
@@ -457,6 +548,12 @@ if __name__ == "__main__":
         data = yolo_filter_onnx()
     elif kind in ("recognizer_gru", "recognizer_lstm"):
         data = recognizer_onnx(kind=kind.split("_")[1])
+    elif kind == "recognizer_ctc":
+        data = recognizer_onnx(recognizer_module("gru", log_softmax=True))
+    elif kind == "generator":
+        data = generator_onnx()
+    elif kind == "preact":
+        data = preact_onnx()
     else:
         data = bert_onnx(bert_module())
     open(path, "wb").write(data)
