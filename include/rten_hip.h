@@ -466,8 +466,30 @@ int32_t rten_hip_add_f32(rten_hip_ctx *ctx, int64_t n, const float *a, const flo
 int32_t rten_hip_mul_f32(rten_hip_ctx *ctx, int64_t n, const float *a, const float *b, int64_t b_len, float *y);
 int32_t rten_hip_sub_f32(rten_hip_ctx *ctx, int64_t n, const float *a, const float *b, int64_t b_len, float *y);
 int32_t rten_hip_div_f32(rten_hip_ctx *ctx, int64_t n, const float *a, const float *b, int64_t b_len, float *y);
-/* General numpy broadcasting (binary_elementwise.rs:58-170): op 0 add, 1 mul, 2 sub, 3 div; out_shape[ndim] (ndim <= 6);
- * a_strides / b_strides in elements of the operands as expanded to out_shape, 0 on broadcast axes. */
+/* Unary math operators (src/ops/unary_elementwise.rs), contiguous, y may equal x.  Exactly rounded and bit-identical to the reference: NEG / ABS
+ * (sign-bit operations), SIGN (Rust signum: +0 -> 1, -0 -> -1, NaN -> NaN), FLOOR / CEIL, ROUND (ties to even), SQRT and RECIPROCAL (correctly rounded,
+ * subnormals included), EXP (rten-vecmath's polynomial, the Exp of the activation kernels).  LOG and SOFTPLUS are the functions the reference hands to the
+ * host's libm (ln, exp(x).ln_1p()): here the float64 function rounded once to f32 -- Softplus rounds exp(x) to f32 first, so x >= 88.73 gives +inf as in
+ * the reference (docs/KERNELS.md 4.8).  One kernel instantiation per code; 16-byte accesses between a scalar head and tail when x and y are misaligned by
+ * the same amount, scalar accesses otherwise.  An unknown code is RTEN_HIP_ERR_INVALID_VALUE. */
+#define RTEN_HIP_UNARY_NEG 0
+#define RTEN_HIP_UNARY_ABS 1
+#define RTEN_HIP_UNARY_SIGN 2
+#define RTEN_HIP_UNARY_FLOOR 3
+#define RTEN_HIP_UNARY_CEIL 4
+#define RTEN_HIP_UNARY_ROUND 5
+#define RTEN_HIP_UNARY_SQRT 6
+#define RTEN_HIP_UNARY_RECIPROCAL 7
+#define RTEN_HIP_UNARY_EXP 8
+#define RTEN_HIP_UNARY_LOG 9
+#define RTEN_HIP_UNARY_SOFTPLUS 10
+int32_t rten_hip_unary_f32(rten_hip_ctx *ctx, int32_t op, int64_t n, const float *x, float *y);
+/* General numpy broadcasting (binary_elementwise.rs:58-170): op 0 add, 1 mul, 2 sub, 3 div, 4 min, 5 max, 6 pow, 7 prelu; out_shape[ndim] (ndim <= 6);
+ * a_strides / b_strides in elements of the operands as expanded to out_shape, 0 on broadcast axes.
+ * min / max: the reference's cmp_nan_less / cmp_nan_greater (reduce.rs:847-873) -- a NaN in either operand wins, on a tie `a` is kept (max(+0, -0) = +0,
+ * max(-0, +0) = -0).  pow: a = base, b = exponent, tested per element: 2 -> a * a, 3 -> a * a * a (two roundings, binary_elementwise.rs:977-987), anything
+ * else the float64 pow rounded once to f32 (C99 special values).  prelu: a = x, b = slope: a < 0 ? b * a : a.  Ops 4-7 take 16-byte accesses when both
+ * operands are dense, or `a` is dense and `b` one element (stride 0 on every axis: the 2 / 3 / general branch of pow is then uniform). */
 int32_t rten_hip_binary_broadcast_f32(rten_hip_ctx *ctx, int32_t op, int32_t ndim, const int64_t *out_shape, const int64_t *a_strides,
                                       const int64_t *b_strides, const float *a, const float *b, float *y);
 /* Transpose (src/ops/layout.rs:669+) of 4-byte elements: y.shape[d] = x_shape[perm[d]], ndim <= 6; an invalid perm is
@@ -506,8 +528,28 @@ int32_t rten_hip_copy_strided_b32(rten_hip_ctx *ctx, int32_t ndim, const int64_t
 #define RTEN_HIP_EW_ISUB 12
 #define RTEN_HIP_EW_IMUL 13
 #define RTEN_HIP_EW_IDIV 14
+/* int32 Neg / Abs (wrapping: i32::MIN stays i32::MIN) / Sign (-1, 0, 1): unary; int32 Min / Max (variadic_elementwise.rs:58-66,132-140) */
+#define RTEN_HIP_EW_INEG 15
+#define RTEN_HIP_EW_IABS 16
+#define RTEN_HIP_EW_ISIGN 17
+#define RTEN_HIP_EW_IMIN 18
+#define RTEN_HIP_EW_IMAX 19
 int32_t rten_hip_elementwise_nd(rten_hip_ctx *ctx, int32_t op, int32_t ndim, const int64_t *shape, const void *a, int32_t a_dtype, const int64_t *a_strides,
                                 const void *b, int32_t b_dtype, const int64_t *b_strides, const void *c, const int64_t *c_strides, void *y, int32_t y_dtype);
+/* Pad (src/ops/pad.rs) of 4-byte elements, ndim <= 6, one launch: a gather over the output.  pads[2 * ndim] = every axis' begin, then every axis' end; a
+ * negative entry crops that side first.  With len = the cropped axis length and p = the begin pad, output index o reads (pad.rs:235-286, taken literally)
+ *   RTEN_HIP_PAD_CONSTANT  o - p, or the word fill_bits where any axis falls outside [0, len)
+ *   RTEN_HIP_PAD_REFLECT   (o < p ? p - o : o < len + p ? o - p : len - (o - len - p) - 2) mod len (euclidean, also for pads >= len)
+ *   RTEN_HIP_PAD_EDGE      clamp(o - p, 0, len - 1)
+ *   RTEN_HIP_PAD_WRAP      (o - p) mod len
+ * on every axis (the host operators keep the reference's restriction of the last three modes to the last two dims).  y is contiguous with
+ * max(pads, 0) + len on each axis.  Rows of an unpadded innermost axis move as 16-byte words when x, y, the row length and the crop allow.  A crop larger
+ * than its axis, and a padded empty axis in a non-constant mode, are RTEN_HIP_ERR_INVALID_VALUE with the reference's messages.  An empty output launches nothing. */
+#define RTEN_HIP_PAD_CONSTANT 0
+#define RTEN_HIP_PAD_REFLECT 1
+#define RTEN_HIP_PAD_EDGE 2
+#define RTEN_HIP_PAD_WRAP 3
+int32_t rten_hip_pad_b32(rten_hip_ctx *ctx, int32_t mode, int32_t ndim, const int64_t *x_shape, const int64_t *pads, uint32_t fill_bits, const void *x, void *y);
 /* Gather along any axis of 4-byte elements (src/ops/gather.rs:21-110): y[o][j][k] = data[o][ids[j]][k] with data viewed as [outer][axis_len][inner];
  * negative indices count from the end; out-of-range indices are clamped (the reference reports "Entry in indices is out of range"). */
 int32_t rten_hip_gather_axis_b32(rten_hip_ctx *ctx, int64_t outer, int64_t axis_len, int64_t inner, int64_t n_ids, const void *data, const int32_t *ids, void *y);

@@ -538,6 +538,95 @@ inline HostVal reduce_minmax(const HostVal &x, const std::vector<int> &axes, boo
     }
     return y;
 }
+// ---- unary math of a host value, with the device's semantics (all exact in C++): Neg / Abs / Sign for both types (int32 wraps: i32::MIN stays; float Sign is
+// Rust's signum: +0 -> 1, -0 -> -1, NaN -> NaN), Floor / Ceil / Round (ties to even) / Sqrt / Reciprocal for float32.  false: not this operator / type.
+inline bool unary(const std::string &op, const HostVal &x, HostVal &out) {
+    out = HostVal();
+    out.shape = x.shape;
+    out.is_float = x.is_float;
+    if (!x.is_float) {
+        if (op != "Neg" && op != "Abs" && op != "Sign") return false;
+        for (int64_t v : x.i) out.i.push_back(op == "Neg" ? wrap32(-v) : op == "Abs" ? wrap32(v < 0 ? -v : v) : (int64_t)(v > 0) - (int64_t)(v < 0));
+        return true;
+    }
+    for (float v : x.f) {
+        float r;
+        uint32_t w;
+        std::memcpy(&w, &v, 4);
+        if (op == "Neg") { w ^= 0x80000000u; std::memcpy(&r, &w, 4); }
+        else if (op == "Abs") { w &= 0x7fffffffu; std::memcpy(&r, &w, 4); }
+        else if (op == "Sign") r = v != v ? std::numeric_limits<float>::quiet_NaN() : std::copysign(1.0f, v);
+        else if (op == "Floor") r = std::floor(v);
+        else if (op == "Ceil") r = std::ceil(v);
+        else if (op == "Round") r = std::nearbyint(v); // the default rounding mode: ties to even
+        else if (op == "Sqrt") r = std::sqrt(v);
+        else if (op == "Reciprocal") r = 1.0f / v;
+        else return false;
+        out.f.push_back(r);
+    }
+    return true;
+}
+// Min / Max of two host values (reduce.rs:847-873: a NaN in either operand wins, a tie keeps `a`), numpy broadcasting
+inline bool minmax(bool is_min, const HostVal &a, const HostVal &b, HostVal &out) {
+    if (a.is_float != b.is_float) return false;
+    out = HostVal();
+    out.shape = bshape({&a, &b});
+    if (out.len() > kMaxHostElems) return false;
+    out.is_float = a.is_float;
+    const std::vector<std::vector<int64_t>> st{strides_for(a.shape, out.shape), strides_for(b.shape, out.shape)};
+    if (out.is_float) out.f.resize((size_t)out.len()); else out.i.resize((size_t)out.len());
+    for_each_broadcast(out.shape, st, [&](int64_t i, const std::vector<int64_t> &o) {
+        if (out.is_float) {
+            const float x = a.f[(size_t)o[0]], y = b.f[(size_t)o[1]];
+            out.f[(size_t)i] = x != x ? x : (y != y ? y : ((is_min ? x <= y : x >= y) ? x : y));
+        } else {
+            const int64_t x = a.i[(size_t)o[0]], y = b.i[(size_t)o[1]];
+            out.i[(size_t)i] = (is_min ? x <= y : x >= y) ? x : y;
+        }
+    });
+    return true;
+}
+// variadic Min / Max: one operand is a copy, otherwise a left fold
+inline bool minmax_fold(bool is_min, const std::vector<const HostVal *> &v, HostVal &out) {
+    if (v.empty() || !v[0]) return false;
+    HostVal acc = *v[0];
+    for (size_t k = 1; k < v.size(); k++) {
+        if (!v[k]) return false;
+        HostVal next;
+        if (!minmax(is_min, acc, *v[k], next)) return false;
+        acc = std::move(next);
+    }
+    out = std::move(acc);
+    return true;
+}
+// Pad of a host value in constant mode (src/ops/pad.rs:34-108; exporters pad shape vectors): negative entries crop first
+inline bool pad_constant(const HostVal &x, const std::vector<int64_t> &pads, const HostVal *value, HostVal &out) {
+    if (value && (value->is_float != x.is_float || !value->shape.empty())) return false;
+    const PadGeometry g = pad_geometry(x.shape, pads, RTEN_HIP_PAD_CONSTANT);
+    const size_t nd = x.shape.size();
+    out = HostVal();
+    out.shape = g.out;
+    out.is_float = x.is_float;
+    if (out.len() > kMaxHostElems) return false;
+    const float ff = value && x.is_float ? value->f.at(0) : 0.f;
+    const int64_t fi = value && !x.is_float ? value->i.at(0) : 0;
+    if (out.is_float) out.f.assign((size_t)out.len(), ff); else out.i.assign((size_t)out.len(), fi);
+    std::vector<int64_t> xs(nd, 1), idx(nd, 0);
+    for (size_t d = nd; d-- > 1;) xs[d - 1] = xs[d] * x.shape[d];
+    for (int64_t e = 0, n = out.len(); e < n; e++) {
+        int64_t src = 0;
+        bool inside = true;
+        for (size_t d = 0; d < nd; d++) {
+            const int64_t s = idx[d] - pads[d]; // (a negative begin pad shifts into the cropped region)
+            const int64_t hi = x.shape[d] - std::max<int64_t>(-pads[nd + d], 0), lo = std::max<int64_t>(-pads[d], 0);
+            inside = inside && s >= lo && s < hi;
+            src += s * xs[d];
+        }
+        if (inside) { if (out.is_float) out.f[(size_t)e] = x.f[(size_t)src]; else out.i[(size_t)e] = x.i[(size_t)src]; }
+        for (size_t d = nd; d-- > 0;) { if (++idx[d] < out.shape[d]) break; idx[d] = 0; }
+    }
+    return true;
+}
 } // namespace hostops
 
 // ======================================================================================================== executor
@@ -849,6 +938,55 @@ class Graph {
     // What an InstanceNormalization / BatchNormalization / LogSoftmax node asks for, read as onnx_registry.rs:830-842,1254-1257,1289-1292 reads it.
     // BatchNormalization: training_mode != 0 and spatial != 1 are load errors that name the node, momentum is ignored, and a named output beyond Y
     // (running_mean, running_var, saved_mean, saved_var: training only, norm.rs:249-256) is refused like MaxPool's Indices.  Needs no device.
+    // What the loader reads from, and refuses about, a Pad / Pow node (make_pad_step / make_math_step; rten_hip_run --parse-only runs the same checks without a
+    // device).  `m` = the canonical model: an operand is a constant when an initializer carries its name, device data when it is a graph input.
+    struct PadNode {
+        int mode = RTEN_HIP_PAD_CONSTANT;
+        std::string mode_name = "constant";
+        bool attr_form = false;       // before opset 11: the pads / value attributes (onnx_registry.rs:1545-1552)
+        std::vector<int64_t> pads;
+        float value = 0.f;
+    };
+    static const onnx::TensorProto *initializer_named(const onnx::Model &m, const std::string &v) {
+        for (auto &t : m.initializers) if (t.name == v) return &t;
+        return nullptr;
+    }
+    static const onnx::ValueInfo *graph_input_named(const onnx::Model &m, const std::string &v) {
+        for (auto &gi : m.inputs) if (gi.name == v && !initializer_named(m, v)) return &gi;
+        return nullptr;
+    }
+    static PadNode read_pad_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        const std::string where = "Pad " + label + ": ";
+        PadNode a;
+        if (const onnx::Attr *ma = n.attr("mode")) if (!ma->s.empty()) a.mode_name = ma->s;
+        a.mode = pad_mode_of(a.mode_name);
+        if (a.mode < 0) throw GraphError(where + "mode \"" + a.mode_name + "\" is not supported (constant, reflect, edge, wrap)");
+        if (n.inputs.size() > 3 && !n.inputs[3].empty()) throw GraphError(where + "Pad operator does not yet support `axes` input");
+        if (const onnx::Attr *pa = n.attr("pads")) { a.attr_form = true; a.pads = pa->ints; a.value = n.get_float("value", 0.f); return a; }
+        if (n.inputs.size() < 2 || n.inputs[1].empty()) throw GraphError(where + "the pads input is missing");
+        if (graph_input_named(m, n.inputs[1]))
+            throw GraphError(where + "pads must be a constant or computable from the input shapes (it is the graph input \"" + n.inputs[1] + "\", device data at run time)");
+        if (n.inputs.size() > 2 && !n.inputs[2].empty() && graph_input_named(m, n.inputs[2]))
+            throw GraphError(where + "constant_value must be a constant or computable from the input shapes (it is the graph input \"" + n.inputs[2] + "\", device data at run time)");
+        return a;
+    }
+    // Pow: the reference's int32-base forms are not built; a base whose element type the model states (an initializer or a graph input) is refused at load
+    static void check_pow_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        if (n.inputs.empty()) return;
+        int et = 0;
+        if (const onnx::TensorProto *t = initializer_named(m, n.inputs[0])) et = t->data_type;
+        else if (const onnx::ValueInfo *gi = graph_input_named(m, n.inputs[0])) et = gi->elem_type;
+        if (et == onnx::INT32 || et == onnx::INT64) throw GraphError("Pow " + label + ": an int32 base is not supported by the device path (float32 base and exponent only)");
+    }
+    static bool is_math_kind(const std::string &k) {
+        static const std::set<std::string> kinds = {"Neg", "Abs", "Sign", "Floor", "Ceil", "Round", "Sqrt", "Reciprocal", "Exp", "Log", "Softplus", "Pow", "PRelu", "Min", "Max", "Sum", "Mean"};
+        return kinds.count(k) != 0;
+    }
+    // hostable: evaluated on the host when every operand is a host value
+    static bool is_hostable_math_kind(const std::string &k) {
+        static const std::set<std::string> kinds = {"Neg", "Abs", "Sign", "Floor", "Ceil", "Round", "Sqrt", "Reciprocal", "Min", "Max"};
+        return kinds.count(k) != 0;
+    }
     struct NormNode {
         std::optional<float> epsilon; // absent: the operator's default (1e-5)
         int axis = -1;                // LogSoftmax
@@ -2066,6 +2204,8 @@ class Graph {
             else if (kind == "Split") make_split_step(st, n);
             else if (kind == "GRU" || kind == "LSTM") make_rnn_step(st, n);
             else if (kind == "InstanceNormalization" || kind == "BatchNormalization" || kind == "LogSoftmax") make_norm_step(st, n, nodes, out_name);
+            else if (is_math_kind(kind)) make_math_step(st, n, m);
+            else if (kind == "Pad") make_pad_step(st, n, m);
             else if (kind == "Flatten" || kind == "Reshape" || kind == "Squeeze" || kind == "Unsqueeze" || kind == "Identity" || kind == "Dropout") make_view_step(st, n);
             else if (make_layout_step(st, n)) {
                 // Shape / ConstantOfShape / NonZero / Range / Slice / Concat / Expand / Where / comparisons / logic / integer arithmetic / Cast / Gather /
@@ -2394,6 +2534,54 @@ class Graph {
             op->act = act;
             run_plainly(st, op);
         }
+    }
+
+    // Neg / Abs / Sign / Floor / Ceil / Round / Sqrt / Reciprocal / Min / Max: on the host when every operand is a host value (shape arithmetic: exporters
+    // write F.interpolate(scale_factor=..) as Shape -> Cast -> Mul -> Floor -> Cast, attention scaling as Sqrt(Cast(Shape[-1]))), on the device otherwise.
+    // Exp / Log / Softplus / Pow / PRelu / Sum / Mean run on the device always: a host value's device copy is the operand and the result carries no host value.
+    void make_math_step(Step &st, const onnx::Node &n, const onnx::Model &m) {
+        const std::string kind = n.op_type;
+        if (kind == "Pow") check_pow_node(m, n, st.name);
+        static const OpRegistry reg = OpRegistry::with_all_ops();
+        std::shared_ptr<Operator> op(reg.create(kind).release());
+        if (!is_hostable_math_kind(kind)) { run_plainly(st, op); return; }
+        if (kind == "Min" || kind == "Max")
+            make_hostable(st, [kind](const std::vector<const HostVal *> &v, HostVal &out) { return hostops::minmax_fold(kind == "Min", v, out); },
+                          [op](Context &c, const InputList &in) { return op->run(c, in); });
+        else
+            make_hostable(st, [kind](const std::vector<const HostVal *> &v, HostVal &out) { return v.size() == 1 && v[0] && hostops::unary(kind, *v[0], out); },
+                          [op](Context &c, const InputList &in) { return op->run(c, in); });
+    }
+
+    // Pad: read_pad_node's checks at load; before opset 11 the pads / value attributes, otherwise pads and constant_value are host values at run time
+    // (constants or shape arithmetic), read as Slice reads its starts: nothing is read back, the step is one rten_hip_pad_b32 launch and capture-safe.  A
+    // host-valued operand in constant mode is padded on the host (exporters pad shape vectors).  A pad or crop of dim 0 couples the batch rows (sub-batch
+    // chains split dim 0).
+    void make_pad_step(Step &st, const onnx::Node &n, const onnx::Model &m) {
+        const std::string nm = st.name;
+        const PadNode a = read_pad_node(m, n, nm);
+        auto cache = std::make_shared<HostCache>();
+        st.run = [this, nm, a, cache](Context &c, const InputList &in) {
+            const Tensor &x = require(in, 0);
+            const std::vector<int64_t> pads = a.attr_form ? a.pads : host_ints(&require(in, 1), "Pad: pads");
+            const Tensor *value = a.attr_form ? nullptr : get(in, 2);
+            if (value && !value->host()) throw OpError(OpError::UnsupportedValue, "Pad: constant_value must be a constant or computable from the input shapes (it depends on device data)");
+            const size_t nd = (size_t)x.ndim();
+            if (nd > 0 && pads.size() == 2 * nd && (pads[0] != 0 || pads[nd] != 0) && runtime_coupled_.empty()) runtime_coupled_ = "Pad \"" + nm + "\" (pads or crops dim 0)";
+            OutputList o;
+            if (x.host() && a.mode == RTEN_HIP_PAD_CONSTANT) {
+                HostVal attr_fill, out;
+                attr_fill.is_float = x.host()->is_float;
+                if (attr_fill.is_float) attr_fill.f = {a.value}; else attr_fill.i = {(int64_t)a.value};
+                if (hostops::pad_constant(*x.host(), pads, a.attr_form ? &attr_fill : (value ? value->host() : nullptr), out)) { o.push_back(materialize(c, std::move(out), *cache)); return o; }
+            }
+            uint32_t fill_bits = 0;
+            if (!a.attr_form) fill_bits = Pad::fill_word(x, value);
+            else if (x.dtype() == DType::F32) std::memcpy(&fill_bits, &a.value, 4);
+            else fill_bits = (uint32_t)(int32_t)a.value;
+            o.push_back(pad_tensor(c, x, pads, a.mode, fill_bits));
+            return o;
+        };
     }
 
     // ArgMax / ArgMin, TopK and Softmax: one axis each, noted per run in case it resolves to dim 0

@@ -1621,6 +1621,228 @@ struct Where : Operator { // binary_elementwise.rs:1189-1280: cond != 0 ? x : y,
     }
 };
 
+// ------------------------------------------------------------------------------------------------ unary math, Pow, PRelu, variadic Min / Max / Sum / Mean, Pad
+// Neg, Abs, Sign, Floor, Ceil, Round, Sqrt, Reciprocal, Exp, Log, Softplus (src/ops/unary_elementwise.rs): float32 through rten_hip_unary_f32 (`code`, one kernel
+// instantiation per operator); the operators the reference also defines for int32 (Neg, Abs, Sign) through `int_code` of rten_hip_elementwise_nd.
+struct UnaryMath : Operator {
+    const char *nm;
+    int code, int_code;
+    UnaryMath(const char *n, int c, int ic = -1) : nm(n), code(c), int_code(ic) {}
+    const char *name() const override { return nm; }
+    int max_inputs() const override { return 1; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0);
+        OutputList out;
+        if (int_code >= 0 && x.dtype() == DType::I32) {
+            Tensor y(ctx, x.shape(), DType::I32);
+            const int64_t n = x.len(), one = 1;
+            if (n) ctx.check(rten_hip_elementwise_nd(ctx.raw(), int_code, 1, &n, x.ptr(), RTEN_HIP_DT_I32, &one, nullptr, 0, nullptr, nullptr, nullptr, y.ptr(), RTEN_HIP_DT_I32));
+            y.set_uniform_dims(x.uniform_dims());
+            out.push_back(std::move(y));
+            return out;
+        }
+        if (int_code >= 0 && x.dtype() != DType::F32) throw OpError(OpError::UnsupportedType, "");
+        want(x, DType::F32, "float32");
+        Tensor y(ctx, x.shape(), DType::F32);
+        if (x.len()) ctx.check(rten_hip_unary_f32(ctx.raw(), code, x.len(), (const float *)x.ptr(), (float *)y.ptr()));
+        y.set_uniform_dims(x.uniform_dims());
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+struct Neg : UnaryMath { Neg() : UnaryMath("Neg", RTEN_HIP_UNARY_NEG, RTEN_HIP_EW_INEG) {} };
+struct Abs : UnaryMath { Abs() : UnaryMath("Abs", RTEN_HIP_UNARY_ABS, RTEN_HIP_EW_IABS) {} };
+struct Sign : UnaryMath { Sign() : UnaryMath("Sign", RTEN_HIP_UNARY_SIGN, RTEN_HIP_EW_ISIGN) {} }; // Rust signum: +0 -> 1, -0 -> -1, NaN -> NaN
+struct Floor : UnaryMath { Floor() : UnaryMath("Floor", RTEN_HIP_UNARY_FLOOR) {} };
+struct Ceil : UnaryMath { Ceil() : UnaryMath("Ceil", RTEN_HIP_UNARY_CEIL) {} };
+struct Round : UnaryMath { Round() : UnaryMath("Round", RTEN_HIP_UNARY_ROUND) {} }; // round_ties_even
+struct Sqrt : UnaryMath { Sqrt() : UnaryMath("Sqrt", RTEN_HIP_UNARY_SQRT) {} };
+struct Reciprocal : UnaryMath { Reciprocal() : UnaryMath("Reciprocal", RTEN_HIP_UNARY_RECIPROCAL) {} };
+struct Exp : UnaryMath { Exp() : UnaryMath("Exp", RTEN_HIP_UNARY_EXP) {} };
+struct Log : UnaryMath { Log() : UnaryMath("Log", RTEN_HIP_UNARY_LOG) {} };                // the float64 logarithm rounded once (docs/KERNELS.md 4.8)
+struct Softplus : UnaryMath { Softplus() : UnaryMath("Softplus", RTEN_HIP_UNARY_SOFTPLUS) {} };
+
+// y = op(a, b) with numpy broadcasting and the operand order kept: float32 through rten_hip_binary_broadcast_f32 (`f32_op`), int32 through
+// rten_hip_elementwise_nd (`i32_op`); both operands have the same 4-byte type
+inline Tensor broadcast_binary(Context &ctx, const Tensor &a, const Tensor &b, int f32_op, int i32_op) {
+    const Broadcast bc = broadcast_shapes({&a.shape(), &b.shape()});
+    Tensor y(ctx, bc.shape, a.dtype());
+    if (y.len()) {
+        if (a.dtype() == DType::F32)
+            ctx.check(rten_hip_binary_broadcast_f32(ctx.raw(), f32_op, (int32_t)bc.shape.size(), bc.shape.data(), bc.strides[0].data(), bc.strides[1].data(), (const float *)a.ptr(),
+                                                    (const float *)b.ptr(), (float *)y.ptr()));
+        else
+            ctx.check(rten_hip_elementwise_nd(ctx.raw(), i32_op, (int32_t)bc.shape.size(), bc.shape.data(), a.ptr(), RTEN_HIP_DT_I32, bc.strides[0].data(), b.ptr(), RTEN_HIP_DT_I32,
+                                              bc.strides[1].data(), nullptr, nullptr, y.ptr(), RTEN_HIP_DT_I32));
+    }
+    y.set_uniform_dims(uniform_after_broadcast({&a, &b}, bc.shape));
+    return y;
+}
+
+// Pow (src/ops/binary_elementwise.rs:958-1117), float32 base and exponent: exponent 2 -> x * x, 3 -> x * x * x, tested per element; anything else the float64
+// pow rounded once.  The reference's int32-base forms are not built.
+struct Pow : Operator {
+    const char *name() const override { return "Pow"; }
+    int max_inputs() const override { return 2; }
+    static void check_types(DType base, DType exponent) {
+        if (base == DType::I32 && (exponent == DType::F32 || exponent == DType::I32)) throw OpError(OpError::UnsupportedValue, "Pow: int32 base is not supported by the device path");
+        if (base != DType::F32 || exponent != DType::F32) throw OpError(OpError::UnsupportedValue, "Unsupported base and exponent type combination");
+    }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &base = require(in, 0), &exponent = require(in, 1);
+        check_types(base.dtype(), exponent.dtype());
+        OutputList out;
+        out.push_back(broadcast_binary(ctx, base, exponent, 6, 0));
+        return out;
+    }
+};
+
+// PRelu (src/ops/unary_elementwise.rs:624-671): x < 0 ? slope * x : x; the slope broadcasts to x's shape only
+struct PRelu : Operator {
+    const char *name() const override { return "PRelu"; }
+    int max_inputs() const override { return 2; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0);
+        if (x.dtype() != DType::F32) throw OpError(OpError::UnsupportedType, "");
+        const Tensor &slope = want(require(in, 1), DType::F32, "float32");
+        bool ok = slope.ndim() <= x.ndim();
+        for (int i = 0; ok && i < slope.ndim(); i++) {
+            const int64_t sd = slope.size(slope.ndim() - 1 - i);
+            ok = sd == 1 || sd == x.size(x.ndim() - 1 - i);
+        }
+        if (!ok) throw OpError(OpError::IncompatibleInputShapes, "Slope is not broadcastable to input shape");
+        OutputList out;
+        out.push_back(broadcast_binary(ctx, x, slope, 7, 0));
+        return out;
+    }
+};
+
+// Min / Max / Sum / Mean (src/ops/variadic_elementwise.rs:21-39): one input is a copy, otherwise a left fold of the binary operator.  Min / Max follow
+// cmp_nan_less / cmp_nan_greater (reduce.rs:847-873): a NaN in either operand wins, a tie keeps the left operand.
+struct Variadic : Operator {
+    const char *nm;
+    int f32_op, i32_op; // i32_op < 0: float32 only (Mean)
+    Variadic(const char *n, int f, int i) : nm(n), f32_op(f), i32_op(i) {}
+    const char *name() const override { return nm; }
+    Tensor fold(Context &ctx, const InputList &in) const {
+        const Tensor &first = require(in, 0);
+        if (i32_op < 0) want(first, DType::F32, "float32");
+        else if (first.dtype() != DType::F32 && first.dtype() != DType::I32) throw OpError(OpError::UnsupportedType, "");
+        std::vector<const Tensor *> ts;
+        for (const Tensor *t : in)
+            if (t) ts.push_back(&want(*t, first.dtype(), first.dtype() == DType::F32 ? "float32" : "int32"));
+        if (ts.size() == 1) {
+            Tensor y(ctx, first.shape(), first.dtype());
+            if (first.bytes()) ctx.check(rten_hip_memcpy_d2d(ctx.raw(), y.ptr(), first.ptr(), first.bytes()));
+            y.set_uniform_dims(first.uniform_dims());
+            return y;
+        }
+        Tensor acc = broadcast_binary(ctx, *ts[0], *ts[1], f32_op, i32_op);
+        for (size_t k = 2; k < ts.size(); k++) acc = broadcast_binary(ctx, acc, *ts[k], f32_op, i32_op);
+        return acc;
+    }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        OutputList out;
+        out.push_back(fold(ctx, in));
+        return out;
+    }
+};
+struct Min : Variadic { Min() : Variadic("Min", 4, RTEN_HIP_EW_IMIN) {} };
+struct Max : Variadic { Max() : Variadic("Max", 5, RTEN_HIP_EW_IMAX) {} };
+struct Sum : Variadic { Sum() : Variadic("Sum", 0, RTEN_HIP_EW_IADD) {} };
+// Mean: the sum DIVIDED by n as f32 (variadic_elementwise.rs:98-102), through the Div kernel.  The divisor is a one-element device constant made on the
+// first run (an upload: the warm-up run that precedes every capture makes it, a captured run finds it).
+struct Mean : Variadic {
+    Mean() : Variadic("Mean", 0, -1) {}
+    OutputList run(Context &ctx, const InputList &in) const override {
+        Tensor total = fold(ctx, in);
+        size_t n = 0;
+        for (const Tensor *t : in) n += t != nullptr;
+        if (!divisor_ || divisor_n_ != n || divisor_ctx_ != &ctx) {
+            if (rten_hip_capture_active(ctx.raw())) throw OpError(OpError::UnsupportedValue, "Mean: the divisor must be uploaded before the run is captured");
+            const float d = (float)n;
+            divisor_ = std::make_shared<Tensor>(Tensor::from_host<float>(ctx, {}, &d));
+            divisor_n_ = n;
+            divisor_ctx_ = &ctx;
+        }
+        if (total.len()) ctx.check(rten_hip_div_f32(ctx.raw(), total.len(), (const float *)total.ptr(), (const float *)divisor_->ptr(), 1, (float *)total.ptr()));
+        OutputList out;
+        out.push_back(std::move(total));
+        return out;
+    }
+  private:
+    mutable std::shared_ptr<Tensor> divisor_;
+    mutable size_t divisor_n_ = 0;
+    mutable const Context *divisor_ctx_ = nullptr;
+};
+
+// Pad (src/ops/pad.rs).  pad_geometry: the reference's checks on a shape (pad.rs:41-124) -> the output shape; `copy` = the output equals the cropped input.
+struct PadGeometry { std::vector<int64_t> out; bool copy = false; };
+inline PadGeometry pad_geometry(const std::vector<int64_t> &shape, const std::vector<int64_t> &pads, int mode) {
+    const size_t nd = shape.size();
+    if (pads.size() != 2 * nd) throw OpError(OpError::InvalidValue, "padding length should be 2 * input dims");
+    std::vector<int64_t> cropped = shape;
+    for (size_t d = 0; d < nd; d++) {
+        const int64_t crop = std::max<int64_t>(-pads[d], 0) + std::max<int64_t>(-pads[nd + d], 0);
+        if (crop > shape[d]) throw OpError(OpError::InvalidValue, "Negative pads remove more elements than axis contains");
+        cropped[d] = shape[d] - crop;
+    }
+    PadGeometry g;
+    for (size_t d = 0; d < nd; d++) g.out.push_back(std::max<int64_t>(pads[d], 0) + cropped[d] + std::max<int64_t>(pads[nd + d], 0));
+    g.copy = g.out == cropped;
+    if (!g.copy && mode != RTEN_HIP_PAD_CONSTANT) {
+        const size_t batch = nd > 2 ? nd - 2 : 0;
+        for (size_t d = 0; d < batch; d++)
+            if (g.out[d] != cropped[d]) throw OpError(OpError::UnsupportedValue, "Pad only supports non-constant padding of last 2 dims");
+        for (size_t d = batch; d < nd; d++)
+            if (cropped[d] == 0) throw OpError(OpError::InvalidValue, "Padded dimension for non-constant padding is empty");
+    }
+    return g;
+}
+inline int pad_mode_of(const std::string &s) { // -1: unknown
+    return s == "constant" ? RTEN_HIP_PAD_CONSTANT : s == "reflect" ? RTEN_HIP_PAD_REFLECT : s == "edge" ? RTEN_HIP_PAD_EDGE : s == "wrap" ? RTEN_HIP_PAD_WRAP : -1;
+}
+// One rten_hip_pad_b32 launch; `fill_bits` = the constant value's word
+inline Tensor pad_tensor(Context &ctx, const Tensor &x, const std::vector<int64_t> &pads, int mode, uint32_t fill_bits) {
+    if (dtype_size(x.dtype()) != 4) throw OpError(OpError::UnsupportedType, "");
+    const PadGeometry g = pad_geometry(x.shape(), pads, mode);
+    if (x.ndim() > 6) throw OpError(OpError::UnsupportedValue, "Pad of more than 6 dims is not supported by the device path");
+    Tensor y(ctx, g.out, x.dtype());
+    if (y.len()) ctx.check(rten_hip_pad_b32(ctx.raw(), mode, x.ndim(), x.shape().data(), pads.data(), fill_bits, x.ptr(), y.ptr()));
+    return y;
+}
+// Inputs (data, pads, constant_value, axes).  pads and the constant value are read from their host values when they carry one (constants, shape
+// arithmetic) and read back from the device otherwise (the graph executor refuses that case before it gets here: a read-back cannot be captured).
+struct Pad : Operator {
+    int mode = RTEN_HIP_PAD_CONSTANT;
+    const char *name() const override { return "Pad"; }
+    int max_inputs() const override { return 4; }
+    static uint32_t fill_word(const Tensor &x, const Tensor *value) {
+        if (!value) return 0;
+        if (value->dtype() != x.dtype()) throw OpError(OpError::InputCastFailed, x.dtype() == DType::F32 ? "expected float32 tensor" : "expected int32 tensor");
+        if (value->ndim() != 0) throw OpError(OpError::InputCastFailed, "expected tensor with 0 dims");
+        uint32_t w = 0;
+        if (const HostVal *h = value->host()) {
+            if (h->is_float) std::memcpy(&w, &h->f.at(0), 4); else w = (uint32_t)(int32_t)h->i.at(0);
+        } else {
+            const std::vector<int32_t> v = value->to_host<int32_t>(); // (the raw word of either type)
+            w = (uint32_t)v.at(0);
+        }
+        return w;
+    }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0), &p = want(require(in, 1), DType::I32, "int32");
+        if (get(in, 3)) throw OpError(OpError::UnsupportedValue, "Pad operator does not yet support `axes` input");
+        if (p.ndim() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 1 dims");
+        std::vector<int64_t> pads;
+        if (p.host()) pads = p.host()->i;
+        else for (int32_t v : p.to_host<int32_t>()) pads.push_back(v);
+        OutputList out;
+        out.push_back(pad_tensor(ctx, x, pads, mode, fill_word(x, get(in, 2))));
+        return out;
+    }
+};
+
 // Expand (src/ops/layout.rs:177-262): numpy broadcast of x against `shape` (the values of the second input, which the host must know)
 inline Tensor expand_to(Context &ctx, const Tensor &x, const std::vector<int64_t> &target) {
     if (dtype_size(x.dtype()) != 4) throw OpError(OpError::UnsupportedType, "");
@@ -2616,6 +2838,24 @@ class OpRegistry {
         r.register_op<TopK>("TopK");
         r.register_op<GRU>("GRU");
         r.register_op<LSTM>("LSTM");
+        r.register_op<Neg>("Neg");
+        r.register_op<Abs>("Abs");
+        r.register_op<Sign>("Sign");
+        r.register_op<Floor>("Floor");
+        r.register_op<Ceil>("Ceil");
+        r.register_op<Round>("Round");
+        r.register_op<Sqrt>("Sqrt");
+        r.register_op<Reciprocal>("Reciprocal");
+        r.register_op<Exp>("Exp");
+        r.register_op<Log>("Log");
+        r.register_op<Softplus>("Softplus");
+        r.register_op<Pow>("Pow");
+        r.register_op<PRelu>("PRelu");
+        r.register_op<Min>("Min");
+        r.register_op<Max>("Max");
+        r.register_op<Sum>("Sum");
+        r.register_op<Mean>("Mean");
+        r.register_op<Pad>("Pad");
         return r;
     }
 

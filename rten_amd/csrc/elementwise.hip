@@ -74,14 +74,45 @@ __global__ __launch_bounds__(EW_THREADS) void activation_kernel(int64_t n, const
     }
 }
 
-enum BinaryOp { B_ADD, B_MUL, B_SUB, B_DIV };
+enum BinaryOp { B_ADD, B_MUL, B_SUB, B_DIV, B_MIN, B_MAX, B_POW, B_PRELU };
 
+// Min / Max: cmp_nan_less / cmp_nan_greater (reduce.rs:847-873) -- a NaN in either operand wins (a's first), a tie keeps a.  Pow: FastPow<f32> for f32
+// (binary_elementwise.rs:977-987), the exponent tested per element; the general case is the float64 pow rounded once (the reference calls libm's powf).
 template <int OP>
 __device__ __forceinline__ float binary(float a, float b) {
     if constexpr (OP == B_ADD) return a + b;
     else if constexpr (OP == B_MUL) return a * b;
     else if constexpr (OP == B_SUB) return a - b;
-    else return a / b;
+    else if constexpr (OP == B_DIV) return a / b;
+    else if constexpr (OP == B_MIN) return a != a ? a : (b != b ? b : (a <= b ? a : b));
+    else if constexpr (OP == B_MAX) return a != a ? a : (b != b ? b : (a >= b ? a : b));
+    else if constexpr (OP == B_POW) {
+        if (b == 2.0f) return a * a;
+        if (b == 3.0f) return a * a * a;
+        return (float)pow((double)a, (double)b);
+    } else return a < 0.f ? b * a : a; // PRelu(x = a, slope = b)
+}
+
+// y = op(a, b[0]) over a dense `a`: the scalar rides in an SGPR (Pow's 2 / 3 / general branch is uniform), 16 B per lane when a and y are aligned
+template <int OP>
+__global__ __launch_bounds__(EW_THREADS) void binary_scalar_kernel(int64_t n, const float *__restrict__ a, const float *__restrict__ b,
+                                                                   float *__restrict__ y, int vec) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const float bv = b[0];
+    if (vec) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = tid; i < n4; i += stride) {
+            f32x4 va = reinterpret_cast<const f32x4 *>(a)[i];
+            f32x4 r;
+#pragma unroll
+            for (int k = 0; k < 4; k++) r[k] = binary<OP>(va[k], bv);
+            reinterpret_cast<f32x4 *>(y)[i] = r;
+        }
+        for (int64_t i = (n4 << 2) + tid; i < n; i += stride) y[i] = binary<OP>(a[i], bv);
+    } else {
+        for (int64_t i = tid; i < n; i += stride) y[i] = binary<OP>(a[i], bv);
+    }
 }
 
 template <int OP>
@@ -271,8 +302,8 @@ RTEN_EXPORT int32_t rten_hip_div_f32(rten_hip_ctx *ctx, int64_t n, const float *
 RTEN_EXPORT int32_t rten_hip_binary_broadcast_f32(rten_hip_ctx *ctx, int32_t op, int32_t ndim, const int64_t *out_shape, const int64_t *a_strides,
                                                   const int64_t *b_strides, const float *a, const float *b, float *y) {
     RTEN_CHECK_CTX(ctx);
-    if (op < 0 || op > 3 || ndim < 0 || ndim > 6 || (ndim && (!out_shape || !a_strides || !b_strides)))
-        return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "binary_broadcast: op in 0..3, at most 6 dims");
+    if (op < 0 || op > 7 || ndim < 0 || ndim > 6 || (ndim && (!out_shape || !a_strides || !b_strides)))
+        return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "binary_broadcast: op in 0..7, at most 6 dims");
     NdArgs p = {};
     p.ndim = ndim;
     p.n = 1;
@@ -285,7 +316,31 @@ RTEN_EXPORT int32_t rten_hip_binary_broadcast_f32(rten_hip_ctx *ctx, int32_t op,
     if (!a || !b || !y) return RTEN_HIP_ERR_INVALID_VALUE;
     ProfScope ps(ctx, "binary_broadcast_f32", 0.0, 12.0 * p.n);
     const dim3 grid(ew_blocks(p.n)), block(EW_THREADS);
-    if (op == 0) hipLaunchKernelGGL((binary_bcast_kernel<B_ADD>), grid, block, 0, ctx->stream, p, a, b, y);
+    if (op >= 4) {
+        // dense `a` with a dense or one-element `b`: the flat kernels (same element function, no index decomposition)
+        bool a_dense = true, b_dense = true, b_scalar = true;
+        int64_t acc = 1;
+        for (int d = ndim - 1; d >= 0; d--) {
+            if (p.shape[d] != 1) {
+                a_dense = a_dense && a_strides[d] == acc;
+                b_dense = b_dense && b_strides[d] == acc;
+                b_scalar = b_scalar && b_strides[d] == 0;
+            }
+            acc *= p.shape[d];
+        }
+        const int mode = !a_dense ? 0 : (b_dense ? 1 : (b_scalar ? 2 : 0));
+        const int vec = al16(a) && al16(y) && (mode == 2 || al16(b));
+        const dim3 fgrid(ew_blocks(vec ? p.n / 4 : p.n));
+#define RTEN_BCAST_CASE(K)                                                                                                          \
+    if (mode == 1) hipLaunchKernelGGL((binary_kernel<K>), fgrid, block, 0, ctx->stream, p.n, a, b, p.n, y, vec);                    \
+    else if (mode == 2) hipLaunchKernelGGL((binary_scalar_kernel<K>), fgrid, block, 0, ctx->stream, p.n, a, b, y, vec);             \
+    else hipLaunchKernelGGL((binary_bcast_kernel<K>), grid, block, 0, ctx->stream, p, a, b, y);
+        if (op == 4) { RTEN_BCAST_CASE(B_MIN) }
+        else if (op == 5) { RTEN_BCAST_CASE(B_MAX) }
+        else if (op == 6) { RTEN_BCAST_CASE(B_POW) }
+        else { RTEN_BCAST_CASE(B_PRELU) }
+#undef RTEN_BCAST_CASE
+    } else if (op == 0) hipLaunchKernelGGL((binary_bcast_kernel<B_ADD>), grid, block, 0, ctx->stream, p, a, b, y);
     else if (op == 1) hipLaunchKernelGGL((binary_bcast_kernel<B_MUL>), grid, block, 0, ctx->stream, p, a, b, y);
     else if (op == 2) hipLaunchKernelGGL((binary_bcast_kernel<B_SUB>), grid, block, 0, ctx->stream, p, a, b, y);
     else hipLaunchKernelGGL((binary_bcast_kernel<B_DIV>), grid, block, 0, ctx->stream, p, a, b, y);
@@ -442,6 +497,12 @@ __global__ __launch_bounds__(EW_THREADS) void generic_nd_kernel(const GenArgs p,
             else out.i = af ? gen_f2i(va.f, -128.f, 127.f, -128, 127) : (int)(int8_t)(va.i & 0xff);
         } else if (p.op == RTEN_HIP_EW_NOT) {
             out.i = va.i == 0;
+        } else if (p.op == RTEN_HIP_EW_INEG) {
+            out.i = (int)(0u - (unsigned)va.i); // wrapping: i32::MIN stays
+        } else if (p.op == RTEN_HIP_EW_IABS) {
+            out.i = va.i < 0 ? (int)(0u - (unsigned)va.i) : va.i;
+        } else if (p.op == RTEN_HIP_EW_ISIGN) {
+            out.i = (va.i > 0) - (va.i < 0);
         } else if (p.op == RTEN_HIP_EW_WHERE) {
             out.i = va.i != 0 ? ((const int32_t *)b)[bo] : ((const int32_t *)c)[co]; // (4-byte payloads moved as raw words)
         } else {
@@ -459,6 +520,8 @@ __global__ __launch_bounds__(EW_THREADS) void generic_nd_kernel(const GenArgs p,
             case RTEN_HIP_EW_IADD: out.i = (int)((unsigned)va.i + (unsigned)vb.i); break;
             case RTEN_HIP_EW_ISUB: out.i = (int)((unsigned)va.i - (unsigned)vb.i); break;
             case RTEN_HIP_EW_IMUL: out.i = (int)((unsigned)va.i * (unsigned)vb.i); break;
+            case RTEN_HIP_EW_IMIN: out.i = va.i <= vb.i ? va.i : vb.i; break;
+            case RTEN_HIP_EW_IMAX: out.i = va.i >= vb.i ? va.i : vb.i; break;
             default: out.i = vb.i == 0 ? 0 : (va.i == (int)0x80000000 && vb.i == -1 ? va.i : va.i / vb.i); break; // IDIV (the host refuses a constant zero divisor)
             }
         }
@@ -495,9 +558,9 @@ __global__ __launch_bounds__(EW_THREADS) void copy_rows_kernel(int64_t rows, int
 RTEN_EXPORT int32_t rten_hip_elementwise_nd(rten_hip_ctx *ctx, int32_t op, int32_t ndim, const int64_t *shape, const void *a, int32_t a_dtype, const int64_t *a_strides,
                                             const void *b, int32_t b_dtype, const int64_t *b_strides, const void *c, const int64_t *c_strides, void *y, int32_t y_dtype) {
     RTEN_CHECK_CTX(ctx);
-    if (op < RTEN_HIP_EW_CAST || op > RTEN_HIP_EW_IDIV || ndim < 0 || ndim > 6 || (ndim && (!shape || !a_strides)))
+    if (op < RTEN_HIP_EW_CAST || op > RTEN_HIP_EW_IMAX || ndim < 0 || ndim > 6 || (ndim && (!shape || !a_strides)))
         return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "elementwise_nd: unknown op / more than 6 dims");
-    const bool unary = op == RTEN_HIP_EW_CAST || op == RTEN_HIP_EW_NOT, where = op == RTEN_HIP_EW_WHERE;
+    const bool unary = op == RTEN_HIP_EW_CAST || op == RTEN_HIP_EW_NOT || (op >= RTEN_HIP_EW_INEG && op <= RTEN_HIP_EW_ISIGN), where = op == RTEN_HIP_EW_WHERE;
     auto dt_ok = [](int32_t d) { return d >= RTEN_HIP_DT_F32 && d <= RTEN_HIP_DT_I8; };
     if (!dt_ok(a_dtype) || !dt_ok(y_dtype) || (!unary && !where && !dt_ok(b_dtype))) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "elementwise_nd: unknown element type");
     if (op == RTEN_HIP_EW_CAST) {

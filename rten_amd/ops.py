@@ -1115,6 +1115,259 @@ class Div(_Binary):
     fn, opcode, commutative = "rten_hip_div_f32", 3, False
 
 
+# ------------------------------------------------------------------------------------------ unary math, Pow, PRelu, variadic, Pad
+def _i64(v):
+    return (C.c_int64 * max(len(v), 1))(*[int(a) for a in v])
+
+
+class _UnaryMath(Operator):
+    """src/ops/unary_elementwise.rs: float32 through rten_hip_unary_f32 (one kernel instantiation per operator); the operators the reference also
+    defines for int32 (Neg, Abs, Sign) through an RTEN_HIP_EW_* code of rten_hip_elementwise_nd."""
+    code = -1
+    int_code = None
+
+    def max_inputs(self):
+        return 1
+
+    def run(self, ctx, inputs, in_place=False):
+        x = _require(inputs, 0)
+        if x.dtype == np.int32 and self.int_code is not None:
+            y = x if in_place else DeviceTensor(ctx, x.shape, np.int32)
+            if x.size:
+                ctx.call("rten_hip_elementwise_nd", self.int_code, 1, _i64([x.size]), x.vp, L.DT_I32, _i64([1]), None, L.DT_I32, None, None, None, y.vp, L.DT_I32)
+            return [y]
+        if self.int_code is not None and x.dtype != np.float32:
+            raise UnsupportedType
+        _want(x, np.float32)
+        y = x if in_place else DeviceTensor(ctx, x.shape, np.float32)
+        ctx.call("rten_hip_unary_f32", self.code, x.size, x.vp, y.vp)
+        return [y]
+
+
+class Neg(_UnaryMath):
+    code, int_code = L.UNARY_NEG, L.EW_INEG
+
+
+class Abs(_UnaryMath):
+    code, int_code = L.UNARY_ABS, L.EW_IABS
+
+
+class Sign(_UnaryMath):
+    """Rust signum: +0 -> 1, -0 -> -1, NaN -> NaN (float32); -1 / 0 / 1 (int32)."""
+    code, int_code = L.UNARY_SIGN, L.EW_ISIGN
+
+
+class Floor(_UnaryMath):
+    code = L.UNARY_FLOOR
+
+
+class Ceil(_UnaryMath):
+    code = L.UNARY_CEIL
+
+
+class Round(_UnaryMath):
+    """round_ties_even"""
+    code = L.UNARY_ROUND
+
+
+class Sqrt(_UnaryMath):
+    code = L.UNARY_SQRT
+
+
+class Reciprocal(_UnaryMath):
+    code = L.UNARY_RECIPROCAL
+
+
+class Exp(_UnaryMath):
+    """rten-vecmath/src/exp.rs:59-132, bit-identical"""
+    code = L.UNARY_EXP
+
+
+class Log(_UnaryMath):
+    """The float64 logarithm rounded once (the reference calls the host's logf: docs/KERNELS.md 4.8)."""
+    code = L.UNARY_LOG
+
+
+class Softplus(_UnaryMath):
+    """exp(x).ln_1p() with exp(x) rounded to float32, each step the float64 function rounded once."""
+    code = L.UNARY_SOFTPLUS
+
+
+def _expanded_strides(shape, nd):
+    sh, st, acc = (1,) * (nd - len(shape)) + tuple(shape), [0] * nd, 1
+    for i in range(nd - 1, -1, -1):
+        st[i] = 0 if sh[i] == 1 else acc
+        acc *= sh[i]
+    return st
+
+
+def _broadcast_launch(ctx, a, b, f32_op, i32_op):
+    """y = op(a, b) with numpy broadcasting, operand order kept: float32 through rten_hip_binary_broadcast_f32 (`f32_op`), int32 through
+    rten_hip_elementwise_nd (`i32_op`)."""
+    bshape = _broadcast_shapes(a.shape, b.shape)
+    if bshape is None:
+        raise IncompatibleInputShapes("Cannot broadcast inputs")
+    nd = len(bshape)
+    if nd > 6:
+        raise UnsupportedValue("broadcasting over more than 6 dims is not supported by the device path")
+    y = DeviceTensor(ctx, bshape, a.dtype)
+    if y.size:
+        sa, sb = _i64(_expanded_strides(a.shape, nd)), _i64(_expanded_strides(b.shape, nd))
+        if a.dtype == np.float32:
+            ctx.call("rten_hip_binary_broadcast_f32", f32_op, nd, _i64(list(bshape)), sa, sb, a.vp, b.vp, y.vp)
+        else:
+            ctx.call("rten_hip_elementwise_nd", i32_op, nd, _i64(list(bshape)), a.vp, L.DT_I32, sa, b.vp, L.DT_I32, sb, None, None, y.vp, L.DT_I32)
+    return y
+
+
+class Pow(Operator):
+    """src/ops/binary_elementwise.rs:958-1117, float32 base and exponent: exponent 2 -> x * x, 3 -> x * x * x (tested per element), otherwise the
+    float64 pow rounded once.  The reference's int32-base forms are not built."""
+
+    def max_inputs(self):
+        return 2
+
+    def run(self, ctx, inputs):
+        base, exponent = _require(inputs, 0), _require(inputs, 1)
+        if base.dtype == np.int32 and exponent.dtype in (np.dtype(np.float32), np.dtype(np.int32)):
+            raise UnsupportedValue("Pow: int32 base is not supported by the device path")
+        if base.dtype != np.float32 or exponent.dtype != np.float32:
+            raise UnsupportedValue("Unsupported base and exponent type combination")
+        return [_broadcast_launch(ctx, base, exponent, L.BINARY_POW, None)]
+
+
+class PRelu(Operator):
+    """src/ops/unary_elementwise.rs:624-671: x < 0 ? slope * x : x; the slope broadcasts to x's shape only."""
+
+    def max_inputs(self):
+        return 2
+
+    def run(self, ctx, inputs):
+        x = _require(inputs, 0)
+        if x.dtype != np.float32:
+            raise UnsupportedType
+        slope = _want(_require(inputs, 1), np.float32)
+        if _broadcast_shapes(x.shape, slope.shape) != tuple(x.shape):
+            raise IncompatibleInputShapes("Slope is not broadcastable to input shape")
+        return [_broadcast_launch(ctx, x, slope, L.BINARY_PRELU, None)]
+
+
+class _Variadic(Operator):
+    """src/ops/variadic_elementwise.rs:21-39: one input is a copy, otherwise a left fold of the binary operator with numpy broadcasting."""
+    f32_op, i32_op = None, None
+
+    def _operands(self, inputs):
+        first = _require(inputs, 0)
+        if first.dtype not in (np.dtype(np.float32), np.dtype(np.int32)):
+            raise UnsupportedType
+        return [_want(t, first.dtype) for t in inputs if t is not None]
+
+    def run(self, ctx, inputs):
+        ts = self._operands(inputs)
+        if len(ts) == 1:
+            y = DeviceTensor(ctx, ts[0].shape, ts[0].dtype)
+            if y.nbytes:
+                ctx.call("rten_hip_memcpy_d2d", y.vp, ts[0].vp, C.c_size_t(y.nbytes))
+            return [y]
+        acc = ts[0]
+        for b in ts[1:]:
+            acc = _broadcast_launch(ctx, acc, b, self.f32_op, self.i32_op)
+        return [acc]
+
+
+class Min(_Variadic):
+    """cmp_nan_less (reduce.rs:861-873): a NaN in either operand wins, a tie keeps the left operand."""
+    f32_op, i32_op = L.BINARY_MIN, L.EW_IMIN
+
+
+class Max(_Variadic):
+    """cmp_nan_greater (reduce.rs:847-859): a NaN in either operand wins, a tie keeps the left operand (Max(+0, -0) = +0, Max(-0, +0) = -0)."""
+    f32_op, i32_op = L.BINARY_MAX, L.EW_IMAX
+
+
+class Sum(_Variadic):
+    """Left fold of `+` (int32 wraps)."""
+    f32_op, i32_op = L.BINARY_ADD, L.EW_IADD
+
+
+class Mean(_Variadic):
+    """Sum, then divided by n as f32 (variadic_elementwise.rs:98-102: a division, through the Div path)."""
+    f32_op = L.BINARY_ADD
+
+    def run(self, ctx, inputs):
+        first = _want(_require(inputs, 0), np.float32)
+        ts = self._operands(inputs)
+        total = super().run(ctx, [first] + ts[1:])[0]
+        return Div().run(ctx, [total, DeviceTensor.from_numpy(ctx, np.float32(len(ts)))], in_place=True)
+
+
+PAD_MODES = {"constant": L.PAD_CONSTANT, "reflect": L.PAD_REFLECT, "edge": L.PAD_EDGE, "wrap": L.PAD_WRAP}
+
+
+def pad_geometry(shape, pads, mode):
+    """The reference's checks (src/ops/pad.rs:41-124) on a shape: returns (output shape, whether the result is a plain copy of the cropped input)."""
+    nd = len(shape)
+    if len(pads) != 2 * nd:
+        raise InvalidValue("padding length should be 2 * input dims")
+    cropped = list(shape)
+    if any(p < 0 for p in pads):
+        for d in range(nd):
+            crop = max(-pads[d], 0) + max(-pads[nd + d], 0)
+            if crop > shape[d]:
+                raise InvalidValue("Negative pads remove more elements than axis contains")
+            cropped[d] = shape[d] - crop
+    out = [max(pads[d], 0) + cropped[d] + max(pads[nd + d], 0) for d in range(nd)]
+    if out == cropped:
+        return out, True
+    if mode != "constant":
+        batch = max(nd - 2, 0)
+        if out[:batch] != cropped[:batch]:
+            raise UnsupportedValue("Pad only supports non-constant padding of last 2 dims")
+        if 0 in cropped[batch:]:
+            raise InvalidValue("Padded dimension for non-constant padding is empty")
+    return out, False
+
+
+class Pad(Operator):
+    """src/ops/pad.rs: inputs (data, pads, constant_value, axes); float32 / int32 data of at most 6 dims.  `pads` is a host-side operand (a numpy
+    array or list, or a DeviceTensor that is read back), the fill value a scalar of the data's type.  One launch, rten_hip_pad_b32."""
+
+    def __init__(self, mode="constant"):
+        if mode not in PAD_MODES:
+            raise InvalidValue(f"Pad: unknown mode {mode!r}")
+        self.mode = mode
+
+    def max_inputs(self):
+        return 4
+
+    def run(self, ctx, inputs):
+        x = _require(inputs, 0)
+        pads_t = _require(inputs, 1)
+        if _get(inputs, 3) is not None:
+            raise UnsupportedValue("Pad operator does not yet support `axes` input")
+        if x.dtype not in (np.dtype(np.float32), np.dtype(np.int32)):
+            raise UnsupportedType
+        pads_a = _host_values(pads_t)
+        if pads_a.ndim != 1:
+            raise OpError("InputCastFailed", "expected pads with 1 dims")
+        pads = [int(p) for p in pads_a]
+        value = _get(inputs, 2)
+        fill = np.zeros((), x.dtype)
+        if value is not None:
+            if value.dtype != x.dtype:
+                raise OpError("InputCastFailed", f"expected {x.dtype.name} tensor")
+            if len(value.shape) != 0:
+                raise OpError("InputCastFailed", "expected tensor with 0 dims")
+            fill = np.asarray(_host_values(value), x.dtype).reshape(())
+        out, _ = pad_geometry(list(x.shape), pads, self.mode)
+        if len(x.shape) > 6:
+            raise UnsupportedValue("Pad of more than 6 dims is not supported by the device path")
+        y = DeviceTensor(ctx, out, x.dtype)
+        if y.size:
+            ctx.call("rten_hip_pad_b32", PAD_MODES[self.mode], len(x.shape), _i64(list(x.shape)), _i64(pads), C.c_uint32(int(fill.view(np.uint32))), x.vp, y.vp)
+        return [y]
+
+
 class Transpose(Operator):
     """src/ops/layout.rs:669+: perm None = reverse the axes; 4-byte element types."""
 
@@ -1770,7 +2023,8 @@ class OpRegistry:
         for op in (Conv, ConvTranspose, ConvInteger, ConvIntegerToFloat, MatMul, FusedMatMul, Gemm, MatMulInteger, MatMulIntegerToFloat, MatMulNBits,
                    Softmax, LogSoftmax, AddSoftmax, LayerNormalization, BatchNormalization, InstanceNormalization, Relu, Gelu, Erf, Add, Mul, Sub, Div, Transpose, MaxPool,
                    AveragePool, GlobalAveragePool, Flatten, DynamicQuantizeLinear, Attention, Gather, ReduceSum, ReduceMean, Einsum, Resize, Upsample,
-                   Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK, GRU, LSTM):
+                   Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK, GRU, LSTM, Neg, Abs, Sign, Floor, Ceil, Round, Sqrt, Reciprocal, Exp, Log, Softplus,
+                   Pow, PRelu, Min, Max, Sum, Mean, Pad):
             r.register_op(op)
         return r
 

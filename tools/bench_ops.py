@@ -142,6 +142,25 @@ def main():
         hbm("LogSoftmax", f"rows={r} cols={c}", (lambda r=r, c=c: ctx.call("rten_hip_log_softmax_f32", r, c, x.vp, y.vp)), 8.0 * r * c)
         copy_row(f"LogSoftmax {r}x{c}", r * c)
 
+    # Unary math, Pow, Max and Pad at 32x64x56x56 (--only math: selects these rows), beside the parameterised activation kernel's Sigmoid at the same element count (the row they are read
+    # against: same bytes, more arithmetic).  Positive operands, so that Log / Pow(0.5) / Softplus run their ordinary path.
+    mshape = (32, 64, 56, 56)
+    n_m = int(np.prod(mshape))
+    xp = dev(np.abs(rng.standard_normal(n_m, dtype=np.float32)) + np.float32(0.1))
+    hbm("math: activation Sigmoid (reference point)", f"n={n_m}", (lambda: ctx.call("rten_hip_activation_f32", L.ACT_SIGMOID, 0.0, 0.0, n_m, xp.vp, y.vp)), 8.0 * n_m)
+    for name, code in (("Exp", L.UNARY_EXP), ("Log", L.UNARY_LOG), ("Sqrt", L.UNARY_SQRT), ("Neg", L.UNARY_NEG), ("Softplus", L.UNARY_SOFTPLUS)):
+        hbm(f"math: unary {name}", f"n={n_m}", (lambda code=code: ctx.call("rten_hip_unary_f32", code, n_m, xp.vp, y.vp)), 8.0 * n_m)
+    i64 = lambda v: (C.c_int64 * len(v))(*v)
+    dense, zero = i64([64 * 56 * 56, 56 * 56, 56, 1]), i64([0, 0, 0, 0])
+    for e in (2.0, 0.5):
+        ed = dev(np.array(e, np.float32))
+        hbm(f"math: Pow({e:g})", "32x64x56x56 x []", (lambda ed=ed: ctx.call("rten_hip_binary_broadcast_f32", L.BINARY_POW, 4, i64(mshape), dense, zero, xp.vp, ed.vp, y.vp)), 8.0 * n_m)
+    hbm("math: Max (two operands)", "32x64x56x56 x 32x64x56x56", (lambda: ctx.call("rten_hip_binary_broadcast_f32", L.BINARY_MAX, 4, i64(mshape), dense, dense, xp.vp, x2.vp, y.vp)), 12.0 * n_m)
+    n_pad = 32 * 64 * 58 * 58
+    for mname, mode in (("reflect", L.PAD_REFLECT), ("constant", L.PAD_CONSTANT)):
+        hbm(f"math: Pad {mname} by 1", "32x64x56x56 -> 32x64x58x58", (lambda mode=mode: ctx.call("rten_hip_pad_b32", mode, 4, i64(mshape), i64([0, 0, 1, 1, 0, 0, 1, 1]), 0, xp.vp, y.vp)),
+            4.0 * (n_m + n_pad))
+
     # depthwise 3x3 (MobileNet-style: 32 x 144 x 56 x 56) and a 2x upsampling ConvTranspose (32 x 64 x 28 x 28 -> 32 x 32 x 56 x 56, 4x4 / 2)
     cdw = 144
     xdw, wdw, bdw = dev(rng.standard_normal((32, cdw, 56, 56), dtype=np.float32)), dev(rng.standard_normal((cdw, 1, 3, 3), dtype=np.float32)), dev(np.zeros(cdw, np.float32))

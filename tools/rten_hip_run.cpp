@@ -16,7 +16,7 @@
 //     -t, --timing           per-operator table (each operator followed by a sync)
 //     --tune                 time the candidate launch plans of every f32 convolution at load and keep the fastest
 //     --graph                capture one run into a hipGraph and replay it for the timed runs
-//     --parse-only           print the model summary (and check the attributes of GRU / LSTM and normalisation nodes as the loader does) and exit (needs no GPU)
+//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad and Pow nodes as the loader does) and exit (needs no GPU)
 //     --safetensors-info F   list the tensors of a Safetensors file (with --save-outputs: re-write it); no model, no GPU
 //
 // There is no CPU fallback: without an MI355X the tool reports BackendUnavailable and exits 2.
@@ -129,6 +129,20 @@ int main(int argc, char **argv) {
                 const Graph::NormNode a = Graph::read_norm_node(n, n.name.empty() ? n.outputs.at(0) : n.name);
                 if (n.op_type == "LogSoftmax") std::printf("  norm step LogSoftmax \"%s\": axis %d\n", n.name.c_str(), a.axis);
                 else std::printf("  norm step %s \"%s\": epsilon %g\n", (fuse ? Graph::norm_step_name(c, i) : n.op_type).c_str(), n.name.c_str(), (double)a.epsilon.value_or(1e-5f));
+            }
+        }
+        {
+            const onnx::Model c = Graph::canonical_form(m); // Pad, Pow and the math operators: the loader's checks, and where each step may run
+            for (auto &n : c.nodes) {
+                if (!(n.domain.empty() || n.domain == "ai.onnx")) continue;
+                const std::string label = n.name.empty() ? n.outputs.at(0) : n.name;
+                if (n.op_type == "Pad") {
+                    const Graph::PadNode a = Graph::read_pad_node(c, n, label);
+                    std::printf("  pad step Pad \"%s\": mode %s, pads from %s\n", n.name.c_str(), a.mode_name.c_str(), a.attr_form ? "the pads attribute" : "input 1 (a host value at run time)");
+                } else if (Graph::is_math_kind(n.op_type)) {
+                    if (n.op_type == "Pow") Graph::check_pow_node(c, n, label);
+                    std::printf("  math step %s \"%s\": %s\n", n.op_type.c_str(), n.name.c_str(), Graph::is_hostable_math_kind(n.op_type) ? "host-evaluated on host values, device otherwise" : "device");
+                }
             }
         }
         if (parse_only) return 0;

@@ -21,6 +21,10 @@ Test and tooling infrastructure only: nothing under rten_amd/ imports this.
     python tools/torch_export.py recognizer_ctc /tmp/rec_ctc.onnx      # the GRU recogniser with its log_softmax head (LogSoftmax)
     python tools/torch_export.py generator /tmp/generator.onnx         # image-to-image generator: Conv / InstanceNorm2d / ReLU, residual blocks, ConvTranspose, Tanh
     python tools/torch_export.py preact /tmp/preact.onnx               # pre-activation blocks (BN -> ReLU -> Conv): BatchNormalization nodes that survive export
+    python tools/torch_export.py reflect_generator /tmp/rgen.onnx      # the generator with ReflectionPad2d / ReplicationPad2d / F.pad (Pad nodes) and nn.PReLU
+    python tools/torch_export.py gpt2_mlp /tmp/gpt2_mlp.onnx           # LayerNorm, Linear, gelu_new written out with torch.pow(x, 3.0), Linear
+    python tools/torch_export.py box_decode /tmp/box_decode.onnx       # conv head + anchor decode: Exp, Min / Max against the image bounds, Sqrt, Reciprocal, Neg, Abs
+    python tools/torch_export.py dynamic_upsample /tmp/dyn_up.onnx     # F.interpolate(scale_factor=2) with dynamic H / W as Shape -> .. -> Floor -> .. -> Resize(sizes), written with onnx_writer
 """
 from __future__ import annotations
 
@@ -527,6 +531,161 @@ def preact_onnx(model=None, image: int = 16, batch: int = 2, dynamic: bool = Tru
     return export_bytes(model, (torch.zeros(batch, 3, image, image),), ["x"], ["logits"], axes)
 
 
+def reflect_generator_module(seed: int = 0, width: int = 8):
+    """The image-to-image generator as such nets are written: a ReflectionPad2d(3) + 7x7 stem, residual blocks of ReflectionPad2d(1) + 3x3 convolutions with
+    InstanceNorm and nn.PReLU(c), a ReplicationPad2d in front of the output convolution, and one F.pad with a negative entry (a crop and a zero pad in one
+    node).  Exports Pad nodes with mode reflect / edge / constant, and PRelu with a [C, 1, 1] slope."""
+    import torch
+    from torch import nn
+    torch.manual_seed(seed)
+    c = width
+
+    class Res(nn.Module):
+        def __init__(self, c):
+            super().__init__()
+            self.body = nn.Sequential(nn.ReflectionPad2d(1), nn.Conv2d(c, c, 3), nn.InstanceNorm2d(c, affine=True), nn.PReLU(c),
+                                      nn.ReflectionPad2d(1), nn.Conv2d(c, c, 3), nn.InstanceNorm2d(c, affine=True))
+
+        def forward(self, x):
+            return x + self.body(x)
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.stem = nn.Sequential(nn.ReflectionPad2d(3), nn.Conv2d(3, c, 7), nn.InstanceNorm2d(c, affine=True), nn.PReLU(c))
+            self.blocks = nn.Sequential(Res(c), Res(c))
+            self.out = nn.Sequential(nn.ReplicationPad2d(1), nn.Conv2d(c, 3, 3), nn.Tanh())
+            for m in self.modules():
+                if isinstance(m, nn.InstanceNorm2d):
+                    nn.init.uniform_(m.weight, 0.5, 1.5)
+                    nn.init.uniform_(m.bias, -0.5, 0.5)
+                if isinstance(m, nn.PReLU):
+                    nn.init.uniform_(m.weight, 0.05, 0.45)
+
+        def forward(self, x):
+            y = self.blocks(self.stem(x))
+            y = nn.functional.pad(y, (1, -2, -1, 2))  # W: one zero column in front, two cropped at the end; H: one row cropped, two zero rows appended
+            return self.out(y)
+
+    return Net().eval()
+
+
+def reflect_generator_onnx(model=None, image: int = 16, batch: int = 2, dynamic: bool = True) -> bytes:
+    import torch
+    model = model if model is not None else reflect_generator_module()
+    axes = {"x": {0: "batch"}, "y": {0: "batch"}} if dynamic else None
+    return export_bytes(model, (torch.zeros(batch, 3, image, image),), ["x"], ["y"], axes)
+
+
+def gpt2_mlp_module(seed: int = 0, hidden: int = 32, ffn: int = 96):
+    """A GPT-2 block's MLP half: LayerNorm, Linear, `gelu_new` written out (0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) with torch.pow(x, 3.0)),
+    Linear.  Exports Pow with a scalar exponent of 3 between Mul / Add / Tanh nodes."""
+    import math
+    import torch
+    from torch import nn
+    torch.manual_seed(seed)
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.ln, self.fc, self.proj = nn.LayerNorm(hidden), nn.Linear(hidden, ffn), nn.Linear(ffn, hidden)
+            nn.init.uniform_(self.ln.weight, 0.5, 1.5)
+            nn.init.uniform_(self.ln.bias, -0.5, 0.5)
+
+        def forward(self, x):
+            h = self.fc(self.ln(x))
+            h = 0.5 * h * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (h + 0.044715 * torch.pow(h, 3.0))))
+            return self.proj(h)
+
+    return Net().eval()
+
+
+def gpt2_mlp_onnx(model=None, batch: int = 2, seq: int = 5, hidden: int = 32, dynamic: bool = True) -> bytes:
+    import torch
+    model = model if model is not None else gpt2_mlp_module(hidden=hidden)
+    axes = {"x": {0: "batch"}, "y": {0: "batch"}} if dynamic else None
+    return export_bytes(model, (torch.zeros(batch, seq, hidden),), ["x"], ["y"], axes)
+
+
+BOX_IMAGE = (48.0, 64.0)  # (height, width) the box decoder clips against
+
+
+def box_decode_module(seed: int = 0, anchors: int = 3):
+    """A detection head's decode step: a 3x3 convolution gives (dx, dy, dw, dh) per anchor and cell; centres move by the offsets, sizes scale by exp(dw / dh),
+    the corners are clipped to the image with torch.maximum / torch.minimum, and a few per-box statistics use sqrt, reciprocal, neg and abs.  Exports Exp,
+    Min, Max, Sqrt, Reciprocal, Neg and Abs around Mul / Add / Sub / Div / Slice / Concat."""
+    import torch
+    from torch import nn
+    torch.manual_seed(seed)
+    a = anchors
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.head = nn.Conv2d(4, 4 * a, 3, 1, 1)
+            self.register_buffer("anchor_wh", torch.rand(1, 2 * a, 1, 1) * 12 + 4)
+            self.register_buffer("lo", torch.zeros(1, 1, 1, 1))
+            self.register_buffer("hi_x", torch.full((1, 1, 1, 1), BOX_IMAGE[1]))
+            self.register_buffer("hi_y", torch.full((1, 1, 1, 1), BOX_IMAGE[0]))
+
+        def forward(self, x, grid):
+            t = self.head(x)                                      # [N, 4a, H, W]
+            cx = grid[:, 0:1] + t[:, 0:a]                         # centres: the cell's position plus the offsets
+            cy = grid[:, 1:2] + t[:, a:2 * a]
+            wh = torch.exp(t[:, 2 * a:]) * self.anchor_wh         # sizes
+            w, h = wh[:, :a], wh[:, a:]
+            x0 = torch.maximum(cx - w * 0.5, self.lo)
+            y0 = torch.maximum(cy - h * 0.5, self.lo)
+            x1 = torch.minimum(cx + w * 0.5, self.hi_x)
+            y1 = torch.minimum(cy + h * 0.5, self.hi_y)
+            side = torch.sqrt(torch.abs((x1 - x0) * (y1 - y0)))   # geometric mean side of the clipped box (Abs: a box clipped away has a negative extent)
+            inv = torch.reciprocal(side + 1.0)
+            return torch.cat([x0, y0, x1, y1, side, inv, torch.neg(torch.abs(t[:, 0:a]))], 1)
+
+    return Net().eval()
+
+
+def box_decode_onnx(model=None, batch: int = 2, height: int = 6, width: int = 8, dynamic: bool = True) -> bytes:
+    import torch
+    model = model if model is not None else box_decode_module()
+    axes = {"x": {0: "batch"}, "boxes": {0: "batch"}} if dynamic else None
+    return export_bytes(model, (torch.zeros(batch, 4, height, width), torch.zeros(1, 2, height, width)), ["x", "grid"], ["boxes"], axes)
+
+
+def dynamic_upsample_weights(seed: int = 0):
+    rng = np.random.default_rng(seed)
+    return {"a.weight": rng.normal(0, 0.3, (4, 3, 3, 3)).astype(np.float32), "a.bias": rng.normal(0, 0.1, 4).astype(np.float32),
+            "b.weight": rng.normal(0, 0.3, (3, 4, 3, 3)).astype(np.float32), "b.bias": rng.normal(0, 0.1, 3).astype(np.float32)}
+
+
+def dynamic_upsample_onnx(weights=None, scale: float = 2.0) -> bytes:
+    """Conv -> F.interpolate(scale_factor=scale, nearest) -> F.pad(1, value 0.5) -> Conv with dynamic N / H / W, in the form exporters give the output size under
+    dynamic axes: Shape -> Slice -> Cast -> Mul -> Floor -> Cast -> Concat -> Resize(sizes).  This torch's TorchScript exporter passes `scales` to Resize
+    instead (no shape arithmetic at all), so the graph is written with rten_amd/onnx_writer.py; the Pad takes its pads and constant_value as inputs (the
+    opset 11+ form; the exporter's own Pad nodes carry attributes)."""
+    from rten_amd import onnx_writer as ow
+    w = weights if weights is not None else dynamic_upsample_weights()
+    i64 = lambda *v: np.array(v, np.int64)
+    inits = [ow.tensor(k, v) for k, v in w.items()] + [
+        ow.tensor("c0", i64(0)), ow.tensor("c2", i64(2)), ow.tensor("c4", i64(4)), ow.tensor("scale", np.array([scale, scale], np.float32)),
+        ow.tensor("pads", i64(0, 0, 1, 1, 0, 0, 1, 1)), ow.tensor("pad_value", np.array(0.5, np.float32))]
+    nodes = [
+        ow.node("Conv", ["x", "a.weight", "a.bias"], ["a"], name="conv_a", kernel_shape=[3, 3], pads=[1, 1, 1, 1]),
+        ow.node("Shape", ["a"], ["shape"], name="shape"),
+        ow.node("Slice", ["shape", "c0", "c2", "c0"], ["nc"], name="slice_nc"),
+        ow.node("Slice", ["shape", "c2", "c4", "c0"], ["hw"], name="slice_hw"),
+        ow.node("Cast", ["hw"], ["hw_f"], name="cast_f", to=1),
+        ow.node("Mul", ["hw_f", "scale"], ["hw_scaled"], name="mul_scale"),
+        ow.node("Floor", ["hw_scaled"], ["hw_floor"], name="floor_hw"),
+        ow.node("Cast", ["hw_floor"], ["hw_i"], name="cast_i", to=7),
+        ow.node("Concat", ["nc", "hw_i"], ["sizes"], name="concat_sizes", axis=0),
+        ow.node("Resize", ["a", "", "", "sizes"], ["up"], name="resize", mode="nearest", coordinate_transformation_mode="asymmetric", nearest_mode="floor"),
+        ow.node("Pad", ["up", "pads", "pad_value"], ["padded"], name="pad_up", mode="constant"),
+        ow.node("Conv", ["padded", "b.weight", "b.bias"], ["y"], name="conv_b", kernel_shape=[3, 3], pads=[0, 0, 0, 0]),
+    ]
+    return ow.model(nodes, [ow.value_info("x", 1, ["batch", 3, "height", "width"])], [ow.value_info("y", 1, ["batch", 3, "height2", "width2"])], inits)
+
+
 if __name__ == "__main__":
     kind, path = sys.argv[1], sys.argv[2]
     if kind == "resnet50":
@@ -554,6 +713,14 @@ if __name__ == "__main__":
         data = generator_onnx()
     elif kind == "preact":
         data = preact_onnx()
+    elif kind == "reflect_generator":
+        data = reflect_generator_onnx()
+    elif kind == "gpt2_mlp":
+        data = gpt2_mlp_onnx()
+    elif kind == "box_decode":
+        data = box_decode_onnx()
+    elif kind == "dynamic_upsample":
+        data = dynamic_upsample_onnx()
     else:
         data = bert_onnx(bert_module())
     open(path, "wb").write(data)
