@@ -550,6 +550,23 @@ int32_t rten_hip_elementwise_nd(rten_hip_ctx *ctx, int32_t op, int32_t ndim, con
 #define RTEN_HIP_PAD_EDGE 2
 #define RTEN_HIP_PAD_WRAP 3
 int32_t rten_hip_pad_b32(rten_hip_ctx *ctx, int32_t mode, int32_t ndim, const int64_t *x_shape, const int64_t *pads, uint32_t fill_bits, const void *x, void *y);
+/* QuantizeLinear / DequantizeLinear (src/ops/quantize.rs:19-334) and their round trip.  One geometry: the tensor viewed as [outer][channels][inner], element
+ * (o, c, i) uses scale[c] and zero_point[c]; channels == 1 is per-tensor quantisation.  scale and zero_point are DEVICE pointers (they may be run-time values;
+ * nothing is read back); zero_point has the quantised type and may be NULL (= 0).  `dtype` is the quantised type: RTEN_HIP_DT_U8 / RTEN_HIP_DT_I8, for
+ * dequantize also RTEN_HIP_DT_I32.
+ *   quantize     y = saturate(round_ties_even(x * inv_scale) + zp), inv_scale = 1.0f / scale[c]: one correctly rounded f32 division on the device
+ *   dequantize   y = (float)((int32)x - (int32)zp) * scale[c]; the int32 subtraction wraps
+ *   quantize_dequantize   the two above in one pass, f32 -> f32, the same bits as running them back to back; y may equal x
+ * Bit-identical to every path of the reference for |x * inv_scale| < 2^31.  Outside (NaN, +-inf, larger products), where the reference's own paths disagree:
+ * u8 with channels == 1 follows rten-vecmath's vector kernel (dql::quant_u8: NaN, +-inf and a product >= 2^31 all give 0), every other form the scalar
+ * definition (quantize.rs:171-194: a saturating cast, NaN -> 0, so +inf gives the type's maximum).  docs/KERNELS.md 4.9.  16-byte f32 / 4-byte 8-bit accesses between a scalar head and tail where both operands' addresses allow,
+ * per-element accesses otherwise; the 8-bit operand may sit at any byte address, f32 / int32 operands are 4-byte aligned.  No integer division per element. */
+int32_t rten_hip_quantize_linear_f32(rten_hip_ctx *ctx, int32_t dtype, int64_t outer, int64_t channels, int64_t inner, const float *x, const float *scale,
+                                     const void *zero_point, void *y);
+int32_t rten_hip_dequantize_linear_f32(rten_hip_ctx *ctx, int32_t dtype, int64_t outer, int64_t channels, int64_t inner, const void *x, const float *scale,
+                                       const void *zero_point, float *y);
+int32_t rten_hip_quantize_dequantize_f32(rten_hip_ctx *ctx, int32_t dtype, int64_t outer, int64_t channels, int64_t inner, const float *x, const float *scale,
+                                         const void *zero_point, float *y);
 /* Gather along any axis of 4-byte elements (src/ops/gather.rs:21-110): y[o][j][k] = data[o][ids[j]][k] with data viewed as [outer][axis_len][inner];
  * negative indices count from the end; out-of-range indices are clamped (the reference reports "Entry in indices is out of range"). */
 int32_t rten_hip_gather_axis_b32(rten_hip_ctx *ctx, int64_t outer, int64_t axis_len, int64_t inner, int64_t n_ids, const void *data, const int32_t *ids, void *y);

@@ -85,6 +85,7 @@ struct Model {
     std::vector<Node> nodes;
     std::vector<TensorProto> initializers;
     std::vector<ValueInfo> inputs, outputs;
+    size_t folded_dequantize = 0; // canonical form only: DequantizeLinear nodes over initializers that became f32 initializers (Graph::canonicalize)
 };
 
 struct ParseError : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -987,6 +988,97 @@ class Graph {
         static const std::set<std::string> kinds = {"Neg", "Abs", "Sign", "Floor", "Ceil", "Round", "Sqrt", "Reciprocal", "Min", "Max"};
         return kinds.count(k) != 0;
     }
+    // What the loader reads from, and refuses about, a QuantizeLinear / DequantizeLinear node (onnx_registry.rs:1081-1092,1560-1582: axis defaults to -1 for
+    // QuantizeLinear and to 1 for DequantizeLinear).  Needs no device; make_qdq_step and rten_hip_run --parse-only both call it.
+    struct QdqNode {
+        bool quantize = false;
+        int axis = 0;
+        std::optional<DType> output_dtype; // QuantizeLinear: the output_dtype attribute (UINT8 / INT8) when it is given
+        bool has_zero_point = false;
+    };
+    static QdqNode read_qdq_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        const std::string where = n.op_type + " " + label + ": ";
+        QdqNode a;
+        a.quantize = n.op_type == "QuantizeLinear";
+        a.axis = (int)n.get_int("axis", a.quantize ? -1 : 1);
+        a.has_zero_point = n.inputs.size() > 2 && !n.inputs[2].empty();
+        if (n.get_int("block_size", 0) != 0) throw GraphError(where + "block_size " + std::to_string(n.get_int("block_size", 0)) + ": blocked quantization is not supported");
+        if (n.get_int("saturate", 1) != 1) throw GraphError(where + "saturate = " + std::to_string(n.get_int("saturate", 1)) + " is not supported (float8 outputs only)");
+        if (n.get_int("precision", 0) != 0) throw GraphError(where + "precision = " + std::to_string(n.get_int("precision", 0)) + " is not supported");
+        const int64_t od = n.get_int("output_dtype", 0);
+        if (!a.quantize) {
+            if (od != 0) throw GraphError(where + "output_dtype = " + std::to_string(od) + " is not supported (the output is float32)");
+            return a;
+        }
+        if (od != 0 && od != onnx::UINT8 && od != onnx::INT8) throw GraphError(where + "output_dtype = " + std::to_string(od) + " is not supported (uint8 or int8)");
+        if (od != 0) a.output_dtype = od == onnx::UINT8 ? DType::U8 : DType::I8;
+        if (!a.has_zero_point && od == 0) throw GraphError(where + "neither a zero-point input nor output_dtype gives the output type");
+        return a;
+    }
+    // The DequantizeLinear that a QuantizeLinear (node i of the canonical model) forms one round-trip step with, or -1: the quantised value has exactly one
+    // reader, a DequantizeLinear taking it as data, and is not a graph output; both nodes take constant scales and zero points with bitwise equal values (both
+    // or neither have a zero point) and the same quantisation axis.  A per-axis pair whose two `axis` attributes differ is left alone even where they would
+    // resolve to the same dim for the rank met at run time (the rank is not known here).
+    static long qdq_pair_partner(const onnx::Model &m, size_t i) {
+        const onnx::Node &q = m.nodes[i];
+        if (q.op_type != "QuantizeLinear" || q.inputs.size() < 2 || q.outputs.empty() || !(q.domain.empty() || q.domain == "ai.onnx")) return -1;
+        const std::string &v = q.outputs[0];
+        for (auto &o : m.outputs) if (o.name == v) return -1;
+        long reader = -1;
+        for (size_t j = 0; j < m.nodes.size(); j++)
+            for (auto &in : m.nodes[j].inputs)
+                if (in == v) { if (reader >= 0) return -1; reader = (long)j; }
+        if (reader < 0) return -1;
+        const onnx::Node &d = m.nodes[(size_t)reader];
+        if (d.op_type != "DequantizeLinear" || d.inputs.size() < 2 || d.inputs[0] != v || !(d.domain.empty() || d.domain == "ai.onnx")) return -1;
+        auto same_const = [&](const std::string &a, const std::string &b) {
+            const onnx::TensorProto *ta = initializer_named(m, a), *tb = initializer_named(m, b);
+            return ta && tb && ta->data_type == tb->data_type && ta->raw == tb->raw && (ta->len() == 1 || ta->dims == tb->dims);
+        };
+        if (!same_const(q.inputs[1], d.inputs[1])) return -1;
+        const bool qz = q.inputs.size() > 2 && !q.inputs[2].empty(), dz = d.inputs.size() > 2 && !d.inputs[2].empty();
+        if (qz != dz || (qz && !same_const(q.inputs[2], d.inputs[2]))) return -1;
+        const onnx::TensorProto *sc = initializer_named(m, q.inputs[1]);
+        if (sc->data_type != onnx::FLOAT) return -1;
+        if (sc->len() != 1 && q.get_int("axis", -1) != d.get_int("axis", 1)) return -1;
+        return reader;
+    }
+    // Constant DequantizeLinear (data, scale and zero point all initializers), evaluated at load as the reference's propagate_constants does: one exact
+    // int -> f32 conversion (ties to even above 2^24, Rust's `as f32`) and one IEEE multiply per element -- the kernel's bits.  Errors name the node.
+    static onnx::TensorProto fold_dequantize(const onnx::Node &n, const onnx::TensorProto &x, const onnx::TensorProto &scale, const onnx::TensorProto *zp) {
+        const std::string where = "DequantizeLinear " + label_of(n) + ": ";
+        read_qdq_node(onnx::Model(), n, label_of(n));
+        if (scale.data_type != onnx::FLOAT) throw GraphError(where + "the scale must be float32");
+        if (x.data_type != onnx::UINT8 && x.data_type != onnx::INT8 && x.data_type != onnx::INT32) throw GraphError(where + "the input must be uint8, int8 or int32");
+        if (zp && zp->data_type != x.data_type) throw GraphError(where + "the zero point must have the input's type");
+        const size_t esz = x.data_type == onnx::INT32 ? 4 : 1;
+        if (x.raw.size() != (size_t)x.len() * esz || scale.raw.size() != (size_t)scale.len() * 4 || (zp && zp->raw.size() != (size_t)zp->len() * esz))
+            throw GraphError(where + "an initializer's data size does not match its dims");
+        QdqGeometry g;
+        try { g = qdq_geometry(x.dims, scale.dims, zp ? &zp->dims : nullptr, (int)n.get_int("axis", 1), true); }
+        catch (const OpError &e) { throw GraphError(where + e.msg); }
+        auto elem = [esz](const onnx::TensorProto &t, int64_t i) -> int32_t {
+            if (esz == 4) { int32_t v; std::memcpy(&v, t.raw.data() + 4 * i, 4); return v; }
+            return t.data_type == onnx::UINT8 ? (int32_t)(uint8_t)t.raw[(size_t)i] : (int32_t)(int8_t)t.raw[(size_t)i];
+        };
+        onnx::TensorProto y;
+        y.name = n.outputs.at(0);
+        y.dims = x.dims;
+        y.data_type = onnx::FLOAT;
+        y.raw.resize((size_t)x.len() * 4);
+        int64_t at = 0;
+        for (int64_t o = 0; o < g.outer; o++)
+            for (int64_t c = 0; c < g.channels; c++) {
+                float s;
+                std::memcpy(&s, scale.raw.data() + 4 * c, 4);
+                const int32_t z = zp ? elem(*zp, c) : 0;
+                for (int64_t k = 0; k < g.inner; k++, at++) {
+                    const float v = (float)(int32_t)((uint32_t)elem(x, at) - (uint32_t)z) * s;
+                    std::memcpy(&y.raw[(size_t)at * 4], &v, 4);
+                }
+            }
+        return y;
+    }
     struct NormNode {
         std::optional<float> epsilon; // absent: the operator's default (1e-5)
         int axis = -1;                // LogSoftmax
@@ -1645,6 +1737,30 @@ class Graph {
                 m.initializers.push_back(std::move(t));
                 n.op_type.clear(); // removed below
             }
+        { // ---- DequantizeLinear over initializers -> an f32 initializer (fold_dequantize); an int8 / int32 initializer left without a reader is dropped
+            std::map<std::string, size_t> init_at;
+            for (size_t i = 0; i < m.initializers.size(); i++) init_at[m.initializers[i].name] = i;
+            std::set<std::string> graph_outs, folded_operands;
+            for (auto &o : m.outputs) graph_outs.insert(o.name);
+            for (auto &n : m.nodes) {
+                if (n.op_type != "DequantizeLinear" || !(n.domain.empty() || n.domain == "ai.onnx") || n.inputs.size() < 2 || n.outputs.size() != 1 || graph_outs.count(n.outputs[0])) continue;
+                const bool has_zp = n.inputs.size() > 2 && !n.inputs[2].empty();
+                if (!init_at.count(n.inputs[0]) || !init_at.count(n.inputs[1]) || (has_zp && !init_at.count(n.inputs[2]))) continue;
+                onnx::TensorProto y = fold_dequantize(n, m.initializers[init_at[n.inputs[0]]], m.initializers[init_at[n.inputs[1]]], has_zp ? &m.initializers[init_at[n.inputs[2]]] : nullptr);
+                for (auto &in : n.inputs) if (!in.empty()) folded_operands.insert(in);
+                init_at[y.name] = m.initializers.size();
+                m.initializers.push_back(std::move(y));
+                m.folded_dequantize++;
+                n.op_type.clear();
+            }
+            if (m.folded_dequantize) {
+                for (auto &n : m.nodes) if (!n.op_type.empty()) for (auto &in : n.inputs) folded_operands.erase(in);
+                for (auto &o : graph_outs) folded_operands.erase(o);
+                std::vector<onnx::TensorProto> kept;
+                for (auto &t : m.initializers) if (!folded_operands.count(t.name)) kept.push_back(std::move(t));
+                m.initializers = std::move(kept);
+            }
+        }
         std::map<std::string, size_t> producer, uses;
         std::map<std::string, const onnx::TensorProto *> inits;
         auto index = [&] {
@@ -2206,6 +2322,7 @@ class Graph {
             else if (kind == "InstanceNormalization" || kind == "BatchNormalization" || kind == "LogSoftmax") make_norm_step(st, n, nodes, out_name);
             else if (is_math_kind(kind)) make_math_step(st, n, m);
             else if (kind == "Pad") make_pad_step(st, n, m);
+            else if (kind == "QuantizeLinear" || kind == "DequantizeLinear") make_qdq_step(st, n, m, nodes, out_name);
             else if (kind == "Flatten" || kind == "Reshape" || kind == "Squeeze" || kind == "Unsqueeze" || kind == "Identity" || kind == "Dropout") make_view_step(st, n);
             else if (make_layout_step(st, n)) {
                 // Shape / ConstantOfShape / NonZero / Range / Slice / Concat / Expand / Where / comparisons / logic / integer arithmetic / Cast / Gather /
@@ -2582,6 +2699,39 @@ class Graph {
             o.push_back(pad_tensor(c, x, pads, a.mode, fill_bits));
             return o;
         };
+    }
+
+    // QuantizeLinear / DequantizeLinear: read_qdq_node's checks at load.  With fusion on, a QuantizeLinear whose value only feeds a DequantizeLinear with the same
+    // constant parameters (qdq_pair_partner) becomes one round-trip step on rten_hip_quantize_dequantize_f32; otherwise each node is its own step.  Scales and
+    // zero points stay device operands (they may be run-time values): nothing is read back, the steps are capture-safe.  A per-axis step whose axis resolves to
+    // dim 0 couples the batch rows.  (A DequantizeLinear over initializers never gets here: canonicalize folded it.)
+    void make_qdq_step(Step &st, const onnx::Node &n, const onnx::Model &m, Nodes &nodes, std::string &out_name) {
+        const std::string nm = st.name, kind = n.op_type;
+        const QdqNode a = read_qdq_node(m, n, nm);
+        const int axis = a.axis;
+        if (const onnx::TensorProto *sc = n.inputs.size() > 1 ? initializer_named(m, n.inputs[1]) : nullptr) st.batch_coupled = sc->len() != 1 && axis == 0;
+        auto note = [this, nm, kind, axis](const InputList &in) { if (require(in, 1).len() != 1) note_axis(kind, nm, axis, require(in, 0)); };
+        if (!a.quantize) {
+            auto op = std::make_shared<DequantizeLinear>();
+            op->axis = axis;
+            st.run = [op, note](Context &c, const InputList &in) { note(in); return op->run(c, in); };
+            return;
+        }
+        const long partner = opt_.fuse ? qdq_pair_partner(m, st.pos) : -1;
+        if (partner >= 0 && !nodes.dead[(size_t)partner]) {
+            read_qdq_node(m, nodes[partner], label_of(nodes[partner]));
+            auto op = std::make_shared<QuantizeDequantizeLinear>();
+            op->q.axis = axis;
+            op->q.output_dtype = a.output_dtype;
+            nodes.absorb(st, (size_t)partner, out_name);
+            st.kind_name = "QuantizeLinear+DequantizeLinear";
+            st.run = [op, note](Context &c, const InputList &in) { note(in); return op->run(c, in); };
+            return;
+        }
+        auto op = std::make_shared<QuantizeLinear>();
+        op->axis = axis;
+        op->output_dtype = a.output_dtype;
+        st.run = [op, note](Context &c, const InputList &in) { note(in); return op->run(c, in); };
     }
 
     // ArgMax / ArgMin, TopK and Softmax: one axis each, noted per run in case it resolves to dim 0

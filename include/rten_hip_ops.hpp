@@ -1376,6 +1376,96 @@ struct DynamicQuantizeLinear : Operator { // src/ops/quantize.rs:352-436: output
     }
 };
 
+// QuantizeLinear / DequantizeLinear (src/ops/quantize.rs:41-334).  qdq_geometry: the reference's rules on the shapes -> [outer][channels][inner].  A scalar or
+// one-element scale is per-tensor (its zero point must have one element), a rank-1 scale per-axis (checked against the axis), anything else blocked
+// quantisation.  One deviation: the reference does not check the zero-point length of a per-axis QuantizeLinear (its zip is cut short); a mismatch is refused
+// with DequantizeLinear's message.  `zp_shape` null = no zero point.
+struct QdqGeometry { int64_t outer = 1, channels = 1, inner = 1; int axis = -1; }; // axis: the resolved axis of a per-axis form, -1 per-tensor
+inline int64_t shape_len(const std::vector<int64_t> &s) { int64_t n = 1; for (int64_t d : s) n *= d; return n; }
+inline QdqGeometry qdq_geometry(const std::vector<int64_t> &x, const std::vector<int64_t> &scale, const std::vector<int64_t> *zp_shape, int axis, bool dequantize) {
+    QdqGeometry g;
+    if (shape_len(scale) == 1) {
+        if (zp_shape && shape_len(*zp_shape) != 1) throw OpError(OpError::InvalidValue, "scale and zero_point must have same shape");
+        g.inner = shape_len(x);
+        return g;
+    }
+    if (scale.size() != 1) throw OpError(OpError::UnsupportedValue, dequantize ? "Blocked dequantization is not supported" : "Blocked quantization is not supported");
+    const int ax = resolve_axis(axis, (int)x.size());
+    if (scale[0] != x[(size_t)ax]) throw OpError(OpError::IncompatibleInputShapes, "scale length does not match size of quantization axis");
+    if (zp_shape) {
+        if (zp_shape->size() != 1) throw OpError(OpError::InvalidValue, dequantize ? "scale and zero point must have same rank" : "scale and zero point must have same shape");
+        if ((*zp_shape)[0] != x[(size_t)ax]) throw OpError(OpError::IncompatibleInputShapes, "zero_point length does not match size of quantization axis");
+    }
+    g.axis = ax;
+    g.channels = x[(size_t)ax];
+    for (int d = 0; d < ax; d++) g.outer *= x[(size_t)d];
+    for (size_t d = (size_t)ax + 1; d < x.size(); d++) g.inner *= x[d];
+    return g;
+}
+inline int qdq_dtype_code(DType t) { return t == DType::U8 ? RTEN_HIP_DT_U8 : t == DType::I8 ? RTEN_HIP_DT_I8 : t == DType::I32 ? RTEN_HIP_DT_I32 : -1; }
+
+struct QuantizeLinear : Operator {
+    int axis = -1;
+    std::optional<DType> output_dtype; // U8 / I8; used when there is no zero point
+    const char *name() const override { return "QuantizeLinear"; }
+    int max_inputs() const override { return 3; }
+    // quantize.rs:299-323: the zero point's type (which output_dtype, if given, must equal), or output_dtype alone
+    DType out_dtype(const Tensor *zp) const {
+        if (zp) {
+            if ((zp->dtype() == DType::U8 || zp->dtype() == DType::I8) && (!output_dtype || *output_dtype == zp->dtype())) return zp->dtype();
+        } else if (output_dtype && (*output_dtype == DType::U8 || *output_dtype == DType::I8)) return *output_dtype;
+        throw OpError(OpError::UnsupportedType, "");
+    }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = want(require(in, 0), DType::F32, "float32"), &scale = want(require(in, 1), DType::F32, "float32");
+        const Tensor *zp = get(in, 2);
+        const DType dt = out_dtype(zp);
+        const QdqGeometry g = qdq_geometry(x.shape(), scale.shape(), zp ? &zp->shape() : nullptr, axis, false);
+        Tensor y(ctx, x.shape(), dt);
+        if (x.len()) ctx.check(rten_hip_quantize_linear_f32(ctx.raw(), qdq_dtype_code(dt), g.outer, g.channels, g.inner, (const float *)x.ptr(), (const float *)scale.ptr(), vp(zp), y.ptr()));
+        OutputList out;
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+
+struct DequantizeLinear : Operator {
+    int axis = 1;
+    const char *name() const override { return "DequantizeLinear"; }
+    int max_inputs() const override { return 3; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0), &scale = want(require(in, 1), DType::F32, "float32");
+        if (qdq_dtype_code(x.dtype()) < 0) throw OpError(OpError::UnsupportedType, "");
+        const Tensor *zp = get(in, 2);
+        if (zp) want(*zp, x.dtype(), x.dtype() == DType::U8 ? "uint8" : x.dtype() == DType::I8 ? "int8" : "int32");
+        const QdqGeometry g = qdq_geometry(x.shape(), scale.shape(), zp ? &zp->shape() : nullptr, axis, true);
+        Tensor y(ctx, x.shape(), DType::F32);
+        if (x.len()) ctx.check(rten_hip_dequantize_linear_f32(ctx.raw(), qdq_dtype_code(x.dtype()), g.outer, g.channels, g.inner, x.ptr(), (const float *)scale.ptr(), vp(zp), (float *)y.ptr()));
+        OutputList out;
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+
+// QuantizeLinear -> DequantizeLinear with equal parameters as one pass (the graph executor's pair fusion): f32 -> f32, the bits of the two operators run back
+// to back.  Inputs as QuantizeLinear's.
+struct QuantizeDequantizeLinear : Operator {
+    QuantizeLinear q;
+    const char *name() const override { return "QuantizeLinear+DequantizeLinear"; }
+    int max_inputs() const override { return 3; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = want(require(in, 0), DType::F32, "float32"), &scale = want(require(in, 1), DType::F32, "float32");
+        const Tensor *zp = get(in, 2);
+        const DType dt = q.out_dtype(zp);
+        const QdqGeometry g = qdq_geometry(x.shape(), scale.shape(), zp ? &zp->shape() : nullptr, q.axis, false);
+        Tensor y(ctx, x.shape(), DType::F32);
+        if (x.len()) ctx.check(rten_hip_quantize_dequantize_f32(ctx.raw(), qdq_dtype_code(dt), g.outer, g.channels, g.inner, (const float *)x.ptr(), (const float *)scale.ptr(), vp(zp), (float *)y.ptr()));
+        OutputList out;
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+
 // DynamicQuantizeLinear whose u8 output is only consumed by int8 convolutions of one staging geometry: the codes are
 // written once, directly in the kernel's staged layout (bit-identical values), and -- when the producer of `x` left
 // min/max statistics -- without the extra sweep over x.  Outputs: staged image (logical shape of x), y_scale, y_zero_point.
@@ -2856,6 +2946,8 @@ class OpRegistry {
         r.register_op<Sum>("Sum");
         r.register_op<Mean>("Mean");
         r.register_op<Pad>("Pad");
+        r.register_op<QuantizeLinear>("QuantizeLinear");
+        r.register_op<DequantizeLinear>("DequantizeLinear");
         return r;
     }
 

@@ -36,7 +36,7 @@ UNARY_NEG, UNARY_ABS, UNARY_SIGN, UNARY_FLOOR, UNARY_CEIL, UNARY_ROUND, UNARY_SQ
 # op of rten_hip_binary_broadcast_f32
 BINARY_ADD, BINARY_MUL, BINARY_SUB, BINARY_DIV, BINARY_MIN, BINARY_MAX, BINARY_POW, BINARY_PRELU = range(8)
 # element types and the operator codes of rten_hip_elementwise_nd that the Python operators use (RTEN_HIP_DT_*, RTEN_HIP_EW_*)
-DT_F32, DT_I32 = 0, 1
+DT_F32, DT_I32, DT_U8, DT_I8 = 0, 1, 2, 3
 EW_IADD, EW_INEG, EW_IABS, EW_ISIGN, EW_IMIN, EW_IMAX = 11, 15, 16, 17, 18, 19
 # mode of rten_hip_pad_b32 (RTEN_HIP_PAD_*)
 PAD_CONSTANT, PAD_REFLECT, PAD_EDGE, PAD_WRAP = 0, 1, 2, 3
@@ -197,6 +197,9 @@ PROTOTYPES = {
     "rten_hip_copy_strided_b32": (_I32, [_VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_elementwise_nd": (_I32, [_VP, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _I32]),
     "rten_hip_pad_b32": (_I32, [_VP, _I32, _I32, _VP, _VP, _U32, _VP, _VP]),
+    "rten_hip_quantize_linear_f32": (_I32, [_VP, _I32, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
+    "rten_hip_dequantize_linear_f32": (_I32, [_VP, _I32, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
+    "rten_hip_quantize_dequantize_f32": (_I32, [_VP, _I32, _I64, _I64, _I64, _VP, _VP, _VP, _VP]),
     "rten_hip_gather_axis_b32": (_I32, [_VP, _I64, _I64, _I64, _I64, _VP, _VP, _VP]),
     "rten_hip_copy_rows_b32": (_I32, [_VP, _I64, _I64, _VP, _I64, _VP, _I64]),
     "rten_hip_resize_f32": (_I32, [_VP, _I32, _I32, _I32, _I64, _I64, _I64, _I64, _I64, C.c_float, C.c_float, _VP, _VP]),

@@ -221,10 +221,21 @@ def small_cnn_f32(seed: int = 7):
 
 def bert_encoder(cfg, weights, seq: int, batch="batch") -> bytes:
     """inputs: input_ids, token_type_ids, attention_mask -- int64 [batch, seq]; output: last_hidden_state [batch, seq, hidden]."""
+    return _bert_encoder(cfg, weights, seq, batch, [], [], None)
+
+
+def _bert_encoder(cfg, weights, seq, batch, nodes, inits, weight_matmul) -> bytes:
+    """`weight_matmul(nodes, inits, x, weight name, out, node name)`: writes the MatMul of an activation with a weight (bert_encoder_qdq puts its
+    Q/DQ nodes there); None = a plain MatMul over the f32 initializer."""
     H, nh = cfg.hidden, cfg.heads
     dh = H // nh
     w = weights
-    nodes, inits = [], []
+
+    def wmm(x, wname, out, name):
+        if weight_matmul is None:
+            nodes.append(node("MatMul", [x, wname], [out], name=name))
+        else:
+            weight_matmul(nodes, inits, x, wname, out, name)
 
     def const(name, arr):
         inits.append(tensor(name, arr))
@@ -251,9 +262,10 @@ def bert_encoder(cfg, weights, seq: int, batch="batch") -> bytes:
     for i, lw in enumerate(w["layers"]):
         p = f"l{i}."
         for k in ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln1_g", "ln1_b", "w1", "b1", "w2", "b2", "ln2_g", "ln2_b"):
-            const(p + k, lw[k])
+            if weight_matmul is None or k not in ("wq", "wk", "wv", "wo", "w1", "w2"):
+                const(p + k, lw[k])
         for t in ("q", "k", "v"):
-            nodes.append(node("MatMul", [x, p + "w" + t], [p + t + ".mm"], name=p + t + ".matmul"))
+            wmm(x, p + "w" + t, p + t + ".mm", p + t + ".matmul")
             nodes.append(node("Add", [p + t + ".mm", p + "b" + t], [p + t + ".lin"], name=p + t + ".bias"))
             nodes.append(node("Reshape", [p + t + ".lin", "split_heads"], [p + t + ".4d"], name=p + t + ".reshape"))
             nodes.append(node("Transpose", [p + t + ".4d"], [p + t], name=p + t + ".transpose", perm=[0, 2, 3, 1] if t == "k" else [0, 2, 1, 3]))
@@ -264,14 +276,14 @@ def bert_encoder(cfg, weights, seq: int, batch="batch") -> bytes:
         nodes.append(node("MatMul", [p + "probs", p + "v"], [p + "ctx.h"], name=p + "pv"))
         nodes.append(node("Transpose", [p + "ctx.h"], [p + "ctx.t"], name=p + "ctx.transpose", perm=[0, 2, 1, 3]))
         nodes.append(node("Reshape", [p + "ctx.t", "merge_heads"], [p + "ctx"], name=p + "ctx.reshape"))
-        nodes.append(node("MatMul", [p + "ctx", p + "wo"], [p + "o.mm"], name=p + "o.matmul"))
+        wmm(p + "ctx", p + "wo", p + "o.mm", p + "o.matmul")
         nodes.append(node("Add", [p + "o.mm", p + "bo"], [p + "o.lin"], name=p + "o.bias"))
         nodes.append(node("Add", [p + "o.lin", x], [p + "res1"], name=p + "res1"))
         nodes.append(node("LayerNormalization", [p + "res1", p + "ln1_g", p + "ln1_b"], [p + "x1"], name=p + "ln1", axis=-1, epsilon=float(cfg.eps)))
-        nodes.append(node("MatMul", [p + "x1", p + "w1"], [p + "h.mm"], name=p + "ffn1.matmul"))
+        wmm(p + "x1", p + "w1", p + "h.mm", p + "ffn1.matmul")
         nodes.append(node("Add", [p + "h.mm", p + "b1"], [p + "h.lin"], name=p + "ffn1.bias"))
         nodes.append(node("Gelu", [p + "h.lin"], [p + "h"], name=p + "gelu"))
-        nodes.append(node("MatMul", [p + "h", p + "w2"], [p + "f.mm"], name=p + "ffn2.matmul"))
+        wmm(p + "h", p + "w2", p + "f.mm", p + "ffn2.matmul")
         nodes.append(node("Add", [p + "f.mm", p + "b2"], [p + "f.lin"], name=p + "ffn2.bias"))
         nodes.append(node("Add", [p + "f.lin", p + "x1"], [p + "res2"], name=p + "res2"))
         out = "last_hidden_state" if i == len(w["layers"]) - 1 else p + "x2"
@@ -279,3 +291,260 @@ def bert_encoder(cfg, weights, seq: int, batch="batch") -> bytes:
         x = out
     ins = [value_info(n, INT64, [batch, seq]) for n in ("input_ids", "token_type_ids", "attention_mask")]
     return model(nodes, ins, [value_info("last_hidden_state", FLOAT, [batch, seq, H])], inits, opset=20, name="bert_encoder")
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Static quantisation in ONNX Runtime's QDQ layout (`quantize_static`, QuantFormat.QDQ): int8 weights and int32 biases behind a
+# DequantizeLinear each, a QuantizeLinear -> DequantizeLinear pair on the activations.  The scales come from a min/max calibration
+# pass over the f32 network, run here in numpy on seeded inputs.
+# ----------------------------------------------------------------------------------------------------------------
+
+def activation_qparams(lo, hi):
+    """ort's asymmetric u8 parameters of a calibrated range (the range is widened to contain 0): scale, zero point."""
+    lo, hi = min(float(lo), 0.0), max(float(hi), 0.0)
+    scale = np.float32((hi - lo) / 255.0) if hi > lo else np.float32(1.0)
+    zp = np.uint8(np.clip(np.rint(-lo / float(scale)), 0, 255))
+    return scale, zp
+
+
+def quantize_weight_per_channel(w, axis):
+    """Symmetric int8 weights, one scale per slice of `axis`: scale = max|w| / 127, q = clip(rint(w / scale), -127, 127), zero points 0."""
+    red = tuple(d for d in range(w.ndim) if d != axis)
+    s = (np.abs(w).max(axis=red) / 127.0).astype(np.float32)
+    s = np.where(s == 0, np.float32(1.0), s).astype(np.float32)
+    shape = [1] * w.ndim
+    shape[axis] = -1
+    q = np.clip(np.rint(w / s.reshape(shape)), -127, 127).astype(np.int8)
+    return q, s, np.zeros(s.shape, np.int8)
+
+
+def quantize_weight_per_tensor(w):
+    s = np.float32(np.abs(w).max() / 127.0) or np.float32(1.0)
+    return np.clip(np.rint(w / s), -127, 127).astype(np.int8), np.float32(s), np.int8(0)
+
+
+class _QdqGraph:
+    """Node / initializer lists plus the Q/DQ bookkeeping of a QDQ builder.  `q` records every quantised constant and every activation's parameters
+    by name, so that a test can restate the graph with its own operators."""
+
+    def __init__(self, enabled=True):
+        self.nodes, self.inits, self.q = [], [], {"act": {}, "weight": {}, "bias": {}}
+        self._pairs = {}
+        self.enabled = enabled  # False: the same network in f32 (no Q/DQ node, f32 initializers): the twin a QDQ graph's time is read against
+
+    def const(self, name, arr):
+        self.inits.append(tensor(name, arr))
+        return name
+
+    def pair(self, src, lo_hi, dequantize=True):
+        """QuantizeLinear -> DequantizeLinear on `src` with per-tensor u8 constants (one pair per tensor, shared by its readers)."""
+        if not self.enabled:
+            return src
+        if src not in self._pairs:
+            scale, zp = activation_qparams(*lo_hi)
+            self.q["act"][src] = (scale, zp)
+            self.const(src + ".scale", np.array(scale, np.float32))
+            self.const(src + ".zp", np.array(zp, np.uint8))
+            self.nodes.append(node("QuantizeLinear", [src, src + ".scale", src + ".zp"], [src + ".q"], name=src + ".quant"))
+            if dequantize:
+                self.nodes.append(node("DequantizeLinear", [src + ".q", src + ".scale", src + ".zp"], [src + ".dq"], name=src + ".dequant"))
+            self._pairs[src] = src + ".dq" if dequantize else src + ".q"
+        return self._pairs[src]
+
+    def weight(self, name, w, axis=None):
+        """int8 weight behind a DequantizeLinear: per slice of `axis`, or per-tensor (axis None)."""
+        if not self.enabled:
+            return self.const(name, w), None
+        wq, ws, wz = quantize_weight_per_tensor(w) if axis is None else quantize_weight_per_channel(w, axis)
+        self.q["weight"][name] = (wq, ws, wz, axis)
+        self.const(name + ".q", wq); self.const(name + ".scale", np.asarray(ws, np.float32)); self.const(name + ".zp", np.asarray(wz, np.int8))
+        self.nodes.append(node("DequantizeLinear", [name + ".q", name + ".scale", name + ".zp"], [name + ".dq"], name=name + ".dequant", **({} if axis is None else {"axis": axis})))
+        return name + ".dq", ws
+
+    def bias(self, name, b, x_scale, w_scale):
+        """int32 bias with scale x_scale * w_scale[c] and no zero point."""
+        if not self.enabled:
+            return self.const(name, b)
+        bs = (np.float32(x_scale) * np.asarray(w_scale, np.float32).reshape(-1)).astype(np.float32)
+        if bs.size == 1:
+            bs = np.repeat(bs, b.size)
+        bq = np.clip(np.rint(b.astype(np.float64) / bs), -(2 ** 31), 2 ** 31 - 1).astype(np.int32)
+        self.q["bias"][name] = (bq, bs)
+        self.const(name + ".q", bq); self.const(name + ".scale", bs)
+        self.nodes.append(node("DequantizeLinear", [name + ".q", name + ".scale"], [name + ".dq"], name=name + ".dequant", axis=0))
+        return name + ".dq"
+
+
+def _np_conv2d(x, w, b, stride=1, pad=0, groups=1):
+    """Plain numpy convolution (calibration only: its rounding is not the device's)."""
+    n, c, h, wd = x.shape
+    o, cg, kh, kw = w.shape
+    xp = np.pad(x, ((0, 0), (0, 0), (pad, pad), (pad, pad)))
+    win = np.lib.stride_tricks.sliding_window_view(xp, (kh, kw), axis=(2, 3))[:, :, ::stride, ::stride]  # [n, c, oh, ow, kh, kw]
+    og = o // groups
+    out = [np.einsum("nchwij,ocij->nohw", win[:, g * cg:(g + 1) * cg], w[g * og:(g + 1) * og]) for g in range(groups)]
+    return (np.concatenate(out, 1) + b.reshape(1, -1, 1, 1)).astype(np.float32)
+
+
+def small_cnn_qdq_weights(seed: int = 9):
+    rng = np.random.default_rng(seed)
+    n = lambda std, *s: rng.normal(0, std, s).astype(np.float32)
+    return {"stem": (n(0.3, 8, 3, 3, 3), n(0.1, 8)), "b1": (n(0.15, 8, 8, 3, 3), n(0.1, 8)), "b2": (n(0.15, 8, 8, 3, 3), n(0.1, 8)),
+            "dw": (n(0.3, 8, 1, 3, 3), n(0.1, 8)), "fc": (n(0.3, 5, 8), n(0.1, 5))}
+
+
+def small_cnn_qdq(seed: int = 9, image: int = 16, quantized_output: bool = False, quantize: bool = True):
+    """A small CNN after static quantisation in the QDQ layout: stem conv, one residual block (Conv+Relu, Conv, Add, Relu), a depthwise conv, MaxPool,
+    GlobalAveragePool and a Gemm with transB.  u8 activations with per-tensor constants, i8 weights per output channel (axis 0), int32 biases with scale
+    x_scale * w_scale[c] and no zero point.  A Q/DQ pair sits on the graph input, behind every convolution group (the pair follows the group's Relu, and
+    the residual Add and its Relu stay next to their convolution, as ort places the pair behind a fused activation), behind both pools and on the logits.
+    `quantized_output`: the graph output is the quantised logits (u8), without the last DequantizeLinear.  `quantize=False`: the f32 network itself
+    (output "logits"), the twin a QDQ graph's time is read against.
+    -> (model bytes, q): q["act"][tensor] = (scale, zero point), q["weight"][name] = (wq, scale, zero point, axis), q["bias"][name] = (bq, scale),
+    q["folded"] = the number of DequantizeLinear nodes over initializers."""
+    w = small_cnn_qdq_weights(seed)
+    # calibration: the f32 network on seeded inputs
+    x = np.random.default_rng(seed + 1).normal(0, 1, (4, 3, image, image)).astype(np.float32)
+    relu = lambda t: np.maximum(t, 0)
+    a = relu(_np_conv2d(x, *w["stem"], stride=2, pad=1))
+    b = relu(_np_conv2d(a, *w["b1"], pad=1))
+    s = relu(_np_conv2d(b, *w["b2"], pad=1) + a)
+    d = _np_conv2d(s, *w["dw"], pad=1, groups=8)
+    p = d.reshape(d.shape[0], 8, d.shape[2] // 2, 2, d.shape[3] // 2, 2).max(axis=(3, 5))
+    gp = p.mean(axis=(2, 3), keepdims=True)
+    y = gp.reshape(gp.shape[0], -1) @ w["fc"][0].T + w["fc"][1]
+    rng_of = lambda t: (t.min(), t.max())
+
+    g = _QdqGraph(quantize)
+
+    def conv(name, src, src_range, dst, **attrs):
+        xin = g.pair(src, src_range)
+        wd, ws = g.weight(name + ".w", w[name][0], axis=0)
+        bd = g.bias(name + ".b", w[name][1], g.q["act"].get(src, (None,))[0], ws)
+        g.nodes.append(node("Conv", [xin, wd, bd], [dst], name=name, kernel_shape=[3, 3], **attrs))
+
+    conv("stem", "x", rng_of(x), "a.conv", pads=[1, 1, 1, 1], strides=[2, 2])
+    g.nodes.append(node("Relu", ["a.conv"], ["a"], name="stem.relu"))
+    conv("b1", "a", rng_of(a), "b.conv", pads=[1, 1, 1, 1])
+    g.nodes.append(node("Relu", ["b.conv"], ["b"], name="b1.relu"))
+    conv("b2", "b", rng_of(b), "s.conv", pads=[1, 1, 1, 1])
+    g.nodes.append(node("Add", ["s.conv", g.pair("a", rng_of(a))], ["s.sum"], name="b2.add"))
+    g.nodes.append(node("Relu", ["s.sum"], ["s"], name="b2.relu"))
+    conv("dw", "s", rng_of(s), "d", pads=[1, 1, 1, 1], group=8)
+    g.nodes.append(node("MaxPool", [g.pair("d", rng_of(d))], ["p"], name="pool", kernel_shape=[2, 2], strides=[2, 2]))
+    g.nodes.append(node("GlobalAveragePool", [g.pair("p", rng_of(p))], ["g"], name="gap"))
+    g.nodes.append(node("Flatten", [g.pair("g", rng_of(gp))], ["f"], name="flatten", axis=1))
+    wd, ws = g.weight("fc.w", w["fc"][0], axis=0)
+    bd = g.bias("fc.b", w["fc"][1], g.q["act"].get("g", (None,))[0], ws)
+    g.nodes.append(node("Gemm", ["f", wd, bd], ["logits"], name="fc", transB=1))
+    out = g.pair("logits", rng_of(y), dequantize=not quantized_output)
+    g.q["folded"] = len(g.q["weight"]) + len(g.q["bias"])
+    g.q["pairs"] = len(g.q["act"]) - (1 if quantized_output else 0)
+    outs = [value_info(out, UINT8 if quantized_output and quantize else FLOAT, ["batch", 5])]
+    return model(g.nodes, [value_info("x", FLOAT, ["batch", 3, image, image])], outs, g.inits, opset=19, name="small_cnn_qdq"), g.q
+
+
+def _np_bert_activations(cfg, w, ids, tts, seq):
+    """The f32 encoder in numpy, returning the inputs of its weight MatMuls per layer (calibration only)."""
+    import math
+    erf = np.vectorize(math.erf)
+    H, nh = cfg.hidden, cfg.heads
+    dh = H // nh
+
+    def ln(t, gam, bet):
+        mu = t.mean(-1, keepdims=True)
+        return ((t - mu) / np.sqrt(((t - mu) ** 2).mean(-1, keepdims=True) + cfg.eps) * gam + bet).astype(np.float32)
+
+    x = ln(w["word"][ids] + w["type"][tts] + w["pos"][:seq], w["emb_ln_g"], w["emb_ln_b"])
+    acts = []
+    for lw in w["layers"]:
+        B = x.shape[0]
+        split = lambda t: t.reshape(B, seq, nh, dh).transpose(0, 2, 1, 3)
+        q, k, v = (split(x @ lw["w" + t] + lw["b" + t]) for t in "qkv")
+        sc = q @ k.transpose(0, 1, 3, 2) / np.sqrt(np.float32(dh))
+        pr = np.exp(sc - sc.max(-1, keepdims=True))
+        pr = pr / pr.sum(-1, keepdims=True)
+        ctx = (pr @ v).transpose(0, 2, 1, 3).reshape(B, seq, H)
+        x1 = ln(ctx @ lw["wo"] + lw["bo"] + x, lw["ln1_g"], lw["ln1_b"])
+        h = x1 @ lw["w1"] + lw["b1"]
+        h = (0.5 * h * (1.0 + erf(h / math.sqrt(2.0)))).astype(np.float32)
+        x2 = ln(h @ lw["w2"] + lw["b2"] + x1, lw["ln2_g"], lw["ln2_b"])
+        acts.append({"x": x, "ctx": ctx, "x1": x1, "h": h})
+        x = x2
+    return acts
+
+
+def bert_encoder_qdq(cfg, weights, seq: int, batch="batch", seed: int = 11):
+    """bert_encoder after static quantisation of its weight MatMuls in the QDQ layout: i8 weights behind a DequantizeLinear -- per-tensor, the first
+    feed-forward weight per column (axis 1) -- and a Q/DQ pair with per-tensor u8 constants on each such MatMul's activation input (the three
+    projections share the pair on their input).  The attention products, biases, LayerNormalization and Gelu stay f32.
+    -> (model bytes, q) as small_cnn_qdq."""
+    rng = np.random.default_rng(seed)
+    ids = rng.integers(0, cfg.vocab, (4, seq))
+    acts = _np_bert_activations(cfg, weights, ids, np.zeros((4, seq), np.int64), seq)
+    g = _QdqGraph()
+    ranges = {}
+    for i, a in enumerate(acts):
+        x_name = "x0" if i == 0 else f"l{i - 1}.x2"
+        ranges.update({x_name: a["x"], f"l{i}.ctx": a["ctx"], f"l{i}.x1": a["x1"], f"l{i}.h": a["h"]})
+
+    def matmul(nodes, inits, x, wname, out, name):
+        assert nodes is g.nodes and inits is g.inits
+        wd, _ = g.weight(wname, weights["layers"][int(wname[1:wname.index(".")])][wname.split(".")[1]], axis=1 if wname.endswith(".w1") else None)
+        t = ranges[x]
+        nodes.append(node("MatMul", [g.pair(x, (t.min(), t.max())), wd], [out], name=name))
+
+    data = _bert_encoder(cfg, weights, seq, batch, g.nodes, g.inits, matmul)
+    g.q["folded"] = len(g.q["weight"])
+    g.q["pairs"] = len(g.q["act"])
+    return data, g.q
+
+
+def resnet50_qdq(weights, batch="batch", image: int = 224, calibration_image: int = 32, quantize: bool = True, seed: int = 13):
+    """ResNet-50 (the graph of resnet50_f32) after static quantisation in the QDQ layout, built as small_cnn_qdq: i8 weights per output channel, int32
+    biases, a per-tensor u8 Q/DQ pair on the input, behind every Conv(+Add)(+Relu) group, both pools and the logits.  The calibration pass runs the f32
+    network in numpy on one seeded `calibration_image`-sized picture (the scales are parameters: any plausible range serves a timing run).
+    `quantize=False`: the f32 network written by the same code (output "logits").  -> (model bytes, q)."""
+    from .workloads.resnet50 import conv_specs
+    specs = conv_specs()
+    acts = {"x": np.random.default_rng(seed).random((1, 3, calibration_image, calibration_image), dtype=np.float32)}
+    for l in specs:
+        t = _np_conv2d(acts[l["src"]], *weights[l["name"]], stride=l["stride"], pad=l["pad"])
+        if l["res"]:
+            t = t + acts[l["res"]]
+        acts[l["dst"]] = np.maximum(t, 0) if l["relu"] else t
+        if l["name"] == "stem":
+            win = np.lib.stride_tricks.sliding_window_view(np.pad(acts["stem"], ((0, 0), (0, 0), (1, 1), (1, 1)), constant_values=-np.inf), (3, 3), axis=(2, 3))
+            acts["pool"] = win[:, :, ::2, ::2].max(axis=(4, 5))
+    last = specs[-1]["dst"]
+    acts["gap"] = acts[last].mean(axis=(2, 3), keepdims=True)
+    fw, fb = weights["fc"]
+    acts["logits"] = acts["gap"].reshape(1, -1) @ fw.T + fb
+    rng_of = lambda n: (acts[n].min(), acts[n].max())
+
+    g = _QdqGraph(quantize)
+    for l in specs:
+        n = l["name"]
+        xin = g.pair(l["src"], rng_of(l["src"]))
+        wd, ws = g.weight(n + ".w", weights[n][0], axis=0)
+        bd = g.bias(n + ".b", weights[n][1], g.q["act"].get(l["src"], (None,))[0], ws)
+        conv_out = l["dst"] + ".conv" if (l["relu"] or l["res"]) else l["dst"]
+        g.nodes.append(node("Conv", [xin, wd, bd], [conv_out], name=n, dilations=[1, 1], group=1, kernel_shape=[l["k"], l["k"]], pads=[l["pad"]] * 4, strides=[l["stride"]] * 2))
+        cur = conv_out
+        if l["res"]:
+            nxt = l["dst"] + ".sum" if l["relu"] else l["dst"]
+            g.nodes.append(node("Add", [cur, g.pair(l["res"], rng_of(l["res"]))], [nxt], name=n + ".add"))
+            cur = nxt
+        if l["relu"]:
+            g.nodes.append(node("Relu", [cur], [l["dst"]], name=n + ".relu"))
+        if n == "stem":
+            g.nodes.append(node("MaxPool", [g.pair("stem", rng_of("stem"))], ["pool"], name="maxpool", ceil_mode=0, kernel_shape=[3, 3], pads=[1, 1, 1, 1], strides=[2, 2]))
+    g.nodes.append(node("GlobalAveragePool", [g.pair(last, rng_of(last))], ["gap"], name="gap"))
+    g.nodes.append(node("Flatten", [g.pair("gap", rng_of("gap"))], ["flat"], name="flatten", axis=1))
+    wd, ws = g.weight("fc.w", fw, axis=0)
+    bd = g.bias("fc.b", fb, g.q["act"].get("gap", (None,))[0], ws)
+    g.nodes.append(node("Gemm", ["flat", wd, bd], ["logits"], name="fc", alpha=1.0, beta=1.0, transB=1))
+    out = g.pair("logits", rng_of("logits"))
+    g.q["folded"] = len(g.q["weight"]) + len(g.q["bias"])
+    g.q["pairs"] = len(g.q["act"])
+    return model(g.nodes, [value_info("x", FLOAT, [batch, 3, image, image])], [value_info(out, FLOAT, [batch, fw.shape[0]])], g.inits, opset=19, name="resnet50_qdq"), g.q

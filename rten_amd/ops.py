@@ -1480,6 +1480,86 @@ class DynamicQuantizeLinear(Operator):
         return [y, scale, zp]
 
 
+_QDQ_DT = {np.dtype(np.uint8): L.DT_U8, np.dtype(np.int8): L.DT_I8, np.dtype(np.int32): L.DT_I32}
+
+
+def _qdq_geometry(x, scale, zero_point, axis, what):
+    """quantize.rs:41-99,196-275: a scalar or one-element scale is per-tensor (its zero point must have one element); a rank-1 scale is per-axis and is
+    checked against the axis; anything else is blocked quantisation.  -> (outer, channels, inner).  One deviation: the reference does not check the
+    zero-point length of a per-axis QuantizeLinear (its zip is cut short); a mismatch is refused here with DequantizeLinear's message."""
+    if scale.size == 1:
+        if zero_point is not None and zero_point.size != 1:
+            raise InvalidValue("scale and zero_point must have same shape")
+        return 1, 1, int(x.size)
+    if len(scale.shape) != 1:
+        raise UnsupportedValue(f"Blocked {what} is not supported")
+    ax = _resolve_axis(len(x.shape), axis)
+    if scale.shape[0] != x.shape[ax]:
+        raise IncompatibleInputShapes("scale length does not match size of quantization axis")
+    if zero_point is not None:
+        if len(zero_point.shape) != 1:
+            raise InvalidValue("scale and zero point must have same rank" if what == "dequantization" else "scale and zero point must have same shape")
+        if zero_point.shape[0] != x.shape[ax]:
+            raise IncompatibleInputShapes("zero_point length does not match size of quantization axis")
+    return int(np.prod(x.shape[:ax], dtype=np.int64)), int(x.shape[ax]), int(np.prod(x.shape[ax + 1:], dtype=np.int64))
+
+
+class QuantizeLinear(Operator):
+    """src/ops/quantize.rs:196-334.  Inputs (x f32, y_scale f32, y_zero_point u8 / i8, optional); the output type is the zero point's, or
+    `output_dtype` (np.uint8 / np.int8) without one.  scale and zero point stay on the device: nothing is read back."""
+
+    def __init__(self, axis=-1, output_dtype=None):
+        self.axis = axis
+        self.output_dtype = None if output_dtype is None else np.dtype(output_dtype)
+
+    def max_inputs(self):
+        return 3
+
+    def out_dtype(self, zero_point):
+        u8, i8 = np.dtype(np.uint8), np.dtype(np.int8)
+        if zero_point is not None:
+            if zero_point.dtype in (u8, i8) and self.output_dtype in (None, zero_point.dtype):
+                return zero_point.dtype
+        elif self.output_dtype in (u8, i8):
+            return self.output_dtype
+        raise UnsupportedType
+
+    def run(self, ctx, inputs):
+        x = _want(_require(inputs, 0), np.float32)
+        scale = _want(_require(inputs, 1), np.float32)
+        zp = _get(inputs, 2)
+        dt = self.out_dtype(zp)
+        outer, channels, inner = _qdq_geometry(x, scale, zp, self.axis, "quantization")
+        y = DeviceTensor(ctx, x.shape, dt)
+        if x.size:
+            ctx.call("rten_hip_quantize_linear_f32", _QDQ_DT[dt], outer, channels, inner, x.vp, scale.vp, _vp(zp), y.vp)
+        return [y]
+
+
+class DequantizeLinear(Operator):
+    """src/ops/quantize.rs:41-133.  Inputs (x u8 / i8 / i32, x_scale f32, x_zero_point of x's type, optional) -> f32."""
+
+    def __init__(self, axis=1):
+        self.axis = axis
+
+    def max_inputs(self):
+        return 3
+
+    def run(self, ctx, inputs):
+        x = _require(inputs, 0)
+        scale = _want(_require(inputs, 1), np.float32)
+        if x.dtype not in _QDQ_DT:
+            raise UnsupportedType
+        zp = _get(inputs, 2)
+        if zp is not None:
+            _want(zp, x.dtype)
+        outer, channels, inner = _qdq_geometry(x, scale, zp, self.axis, "dequantization")
+        y = DeviceTensor(ctx, x.shape, np.float32)
+        if x.size:
+            ctx.call("rten_hip_dequantize_linear_f32", _QDQ_DT[x.dtype], outer, channels, inner, x.vp, scale.vp, _vp(zp), y.vp)
+        return [y]
+
+
 # ------------------------------------------------------------------------------------------ attention
 class Attention(Operator):
     """ONNX Attention restricted to the BERT path (src/ops/attention.rs:645-905): 4-D Q/K/V
@@ -2024,7 +2104,7 @@ class OpRegistry:
                    Softmax, LogSoftmax, AddSoftmax, LayerNormalization, BatchNormalization, InstanceNormalization, Relu, Gelu, Erf, Add, Mul, Sub, Div, Transpose, MaxPool,
                    AveragePool, GlobalAveragePool, Flatten, DynamicQuantizeLinear, Attention, Gather, ReduceSum, ReduceMean, Einsum, Resize, Upsample,
                    Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK, GRU, LSTM, Neg, Abs, Sign, Floor, Ceil, Round, Sqrt, Reciprocal, Exp, Log, Softplus,
-                   Pow, PRelu, Min, Max, Sum, Mean, Pad):
+                   Pow, PRelu, Min, Max, Sum, Mean, Pad, QuantizeLinear, DequantizeLinear):
             r.register_op(op)
         return r
 

@@ -161,6 +161,27 @@ def main():
         hbm(f"math: Pad {mname} by 1", "32x64x56x56 -> 32x64x58x58", (lambda mode=mode: ctx.call("rten_hip_pad_b32", mode, 4, i64(mshape), i64([0, 0, 1, 1, 0, 0, 1, 1]), 0, xp.vp, y.vp)),
             4.0 * (n_m + n_pad))
 
+    # QuantizeLinear / DequantizeLinear at the shape of the math rows (--only qdq: selects these rows): per-tensor u8, the fused round trip beside the two
+    # launches it replaces, and the per-axis (axis 1: 64 channels of 56 x 56) forms.  The Sigmoid row is measured before and after the others: the round trip moves
+    # the same 8 bytes per element with less arithmetic, and the two readings of that row give the spread it is read against.
+    xq_in = dev((rng.standard_normal(n_m, dtype=np.float32) * np.float32(2.0)))
+    q8 = empty((n_m,), np.uint8)
+    s1, z1 = dev(np.array(0.05, np.float32)), dev(np.array(128, np.uint8))
+    s64, z64 = dev(np.linspace(0.02, 0.08, 64).astype(np.float32)), dev(np.arange(96, 160, dtype=np.uint8))
+    per_tensor, per_axis = (1, 1, n_m), (32, 64, 56 * 56)
+    sigmoid_row = lambda tag: hbm(f"qdq: activation Sigmoid (reference point, {tag})", f"n={n_m}", (lambda: ctx.call("rten_hip_activation_f32", L.ACT_SIGMOID, 0.0, 0.0, n_m, xq_in.vp, y.vp)), 8.0 * n_m)
+    quant = lambda g, s, z: ctx.call("rten_hip_quantize_linear_f32", L.DT_U8, *g, xq_in.vp, s.vp, z.vp, q8.vp)
+    dequant = lambda g, s, z: ctx.call("rten_hip_dequantize_linear_f32", L.DT_U8, *g, q8.vp, s.vp, z.vp, y.vp)
+    fused = lambda g, s, z: ctx.call("rten_hip_quantize_dequantize_f32", L.DT_U8, *g, xq_in.vp, s.vp, z.vp, y.vp)
+    sigmoid_row("first")
+    hbm("qdq: quantize u8, per-tensor", "32x64x56x56", (lambda: quant(per_tensor, s1, z1)), 5.0 * n_m)
+    hbm("qdq: dequantize u8, per-tensor", "32x64x56x56", (lambda: dequant(per_tensor, s1, z1)), 5.0 * n_m)
+    hbm("qdq: round trip u8, per-tensor, one launch", "32x64x56x56", (lambda: fused(per_tensor, s1, z1)), 8.0 * n_m)
+    hbm("qdq: quantize + dequantize u8, per-tensor, two launches", "32x64x56x56", (lambda: (quant(per_tensor, s1, z1), dequant(per_tensor, s1, z1))), 10.0 * n_m)
+    hbm("qdq: quantize u8, per-axis (axis 1)", "32x64x56x56", (lambda: quant(per_axis, s64, z64)), 5.0 * n_m)
+    hbm("qdq: round trip u8, per-axis (axis 1), one launch", "32x64x56x56", (lambda: fused(per_axis, s64, z64)), 8.0 * n_m)
+    sigmoid_row("second")
+
     # depthwise 3x3 (MobileNet-style: 32 x 144 x 56 x 56) and a 2x upsampling ConvTranspose (32 x 64 x 28 x 28 -> 32 x 32 x 56 x 56, 4x4 / 2)
     cdw = 144
     xdw, wdw, bdw = dev(rng.standard_normal((32, cdw, 56, 56), dtype=np.float32)), dev(rng.standard_normal((cdw, 1, 3, 3), dtype=np.float32)), dev(np.zeros(cdw, np.float32))

@@ -16,7 +16,7 @@
 //     -t, --timing           per-operator table (each operator followed by a sync)
 //     --tune                 time the candidate launch plans of every f32 convolution at load and keep the fastest
 //     --graph                capture one run into a hipGraph and replay it for the timed runs
-//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad and Pow nodes as the loader does) and exit (needs no GPU)
+//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
 //     --safetensors-info F   list the tensors of a Safetensors file (with --save-outputs: re-write it); no model, no GPU
 //
 // There is no CPU fallback: without an MI355X the tool reports BackendUnavailable and exits 2.
@@ -114,6 +114,8 @@ int main(int argc, char **argv) {
                 for (auto &h : chist) std::printf(" %s x%d", h.first.c_str(), h.second);
                 std::printf("\n");
             }
+            if (c.folded_dequantize)
+                std::printf("  canonical form: %zu constant DequantizeLinear folded into float32 initializers (%zu initializers remain)\n", c.folded_dequantize, c.initializers.size());
         }
         for (auto &n : Graph::canonical_form(m).nodes) // recurrent layers: what the loader would refuse is refused here too (needs no GPU)
             if (n.domain.empty() || n.domain == "ai.onnx") if (n.op_type == "GRU" || n.op_type == "LSTM") {
@@ -143,6 +145,22 @@ int main(int argc, char **argv) {
                     if (n.op_type == "Pow") Graph::check_pow_node(c, n, label);
                     std::printf("  math step %s \"%s\": %s\n", n.op_type.c_str(), n.name.c_str(), Graph::is_hostable_math_kind(n.op_type) ? "host-evaluated on host values, device otherwise" : "device");
                 }
+            }
+        }
+        {
+            const onnx::Model c = Graph::canonical_form(m); // QuantizeLinear / DequantizeLinear: the loader's checks, and the pairs that become one round-trip step
+            std::vector<bool> taken(c.nodes.size(), false);
+            for (size_t i = 0; i < c.nodes.size(); i++) {
+                const onnx::Node &n = c.nodes[i];
+                if (!(n.domain.empty() || n.domain == "ai.onnx") || !(n.op_type == "QuantizeLinear" || n.op_type == "DequantizeLinear")) continue;
+                const Graph::QdqNode a = Graph::read_qdq_node(c, n, n.name.empty() ? n.outputs.at(0) : n.name);
+                if (taken[i]) continue;
+                const long partner = fuse ? Graph::qdq_pair_partner(c, i) : -1;
+                if (partner >= 0) {
+                    taken[(size_t)partner] = true;
+                    std::printf("  qdq step QuantizeLinear+DequantizeLinear \"%s\" + \"%s\": one round-trip launch, axis %d\n", n.name.c_str(), c.nodes[(size_t)partner].name.c_str(), a.axis);
+                } else
+                    std::printf("  qdq step %s \"%s\": axis %d%s\n", n.op_type.c_str(), n.name.c_str(), a.axis, a.quantize ? (a.has_zero_point ? ", output type of the zero point" : ", output type from output_dtype") : "");
             }
         }
         if (parse_only) return 0;
