@@ -384,6 +384,7 @@ RTEN_EXPORT int32_t rten_hip_conv2d_f32_pair(rten_hip_ctx *ctx, const rten_hip_c
     a.act2 = (flags2 & RTEN_HIP_CONV_RELU) ? RTEN_HIP_ACT_RELU : RTEN_HIP_ACT_NONE;
     a.dbg = ctx->debug >> 8;
     const int tiles = (a.N + 63) / 64;
+    ProfScope ps(ctx, "conv_pair_f32_kernel", 2.0 * a.N * ((double)a.M1 * a.K1 + (double)a.M2 * a.M1), 4.0 * a.N * ((double)a.K1 + a.M1 + a.M2));
     if (a.M2 == 64) hipLaunchKernelGGL((conv_pair_f32_kernel<64, 64, 64>), dim3(tiles), dim3(256), 0, ctx->stream, a);
     else hipLaunchKernelGGL((conv_pair_f32_kernel<64, 128, 64>), dim3(tiles), dim3(256), 0, ctx->stream, a);
     RTEN_LAUNCH_CHECK(ctx, "conv_pair_f32_kernel launch");
@@ -424,6 +425,7 @@ RTEN_EXPORT int32_t rten_hip_conv2d_f32_pair_shortcut(rten_hip_ctx *ctx, const r
     a.xd_bytes = (unsigned)((long long)ds->n * ds->c * P * 4);
     a.wd_bytes = (unsigned)((long long)ds->c * a.wd_cs * 4);
     const int tiles = (a.N + 63) / 64;
+    ProfScope ps(ctx, "conv_pair_f32_kernel<shortcut>", 2.0 * a.N * ((double)a.M1 * a.K1 * 2 + (double)a.M2 * a.M1), 4.0 * a.N * ((double)a.K1 * 2 + a.M1 + a.M2));
     hipLaunchKernelGGL((conv_pair_f32_kernel<64, 64, 64, true>), dim3(tiles), dim3(256), 0, ctx->stream, a);
     RTEN_LAUNCH_CHECK(ctx, "conv_pair_f32_kernel (shortcut form) launch");
     return RTEN_HIP_OK;

@@ -197,6 +197,8 @@ int32_t rten_small_c_conv_f32(rten_hip_ctx *ctx, const rten_hip_conv2d_desc *d, 
     a.act = (flags & RTEN_HIP_CONV_RELU) ? RTEN_HIP_ACT_RELU : RTEN_HIP_ACT_NONE;
     const long long tiles = (long long)a.tiles_x * a.tiles_y * d->n;
     if (tiles > 0x7fffffffLL) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "conv: too many output tiles");
+    ProfScope ps(ctx, "conv_small_c_f32_kernel<3,7,7,2>", 2.0 * d->n * (double)d->o * d->out_h * d->out_w * d->c * d->kh * d->kw,
+                 4.0 * ((double)d->n * d->c * d->h * d->w + (double)d->n * d->o * d->out_h * d->out_w));
     hipLaunchKernelGGL((conv_small_c_f32_kernel<3, 7, 7, 2>), dim3((unsigned)tiles), dim3(256), 0, ctx->stream, a);
     RTEN_LAUNCH_CHECK(ctx, "conv_small_c_f32_kernel launch");
     return RTEN_HIP_OK;
