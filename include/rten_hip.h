@@ -604,6 +604,31 @@ int32_t rten_hip_reduce_sum_strided_f32(rten_hip_ctx *ctx, int32_t n_outer, cons
 int32_t rten_hip_reduce_mean_strided_f32(rten_hip_ctx *ctx, int32_t n_outer, const int64_t *outer_shape, const int64_t *outer_strides,
                                          int32_t n_inner, const int64_t *inner_shape, const int64_t *inner_strides,
                                          const float *x, float *y);
+/* The rest of the Reduce* family on a strided view (src/ops/reduce.rs:590-604,653-667,710-732,775-804,1046-1059,1167-1192); kept dims and reduced dims as
+ * for rten_hip_reduce_sum_strided_f32 (<= 6 + 6, element strides, nothing is packed); no host read-back, capture-safe.  Per slice s, float32:
+ *   L1          SumAbs(s): fold_unroll<4> with acc + |x|          SUM_SQUARE  SumSquare(s): fold_unroll<4> with fma(x, x, acc)
+ *   L2          sqrt(SumSquare(s)), one correctly rounded sqrt     LOG_SUM     ln(Sum(s))
+ *   LOG_SUM_EXP m = MaxNum(s) (a NaN anywhere gives NaN); m if it is not finite, otherwise m + ln(SumExpSub(s, m)): one 16-lane accumulator, full-range Exp
+ *   PROD        ((1 * s0) * s1) * ...: one multiply chain in element order
+ * (rten-vecmath/src/sum.rs:37-159; the four accumulators of fold_unroll are merged, and the 16 lanes added from lane 0, by plain adds; ln is the float64
+ * logarithm rounded once to float32).  An empty slice gives 0 (L1, SUM_SQUARE, L2), 1 (PROD) or -inf (LOG_SUM, LOG_SUM_EXP).  RTEN_HIP_DT_I32 is taken
+ * for L1, SUM_SQUARE and PROD (two's complement wrapping arithmetic; |INT32_MIN| stays INT32_MIN); the other kinds give RTEN_HIP_ERR_UNSUPPORTED for it.
+ * y has x's element type. */
+#define RTEN_HIP_REDUCE_L1 0
+#define RTEN_HIP_REDUCE_SUM_SQUARE 1
+#define RTEN_HIP_REDUCE_L2 2
+#define RTEN_HIP_REDUCE_LOG_SUM 3
+#define RTEN_HIP_REDUCE_LOG_SUM_EXP 4
+#define RTEN_HIP_REDUCE_PROD 5
+int32_t rten_hip_reduce_strided(rten_hip_ctx *ctx, int32_t kind, int32_t dtype, int32_t n_outer, const int64_t *outer_shape,
+                                const int64_t *outer_strides, int32_t n_inner, const int64_t *inner_shape, const int64_t *inner_strides,
+                                const void *x, void *y);
+/* LpNormalization (lp_normalization, src/ops/norm.rs:611-650): every lane along one axis is scaled by 1 / norm, norm = SumAbs(lane) (p = 1) or
+ * sqrt(SumSquare(lane)) (p = 2): one correctly rounded division per lane, one multiply per element; a lane whose norm is 0 becomes all zeros.  Lanes start at
+ * sum(c[d] * outer_strides[d]) over the kept-dims coordinate c and step by axis_stride, in x AND in y (y has x's layout; y may be x).  axis_len == 0
+ * writes nothing.  Any other p: RTEN_HIP_ERR_UNSUPPORTED "`p` must be 1 or 2".  Lanes of up to 1024 elements are read once; longer ones twice. */
+int32_t rten_hip_lp_normalize_f32(rten_hip_ctx *ctx, int32_t p, int32_t n_outer, const int64_t *outer_shape, const int64_t *outer_strides,
+                                  int64_t axis_len, int64_t axis_stride, const float *x, float *y);
 /* The selection family on strided views, float32 (RTEN_HIP_DT_F32) and int32 (RTEN_HIP_DT_I32) elements; kept dims and reduced dims as for
  * rten_hip_reduce_sum_strided_f32 (<= 6 + 6, element strides, nothing is packed); no host read-back, capture-safe.
  * ReduceMax / ReduceMin (reduce_max / reduce_min, src/ops/reduce.rs:414-520,876-1044): y[r] = extreme of the slice; a NaN anywhere in the slice gives

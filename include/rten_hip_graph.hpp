@@ -539,6 +539,39 @@ inline HostVal reduce_minmax(const HostVal &x, const std::vector<int> &axes, boo
     }
     return y;
 }
+// int32 ReduceL1 / ReduceSumSquare / ReduceProd of a host value over sorted unique `axes` (dynamic-axes exports take ReduceProd of a Shape): two's complement
+// wrapping arithmetic, as the device kernels and the reference's generic kernels in a release build (src/ops/reduce.rs:782-794,1052-1057,1174-1181); an
+// empty slice gives 0 (Prod: 1).  `kind`: RTEN_HIP_REDUCE_L1 / _SUM_SQUARE / _PROD.
+inline HostVal reduce_i32(const HostVal &x, const std::vector<int> &axes, bool keep_dims, int kind) {
+    const size_t nd = x.shape.size();
+    std::vector<int64_t> kept_stride(nd, 0);
+    HostVal y;
+    y.is_float = false;
+    int64_t acc = 1;
+    for (size_t d = nd; d-- > 0;) {
+        const bool red = std::find(axes.begin(), axes.end(), (int)d) != axes.end();
+        if (!red) { kept_stride[d] = acc; acc *= x.shape[d]; }
+    }
+    for (size_t d = 0; d < nd; d++) {
+        const bool red = std::find(axes.begin(), axes.end(), (int)d) != axes.end();
+        if (!red) y.shape.push_back(x.shape[d]);
+        else if (keep_dims) y.shape.push_back(1);
+    }
+    std::vector<uint32_t> r((size_t)acc, kind == RTEN_HIP_REDUCE_PROD ? 1u : 0u);
+    std::vector<int64_t> idx(nd, 0);
+    for (int64_t e = 0, n = x.len(); e < n; e++) {
+        int64_t o = 0;
+        for (size_t d = 0; d < nd; d++) o += idx[d] * kept_stride[d];
+        const uint32_t v = (uint32_t)(int32_t)x.i[(size_t)e];
+        uint32_t &a = r[(size_t)o];
+        if (kind == RTEN_HIP_REDUCE_L1) a += (v & 0x80000000u) ? 0u - v : v;
+        else if (kind == RTEN_HIP_REDUCE_SUM_SQUARE) a += v * v;
+        else a *= v;
+        for (size_t d = nd; d-- > 0;) { if (++idx[d] < x.shape[d]) break; idx[d] = 0; }
+    }
+    for (uint32_t v : r) y.i.push_back((int64_t)(int32_t)v);
+    return y;
+}
 // ---- unary math of a host value, with the device's semantics (all exact in C++): Neg / Abs / Sign for both types (int32 wraps: i32::MIN stays; float Sign is
 // Rust's signum: +0 -> 1, -0 -> -1, NaN -> NaN), Floor / Ceil / Round (ties to even) / Sqrt / Reciprocal for float32.  false: not this operator / type.
 inline bool unary(const std::string &op, const HostVal &x, HostVal &out) {
@@ -978,6 +1011,30 @@ class Graph {
         if (const onnx::TensorProto *t = initializer_named(m, n.inputs[0])) et = t->data_type;
         else if (const onnx::ValueInfo *gi = graph_input_named(m, n.inputs[0])) et = gi->elem_type;
         if (et == onnx::INT32 || et == onnx::INT64) throw GraphError("Pow " + label + ": an int32 base is not supported by the device path (float32 base and exponent only)");
+    }
+    // The Reduce* kinds make_reduce_step takes beyond Sum / Mean / Max / Min, as the RTEN_HIP_REDUCE_* kernel each runs; -1: not one of them
+    static int reduce_family_kind(const std::string &k) {
+        static const std::map<std::string, int> kinds = {{"ReduceL1", RTEN_HIP_REDUCE_L1}, {"ReduceSumSquare", RTEN_HIP_REDUCE_SUM_SQUARE}, {"ReduceL2", RTEN_HIP_REDUCE_L2},
+                                                         {"ReduceLogSum", RTEN_HIP_REDUCE_LOG_SUM}, {"ReduceLogSumExp", RTEN_HIP_REDUCE_LOG_SUM_EXP}, {"ReduceProd", RTEN_HIP_REDUCE_PROD}};
+        auto it = kinds.find(k);
+        return it == kinds.end() ? -1 : it->second;
+    }
+    // What the loader reads from, and refuses about, an LpNormalization node (onnx_registry.rs:1284-1287: axis defaults to -1, p to 2; any other p is the
+    // operator's UnsupportedValue, norm.rs:644-646: no point in loading such a model).  Needs no device; rten_hip_run --parse-only calls it too.
+    struct LpNormNode { int axis = -1, p = 2; };
+    static LpNormNode read_lp_norm_node(const onnx::Node &n, const std::string &label) {
+        LpNormNode a;
+        a.axis = (int)n.get_int("axis", -1);
+        const int64_t p = n.get_int("p", 2);
+        if (p != 1 && p != 2) throw GraphError("LpNormalization " + label + ": p = " + std::to_string(p) + " is not supported (`p` must be 1 or 2)");
+        a.p = (int)p;
+        return a;
+    }
+    // What the loader refuses about a Reduce* node of reduce_family_kind: axes that are neither an attribute nor a constant input are found when the plan
+    // is built (read_reduce_attrs); here, without a device, an axes input that is a graph input (device data at run time).
+    static void check_reduce_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        if (n.inputs.size() > 1 && !n.inputs[1].empty() && graph_input_named(m, n.inputs[1]))
+            throw GraphError(n.op_type + " " + label + ": the axes input must be a constant (it is the graph input \"" + n.inputs[1] + "\", device data at run time)");
     }
     static bool is_math_kind(const std::string &k) {
         static const std::set<std::string> kinds = {"Neg", "Abs", "Sign", "Floor", "Ceil", "Round", "Sqrt", "Reciprocal", "Exp", "Log", "Softplus", "Pow", "PRelu", "Min", "Max", "Sum", "Mean"};
@@ -1651,8 +1708,10 @@ class Graph {
             throw GraphError("a shape-dependent constant changed between the warm-up run and the capture (input shapes must stay fixed while a graph is captured)");
         auto h = std::make_shared<const HostVal>(std::move(hv));
         std::unique_ptr<Tensor> t;
-        if (h->is_float) t.reset(new Tensor(Tensor::from_host<float>(c, h->shape, h->f.data())));
-        else { std::vector<int32_t> w(h->i.begin(), h->i.end()); t.reset(new Tensor(Tensor::from_host<int32_t>(c, h->shape, w.data()))); }
+        // (not from the pool: the cached copy stays, and a pool buffer taken here -- say the 8 bytes of a [2] shape vector, which are also the 8 bytes of a
+        //  [2, 1] activation -- would be missing in the captured run that follows, whose first request of that size would then allocate inside the capture)
+        if (h->is_float) t.reset(new Tensor(Tensor::from_host_unpooled<float>(c, h->shape, h->f.data())));
+        else { std::vector<int32_t> w(h->i.begin(), h->i.end()); t.reset(new Tensor(Tensor::from_host_unpooled<int32_t>(c, h->shape, w.data()))); }
         if (cache.entries.size() >= 8) cache.entries.erase(cache.entries.begin()); // (shapes changed a few times: keep the recent ones)
         cache.entries.emplace_back(h, std::move(t));
         Tensor v = Tensor::view_of(*cache.entries.back().second, h->shape);
@@ -2314,7 +2373,16 @@ class Graph {
                 if (!n.attr("equation")) throw GraphError("Einsum " + st.name + ": the equation attribute is missing");
                 op->equation = n.attr("equation")->s;
                 run_plainly(st, op);
-            } else if (kind == "ReduceSum" || kind == "ReduceMean" || kind == "ReduceMax" || kind == "ReduceMin") make_reduce_step(st, n);
+            } else if (kind == "ReduceSum" || kind == "ReduceMean" || kind == "ReduceMax" || kind == "ReduceMin" || reduce_family_kind(kind) >= 0) make_reduce_step(st, n);
+            else if (kind == "LpNormalization") {
+                const LpNormNode a = read_lp_norm_node(n, st.name);
+                auto op = std::make_shared<LpNormalization>();
+                op->axis = a.axis;
+                op->p = a.p;
+                st.batch_coupled = op->axis == 0; // (a negative axis that resolves to dim 0 is a run-time fact: note_axis)
+                const std::string nm = st.name;
+                st.run = [this, op, nm](Context &c, const InputList &in) { note_axis("LpNormalization", nm, op->axis, require(in, 0)); return op->run(c, in); };
+            } else if (kind == "GlobalMaxPool") run_plainly(st, std::make_shared<GlobalMaxPool>()); // per (n, c) plane: rows of the batch are independent
             else if (kind == "ArgMax" || kind == "ArgMin" || kind == "TopK" || kind == "Softmax") make_select_step(st, n);
             else if (kind == "Resize" || kind == "Upsample") make_resize_step(st, n);
             else if (kind == "Split") make_split_step(st, n);
@@ -2591,7 +2659,8 @@ class Graph {
         if (n.op_type == "MaxPool") st.maxpool = finish(std::make_shared<MaxPool>());
         else finish(std::make_shared<AveragePool>())->count_include_pad = n.get_int("count_include_pad", 0) != 0;
     }
-    // ReduceSum / ReduceMean, and ReduceMax / ReduceMin (which shape arithmetic sometimes applies to a shape vector: those run on the host)
+    // ReduceSum / ReduceMean; ReduceMax / ReduceMin and the int32 forms of ReduceL1 / ReduceSumSquare / ReduceProd (which shape arithmetic sometimes applies to a
+    // shape vector: those run on the host); ReduceL2 / ReduceLogSum / ReduceLogSumExp.  Coupled to the batch exactly when dim 0 is reduced (read_reduce_attrs).
     void make_reduce_step(Step &st, const onnx::Node &n) {
         const std::string kind = n.op_type, nm = st.name;
         if (kind == "ReduceSum" || kind == "ReduceMean") {
@@ -2599,6 +2668,31 @@ class Graph {
             op->mean = kind == "ReduceMean";
             read_reduce_attrs(st, n, *op);
             st.run = [this, op, kind, nm](Context &c, const InputList &in) { for (int a : op->axes) note_axis(kind, nm, a, require(in, 0)); return op->run(c, in); };
+            return;
+        }
+        if (const int rk = reduce_family_kind(kind); rk >= 0) {
+            std::shared_ptr<Reduce> op;
+            switch (rk) {
+            case RTEN_HIP_REDUCE_L1: op = std::make_shared<ReduceL1>(); break;
+            case RTEN_HIP_REDUCE_SUM_SQUARE: op = std::make_shared<ReduceSumSquare>(); break;
+            case RTEN_HIP_REDUCE_L2: op = std::make_shared<ReduceL2>(); break;
+            case RTEN_HIP_REDUCE_LOG_SUM: op = std::make_shared<ReduceLogSum>(); break;
+            case RTEN_HIP_REDUCE_LOG_SUM_EXP: op = std::make_shared<ReduceLogSumExp>(); break;
+            default: op = std::make_shared<ReduceProd>(); break;
+            }
+            read_reduce_attrs(st, n, *op);
+            auto cache = std::make_shared<HostCache>();
+            st.run = [this, op, kind, nm, rk, cache](Context &c, const InputList &in) {
+                const Tensor &x = require(in, 0);
+                for (int a : op->axes) note_axis(kind, nm, a, x);
+                // shape arithmetic (ReduceProd of a Shape): int32 host values stay on the host
+                if (op->int32 && x.host() && !x.host()->is_float && x.ndim() > 0 && !(op->axes.empty() && op->noop_with_empty_axes)) {
+                    OutputList o;
+                    o.push_back(materialize(c, hostops::reduce_i32(*x.host(), resolve_axes(op->axes, x.ndim()), op->keep_dims, rk), *cache));
+                    return o;
+                }
+                return op->run(c, in);
+            };
             return;
         }
         auto op = std::make_shared<ReduceMax>();

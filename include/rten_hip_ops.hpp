@@ -83,6 +83,13 @@ class Context {
         check(rten_hip_malloc(h_, bytes, &p));
         return p;
     }
+    // A buffer that does NOT come from the pool (it returns to it when released): for values that outlive the run that makes them -- taken from the pool,
+    // such a buffer would leave the next run one buffer of its size short.
+    void *alloc_unpooled(size_t bytes) {
+        void *p = nullptr;
+        check(rten_hip_malloc(h_, bytes, &p));
+        return p;
+    }
     void release(void *p, size_t bytes) {
         if (!p) return;
         if (pool_on_) { std::lock_guard<std::mutex> lk(pool_mu_); pool_[bytes].push_back(p); }
@@ -185,6 +192,16 @@ class Tensor {
     template <typename T>
     static Tensor from_host(Context &ctx, std::vector<int64_t> shape, const T *data) {
         Tensor t(ctx, std::move(shape), dtype_of<T>());
+        if (t.bytes()) ctx.check(rten_hip_memcpy_h2d(ctx.raw(), t.ptr_, data, t.bytes()));
+        return t;
+    }
+    // ... into a buffer of its own rather than one of the pool's (Context::alloc_unpooled): a value a step keeps across runs
+    template <typename T>
+    static Tensor from_host_unpooled(Context &ctx, std::vector<int64_t> shape, const T *data) {
+        Tensor t;
+        t.ctx_ = &ctx; t.shape_ = std::move(shape); t.dtype_ = dtype_of<T>();
+        t.cap_ = std::max<size_t>(t.bytes(), 4);
+        t.ptr_ = ctx.alloc_unpooled(t.cap_);
         if (t.bytes()) ctx.check(rten_hip_memcpy_h2d(ctx.raw(), t.ptr_, data, t.bytes()));
         return t;
     }
@@ -2689,6 +2706,117 @@ struct ReduceMin : ReduceMax { // src/ops/reduce.rs:907-975
     ReduceMin() { min = true; }
 };
 
+// ReduceL1 / ReduceSumSquare / ReduceL2 / ReduceLogSum / ReduceLogSumExp / ReduceProd (src/ops/reduce.rs:590-845, 1046-1100, 1167-1234) around one kernel
+// of rten_hip_reduce_strided (rten_amd/csrc/reduce.hip): axes as the attribute or the second input; a 0-d input is a slice of one element; an empty slice
+// gives the kernel's value for it.  With noop_with_empty_axes and no axes the reduction is skipped but the operator's element map still applies:
+// L1 |x|, SumSquare x * x, LogSum ln(x), the others a copy.
+struct Reduce : Operator {
+    int kind;
+    const char *nm;
+    bool int32;       // the reference also takes Int32Tensor (its generic kernels: wrapping arithmetic)
+    bool typed_first; // the operand's type is checked before noop_with_empty_axes is looked at (map_value_view! / require_as outside the test)
+    bool cast_error;  // float32 only through require_as (its cast error) rather than map_value_view! (UnsupportedType)
+    std::vector<int> axes;
+    bool keep_dims = true, noop_with_empty_axes = false;
+    Reduce(int k, const char *n, bool i32, bool tf, bool ce) : kind(k), nm(n), int32(i32), typed_first(tf), cast_error(ce) {}
+    const char *name() const override { return nm; }
+    int max_inputs() const override { return 2; }
+    void check_type(const Tensor &x) const {
+        if (x.dtype() == DType::F32 || (int32 && x.dtype() == DType::I32)) return;
+        if (cast_error) want(x, DType::F32, "float32");
+        throw OpError(OpError::UnsupportedType, "");
+    }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        namespace E = einsum_detail;
+        namespace S = select_detail;
+        const Tensor &x = require(in, 0);
+        std::vector<int> given = axes;
+        if (const Tensor *a = get(in, 1)) { given.clear(); for (int64_t e : S::host_ints(*a)) given.push_back((int)e); }
+        if (typed_first) check_type(x);
+        OutputList out;
+        if (given.empty() && noop_with_empty_axes) {
+            if (dtype_size(x.dtype()) != 4) throw OpError(OpError::UnsupportedType, "");
+            InputList self{&x};
+            if (kind == RTEN_HIP_REDUCE_L1) return Abs().run(ctx, self);
+            if (kind == RTEN_HIP_REDUCE_LOG_SUM) return Log().run(ctx, self);
+            if (kind == RTEN_HIP_REDUCE_SUM_SQUARE) out.push_back(broadcast_binary(ctx, x, x, 1, RTEN_HIP_EW_IMUL));
+            else out.push_back(E::materialize(ctx, E::View::of(x), x.dtype()));
+            return out;
+        }
+        check_type(x);
+        const int nd = x.ndim();
+        if (nd == 0) for (int a : given) resolve_axis(a, 0);
+        const std::vector<int> ax = nd ? resolve_axes(given, nd) : std::vector<int>();
+        const E::View v = E::View::of(x);
+        const S::Split2 d = S::split_dims(v, ax);
+        Tensor y(ctx, d.kshape, x.dtype());
+        if (y.len())
+            ctx.check(rten_hip_reduce_strided(ctx.raw(), kind, S::abi_dtype(x), (int)d.mo.size(), d.mo.data(), d.mos[0].data(), (int)d.mi.size(), d.mi.data(), d.mis[0].data(),
+                                              v.p, y.ptr()));
+        if (keep_dims) {
+            std::vector<int64_t> s = x.shape();
+            for (int a : ax) s[(size_t)a] = 1;
+            y.reshape(s);
+        }
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+struct ReduceL1 : Reduce { ReduceL1() : Reduce(RTEN_HIP_REDUCE_L1, "ReduceL1", true, true, false) {} };                             // reduce.rs:775-845
+struct ReduceSumSquare : Reduce { ReduceSumSquare() : Reduce(RTEN_HIP_REDUCE_SUM_SQUARE, "ReduceSumSquare", true, true, false) {} }; // reduce.rs:1167-1234
+struct ReduceL2 : Reduce { ReduceL2() : Reduce(RTEN_HIP_REDUCE_L2, "ReduceL2", false, false, false) {} };                            // reduce.rs:590-651
+struct ReduceLogSum : Reduce { ReduceLogSum() : Reduce(RTEN_HIP_REDUCE_LOG_SUM, "ReduceLogSum", false, true, true) {} };             // reduce.rs:653-708
+struct ReduceLogSumExp : Reduce { ReduceLogSumExp() : Reduce(RTEN_HIP_REDUCE_LOG_SUM_EXP, "ReduceLogSumExp", false, true, true) {} }; // reduce.rs:710-773
+struct ReduceProd : Reduce { ReduceProd() : Reduce(RTEN_HIP_REDUCE_PROD, "ReduceProd", true, false, false) {} };                     // reduce.rs:1046-1100
+
+// LpNormalization (src/ops/norm.rs:611-693): every lane along `axis` times 1 / norm, norm = SumAbs (p = 1) or sqrt(SumSquare) (p = 2); a zero norm zeroes
+// the lane.  Defaults as the reference's loader (onnx_registry.rs:1284-1287).  Lanes along a non-last axis are read and written through the axis stride.
+struct LpNormalization : Operator {
+    int axis = -1, p = 2;
+    const char *name() const override { return "LpNormalization"; }
+    int max_inputs() const override { return 1; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        namespace E = einsum_detail;
+        const Tensor &x = want(require(in, 0), DType::F32, "float32");
+        if (p != 1 && p != 2) throw OpError(OpError::UnsupportedValue, "`p` must be 1 or 2");
+        const int a = resolve_axis(axis, x.ndim());
+        Tensor y(ctx, x.shape(), DType::F32);
+        if (x.len()) {
+            const E::View v = E::View::of(x);
+            const select_detail::Split2 d = select_detail::split_dims(v, {a});
+            ctx.check(rten_hip_lp_normalize_f32(ctx.raw(), p, (int)d.mo.size(), d.mo.data(), d.mos[0].data(), v.shape[(size_t)a], v.strides[(size_t)a], v.p, (float *)y.ptr()));
+        }
+        OutputList out;
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+
+// GlobalMaxPool (src/ops/pooling.rs:477-514,549-580): MaxNum over dims 2.. of an input of at least 2 dims, output [N, C, 1, ...]
+struct GlobalMaxPool : Operator {
+    const char *name() const override { return "GlobalMaxPool"; }
+    int max_inputs() const override { return 1; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        namespace E = einsum_detail;
+        const Tensor &x = want(require(in, 0), DType::F32, "float32");
+        if (x.ndim() < 2) throw OpError(OpError::InvalidValue, "Input must have at least 2 dims");
+        std::vector<int> ax;
+        for (int d = 2; d < x.ndim(); d++) ax.push_back(d);
+        const E::View v = E::View::of(x);
+        const select_detail::Split2 d = select_detail::split_dims(v, ax);
+        std::vector<int64_t> s(x.shape().size(), 1);
+        s[0] = x.size(0);
+        s[1] = x.size(1);
+        Tensor y(ctx, s, DType::F32);
+        if (y.len())
+            ctx.check(rten_hip_reduce_minmax_strided(ctx.raw(), RTEN_HIP_SELECT_MAX, RTEN_HIP_DT_F32, (int)d.mo.size(), d.mo.data(), d.mos[0].data(), (int)d.mi.size(), d.mi.data(),
+                                                     d.mis[0].data(), v.p, y.ptr()));
+        OutputList out;
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+
 struct ArgMax : Operator { // src/ops/reduce.rs:64-160: the FIRST NaN of a lane that holds one, otherwise the LAST element equal to the extreme
     int axis = 0;
     bool keep_dims = true, min = false;
@@ -2948,6 +3076,14 @@ class OpRegistry {
         r.register_op<Pad>("Pad");
         r.register_op<QuantizeLinear>("QuantizeLinear");
         r.register_op<DequantizeLinear>("DequantizeLinear");
+        r.register_op<ReduceL1>("ReduceL1");
+        r.register_op<ReduceL2>("ReduceL2");
+        r.register_op<ReduceSumSquare>("ReduceSumSquare");
+        r.register_op<ReduceLogSum>("ReduceLogSum");
+        r.register_op<ReduceLogSumExp>("ReduceLogSumExp");
+        r.register_op<ReduceProd>("ReduceProd");
+        r.register_op<LpNormalization>("LpNormalization");
+        r.register_op<GlobalMaxPool>("GlobalMaxPool");
         return r;
     }
 

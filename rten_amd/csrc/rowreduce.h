@@ -8,7 +8,7 @@
 
 static __device__ __forceinline__ float lane_bcast(float v, int src_lane) { return __shfl(v, src_lane, 64); }
 
-// fold_unroll<4> order (sum.rs:27-33,110-127).  kind 0: sum x ; kind 1: sum (x-off)^2 via mul_add.
+// fold_unroll<4> order (sum.rs:27-33,60-66,86-92,110-127).  kind 0: sum x ; kind 1: sum (x-off)^2 via mul_add (off = 0: SumSquare) ; kind 2: sum |x|.
 // `get(i)` returns element i (i < n).  All lanes return the same total.
 // BATCH > 1: the chain of adds is unchanged (one accumulator per lane, chunks in order), but BATCH chunks are requested before the first of them is
 // added -- for a `get` that reads memory, a load per add is one round trip per 256 bytes.
@@ -16,7 +16,8 @@ template <int KIND, int BATCH = 1, typename Get, typename Index>
 __device__ __forceinline__ float simd16_reduce(Get get, Index n, float off, int lane) {
     auto f = [&](float acc, float x) -> float {
         if constexpr (KIND == 0) return acc + x;
-        else { const float d = x - off; return vm::fma(d, d, acc); }
+        else if constexpr (KIND == 1) { const float d = x - off; return vm::fma(d, d, acc); }
+        else return acc + __builtin_fabsf(x);
     };
     float acc = 0.f;
     const Index full4 = n / 64;

@@ -457,153 +457,6 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void global_avg_pool_rows16_ke
     if (l == 15 && row < rows) y[row] = acc / (float)inner;
 }
 
-// ReduceSum over a strided view (src/ops/reduce.rs:414-520,1101-1124): output element r = vecmath::Sum of the reduced
-// slice, whose elements are the reduced axes walked in row-major order -- the order in which the reference packs a
-// non-contiguous slice before calling the kernel (reduce.rs:470-505).  The view is read in place through its strides
-// (stride 0 = broadcast axis, summed strides = a diagonal): nothing is packed.
-struct ReduceArgs {
-    int n_outer, n_inner;
-    int64_t rows;
-    int inner;
-    float divisor; // 0: ReduceSum; slice length: ReduceMean = Sum / len (reduce.rs:532-537)
-    int32_t oshape[6], ishape[6];
-    int64_t ostride[6], istride[6];
-};
-
-// (The outermost kept axis needs no division -- what is left of the row index IS its coordinate -- and a 64-bit division is ~100 instructions on this
-// machine: with one per row the last-axis kernels were division-bound, 10 us for 49152 rows of 128.  32-bit arithmetic whenever the row count allows.)
-__device__ __forceinline__ int64_t reduce_row_base(const ReduceArgs &p, int64_t row) {
-    if (p.n_outer <= 0) return 0;
-    int64_t off = 0;
-    if (p.rows <= 0x7fffffff) {
-        unsigned r = (unsigned)row;
-        for (int d = p.n_outer - 1; d > 0; d--) {
-            const unsigned q = r / (unsigned)p.oshape[d];
-            off += (int64_t)(r - q * (unsigned)p.oshape[d]) * p.ostride[d];
-            r = q;
-        }
-        return off + (int64_t)r * p.ostride[0];
-    }
-    int64_t r = row;
-    for (int d = p.n_outer - 1; d > 0; d--) {
-        const int64_t q = r / p.oshape[d];
-        off += (r - q * p.oshape[d]) * p.ostride[d];
-        r = q;
-    }
-    return off + r * p.ostride[0];
-}
-
-__device__ __forceinline__ int64_t reduce_elem_off(const ReduceArgs &p, int i) {
-    if (p.n_inner == 1) return (int64_t)i * p.istride[0];
-    int r = i;
-    int64_t off = 0;
-    for (int d = p.n_inner - 1; d >= 0; d--) {
-        const int q = r / p.ishape[d];
-        off += (int64_t)(r - q * p.ishape[d]) * p.istride[d];
-        r = q;
-    }
-    return off;
-}
-
-__global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void reduce_sum_kernel(const ReduceArgs p, const float *__restrict__ x,
-                                                                         float *__restrict__ y) {
-    const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    if (row >= p.rows) return;
-    const float *xr = x + reduce_row_base(p, row);
-    auto get = [&](int i) -> float { return xr[reduce_elem_off(p, i)]; };
-    const float s = simd16_reduce<0>(get, p.inner, 0.f, lane);
-    if (lane == 0) y[row] = p.divisor != 0.f ? s / p.divisor : s;
-}
-
-// Slices of at most 16 * EPL elements: four output elements per wave, one per 16-lane DPP row (global_avg_pool_rows16_kernel's
-// scheme).  Lane l owns elements l + 16 q -- the ones the reference's accumulator lane l adds: the first 4 * (n / 64) of them
-// go round-robin into the four unrolled accumulators, which fold left to right; the rest (whole vectors, masked tail) are
-// added to the folded value one by one (rten-simd/src/iter.rs:97-120).
-template <int EPL>
-__global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void reduce_sum_rows16_kernel(const ReduceArgs p, const float *__restrict__ x,
-                                                                                float *__restrict__ y) {
-    const int lane = threadIdx.x & 63, l = lane & 15;
-    const int64_t row = ((int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6)) * 4 + (lane >> 4);
-    const int64_t rr = row < p.rows ? row : p.rows - 1;
-    const float *xr = x + reduce_row_base(p, rr);
-    float v[EPL];
-#pragma unroll
-    for (int q = 0; q < EPL; q++) v[q] = xr[reduce_elem_off(p, l + 16 * q < p.inner ? l + 16 * q : 0)];
-    const int unrolled = (p.inner >> 6) * 4;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < EPL; q++)
-        if (q < unrolled) acc[q & 3] = acc[q & 3] + v[q];
-    float a = ((acc[0] + acc[1]) + acc[2]) + acc[3];
-#pragma unroll
-    for (int q = 0; q < EPL; q++)
-        if (q >= unrolled && l + 16 * q < p.inner) a = a + v[q];
-    float s = a;
-#pragma unroll
-    for (int k = 1; k < 16; k++) s = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x111, 0xf, 0xf, true)) + a;
-    if (l == 15 && row < p.rows) y[row] = p.divisor != 0.f ? s / p.divisor : s;
-}
-
-// Reduced axes strided, innermost kept axis contiguous (a column sum): a wave-per-row walk would touch 64 cache lines per
-// load.  Here a 1024-thread workgroup owns 16 adjacent output elements j; wave w is the reference's accumulator lane l = w and
-// its lanes are (u = unrolled accumulator, j): every load instruction reads four 64-byte runs.  Each thread's chain is the
-// reference's acc[u][l]; the fold over u is three lane shuffles, the in-order sum over l goes through LDS.
-__global__ __launch_bounds__(1024) void reduce_sum_cols_kernel(const ReduceArgs p, const float *__restrict__ x, float *__restrict__ y) {
-    __shared__ float part[16][16];
-    const int lane = threadIdx.x & 63, l = threadIdx.x >> 6, u = lane >> 4, j = lane & 15;
-    const int last = p.oshape[p.n_outer - 1];
-    const int groups = (last + 15) >> 4;
-    // Two neighbouring column groups read the two 64-byte halves of the same 128-byte lines.  Workgroup ids go round-robin over the eight XCDs, so
-    // neighbours in id order never share an L2 and every line is fetched twice; here each XCD gets a CONTIGUOUS run of groups (ids id, id + 8, ...
-    // are dispatched to the same XCD one after the other), and the second half of a line is an L2 hit.
-    unsigned bid = blockIdx.x;
-    {
-        const unsigned nt = gridDim.x, xcd = bid & 7, qn = nt >> 3, rn = nt & 7;
-        bid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (bid >> 3);
-    }
-    const int64_t prefix = bid / groups;
-    const int j0 = (int)(bid - prefix * groups) * 16;
-    const int jj = j0 + j < last ? j0 + j : last - 1;
-    const int64_t row = prefix * last + jj;
-    const float *xr = x + reduce_row_base(p, row);
-    const int n = p.inner, full4 = n >> 6;
-    // The chain of adds is the reference's (one accumulator, elements in order); the LOADS are independent, so eight are requested before the
-    // first add -- a load per add made this kernel one memory round trip per element (31.5 us for 4096 x 3072 -> 3072: round 3).
-    float acc = 0.f;
-    int c = 0;
-    for (; c + 16 <= full4; c += 16) {
-        float tv[16];
-#pragma unroll
-        for (int k = 0; k < 16; k++) tv[k] = xr[reduce_elem_off(p, (c + k) * 64 + u * 16 + l)];
-#pragma unroll
-        for (int k = 0; k < 16; k++) acc = acc + tv[k];
-    }
-    for (; c + 8 <= full4; c += 8) {
-        float tv[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) tv[k] = xr[reduce_elem_off(p, (c + k) * 64 + u * 16 + l)];
-#pragma unroll
-        for (int k = 0; k < 8; k++) acc = acc + tv[k];
-    }
-    for (; c < full4; c++) acc = acc + xr[reduce_elem_off(p, c * 64 + u * 16 + l)];
-    float a = lane_bcast(acc, j);
-    a = a + lane_bcast(acc, j + 16);
-    a = a + lane_bcast(acc, j + 32);
-    a = a + lane_bcast(acc, j + 48);
-    int i0 = full4 * 64;
-    for (; i0 + 16 <= n; i0 += 16) a = a + xr[reduce_elem_off(p, i0 + l)];
-    if (i0 + l < n) a = a + xr[reduce_elem_off(p, i0 + l)];
-    if (u == 0) part[l][j] = a;
-    __syncthreads();
-    if (threadIdx.x < 16 && j0 + (int)threadIdx.x < last) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; k++) s = s + part[k][threadIdx.x];
-        y[prefix * last + j0 + threadIdx.x] = p.divisor != 0.f ? s / p.divisor : s;
-    }
-}
-
 } // namespace
 
 RTEN_EXPORT int32_t rten_hip_softmax_f32(rten_hip_ctx *ctx, int64_t rows, int32_t cols, const float *x,
@@ -708,65 +561,4 @@ RTEN_EXPORT int32_t rten_hip_global_average_pool_f32(rten_hip_ctx *ctx, int64_t 
         hipLaunchKernelGGL(global_avg_pool_kernel, grid, block, 0, ctx->stream, nc, inner, x, y);
     RTEN_LAUNCH_CHECK(ctx, "global_avg_pool_kernel");
     return RTEN_HIP_OK;
-}
-
-static int32_t reduce_strided(rten_hip_ctx *ctx, bool mean, int32_t n_outer, const int64_t *outer_shape, const int64_t *outer_strides,
-                              int32_t n_inner, const int64_t *inner_shape, const int64_t *inner_strides, const float *x, float *y) {
-    RTEN_CHECK_CTX(ctx);
-    if (n_outer < 0 || n_outer > 6 || n_inner < 0 || n_inner > 6 || (n_outer && (!outer_shape || !outer_strides)) ||
-        (n_inner && (!inner_shape || !inner_strides)))
-        return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "reduce_sum: at most 6 kept and 6 reduced dims");
-    ReduceArgs p = {};
-    p.n_outer = n_outer;
-    p.n_inner = n_inner > 0 ? n_inner : 1;
-    p.rows = 1;
-    int64_t inner = 1;
-    for (int d = 0; d < n_outer; d++) {
-        if (outer_shape[d] < 0 || outer_shape[d] > 0x7fffffff || outer_strides[d] < 0) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "reduce_sum: bad dimension");
-        p.oshape[d] = (int32_t)outer_shape[d];
-        p.ostride[d] = outer_strides[d];
-        p.rows *= outer_shape[d];
-    }
-    p.ishape[0] = 1;
-    for (int d = 0; d < n_inner; d++) {
-        if (inner_shape[d] < 0 || inner_strides[d] < 0) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "reduce_sum: bad dimension");
-        inner *= inner_shape[d];
-        if (inner > 0x7fffffff) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "reduce_sum: reduced slice longer than 2^31 - 1");
-        p.ishape[d] = (int32_t)inner_shape[d];
-        p.istride[d] = inner_strides[d];
-    }
-    p.inner = (int)inner;
-    p.divisor = mean ? (float)inner : 0.f;
-    if (p.rows == 0) return RTEN_HIP_OK;
-    if (!y) return RTEN_HIP_ERR_INVALID_VALUE;
-    if (inner == 0) { // an empty slice gives the kernel's value for it (reduce.rs:446-452): Sum 0, Mean 0 / 0 = NaN
-        RTEN_HIP_TRY(ctx, hipMemsetAsync(y, mean ? 0xff : 0, sizeof(float) * (size_t)p.rows, ctx->stream));
-        return RTEN_HIP_OK;
-    }
-    if (!x) return RTEN_HIP_ERR_INVALID_VALUE;
-    const dim3 block(64 * ROWS_PER_BLOCK);
-    ProfScope ps(ctx, "reduce_sum_f32", 0.0, 4.0 * p.rows * (inner + 1));
-    const dim3 grid16((unsigned)((p.rows + 4 * ROWS_PER_BLOCK - 1) / (4 * ROWS_PER_BLOCK)));
-    const int64_t last = n_outer ? p.oshape[n_outer - 1] : 1;
-    if (inner > 64 && n_outer && p.ostride[n_outer - 1] == 1 && last >= 16 && p.istride[p.n_inner - 1] > 1)
-        hipLaunchKernelGGL(reduce_sum_cols_kernel, dim3((unsigned)(p.rows / last * ((last + 15) / 16))), dim3(1024), 0, ctx->stream, p, x, y);
-    else if (inner <= 64) hipLaunchKernelGGL(reduce_sum_rows16_kernel<4>, grid16, block, 0, ctx->stream, p, x, y);
-    else if (inner <= 128) hipLaunchKernelGGL(reduce_sum_rows16_kernel<8>, grid16, block, 0, ctx->stream, p, x, y);
-    else if (inner <= 256) hipLaunchKernelGGL(reduce_sum_rows16_kernel<16>, grid16, block, 0, ctx->stream, p, x, y);
-    else
-        hipLaunchKernelGGL(reduce_sum_kernel, dim3((unsigned)((p.rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), block, 0, ctx->stream, p, x, y);
-    RTEN_LAUNCH_CHECK(ctx, "reduce_sum_kernel");
-    return RTEN_HIP_OK;
-}
-
-RTEN_EXPORT int32_t rten_hip_reduce_sum_strided_f32(rten_hip_ctx *ctx, int32_t n_outer, const int64_t *outer_shape, const int64_t *outer_strides,
-                                                    int32_t n_inner, const int64_t *inner_shape, const int64_t *inner_strides,
-                                                    const float *x, float *y) {
-    return reduce_strided(ctx, false, n_outer, outer_shape, outer_strides, n_inner, inner_shape, inner_strides, x, y);
-}
-
-RTEN_EXPORT int32_t rten_hip_reduce_mean_strided_f32(rten_hip_ctx *ctx, int32_t n_outer, const int64_t *outer_shape, const int64_t *outer_strides,
-                                                     int32_t n_inner, const int64_t *inner_shape, const int64_t *inner_strides,
-                                                     const float *x, float *y) {
-    return reduce_strided(ctx, true, n_outer, outer_shape, outer_strides, n_inner, inner_shape, inner_strides, x, y);
 }

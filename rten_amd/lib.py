@@ -37,7 +37,7 @@ UNARY_NEG, UNARY_ABS, UNARY_SIGN, UNARY_FLOOR, UNARY_CEIL, UNARY_ROUND, UNARY_SQ
 BINARY_ADD, BINARY_MUL, BINARY_SUB, BINARY_DIV, BINARY_MIN, BINARY_MAX, BINARY_POW, BINARY_PRELU = range(8)
 # element types and the operator codes of rten_hip_elementwise_nd that the Python operators use (RTEN_HIP_DT_*, RTEN_HIP_EW_*)
 DT_F32, DT_I32, DT_U8, DT_I8 = 0, 1, 2, 3
-EW_IADD, EW_INEG, EW_IABS, EW_ISIGN, EW_IMIN, EW_IMAX = 11, 15, 16, 17, 18, 19
+EW_IADD, EW_IMUL, EW_INEG, EW_IABS, EW_ISIGN, EW_IMIN, EW_IMAX = 11, 13, 15, 16, 17, 18, 19
 # mode of rten_hip_pad_b32 (RTEN_HIP_PAD_*)
 PAD_CONSTANT, PAD_REFLECT, PAD_EDGE, PAD_WRAP = 0, 1, 2, 3
 MODEL_RECEIVE_WEIGHTS = 1  # rten_hip_model_load_ex flag
@@ -207,6 +207,8 @@ PROTOTYPES = {
     "rten_hip_reduce_sum_strided_f32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_reduce_mean_strided_f32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_reduce_minmax_strided": (_I32, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
+    "rten_hip_reduce_strided": (_I32, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
+    "rten_hip_lp_normalize_f32": (_I32, [_VP, _I32, _I32, _VP, _VP, _I64, _I64, _VP, _VP]),
     "rten_hip_arg_minmax_strided": (_I32, [_VP, _I32, _I32, _I32, _VP, _VP, _I64, _I64, _VP, _VP]),
     "rten_hip_topk_strided": (_I32, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _I64]),
     "rten_hip_conv_transpose_output_size": (_I32, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP]),

@@ -548,3 +548,39 @@ def resnet50_qdq(weights, batch="batch", image: int = 224, calibration_image: in
     g.q["folded"] = len(g.q["weight"]) + len(g.q["bias"])
     g.q["pairs"] = len(g.q["act"])
     return model(g.nodes, [value_info("x", FLOAT, [batch, 3, image, image])], [value_info(out, FLOAT, [batch, fw.shape[0]])], g.inits, opset=19, name="resnet50_qdq"), g.q
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The reduction operators PyTorch's exporter never writes: LpNormalization (both p, a non-last axis), GlobalMaxPool,
+# ReduceLogSum, ReduceSumSquare and a Reduce with noop_with_empty_axes = 1.  Opset 18: the axes are constant inputs.
+# ----------------------------------------------------------------------------------------------------------------
+REDUCE_FAMILY_OUTPUTS = ["lp2_channels", "lp1_last", "global_max", "log_sum", "sum_square", "l1_noop", "log_sum_exp_noop"]
+
+
+def reduce_family_graph(batch="batch", channels: int = 3, height: int = 5, width: int = 7) -> bytes:
+    """x [batch, C, H, W] ->
+         lp2_channels      LpNormalization(axis = 1, p = 2)            lanes strided by H * W
+         lp1_last          LpNormalization(axis = -1, p = 1)
+         global_max        GlobalMaxPool                               [batch, C, 1, 1]
+         log_sum           ReduceLogSum(Abs(x) + 1, axes = [2, 3], keepdims = 0)
+         sum_square        ReduceSumSquare(axes = [-1], keepdims = 1)
+         l1_noop           ReduceL1(noop_with_empty_axes = 1), no axes: |x|
+         log_sum_exp_noop  ReduceLogSumExp(noop_with_empty_axes = 1) with an empty axes input: x"""
+    i64 = lambda *v: np.array(v, np.int64)
+    inits = [tensor("one", np.array(1.0, np.float32)), tensor("axes_hw", i64(2, 3)), tensor("axes_last", i64(-1)), tensor("axes_none", np.zeros(0, np.int64))]
+    nodes = [
+        node("LpNormalization", ["x"], ["lp2_channels"], name="lp2_channels", axis=1, p=2),
+        node("LpNormalization", ["x"], ["lp1_last"], name="lp1_last", axis=-1, p=1),
+        node("GlobalMaxPool", ["x"], ["global_max"], name="global_max"),
+        node("Abs", ["x"], ["abs_x"], name="abs"),
+        node("Add", ["abs_x", "one"], ["positive"], name="add_one"),
+        node("ReduceLogSum", ["positive", "axes_hw"], ["log_sum"], name="log_sum", keepdims=0),
+        node("ReduceSumSquare", ["x", "axes_last"], ["sum_square"], name="sum_square", keepdims=1),
+        node("ReduceL1", ["x"], ["l1_noop"], name="l1_noop", noop_with_empty_axes=1),
+        node("ReduceLogSumExp", ["x", "axes_none"], ["log_sum_exp_noop"], name="log_sum_exp_noop", noop_with_empty_axes=1),
+    ]
+    shape = [batch, channels, height, width]
+    outs = [value_info("lp2_channels", FLOAT, shape), value_info("lp1_last", FLOAT, shape), value_info("global_max", FLOAT, [batch, channels, 1, 1]),
+            value_info("log_sum", FLOAT, [batch, channels]), value_info("sum_square", FLOAT, [batch, channels, height, 1]), value_info("l1_noop", FLOAT, shape),
+            value_info("log_sum_exp_noop", FLOAT, shape)]
+    return model(nodes, [value_info("x", FLOAT, shape)], outs, inits, opset=18)

@@ -1726,6 +1726,155 @@ class ReduceMin(ReduceMax):
     op = SELECT_MIN
 
 
+# ------------------------------------------------------------------------------------------ the rest of the Reduce* family
+REDUCE_L1, REDUCE_SUM_SQUARE, REDUCE_L2, REDUCE_LOG_SUM, REDUCE_LOG_SUM_EXP, REDUCE_PROD = range(6)  # RTEN_HIP_REDUCE_*
+
+
+class _Reduce(Operator):
+    """reduce() (src/ops/reduce.rs:414-520) around one kernel of rten_hip_reduce_strided: axes attribute or host-side second input, resolved, sorted and
+    de-duplicated; a 0-d input is a slice of one element; an empty slice gives the kernel's value for it.  The slice is read in place through the view's
+    strides.  `int32`: the reference also takes Int32Tensor (wrapping arithmetic); `typed_first`: the operand's type is checked before
+    noop_with_empty_axes is looked at (map_value_view! / require_as outside the test, reduce.rs:687,752,827,1215)."""
+    kind = -1
+    int32 = False
+    typed_first = True
+    f32_error = None  # None: UnsupportedType (map_value_view!); otherwise require_as::<f32>'s cast error
+
+    def __init__(self, axes=None, keep_dims=True, noop_with_empty_axes=False):
+        self.axes, self.keep_dims, self.noop_with_empty_axes = axes, keep_dims, noop_with_empty_axes
+
+    def max_inputs(self):
+        return 2
+
+    def _check_type(self, v):
+        if v.t.dtype == np.float32 or (self.int32 and v.t.dtype == np.int32):
+            return
+        if self.f32_error:
+            _want(v.t, np.float32)
+        raise UnsupportedType
+
+    def _noop(self, ctx, t):
+        """What the operator gives when the reduction is skipped: `t` is a fresh contiguous copy of the input."""
+        return t
+
+    def run(self, ctx, inputs):
+        from . import einsum as E
+        x = _require(inputs, 0)
+        v = x if isinstance(x, E.View) else E.View(x)
+        axes = _host_ints(_get(inputs, 1))
+        axes = list(self.axes) if axes is None and self.axes is not None else axes
+        if self.typed_first:
+            self._check_type(v)
+        if not axes and self.noop_with_empty_axes:
+            if v.t.dtype.itemsize != 4:
+                raise UnsupportedType
+            return [self._noop(ctx, E.materialize(ctx, v, dtype=v.t.dtype))]
+        self._check_type(v)
+        nd = len(v.shape)
+        axes = resolve_axes(nd, axes if axes else range(nd))
+        keep, osh, ost, ish, ist = _kept_and_reduced(v, axes)
+        y = DeviceTensor(ctx, [v.shape[d] for d in keep], v.t.dtype)
+        if y.size:
+            ctx.call("rten_hip_reduce_strided", self.kind, _DT[v.t.dtype], len(osh), E._i64(osh), E._i64(ost), len(ish), E._i64(ish), E._i64(ist), v.t.vp, y.vp)
+        if self.keep_dims:
+            y = y.reshape([1 if d in axes else v.shape[d] for d in range(nd)])
+        return [y]
+
+
+class ReduceL1(_Reduce):
+    """src/ops/reduce.rs:775-845: SumAbs(slice) in the fold_unroll<4> order (float32), wrapping sum of |x| (int32); with the reduction skipped, |x|."""
+    kind, int32 = REDUCE_L1, True
+
+    def _noop(self, ctx, t):
+        return Abs().run(ctx, [t], in_place=True)[0]
+
+
+class ReduceSumSquare(_Reduce):
+    """src/ops/reduce.rs:1167-1234: SumSquare(slice), fma(x, x, acc) in the fold_unroll<4> order (float32), wrapping sum of x * x (int32); with the
+    reduction skipped, x * x (reduce.rs:1216-1218)."""
+    kind, int32 = REDUCE_SUM_SQUARE, True
+
+    def _noop(self, ctx, t):
+        if t.dtype == np.float32:
+            return Mul().run(ctx, [t, t])[0]
+        y = DeviceTensor(ctx, t.shape, np.int32)
+        if t.size:
+            ctx.call("rten_hip_elementwise_nd", L.EW_IMUL, 1, _i64([t.size]), t.vp, L.DT_I32, _i64([1]), t.vp, L.DT_I32, _i64([1]), None, None, y.vp, L.DT_I32)
+        return y
+
+
+class ReduceL2(_Reduce):
+    """src/ops/reduce.rs:590-651: sqrt(SumSquare(slice)); float32 only; with the reduction skipped, a copy of the input whatever its type."""
+    kind, typed_first = REDUCE_L2, False
+
+
+class ReduceLogSum(_Reduce):
+    """src/ops/reduce.rs:653-708: ln(Sum(slice)), ln = the float64 logarithm rounded once; with the reduction skipped, ln(x)."""
+    kind, f32_error = REDUCE_LOG_SUM, True
+
+    def _noop(self, ctx, t):
+        return Log().run(ctx, [t], in_place=True)[0]
+
+
+class ReduceLogSumExp(_Reduce):
+    """src/ops/reduce.rs:710-773: m = MaxNum(slice); m when it is not finite, otherwise m + ln(SumExpSub(slice, m)); with the reduction skipped, x."""
+    kind, f32_error = REDUCE_LOG_SUM_EXP, True
+
+
+class ReduceProd(_Reduce):
+    """src/ops/reduce.rs:1046-1100: one multiply chain per slice in element order (float32), wrapping product (int32); with the reduction skipped, a
+    copy of the input whatever its type."""
+    kind, int32, typed_first = REDUCE_PROD, True, False
+
+
+class LpNormalization(Operator):
+    """src/ops/norm.rs:611-693: every lane along `axis` times 1 / norm, norm = SumAbs (p = 1) or sqrt(SumSquare) (p = 2); a zero norm zeroes the lane.
+    Defaults as the reference's loader (onnx_registry.rs:1284-1287).  Lanes along a non-last axis are read and written through the axis stride."""
+
+    def __init__(self, axis=-1, p=2):
+        self.axis, self.p = axis, p
+
+    def max_inputs(self):
+        return 1
+
+    def run(self, ctx, inputs):
+        from . import einsum as E
+        x = _require(inputs, 0)
+        _want(x.t if isinstance(x, E.View) else x, np.float32)
+        if self.p not in (1, 2):
+            raise UnsupportedValue("`p` must be 1 or 2")
+        src = E.materialize(ctx, x) if isinstance(x, E.View) else x  # (the reference normalises a contiguous copy in place)
+        nd = len(src.shape)
+        ax = _resolve_axis(nd, self.axis)
+        y = src if src is not x else DeviceTensor(ctx, src.shape, np.float32)
+        v = E.View(src)
+        if src.size == 0:
+            return [y]
+        keep, osh, ost, _, _ = _kept_and_reduced(v, [ax])
+        ctx.call("rten_hip_lp_normalize_f32", self.p, len(osh), E._i64(osh), E._i64(ost), v.shape[ax], v.strides[ax], src.vp, y.vp)
+        return [y]
+
+
+class GlobalMaxPool(Operator):
+    """src/ops/pooling.rs:549-580: MaxNum over dims 2.. of an input of at least 2 dims, output [N, C, 1, ...]; float32."""
+
+    def max_inputs(self):
+        return 1
+
+    def run(self, ctx, inputs):
+        from . import einsum as E
+        x = _want(_require(inputs, 0), np.float32)
+        nd = len(x.shape)
+        if nd < 2:
+            raise InvalidValue("Input must have at least 2 dims")
+        v = E.View(x)
+        _, osh, ost, ish, ist = _kept_and_reduced(v, list(range(2, nd)))
+        y = DeviceTensor(ctx, tuple(x.shape[:2]) + (1,) * (nd - 2), np.float32)
+        if y.size:
+            ctx.call("rten_hip_reduce_minmax_strided", SELECT_MAX, _DT[x.dtype], len(osh), E._i64(osh), E._i64(ost), len(ish), E._i64(ish), E._i64(ist), x.vp, y.vp)
+        return [y]
+
+
 class ArgMax(Operator):
     """src/ops/reduce.rs:64-160: int32 index along `axis` following Iterator::max_by with cmp_nan_greater -- the FIRST NaN if the lane holds
     one, otherwise the LAST element equal to the extreme.  select_last_index != 0 is refused as by the reference's loader (onnx_registry.rs:769)."""
@@ -2104,7 +2253,8 @@ class OpRegistry:
                    Softmax, LogSoftmax, AddSoftmax, LayerNormalization, BatchNormalization, InstanceNormalization, Relu, Gelu, Erf, Add, Mul, Sub, Div, Transpose, MaxPool,
                    AveragePool, GlobalAveragePool, Flatten, DynamicQuantizeLinear, Attention, Gather, ReduceSum, ReduceMean, Einsum, Resize, Upsample,
                    Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK, GRU, LSTM, Neg, Abs, Sign, Floor, Ceil, Round, Sqrt, Reciprocal, Exp, Log, Softplus,
-                   Pow, PRelu, Min, Max, Sum, Mean, Pad, QuantizeLinear, DequantizeLinear):
+                   Pow, PRelu, Min, Max, Sum, Mean, Pad, QuantizeLinear, DequantizeLinear, ReduceL1, ReduceL2, ReduceSumSquare, ReduceLogSum, ReduceLogSumExp,
+                   ReduceProd, LpNormalization, GlobalMaxPool):
             r.register_op(op)
         return r
 

@@ -291,6 +291,53 @@ def main():
         4.0 * (49152 * 128 + 49152))
     hbm("ReduceMax strided axis", "4096x3072 -> 3072", (lambda: ctx.call("rten_hip_reduce_minmax_strided", 0, 0, 1, i64(3072), i64(1), 1, i64(4096), i64(3072), xc.vp, yc.vp)),
         4.0 * (4096 * 3072 + 3072))
+    # ---- the rest of the Reduce* family and LpNormalization (rten_amd/csrc/reduce.hip) on the two ReduceSum shapes above.  L1 / SumSquare / L2 move
+    # ReduceSum's bytes through ReduceSum's kernels, so their yardstick is ReduceSum ITSELF, timed in the same loop: the rows of a shape are timed one
+    # after the other, `rounds` times over, and every row reports the median with the fastest and slowest round (the run-to-run spread the comparison
+    # has to be read against).  LogSumExp and LpNormalization are reported as bytes/s against the HBM peak: one-read forms at these sizes.
+    def alternating(group, specs, rounds=5):
+        specs = [s for s in specs if want(s[0])]
+        if not specs:
+            return
+        samples = {s[0]: [] for s in specs}
+        for _ in range(rounds):
+            for op, shape, fn, nbytes in specs:
+                samples[op].append(timeit(fn))
+        for op, shape, fn, nbytes in specs:
+            t = sorted(samples[op])
+            us = t[len(t) // 2]
+            gbs = nbytes / us / 1e3
+            rows.append({"op": op, "shape": shape, "us": round(us, 2), "us_min": round(t[0], 2), "us_max": round(t[-1], 2), "rounds": rounds, "group": group, "bound": "hbm",
+                         "achieved": round(gbs, 1), "unit": "GB/s", "peak": HBM_PEAK_GBS, "frac": round(gbs / HBM_PEAK_GBS, 3), "algorithmic_bytes": int(nbytes)})
+
+    def red(kind, dt=0):
+        last = (lambda: ctx.call("rten_hip_reduce_strided", kind, dt, 1, i64(49152), i64(128), 1, i64(128), i64(1), xr.vp, yr.vp))
+        cols = (lambda: ctx.call("rten_hip_reduce_strided", kind, dt, 1, i64(3072), i64(1), 1, i64(4096), i64(3072), xc.vp, yc.vp))
+        return last, cols
+    b_last, b_cols = 4.0 * (49152 * 128 + 49152), 4.0 * (4096 * 3072 + 3072)
+    sum_last = (lambda: ctx.call("rten_hip_reduce_sum_strided_f32", 1, i64(49152), i64(128), 1, i64(128), i64(1), xr.vp, yr.vp))
+    sum_cols = (lambda: ctx.call("rten_hip_reduce_sum_strided_f32", 1, i64(3072), i64(1), 1, i64(4096), i64(3072), xc.vp, yc.vp))
+    alternating("reduce last axis", [("reduce: ReduceSum last axis (yardstick)", "49152x128", sum_last, b_last),
+                                     ("reduce: ReduceL1 last axis", "49152x128", red(0)[0], b_last),
+                                     ("reduce: ReduceSumSquare last axis", "49152x128", red(1)[0], b_last),
+                                     ("reduce: ReduceL2 last axis", "49152x128", red(2)[0], b_last),
+                                     ("reduce: ReduceLogSumExp last axis (one read)", "49152x128", red(4)[0], b_last),
+                                     ("reduce: ReduceProd last axis", "49152x128", red(5)[0], b_last)])
+    alternating("reduce strided axis", [("reduce: ReduceSum strided axis (yardstick)", "4096x3072 -> 3072", sum_cols, b_cols),
+                                        ("reduce: ReduceL1 strided axis", "4096x3072 -> 3072", red(0)[1], b_cols),
+                                        ("reduce: ReduceSumSquare strided axis", "4096x3072 -> 3072", red(1)[1], b_cols),
+                                        ("reduce: ReduceL2 strided axis", "4096x3072 -> 3072", red(2)[1], b_cols),
+                                        ("reduce: ReduceLogSumExp strided axis (two reads)", "4096x3072 -> 3072", red(4)[1], 2 * b_cols)])
+    lp_specs = []
+    for rows_lp in (16384, 32):
+        xl_ = dev(rng.standard_normal((rows_lp, 768), dtype=np.float32))
+        yl_ = empty((rows_lp, 768))
+        lp_specs.append(("reduce: LpNormalization p=2 (one read, one write)", f"{rows_lp}x768",
+                         (lambda xl_=xl_, yl_=yl_, rows_lp=rows_lp: ctx.call("rten_hip_lp_normalize_f32", 2, 1, i64(rows_lp), i64(768), 768, 1, xl_.vp, yl_.vp)), 8.0 * rows_lp * 768))
+        lp_specs.append(("reduce: copy, LpNormalization's size (reference point)", f"{rows_lp}x768",
+                         (lambda xl_=xl_, yl_=yl_, rows_lp=rows_lp: ctx.call("rten_hip_memcpy_d2d", yl_.vp, xl_.vp, C.c_size_t(4 * rows_lp * 768))), 8.0 * rows_lp * 768))
+    for k in range(0, len(lp_specs), 2):  # (two specs share a name across the shapes: one group per shape keeps their samples apart)
+        alternating("LpNormalization " + lp_specs[k][1], lp_specs[k:k + 2])
     xs = dev(rng.standard_normal((1, 21, 512, 512), dtype=np.float32))
     ys = empty((512 * 512,), np.int32)
     hbm("ArgMax over channels", "1x21x512x512", (lambda: ctx.call("rten_hip_arg_minmax_strided", 0, 0, 1, i64(512 * 512), i64(1), 21, 512 * 512, xs.vp, ys.vp)),

@@ -16,7 +16,7 @@
 //     -t, --timing           per-operator table (each operator followed by a sync)
 //     --tune                 time the candidate launch plans of every f32 convolution at load and keep the fastest
 //     --graph                capture one run into a hipGraph and replay it for the timed runs
-//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
+//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow, Reduce*, LpNormalization and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
 //     --safetensors-info F   list the tensors of a Safetensors file (with --save-outputs: re-write it); no model, no GPU
 //
 // There is no CPU fallback: without an MI355X the tool reports BackendUnavailable and exits 2.
@@ -144,6 +144,20 @@ int main(int argc, char **argv) {
                 } else if (Graph::is_math_kind(n.op_type)) {
                     if (n.op_type == "Pow") Graph::check_pow_node(c, n, label);
                     std::printf("  math step %s \"%s\": %s\n", n.op_type.c_str(), n.name.c_str(), Graph::is_hostable_math_kind(n.op_type) ? "host-evaluated on host values, device otherwise" : "device");
+                }
+            }
+        }
+        {
+            const onnx::Model c = Graph::canonical_form(m); // the Reduce* family and LpNormalization: the loader's checks
+            for (auto &n : c.nodes) {
+                if (!(n.domain.empty() || n.domain == "ai.onnx")) continue;
+                const std::string label = n.name.empty() ? n.outputs.at(0) : n.name;
+                if (n.op_type == "LpNormalization") {
+                    const Graph::LpNormNode a = Graph::read_lp_norm_node(n, label);
+                    std::printf("  norm step LpNormalization \"%s\": axis %d, p %d\n", n.name.c_str(), a.axis, a.p);
+                } else if (Graph::reduce_family_kind(n.op_type) >= 0) {
+                    Graph::check_reduce_node(c, n, label);
+                    std::printf("  reduce step %s \"%s\": device (int32 host values of ReduceL1 / ReduceSumSquare / ReduceProd stay on the host)\n", n.op_type.c_str(), n.name.c_str());
                 }
             }
         }

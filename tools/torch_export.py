@@ -24,6 +24,8 @@ Test and tooling infrastructure only: nothing under rten_amd/ imports this.
     python tools/torch_export.py reflect_generator /tmp/rgen.onnx      # the generator with ReflectionPad2d / ReplicationPad2d / F.pad (Pad nodes) and nn.PReLU
     python tools/torch_export.py gpt2_mlp /tmp/gpt2_mlp.onnx           # LayerNorm, Linear, gelu_new written out with torch.pow(x, 3.0), Linear
     python tools/torch_export.py box_decode /tmp/box_decode.onnx       # conv head + anchor decode: Exp, Min / Max against the image bounds, Sqrt, Reciprocal, Neg, Abs
+    python tools/torch_export.py embedding_head /tmp/embed.onnx         # small encoder + masked mean pooling + F.normalize (ReduceL2), dynamic batch / sequence
+    python tools/torch_export.py reduce_zoo /tmp/reduce_zoo.onnx        # ReduceL1 / ReduceLogSumExp / two-axis ReduceL2 / ReduceProd as the exporter writes them
     python tools/torch_export.py dynamic_upsample /tmp/dyn_up.onnx     # F.interpolate(scale_factor=2) with dynamic H / W as Shape -> .. -> Floor -> .. -> Resize(sizes), written with onnx_writer
 """
 from __future__ import annotations
@@ -102,11 +104,12 @@ def resnet50_onnx(weights, image: int = 224) -> bytes:
     return export_bytes(resnet50_module(weights), (torch.zeros(2, 3, image, image),), ["x"], ["logits"], {"x": {0: "batch"}, "logits": {0: "batch"}})
 
 
-def encoder_module(cfg, w, seq):
+def encoder_module(cfg, w, seq, dynamic_seq=False):
     """A BERT encoder in plain torch.nn (Embedding, Linear, LayerNorm, GELU, matmul / softmax attention with an additive
     mask) holding rten_amd.workloads.bert.make_weights(cfg): the operator order of oracle.models.bert_forward.  PyTorch's
     exporter writes nn.LayerNorm as ReduceMean / Sub / Pow / Sqrt / Div / Mul / Add and nn.GELU as Div / Erf / Add / Mul / Mul,
-    Linear as MatMul + Add, scalars as Constant nodes."""
+    Linear as MatMul + Add, scalars as Constant nodes.  dynamic_seq: the position ids are sliced to the input's sequence length (a Shape -> Gather -> Slice
+    chain in the export) instead of being a [1, seq] constant, so that the file can be exported with a dynamic sequence axis."""
     import math
     import torch
     import torch.nn as nn
@@ -150,10 +153,11 @@ def encoder_module(cfg, w, seq):
             self.word, self.ttype, self.pos = emb(w["word"]), emb(w["type"]), emb(w["pos"])
             self.ln = ln(w["emb_ln_g"], w["emb_ln_b"])
             self.layers = nn.ModuleList([Layer(lw) for lw in w["layers"]])
-            self.register_buffer("position_ids", torch.arange(seq).unsqueeze(0))
+            self.register_buffer("position_ids", torch.arange(cfg.max_pos if dynamic_seq else seq).unsqueeze(0))
 
         def forward(self, input_ids, attention_mask, token_type_ids):
-            x = self.ln((self.word(input_ids) + self.ttype(token_type_ids)) + self.pos(self.position_ids))
+            pos = self.position_ids[:, :input_ids.shape[1]] if dynamic_seq else self.position_ids
+            x = self.ln((self.word(input_ids) + self.ttype(token_type_ids)) + self.pos(pos))
             mask = (1.0 - attention_mask[:, None, None, :].to(torch.float32)) * torch.finfo(torch.float32).min
             for l in self.layers:
                 x = l(x, mask)
@@ -167,6 +171,72 @@ def encoder_onnx(cfg, w, batch, seq) -> bytes:
     ids = torch.zeros(batch, seq, dtype=torch.int64)
     return export_bytes(encoder_module(cfg, w, seq), (ids, torch.ones_like(ids), torch.zeros_like(ids)),
                         ["input_ids", "attention_mask", "token_type_ids"], ["last_hidden_state"])
+
+
+def embedding_head_config():
+    """bert_module's sizes scaled down: 2 layers, hidden 32, 2 heads."""
+    from rten_amd.workloads import bert as Bw
+    return Bw.BertConfig(hidden=32, heads=2, layers=2, ffn=64, vocab=50, max_pos=16, type_vocab=2)
+
+
+def embedding_head_module(cfg=None, w=None, seq: int = 5, p: float = 2.0, dynamic_seq: bool = False):
+    """A sentence-embedding model: the encoder above, masked mean pooling over the tokens and F.normalize(p, dim=1).  The exporter writes the head as
+    Unsqueeze / Cast / Mul / ReduceSum / Clip / Div for the pooling and ReduceL2 (p = 2) or ReduceL1 (p = 1) / Clip / Shape / Expand / Div for the
+    normalisation."""
+    import torch
+    import torch.nn as nn
+    import torch.nn.functional as Fn
+    from rten_amd.workloads import bert as Bw
+    cfg = cfg if cfg is not None else embedding_head_config()
+    w = w if w is not None else Bw.make_weights(cfg)
+
+    class Head(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.encoder = encoder_module(cfg, w, seq, dynamic_seq)
+
+        def forward(self, input_ids, attention_mask, token_type_ids):
+            h = self.encoder(input_ids, attention_mask, token_type_ids)
+            m = attention_mask.unsqueeze(-1).to(torch.float32)
+            pooled = (h * m).sum(1) / torch.clamp(m.sum(1), min=1e-9)
+            return Fn.normalize(pooled, p=p, dim=1)
+
+    return Head().eval()
+
+
+def embedding_head_onnx(model=None, batch: int = 2, seq: int = 5, dynamic: bool = False, p: float = 2.0) -> bytes:
+    import torch
+    model = model if model is not None else embedding_head_module(seq=seq, p=p, dynamic_seq=dynamic)
+    ids = torch.zeros(batch, seq, dtype=torch.int64)
+    names = ["input_ids", "attention_mask", "token_type_ids"]
+    axes = dict({n: {0: "batch", 1: "seq"} for n in names}, embedding={0: "batch"}) if dynamic else None
+    return export_bytes(model, (ids, torch.ones_like(ids), torch.zeros_like(ids)), names, ["embedding"], axes)
+
+
+def reduce_zoo_module():
+    """The reductions PyTorch's exporter writes as Reduce* nodes of their own: F.normalize(p=1) (ReduceL1), torch.logsumexp (ReduceLogSumExp),
+    torch.linalg.vector_norm over two axes (ReduceL2), torch.prod (ReduceProd), and (x * x).sum, which it writes as Mul + ReduceSum -- the same value
+    as a ReduceSumSquare only where the fused multiply-add rounds like the product and the add (the hand-built graph of rten_amd/onnx_writer.py has
+    the ReduceSumSquare node)."""
+    import torch
+    import torch.nn as nn
+    import torch.nn.functional as Fn
+
+    class Zoo(nn.Module):
+        def forward(self, x):  # [N, 3, 4, 6]
+            return (Fn.normalize(x, p=1.0, dim=-1), torch.logsumexp(x, dim=2), torch.linalg.vector_norm(x, dim=(1, 2)), torch.prod(x, dim=1), (x * x).sum(-1))
+
+    return Zoo().eval()
+
+
+ZOO_OUTPUTS = ["l1_normalized", "logsumexp", "norm2", "prod", "sum_of_squares"]
+
+
+def reduce_zoo_onnx(model=None, batch: int = 2, dynamic: bool = True) -> bytes:
+    import torch
+    model = model if model is not None else reduce_zoo_module()
+    axes = dict({"x": {0: "batch"}}, **{n: {0: "batch"} for n in ZOO_OUTPUTS}) if dynamic else None
+    return export_bytes(model, (torch.zeros(batch, 3, 4, 6),), ["x"], ZOO_OUTPUTS, axes)
 
 
 def bert_module(layers=2, hidden=768, heads=12, ffn=3072, vocab=30522, seed=0):
@@ -721,6 +791,10 @@ if __name__ == "__main__":
         data = box_decode_onnx()
     elif kind == "dynamic_upsample":
         data = dynamic_upsample_onnx()
+    elif kind == "embedding_head":
+        data = embedding_head_onnx(dynamic=True)
+    elif kind == "reduce_zoo":
+        data = reduce_zoo_onnx()
     else:
         data = bert_onnx(bert_module())
     open(path, "wb").write(data)
