@@ -506,8 +506,9 @@ int32_t rten_hip_copy_strided_b32(rten_hip_ctx *ctx, int32_t ndim, const int64_t
  *   RTEN_HIP_EW_NOT / AND / OR / XOR  int32 operands, int32 0 / 1 result (unary_elementwise.rs:563-565, binary_elementwise.rs:546-598)
  *   RTEN_HIP_EW_EQUAL .. GREATER_EQ   two float32 or two int32 operands, int32 0 / 1 result (binary_elementwise.rs:733-786)
  *   RTEN_HIP_EW_WHERE                 y = a != 0 ? b : c; a int32, b / c / y 4-byte elements of one type (binary_elementwise.rs:1189-1247)
- *   RTEN_HIP_EW_IADD / ISUB / IMUL / IDIV   int32 arithmetic (wrapping; division truncates toward zero; x / 0 = 0 on the device -- the reference
- *                                     panics -- so hosts reject a constant zero divisor)
+ *   RTEN_HIP_EW_IADD / ISUB / IMUL / IDIV   int32 arithmetic (wrapping; division truncates toward zero; i32::MIN / -1 = i32::MIN; x / 0 = 0 on the
+ *                                     device -- the reference returns InvalidValue("Divisor contains zero"), binary_elementwise.rs:604-610, which a
+ *                                     kernel cannot -- so hosts reject a constant zero divisor with that message)
  * Operands an operator does not take are NULL.  Mask and index preparation, never a model's critical path: one scalar kernel, no vector forms. */
 #define RTEN_HIP_DT_F32 0
 #define RTEN_HIP_DT_I32 1
@@ -568,7 +569,7 @@ int32_t rten_hip_dequantize_linear_f32(rten_hip_ctx *ctx, int32_t dtype, int64_t
 int32_t rten_hip_quantize_dequantize_f32(rten_hip_ctx *ctx, int32_t dtype, int64_t outer, int64_t channels, int64_t inner, const float *x, const float *scale,
                                          const void *zero_point, float *y);
 /* Gather along any axis of 4-byte elements (src/ops/gather.rs:21-110): y[o][j][k] = data[o][ids[j]][k] with data viewed as [outer][axis_len][inner];
- * negative indices count from the end; out-of-range indices are clamped (the reference reports "Entry in indices is out of range"). */
+ * negative indices count from the end; out-of-range indices are clamped (the reference reports "Entry in `indices` is out of range"). */
 int32_t rten_hip_gather_axis_b32(rten_hip_ctx *ctx, int64_t outer, int64_t axis_len, int64_t inner, int64_t n_ids, const void *data, const int32_t *ids, void *y);
 /* rows x row_elems 4-byte elements from src (row pitch src_pitch elements) to dst (row pitch dst_pitch >= row_elems): one piece of a Concat
  * (src/ops/concat.rs:108) written into its slot of the output. */

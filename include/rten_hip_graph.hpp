@@ -336,6 +336,22 @@ template <typename F> void for_each_broadcast(const std::vector<int64_t> &out, c
 }
 inline HostVal make_ints(std::vector<int64_t> shape, std::vector<int64_t> v) { HostVal h; h.shape = std::move(shape); h.i = std::move(v); return h; }
 
+// Shape (src/ops/layout.rs:475-505): dims[start .. end) with negative bounds counted from the end and both clamped to [0, rank]
+inline HostVal shape_of(const std::vector<int64_t> &dims, int64_t start, bool has_end, int64_t end) {
+    const int64_t nd = (int64_t)dims.size();
+    int64_t s = start < 0 ? start + nd : start, e = has_end ? (end < 0 ? end + nd : end) : nd;
+    s = std::min(std::max<int64_t>(s, 0), nd); e = std::min(std::max<int64_t>(e, 0), nd);
+    std::vector<int64_t> v;
+    for (int64_t d = s; d < e; d++) v.push_back(dims[(size_t)d]);
+    return make_ints({(int64_t)v.size()}, v);
+}
+inline bool logical_not(const HostVal &x, HostVal &out) { // unary_elementwise.rs:563-565
+    if (x.is_float) return false;
+    out.shape = x.shape;
+    for (int64_t v : x.i) out.i.push_back(v == 0);
+    return true;
+}
+
 // ---- element-wise: Add Sub Mul Div (both types), And Or Xor, Equal Less LessOrEqual Greater GreaterOrEqual
 inline bool binary(const std::string &op, const HostVal &a, const HostVal &b, HostVal &out) {
     if (a.is_float != b.is_float) return false;
@@ -349,18 +365,24 @@ inline bool binary(const std::string &op, const HostVal &a, const HostVal &b, Ho
     const int64_t n = out.len();
     if (out.is_float) out.f.resize((size_t)n); else out.i.resize((size_t)n);
     bool ok = true;
+    // Div (binary_elementwise.rs:613-637): an integer divisor that holds a zero anywhere is refused before anything is computed (check_nonzero); a float
+    // divisor of exactly ONE element, at any rank, multiplies by its reciprocal -- a * (1 / b), two roundings -- and every other divisor divides
+    if (op == "Div" && !a.is_float)
+        for (int64_t y : b.i) if (y == 0) throw OpError(OpError::InvalidValue, "Divisor contains zero");
+    const bool by_reciprocal = op == "Div" && a.is_float && b.len() == 1;
+    const float reciprocal = by_reciprocal ? 1.f / b.f[0] : 0.f;
     for_each_broadcast(out.shape, st, [&](int64_t i, const std::vector<int64_t> &o) {
         if (a.is_float) {
             const float x = a.f[(size_t)o[0]], y = b.f[(size_t)o[1]];
             if (op == "Add") out.f[(size_t)i] = x + y; else if (op == "Sub") out.f[(size_t)i] = x - y; else if (op == "Mul") out.f[(size_t)i] = x * y;
-            else if (op == "Div") out.f[(size_t)i] = x / y;
+            else if (op == "Div") out.f[(size_t)i] = by_reciprocal ? x * reciprocal : x / y;
             else if (op == "Equal") out.i[(size_t)i] = x == y; else if (op == "Less") out.i[(size_t)i] = x < y; else if (op == "LessOrEqual") out.i[(size_t)i] = x <= y;
             else if (op == "Greater") out.i[(size_t)i] = x > y; else if (op == "GreaterOrEqual") out.i[(size_t)i] = x >= y; else ok = false;
         } else {
             const int64_t x = a.i[(size_t)o[0]], y = b.i[(size_t)o[1]];
             int64_t r = 0;
             if (op == "Add") r = wrap32(x + y); else if (op == "Sub") r = wrap32(x - y); else if (op == "Mul") r = wrap32(x * y);
-            else if (op == "Div") { if (y == 0) throw OpError(OpError::InvalidValue, "integer division by zero"); r = wrap32(x / y); }
+            else if (op == "Div") r = wrap32(x / y); // truncating; i32::MIN / -1 (a panic in the reference) wraps to i32::MIN, as on the device
             else if (op == "And") r = (x != 0) && (y != 0); else if (op == "Or") r = (x != 0) || (y != 0); else if (op == "Xor") r = (x != 0) != (y != 0);
             else if (op == "Equal") r = x == y; else if (op == "Less") r = x < y; else if (op == "LessOrEqual") r = x <= y;
             else if (op == "Greater") r = x > y; else if (op == "GreaterOrEqual") r = x >= y; else ok = false;
@@ -383,7 +405,16 @@ inline bool where(const HostVal &c, const HostVal &x, const HostVal &y, HostVal 
     });
     return true;
 }
+// Expand's shape checks (src/ops/layout.rs:106-118), shared by the host and the device path
+inline void check_expand(const std::vector<int64_t> &shape, const std::vector<int64_t> &target) {
+    for (int64_t d : target) if (d < 0) throw OpError(OpError::InvalidValue, "Target shape contains negative values");
+    for (size_t i = 0; i < shape.size() && i < target.size(); i++) {
+        const int64_t a = shape[shape.size() - 1 - i], b = target[target.size() - 1 - i];
+        if (a != b && a != 1 && b != 1) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast input with target shape");
+    }
+}
 inline HostVal expand(const HostVal &x, const std::vector<int64_t> &target) {
+    check_expand(x.shape, target);
     HostVal out;
     out.is_float = x.is_float;
     HostVal t; t.shape = target;
@@ -423,9 +454,11 @@ inline HostVal transpose(const HostVal &x, const std::vector<int> &perm_in) {
     HostVal out;
     out.is_float = x.is_float;
     std::vector<int64_t> st((size_t)nd);
+    unsigned seen = 0;
     for (int d = 0; d < nd; d++) {
         const int pd = perm[(size_t)d] < 0 ? perm[(size_t)d] + nd : perm[(size_t)d];
-        if (pd < 0 || pd >= nd) throw OpError(OpError::InvalidValue, "Permutation is invalid");
+        if (pd < 0 || pd >= nd || (seen >> pd & 1u)) throw OpError(OpError::InvalidValue, "Permutation is invalid"); // (a repeated axis too: layout.rs:647-660)
+        seen |= 1u << pd;
         out.shape.push_back(x.shape[(size_t)pd]);
         st[(size_t)d] = xs[(size_t)pd];
     }
@@ -448,7 +481,7 @@ inline HostVal gather(const HostVal &x, const HostVal &ids, int axis) { // src/o
         for (int64_t j = 0; j < nid; j++) {
             int64_t id = ids.i[(size_t)j];
             if (id < 0) id += alen;
-            if (id < 0 || id >= alen) throw OpError(OpError::InvalidValue, "Entry in indices is out of range");
+            if (id < 0 || id >= alen) throw OpError(OpError::InvalidValue, "Entry in `indices` is out of range");
             for (int64_t k = 0; k < inner; k++) {
                 const size_t src = (size_t)((o * alen + id) * inner + k);
                 if (out.is_float) out.f.push_back(x.f[src]); else out.i.push_back(x.i[src]);
@@ -466,6 +499,8 @@ inline HostVal concat(const std::vector<const HostVal *> &v, int axis) { // src/
     for (auto *x : v) {
         if ((int)x->shape.size() != nd) throw OpError(OpError::IncompatibleInputShapes, "Tensors must have the same number of dimensions");
         if (x->is_float != out.is_float) throw OpError(OpError::UnsupportedType, "");
+        for (int d = 0; d < nd; d++)
+            if (d != ax && x->shape[(size_t)d] != v[0]->shape[(size_t)d]) throw OpError(OpError::IncompatibleInputShapes, "Dimensions must be the same except for concat axis");
         out.shape[(size_t)ax] += x->shape[(size_t)ax];
     }
     const int64_t outer = detail::prod(out.shape, 0, (size_t)ax), inner = detail::prod(out.shape, (size_t)ax + 1, out.shape.size());
@@ -487,7 +522,7 @@ inline HostVal slice(const HostVal &x, const std::vector<SliceRange> &r) {
     for_each_broadcast(out.shape, {st}, [&](int64_t i, const std::vector<int64_t> &o) { if (out.is_float) out.f[(size_t)i] = x.f[(size_t)(base + o[0])]; else out.i[(size_t)i] = x.i[(size_t)(base + o[0])]; });
     return out;
 }
-inline HostVal nonzero(const HostVal &x) { // src/ops/non_zero.rs: [rank, count] int32 indices of the non-zero elements, row-major order
+inline HostVal nonzero(const HostVal &x) { // src/ops/reduce.rs:299-325: [rank, count] int32 indices of the non-zero elements, row-major order
     const int nd = (int)x.shape.size();
     std::vector<std::vector<int64_t>> cols;
     const int64_t n = x.len();
@@ -498,10 +533,103 @@ inline HostVal nonzero(const HostVal &x) { // src/ops/non_zero.rs: [rank, count]
         for (int d = nd - 1; d >= 0; d--) { if (++idx[(size_t)d] < x.shape[(size_t)d]) break; idx[(size_t)d] = 0; }
     }
     HostVal out;
-    out.shape = {(int64_t)std::max(nd, 1), (int64_t)cols.size()}; // (a scalar input gives [1, 0 or 1] in ONNX; the reference rejects scalars)
+    out.shape = {(int64_t)nd, (int64_t)cols.size()}; // (a scalar input gives [0, 0 or 1]: reduce.rs:301-306)
     out.i.resize((size_t)(out.shape[0] * out.shape[1]));
     for (int d = 0; d < nd; d++) for (size_t c = 0; c < cols.size(); c++) out.i[(size_t)d * cols.size() + c] = cols[c][(size_t)d];
     return out;
+}
+// Range (src/ops/generate.rs:170-189): the reference's loop -- push `val`, then val = val + delta, while val is short of `limit` -- so that a float range
+// has the reference's accumulated roundings and its element count.  Integers wrap at 32 bits.
+inline HostVal range(const HostVal &start, const HostVal &limit, const HostVal &delta) {
+    if (start.is_float != limit.is_float || start.is_float != delta.is_float) throw OpError(OpError::UnsupportedType, "");
+    if (start.len() != 1) throw OpError(OpError::InvalidValue, "`start` must be a scalar");
+    if (limit.len() != 1 || delta.len() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 0 dims");
+    HostVal out;
+    out.is_float = start.is_float;
+    if (out.is_float) {
+        const float l = limit.f[0], d = delta.f[0];
+        if (d == 0.f) throw OpError(OpError::InvalidValue, "delta must be non-zero");
+        for (float v = start.f[0]; (d > 0.f && v < l) || (d < 0.f && v > l); v = v + d) {
+            if ((int64_t)out.f.size() >= kMaxHostElems) throw OpError(OpError::UnsupportedValue, "Range: too many elements");
+            out.f.push_back(v);
+        }
+        out.shape = {(int64_t)out.f.size()};
+    } else {
+        const int64_t l = limit.i[0], d = delta.i[0];
+        if (d == 0) throw OpError(OpError::InvalidValue, "delta must be non-zero");
+        for (int64_t v = start.i[0]; d > 0 ? v < l : v > l; v = wrap32(v + d)) {
+            if ((int64_t)out.i.size() >= kMaxHostElems) throw OpError(OpError::UnsupportedValue, "Range: too many elements");
+            out.i.push_back(v);
+        }
+        out.shape = {(int64_t)out.i.size()};
+    }
+    return out;
+}
+// ConstantOfShape's one-element fill from the `value` attribute's int64 payload: saturated to int32 like every int64 initializer (onnx_loader.rs:464-492)
+inline int64_t saturate32(int64_t v) { return std::max<int64_t>(INT32_MIN, std::min<int64_t>(INT32_MAX, v)); }
+// ConstantOfShape (src/ops/generate.rs:18-29): `fill` (one element) over `shape`; a negative dimension is "Invalid shape"
+inline HostVal constant_fill(const HostVal &fill, const std::vector<int64_t> &shape) {
+    for (int64_t d : shape) if (d < 0) throw OpError(OpError::InvalidValue, "Invalid shape");
+    return expand(fill, shape);
+}
+// The shape Flatten / Reshape / Squeeze / Unsqueeze give a tensor of `shape` (src/ops/layout.rs:231-240, 324-391, 560-600, 710-734), with the reference's
+// checks in its order and words.  `spec`: Reshape's target or the axes; `axis`: Flatten's.
+inline std::vector<int64_t> view_shape(const std::string &kind, const std::vector<int64_t> &shape, const std::vector<int64_t> &spec, bool have_spec, int axis, bool allowzero) {
+    const int nd = (int)shape.size();
+    const int64_t len = detail::prod(shape, 0, shape.size());
+    if (kind == "Flatten") {
+        const int a = axis < 0 ? axis + nd : axis;
+        if (a < 0 || a > nd) throw OpError(OpError::InvalidValue, "Axis is invalid");
+        return {detail::prod(shape, 0, (size_t)a), detail::prod(shape, (size_t)a, (size_t)nd)};
+    }
+    if (kind == "Reshape") {
+        if (!have_spec) throw OpError(OpError::MissingInputs, "");
+        std::vector<int64_t> s(spec);
+        int64_t known = 1;
+        int infer = -1;
+        for (size_t i = 0; i < s.size(); i++) {
+            if (s[i] < -1) throw OpError(OpError::InvalidValue, "Invalid dimension size in shape");
+            if (s[i] == 0 && !allowzero) {
+                if (i >= (size_t)nd) throw OpError(OpError::InvalidValue, "Zero dim has no corresponding input dim");
+                s[i] = shape[i];
+                known *= s[i];
+            } else if (s[i] != -1) known *= s[i];
+            else if (infer >= 0) throw OpError(OpError::InvalidValue, "Multiple dimensions in new shape set to -1");
+            else infer = (int)i;
+        }
+        if (infer >= 0) {
+            if (known == 0) throw OpError(OpError::InvalidValue, "Cannot infer size of -1 dim when other dims are zero");
+            if (len % known != 0) throw OpError(OpError::InvalidValue, "Input length does not match target shape");
+            s[(size_t)infer] = len / known;
+        } else if (known != len) throw OpError(OpError::InvalidValue, "Input length does not match target shape");
+        return s;
+    }
+    if (kind == "Squeeze") {
+        std::vector<int64_t> o;
+        std::vector<bool> drop((size_t)nd, false);
+        for (int64_t a : spec) drop[(size_t)resolve_axis((int)a, nd)] = true;
+        for (int i = 0; i < nd; i++) {
+            if (have_spec ? drop[(size_t)i] : shape[(size_t)i] == 1) {
+                if (shape[(size_t)i] != 1) throw OpError(OpError::InvalidValue, "Can only remove dimensions of size 1");
+            } else o.push_back(shape[(size_t)i]);
+        }
+        return o;
+    }
+    if (kind == "Unsqueeze") {
+        if (!have_spec) throw OpError(OpError::MissingInputs, "");
+        const int out_nd = nd + (int)spec.size();
+        std::vector<int64_t> o((size_t)out_nd, 0);
+        std::vector<int> axes;
+        for (int64_t a : spec) axes.push_back(resolve_axis((int)a, out_nd)); // ("Axis is invalid" before the uniqueness check)
+        for (int a : axes) {
+            if (o[(size_t)a] == 1) throw OpError(OpError::InvalidValue, "Axes must be unique");
+            o[(size_t)a] = 1;
+        }
+        size_t src = 0;
+        for (auto &d : o) if (d == 0) d = shape[src++];
+        return o;
+    }
+    return shape; // Identity, Dropout
 }
 // ReduceMax / ReduceMin of a host value over sorted unique `axes` (shape arithmetic sometimes takes the extreme of a shape vector): NaN propagates, an empty
 // slice gives the identity (src/ops/reduce.rs:414-520, 876-1044)
@@ -2879,13 +3007,8 @@ class Graph {
             auto cache = std::make_shared<HostCache>();
             st.run = [start, has_end, end, cache](Context &c, const InputList &in) {
                 const Tensor &x = require(in, 0);
-                const int64_t nd = x.ndim();
-                int64_t s = start < 0 ? start + nd : start, e = has_end ? (end < 0 ? end + nd : end) : nd;
-                s = std::min(std::max<int64_t>(s, 0), nd); e = std::min(std::max<int64_t>(e, 0), nd);
-                std::vector<int64_t> dims;
-                for (int64_t d = s; d < e; d++) dims.push_back(x.size((int)d));
                 OutputList o;
-                o.push_back(materialize(c, hostops::make_ints({(int64_t)dims.size()}, dims), *cache));
+                o.push_back(materialize(c, hostops::shape_of(x.shape(), start, has_end, end), *cache));
                 return o;
             };
             return true;
@@ -2901,7 +3024,7 @@ class Graph {
                           [dev, fop, is_arith](Context &c, const InputList &in) {
                               if (is_arith && !(require(in, 0).dtype() == DType::I32 && require(in, 1).dtype() == DType::I32)) return fop->run(c, in); // the f32 kernels
                               if (is_arith && dev->code == RTEN_HIP_EW_IDIV && in[1]->host())
-                                  for (int64_t d : in[1]->host()->i) if (d == 0) throw OpError(OpError::InvalidValue, "integer division by zero");
+                                  for (int64_t d : in[1]->host()->i) if (d == 0) throw OpError(OpError::InvalidValue, "Divisor contains zero");
                               return dev->run(c, in);
                           });
             return true;
@@ -2909,12 +3032,7 @@ class Graph {
         if (op == "Not") {
             auto dev = std::make_shared<ElementwiseNd>(RTEN_HIP_EW_NOT, "Not");
             make_hostable(st,
-                          [](const std::vector<const HostVal *> &v, HostVal &out) {
-                              if (v.size() != 1 || !v[0] || v[0]->is_float) return false;
-                              out.shape = v[0]->shape;
-                              for (int64_t x : v[0]->i) out.i.push_back(x == 0);
-                              return true;
-                          },
+                          [](const std::vector<const HostVal *> &v, HostVal &out) { return v.size() == 1 && v[0] && hostops::logical_not(*v[0], out); },
                           [dev](Context &c, const InputList &in) { return dev->run(c, in); });
             return true;
         }
@@ -2987,6 +3105,7 @@ class Graph {
             st.run = [cache](Context &c, const InputList &in) {
                 const Tensor &x = require(in, 0);
                 const std::vector<int64_t> target = host_ints(&require(in, 1), "Expand: the shape input");
+                hostops::check_expand(x.shape(), target);
                 OutputList o;
                 if (x.host() && detail::prod(target, 0, target.size()) <= hostops::kMaxHostElems) o.push_back(materialize(c, hostops::expand(*x.host(), target), *cache));
                 else o.push_back(expand_to(c, x, target));
@@ -3001,7 +3120,7 @@ class Graph {
                 const onnx::TensorProto &t = v->t;
                 if (t.len() != 1) throw GraphError("ConstantOfShape " + name + ": value must hold one element");
                 if (t.data_type == onnx::FLOAT && t.raw.size() == 4) std::memcpy(&fill.f[0], t.raw.data(), 4);
-                else if (t.data_type == onnx::INT64 && t.raw.size() == 8) { int64_t x; std::memcpy(&x, t.raw.data(), 8); fill.is_float = false; fill.f.clear(); fill.i = {hostops::wrap32(x)}; }
+                else if (t.data_type == onnx::INT64 && t.raw.size() == 8) { int64_t x; std::memcpy(&x, t.raw.data(), 8); fill.is_float = false; fill.f.clear(); fill.i = {hostops::saturate32(x)}; }
                 else if (t.data_type == onnx::INT32 && t.raw.size() == 4) { int32_t x; std::memcpy(&x, t.raw.data(), 4); fill.is_float = false; fill.f.clear(); fill.i = {x}; }
                 else if (t.data_type == onnx::BOOL && t.raw.size() == 1) { fill.is_float = false; fill.f.clear(); fill.i = {t.raw[0] != 0}; }
                 else throw GraphError("ConstantOfShape " + name + ": unsupported value type");
@@ -3009,9 +3128,9 @@ class Graph {
             auto cache = std::make_shared<HostCache>();
             st.run = [fill, cache](Context &c, const InputList &in) {
                 const std::vector<int64_t> shape = host_ints(&require(in, 0), "ConstantOfShape: the shape input");
-                for (int64_t d : shape) if (d < 0) throw OpError(OpError::InvalidValue, "ConstantOfShape: negative dimension");
                 OutputList o;
-                if (detail::prod(shape, 0, shape.size()) <= hostops::kMaxHostElems) { o.push_back(materialize(c, hostops::expand(fill, shape), *cache)); return o; }
+                if (detail::prod(shape, 0, shape.size()) <= hostops::kMaxHostElems) { o.push_back(materialize(c, hostops::constant_fill(fill, shape), *cache)); return o; }
+                for (int64_t d : shape) if (d < 0) throw OpError(OpError::InvalidValue, "Invalid shape");
                 Tensor one = materialize(c, HostVal(fill), *cache); // a large fill: expand the one-element device constant
                 o.push_back(expand_to(c, one, shape));
                 return o;
@@ -3034,20 +3153,7 @@ class Graph {
             st.run = [cache](Context &c, const InputList &in) {
                 const Tensor &a = require(in, 0), &b = require(in, 1), &d = require(in, 2);
                 if (!a.host() || !b.host() || !d.host()) throw OpError(OpError::UnsupportedValue, "Range: start / limit / delta must be constants or computable from the input shapes");
-                HostVal out;
-                if (a.host()->is_float) {
-                    const float s = a.host()->f.at(0), l = b.host()->f.at(0), dl = d.host()->f.at(0);
-                    if (dl == 0.f) throw OpError(OpError::InvalidValue, "delta must be non-zero");
-                    out.is_float = true;
-                    const int64_t cnt = std::max<int64_t>((int64_t)std::ceil((l - s) / dl), 0);
-                    for (int64_t k = 0; k < cnt; k++) out.f.push_back(s + (float)k * dl);
-                    out.shape = {cnt};
-                } else {
-                    const int64_t s = a.host()->i.at(0), l = b.host()->i.at(0), dl = d.host()->i.at(0);
-                    if (dl == 0) throw OpError(OpError::InvalidValue, "delta must be non-zero");
-                    for (int64_t v = s; dl > 0 ? v < l : v > l; v += dl) out.i.push_back(v);
-                    out.shape = {(int64_t)out.i.size()};
-                }
+                HostVal out = hostops::range(*a.host(), *b.host(), *d.host());
                 OutputList o;
                 o.push_back(materialize(c, std::move(out), *cache));
                 return o;
@@ -3187,49 +3293,7 @@ class Graph {
             const Tensor &x = require(in, 0);
             const std::vector<int64_t> spec_rt = runtime_spec ? host_ints(&require(in, 1), kind + " " + step_name + ": the shape / axes input") : std::vector<int64_t>();
             const std::vector<int64_t> &spec = runtime_spec ? spec_rt : spec_const;
-            std::vector<int64_t> s = x.shape();
-            const int nd = (int)s.size();
-            if (kind == "Flatten") {
-                const int a = axis < 0 ? axis + nd : axis;
-                if (a < 0 || a > nd) throw OpError(OpError::InvalidValue, "Axis is invalid");
-                s = {detail::prod(x.shape(), 0, (size_t)a), detail::prod(x.shape(), (size_t)a, (size_t)nd)};
-            } else if (kind == "Reshape") {
-                if (!have_spec) throw OpError(OpError::MissingInputs, "");
-                s.assign(spec.begin(), spec.end());
-                int64_t known = 1;
-                int infer = -1;
-                for (size_t i = 0; i < s.size(); i++) {
-                    if (s[i] == 0 && !allowzero) { if (i >= (size_t)nd) throw OpError(OpError::InvalidValue, "Input and output element counts do not match"); s[i] = x.size((int)i); }
-                    if (s[i] == -1) { if (infer >= 0) throw OpError(OpError::InvalidValue, "Multiple dimensions in new shape set to -1"); infer = (int)i; }
-                    else known *= s[i];
-                }
-                if (infer >= 0) {
-                    if (known == 0 || x.len() % known != 0) throw OpError(OpError::InvalidValue, "Input length must be a multiple of specified dimensions");
-                    s[(size_t)infer] = x.len() / known;
-                }
-                if (detail::prod(s, 0, s.size()) != x.len()) throw OpError(OpError::InvalidValue, "Input and output element counts do not match");
-            } else if (kind == "Squeeze") {
-                std::vector<int64_t> o;
-                for (int i = 0; i < nd; i++) {
-                    bool drop = have_spec ? false : s[(size_t)i] == 1;
-                    for (int64_t a : spec) if ((a < 0 ? a + nd : a) == i) drop = true;
-                    if (drop && s[(size_t)i] != 1) throw OpError(OpError::InvalidValue, "Can only remove dimensions of size 1");
-                    if (!drop) o.push_back(s[(size_t)i]);
-                }
-                s = o;
-            } else if (kind == "Unsqueeze") {
-                if (!have_spec) throw OpError(OpError::MissingInputs, "");
-                const int out_nd = nd + (int)spec.size();
-                std::vector<int64_t> o((size_t)out_nd, 0);
-                for (int64_t a : spec) {
-                    const int64_t p = a < 0 ? a + out_nd : a;
-                    if (p < 0 || p >= out_nd || o[(size_t)p] == 1) throw OpError(OpError::InvalidValue, "Axes must be unique and in range");
-                    o[(size_t)p] = 1;
-                }
-                int src = 0;
-                for (auto &d : o) if (d == 0) d = s[(size_t)src++];
-                s = o;
-            }
+            const std::vector<int64_t> s = hostops::view_shape(kind, x.shape(), spec, have_spec, axis, allowzero);
             OutputList out;
             out.push_back(Tensor::view_of(x, s));
             if (x.host()) out.back().set_host(std::make_shared<const HostVal>(hostops::reshaped(*x.host(), s))); // the same values under the new shape

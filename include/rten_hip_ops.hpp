@@ -1125,7 +1125,7 @@ struct BinaryOp : Operator { // binary_elementwise.rs:58-170,476-495: numpy broa
         for (int i = nd - 1; i >= 0; i--) {
             const int ia = i - (nd - a.ndim()), ib = i - (nd - b.ndim());
             const int64_t da = ia >= 0 ? a.size(ia) : 1, db = ib >= 0 ? b.size(ib) : 1;
-            if (da != db && da != 1 && db != 1) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs to same shape");
+            if (da != db && da != 1 && db != 1) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs");
             oshape[(size_t)i] = std::max(da, db) == 1 ? 1 : (da == 1 ? db : da);
             if (da == 0 || db == 0) oshape[(size_t)i] = 0;
             as[(size_t)i] = da == 1 ? 0 : sa;
@@ -1141,7 +1141,42 @@ struct BinaryOp : Operator { // binary_elementwise.rs:58-170,476-495: numpy broa
 struct Add : BinaryOp<rten_hip_add_f32, 0> { Add() : BinaryOp("Add") {} };
 struct Mul : BinaryOp<rten_hip_mul_f32, 1> { Mul() : BinaryOp("Mul") {} };
 struct Sub : BinaryOp<rten_hip_sub_f32, 2> { Sub() : BinaryOp("Sub") {} };
-struct Div : BinaryOp<rten_hip_div_f32, 3> { Div() : BinaryOp("Div") {} };
+// Div (binary_elementwise.rs:613-637): a divisor of exactly ONE element, at any rank, is the reference's multiplication by the reciprocal -- a * (1 / b),
+// two roundings, not a / b -- and every other divisor a true division.  (rten_hip_div_f32 and rten_hip_binary_broadcast_f32 op 3 stay true divisions.)
+// The reciprocal of a divisor the host knows is uploaded once per context and value (by the warm-up run that precedes every capture); a device scalar
+// costs one RTEN_HIP_UNARY_RECIPROCAL launch on its element.  Both forms replay from a captured graph.
+struct Div : BinaryOp<rten_hip_div_f32, 3> {
+    Div() : BinaryOp("Div") {}
+    OutputList run(Context &ctx, const InputList &in) const override {
+        want(require(in, 0), DType::F32, "float32");
+        const Tensor &b = want(require(in, 1), DType::F32, "float32");
+        if (b.len() != 1) return BinaryOp::run(ctx, in);
+        static const Mul mul;
+        if (const HostVal *h = b.host()) {
+            uint32_t bits;
+            std::memcpy(&bits, &h->f.at(0), 4);
+            std::lock_guard<std::mutex> lk(mu_);
+            const Tensor *r = nullptr;
+            for (const auto &e : reciprocals_) if (e.ctx == &ctx && e.bits == bits) r = e.value.get();
+            if (!r) {
+                if (rten_hip_capture_active(ctx.raw())) throw OpError(OpError::UnsupportedValue, "Div: the divisor's reciprocal must be uploaded before the run is captured");
+                const float v = 1.0f / h->f[0];
+                if (reciprocals_.size() >= 8) reciprocals_.erase(reciprocals_.begin());
+                reciprocals_.push_back({&ctx, bits, std::unique_ptr<Tensor>(new Tensor(Tensor::from_host_unpooled<float>(ctx, {}, &v)))});
+                r = reciprocals_.back().value.get();
+            }
+            const Tensor rv = Tensor::view_of(*r, b.shape());
+            return mul.run(ctx, {in[0], &rv});
+        }
+        Tensor r(ctx, b.shape(), DType::F32);
+        ctx.check(rten_hip_unary_f32(ctx.raw(), RTEN_HIP_UNARY_RECIPROCAL, 1, (const float *)b.ptr(), (float *)r.ptr()));
+        return mul.run(ctx, {in[0], &r});
+    }
+  private:
+    struct Entry { const Context *ctx; uint32_t bits; std::unique_ptr<Tensor> value; };
+    mutable std::vector<Entry> reciprocals_;
+    mutable std::mutex mu_;
+};
 
 // ------------------------------------------------------------------------------------------------ layout (src/ops/layout.rs, gather.rs)
 struct Transpose : Operator { // layout.rs:669+: perm absent = reverse the axes
@@ -1170,7 +1205,7 @@ struct Transpose : Operator { // layout.rs:669+: perm absent = reverse the axes
 };
 
 // Gather (src/ops/gather.rs:21-110): 4-byte data, int32 indices, any axis; the embedding-lookup form (axis 0 of a float table) keeps its own kernel.
-// Out-of-range indices are clamped on the device (the reference reports "Entry in indices is out of range").
+// Out-of-range indices are clamped on the device (the reference reports "Entry in `indices` is out of range").
 struct Gather : Operator {
     int axis = 0;
     const char *name() const override { return "Gather"; }
@@ -1213,7 +1248,7 @@ struct AddSoftmax : Operator {
         else if (m.len() == cols && m.size(m.ndim() - 1) == cols) { add_div = rows ? rows : 1; add_mod = 1; }
         else if (x.ndim() == 4 && m.ndim() == 4 && m.size(0) == x.size(0) && m.size(1) == 1 && m.size(2) == 1 && m.size(3) == cols) {
             add_div = x.size(1) * x.size(2); add_mod = x.size(0);
-        } else throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs to same shape");
+        } else throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs");
         Tensor y(ctx, x.shape(), DType::F32);
         if (x.len()) ctx.check(rten_hip_softmax_f32(ctx.raw(), rows, (int)cols, (const float *)x.ptr(), (const float *)m.ptr(), add_div, add_mod, flush_nans_to_zero ? 1 : 0, (float *)y.ptr()));
         OutputList out;
@@ -1267,14 +1302,14 @@ struct MultiHeadSdpa : Operator {
                 // numpy broadcasting of the Add(scores [B, H, S, T], mask): every form without a head axis is the same addend for
                 // all heads, so the expanded copy gives the unfused graph's bits
                 const int nd = mask->ndim();
-                if (nd > 4) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs to same shape");
+                if (nd > 4) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs");
                 int64_t ms[4] = {1, 1, 1, 1};
                 for (int i = 0; i < nd; i++) ms[4 - nd + i] = mask->size(i);
                 const int64_t want_shape[4] = {B, 1, S, T};
                 if (ms[1] != 1) throw OpError(OpError::UnsupportedValue, "fused attention: a mask with a head axis is not supported (run the graph unfused)");
                 int64_t strides[4], acc = 1;
                 for (int i = 3; i >= 0; i--) {
-                    if (ms[i] != 1 && ms[i] != want_shape[i]) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs to same shape");
+                    if (ms[i] != 1 && ms[i] != want_shape[i]) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs");
                     strides[i] = ms[i] == 1 ? 0 : acc;
                     acc *= ms[i];
                 }
@@ -1304,7 +1339,7 @@ struct AddLayerNormalization : Operator {
         const Tensor &x = want(require(in, 0), DType::F32, "float32"), &r = want(require(in, 1), DType::F32, "float32");
         const Tensor &scale = want(require(in, 2), DType::F32, "float32");
         const Tensor *bias = get(in, 3);
-        if (x.shape() != r.shape()) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs to same shape");
+        if (x.shape() != r.shape()) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs");
         const int64_t cols = x.ndim() ? x.size(x.ndim() - 1) : 1, rows = cols ? x.len() / cols : 0;
         if (scale.len() != cols) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast scale to input shape");
         if (bias && bias->len() != cols) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast bias to input shape");
@@ -1966,14 +2001,18 @@ struct SliceRange { int64_t start, count, step; };
 inline std::vector<SliceRange> resolve_slice(const std::vector<int64_t> &shape, const std::vector<int64_t> &starts, const std::vector<int64_t> &ends,
                                              const std::vector<int64_t> &axes, const std::vector<int64_t> &steps) {
     const int nd = (int)shape.size();
-    if (starts.size() != ends.size() || (!axes.empty() && axes.size() != starts.size()) || (!steps.empty() && steps.size() != starts.size()))
-        throw OpError(OpError::InvalidValue, "Slice: starts, ends, axes and steps must have the same length");
+    // the reference's checks, in its order and words (slice.rs:36-60); absent axes are [0 .. r)
+    if (axes.size() > (size_t)nd) throw OpError(OpError::InvalidValue, "`axes` length must be <= input rank");
+    const size_t n_axes = axes.empty() ? (size_t)nd : axes.size();
+    if (starts.size() != n_axes) throw OpError(OpError::InvalidValue, "`starts` length must match axis count");
+    if (ends.size() != n_axes) throw OpError(OpError::InvalidValue, "`ends` length must match axis count");
+    if (!steps.empty() && steps.size() != n_axes) throw OpError(OpError::InvalidValue, "`steps` length must match axis count");
+    for (int64_t step : steps) if (step == 0) throw OpError(OpError::InvalidValue, "steps must be non-zero");
     std::vector<SliceRange> r((size_t)nd);
     for (int d = 0; d < nd; d++) r[(size_t)d] = {0, shape[(size_t)d], 1};
     for (size_t k = 0; k < starts.size(); k++) {
         const int ax = resolve_axis((int)(axes.empty() ? (int64_t)k : axes[k]), nd);
         const int64_t dim = shape[(size_t)ax], step = steps.empty() ? 1 : steps[k];
-        if (step == 0) throw OpError(OpError::InvalidValue, "Slice: steps must be non-zero");
         int64_t st = starts[k], en = ends[k];
         if (st < 0) st += dim;
         if (en < 0) en += dim;

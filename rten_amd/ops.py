@@ -1112,7 +1112,21 @@ class Sub(_Binary):
 
 
 class Div(_Binary):
+    """binary_elementwise.rs:613-637: a divisor of exactly one element, at any rank, is multiplied by its reciprocal -- a * (1 / b), two roundings --
+    and every other divisor is a true division (`divide`)."""
     fn, opcode, commutative = "rten_hip_div_f32", 3, False
+
+    def run(self, ctx, inputs, in_place=False):
+        a = _want(_require(inputs, 0), np.float32)
+        b = _want(_require(inputs, 1), np.float32)
+        if b.size != 1:
+            return self.divide(ctx, inputs, in_place)
+        r = DeviceTensor(ctx, b.shape, np.float32)
+        ctx.call("rten_hip_unary_f32", L.UNARY_RECIPROCAL, 1, b.vp, r.vp)
+        return Mul().run(ctx, [a, r], in_place)
+
+    def divide(self, ctx, inputs, in_place=False):
+        return super().run(ctx, inputs, in_place)
 
 
 # ------------------------------------------------------------------------------------------ unary math, Pow, PRelu, variadic, Pad
@@ -1291,14 +1305,14 @@ class Sum(_Variadic):
 
 
 class Mean(_Variadic):
-    """Sum, then divided by n as f32 (variadic_elementwise.rs:98-102: a division, through the Div path)."""
+    """Sum, then divided by n as f32 (variadic_elementwise.rs:98-102: x / n, a true division -- not the Div operator's reciprocal rule)."""
     f32_op = L.BINARY_ADD
 
     def run(self, ctx, inputs):
         first = _want(_require(inputs, 0), np.float32)
         ts = self._operands(inputs)
         total = super().run(ctx, [first] + ts[1:])[0]
-        return Div().run(ctx, [total, DeviceTensor.from_numpy(ctx, np.float32(len(ts)))], in_place=True)
+        return Div().divide(ctx, [total, DeviceTensor.from_numpy(ctx, np.float32(len(ts)))], in_place=True)
 
 
 PAD_MODES = {"constant": L.PAD_CONSTANT, "reflect": L.PAD_REFLECT, "edge": L.PAD_EDGE, "wrap": L.PAD_WRAP}

@@ -58,7 +58,7 @@ int main() {
     HostVal g2 = hostops::gather(ints({2, 3}, {1, 2, 3, 4, 5, 6}), ints({2}, {-1, 0}), 1);
     CHECK(g2.shape == (std::vector<int64_t>{2, 2}) && g2.i == std::vector<int64_t>({3, 1, 6, 4}));
     threw = false;
-    try { hostops::gather(dims, ints({}, {2}), 0); } catch (const OpError &e) { threw = e.msg == "Entry in indices is out of range"; }
+    try { hostops::gather(dims, ints({}, {2}), 0); } catch (const OpError &e) { threw = e.msg == "Entry in `indices` is out of range"; }
     CHECK(threw);
     // Slice: position ids [1, 512] -> [:, 0:seq]; clamping; negative step
     HostVal pos = ints({1, 6}, {0, 1, 2, 3, 4, 5});

@@ -152,6 +152,15 @@ def _layout_op(op, ins, attrs):
 LAYOUT_OPS = ("Identity", "Reshape", "Flatten", "Squeeze", "Unsqueeze", "Transpose", "Concat", "Slice", "Split", "Shape", "Gather")
 
 
+def reference_div(a, b):
+    """Div as the reference computes it (binary_elementwise.rs:613-637): a float divisor of exactly one element, at any rank, multiplies by its reciprocal,
+    a * (1 / b), each step rounded in the operands' type; every other divisor divides (tests/glue_rules.py states the rule with its evidence)."""
+    a, b = np.asarray(a), np.asarray(b)
+    if b.size == 1 and b.dtype.kind == "f":
+        return a * (b.dtype.type(1) / b)
+    return np.divide(a, b)
+
+
 def eval_node(node, ins):
     """One node on the f32 oracle.  `ins`: the input arrays (None for an omitted optional input).  Returns the list of outputs."""
     from oracle import einsum as OE
@@ -163,7 +172,7 @@ def eval_node(node, ins):
     x = ins[0]
     with np.errstate(all="ignore"):
         if op in ("Add", "Sub", "Mul", "Div"):  # one correctly rounded IEEE operation per element: numpy is exact
-            fn = {"Add": np.add, "Sub": np.subtract, "Mul": np.multiply, "Div": np.divide}[op]
+            fn = {"Add": np.add, "Sub": np.subtract, "Mul": np.multiply, "Div": reference_div}[op]  # (Div: two operations for a one-element divisor)
             return [np.asarray(fn(ins[0], ins[1]), ins[0].dtype)]
         if op == "Conv":
             x4, w4, pads, strides, dil, one_d = _conv_geometry(x, ins[1], attrs)
@@ -310,7 +319,7 @@ def evaluate64(case, binding=0, teacher=None):
             if op in LAYOUT_OPS:
                 out = _layout_op(op, ins, attrs)
             elif op in ("Add", "Sub", "Mul", "Div"):
-                out = [{"Add": np.add, "Sub": np.subtract, "Mul": np.multiply, "Div": np.divide}[op](ins[0], ins[1])]
+                out = [{"Add": np.add, "Sub": np.subtract, "Mul": np.multiply, "Div": reference_div}[op](ins[0], ins[1])]
             elif op in ("Conv", "ConvInteger"):
                 w = ins[1].astype(np.float64)
                 xx = x.astype(np.float64)

@@ -17,6 +17,7 @@ from oracle import ref
 from rten_amd import lib as L
 from rten_amd import ops
 from rten_amd.tensor import DeviceTensor
+from tests import glue_rules as G
 
 pytestmark = pytest.mark.gpu
 
@@ -904,7 +905,8 @@ def test_binary_ops_numpy_broadcasting(ctx):
               rng.f32(2 * 3 * 4 * 5).reshape(2, 3, 4, 5) + 1]
     for o in others:
         o = np.asarray(o, np.float32)
-        for op, fn in ((ops.Add, np.add), (ops.Mul, np.multiply), (ops.Sub, np.subtract), (ops.Div, np.divide)):
+        # Div by a one-element divisor is a * (1 / b) in the reference (binary_elementwise.rs:613-637, tests/glue_rules.py); every other form divides
+        for op, fn in ((ops.Add, np.add), (ops.Mul, np.multiply), (ops.Sub, np.subtract), (ops.Div, G.div_f32)):
             bits_equal(op().run(ctx, [dev(ctx, x), dev(ctx, o)])[0].numpy(), fn(x, o))
             bits_equal(op().run(ctx, [dev(ctx, o), dev(ctx, x)])[0].numpy(), fn(o, x))
     a, b = rng.f32(3).reshape(3, 1), rng.f32(4).reshape(1, 4)
