@@ -300,9 +300,11 @@ inline Model load(const std::string &path) {
 // on input SHAPES and constants: Shape -> Gather -> Unsqueeze -> Concat -> Reshape, ConstantOfShape -> NonZero (an arange), index arithmetic, comparisons.
 // The reference folds them at load against its symbolic shapes (`propagate_constants`, src/optimize.rs:705; shape inference in src/infer_shapes.rs).  This
 // executor has no shape inference: it evaluates them ON THE HOST while a run walks the plan -- a step whose operands all carry a HostVal computes its result
-// on the host and attaches it to a (cached) device copy; Reshape / Expand / Slice / ConstantOfShape read their shape operands from the HostVal.  Shapes are
-// fixed between `prepare` and the next `bind_input`, so the cached device copies are made once, in the eager warm-up run, and a captured hipGraph contains
-// none of this.  Semantics follow the reference's operators (int32 everywhere: onnx_loader.rs:332-339; wrapping integer arithmetic; booleans 0 / 1).
+// on the host and attaches it to a (cached) device copy; Reshape / Expand / Slice / ConstantOfShape read their shape operands from the HostVal.  A Graph
+// may be run at other input shapes every time: each step caches the device copies of its latest 8 distinct values.  Within Graph::capture the shapes are
+// fixed: the copies are made in its eager warm-up run and the captured hipGraph contains none of this arithmetic, only the copies' addresses -- which is why
+// a copy a live capture may know is never released (Graph::materialize, Context::retire).  (The model ABI is stricter: it refuses bind_input after prepare.)
+// Semantics follow the reference's operators (int32 everywhere: onnx_loader.rs:332-339; wrapping integer arithmetic; booleans 0 / 1).
 namespace hostops {
 constexpr int64_t kMaxHostElems = (int64_t)1 << 22; // beyond this a value is not worth mirroring on the host
 
@@ -947,7 +949,9 @@ class Graph {
 
     // hipGraph capture of one run (launch-bound at small batch: ~60 operators of 5-50 us).  The feeds and the returned
     // outputs keep their device addresses: write new inputs into the same feed tensors, call replay(), read the outputs.
-    // While a capture is alive the context's buffer pool must not serve anyone else (the graph's intermediates live there).
+    // The captured graph's intermediates live in the context's buffer pool: every replay rewrites them, so between replays the pool may serve others --
+    // eager runs of this Graph at other shapes included -- but it must not be trimmed, and nothing may use it WHILE a replay is in flight on another stream.
+    // What the captured graph only reads -- the steps' cached shape constants and reciprocals -- stays in place for as long as the capture lives.
     // `tail` (optional) runs at the end of the captured region, on the capturing stream, with the run's outputs: work recorded there -- e.g. the
     // copy of a sub-batch's rows into a resident full-batch tensor -- replays with the graph.
     const std::vector<Tensor> &capture(const Feeds &feeds, const std::function<void(const std::vector<Tensor> &)> &tail = nullptr) {
@@ -956,6 +960,7 @@ class Graph {
         if (graph_) { // re-capture: the previous executable graph is released first
             ctx_.check(rten_hip_graph_destroy(ctx_.raw(), graph_));
             graph_ = 0;
+            ctx_.capture_destroyed();
         }
         ctx_.check(rten_hip_graph_begin(ctx_.raw()));
         try {
@@ -967,13 +972,14 @@ class Graph {
             throw;
         }
         ctx_.check(rten_hip_graph_end(ctx_.raw(), &graph_));
+        if (graph_) ctx_.capture_made(); // from here on the steps' cached device copies stay where they are (Context::retire)
         return captured_outputs_;
     }
     void replay() {
         if (!graph_) throw GraphError("replay: no captured graph");
         ctx_.check(rten_hip_graph_launch(ctx_.raw(), graph_));
     }
-    ~Graph() { if (graph_) rten_hip_graph_destroy(ctx_.raw(), graph_); }
+    ~Graph() { if (graph_) { rten_hip_graph_destroy(ctx_.raw(), graph_); ctx_.capture_destroyed(); } }
     Graph(const Graph &) = delete;
     Graph &operator=(const Graph &) = delete;
 
@@ -1040,8 +1046,9 @@ class Graph {
             const int id = ids_.at(o.name);
             if (!val[(size_t)id]) throw GraphError("run: output " + o.name + " is not produced by an operator");
             // a graph output that is a graph input or an initializer (not owned by this run), one that is listed twice, and a
-            // view (its storage belongs to a value that dies with this run) are handed out as copies
-            if (!owned[(size_t)id] || moved.count(id) || view_values_.count(id)) {
+            // view (its storage belongs to a value that dies with this run) are handed out as copies; so is whatever else does not own its storage -- the
+            // result of a host-evaluated step (Shape(x), shape arithmetic) aliases that step's cached device copy, which the next runs share and evict
+            if (!owned[(size_t)id] || moved.count(id) || view_values_.count(id) || !owned[(size_t)id]->owns()) {
                 const Tensor &v = moved.count(id) ? result[(size_t)std::distance(outputs_.begin(), std::find_if(outputs_.begin(), outputs_.end(), [&](const onnx::ValueInfo &x) { return x.name == o.name; }))]
                                                   : *val[(size_t)id];
                 Tensor copy(ctx_, v.shape(), v.dtype());
@@ -1825,13 +1832,19 @@ class Graph {
         return d;
     }
 
-    // ---- host-evaluated steps (hostops above).  The device copy of a host-computed value is made once per distinct value and cached with the step: shapes
-    // are fixed between prepare and the next bind_input, so the eager warm-up run that precedes every capture fills the cache and the captured run only
-    // finds hits (an upload inside a capture would be recorded with the host pointer: refused).
-    struct HostCache { std::vector<std::pair<std::shared_ptr<const HostVal>, std::unique_ptr<Tensor>>> entries; };
+    // ---- host-evaluated steps (hostops above).  The device copy of a host-computed value is made once per distinct value and cached with the step, the
+    // latest 8 values each.  Input shapes may change from one run to the next (one Graph serves every binding of its dynamic axes); they are fixed WITHIN
+    // capture(): its eager warm-up run fills the cache and the captured run only finds hits (an upload inside a capture would be recorded with the host
+    // pointer: refused).  The captured graph reads the copies at their addresses, so one that existed when a capture was made is parked, not released, when
+    // later eager runs at other shapes push it out of the cache (Context::retire states the bound).  What a step returns is a view of the cached copy:
+    // good for the run that asked; run() hands a graph output out as a copy of it.
+    struct HostCache {
+        struct Entry { std::shared_ptr<const HostVal> host; std::unique_ptr<Tensor> copy; uint64_t born; };
+        std::vector<Entry> entries;
+    };
     static Tensor materialize(Context &c, HostVal &&hv, HostCache &cache) {
         for (auto &e : cache.entries)
-            if (*e.first == hv) { Tensor v = Tensor::view_of(*e.second, e.second->shape()); v.set_host(e.first); return v; }
+            if (*e.host == hv) { Tensor v = Tensor::view_of(*e.copy, e.copy->shape()); v.set_host(e.host); return v; }
         if (rten_hip_capture_active(c.raw()))
             throw GraphError("a shape-dependent constant changed between the warm-up run and the capture (input shapes must stay fixed while a graph is captured)");
         auto h = std::make_shared<const HostVal>(std::move(hv));
@@ -1840,9 +1853,12 @@ class Graph {
         //  [2, 1] activation -- would be missing in the captured run that follows, whose first request of that size would then allocate inside the capture)
         if (h->is_float) t.reset(new Tensor(Tensor::from_host_unpooled<float>(c, h->shape, h->f.data())));
         else { std::vector<int32_t> w(h->i.begin(), h->i.end()); t.reset(new Tensor(Tensor::from_host_unpooled<int32_t>(c, h->shape, w.data()))); }
-        if (cache.entries.size() >= 8) cache.entries.erase(cache.entries.begin()); // (shapes changed a few times: keep the recent ones)
-        cache.entries.emplace_back(h, std::move(t));
-        Tensor v = Tensor::view_of(*cache.entries.back().second, h->shape);
+        if (cache.entries.size() >= 8) { // (shapes changed a few times: keep the recent ones)
+            cache.entries.front().copy->retire(cache.entries.front().born);
+            cache.entries.erase(cache.entries.begin());
+        }
+        cache.entries.push_back({h, std::move(t), c.stamp()});
+        Tensor v = Tensor::view_of(*cache.entries.back().copy, h->shape);
         v.set_host(h);
         return v;
     }

@@ -63,7 +63,7 @@ class Context {
     Context(rten_hip_ctx *borrowed, Borrow) : h_(borrowed), owned_(false) {
         if (!borrowed) throw OpError(OpError::InvalidValue, "null context");
     }
-    ~Context() { if (h_) { trim_pool(); if (one_) rten_hip_free(h_, one_); if (zero_) rten_hip_free(h_, zero_); if (owned_) rten_hip_destroy(h_); } }
+    ~Context() { if (h_) { for (auto &b : parked_) rten_hip_free(h_, b.first); trim_pool(); if (one_) rten_hip_free(h_, one_); if (zero_) rten_hip_free(h_, zero_); if (owned_) rten_hip_destroy(h_); } }
     Context(const Context &) = delete;
     Context &operator=(const Context &) = delete;
     rten_hip_ctx *raw() const { return h_; }
@@ -100,6 +100,32 @@ class Context {
         for (auto &kv : pool_) for (void *p : kv.second) rten_hip_free(h_, p);
         pool_.clear();
     }
+    // ---- device copies a step keeps ACROSS runs (a host-evaluated step's cached constants, Div's reciprocals) and captured hipGraphs.  A captured graph has
+    // the address of every such copy it read baked in, so a copy that existed when a capture was made must neither be freed nor reach the pool while any
+    // capture on this context is alive.  A cache stamps each copy when it makes it (`stamp`), an executor reports its captures (`capture_made` /
+    // `capture_destroyed`), and a cache that evicts a copy hands the buffer to `retire`: it is parked if a live capture may know it, released otherwise, and
+    // everything parked is released when the last capture is destroyed.  Bound: a cache keeps at most 8 copies, so at most 8 copies per caching step are parked
+    // per capture made since the context last had none alive; copies made AFTER the latest capture are evicted as before.
+    uint64_t stamp() { std::lock_guard<std::mutex> lk(pool_mu_); return ++clock_; }
+    void capture_made() { std::lock_guard<std::mutex> lk(pool_mu_); live_captures_++; pinned_before_ = ++clock_; }
+    void capture_destroyed() {
+        std::vector<std::pair<void *, size_t>> parked;
+        {
+            std::lock_guard<std::mutex> lk(pool_mu_);
+            if (live_captures_ == 0 || --live_captures_ > 0) return;
+            pinned_before_ = 0;
+            parked.swap(parked_);
+        }
+        for (auto &b : parked) release(b.first, b.second);
+    }
+    void retire(void *p, size_t bytes, uint64_t born) {
+        if (!p) return;
+        {
+            std::lock_guard<std::mutex> lk(pool_mu_);
+            if (live_captures_ > 0 && born < pinned_before_) { parked_.emplace_back(p, bytes); return; }
+        }
+        release(p, bytes);
+    }
     const int32_t *zero_i32() { // device-resident int32 0 (x + 0: a raw-word move through the generic element-wise kernel)
         if (!zero_) {
             const int32_t v = 0;
@@ -135,6 +161,9 @@ class Context {
     void *one_ = nullptr, *zero_ = nullptr;
     std::map<size_t, std::vector<void *>> pool_;
     std::mutex pool_mu_; // the pool is shared by concurrent Model::run callers (the C ABI context locks itself)
+    uint64_t clock_ = 0, pinned_before_ = 0; // stamps of kept copies; copies stamped before `pinned_before_` may be known to a live capture
+    size_t live_captures_ = 0;
+    std::vector<std::pair<void *, size_t>> parked_;
 };
 
 // ---- device tensor (the backend's `Value`: contiguous, row-major, device resident)
@@ -221,6 +250,9 @@ class Tensor {
     size_t bytes() const { return (size_t)len() * dtype_size(dtype_); }
     DType dtype() const { return dtype_; }
     void *ptr() const { return ptr_; }
+    bool owns() const { return owns_; } // false for view_of / view_at aliases: somebody else keeps the storage alive
+    // Gives up a copy a step kept across runs (stamped `born` when it was made): Context::retire parks the buffer while a captured graph may know its address
+    void retire(uint64_t born) { if (ptr_ && ctx_ && owns_) ctx_->retire(ptr_, cap_, born); ptr_ = nullptr; }
     template <typename T> std::vector<T> to_host() const {
         std::vector<T> out((size_t)len());
         if (bytes()) ctx_->check(rten_hip_memcpy_d2h(ctx_->raw(), out.data(), ptr_, bytes())); // synchronises
@@ -1143,8 +1175,10 @@ struct Mul : BinaryOp<rten_hip_mul_f32, 1> { Mul() : BinaryOp("Mul") {} };
 struct Sub : BinaryOp<rten_hip_sub_f32, 2> { Sub() : BinaryOp("Sub") {} };
 // Div (binary_elementwise.rs:613-637): a divisor of exactly ONE element, at any rank, is the reference's multiplication by the reciprocal -- a * (1 / b),
 // two roundings, not a / b -- and every other divisor a true division.  (rten_hip_div_f32 and rten_hip_binary_broadcast_f32 op 3 stay true divisions.)
-// The reciprocal of a divisor the host knows is uploaded once per context and value (by the warm-up run that precedes every capture); a device scalar
-// costs one RTEN_HIP_UNARY_RECIPROCAL launch on its element.  Both forms replay from a captured graph.
+// The reciprocal of a divisor the host knows is uploaded once per context and value (by the warm-up run that precedes every capture) and the latest 8 are
+// kept; a divisor may change from run to run (sum / Cast(Shape(x)[-1]) at changing shapes), and a reciprocal that a captured graph read stays where it is
+// until that capture is destroyed (Context::retire).  A device scalar costs one RTEN_HIP_UNARY_RECIPROCAL launch on its element.  Both forms replay from a
+// captured graph.
 struct Div : BinaryOp<rten_hip_div_f32, 3> {
     Div() : BinaryOp("Div") {}
     OutputList run(Context &ctx, const InputList &in) const override {
@@ -1161,8 +1195,11 @@ struct Div : BinaryOp<rten_hip_div_f32, 3> {
             if (!r) {
                 if (rten_hip_capture_active(ctx.raw())) throw OpError(OpError::UnsupportedValue, "Div: the divisor's reciprocal must be uploaded before the run is captured");
                 const float v = 1.0f / h->f[0];
-                if (reciprocals_.size() >= 8) reciprocals_.erase(reciprocals_.begin());
-                reciprocals_.push_back({&ctx, bits, std::unique_ptr<Tensor>(new Tensor(Tensor::from_host_unpooled<float>(ctx, {}, &v)))});
+                if (reciprocals_.size() >= 8) { // (the oldest goes; a captured graph that multiplies by it keeps its buffer: Context::retire)
+                    reciprocals_.front().value->retire(reciprocals_.front().born);
+                    reciprocals_.erase(reciprocals_.begin());
+                }
+                reciprocals_.push_back({&ctx, bits, ctx.stamp(), std::unique_ptr<Tensor>(new Tensor(Tensor::from_host_unpooled<float>(ctx, {}, &v)))});
                 r = reciprocals_.back().value.get();
             }
             const Tensor rv = Tensor::view_of(*r, b.shape());
@@ -1173,7 +1210,7 @@ struct Div : BinaryOp<rten_hip_div_f32, 3> {
         return mul.run(ctx, {in[0], &r});
     }
   private:
-    struct Entry { const Context *ctx; uint32_t bits; std::unique_ptr<Tensor> value; };
+    struct Entry { const Context *ctx; uint32_t bits; uint64_t born; std::unique_ptr<Tensor> value; };
     mutable std::vector<Entry> reciprocals_;
     mutable std::mutex mu_;
 };

@@ -152,6 +152,16 @@ def _layout_op(op, ins, attrs):
 LAYOUT_OPS = ("Identity", "Reshape", "Flatten", "Squeeze", "Unsqueeze", "Transpose", "Concat", "Slice", "Split", "Shape", "Gather")
 
 
+GLUE_OPS = ("Equal", "Where", "Expand", "ConstantOfShape")
+_CAST_TO = {ow.FLOAT: np.float32, ow.INT32: np.int32, ow.INT64: np.int32, ow.UINT8: np.uint8, ow.INT8: np.int8}
+
+
+def _narrow(a):
+    """int64 is int32 from load on (onnx_loader.rs:332-339, saturating): what every integer value of a graph is to the executor."""
+    a = np.asarray(a)
+    return np.clip(a, -(1 << 31), (1 << 31) - 1).astype(np.int32) if a.dtype == np.int64 else a
+
+
 def reference_div(a, b):
     """Div as the reference computes it (binary_elementwise.rs:613-637): a float divisor of exactly one element, at any rank, multiplies by its reciprocal,
     a * (1 / b), each step rounded in the operands' type; every other divisor divides (tests/glue_rules.py states the rule with its evidence)."""
@@ -165,6 +175,8 @@ def eval_node(node, ins):
     """One node on the f32 oracle.  `ins`: the input arrays (None for an omitted optional input).  Returns the list of outputs."""
     from oracle import einsum as OE
     from oracle import ref
+    from tests import glue_rules as GR
+    from tests import rnn_rules as RR
     from tests import select_rules as SR
     op, attrs = node["op"], node["attrs"]
     if op in LAYOUT_OPS:
@@ -184,8 +196,23 @@ def eval_node(node, ins):
             wzp = ins[3] if len(ins) > 3 and ins[3] is not None else None
             return [ref.conv2d_int8(x4, w4, x_zp=int(ins[2]), w_zp=wzp, pads=pads, strides=strides, dilations=dil, groups=attrs.get("group", 1))]
         if op == "Cast":
-            assert attrs["to"] == ow.FLOAT
-            return [x.astype(F)]
+            if attrs["to"] == ow.FLOAT and x.dtype != np.int64:
+                return [x.astype(F)]
+            return [GR.cast(_narrow(x), _CAST_TO[attrs["to"]])]
+        if op in GLUE_OPS:  # the shape-polymorphic graphs of tests/graph_sessions.py: the reference's rules as tests/glue_rules.py states them
+            ins = [None if a is None else _narrow(a) for a in ins]
+            if op == "Equal":
+                return [GR.compare("Equal", ins[0], ins[1])]
+            if op == "Where":
+                return [GR.where(ins[0], ins[1], ins[2])]
+            if op == "Expand":
+                return [GR.expand(ins[0], ins[1])]
+            fill = attrs.get("value")
+            return [GR.constant_of_shape(ins[0], None if fill is None else np.asarray(fill).reshape(-1)[0])]
+        if op in ("GRU", "LSTM"):  # tests/rnn_rules.py; outputs Y, Y_h (, Y_c)
+            kw = dict(b=ins[3] if len(ins) > 3 else None, direction=attrs.get("direction", "forward"))
+            assert all(a is None for a in ins[4:]), "the session graphs give no sequence_lens / initial state"
+            return list((RR.gru if op == "GRU" else RR.lstm)(ins[0], ins[1], ins[2], **kw))
         if op == "DynamicQuantizeLinear":
             q, s, z = ref.dynamic_quantize_linear(x)
             return [q, np.asarray(s, F), np.asarray(z, np.uint8)]
@@ -296,11 +323,41 @@ def evaluate(case, binding=0, fused=True):
             out = eval_node(n, [vals[s] if s else None for s in n["inputs"]])
         for name, v in zip(n["outputs"], out):
             if name:
-                vals[name] = v
+                vals[name] = _narrow(v)  # (Shape and what is computed from it: int32 to the executor, so a graph output of that kind reads back as I32)
     return vals
 
 
 # ------------------------------------------------------------------------------------------------ independent float64 evaluation
+def _rnn64(op, ins, attrs):
+    """ONNX GRU (linear_before_reset=1, gates z r h) / LSTM (gates i o f c) with the default activations, zero initial state, in float64."""
+    x, w, r = (np.asarray(a, np.float64) for a in ins[:3])
+    b = np.asarray(ins[3], np.float64) if len(ins) > 3 and ins[3] is not None else None
+    direction = attrs.get("direction", "forward")
+    seq, batch, _ = x.shape
+    G = 3 if op == "GRU" else 4
+    dirs, H = w.shape[0], w.shape[1] // G
+    sg = lambda v: 1.0 / (1.0 + np.exp(-v))
+    y = np.zeros((seq, dirs, batch, H))
+    h, c = np.zeros((dirs, batch, H)), np.zeros((dirs, batch, H))
+    for d in range(dirs):
+        backwards = direction == "reverse" or d == 1
+        wb = b[d, :G * H] if b is not None else 0.0
+        rb = b[d, G * H:] if b is not None else 0.0
+        for t in (reversed(range(seq)) if backwards else range(seq)):
+            gx, gh = x[t] @ w[d].T + wb, h[d] @ r[d].T + rb
+            if op == "GRU":
+                z, rr = sg(gx[:, :H] + gh[:, :H]), sg(gx[:, H:2 * H] + gh[:, H:2 * H])
+                cand = np.tanh(gx[:, 2 * H:] + rr * gh[:, 2 * H:])
+                h[d] = (1.0 - z) * cand + z * h[d]
+            else:
+                g = gx + gh
+                i, o, f = sg(g[:, :H]), sg(g[:, H:2 * H]), sg(g[:, 2 * H:3 * H])
+                c[d] = f * c[d] + i * np.tanh(g[:, 3 * H:])
+                h[d] = o * np.tanh(c[d])
+            y[t, d] = h[d]
+    return [y, h.copy()] + ([c.copy()] if op == "LSTM" else [])
+
+
 def evaluate64(case, binding=0, teacher=None):
     """Every value in float64 with numpy / torch-CPU only.  Integer-valued results (u8 codes, zero points, indices) cannot be carried in a
     different precision: they are computed here for the comparison and then replaced by `teacher`'s (the f32 interpreter's) values, so that one
@@ -335,7 +392,18 @@ def evaluate64(case, binding=0, teacher=None):
                 y = conv(T(xp), T(w), b, stride=tuple(attrs.get("strides", [1] * nsp)), dilation=tuple(attrs.get("dilations", [1] * nsp)), groups=attrs.get("group", 1)).numpy()
                 out = [np.rint(y).astype(np.int32) if op == "ConvInteger" else y]
             elif op == "Cast":
-                out = [x.astype(np.float64)]
+                out = [x.astype(np.float64) if attrs["to"] == ow.FLOAT else np.trunc(x).astype(np.int64)]
+            elif op == "Equal":
+                out = [(ins[0] == ins[1]).astype(np.int32)]
+            elif op == "Where":
+                out = [np.where(np.asarray(ins[0]) != 0, ins[1], ins[2])]
+            elif op == "Expand":
+                out = [np.array(np.broadcast_to(x, np.broadcast_shapes(x.shape, tuple(int(d) for d in ins[1]))))]
+            elif op == "ConstantOfShape":
+                fill = np.asarray(attrs["value"]).reshape(-1)[0] if attrs.get("value") is not None else np.float64(0)
+                out = [np.full([int(d) for d in x], fill, np.float64 if np.asarray(fill).dtype.kind == "f" else np.int64)]
+            elif op in ("GRU", "LSTM"):
+                out = _rnn64(op, ins, attrs)
             elif op == "DynamicQuantizeLinear":  # the ONNX definition
                 lo, hi = min(0.0, float(x.min())), max(0.0, float(x.max()))
                 s = (hi - lo) / 255.0
