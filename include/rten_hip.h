@@ -591,6 +591,14 @@ int32_t rten_hip_copy_rows_b32(rten_hip_ctx *ctx, int64_t rows, int64_t row_elem
 #define RTEN_HIP_RESIZE_NEAREST_CEIL 3
 int32_t rten_hip_resize_f32(rten_hip_ctx *ctx, int32_t mode, int32_t coord_mode, int32_t nearest_mode, int64_t planes, int64_t in_h, int64_t in_w,
                             int64_t out_h, int64_t out_w, float inv_scale_y, float inv_scale_x, const float *x, float *y);
+/* GridSample (grid_sample, src/ops/grid_sample.rs:12-125): bilinear, zero padding.  Per output pixel, every step one rounded f32 operation:
+ * u = (g + 1) * 0.5; s = (len - 1) * u with align_corners, len * u - 0.5 without; w = s - floor(s); i = floor(s) as Rust casts to i32 (saturating,
+ * NaN -> 0); the neighbour is i + 1; a pixel outside [0, in_h) x [0, in_w) is +0 and is never read; top = p00 + (p01 - p00) * wx, bottom likewise,
+ * out = top + (bottom - top) * wy.  A neighbour with zero weight still contributes (its NaN or Inf propagates).  in_h == 0 || in_w == 0 gives all
+ * zeros; an empty output launches nothing; a negative size (or one above 2^31 - 1) is RTEN_HIP_ERR_INVALID_VALUE.  No host read-back, capture-safe. */
+int32_t rten_hip_grid_sample_f32(rten_hip_ctx *ctx, int32_t align_corners, int64_t batch, int64_t channels, int64_t in_h, int64_t in_w, int64_t out_h,
+                                 int64_t out_w, const float *x /* [batch, channels, in_h, in_w] */,
+                                 const float *grid /* [batch, out_h, out_w, 2], (x, y) in [-1, 1] */, float *y /* [batch, channels, out_h, out_w] */);
 /* 1 while a graph capture is active on `ctx` (rten_hip_graph_begin .. _end): host code must not upload from host memory then -- the copy would be
  * recorded with the host pointer and re-read at every replay. */
 int32_t rten_hip_capture_active(rten_hip_ctx *ctx);

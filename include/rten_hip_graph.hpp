@@ -1171,6 +1171,33 @@ class Graph {
         if (n.inputs.size() > 1 && !n.inputs[1].empty() && graph_input_named(m, n.inputs[1]))
             throw GraphError(n.op_type + " " + label + ": the axes input must be a constant (it is the graph input \"" + n.inputs[1] + "\", device data at run time)");
     }
+    // What the loader reads from, and refuses about, a GridSample node (onnx_registry.rs:1203-1212): align_corners defaults to 0; mode must be
+    // "bilinear" (opset 16) or "linear" (opset 20), padding_mode "zeros".  Needs no device; rten_hip_run --parse-only calls it too.
+    struct GridSampleNode { bool align_corners = false; };
+    static GridSampleNode read_grid_sample_node(const onnx::Node &n, const std::string &label) {
+        GridSampleNode a;
+        a.align_corners = n.get_int("align_corners", 0) != 0;
+        if (const onnx::Attr *mode = n.attr("mode"))
+            if (mode->s != "bilinear" && mode->s != "linear") throw GraphError("GridSample " + label + ": mode=\"" + mode->s + "\" is not supported (bilinear / linear only)");
+        if (const onnx::Attr *pad = n.attr("padding_mode"))
+            if (pad->s != "zeros") throw GraphError("GridSample " + label + ": padding_mode=\"" + pad->s + "\" is not supported (zeros only)");
+        return a;
+    }
+    // ... and a DepthToSpace node (onnx_registry.rs:1094-1107): mode "DCR" (the default) or "CRD"; blocksize is required and must fit the
+    // reference's u32 (0 is read, and refused by the operator: "`block_size` must be > 0").
+    struct DepthToSpaceNode { int64_t block_size = 0; DepthToSpaceMode mode = DepthToSpaceMode::DepthColumnRow; };
+    static DepthToSpaceNode read_depth_to_space_node(const onnx::Node &n, const std::string &label) {
+        DepthToSpaceNode a;
+        if (const onnx::Attr *mode = n.attr("mode")) {
+            if (mode->s == "CRD") a.mode = DepthToSpaceMode::ColumnRowDepth;
+            else if (mode->s != "DCR") throw GraphError("DepthToSpace " + label + ": mode=\"" + mode->s + "\" is not supported (DCR / CRD only)");
+        }
+        const onnx::Attr *bs = n.attr("blocksize");
+        if (!bs) throw GraphError("DepthToSpace " + label + ": the blocksize attribute is missing");
+        if (bs->i < 0 || bs->i > 0xffffffffll) throw GraphError("DepthToSpace " + label + ": blocksize " + std::to_string(bs->i) + " is out of range");
+        a.block_size = bs->i;
+        return a;
+    }
     static bool is_math_kind(const std::string &k) {
         static const std::set<std::string> kinds = {"Neg", "Abs", "Sign", "Floor", "Ceil", "Round", "Sqrt", "Reciprocal", "Exp", "Log", "Softplus", "Pow", "PRelu", "Min", "Max", "Sum", "Mean"};
         return kinds.count(k) != 0;
@@ -2527,6 +2554,17 @@ class Graph {
                 const std::string nm = st.name;
                 st.run = [this, op, nm](Context &c, const InputList &in) { note_axis("LpNormalization", nm, op->axis, require(in, 0)); return op->run(c, in); };
             } else if (kind == "GlobalMaxPool") run_plainly(st, std::make_shared<GlobalMaxPool>()); // per (n, c) plane: rows of the batch are independent
+            else if (kind == "GridSample") { // per batch row (the grid's dim 0 is the input's); one launch, nothing read back, no shape from data
+                auto op = std::make_shared<GridSample>();
+                op->align_corners = read_grid_sample_node(n, st.name).align_corners;
+                run_plainly(st, op);
+            } else if (kind == "DepthToSpace") { // a permutation inside every batch row: one transpose launch
+                const DepthToSpaceNode a = read_depth_to_space_node(n, st.name);
+                auto op = std::make_shared<DepthToSpace>();
+                op->block_size = a.block_size;
+                op->mode = a.mode;
+                run_plainly(st, op);
+            }
             else if (kind == "ArgMax" || kind == "ArgMin" || kind == "TopK" || kind == "Softmax") make_select_step(st, n);
             else if (kind == "Resize" || kind == "Upsample") make_resize_step(st, n);
             else if (kind == "Split") make_split_step(st, n);

@@ -2215,6 +2215,56 @@ struct Upsample : Resize {
     }
 };
 
+// GridSample (src/ops/grid_sample.rs:17-145): bilinear sampling with zero padding of X [N, C, H, W] at grid [N, H_out, W_out, 2]; one
+// rten_hip_grid_sample_f32 launch (rten_amd/csrc/sample.hip).  The loaders refuse every other mode / padding_mode (onnx_registry.rs:1203-1212).
+struct GridSample : Operator {
+    bool align_corners = false;
+    const char *name() const override { return "GridSample"; }
+    int max_inputs() const override { return 2; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = want(require(in, 0), DType::F32, "float32");
+        if (x.ndim() != 4) throw OpError(OpError::InvalidValue, "input must have 4 dims (NCHW)");
+        const Tensor &grid = want(require(in, 1), DType::F32, "float32");
+        if (grid.ndim() != 4) throw OpError(OpError::InvalidValue, "grid must have 4 dims");
+        if (grid.size(0) != x.size(0)) throw OpError(OpError::IncompatibleInputShapes, "Batch size of input and grid must match");
+        if (grid.size(3) != 2) throw OpError(OpError::UnsupportedValue, "Unsupported grid coordinate size");
+        Tensor y(ctx, {x.size(0), x.size(1), grid.size(1), grid.size(2)}, DType::F32);
+        if (y.len())
+            ctx.check(rten_hip_grid_sample_f32(ctx.raw(), align_corners ? 1 : 0, x.size(0), x.size(1), x.size(2), x.size(3), grid.size(1), grid.size(2), (const float *)x.ptr(),
+                                               (const float *)grid.ptr(), (float *)y.ptr()));
+        OutputList out;
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+
+// DepthToSpace (src/ops/layout.rs:22-103): the permutation of the ONNX specification as ONE rten_hip_transpose_b32 launch on the 6-D view the
+// reference builds -- DCR [n, b, b, c', h, w] by (0, 3, 4, 1, 5, 2), CRD [n, c', b, b, h, w] by (0, 1, 4, 2, 5, 3) -- read as [n, c', h * b, w * b].
+// float32 only, as the reference's run().
+enum class DepthToSpaceMode { DepthColumnRow, ColumnRowDepth };
+struct DepthToSpace : Operator {
+    int64_t block_size = 0; // the attribute is required (onnx_registry.rs:1106)
+    DepthToSpaceMode mode = DepthToSpaceMode::DepthColumnRow;
+    const char *name() const override { return "DepthToSpace"; }
+    int max_inputs() const override { return 1; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = want(require(in, 0), DType::F32, "float32");
+        if (block_size <= 0) throw OpError(OpError::InvalidValue, "`block_size` must be > 0");
+        if (x.ndim() != 4) throw OpError(OpError::InvalidValue, "input must have 4 dims (NCHW)");
+        const int64_t n = x.size(0), c = x.size(1), h = x.size(2), w = x.size(3), b = block_size;
+        if (b > 0x7fffffff || c % (b * b) != 0) throw OpError(OpError::InvalidValue, "input channels must be a multiple of `block_size` squared");
+        const int64_t nc = c / (b * b);
+        const bool dcr = mode == DepthToSpaceMode::DepthColumnRow;
+        const std::vector<int64_t> view = dcr ? std::vector<int64_t>{n, b, b, nc, h, w} : std::vector<int64_t>{n, nc, b, b, h, w};
+        const int32_t dcr_perm[6] = {0, 3, 4, 1, 5, 2}, crd_perm[6] = {0, 1, 4, 2, 5, 3};
+        Tensor y(ctx, {n, nc, h * b, w * b}, DType::F32);
+        if (y.len()) ctx.check(rten_hip_transpose_b32(ctx.raw(), 6, view.data(), dcr ? dcr_perm : crd_perm, x.ptr(), y.ptr()));
+        OutputList out;
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+
 // Split (src/ops/split.rs:34-136) of 4-byte tensors, one strided copy per piece: the sizes of input 1 (the opset < 13 `split` attribute arrives
 // there too), else `num_outputs` (opset 18), else the node's output count, as equal chunks of ceil(dim / n) -- the last piece is smaller, and there
 // may be fewer than n pieces (5 split 4 ways gives 3).
@@ -3160,6 +3210,8 @@ class OpRegistry {
         r.register_op<ReduceProd>("ReduceProd");
         r.register_op<LpNormalization>("LpNormalization");
         r.register_op<GlobalMaxPool>("GlobalMaxPool");
+        r.register_op<GridSample>("GridSample");
+        r.register_op<DepthToSpace>("DepthToSpace");
         return r;
     }
 

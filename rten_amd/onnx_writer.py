@@ -584,3 +584,55 @@ def reduce_family_graph(batch="batch", channels: int = 3, height: int = 5, width
             value_info("log_sum", FLOAT, [batch, channels]), value_info("sum_square", FLOAT, [batch, channels, height, 1]), value_info("l1_noop", FLOAT, shape),
             value_info("log_sum_exp_noop", FLOAT, shape)]
     return model(nodes, [value_info("x", FLOAT, shape)], outs, inits, opset=18)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Image-to-image graphs: flow warping (GridSample) and sub-pixel super-resolution (DepthToSpace as TensorFlow / Keras
+# derived exporters write it; PyTorch's own exporter writes PixelShuffle as Reshape / Transpose / Reshape)
+# ----------------------------------------------------------------------------------------------------------------
+def base_grid(height: int, width: int, align_corners: bool = False):
+    """The identity sampling grid [1, H, W, 2] of GridSample: (x, y) of every output pixel's centre in [-1, 1]."""
+    def axis(n):
+        i = np.arange(n, dtype=np.float32)
+        if align_corners:
+            return (i * np.float32(2) / np.float32(max(n - 1, 1)) - np.float32(1)).astype(np.float32)
+        return ((i * np.float32(2) + np.float32(1)) / np.float32(n) - np.float32(1)).astype(np.float32)
+    gx, gy = np.meshgrid(axis(width), axis(height))
+    return np.stack([gx, gy], -1)[None].astype(np.float32)
+
+
+def flow_warp_graph(seed: int = 21, height: int = 6, width: int = 9, channels: int = 5, align_corners: bool = False, mode: str = "bilinear",
+                    padding_mode: str = "zeros", batch="batch"):
+    """x [batch, 3, h, w], flow [batch, 2, H, W] (normalised offsets) ->
+         feat  Conv 3x3 (3 -> channels), pad 1                                 [batch, channels, h, w]
+         grid  Transpose(flow, 0 2 3 1) + the constant identity grid           [batch, H, W, 2]
+         warp  GridSample(feat, grid)                                          [batch, channels, H, W]
+         y     Conv 1x1 (channels -> 3)
+    h and w are free: the sampled plane need not have the grid's size.  Returns (model bytes, weights dict); `mode` / `padding_mode` other than
+    the defaults give graphs the loader refuses at the node named "warp"."""
+    rng = np.random.default_rng(seed)
+    w = {"feat": (rng.normal(0, 0.3, (channels, 3, 3, 3)).astype(np.float32), rng.normal(0, 0.1, channels).astype(np.float32)),
+         "out": (rng.normal(0, 0.3, (3, channels, 1, 1)).astype(np.float32), rng.normal(0, 0.1, 3).astype(np.float32)),
+         "base_grid": base_grid(height, width, align_corners)}
+    inits = [tensor("feat.w", w["feat"][0]), tensor("feat.b", w["feat"][1]), tensor("out.w", w["out"][0]), tensor("out.b", w["out"][1]), tensor("base_grid", w["base_grid"])]
+    nodes = [node("Conv", ["x", "feat.w", "feat.b"], ["feat"], name="feat", kernel_shape=[3, 3], pads=[1, 1, 1, 1]),
+             node("Transpose", ["flow"], ["flow_nhwc"], name="flow_nhwc", perm=[0, 2, 3, 1]),
+             node("Add", ["flow_nhwc", "base_grid"], ["grid"], name="grid"),
+             node("GridSample", ["feat", "grid"], ["warped"], name="warp", mode=mode, padding_mode=padding_mode, align_corners=int(align_corners)),
+             node("Conv", ["warped", "out.w", "out.b"], ["y"], name="out", kernel_shape=[1, 1])]
+    ins = [value_info("x", FLOAT, [batch, 3, "h", "w"]), value_info("flow", FLOAT, [batch, 2, height, width])]
+    return model(nodes, ins, [value_info("y", FLOAT, [batch, 3, height, width])], inits, opset=16, name="flow_warp"), w
+
+
+def subpixel_sr_graph(mode: str = "DCR", block: int = 2, seed: int = 23, features: int = 6, batch="batch"):
+    """x [batch, 3, h, w] -> Conv 3x3 (3 -> features) -> Relu -> Conv 3x3 (features -> 3 * block^2) -> DepthToSpace(block, mode) [batch, 3, h * block, w * block].
+    Returns (model bytes, weights dict).  The weights depend on the seed only, so the DCR and CRD variants (and a PixelShuffle export) can share them."""
+    rng = np.random.default_rng(seed)
+    w = {"c1": (rng.normal(0, 0.3, (features, 3, 3, 3)).astype(np.float32), rng.normal(0, 0.1, features).astype(np.float32)),
+         "c2": (rng.normal(0, 0.2, (3 * block * block, features, 3, 3)).astype(np.float32), rng.normal(0, 0.1, 3 * block * block).astype(np.float32))}
+    inits = [tensor("c1.w", w["c1"][0]), tensor("c1.b", w["c1"][1]), tensor("c2.w", w["c2"][0]), tensor("c2.b", w["c2"][1])]
+    nodes = [node("Conv", ["x", "c1.w", "c1.b"], ["a"], name="c1", kernel_shape=[3, 3], pads=[1, 1, 1, 1]),
+             node("Relu", ["a"], ["a.r"], name="c1.relu"),
+             node("Conv", ["a.r", "c2.w", "c2.b"], ["b"], name="c2", kernel_shape=[3, 3], pads=[1, 1, 1, 1]),
+             node("DepthToSpace", ["b"], ["y"], name="shuffle", blocksize=block, mode=mode)]
+    return model(nodes, [value_info("x", FLOAT, [batch, 3, "h", "w"])], [value_info("y", FLOAT, [batch, 3, "H", "W"])], inits, opset=13, name="subpixel_sr"), w

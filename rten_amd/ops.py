@@ -2108,6 +2108,69 @@ class Upsample(Resize):
         return [self.resize(ctx, x, scales=scales.astype(np.float32))]
 
 
+class GridSample(Operator):
+    """src/ops/grid_sample.rs:17-145 (rten_hip_grid_sample_f32): bilinear sampling with zero padding of X [N, C, H, W] at grid [N, H_out, W_out, 2].
+    The loaders refuse every other mode / padding_mode (onnx_registry.rs:1203-1212)."""
+
+    def __init__(self, align_corners=False):
+        self.align_corners = align_corners
+
+    def max_inputs(self):
+        return 2
+
+    def run(self, ctx, inputs):
+        x = _want(_require(inputs, 0), np.float32)
+        if len(x.shape) != 4:
+            raise InvalidValue("input must have 4 dims (NCHW)")
+        grid = _want(_require(inputs, 1), np.float32)
+        if len(grid.shape) != 4:
+            raise InvalidValue("grid must have 4 dims")
+        if grid.shape[0] != x.shape[0]:
+            raise IncompatibleInputShapes("Batch size of input and grid must match")
+        if grid.shape[3] != 2:
+            raise UnsupportedValue("Unsupported grid coordinate size")
+        n, c, h, w = x.shape
+        y = DeviceTensor(ctx, (n, c, grid.shape[1], grid.shape[2]), np.float32)
+        if y.size:
+            ctx.call("rten_hip_grid_sample_f32", 1 if self.align_corners else 0, n, c, h, w, grid.shape[1], grid.shape[2], x.vp, grid.vp, y.vp)
+        return [y]
+
+
+DEPTH_TO_SPACE_PERMS = {"DCR": (0, 3, 4, 1, 5, 2), "CRD": (0, 1, 4, 2, 5, 3)}
+
+
+class DepthToSpace(Operator):
+    """src/ops/layout.rs:22-103: ONE rten_hip_transpose_b32 launch on the 6-D view the reference builds -- DCR [n, b, b, c', h, w] by (0, 3, 4, 1, 5, 2),
+    CRD [n, c', b, b, h, w] by (0, 1, 4, 2, 5, 3) -- read as [n, c', h * b, w * b].  float32 only, as the reference's run()."""
+
+    def __init__(self, block_size, mode="DCR"):
+        if mode not in DEPTH_TO_SPACE_PERMS:  # (the reference's DepthToSpaceMode has the two variants only; its loader refuses any other string)
+            raise UnsupportedValue("DepthToSpace mode must be DCR or CRD")
+        self.block_size, self.mode = block_size, mode
+
+    def max_inputs(self):
+        return 1
+
+    def run(self, ctx, inputs):
+        x = _want(_require(inputs, 0), np.float32)
+        if self.mode not in DEPTH_TO_SPACE_PERMS:
+            raise UnsupportedValue("DepthToSpace mode must be DCR or CRD")
+        b = int(self.block_size)
+        if b <= 0:
+            raise InvalidValue("`block_size` must be > 0")
+        if len(x.shape) != 4:
+            raise InvalidValue("input must have 4 dims (NCHW)")
+        n, c, h, w = x.shape
+        if c % (b * b) != 0:
+            raise InvalidValue("input channels must be a multiple of `block_size` squared")
+        nc = c // (b * b)
+        view = (n, b, b, nc, h, w) if self.mode == "DCR" else (n, nc, b, b, h, w)
+        y = DeviceTensor(ctx, (n, nc, h * b, w * b), np.float32)
+        if y.size:
+            ctx.call("rten_hip_transpose_b32", 6, (C.c_int64 * 6)(*view), (C.c_int32 * 6)(*DEPTH_TO_SPACE_PERMS[self.mode]), x.vp, y.vp)
+        return [y]
+
+
 class Split(Operator):
     """src/ops/split.rs:34-136 on 4-byte tensors (one rten_hip_copy_strided_b32 per piece): the sizes of input 1, else `num_outputs`, else the
     node's output count as equal chunks of ceil(dim / n) -- the last piece is smaller, and there may be fewer than n pieces (5 split 4 ways
@@ -2268,7 +2331,7 @@ class OpRegistry:
                    AveragePool, GlobalAveragePool, Flatten, DynamicQuantizeLinear, Attention, Gather, ReduceSum, ReduceMean, Einsum, Resize, Upsample,
                    Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK, GRU, LSTM, Neg, Abs, Sign, Floor, Ceil, Round, Sqrt, Reciprocal, Exp, Log, Softplus,
                    Pow, PRelu, Min, Max, Sum, Mean, Pad, QuantizeLinear, DequantizeLinear, ReduceL1, ReduceL2, ReduceSumSquare, ReduceLogSum, ReduceLogSumExp,
-                   ReduceProd, LpNormalization, GlobalMaxPool):
+                   ReduceProd, LpNormalization, GlobalMaxPool, GridSample, DepthToSpace):
             r.register_op(op)
         return r
 

@@ -338,6 +338,44 @@ def main():
                          (lambda xl_=xl_, yl_=yl_, rows_lp=rows_lp: ctx.call("rten_hip_memcpy_d2d", yl_.vp, xl_.vp, C.c_size_t(4 * rows_lp * 768))), 8.0 * rows_lp * 768))
     for k in range(0, len(lp_specs), 2):  # (two specs share a name across the shapes: one group per shape keeps their samples apart)
         alternating("LpNormalization " + lp_specs[k][1], lp_specs[k:k + 2])
+    # ---- GridSample (rten_amd/csrc/sample.hip) and DepthToSpace (one rten_hip_transpose_b32 launch on a 6-D view).  Bytes: x and y once, the grid's
+    # 8 bytes per output pixel.  The identity-grid row reads what a same-size bilinear Resize reads and writes the same output, so that Resize
+    # (existing code) is timed beside it in the same loop, round by round; a uniformly random grid is the gather's worst case.
+    from rten_amd import onnx_writer as _ow
+
+    def gs_rows(label, n_, c_, h_, w_, oh_, ow_, grid_np, with_resize=False):
+        xg_ = dev(rng.standard_normal((n_, c_, h_, w_), dtype=np.float32))
+        gg_, yg_ = dev(grid_np), empty((n_, c_, oh_, ow_))
+        nbytes = 4.0 * n_ * c_ * (h_ * w_ + oh_ * ow_)
+        gbytes = 8.0 * n_ * oh_ * ow_
+        shape = f"{n_}x{c_}x{h_}x{w_} at {n_}x{oh_}x{ow_}x2"
+        specs = [(f"image: GridSample {label}", shape, (lambda: ctx.call("rten_hip_grid_sample_f32", 0, n_, c_, h_, w_, oh_, ow_, xg_.vp, gg_.vp, yg_.vp)), nbytes + gbytes)]
+        if with_resize:
+            specs.append(("image: Resize linear half_pixel, same input and output size (yardstick)", f"{n_}x{c_}x{h_}x{w_} -> {oh_}x{ow_}",
+                          (lambda: ctx.call("rten_hip_resize_f32", L.RESIZE_MODE_LINEAR, L.RESIZE_COORD_HALF_PIXEL, L.RESIZE_NEAREST_FLOOR, n_ * c_, h_, w_, oh_, ow_,
+                                            h_ / oh_, w_ / ow_, xg_.vp, yg_.vp)), nbytes))
+        before = len(rows)
+        alternating(f"GridSample {label} {shape}", specs)
+        for row in rows[before:]:
+            if row["op"].startswith("image: GridSample"):
+                row["grid_bytes"] = int(gbytes)
+    if want("image: GridSample"):
+        ident = lambda n_, h_, w_: np.ascontiguousarray(np.broadcast_to(_ow.base_grid(h_, w_), (n_, h_, w_, 2)))
+        gs_rows("identity grid", 8, 64, 128, 128, 128, 128, ident(8, 128, 128), with_resize=True)
+        gs_rows("random grid", 8, 64, 128, 128, 128, 128, rng.uniform(-1, 1, (8, 128, 128, 2)).astype(np.float32))
+        gs_rows("flow warp (identity + N(0, 0.05))", 2, 3, 512, 512, 512, 512, (ident(2, 512, 512) + rng.normal(0, 0.05, (2, 512, 512, 2))).astype(np.float32))
+        gs_rows("deformable attention points", 64, 32, 32, 32, 100, 4, rng.uniform(-1, 1, (64, 100, 4, 2)).astype(np.float32))
+    if want("image: DepthToSpace"):
+        nd2s = 8 * 256 * 128 * 128
+        xd_, yd_ = dev(rng.standard_normal((nd2s,), dtype=np.float32)), empty((nd2s,))
+        i32 = lambda *v: (C.c_int32 * len(v))(*v)
+        alternating("DepthToSpace 8x256x128x128", [
+            ("image: DepthToSpace DCR block 2 (one 6-D transpose)", "8x256x128x128 -> 8x64x256x256",
+             (lambda: ctx.call("rten_hip_transpose_b32", 6, i64(8, 2, 2, 64, 128, 128), i32(0, 3, 4, 1, 5, 2), xd_.vp, yd_.vp)), 8.0 * nd2s),
+            ("image: DepthToSpace CRD block 2 (one 6-D transpose)", "8x256x128x128 -> 8x64x256x256",
+             (lambda: ctx.call("rten_hip_transpose_b32", 6, i64(8, 64, 2, 2, 128, 128), i32(0, 1, 4, 2, 5, 3), xd_.vp, yd_.vp)), 8.0 * nd2s),
+            ("image: copy, DepthToSpace's size (reference point)", f"{4 * nd2s} B", (lambda: ctx.call("rten_hip_memcpy_d2d", yd_.vp, xd_.vp, C.c_size_t(4 * nd2s))), 8.0 * nd2s)])
+        del xd_, yd_
     xs = dev(rng.standard_normal((1, 21, 512, 512), dtype=np.float32))
     ys = empty((512 * 512,), np.int32)
     hbm("ArgMax over channels", "1x21x512x512", (lambda: ctx.call("rten_hip_arg_minmax_strided", 0, 0, 1, i64(512 * 512), i64(1), 21, 512 * 512, xs.vp, ys.vp)),

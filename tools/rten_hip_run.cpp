@@ -16,7 +16,7 @@
 //     -t, --timing           per-operator table (each operator followed by a sync)
 //     --tune                 time the candidate launch plans of every f32 convolution at load and keep the fastest
 //     --graph                capture one run into a hipGraph and replay it for the timed runs
-//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow, Reduce*, LpNormalization and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
+//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow, Reduce*, LpNormalization, GridSample, DepthToSpace and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
 //     --safetensors-info F   list the tensors of a Safetensors file (with --save-outputs: re-write it); no model, no GPU
 //
 // There is no CPU fallback: without an MI355X the tool reports BackendUnavailable and exits 2.
@@ -158,6 +158,21 @@ int main(int argc, char **argv) {
                 } else if (Graph::reduce_family_kind(n.op_type) >= 0) {
                     Graph::check_reduce_node(c, n, label);
                     std::printf("  reduce step %s \"%s\": device (int32 host values of ReduceL1 / ReduceSumSquare / ReduceProd stay on the host)\n", n.op_type.c_str(), n.name.c_str());
+                }
+            }
+        }
+        {
+            const onnx::Model c = Graph::canonical_form(m); // GridSample and DepthToSpace: the loader's attribute checks
+            for (auto &n : c.nodes) {
+                if (!(n.domain.empty() || n.domain == "ai.onnx")) continue;
+                const std::string label = n.name.empty() ? n.outputs.at(0) : n.name;
+                if (n.op_type == "GridSample") {
+                    const Graph::GridSampleNode a = Graph::read_grid_sample_node(n, label);
+                    std::printf("  sample step GridSample \"%s\": bilinear, zero padding, align_corners %d\n", n.name.c_str(), a.align_corners ? 1 : 0);
+                } else if (n.op_type == "DepthToSpace") {
+                    const Graph::DepthToSpaceNode a = Graph::read_depth_to_space_node(n, label);
+                    std::printf("  layout step DepthToSpace \"%s\": mode %s, blocksize %" PRId64 " (one transpose launch)\n", n.name.c_str(),
+                                a.mode == DepthToSpaceMode::DepthColumnRow ? "DCR" : "CRD", a.block_size);
                 }
             }
         }

@@ -26,6 +26,8 @@ Test and tooling infrastructure only: nothing under rten_amd/ imports this.
     python tools/torch_export.py box_decode /tmp/box_decode.onnx       # conv head + anchor decode: Exp, Min / Max against the image bounds, Sqrt, Reciprocal, Neg, Abs
     python tools/torch_export.py embedding_head /tmp/embed.onnx         # small encoder + masked mean pooling + F.normalize (ReduceL2), dynamic batch / sequence
     python tools/torch_export.py reduce_zoo /tmp/reduce_zoo.onnx        # ReduceL1 / ReduceLogSumExp / two-axis ReduceL2 / ReduceProd as the exporter writes them
+    python tools/torch_export.py warp /tmp/warp.onnx                    # Conv features warped by F.grid_sample along a predicted flow (GridSample), dynamic batch
+    python tools/torch_export.py pixel_shuffle_sr /tmp/sr.onnx          # Conv / ReLU / Conv / nn.PixelShuffle (Reshape / 6-D Transpose / Reshape)
     python tools/torch_export.py dynamic_upsample /tmp/dyn_up.onnx     # F.interpolate(scale_factor=2) with dynamic H / W as Shape -> .. -> Floor -> .. -> Resize(sizes), written with onnx_writer
 """
 from __future__ import annotations
@@ -42,6 +44,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def export_bytes(model, args, input_names, output_names, dynamic_axes=None, opset: int = 17) -> bytes:
     import torch
     import torch.onnx._internal.torchscript_exporter.utils as TU
+    import torch.onnx._internal.torchscript_exporter.symbolic_opset16  # noqa: F401  (registers grid_sampler -> GridSample; without it F.grid_sample is UnsupportedOperatorError)
     from torch.onnx._internal.torchscript_exporter._globals import GLOBALS
     warnings.filterwarnings("ignore")
     GLOBALS.export_onnx_opset_version = opset
@@ -756,6 +759,51 @@ def dynamic_upsample_onnx(weights=None, scale: float = 2.0) -> bytes:
     return ow.model(nodes, [ow.value_info("x", 1, ["batch", 3, "height", "width"])], [ow.value_info("y", 1, ["batch", 3, "height2", "width2"])], inits)
 
 
+def warp_module(seed: int = 0, channels: int = 4, align_corners: bool = False):
+    """Flow warping as video and stereo networks write it: a 3x3 convolution makes features, another predicts a two-channel flow from them, and
+    F.grid_sample(bilinear, zeros) reads the features at the identity grid (an input, one per batch row: it has the image's size) plus the flow.  The exporter
+    writes Conv / Conv / Tanh / Mul / Transpose / Add / GridSample(mode="bilinear", padding_mode="zeros", align_corners)."""
+    import torch
+    from torch import nn
+    import torch.nn.functional as Fn
+    torch.manual_seed(seed)
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.feat = nn.Conv2d(3, channels, 3, 1, 1)
+            self.flow = nn.Conv2d(channels, 2, 3, 1, 1)
+
+        def forward(self, x, grid):
+            f = self.feat(x)
+            flow = torch.tanh(self.flow(f)) * 0.5                  # [N, 2, H, W], offsets of up to half the image either way (some samples fall outside)
+            return Fn.grid_sample(f, grid + flow.permute(0, 2, 3, 1), mode="bilinear", padding_mode="zeros", align_corners=align_corners)
+
+    return Net().eval()
+
+
+def warp_onnx(model=None, batch: int = 2, height: int = 6, width: int = 8, dynamic: bool = True, align_corners: bool = False) -> bytes:
+    """Inputs x [batch, 3, H, W] and grid [batch, H, W, 2] (rten_amd.onnx_writer.base_grid for every row), output warped [batch, channels, H, W]."""
+    import torch
+    model = model if model is not None else warp_module(align_corners=align_corners)
+    axes = {"x": {0: "batch"}, "grid": {0: "batch"}, "warped": {0: "batch"}} if dynamic else None
+    return export_bytes(model, (torch.zeros(batch, 3, height, width), torch.zeros(batch, height, width, 2)), ["x", "grid"], ["warped"], axes)
+
+
+def pixel_shuffle_sr_onnx(weights, block: int = 2, batch: int = 2, height: int = 5, width: int = 7) -> bytes:
+    """rten_amd.onnx_writer.subpixel_sr_graph's network (same weights dict) with nn.PixelShuffle for the DepthToSpace: the exporter writes it as
+    Reshape / 6-D Transpose / Reshape, the same permutation as DepthToSpace(mode="CRD").  Static shapes (the Reshape targets are constants)."""
+    import torch
+    from torch import nn
+
+    def conv(w, b):
+        c = nn.Conv2d(w.shape[1], w.shape[0], 3, 1, 1)
+        c.weight.data, c.bias.data = torch.from_numpy(w.copy()), torch.from_numpy(b.copy())
+        return c
+    net = nn.Sequential(conv(*weights["c1"]), nn.ReLU(), conv(*weights["c2"]), nn.PixelShuffle(block)).eval()
+    return export_bytes(net, (torch.zeros(batch, 3, height, width),), ["x"], ["y"])
+
+
 if __name__ == "__main__":
     kind, path = sys.argv[1], sys.argv[2]
     if kind == "resnet50":
@@ -795,6 +843,11 @@ if __name__ == "__main__":
         data = embedding_head_onnx(dynamic=True)
     elif kind == "reduce_zoo":
         data = reduce_zoo_onnx()
+    elif kind == "warp":
+        data = warp_onnx()
+    elif kind == "pixel_shuffle_sr":
+        from rten_amd import onnx_writer as ow
+        data = pixel_shuffle_sr_onnx(ow.subpixel_sr_graph("CRD")[1])
     else:
         data = bert_onnx(bert_module())
     open(path, "wb").write(data)
