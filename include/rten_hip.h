@@ -599,6 +599,24 @@ int32_t rten_hip_resize_f32(rten_hip_ctx *ctx, int32_t mode, int32_t coord_mode,
 int32_t rten_hip_grid_sample_f32(rten_hip_ctx *ctx, int32_t align_corners, int64_t batch, int64_t channels, int64_t in_h, int64_t in_w, int64_t out_h,
                                  int64_t out_w, const float *x /* [batch, channels, in_h, in_w] */,
                                  const float *grid /* [batch, out_h, out_w, 2], (x, y) in [-1, 1] */, float *y /* [batch, channels, out_h, out_w] */);
+/* CumSum (cum_sum, src/ops/reduce.rs:217-257) of float32 / int32 (dtype: RTEN_HIP_DTYPE_F32 or _I32) on the [outer][axis_len][inner] view.  Per lane
+ * along the axis: acc = 0; for x in order (from the end if reverse): prev = acc; acc = acc + x; y = exclusive ? prev : acc.  The f32 sum is strictly
+ * sequential, each partial sum one rounded add, the first +0.0 + x0 (a leading -0.0 gives +0.0); int32 wraps.  inner == 1 runs the row form (rows tiled
+ * through LDS), inner > 1 the column form (a thread per lane): rten_amd/csrc/scan.hip.  An empty tensor launches nothing.  Capture-safe. */
+int32_t rten_hip_cumsum_b32(rten_hip_ctx *ctx, int32_t dtype, int32_t exclusive, int32_t reverse, int64_t outer, int64_t axis_len, int64_t inner, const void *x, void *y);
+/* GatherElements (gather_elements, src/ops/gather.rs:196-284) of 4-byte elements, ndim in 1..6, axis already resolved: y has idx_shape and
+ * y[i0, .., i_axis, ..] = x[i0, .., ids[i0, ..], ..]; every non-axis extent of idx_shape must be <= x_shape's ("`indices` size must be <= input size in
+ * non-axis dimensions").  Negative indices add the axis length once.  Out-of-range indices are CLAMPED to the axis, exactly as rten_hip_gather_axis_b32
+ * does (the reference reports "Entry in `indices` is out of range"; nothing is read back here): the index is normalised and clamped before the address
+ * is formed, so nothing outside x is read whatever the index.  An empty axis with a non-empty output is that error.  An empty output launches nothing. */
+int32_t rten_hip_gather_elements_b32(rten_hip_ctx *ctx, int32_t ndim, const int64_t *x_shape, const int64_t *idx_shape, int32_t axis, const void *x,
+                                     const int32_t *ids, void *y);
+/* Trilu (src/ops/trilu.rs:15-64) of 4-byte elements viewed as [batch][rows][cols]: delta = row + k - col in 64 bits; the element is kept when
+ * delta <= 0 (upper) / delta >= 0 (lower), else the all-zero word is written (+0.0 / 0): a masked element's value never reaches the output. */
+int32_t rten_hip_trilu_b32(rten_hip_ctx *ctx, int32_t upper, int64_t k, int64_t batch, int64_t rows, int64_t cols, const void *x, void *y);
+/* Tile (src/ops/concat.rs:239-272) of 4-byte elements, ndim <= 6: y.shape[d] = x_shape[d] * repeats[d], y[i] = x[i mod x_shape] per axis.  A negative
+ * repeat is "invalid repeats"; a zero repeat (an empty output) launches nothing. */
+int32_t rten_hip_tile_b32(rten_hip_ctx *ctx, int32_t ndim, const int64_t *x_shape, const int64_t *repeats, const void *x, void *y);
 /* 1 while a graph capture is active on `ctx` (rten_hip_graph_begin .. _end): host code must not upload from host memory then -- the copy would be
  * recorded with the host pointer and re-read at every replay. */
 int32_t rten_hip_capture_active(rten_hip_ctx *ctx);

@@ -491,6 +491,83 @@ inline HostVal gather(const HostVal &x, const HostVal &ids, int axis) { // src/o
         }
     return out;
 }
+// ---- CumSum / GatherElements / Trilu / Tile on host values: the arithmetic of the kernels in rten_amd/csrc/scan.hip (the f32 sum strictly sequential and
+// starting as +0.0 + x0, int32 wrapping; the all-zero word where Trilu masks)
+inline HostVal cumsum(const HostVal &x, int64_t axis, bool exclusive, bool reverse) { // reduce.rs:217-257
+    if (axis < INT32_MIN || axis > INT32_MAX) throw OpError(OpError::InvalidValue, "Axis is invalid");
+    const int ax = resolve_axis((int)axis, (int)x.shape.size());
+    const int64_t outer = detail::prod(x.shape, 0, (size_t)ax), alen = x.shape[(size_t)ax], inner = detail::prod(x.shape, (size_t)ax + 1, x.shape.size());
+    HostVal out;
+    out.is_float = x.is_float;
+    out.shape = x.shape;
+    if (out.is_float) out.f.resize((size_t)out.len()); else out.i.resize((size_t)out.len());
+    for (int64_t o = 0; o < outer; o++)
+        for (int64_t k = 0; k < inner; k++) {
+            volatile float facc = 0.f; // (volatile: every partial sum is stored as a float32, whatever the host compiler's excess precision)
+            int64_t iacc = 0;
+            for (int64_t t = 0; t < alen; t++) {
+                const size_t at = (size_t)((o * alen + (reverse ? alen - 1 - t : t)) * inner + k);
+                if (out.is_float) { const float prev = facc; facc = prev + x.f[at]; out.f[at] = exclusive ? prev : (float)facc; }
+                else { const int64_t prev = iacc; iacc = wrap32(iacc + x.i[at]); out.i[at] = exclusive ? prev : iacc; }
+            }
+        }
+    return out;
+}
+inline HostVal gather_elements(const HostVal &x, const HostVal &ids, int axis) { // gather.rs:196-284
+    const int ax = check_gather_elements(x.shape, ids.shape, axis);
+    const int nd = (int)x.shape.size();
+    std::vector<int64_t> xs((size_t)nd, 1);
+    for (int d = nd - 2; d >= 0; d--) xs[(size_t)d] = xs[(size_t)d + 1] * x.shape[(size_t)d + 1];
+    HostVal out;
+    out.is_float = x.is_float;
+    out.shape = ids.shape;
+    const int64_t n = out.len(), alen = x.shape[(size_t)ax];
+    if (out.is_float) out.f.resize((size_t)n); else out.i.resize((size_t)n);
+    std::vector<int64_t> idx((size_t)nd, 0);
+    for (int64_t i = 0; i < n; i++) {
+        int64_t id = ids.i[(size_t)i];
+        if (id < 0) id += alen;
+        if (id < 0 || id >= alen) throw OpError(OpError::InvalidValue, "Entry in `indices` is out of range");
+        int64_t off = 0;
+        for (int d = 0; d < nd; d++) off += (d == ax ? id : idx[(size_t)d]) * xs[(size_t)d];
+        if (out.is_float) out.f[(size_t)i] = x.f[(size_t)off]; else out.i[(size_t)i] = x.i[(size_t)off];
+        for (int d = nd - 1; d >= 0; d--) { if (++idx[(size_t)d] < out.shape[(size_t)d]) break; idx[(size_t)d] = 0; }
+    }
+    return out;
+}
+inline HostVal trilu(const HostVal &x, int64_t k, bool upper) { // trilu.rs:15-64, delta in 64 bits
+    const size_t nd = x.shape.size();
+    if (nd < 2) throw OpError(OpError::InvalidValue, "Input must have >= 2 dims");
+    const int64_t rows = x.shape[nd - 2], cols = x.shape[nd - 1], n = x.len();
+    const int64_t kc = std::max<int64_t>(-((int64_t)1 << 32), std::min<int64_t>((int64_t)1 << 32, k));
+    HostVal out = x;
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t col = i % cols, row = (i / cols) % rows, delta = row + kc - col;
+        if (upper ? delta <= 0 : delta >= 0) continue;
+        if (out.is_float) out.f[(size_t)i] = 0.f; else out.i[(size_t)i] = 0;
+    }
+    return out;
+}
+inline bool tile(const HostVal &x, const std::vector<int64_t> &repeats, HostVal &out) { // concat.rs:239-272; false: too large to mirror on the host
+    out.is_float = x.is_float;
+    out.shape = tiled_shape(x.shape, repeats);
+    double total = 1;
+    for (int64_t d : out.shape) total *= (double)d;
+    if (total > (double)kMaxHostElems) return false;
+    const size_t nd = x.shape.size();
+    const int64_t n = out.len();
+    std::vector<int64_t> xs(nd, 1);
+    for (size_t d = nd; d-- > 1;) xs[d - 1] = xs[d] * x.shape[d];
+    if (out.is_float) out.f.resize((size_t)n); else out.i.resize((size_t)n);
+    std::vector<int64_t> idx(nd, 0);
+    for (int64_t i = 0; i < n; i++) {
+        int64_t off = 0;
+        for (size_t d = 0; d < nd; d++) off += (idx[d] % x.shape[d]) * xs[d];
+        if (out.is_float) out.f[(size_t)i] = x.f[(size_t)off]; else out.i[(size_t)i] = x.i[(size_t)off];
+        for (size_t d = nd; d-- > 0;) { if (++idx[d] < out.shape[d]) break; idx[d] = 0; }
+    }
+    return true;
+}
 inline HostVal concat(const std::vector<const HostVal *> &v, int axis) { // src/ops/concat.rs
     const int nd = (int)v[0]->shape.size();
     const int ax = resolve_axis(axis, nd);
@@ -1198,6 +1275,51 @@ class Graph {
         a.block_size = bs->i;
         return a;
     }
+    // What the loader reads from, and refuses about, a CumSum / GatherElements / Trilu / Tile node (make_index_step; onnx_registry.rs:1056-1060 and the
+    // operators' max_inputs).  The axis of CumSum, k of Trilu and the repeats of Tile are host values at run time -- constants or shape arithmetic -- so one
+    // that is a graph input (device data) is refused here, by node name; any other device-computed one is refused by the step when it runs.  Needs no
+    // device; rten_hip_run --parse-only calls them too.
+    static void refuse_device_operand(const onnx::Model &m, const onnx::Node &n, size_t i, const std::string &where, const char *what) {
+        if (n.inputs.size() > i && !n.inputs[i].empty() && graph_input_named(m, n.inputs[i]))
+            throw GraphError(where + what + " must be a constant or computable from the input shapes (it is the graph input \"" + n.inputs[i] + "\", device data at run time)");
+    }
+    static void refuse_extra_inputs(const onnx::Node &n, size_t max, const std::string &where) {
+        if (n.inputs.size() > max) throw GraphError(where + "takes at most " + std::to_string(max) + " inputs (it has " + std::to_string(n.inputs.size()) + ")");
+    }
+    struct CumSumNode { bool exclusive = false, reverse = false; };
+    static CumSumNode read_cumsum_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        const std::string where = "CumSum " + label + ": ";
+        CumSumNode a;
+        a.exclusive = n.get_int("exclusive", 0) != 0;
+        a.reverse = n.get_int("reverse", 0) != 0;
+        refuse_extra_inputs(n, 2, where);
+        if (n.inputs.size() < 2 || n.inputs[1].empty()) throw GraphError(where + "the axis input is missing");
+        refuse_device_operand(m, n, 1, where, "axis");
+        return a;
+    }
+    struct GatherElementsNode { int axis = 0; };
+    static GatherElementsNode read_gather_elements_node(const onnx::Node &n, const std::string &label) {
+        GatherElementsNode a;
+        a.axis = (int)n.get_int("axis", 0);
+        refuse_extra_inputs(n, 2, "GatherElements " + label + ": ");
+        return a;
+    }
+    struct TriluNode { bool upper = true; };
+    static TriluNode read_trilu_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        const std::string where = "Trilu " + label + ": ";
+        TriluNode a;
+        a.upper = n.get_int("upper", 1) != 0;
+        refuse_extra_inputs(n, 2, where);
+        refuse_device_operand(m, n, 1, where, "k");
+        return a;
+    }
+    static void read_tile_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        const std::string where = "Tile " + label + ": ";
+        refuse_extra_inputs(n, 2, where);
+        if (n.inputs.size() < 2 || n.inputs[1].empty()) throw GraphError(where + "the repeats input is missing");
+        refuse_device_operand(m, n, 1, where, "repeats");
+    }
+    static bool is_index_kind(const std::string &k) { return k == "CumSum" || k == "GatherElements" || k == "Trilu" || k == "Tile"; }
     static bool is_math_kind(const std::string &k) {
         static const std::set<std::string> kinds = {"Neg", "Abs", "Sign", "Floor", "Ceil", "Round", "Sqrt", "Reciprocal", "Exp", "Log", "Softplus", "Pow", "PRelu", "Min", "Max", "Sum", "Mean"};
         return kinds.count(k) != 0;
@@ -2572,6 +2694,7 @@ class Graph {
             else if (kind == "InstanceNormalization" || kind == "BatchNormalization" || kind == "LogSoftmax") make_norm_step(st, n, nodes, out_name);
             else if (is_math_kind(kind)) make_math_step(st, n, m);
             else if (kind == "Pad") make_pad_step(st, n, m);
+            else if (is_index_kind(kind)) make_index_step(st, n, m);
             else if (kind == "QuantizeLinear" || kind == "DequantizeLinear") make_qdq_step(st, n, m, nodes, out_name);
             else if (kind == "Flatten" || kind == "Reshape" || kind == "Squeeze" || kind == "Unsqueeze" || kind == "Identity" || kind == "Dropout") make_view_step(st, n);
             else if (make_layout_step(st, n)) {
@@ -2975,6 +3098,94 @@ class Graph {
             o.push_back(pad_tensor(c, x, pads, a.mode, fill_bits));
             return o;
         };
+    }
+
+    // CumSum / GatherElements / Trilu / Tile: the read_*_node checks at load.  CumSum's axis, Trilu's k and Tile's repeats are host values at run time (constants
+    // or shape arithmetic), read as Slice reads its starts: nothing is read back, each step is one launch of rten_amd/csrc/scan.hip and capture-safe.  When the
+    // data operand (and GatherElements' indices) are host values too, the step is evaluated on the host (hostops::cumsum / gather_elements / trilu / tile): an
+    // exporter's triu(full((S, S))) mask or the repeat of a shape vector costs no launch.  A host-valued data operand with device indices (RoBERTa's buffered
+    // token_type_ids) runs on the data's cached device copy.  On the device path the rows of dim 0 are coupled (sub-batch chains split dim 0) when CumSum or
+    // GatherElements resolve to axis 0, when repeats[0] != 1, and when Trilu runs on a rank-2 operand (dim 0 is its row index); a host-evaluated value is
+    // not split.
+    void make_index_step(Step &st, const onnx::Node &n, const onnx::Model &m) {
+        const std::string kind = n.op_type, nm = st.name;
+        auto couple = [this, kind, nm](const char *why) { if (runtime_coupled_.empty()) runtime_coupled_ = kind + " \"" + nm + "\" (" + why + ")"; };
+        auto one_int = [kind](const Tensor &t, const char *what) {
+            const std::vector<int64_t> v = host_ints(&t, kind + ": " + what);
+            if (v.size() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 0 dims");
+            return v[0];
+        };
+        if (kind == "CumSum") {
+            const CumSumNode a = read_cumsum_node(m, n, nm);
+            if (const onnx::TensorProto *t = initializer_named(m, n.inputs[1])) { // a constant axis 0 is known at load; a negative one resolves at run time
+                int64_t v = -1;
+                if (t->data_type == onnx::INT64 && t->raw.size() == 8) std::memcpy(&v, t->raw.data(), 8);
+                else if (t->data_type == onnx::INT32 && t->raw.size() == 4) { int32_t w; std::memcpy(&w, t->raw.data(), 4); v = w; }
+                st.batch_coupled = v == 0;
+            }
+            make_hostable(st,
+                          [a](const std::vector<const HostVal *> &v, HostVal &out) {
+                              if (v.size() != 2 || !v[0] || !v[1] || v[1]->is_float || v[1]->i.size() != 1) return false;
+                              out = hostops::cumsum(*v[0], v[1]->i[0], a.exclusive, a.reverse);
+                              return true;
+                          },
+                          [a, couple, one_int](Context &c, const InputList &in) {
+                              const Tensor &x = require(in, 0);
+                              const int64_t axis = one_int(require(in, 1), "axis");
+                              if (x.ndim() > 0 && (axis == 0 || axis + x.ndim() == 0)) couple("sums along dim 0");
+                              OutputList o;
+                              o.push_back(cumsum_tensor(c, x, axis, a.exclusive, a.reverse));
+                              return o;
+                          });
+        } else if (kind == "GatherElements") {
+            const int axis = read_gather_elements_node(n, nm).axis;
+            st.batch_coupled = axis == 0;
+            make_hostable(st,
+                          [axis](const std::vector<const HostVal *> &v, HostVal &out) {
+                              if (v.size() != 2 || !v[0] || !v[1] || v[1]->is_float) return false;
+                              out = hostops::gather_elements(*v[0], *v[1], axis);
+                              return true;
+                          },
+                          [this, axis, nm](Context &c, const InputList &in) {
+                              note_axis("GatherElements", nm, axis, require(in, 0));
+                              OutputList o;
+                              o.push_back(gather_elements_tensor(c, require(in, 0), require(in, 1), axis));
+                              return o;
+                          });
+        } else if (kind == "Trilu") {
+            const bool upper = read_trilu_node(m, n, nm).upper;
+            make_hostable(st,
+                          [upper](const std::vector<const HostVal *> &v, HostVal &out) {
+                              if (v.empty() || v.size() > 2 || !v[0]) return false;
+                              if (v.size() == 2 && v[1] && (v[1]->is_float || v[1]->i.size() != 1)) return false;
+                              out = hostops::trilu(*v[0], v.size() == 2 && v[1] ? v[1]->i[0] : 0, upper);
+                              return true;
+                          },
+                          [upper, couple, one_int](Context &c, const InputList &in) {
+                              const Tensor &x = require(in, 0);
+                              const int64_t k = get(in, 1) ? one_int(*get(in, 1), "k") : 0;
+                              if (x.ndim() == 2) couple("dim 0 is the matrix row");
+                              OutputList o;
+                              o.push_back(trilu_tensor(c, x, k, upper));
+                              return o;
+                          });
+        } else {
+            read_tile_node(m, n, nm);
+            make_hostable(st,
+                          [](const std::vector<const HostVal *> &v, HostVal &out) {
+                              if (v.size() != 2 || !v[0] || !v[1] || v[1]->is_float || v[1]->shape.size() != 1) return false;
+                              return hostops::tile(*v[0], v[1]->i, out);
+                          },
+                          [couple](Context &c, const InputList &in) {
+                              const Tensor &x = require(in, 0), &r = require(in, 1);
+                              const std::vector<int64_t> repeats = host_ints(&r, "Tile: repeats");
+                              if (r.ndim() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 1 dims");
+                              if (!repeats.empty() && repeats[0] != 1) couple("repeats dim 0");
+                              OutputList o;
+                              o.push_back(tile_tensor(c, x, repeats));
+                              return o;
+                          });
+        }
     }
 
     // QuantizeLinear / DequantizeLinear: read_qdq_node's checks at load.  With fusion on, a QuantizeLinear whose value only feeds a DequantizeLinear with the same

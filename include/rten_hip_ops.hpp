@@ -2265,6 +2265,132 @@ struct DepthToSpace : Operator {
     }
 };
 
+// ---- CumSum, GatherElements, Trilu, Tile (rten_amd/csrc/scan.hip): float32 / int32 data (booleans are int32), rank <= 6, one launch each, nothing read back
+inline void want_b32_numeric(const Tensor &x) {
+    if (x.dtype() != DType::F32 && x.dtype() != DType::I32) throw OpError(OpError::UnsupportedType, "");
+}
+// a one-element int32 operand (the reference's `require_as::<i32>`: any rank, one element): from its host value, else read back
+inline int64_t scalar_i32(const Tensor &t) {
+    want(t, DType::I32, "int32");
+    if (t.len() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 0 dims");
+    if (t.host()) return t.host()->i.at(0);
+    return t.to_host<int32_t>().at(0);
+}
+// cum_sum (reduce.rs:217-257): a rank-0 operand is resolve_axis's "Axis is invalid"; an empty tensor launches nothing
+inline Tensor cumsum_tensor(Context &ctx, const Tensor &x, int64_t axis, bool exclusive, bool reverse) {
+    want_b32_numeric(x);
+    if (axis < INT32_MIN || axis > INT32_MAX) throw OpError(OpError::InvalidValue, "Axis is invalid");
+    const int ax = resolve_axis((int)axis, x.ndim());
+    const int64_t outer = detail::prod(x.shape(), 0, (size_t)ax), inner = detail::prod(x.shape(), (size_t)ax + 1, x.shape().size());
+    Tensor y(ctx, x.shape(), x.dtype());
+    if (y.len())
+        ctx.check(rten_hip_cumsum_b32(ctx.raw(), x.dtype() == DType::F32 ? RTEN_HIP_DTYPE_F32 : RTEN_HIP_DTYPE_I32, exclusive ? 1 : 0, reverse ? 1 : 0, outer, x.size(ax), inner,
+                                      x.ptr(), y.ptr()));
+    return y;
+}
+// gather_elements' shape checks (gather.rs:202-217), shared by the host and the device path: -> the resolved axis
+inline int check_gather_elements(const std::vector<int64_t> &x_shape, const std::vector<int64_t> &idx_shape, int axis) {
+    if (x_shape.size() != idx_shape.size()) throw OpError(OpError::IncompatibleInputShapes, "Input and indices must have same rank");
+    const int ax = resolve_axis(axis, (int)x_shape.size());
+    for (size_t d = 0; d < x_shape.size(); d++)
+        if ((int)d != ax && idx_shape[d] > x_shape[d]) throw OpError(OpError::IncompatibleInputShapes, "`indices` size must be <= input size in non-axis dimensions");
+    return ax;
+}
+// Out-of-range indices: host-valued indices are checked here with the reference's message; device indices are clamped by the kernel (the deviation
+// rten_hip_gather_axis_b32 documents for Gather: nothing is read back).
+inline Tensor gather_elements_tensor(Context &ctx, const Tensor &x, const Tensor &ids, int axis) {
+    want(ids, DType::I32, "int32");
+    if (dtype_size(x.dtype()) != 4) throw OpError(OpError::UnsupportedType, "");
+    const int ax = check_gather_elements(x.shape(), ids.shape(), axis);
+    if (x.ndim() > 6) throw OpError(OpError::UnsupportedValue, "GatherElements supports at most 6 dims");
+    const int64_t alen = x.size(ax);
+    if (ids.len() && alen == 0) throw OpError(OpError::InvalidValue, "Entry in `indices` is out of range");
+    if (const HostVal *h = ids.host())
+        for (int64_t id : h->i) if (id < -alen || id >= alen) throw OpError(OpError::InvalidValue, "Entry in `indices` is out of range");
+    Tensor y(ctx, ids.shape(), x.dtype());
+    if (y.len()) ctx.check(rten_hip_gather_elements_b32(ctx.raw(), x.ndim(), x.shape().data(), ids.shape().data(), ax, x.ptr(), (const int32_t *)ids.ptr(), y.ptr()));
+    return y;
+}
+inline Tensor trilu_tensor(Context &ctx, const Tensor &x, int64_t k, bool upper) {
+    want_b32_numeric(x);
+    if (x.ndim() < 2) throw OpError(OpError::InvalidValue, "Input must have >= 2 dims");
+    const int nd = x.ndim();
+    Tensor y(ctx, x.shape(), x.dtype());
+    if (y.len()) ctx.check(rten_hip_trilu_b32(ctx.raw(), upper ? 1 : 0, k, detail::prod(x.shape(), 0, (size_t)nd - 2), x.size(nd - 2), x.size(nd - 1), x.ptr(), y.ptr()));
+    return y;
+}
+// tile's check (concat.rs:244-246) and output shape
+inline std::vector<int64_t> tiled_shape(const std::vector<int64_t> &shape, const std::vector<int64_t> &repeats) {
+    if (repeats.size() != shape.size()) throw OpError(OpError::InvalidValue, "invalid repeats");
+    for (int64_t r : repeats) if (r < 0) throw OpError(OpError::InvalidValue, "invalid repeats");
+    std::vector<int64_t> out(shape);
+    for (size_t d = 0; d < out.size(); d++) out[d] *= repeats[d];
+    return out;
+}
+inline Tensor tile_tensor(Context &ctx, const Tensor &x, const std::vector<int64_t> &repeats) {
+    want_b32_numeric(x);
+    const std::vector<int64_t> oshape = tiled_shape(x.shape(), repeats);
+    if (x.ndim() > 6) throw OpError(OpError::UnsupportedValue, "Tile supports at most 6 dims");
+    Tensor y(ctx, oshape, x.dtype());
+    if (y.len()) ctx.check(rten_hip_tile_b32(ctx.raw(), x.ndim(), x.shape().data(), repeats.data(), x.ptr(), y.ptr()));
+    return y;
+}
+
+// CumSum (src/ops/reduce.rs:259-297): inputs (data, axis); the axis is a one-element int32 operand, read from its host value when it carries one (a
+// constant, shape arithmetic) and read back otherwise (the graph executor refuses that case before it gets here: a read-back cannot be captured).
+struct CumSum : Operator {
+    bool exclusive = false, reverse = false;
+    const char *name() const override { return "CumSum"; }
+    int max_inputs() const override { return 2; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0);
+        const int64_t axis = scalar_i32(require(in, 1));
+        OutputList out;
+        out.push_back(cumsum_tensor(ctx, x, axis, exclusive, reverse));
+        return out;
+    }
+};
+// GatherElements (src/ops/gather.rs:196-319): y[i0, ..] = x[i0, .., indices[i0, ..], ..] along `axis`, on the input trimmed to the indices' extent
+struct GatherElements : Operator {
+    int axis = 0;
+    const char *name() const override { return "GatherElements"; }
+    int max_inputs() const override { return 2; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0), &ids = require(in, 1);
+        OutputList out;
+        out.push_back(gather_elements_tensor(ctx, x, ids, axis));
+        return out;
+    }
+};
+// Trilu (src/ops/trilu.rs:66-97): inputs (data, k); k is optional, default 0, read like CumSum's axis
+struct Trilu : Operator {
+    bool upper = true;
+    const char *name() const override { return "Trilu"; }
+    int max_inputs() const override { return 2; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0);
+        const int64_t k = get(in, 1) ? scalar_i32(*get(in, 1)) : 0;
+        OutputList out;
+        out.push_back(trilu_tensor(ctx, x, k, upper));
+        return out;
+    }
+};
+// Tile (src/ops/concat.rs:274-295): inputs (data, repeats); repeats is a 1-D int32 operand read like Pad's pads
+struct Tile : Operator {
+    const char *name() const override { return "Tile"; }
+    int max_inputs() const override { return 2; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0), &r = want(require(in, 1), DType::I32, "int32");
+        if (r.ndim() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 1 dims");
+        std::vector<int64_t> repeats;
+        if (r.host()) repeats = r.host()->i;
+        else for (int32_t v : r.to_host<int32_t>()) repeats.push_back(v);
+        OutputList out;
+        out.push_back(tile_tensor(ctx, x, repeats));
+        return out;
+    }
+};
+
 // Split (src/ops/split.rs:34-136) of 4-byte tensors, one strided copy per piece: the sizes of input 1 (the opset < 13 `split` attribute arrives
 // there too), else `num_outputs` (opset 18), else the node's output count, as equal chunks of ceil(dim / n) -- the last piece is smaller, and there
 // may be fewer than n pieces (5 split 4 ways gives 3).
@@ -3212,6 +3338,10 @@ class OpRegistry {
         r.register_op<GlobalMaxPool>("GlobalMaxPool");
         r.register_op<GridSample>("GridSample");
         r.register_op<DepthToSpace>("DepthToSpace");
+        r.register_op<CumSum>("CumSum");
+        r.register_op<GatherElements>("GatherElements");
+        r.register_op<Trilu>("Trilu");
+        r.register_op<Tile>("Tile");
         return r;
     }
 

@@ -205,6 +205,10 @@ PROTOTYPES = {
     "rten_hip_resize_f32": (_I32, [_VP, _I32, _I32, _I32, _I64, _I64, _I64, _I64, _I64, C.c_float, C.c_float, _VP, _VP]),
     "rten_hip_capture_active": (_I32, [_VP]),
     "rten_hip_grid_sample_f32": (_I32, [_VP, _I32, _I64, _I64, _I64, _I64, _I64, _I64, _VP, _VP, _VP]),
+    "rten_hip_cumsum_b32": (_I32, [_VP, _I32, _I32, _I32, _I64, _I64, _I64, _VP, _VP]),
+    "rten_hip_gather_elements_b32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "rten_hip_trilu_b32": (_I32, [_VP, _I32, _I64, _I64, _I64, _I64, _VP, _VP]),
+    "rten_hip_tile_b32": (_I32, [_VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_reduce_sum_strided_f32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_reduce_mean_strided_f32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_reduce_minmax_strided": (_I32, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),

@@ -636,3 +636,48 @@ def subpixel_sr_graph(mode: str = "DCR", block: int = 2, seed: int = 23, feature
              node("Conv", ["a.r", "c2.w", "c2.b"], ["b"], name="c2", kernel_shape=[3, 3], pads=[1, 1, 1, 1]),
              node("DepthToSpace", ["b"], ["y"], name="shuffle", blocksize=block, mode=mode)]
     return model(nodes, [value_info("x", FLOAT, [batch, 3, "h", "w"])], [value_info("y", FLOAT, [batch, 3, "H", "W"])], inits, opset=13, name="subpixel_sr"), w
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# CumSum / GatherElements / Trilu / Tile on device data with every attribute (PyTorch's exporter only writes the default forms)
+# ----------------------------------------------------------------------------------------------------------------
+INDEX_OPS_OUTPUTS = ["cum_excl_rev", "cum_mid_rev", "cum_int_excl", "cum_rows", "gather_mid", "gather_last", "tril_km1", "triu_k1", "tiled"]
+INDEX_OPS_BAD = ("cumsum_no_axis", "cumsum_axis_input", "trilu_k_input", "tile_repeats_input", "trilu_extra_input", "tile_extra_input")
+
+
+def index_ops_graph(batch="batch", rows: int = 4, cols: int = 5, picks: int = 3, bad: str | None = None) -> bytes:
+    """x [batch, rows, cols] f32, m [batch, rows, cols] int32, idx [batch, picks, cols] int32 (entries in [-rows, rows)) ->
+         cum_excl_rev  CumSum(x, -1, exclusive=1, reverse=1)       cum_mid_rev   CumSum(x, 1, reverse=1)
+         cum_int_excl  CumSum(m, 2, exclusive=1)  (int32)          cum_rows      CumSum(x, 0)  (couples the batch rows)
+         gather_mid    GatherElements(x, idx, axis=1)              gather_last   GatherElements(x, idx, axis=-1)  (rows <= cols)
+         tril_km1      Trilu(x, k=-1, upper=0)                     triu_k1       Trilu(x, k=1)
+         tiled         Tile(x, [1, 2, 3])
+    `bad` (one of INDEX_OPS_BAD) gives a graph the loader refuses at the node it names: "cum_rows" without its axis operand or with the graph input
+    "axis_in" for it, "triu_k1" with the graph input "k_in" / a third input, "tiled" with the graph input "repeats_in" / a third input."""
+    assert bad is None or bad in INDEX_OPS_BAD, bad
+    shape = [batch, rows, cols]
+    i64 = lambda name, v: tensor(name, np.asarray(v, np.int64))
+    inits = [i64("axis_m1", -1), i64("axis_0", 0), i64("axis_1", 1), i64("axis_2", 2), i64("k_m1", -1), i64("k_1", 1), i64("repeats", [1, 2, 3])]
+    ins = [value_info("x", FLOAT, shape), value_info("m", INT32, shape), value_info("idx", INT32, [batch, picks, cols])]
+    cum_rows_in = {"cumsum_no_axis": ["x"], "cumsum_axis_input": ["x", "axis_in"]}.get(bad, ["x", "axis_0"])
+    triu_in = {"trilu_k_input": ["x", "k_in"], "trilu_extra_input": ["x", "k_1", "k_m1"]}.get(bad, ["x", "k_1"])
+    tile_in = {"tile_repeats_input": ["x", "repeats_in"], "tile_extra_input": ["x", "repeats", "repeats"]}.get(bad, ["x", "repeats"])
+    if bad == "cumsum_axis_input":
+        ins.append(value_info("axis_in", INT64, []))
+    if bad == "trilu_k_input":
+        ins.append(value_info("k_in", INT64, []))
+    if bad == "tile_repeats_input":
+        ins.append(value_info("repeats_in", INT64, [3]))
+    nodes = [node("CumSum", ["x", "axis_m1"], ["cum_excl_rev"], name="cum_excl_rev", exclusive=1, reverse=1),
+             node("CumSum", ["x", "axis_1"], ["cum_mid_rev"], name="cum_mid_rev", reverse=1),
+             node("CumSum", ["m", "axis_2"], ["cum_int_excl"], name="cum_int_excl", exclusive=1),
+             node("CumSum", cum_rows_in, ["cum_rows"], name="cum_rows"),
+             node("GatherElements", ["x", "idx"], ["gather_mid"], name="gather_mid", axis=1),
+             node("GatherElements", ["x", "idx"], ["gather_last"], name="gather_last", axis=-1),
+             node("Trilu", ["x", "k_m1"], ["tril_km1"], name="tril_km1", upper=0),
+             node("Trilu", triu_in, ["triu_k1"], name="triu_k1"),
+             node("Tile", tile_in, ["tiled"], name="tiled")]
+    outs = [value_info("cum_excl_rev", FLOAT, shape), value_info("cum_mid_rev", FLOAT, shape), value_info("cum_int_excl", INT32, shape), value_info("cum_rows", FLOAT, shape),
+            value_info("gather_mid", FLOAT, [batch, picks, cols]), value_info("gather_last", FLOAT, [batch, picks, cols]), value_info("tril_km1", FLOAT, shape),
+            value_info("triu_k1", FLOAT, shape), value_info("tiled", FLOAT, [batch, 2 * rows, 3 * cols])]
+    return model(nodes, ins, outs, inits, opset=14, name="index_ops")

@@ -2171,6 +2171,161 @@ class DepthToSpace(Operator):
         return [y]
 
 
+def _resolve_axis(nd, axis):
+    """resolve_axis (src/ops/mod.rs): a rank-0 operand has no valid axis."""
+    axis = int(axis)
+    if axis < -nd or axis >= nd:
+        raise InvalidValue("Axis is invalid")
+    return axis + nd if axis < 0 else axis
+
+
+def _scalar_i32(t):
+    """The reference's `require_as::<i32>`: an int32 operand of one element, of any rank (a numpy array / int as given, a DeviceTensor read back)."""
+    a = _host_values(t)
+    if a.dtype.kind not in "iu":
+        raise OpError("InputCastFailed", "expected int32 tensor")
+    if a.size != 1:
+        raise OpError("InputCastFailed", "expected tensor with 0 dims")
+    return int(a.reshape(()))
+
+
+def _b32_numeric(x):
+    if x.dtype not in (np.dtype(np.float32), np.dtype(np.int32)):
+        raise UnsupportedType
+    return x
+
+
+class CumSum(Operator):
+    """src/ops/reduce.rs:217-297 (rten_hip_cumsum_b32): inputs (data, axis); float32 / int32.  Per lane along the axis acc = 0; prev = acc; acc += x;
+    y = exclusive ? prev : acc, from the end if `reverse` -- the f32 sum strictly sequential, int32 wrapping.  The axis is a host-side operand.  A lane with
+    inner == 1 takes the kernel's row form, any other the column form (the entry point chooses)."""
+
+    def __init__(self, exclusive=False, reverse=False):
+        self.exclusive, self.reverse = exclusive, reverse
+
+    def max_inputs(self):
+        return 2
+
+    def run(self, ctx, inputs):
+        x = _b32_numeric(_require(inputs, 0))
+        axis = _scalar_i32(_require(inputs, 1))
+        ax = _resolve_axis(len(x.shape), axis)
+        outer = int(np.prod(x.shape[:ax], dtype=np.int64))
+        inner = int(np.prod(x.shape[ax + 1:], dtype=np.int64))
+        y = DeviceTensor(ctx, x.shape, x.dtype)
+        if y.size:
+            ctx.call("rten_hip_cumsum_b32", _DT[x.dtype], 1 if self.exclusive else 0, 1 if self.reverse else 0, outer, x.shape[ax], inner, x.vp, y.vp)
+        return [y]
+
+    def batch_coupled(self, x_shape, axis):
+        """Sub-batch chains split dim 0: the rows are coupled when the sum runs along it."""
+        return _resolve_axis(len(x_shape), axis) == 0
+
+
+class GatherElements(Operator):
+    """src/ops/gather.rs:196-319 (rten_hip_gather_elements_b32): y[i0, ..] = x[i0, .., indices[i0, ..], ..] along `axis` on the input trimmed to the
+    indices' extent; 4-byte data, int32 indices, at most 6 dims.  Negative indices add the axis length once.  Out-of-range indices: host-side
+    indices (a numpy array) are refused with the reference's message; device indices are CLAMPED by the kernel -- the same deliberate deviation as
+    Gather's rten_hip_gather_axis_b32, because nothing is read back."""
+
+    def __init__(self, axis=0):
+        self.axis = axis
+
+    def max_inputs(self):
+        return 2
+
+    def run(self, ctx, inputs):
+        x = _require(inputs, 0)
+        ids = _require(inputs, 1)
+        host_ids = None
+        if not isinstance(ids, DeviceTensor):
+            host_ids = np.asarray(ids)
+            if host_ids.dtype != np.dtype(np.int32):
+                raise OpError("InputCastFailed", "expected int32 tensor")
+        else:
+            _want(ids, np.int32)
+        if x.dtype.itemsize != 4:
+            raise UnsupportedType
+        ishape = tuple(host_ids.shape) if host_ids is not None else tuple(ids.shape)
+        if len(ishape) != len(x.shape):
+            raise IncompatibleInputShapes("Input and indices must have same rank")
+        ax = _resolve_axis(len(x.shape), self.axis)
+        if any(d != ax and ishape[d] > x.shape[d] for d in range(len(ishape))):
+            raise IncompatibleInputShapes("`indices` size must be <= input size in non-axis dimensions")
+        if len(x.shape) > 6:
+            raise UnsupportedValue("GatherElements supports at most 6 dims")
+        n = int(np.prod(ishape, dtype=np.int64))
+        alen = x.shape[ax]
+        if n and alen == 0:
+            raise InvalidValue("Entry in `indices` is out of range")
+        if host_ids is not None:
+            if n and (host_ids.min() < -alen or host_ids.max() >= alen):
+                raise InvalidValue("Entry in `indices` is out of range")
+            ids = DeviceTensor.from_numpy(ctx, host_ids)
+        y = DeviceTensor(ctx, ishape, x.dtype)
+        if y.size:
+            ctx.call("rten_hip_gather_elements_b32", len(x.shape), _i64(x.shape), _i64(ishape), ax, x.vp, ids.vp, y.vp)
+        return [y]
+
+    def batch_coupled(self, x_shape):
+        return _resolve_axis(len(x_shape), self.axis) == 0
+
+
+class Trilu(Operator):
+    """src/ops/trilu.rs:15-97 (rten_hip_trilu_b32): inputs (data, k); k optional (0), a host-side operand.  Per inner matrix delta = row + k - col, kept when
+    delta <= 0 (upper) / delta >= 0 (lower), else the all-zero word."""
+
+    def __init__(self, upper=True):
+        self.upper = upper
+
+    def max_inputs(self):
+        return 2
+
+    def run(self, ctx, inputs):
+        x = _b32_numeric(_require(inputs, 0))
+        k_t = _get(inputs, 1)
+        k = 0 if k_t is None else _scalar_i32(k_t)
+        if len(x.shape) < 2:
+            raise InvalidValue("Input must have >= 2 dims")
+        y = DeviceTensor(ctx, x.shape, x.dtype)
+        if y.size:
+            ctx.call("rten_hip_trilu_b32", 1 if self.upper else 0, k, int(np.prod(x.shape[:-2], dtype=np.int64)), x.shape[-2], x.shape[-1], x.vp, y.vp)
+        return [y]
+
+    def batch_coupled(self, x_shape):
+        """On a rank-2 operand dim 0 is the matrix row."""
+        return len(x_shape) == 2
+
+
+class Tile(Operator):
+    """src/ops/concat.rs:239-300 (rten_hip_tile_b32): inputs (data, repeats); y.shape[d] = x.shape[d] * repeats[d], y[i] = x[i mod x.shape].  `repeats` is a
+    host-side 1-D operand; a length other than the rank, or a negative entry, is "invalid repeats"."""
+
+    def max_inputs(self):
+        return 2
+
+    def run(self, ctx, inputs):
+        x = _b32_numeric(_require(inputs, 0))
+        r = _host_values(_require(inputs, 1))
+        if r.dtype.kind not in "iu":
+            raise OpError("InputCastFailed", "expected int32 tensor")
+        if r.ndim != 1:
+            raise OpError("InputCastFailed", "expected tensor with 1 dims")
+        repeats = [int(v) for v in r]
+        if len(repeats) != len(x.shape) or any(v < 0 for v in repeats):
+            raise InvalidValue("invalid repeats")
+        if len(x.shape) > 6:
+            raise UnsupportedValue("Tile supports at most 6 dims")
+        y = DeviceTensor(ctx, [s * v for s, v in zip(x.shape, repeats)], x.dtype)
+        if y.size:
+            ctx.call("rten_hip_tile_b32", len(x.shape), _i64(x.shape), _i64(repeats), x.vp, y.vp)
+        return [y]
+
+    @staticmethod
+    def batch_coupled(repeats):
+        return len(repeats) > 0 and int(repeats[0]) != 1
+
+
 class Split(Operator):
     """src/ops/split.rs:34-136 on 4-byte tensors (one rten_hip_copy_strided_b32 per piece): the sizes of input 1, else `num_outputs`, else the
     node's output count as equal chunks of ceil(dim / n) -- the last piece is smaller, and there may be fewer than n pieces (5 split 4 ways
@@ -2331,7 +2486,7 @@ class OpRegistry:
                    AveragePool, GlobalAveragePool, Flatten, DynamicQuantizeLinear, Attention, Gather, ReduceSum, ReduceMean, Einsum, Resize, Upsample,
                    Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK, GRU, LSTM, Neg, Abs, Sign, Floor, Ceil, Round, Sqrt, Reciprocal, Exp, Log, Softplus,
                    Pow, PRelu, Min, Max, Sum, Mean, Pad, QuantizeLinear, DequantizeLinear, ReduceL1, ReduceL2, ReduceSumSquare, ReduceLogSum, ReduceLogSumExp,
-                   ReduceProd, LpNormalization, GlobalMaxPool, GridSample, DepthToSpace):
+                   ReduceProd, LpNormalization, GlobalMaxPool, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile):
             r.register_op(op)
         return r
 

@@ -376,6 +376,50 @@ def main():
              (lambda: ctx.call("rten_hip_transpose_b32", 6, i64(8, 64, 2, 2, 128, 128), i32(0, 1, 4, 2, 5, 3), xd_.vp, yd_.vp)), 8.0 * nd2s),
             ("image: copy, DepthToSpace's size (reference point)", f"{4 * nd2s} B", (lambda: ctx.call("rten_hip_memcpy_d2d", yd_.vp, xd_.vp, C.c_size_t(4 * nd2s))), 8.0 * nd2s)])
         del xd_, yd_
+    # ---- CumSum / GatherElements / Trilu / Tile (rten_amd/csrc/scan.hip).  CumSum beside ReduceSum on the same shape (existing code; CumSum also WRITES the
+    # tensor, so its bytes are twice ReduceSum's), the other three beside a rten_hip_copy_strided_b32 of the same output (8 bytes per element; GatherElements
+    # also reads 4 bytes of index per element).  Each group is timed round by round in one loop.
+    if want("index:"):
+        ycs, ycc = empty((49152, 128)), empty((4096, 3072))
+        xri, xci = dev(rng.integers(-1000, 1000, (49152, 128)).astype(np.int32)), dev(rng.integers(-1000, 1000, (4096, 3072)).astype(np.int32))
+        cs = lambda dt, outer, n, inner, src, dst: (lambda: ctx.call("rten_hip_cumsum_b32", dt, 0, 0, outer, n, inner, src.vp, dst.vp))
+        alternating("CumSum last axis 49152x128", [
+            ("index: CumSum f32 last axis (row form)", "49152x128", cs(0, 49152, 128, 1, xr, ycs), 8.0 * 49152 * 128),
+            ("index: CumSum int32 last axis (row form)", "49152x128", cs(1, 49152, 128, 1, xri, ycs), 8.0 * 49152 * 128),
+            ("index: ReduceSum last axis (yardstick)", "49152x128", sum_last, b_last)])
+        alternating("CumSum axis 0 4096x3072", [
+            ("index: CumSum f32 axis 0 (column form)", "4096x3072", cs(0, 1, 4096, 3072, xc, ycc), 8.0 * 4096 * 3072),
+            ("index: CumSum int32 axis 0 (column form)", "4096x3072", cs(1, 1, 4096, 3072, xci, ycc), 8.0 * 4096 * 3072),
+            ("index: ReduceSum strided axis (yardstick)", "4096x3072 -> 3072", sum_cols, b_cols)])
+        sum_rows = (lambda: ctx.call("rten_hip_reduce_sum_strided_f32", 1, i64(4096), i64(3072), 1, i64(3072), i64(1), xc.vp, yr.vp))
+        alternating("CumSum last axis 4096x3072", [
+            ("index: CumSum f32 last axis of long rows (row form)", "4096x3072", cs(0, 4096, 3072, 1, xc, ycc), 8.0 * 4096 * 3072),
+            ("index: ReduceSum last axis of long rows (yardstick)", "4096x3072 -> 4096", sum_rows, 4.0 * (4096 * 3072 + 4096))])
+        one_lane = (lambda: ctx.call("rten_hip_reduce_sum_strided_f32", 1, i64(1), i64(1), 1, i64(1 << 20), i64(1), xc.vp, yc.vp))
+        alternating("CumSum single lane", [
+            ("index: CumSum f32 ONE lane of 2^20 (serial by contract)", "1x1048576", cs(0, 1, 1 << 20, 1, xc, ycc), 8.0 * (1 << 20)),
+            ("index: ReduceSum of the same lane (yardstick)", "1x1048576 -> 1", one_lane, 4.0 * (1 << 20))])
+        alternating("CumSum position ids 32x512", [
+            ("index: CumSum int32 position ids (row form)", "32x512", cs(1, 32, 512, 1, xri, ycs), 8.0 * 32 * 512),
+            ("index: ReduceSum of the same rows (yardstick)", "32x512 -> 32", (lambda: ctx.call("rten_hip_reduce_sum_strided_f32", 1, i64(32), i64(512), 1, i64(512), i64(1), xr.vp, yr.vp)),
+             4.0 * (32 * 512 + 32))])
+        n_ge = 4096 * 3072
+        copy2d = (lambda: ctx.call("rten_hip_copy_strided_b32", 2, i64(4096, 3072), i64(3072, 1), xc.vp, ycc.vp))
+        ids_in = dev(rng.integers(0, 3072, (4096, 3072)).astype(np.int32))
+        ids_out = dev(rng.integers(0, 4096, (4096, 3072)).astype(np.int32))
+        alternating("GatherElements 4096x3072", [
+            ("index: GatherElements innermost axis, random indices", "4096x3072", (lambda: ctx.call("rten_hip_gather_elements_b32", 2, i64(4096, 3072), i64(4096, 3072), 1, xc.vp, ids_in.vp, ycc.vp)), 12.0 * n_ge),
+            ("index: GatherElements axis 0, random indices (a row per element)", "4096x3072", (lambda: ctx.call("rten_hip_gather_elements_b32", 2, i64(4096, 3072), i64(4096, 3072), 0, xc.vp, ids_out.vp, ycc.vp)), 12.0 * n_ge),
+            ("index: strided copy of the same tensor (yardstick)", "4096x3072", copy2d, 8.0 * n_ge)])
+        del ids_in, ids_out
+        alternating("Trilu 48x512x512", [
+            ("index: Trilu upper, k = 1", "48x512x512", (lambda: ctx.call("rten_hip_trilu_b32", 1, 1, 48, 512, 512, xc.vp, ycc.vp)), 8.0 * n_ge),
+            ("index: strided copy of the same tensor (yardstick)", "48x512x512", (lambda: ctx.call("rten_hip_copy_strided_b32", 3, i64(48, 512, 512), i64(512 * 512, 512, 1), xc.vp, ycc.vp)), 8.0 * n_ge)])
+        alternating("Tile 512x768 x (8, 3)", [
+            ("index: Tile rows and columns", "512x768 x (8, 3) -> 4096x2304", (lambda: ctx.call("rten_hip_tile_b32", 2, i64(512, 768), i64(8, 3), xc.vp, ycc.vp)), 4.0 * (4096 * 2304 + 512 * 768)),
+            ("index: Tile as Tensor.repeat(1, 3, 2) of a decoder output", "64x1x768 x (1, 3, 2)", (lambda: ctx.call("rten_hip_tile_b32", 3, i64(64, 1, 768), i64(1, 3, 2), xc.vp, ycc.vp)), 4.0 * 64 * 768 * 7),
+            ("index: broadcasting strided copy to the same output (yardstick)", "-> 4096x2304", (lambda: ctx.call("rten_hip_copy_strided_b32", 2, i64(4096, 2304), i64(2304, 1), xc.vp, ycc.vp)), 8.0 * 4096 * 2304)])
+        del ycs, ycc, xri, xci
     xs = dev(rng.standard_normal((1, 21, 512, 512), dtype=np.float32))
     ys = empty((512 * 512,), np.int32)
     hbm("ArgMax over channels", "1x21x512x512", (lambda: ctx.call("rten_hip_arg_minmax_strided", 0, 0, 1, i64(512 * 512), i64(1), 21, 512 * 512, xs.vp, ys.vp)),

@@ -16,7 +16,7 @@
 //     -t, --timing           per-operator table (each operator followed by a sync)
 //     --tune                 time the candidate launch plans of every f32 convolution at load and keep the fastest
 //     --graph                capture one run into a hipGraph and replay it for the timed runs
-//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow, Reduce*, LpNormalization, GridSample, DepthToSpace and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
+//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow, Reduce*, LpNormalization, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
 //     --safetensors-info F   list the tensors of a Safetensors file (with --save-outputs: re-write it); no model, no GPU
 //
 // There is no CPU fallback: without an MI355X the tool reports BackendUnavailable and exits 2.
@@ -173,6 +173,26 @@ int main(int argc, char **argv) {
                     const Graph::DepthToSpaceNode a = Graph::read_depth_to_space_node(n, label);
                     std::printf("  layout step DepthToSpace \"%s\": mode %s, blocksize %" PRId64 " (one transpose launch)\n", n.name.c_str(),
                                 a.mode == DepthToSpaceMode::DepthColumnRow ? "DCR" : "CRD", a.block_size);
+                }
+            }
+        }
+        {
+            const onnx::Model c = Graph::canonical_form(m); // CumSum, GatherElements, Trilu and Tile: the loader's checks
+            for (auto &n : c.nodes) {
+                if (!(n.domain.empty() || n.domain == "ai.onnx") || !Graph::is_index_kind(n.op_type)) continue;
+                const std::string label = n.name.empty() ? n.outputs.at(0) : n.name;
+                if (n.op_type == "CumSum") {
+                    const Graph::CumSumNode a = Graph::read_cumsum_node(c, n, label);
+                    std::printf("  index step CumSum \"%s\": exclusive %d, reverse %d, axis from input 1 (a host value at run time)\n", n.name.c_str(), a.exclusive ? 1 : 0, a.reverse ? 1 : 0);
+                } else if (n.op_type == "GatherElements") {
+                    std::printf("  index step GatherElements \"%s\": axis %d\n", n.name.c_str(), Graph::read_gather_elements_node(n, label).axis);
+                } else if (n.op_type == "Trilu") {
+                    const Graph::TriluNode a = Graph::read_trilu_node(c, n, label);
+                    std::printf("  index step Trilu \"%s\": %s, k %s\n", n.name.c_str(), a.upper ? "upper" : "lower",
+                                n.inputs.size() > 1 && !n.inputs[1].empty() ? "from input 1 (a host value at run time)" : "0");
+                } else {
+                    Graph::read_tile_node(c, n, label);
+                    std::printf("  index step Tile \"%s\": repeats from input 1 (a host value at run time)\n", n.name.c_str());
                 }
             }
         }

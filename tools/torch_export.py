@@ -28,6 +28,8 @@ Test and tooling infrastructure only: nothing under rten_amd/ imports this.
     python tools/torch_export.py reduce_zoo /tmp/reduce_zoo.onnx        # ReduceL1 / ReduceLogSumExp / two-axis ReduceL2 / ReduceProd as the exporter writes them
     python tools/torch_export.py warp /tmp/warp.onnx                    # Conv features warped by F.grid_sample along a predicted flow (GridSample), dynamic batch
     python tools/torch_export.py pixel_shuffle_sr /tmp/sr.onnx          # Conv / ReLU / Conv / nn.PixelShuffle (Reshape / 6-D Transpose / Reshape)
+    python tools/torch_export.py roberta /tmp/roberta.onnx              # transformers.RobertaModel, 1 small layer: position ids by CumSum, buffered token_type_ids by GatherElements
+    python tools/torch_export.py causal_decoder /tmp/decoder.onnx       # embeddings + one causal attention block in plain torch.nn: CumSum, Trilu, GatherElements, Tile
     python tools/torch_export.py dynamic_upsample /tmp/dyn_up.onnx     # F.interpolate(scale_factor=2) with dynamic H / W as Shape -> .. -> Floor -> .. -> Resize(sizes), written with onnx_writer
 """
 from __future__ import annotations
@@ -41,10 +43,48 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+_INDEX_SYMBOLICS_REGISTERED = False
+
+
+def _register_index_symbolics():
+    """cumsum -> CumSum, gather -> GatherElements, triu / tril -> Trilu, as custom symbolics.  PyTorch has them in its symbolic_opset11 / symbolic_opset14 modules,
+    which the exporter does not load on its own (without them torch.cumsum fails with "ONNX export of cumsum in opset 9").  Importing those modules whole would also
+    change how every OTHER operator exports from then on, for the rest of the process (hardswish becomes a HardSwish node, pixel_shuffle a DepthToSpace node, ...), and
+    with it the graphs the existing builders here are known to produce; so only these four are registered, with the bodies PyTorch gives them."""
+    global _INDEX_SYMBOLICS_REGISTERED
+    if _INDEX_SYMBOLICS_REGISTERED:
+        return
+    import torch
+    from torch.onnx._internal.torchscript_exporter import symbolic_helper as SH
+
+    @SH.parse_args("v", "i", "none")
+    def cumsum(g, self, dim, dtype=None):
+        return g.op("CumSum", self, g.op("Constant", value_t=torch.tensor(dim, dtype=torch.int)))
+
+    @SH.parse_args("v", "i", "v", "v")
+    def gather(g, self, dim, index, sparse_grad=False):
+        if SH._maybe_get_const(sparse_grad, "i"):
+            return SH._unimplemented("gather", "sparse_grad == True")
+        return g.op("GatherElements", self, index, axis_i=dim)
+
+    def triu(g, self, diagonal, out=None):
+        return g.op("Trilu", self, diagonal, upper_i=1)
+
+    def tril(g, self, diagonal, out=None):
+        return g.op("Trilu", self, diagonal, upper_i=0)
+
+    torch.onnx.register_custom_op_symbolic("aten::cumsum", cumsum, 11)
+    torch.onnx.register_custom_op_symbolic("aten::gather", gather, 11)
+    torch.onnx.register_custom_op_symbolic("aten::triu", triu, 14)
+    torch.onnx.register_custom_op_symbolic("aten::tril", tril, 14)
+    _INDEX_SYMBOLICS_REGISTERED = True
+
+
 def export_bytes(model, args, input_names, output_names, dynamic_axes=None, opset: int = 17) -> bytes:
     import torch
     import torch.onnx._internal.torchscript_exporter.utils as TU
     import torch.onnx._internal.torchscript_exporter.symbolic_opset16  # noqa: F401  (registers grid_sampler -> GridSample; without it F.grid_sample is UnsupportedOperatorError)
+    _register_index_symbolics()
     from torch.onnx._internal.torchscript_exporter._globals import GLOBALS
     warnings.filterwarnings("ignore")
     GLOBALS.export_onnx_opset_version = opset
@@ -804,6 +844,75 @@ def pixel_shuffle_sr_onnx(weights, block: int = 2, batch: int = 2, height: int =
     return export_bytes(net, (torch.zeros(batch, 3, height, width),), ["x"], ["y"])
 
 
+def roberta_module(layers: int = 1, hidden: int = 32, heads: int = 2, ffn: int = 64, vocab: int = 100, positions: int = 40, seed: int = 0):
+    """transformers' RobertaModel (eager attention, no pooling layer), random init.  Beside what BertModel exports it holds one CumSum --
+    create_position_ids_from_input_ids: cumsum(mask, dim=1) * mask + padding_idx on int32 data -- and one GatherElements, torch.gather(buffered
+    token_type_ids, 1, position_ids)."""
+    import torch
+    from transformers import RobertaConfig, RobertaModel
+    torch.manual_seed(seed)
+    cfg = RobertaConfig(vocab_size=vocab, hidden_size=hidden, num_hidden_layers=layers, num_attention_heads=heads, intermediate_size=ffn,
+                        max_position_embeddings=positions, hidden_act="gelu", attn_implementation="eager", pad_token_id=1, bos_token_id=0, eos_token_id=2)
+    return RobertaModel(cfg, add_pooling_layer=False).eval()
+
+
+def roberta_onnx(model=None, batch: int = 2, seq: int = 7, dynamic: bool = False) -> bytes:
+    """Inputs input_ids and attention_mask [batch, seq] (int64), output last_hidden_state; `dynamic`: free batch and sequence axes."""
+    import torch
+    model = model if model is not None else roberta_module()
+    ids = torch.full((batch, seq), 5, dtype=torch.int64)
+    axes = {"input_ids": {0: "batch", 1: "seq"}, "attention_mask": {0: "batch", 1: "seq"}, "last_hidden_state": {0: "batch", 1: "seq"}} if dynamic else None
+    return export_bytes(model, (ids, torch.ones_like(ids)), ["input_ids", "attention_mask"], ["last_hidden_state"], axes)
+
+
+CAUSAL_DECODER_PAD = 1
+
+
+def causal_decoder_module(seed: int = 0, vocab: int = 50, hidden: int = 16, heads: int = 2, positions: int = 40):
+    """A small decoder block in plain torch.nn: token + position embeddings with positions from cumsum(ids.ne(pad).int(), 1) * mask + pad (CumSum on int32),
+    one attention block whose scores get torch.triu(torch.full((S, S), -inf), diagonal=1) (Trilu), torch.gather(y, 1, last_token_index) picking each
+    row's last non-pad token (GatherElements), and a .repeat(1, 3, 2) output (Tile).  forward(ids [B, S]) -> [B, 3, 2 * hidden]."""
+    import torch
+    from torch import nn
+    torch.manual_seed(seed)
+    pad = CAUSAL_DECODER_PAD
+
+    class Net(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.tok = nn.Embedding(vocab, hidden)
+            self.pos = nn.Embedding(positions, hidden)
+            self.qkv = nn.Linear(hidden, 3 * hidden)
+            self.proj = nn.Linear(hidden, hidden)
+            self.norm = nn.LayerNorm(hidden)
+
+        def forward(self, ids):
+            b, s = ids.shape[0], ids.shape[1]
+            mask = ids.ne(pad).int()
+            positions_ = (torch.cumsum(mask, dim=1) * mask).long() + pad
+            x = self.tok(ids) + self.pos(positions_)
+            q, k, v = self.qkv(x).view(b, s, 3, heads, hidden // heads).permute(2, 0, 3, 1, 4)
+            scores = q @ k.transpose(-1, -2) * (float(hidden // heads) ** -0.5)
+            scores = scores + torch.triu(torch.full((s, s), float("-inf")), diagonal=1)
+            a = torch.softmax(scores, dim=-1) @ v                                             # [B, heads, S, hidden / heads]
+            y = self.norm(x + self.proj(a.permute(0, 2, 1, 3).reshape(b, s, hidden)))
+            last = (mask.float().sum(dim=1, keepdim=True) - 1).clamp(min=0).long()            # [B, 1]: each row's last non-pad token
+            picked = torch.gather(y, 1, last.unsqueeze(-1).expand(b, 1, hidden))              # [B, 1, hidden]
+            return picked.repeat(1, 3, 2)
+
+    return Net().eval()
+
+
+def causal_decoder_onnx(model=None, batch: int = 2, seq: int = 6, dynamic: bool = False) -> bytes:
+    """Input ids [batch, seq] (int64), output y [batch, 3, 2 * hidden].  Static: the mask is a constant the exporter folds or a Trilu of a constant; `dynamic`
+    (free batch / sequence): the Trilu operand and the Tile repeats are run-time shape arithmetic."""
+    import torch
+    model = model if model is not None else causal_decoder_module()
+    ids = torch.full((batch, seq), 5, dtype=torch.int64)
+    axes = {"ids": {0: "batch", 1: "seq"}, "y": {0: "batch"}} if dynamic else None
+    return export_bytes(model, (ids,), ["ids"], ["y"], axes)
+
+
 if __name__ == "__main__":
     kind, path = sys.argv[1], sys.argv[2]
     if kind == "resnet50":
@@ -843,6 +952,10 @@ if __name__ == "__main__":
         data = embedding_head_onnx(dynamic=True)
     elif kind == "reduce_zoo":
         data = reduce_zoo_onnx()
+    elif kind == "roberta":
+        data = roberta_onnx(dynamic=True)
+    elif kind == "causal_decoder":
+        data = causal_decoder_onnx(dynamic=True)
     elif kind == "warp":
         data = warp_onnx()
     elif kind == "pixel_shuffle_sr":
