@@ -617,6 +617,22 @@ int32_t rten_hip_trilu_b32(rten_hip_ctx *ctx, int32_t upper, int64_t k, int64_t 
 /* Tile (src/ops/concat.rs:239-272) of 4-byte elements, ndim <= 6: y.shape[d] = x_shape[d] * repeats[d], y[i] = x[i mod x_shape] per axis.  A negative
  * repeat is "invalid repeats"; a zero repeat (an empty output) launches nothing. */
 int32_t rten_hip_tile_b32(rten_hip_ctx *ctx, int32_t ndim, const int64_t *x_shape, const int64_t *repeats, const void *x, void *y);
+/* NonMaxSuppression (src/ops/non_max_suppression.rs:40-188) of boxes [n, b, 4] and scores [n, c, b], float32.  The reference's rule, not textbook NMS:
+ * candidates in (n, b) order, class = arg-max of scores[n, :, b] under f32::total_cmp with the LAST maximal class, dropped when max_score < score_threshold
+ * (a NaN score stays); center_point_box != 0 reads [cx, cy, w, h] as [cy - h/2, cx - w/2, cy + h/2, cx + w/2]; iou = area(intersection) / area(bounding
+ * hull), area = max(b - t, 0) * max(r - l, 0), min / max ignoring a NaN operand, 0 / 0 = NaN comparing false; ONE selected list for all images and classes:
+ * a candidate walks it in order and at a member with iou >= iou_threshold either removes it (candidate score > member score) and goes on, or is rejected and
+ * stops -- earlier removals stay; the list is sorted by score descending (total order, ties in (n, b) order); with has_max_per_class != 0 the first
+ * max_per_class rows of each class are kept, counted over the whole batch (<= 0 keeps nothing); without it there is no limit.
+ * `selected` has room for n * b rows of [image, class, box] int32; `*count` (host memory) receives the number of rows written, rows past it are untouched.
+ * n * b == 0 or c == 0 launches nothing and gives 0.  The caller checks the operator's shape errors ("`boxes` last dimension should have size 4",
+ * "`boxes` and `scores` have incompatible shapes"); here a negative dimension, n * b above 2^30 or a null pointer is RTEN_HIP_ERR_INVALID_VALUE.
+ * The call SYNCHRONISES the context's stream once, to read the count back, and CANNOT BE CAPTURED: inside an active capture it returns
+ * RTEN_HIP_ERR_UNSUPPORTED before it launches or copies anything.  Scratch: about 64 bytes per box (+ 4 per class with a cap) of the context's auxiliary
+ * buffer, sized from n * b and c alone.  The selection loop is serial by contract and runs in one workgroup: rten_amd/csrc/nms.hip. */
+int32_t rten_hip_non_max_suppression_f32(rten_hip_ctx *ctx, int32_t center_point_box, int64_t n, int64_t c, int64_t b, const float *boxes, const float *scores,
+                                         int32_t has_max_per_class, int32_t max_per_class, float iou_threshold, float score_threshold, int32_t *selected,
+                                         int64_t *count);
 /* 1 while a graph capture is active on `ctx` (rten_hip_graph_begin .. _end): host code must not upload from host memory then -- the copy would be
  * recorded with the host pointer and re-read at every replay. */
 int32_t rten_hip_capture_active(rten_hip_ctx *ctx);
@@ -819,6 +835,15 @@ int32_t rten_hip_model_prepare(rten_hip_model *model, int32_t tune);
 /* flags bit 0: the inputs were written on the caller context's stream since the last run (the chains wait for it first); bit 1: do not order the
  * caller's stream after the chains (the caller calls rten_hip_model_sync before reading the outputs). */
 int32_t rten_hip_model_run(rten_hip_model *model, uint32_t flags);
+/* A model whose plan holds a step that READS BACK from the device to shape its output (NonMaxSuppression's row count) cannot be captured:
+ * rten_hip_model_prepare refuses it with RTEN_HIP_ERR_UNSUPPORTED -- decided from the plan, before anything runs or any capture begins; last_error names the
+ * node.  Such a model (and any other unprepared model with one chain) runs EAGERLY on the caller's stream with rten_hip_model_run_eager: bind the inputs,
+ * call it, read the outputs of that run with rten_hip_model_output (their shapes may change from run to run).  To run at other input
+ * shapes -- another batch size included -- call rten_hip_model_unbind first and bind every input again: it drops every binding of an unprepared model, and
+ * the device pointers earlier bind_input calls returned become invalid (a prepared model is refused).
+ * Replicas (rten_hip_model_clone) work the same way.  The step synchronises the stream once per run. */
+int32_t rten_hip_model_run_eager(rten_hip_model *model);
+int32_t rten_hip_model_unbind(rten_hip_model *model);
 /* rten_hip_model_load with the device taken from `ctx` (every chain is created on the context's device) and load flags.
  * RTEN_HIP_MODEL_RECEIVE_WEIGHTS: this process RECEIVES the weight arena -- rank != 0 of a batch-sharded job: initializers of 64 KB
  * and more are allocated but not uploaded; the caller then fills rten_hip_model_weight_arena() by rten_hip_broadcast from the rank that loaded the

@@ -960,6 +960,15 @@ class Graph {
     // ... and what only a RUN can tell (ranks are run-time facts here): a Softmax / LayerNormalization / ReduceSum / ReduceMean whose NEGATIVE axis resolved to
     // dim 0, or a device Transpose that moved dim 0.  Empty, or the first such step of the last run (rten_hip_model_prepare checks it after its probe run).
     const std::string &runtime_batch_coupled_step() const { return runtime_coupled_; }
+    // Empty, or the first step that reads a value back from the device to shape its output (NonMaxSuppression's row count): a plan that holds one runs
+    // eagerly, clones and lanes included, and cannot be captured.  Known from the plan, without a run.
+    std::string reading_back_step() const {
+        for (auto &st : steps_) if (st.reads_back) return st.kind_name + " \"" + st.name + "\"";
+        return "";
+    }
+    static std::string capture_refusal(const std::string &step) {
+        return step + " reads its row count back from the device: a graph whose output shape depends on device values cannot be captured (run it eagerly)";
+    }
     std::vector<std::string> step_names() const {
         std::vector<std::string> v;
         for (auto &s : steps_) v.push_back(s.kind_name + ":" + s.name);
@@ -1031,7 +1040,10 @@ class Graph {
     // What the captured graph only reads -- the steps' cached shape constants and reciprocals -- stays in place for as long as the capture lives.
     // `tail` (optional) runs at the end of the captured region, on the capturing stream, with the run's outputs: work recorded there -- e.g. the
     // copy of a sub-batch's rows into a resident full-batch tensor -- replays with the graph.
+    // A plan with a step that reads back (reading_back_step) is refused here, from the plan, before the warm-up run and before any stream capture begins: the
+    // refusal is never discovered by synchronising inside an active capture, and a graph captured earlier stays as it is.
     const std::vector<Tensor> &capture(const Feeds &feeds, const std::function<void(const std::vector<Tensor> &)> &tail = nullptr) {
+        { const std::string rb = reading_back_step(); if (!rb.empty()) throw GraphError("capture: " + capture_refusal(rb)); }
         run(feeds); // warm: every buffer size is in the pool, scratch is grown, code objects are loaded
         ctx_.sync();
         if (graph_) { // re-capture: the previous executable graph is released first
@@ -1319,6 +1331,25 @@ class Graph {
         if (n.inputs.size() < 2 || n.inputs[1].empty()) throw GraphError(where + "the repeats input is missing");
         refuse_device_operand(m, n, 1, where, "repeats");
     }
+    // What the loader reads from, and refuses about, a NonMaxSuppression node (make_nms_step; onnx_registry.rs and the operator's max_inputs): an unknown
+    // center_point_box, more than 5 inputs, fewer than 2, and a graph input (device data at run time) in place of one of the three scalars.
+    struct NmsNode { int center_point_box = 0; bool has_max = false, has_iou = false, has_score = false; };
+    static NmsNode read_nms_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        const std::string where = "NonMaxSuppression " + label + ": ";
+        NmsNode a;
+        const int64_t cpb = n.get_int("center_point_box", 0);
+        if (cpb != 0 && cpb != 1) throw GraphError(where + "center_point_box " + std::to_string(cpb) + " is not 0 ([y1, x1, y2, x2]) or 1 ([cx, cy, w, h])");
+        a.center_point_box = (int)cpb;
+        refuse_extra_inputs(n, 5, where);
+        if (n.inputs.size() < 2 || n.inputs[0].empty() || n.inputs[1].empty()) throw GraphError(where + "the boxes or scores input is missing");
+        refuse_device_operand(m, n, 2, where, "max_output_boxes_per_class");
+        refuse_device_operand(m, n, 3, where, "iou_threshold");
+        refuse_device_operand(m, n, 4, where, "score_threshold");
+        a.has_max = n.inputs.size() > 2 && !n.inputs[2].empty();
+        a.has_iou = n.inputs.size() > 3 && !n.inputs[3].empty();
+        a.has_score = n.inputs.size() > 4 && !n.inputs[4].empty();
+        return a;
+    }
     static bool is_index_kind(const std::string &k) { return k == "CumSum" || k == "GatherElements" || k == "Trilu" || k == "Tile"; }
     static bool is_math_kind(const std::string &k) {
         static const std::set<std::string> kinds = {"Neg", "Abs", "Sign", "Floor", "Ceil", "Round", "Sqrt", "Reciprocal", "Exp", "Log", "Softplus", "Pow", "PRelu", "Min", "Max", "Sum", "Mean"};
@@ -1480,6 +1511,7 @@ class Graph {
         std::shared_ptr<MaxPool> maxpool; // a max-pool whose output is quantized next can accumulate the quantizer's statistics
         bool removed = false;
         bool batch_coupled = false; // the result for one dim-0 row depends on other rows (no sub-batch chains for such a graph)
+        bool reads_back = false;    // the step reads a count back from the device to shape its output (NonMaxSuppression): it synchronises and cannot be captured
         size_t pos = 0; // index of the LAST graph node folded into this step: the step runs where that node stood
     };
 
@@ -2695,6 +2727,7 @@ class Graph {
             else if (is_math_kind(kind)) make_math_step(st, n, m);
             else if (kind == "Pad") make_pad_step(st, n, m);
             else if (is_index_kind(kind)) make_index_step(st, n, m);
+            else if (kind == "NonMaxSuppression") make_nms_step(st, n, m);
             else if (kind == "QuantizeLinear" || kind == "DequantizeLinear") make_qdq_step(st, n, m, nodes, out_name);
             else if (kind == "Flatten" || kind == "Reshape" || kind == "Squeeze" || kind == "Unsqueeze" || kind == "Identity" || kind == "Dropout") make_view_step(st, n);
             else if (make_layout_step(st, n)) {
@@ -3098,6 +3131,18 @@ class Graph {
             o.push_back(pad_tensor(c, x, pads, a.mode, fill_bits));
             return o;
         };
+    }
+
+    // NonMaxSuppression: read_nms_node's checks at load.  The three scalar operands are host values at run time (the operator refuses a device-valued one that
+    // is not a graph input).  One selected list serves every image, so the step is batch_coupled: no sub-batch chains.  It READS BACK the row count to shape
+    // its output -- the one kind of step that does: it synchronises the stream once per run, capture() refuses the plan before it begins (reads_back), and
+    // what follows it (Gather of the boxes by selected[:, 2], Slice, Squeeze) sees an ordinary run-time shape.
+    void make_nms_step(Step &st, const onnx::Node &n, const onnx::Model &m) {
+        auto op = std::make_shared<NonMaxSuppression>();
+        op->center_point_box = read_nms_node(m, n, st.name).center_point_box;
+        st.batch_coupled = true;
+        st.reads_back = true;
+        run_plainly(st, op);
     }
 
     // CumSum / GatherElements / Trilu / Tile: the read_*_node checks at load.  CumSum's axis, Trilu's k and Tile's repeats are host values at run time (constants

@@ -2391,6 +2391,55 @@ struct Tile : Operator {
     }
 };
 
+// ---- NonMaxSuppression (src/ops/non_max_suppression.rs:40-233; rten_amd/csrc/nms.hip): inputs boxes [N, B, 4], scores [N, C, B] and three optional
+// one-element operands, max_output_boxes_per_class (int32; ABSENT = no limit, the reference's default), iou_threshold and score_threshold (float32, 0).
+// The three are HOST values -- constants or shape arithmetic, read the way Slice reads its starts -- and a device-valued one is refused: the reference's
+// get_as (operator.rs:790-806; one element of any rank, else "expected tensor with 0 dims").  The result is int32 [count, 3], rows [n, class, b]: the
+// first operator here whose output SHAPE depends on device values, so the call synchronises once (the count) and cannot be captured into a graph.
+inline void check_nms_shapes(const std::vector<int64_t> &boxes, const std::vector<int64_t> &scores) {
+    if (boxes.size() != 3 || scores.size() != 3) throw OpError(OpError::InputCastFailed, "expected tensor with 3 dims");
+    if (boxes[2] != 4) throw OpError(OpError::InvalidValue, "`boxes` last dimension should have size 4");
+    if (boxes[0] != scores[0] || boxes[1] != scores[2]) throw OpError(OpError::IncompatibleInputShapes, "`boxes` and `scores` have incompatible shapes");
+}
+// one optional scalar operand: false when absent
+inline const HostVal *nms_scalar(const InputList &in, size_t i, bool is_float, const char *what) {
+    const Tensor *t = get(in, i);
+    if (!t) return nullptr;
+    want(*t, is_float ? DType::F32 : DType::I32, is_float ? "float32" : "int32");
+    if (t->len() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 0 dims");
+    if (!t->host() || t->host()->is_float != is_float)
+        throw OpError(OpError::UnsupportedValue, std::string("NonMaxSuppression: ") + what + " must be a constant or computable from the input shapes (it depends on device data)");
+    return t->host();
+}
+inline Tensor nms_tensor(Context &ctx, const Tensor &boxes, const Tensor &scores, int center_point_box, bool has_max, int64_t max_per_class, float iou_threshold, float score_threshold) {
+    want(boxes, DType::F32, "float32");
+    want(scores, DType::F32, "float32");
+    check_nms_shapes(boxes.shape(), scores.shape());
+    if (center_point_box != 0 && center_point_box != 1) throw OpError(OpError::InvalidValue, "center_point_box must be 0 or 1");
+    const int64_t n = boxes.size(0), b = boxes.size(1), c = scores.size(1);
+    if (c == 0 || n * b == 0) return Tensor(ctx, {0, 3}, DType::I32);
+    Tensor rows(ctx, {n * b, 3}, DType::I32);
+    int64_t count = 0;
+    const int64_t cap = std::max<int64_t>(INT32_MIN, std::min<int64_t>(INT32_MAX, max_per_class)); // the loader's saturating int64 -> int32
+    ctx.check(rten_hip_non_max_suppression_f32(ctx.raw(), center_point_box, n, c, b, (const float *)boxes.ptr(), (const float *)scores.ptr(), has_max ? 1 : 0, (int32_t)cap,
+                                               iou_threshold, score_threshold, (int32_t *)rows.ptr(), &count));
+    rows.reshape({count, 3}); // (the buffer keeps its capacity of n * b rows)
+    return rows;
+}
+struct NonMaxSuppression : Operator {
+    int center_point_box = 0;
+    const char *name() const override { return "NonMaxSuppression"; }
+    int max_inputs() const override { return 5; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        if (in.size() > 5) throw OpError(OpError::InvalidValue, "NonMaxSuppression takes at most 5 inputs");
+        const Tensor &boxes = require(in, 0), &scores = require(in, 1);
+        const HostVal *cap = nms_scalar(in, 2, false, "max_output_boxes_per_class"), *iou = nms_scalar(in, 3, true, "iou_threshold"), *score = nms_scalar(in, 4, true, "score_threshold");
+        OutputList out;
+        out.push_back(nms_tensor(ctx, boxes, scores, center_point_box, cap != nullptr, cap ? cap->i.at(0) : 0, iou ? iou->f.at(0) : 0.f, score ? score->f.at(0) : 0.f));
+        return out;
+    }
+};
+
 // Split (src/ops/split.rs:34-136) of 4-byte tensors, one strided copy per piece: the sizes of input 1 (the opset < 13 `split` attribute arrives
 // there too), else `num_outputs` (opset 18), else the node's output count, as equal chunks of ceil(dim / n) -- the last piece is smaller, and there
 // may be fewer than n pieces (5 split 4 ways gives 3).
@@ -3339,6 +3388,7 @@ class OpRegistry {
         r.register_op<GridSample>("GridSample");
         r.register_op<DepthToSpace>("DepthToSpace");
         r.register_op<CumSum>("CumSum");
+        r.register_op<NonMaxSuppression>("NonMaxSuppression");
         r.register_op<GatherElements>("GatherElements");
         r.register_op<Trilu>("Trilu");
         r.register_op<Tile>("Tile");

@@ -126,6 +126,7 @@ struct rten_hip_model {
     std::vector<int64_t> sub, start;                        // sub-batch sizes / first rows
     size_t planned_steps = 0, tuned_steps = 0;
     bool prepared = false;
+    bool eager_ran = false; // full_out / out_shape are those of the last rten_hip_model_run_eager
     void *arena_ptr = nullptr; // chain 0's coalesced constants (owned by graphs[0]; a clone: its origin's)
     size_t arena_bytes = 0;
     std::shared_ptr<onnx::Model> parsed; // kept for rten_hip_model_clone
@@ -318,7 +319,7 @@ RTEN_EXPORT const char *rten_hip_model_input_name(const rten_hip_model *g, int32
 RTEN_EXPORT const char *rten_hip_model_output_name(const rten_hip_model *g, int32_t i) { return (g && i >= 0 && (size_t)i < g->outputs.size()) ? g->outputs[(size_t)i].name.c_str() : nullptr; }
 
 // Declares input `i`'s FULL-batch shape (dim 0 = batch, split over the chains) and allocates its resident buffer; `*dev_ptr` is where the caller
-// writes the input (device memory, valid until _destroy).
+// writes the input (device memory, valid until _destroy, or until rten_hip_model_unbind on an unprepared model).
 RTEN_EXPORT int32_t rten_hip_model_bind_input(rten_hip_model *g, int32_t i, const int64_t *shape, int32_t ndim, void **dev_ptr) {
     if (!g || i < 0 || (size_t)i >= g->inputs.size() || !shape || ndim < 1 || ndim > 8) return RTEN_HIP_ERR_INVALID_VALUE;
     if (g->prepared) return fail(g, RTEN_HIP_ERR_INVALID_VALUE, "bind_input after prepare");
@@ -350,12 +351,32 @@ RTEN_EXPORT int32_t rten_hip_model_bind_input(rten_hip_model *g, int32_t i, cons
     return RTEN_HIP_OK;
 }
 
+// Drops every input binding of an UNPREPARED model, so that its inputs can be bound again at other shapes -- another batch size included: what a model
+// that runs eagerly (rten_hip_model_run_eager) calls between runs at different shapes.  The device pointers earlier rten_hip_model_bind_input calls returned
+// are invalid from here on; the outputs of the last eager run stay readable until the next run.  A prepared model is refused (its captured chains hold
+// the bound addresses).
+RTEN_EXPORT int32_t rten_hip_model_unbind(rten_hip_model *g) {
+    if (!g) return RTEN_HIP_ERR_INVALID_VALUE;
+    if (g->prepared) return fail(g, RTEN_HIP_ERR_INVALID_VALUE, "unbind: the model is prepared (its captured chains read the bound inputs)");
+    for (auto &c : g->ctxs) c->sync(); // nothing in flight still reads them
+    g->chain_in.clear();
+    g->full_in.clear();
+    g->sub.clear();
+    g->start.clear();
+    return RTEN_HIP_OK;
+}
+
 // Applies the launch plan (or, with tune != 0 and no plan file, times the candidates once per distinct sub-batch size), runs every chain once
 // (buffer pool and scratch reach their steady state) and captures each chain into a hipGraph.
 RTEN_EXPORT int32_t rten_hip_model_prepare(rten_hip_model *g, int32_t tune) {
     if (!g) return RTEN_HIP_ERR_INVALID_VALUE;
     if (g->full_in.size() != g->inputs.size()) return fail(g, RTEN_HIP_ERR_INVALID_VALUE, "prepare: bind every input first");
     for (auto &t : g->full_in) if (!t) return fail(g, RTEN_HIP_ERR_INVALID_VALUE, "prepare: bind every input first");
+    // prepare captures every chain: a plan with a step that reads back is refused from the plan, before anything runs and before any capture begins
+    {
+        const std::string rb = g->graphs[0]->reading_back_step();
+        if (!rb.empty()) return fail(g, RTEN_HIP_ERR_UNSUPPORTED, "prepare: " + Graph::capture_refusal(rb) + ": rten_hip_model_run_eager");
+    }
     try {
         std::map<int64_t, std::map<std::string, GemmPlan>> tuned; // per sub-batch size
         g->full_out.clear();
@@ -566,6 +587,36 @@ RTEN_EXPORT int32_t rten_hip_model_run(rten_hip_model *g, uint32_t flags) {
     return RTEN_HIP_OK;
 }
 
+// One EAGER inference over the bound inputs, on the caller's stream: what a model whose plan holds a step that reads back (NonMaxSuppression: the output
+// shape depends on device values, rten_hip_model_prepare refuses it) runs with.  One chain only; the model must not be prepared (a prepared model replays
+// its captured chains).  The outputs of THIS run -- their shapes may differ from the last run's -- are what rten_hip_model_output returns until the next
+// call; inputs may be re-bound to other shapes between calls.  A step that reads back synchronises the stream; anything else is only enqueued.
+RTEN_EXPORT int32_t rten_hip_model_run_eager(rten_hip_model *g) {
+    if (!g) return RTEN_HIP_ERR_INVALID_VALUE;
+    if (g->prepared) return fail(g, RTEN_HIP_ERR_INVALID_VALUE, "run_eager: the model is prepared (rten_hip_model_run replays its captured chains)");
+    if (g->chains != 1) return fail(g, RTEN_HIP_ERR_UNSUPPORTED, "run_eager: one chain only");
+    if (g->full_in.size() != g->inputs.size()) return fail(g, RTEN_HIP_ERR_INVALID_VALUE, "run_eager: bind every input first");
+    for (auto &t : g->full_in) if (!t) return fail(g, RTEN_HIP_ERR_INVALID_VALUE, "run_eager: bind every input first");
+    try {
+        Graph::Feeds feeds;
+        for (size_t i = 0; i < g->inputs.size(); i++) feeds.emplace_back(g->inputs[i].name, &g->chain_in[0][i]);
+        std::vector<Tensor> outs = g->graphs[0]->run(feeds);
+        g->full_out.clear();
+        g->out_shape.clear();
+        for (auto &o : outs) {
+            g->out_shape.push_back(o.shape());
+            g->full_out.emplace_back(new Tensor(std::move(o)));
+        }
+        g->eager_ran = true;
+        g->last_error.clear();
+    } catch (const OpError &e) {
+        return fail(g, code_of(e), e.msg);
+    } catch (const std::exception &e) {
+        return fail(g, RTEN_HIP_ERR_INVALID_VALUE, e.what());
+    }
+    return RTEN_HIP_OK;
+}
+
 // Waits for every chain (and reports a sticky device fault of any of them).
 RTEN_EXPORT int32_t rten_hip_model_sync(rten_hip_model *g) {
     if (!g) return RTEN_HIP_ERR_INVALID_VALUE;
@@ -587,14 +638,14 @@ RTEN_EXPORT int32_t rten_hip_model_input_dtype(const rten_hip_model *g, int32_t 
 }
 
 RTEN_EXPORT int32_t rten_hip_model_output_dtype(const rten_hip_model *g, int32_t i, int32_t *dtype) {
-    if (!g || !dtype || !g->prepared || i < 0 || (size_t)i >= g->full_out.size()) return RTEN_HIP_ERR_INVALID_VALUE;
+    if (!g || !dtype || !(g->prepared || g->eager_ran) || i < 0 || (size_t)i >= g->full_out.size()) return RTEN_HIP_ERR_INVALID_VALUE;
     *dtype = dtype_code(g->full_out[(size_t)i]->dtype());
     return RTEN_HIP_OK;
 }
 
 // Output `i` after a run: device pointer of the resident full-batch tensor, its shape (up to 8 dims) and rank.
 RTEN_EXPORT int32_t rten_hip_model_output(rten_hip_model *g, int32_t i, const void **dev_ptr, int64_t *shape, int32_t *ndim) {
-    if (!g || !g->prepared || i < 0 || (size_t)i >= g->full_out.size()) return RTEN_HIP_ERR_INVALID_VALUE;
+    if (!g || !(g->prepared || g->eager_ran) || i < 0 || (size_t)i >= g->full_out.size()) return RTEN_HIP_ERR_INVALID_VALUE;
     if (dev_ptr) *dev_ptr = g->full_out[(size_t)i]->ptr();
     if (ndim) *ndim = (int32_t)g->out_shape[(size_t)i].size();
     if (shape) for (size_t d = 0; d < g->out_shape[(size_t)i].size() && d < 8; d++) shape[d] = g->out_shape[(size_t)i][d];

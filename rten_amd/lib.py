@@ -209,6 +209,7 @@ PROTOTYPES = {
     "rten_hip_gather_elements_b32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP]),
     "rten_hip_trilu_b32": (_I32, [_VP, _I32, _I64, _I64, _I64, _I64, _VP, _VP]),
     "rten_hip_tile_b32": (_I32, [_VP, _I32, _VP, _VP, _VP, _VP]),
+    "rten_hip_non_max_suppression_f32": (_I32, [_VP, _I32, _I64, _I64, _I64, _VP, _VP, _I32, _I32, C.c_float, C.c_float, _VP, _VP]),
     "rten_hip_reduce_sum_strided_f32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_reduce_mean_strided_f32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_reduce_minmax_strided": (_I32, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
@@ -256,6 +257,8 @@ PROTOTYPES = {
     "rten_hip_model_bind_input": (_I32, [_VP, _I32, C.POINTER(_I64), _I32, C.POINTER(_VP)]),
     "rten_hip_model_prepare": (_I32, [_VP, _I32]),
     "rten_hip_model_run": (_I32, [_VP, _U32]),
+    "rten_hip_model_run_eager": (_I32, [_VP]),
+    "rten_hip_model_unbind": (_I32, [_VP]),
     "rten_hip_model_sync": (_I32, [_VP]),
     "rten_hip_model_output": (_I32, [_VP, _I32, C.POINTER(_VP), C.POINTER(_I64), C.POINTER(_I32)]),
     "rten_hip_model_input_dtype": (_I32, [_VP, _I32, C.POINTER(_I32)]),
@@ -539,6 +542,15 @@ class Model:
         """`join=False`: the caller's stream is not ordered behind the chains (flags bit 1) -- back-to-back runs then let the chains free-run
         across run boundaries; call sync() before reading the outputs."""
         self._check(self.lib.rten_hip_model_run(self.h, (1 if inputs_written_on_caller_stream else 0) | (0 if join else 2)))
+
+    def run_eager(self):
+        """One eager run on the caller's stream (one chain, not prepared): how a model with a NonMaxSuppression node runs -- prepare() refuses it, because a
+        graph whose output shape depends on device values cannot be captured.  output(i) then describes THIS run's outputs."""
+        self._check(self.lib.rten_hip_model_run_eager(self.h))
+
+    def unbind(self):
+        """Drops every input binding of an unprepared model: bind the inputs again, at any shapes (pointers bind_input returned before are invalid)."""
+        self._check(self.lib.rten_hip_model_unbind(self.h))
 
     def sync(self):
         self._check(self.lib.rten_hip_model_sync(self.h))

@@ -681,3 +681,60 @@ def index_ops_graph(batch="batch", rows: int = 4, cols: int = 5, picks: int = 3,
             value_info("gather_mid", FLOAT, [batch, picks, cols]), value_info("gather_last", FLOAT, [batch, picks, cols]), value_info("tril_km1", FLOAT, shape),
             value_info("triu_k1", FLOAT, shape), value_info("tiled", FLOAT, [batch, 2 * rows, 3 * cols])]
     return model(nodes, ins, outs, inits, opset=14, name="index_ops")
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# A detector head that ends in NonMaxSuppression (what an ultralytics export with nms=True, torchvision's detection heads and SSD post-processing end in)
+# ----------------------------------------------------------------------------------------------------------------
+DETECTOR_HEAD_BAD = ("center_point_box_2", "six_inputs", "max_input", "iou_input", "score_input")
+
+
+def detector_head_graph(seed: int = 31, features: int = 6, classes: int = 3, batch="batch", center_point_box: int = 0, max_output_boxes_per_class=None,
+                        iou_threshold=0.5, score_threshold=None, expose_operands: bool = False, bad: str | None = None):
+    """x [batch, features, h, w] -> Conv 1x1 to 4 + classes maps -> Sigmoid -> Split into a box map and a class map -> Reshape / Transpose to
+    boxes [batch, h * w, 4] and scores [batch, classes, h * w] -> NonMaxSuppression "nms" with constant scalar operands -> `selected` [count, 3];
+    Gather(selected, 2, axis 1) -> the box indices; Gather of image 0's boxes by them -> `picked` [count, 4].  With center_point_box == 0 the far corners
+    are moved by +0.6 so that most boxes have a positive area (and some do not).  An optional operand given as None is ABSENT (a later one that is present
+    leaves an empty name in its place); max_output_boxes_per_class is an int64 [1] tensor as exporters write it (2 ** 63 - 1 for "all").
+    `expose_operands` adds `boxes` and `scores` to the graph outputs.  `bad` (one of DETECTOR_HEAD_BAD) gives a graph the loader refuses at node "nms".
+    -> (model bytes, weights)."""
+    assert bad is None or bad in DETECTOR_HEAD_BAD, bad
+    rng = np.random.default_rng(seed)
+    w = {"head": (rng.normal(0, 1.5, (4 + classes, features, 1, 1)).astype(np.float32), rng.normal(0, 0.5, 4 + classes).astype(np.float32))}
+    inits = [tensor("head.w", w["head"][0]), tensor("head.b", w["head"][1]), tensor("split_sizes", np.asarray([4, classes], np.int64)),
+             tensor("box_shape", np.asarray([0, 4, -1], np.int64)), tensor("cls_shape", np.asarray([0, classes, -1], np.int64)),
+             tensor("far_corner_shift", np.asarray([0, 0, 0.6, 0.6], np.float32).reshape(1, 4, 1)), tensor("two", np.asarray(2, np.int64)),
+             tensor("zero", np.asarray(0, np.int64))]
+    ins = [value_info("x", FLOAT, [batch, features, "h", "w"])]
+    scalars = []
+    for name, value, dtype, shape in (("max_per_class", max_output_boxes_per_class, np.int64, (1,)), ("iou_thr", iou_threshold, np.float32, (1,)),
+                                      ("score_thr", score_threshold, np.float32, ())):
+        if bad == {"max_per_class": "max_input", "iou_thr": "iou_input", "score_thr": "score_input"}[name]:
+            ins.append(value_info(name + "_in", INT64 if dtype is np.int64 else FLOAT, list(shape)))
+            scalars.append(name + "_in")
+        elif value is None:
+            scalars.append("")
+        else:
+            inits.append(tensor(name, np.asarray(value, dtype).reshape(shape)))
+            scalars.append(name)
+    while scalars and scalars[-1] == "":
+        scalars.pop()
+    if bad == "six_inputs":
+        scalars = (scalars + ["", "", ""])[:3] + ["zero"]
+    nms_attrs = {"center_point_box": 2 if bad == "center_point_box_2" else center_point_box}
+    nodes = [node("Conv", ["x", "head.w", "head.b"], ["head"], name="head", kernel_shape=[1, 1]),
+             node("Sigmoid", ["head"], ["head.s"], name="head.sigmoid"),
+             node("Split", ["head.s", "split_sizes"], ["box_map", "cls_map"], name="split", axis=1),
+             node("Reshape", ["box_map", "box_shape"], ["box_rows"], name="box_rows")]
+    if center_point_box == 0:
+        nodes.append(node("Add", ["box_rows", "far_corner_shift"], ["box_corners"], name="far_corners"))
+    nodes += [node("Transpose", ["box_corners" if center_point_box == 0 else "box_rows"], ["boxes"], name="boxes", perm=[0, 2, 1]),
+              node("Reshape", ["cls_map", "cls_shape"], ["scores"], name="scores"),
+              node("NonMaxSuppression", ["boxes", "scores"] + scalars, ["selected"], name="nms", **nms_attrs),
+              node("Gather", ["selected", "two"], ["box_ids"], name="box_ids", axis=1),
+              node("Gather", ["boxes", "zero"], ["boxes0"], name="boxes0", axis=0),
+              node("Gather", ["boxes0", "box_ids"], ["picked"], name="picked", axis=0)]
+    outs = [value_info("selected", INT64, ["count", 3]), value_info("picked", FLOAT, ["count", 4])]
+    if expose_operands:
+        outs += [value_info("boxes", FLOAT, [batch, "boxes", 4]), value_info("scores", FLOAT, [batch, classes, "boxes"])]
+    return model(nodes, ins, outs, inits, opset=13, name="detector_head"), w

@@ -2376,6 +2376,66 @@ class Split(Operator):
         return outs
 
 
+def _nms_scalar(t, index, kind, what):
+    """get_as::<i32 / f32> (src/operator.rs:790-806) of one of NonMaxSuppression's optional operands: absent -> None; a host value (numpy array or
+    Python number) of one element, of any rank.  A device tensor is refused: the graph executor hands constants and shape arithmetic over as host values."""
+    if t is None:
+        return None
+    if isinstance(t, DeviceTensor):
+        raise UnsupportedValue(f"NonMaxSuppression: {what} (input {index}) must be a host value, a constant or shape arithmetic; it is device data")
+    a = np.asarray(t)
+    if a.dtype.kind not in kind:
+        raise OpError("InputCastFailed", "expected int32 tensor" if kind == "iu" else "expected float32 tensor")
+    if a.size != 1:
+        raise OpError("InputCastFailed", "expected tensor with 0 dims")
+    return a.reshape(())
+
+
+class NonMaxSuppression(Operator):
+    """src/ops/non_max_suppression.rs:40-233 (rten_hip_non_max_suppression_f32): inputs boxes [N, B, 4], scores [N, C, B] and, optional and host-side,
+    max_output_boxes_per_class (int; ABSENT means no limit, the reference's default, and an int64 is narrowed with saturation as the loader does),
+    iou_threshold and score_threshold (float32, default 0).  The reference's rule, not textbook NMS (the entry point's comment in include/rten_hip.h states
+    it): one selected list across images and classes, candidates in (n, b) order, hull IoU, removals by a rejected candidate stay.  The result is an int32
+    [count, 3] tensor of [n, class, b] rows: its shape depends on device values, so the call synchronises once and cannot be captured."""
+
+    def __init__(self, center_point_box=0):
+        self.center_point_box = center_point_box
+
+    def max_inputs(self):
+        return 5
+
+    def run(self, ctx, inputs):
+        if len(inputs) > 5:
+            raise InvalidValue("NonMaxSuppression takes at most 5 inputs")
+        boxes, scores = _want(_require(inputs, 0), np.float32), _want(_require(inputs, 1), np.float32)
+        for t in (boxes, scores):
+            if len(t.shape) != 3:
+                raise OpError("InputCastFailed", "expected tensor with 3 dims")
+        cap = _nms_scalar(_get(inputs, 2), 2, "iu", "max_output_boxes_per_class")
+        iou = _nms_scalar(_get(inputs, 3), 3, "f", "iou_threshold")
+        score = _nms_scalar(_get(inputs, 4), 4, "f", "score_threshold")
+        if self.center_point_box not in (0, 1):
+            raise InvalidValue("center_point_box must be 0 or 1")
+        n, b, coords = boxes.shape
+        sn, c, sb = scores.shape
+        if coords != 4:
+            raise InvalidValue("`boxes` last dimension should have size 4")
+        if n != sn or b != sb:
+            raise IncompatibleInputShapes("`boxes` and `scores` have incompatible shapes")
+        if c == 0 or n * b == 0:
+            return [DeviceTensor(ctx, (0, 3), np.int32)]
+        rows = DeviceTensor(ctx, (n * b, 3), np.int32)
+        count = C.c_int64(0)
+        cap_v = 0 if cap is None else max(-2 ** 31, min(2 ** 31 - 1, int(cap)))  # saturating_cast_i64_to_i32
+        ctx.call("rten_hip_non_max_suppression_f32", int(self.center_point_box), n, c, b, boxes.vp, scores.vp, 0 if cap is None else 1, cap_v,
+                 C.c_float(0.0 if iou is None else float(np.float32(iou))), C.c_float(0.0 if score is None else float(np.float32(score))), rows.vp, C.byref(count))
+        return [rows.view((int(count.value), 3))]
+
+    def batch_coupled(self):
+        """One selected list serves every image: sub-batch chains would give other rows."""
+        return True
+
+
 RNN_DIRECTIONS = {"forward": L.RNN_FORWARD, "reverse": L.RNN_REVERSE, "bidirectional": L.RNN_BIDIRECTIONAL}
 
 
@@ -2486,7 +2546,8 @@ class OpRegistry:
                    AveragePool, GlobalAveragePool, Flatten, DynamicQuantizeLinear, Attention, Gather, ReduceSum, ReduceMean, Einsum, Resize, Upsample,
                    Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK, GRU, LSTM, Neg, Abs, Sign, Floor, Ceil, Round, Sqrt, Reciprocal, Exp, Log, Softplus,
                    Pow, PRelu, Min, Max, Sum, Mean, Pad, QuantizeLinear, DequantizeLinear, ReduceL1, ReduceL2, ReduceSumSquare, ReduceLogSum, ReduceLogSumExp,
-                   ReduceProd, LpNormalization, GlobalMaxPool, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile):
+                   ReduceProd, LpNormalization, GlobalMaxPool, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile,
+                   NonMaxSuppression):
             r.register_op(op)
         return r
 

@@ -420,6 +420,61 @@ def main():
             ("index: Tile as Tensor.repeat(1, 3, 2) of a decoder output", "64x1x768 x (1, 3, 2)", (lambda: ctx.call("rten_hip_tile_b32", 3, i64(64, 1, 768), i64(1, 3, 2), xc.vp, ycc.vp)), 4.0 * 64 * 768 * 7),
             ("index: broadcasting strided copy to the same output (yardstick)", "-> 4096x2304", (lambda: ctx.call("rten_hip_copy_strided_b32", 2, i64(4096, 2304), i64(2304, 1), xc.vp, ycc.vp)), 8.0 * 4096 * 2304)])
         del ycs, ycc, xri, xci
+    # ---- NonMaxSuppression (rten_amd/csrc/nms.hip) on a detector's post-processing shape: 8400 boxes x 80 classes, one image and 32, at a score threshold that
+    # leaves about 100 candidates per image and at one that leaves all of them.  The call synchronises (it reads the row count back), so a row is the host's
+    # wall time around ONE call, median of `rounds` after a warm-up call; beside it the per-kernel times of the same call from the launch profiler -- the
+    # class walk (step 1, HBM-bound: it reads every score once; its yardstick is the existing ReduceMax over the class axis of the same scores, timed the usual
+    # way), the serial resolve on its own, and the sort / cap / rows launch.  The resolve is ONE workgroup and serial by contract: latency-bound, one barrier
+    # and a dependent load chain per candidate, plus the iou of the candidate against every member alive at that point.
+    if want("nms:"):
+        import time
+
+        def nms_rows(images, per_image, rounds=5):
+            nb_, nc_ = 8400, 80
+            cx, cy = rng.uniform(0, 640, (images, nb_)), rng.uniform(0, 640, (images, nb_))
+            w_, h_ = rng.uniform(20, 200, (images, nb_)), rng.uniform(20, 200, (images, nb_))
+            bx = dev(np.stack([cx, cy, w_, h_], axis=-1).astype(np.float32))
+            sc_np = (rng.random((images, nc_, nb_)) ** 8).astype(np.float32)
+            best = np.sort(sc_np.max(axis=1).reshape(-1))
+            thr = float(best[-per_image * images]) if per_image < nb_ else -1.0
+            sc, out_rows, ymax = dev(sc_np), empty((images * nb_, 3), np.int32), empty((images, nb_))
+            count = C.c_int64(0)
+            call = (lambda: ctx.call("rten_hip_non_max_suppression_f32", 1, images, nc_, nb_, bx.vp, sc.vp, 0, 0, C.c_float(0.5), C.c_float(thr), out_rows.vp, C.byref(count)))
+            call()
+            wall, kernels = [], {}
+            for _ in range(rounds):
+                ctx.profile_reset()
+                ctx.profile(True)
+                t0 = time.perf_counter()
+                call()
+                wall.append((time.perf_counter() - t0) * 1e6)
+                ctx.profile(False)
+                for e in ctx.profile_report():
+                    if str(e.get("kernel", "")).startswith("nms_"):
+                        kernels.setdefault(e["kernel"], []).append(float(e.get("ms", 0.0)) * 1e3)
+            wall.sort()
+            shape = f"{images}x{nb_} boxes x {nc_} classes, {per_image if per_image < nb_ else nb_} candidates per image, iou 0.5 -> {count.value} rows"
+            nbytes = 4.0 * images * nb_ * (nc_ + 4)
+            rows.append({"op": "nms: NonMaxSuppression, whole call (host wall time, one sync)", "shape": shape, "us": round(wall[len(wall) // 2], 2), "us_min": round(wall[0], 2),
+                         "us_max": round(wall[-1], 2), "rounds": rounds, "group": "nms", "bound": "latency (one workgroup, serial by contract)", "algorithmic_bytes": int(nbytes),
+                         "rows": int(count.value)})
+            for name, bound in (("nms_class_f32", "hbm"), ("nms_offsets", "latency"), ("nms_gather_f32", "hbm"), ("nms_resolve", "latency (one workgroup, serial by contract)"),
+                                ("nms_order", "latency (one workgroup)")):
+                t = sorted(kernels.get(name, [0.0]))
+                row = {"op": f"nms: {name} (launch profiler)", "shape": shape, "us": round(t[len(t) // 2], 2), "us_min": round(t[0], 2), "us_max": round(t[-1], 2), "rounds": rounds,
+                       "group": "nms", "bound": bound}
+                if name == "nms_class_f32" and row["us"] > 0:
+                    gbs = 4.0 * images * nb_ * nc_ / row["us"] / 1e3
+                    row.update({"achieved": round(gbs, 1), "unit": "GB/s", "peak": HBM_PEAK_GBS, "frac": round(gbs / HBM_PEAK_GBS, 3), "algorithmic_bytes": int(4.0 * images * nb_ * nc_)})
+                rows.append(row)
+            alternating(f"nms class walk {images}x{nc_}x{nb_}", [
+                ("nms: ReduceMax over the class axis of the same scores (yardstick for nms_class_f32)", f"{images}x{nc_}x{nb_} -> {images}x{nb_}",
+                 (lambda: ctx.call("rten_hip_reduce_minmax_strided", 0, 0, 2, i64(images, nb_), i64(nc_ * nb_, 1), 1, i64(nc_), i64(nb_), sc.vp, ymax.vp)), 4.0 * images * nb_ * (nc_ + 1))])
+
+        nms_rows(1, 100)
+        nms_rows(1, 8400)
+        nms_rows(32, 100)
+        nms_rows(32, 8400, rounds=3)
     xs = dev(rng.standard_normal((1, 21, 512, 512), dtype=np.float32))
     ys = empty((512 * 512,), np.int32)
     hbm("ArgMax over channels", "1x21x512x512", (lambda: ctx.call("rten_hip_arg_minmax_strided", 0, 0, 1, i64(512 * 512), i64(1), 21, 512 * 512, xs.vp, ys.vp)),

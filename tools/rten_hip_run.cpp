@@ -15,8 +15,8 @@
 //     --no-fuse              run the graph node by node (no fusion passes)
 //     -t, --timing           per-operator table (each operator followed by a sync)
 //     --tune                 time the candidate launch plans of every f32 convolution at load and keep the fastest
-//     --graph                capture one run into a hipGraph and replay it for the timed runs
-//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow, Reduce*, LpNormalization, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
+//     --graph                capture one run into a hipGraph and replay it for the timed runs (refused, by node name, for a graph with a NonMaxSuppression node)
+//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow, Reduce*, LpNormalization, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile, NonMaxSuppression and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
 //     --safetensors-info F   list the tensors of a Safetensors file (with --save-outputs: re-write it); no model, no GPU
 //
 // There is no CPU fallback: without an MI355X the tool reports BackendUnavailable and exits 2.
@@ -194,6 +194,16 @@ int main(int argc, char **argv) {
                     Graph::read_tile_node(c, n, label);
                     std::printf("  index step Tile \"%s\": repeats from input 1 (a host value at run time)\n", n.name.c_str());
                 }
+            }
+        }
+        {
+            const onnx::Model c = Graph::canonical_form(m); // NonMaxSuppression: the loader's checks
+            for (auto &n : c.nodes) {
+                if (!(n.domain.empty() || n.domain == "ai.onnx") || n.op_type != "NonMaxSuppression") continue;
+                const Graph::NmsNode a = Graph::read_nms_node(c, n, n.name.empty() ? n.outputs.at(0) : n.name);
+                std::printf("  nms step \"%s\": %s boxes, max_output_boxes_per_class %s, iou_threshold %s, score_threshold %s; reads the row count back (eager runs only, no capture, no sub-batch chains)\n",
+                            n.name.c_str(), a.center_point_box ? "[cx, cy, w, h]" : "[y1, x1, y2, x2]", a.has_max ? "from input 2" : "absent (no limit)", a.has_iou ? "from input 3" : "0",
+                            a.has_score ? "from input 4" : "0");
             }
         }
         {
