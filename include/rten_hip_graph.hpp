@@ -710,72 +710,60 @@ inline std::vector<int64_t> view_shape(const std::string &kind, const std::vecto
     }
     return shape; // Identity, Dropout
 }
-// ReduceMax / ReduceMin of a host value over sorted unique `axes` (shape arithmetic sometimes takes the extreme of a shape vector): NaN propagates, an empty
-// slice gives the identity (src/ops/reduce.rs:414-520, 876-1044)
-inline HostVal reduce_minmax(const HostVal &x, const std::vector<int> &axes, bool keep_dims, bool min) {
+// The walk the host reductions over sorted unique `axes` share (src/ops/reduce.rs:414-520): gives `y` its shape, calls init(n) with the number of output
+// elements, then fold(o, e) for every element e of `x` in row-major order, o being the output element whose slice holds it
+template <class Init, class Fold>
+inline void reduce_walk(const HostVal &x, const std::vector<int> &axes, bool keep_dims, HostVal &y, Init init, Fold fold) {
     const size_t nd = x.shape.size();
-    std::vector<int64_t> kept_stride(nd, 0);
+    std::vector<int64_t> kept_stride(nd, 0), idx(nd, 0);
+    auto reduced = [&](size_t d) { return std::find(axes.begin(), axes.end(), (int)d) != axes.end(); };
+    int64_t acc = 1;
+    for (size_t d = nd; d-- > 0;)
+        if (!reduced(d)) { kept_stride[d] = acc; acc *= x.shape[d]; }
+    for (size_t d = 0; d < nd; d++) {
+        if (!reduced(d)) y.shape.push_back(x.shape[d]);
+        else if (keep_dims) y.shape.push_back(1);
+    }
+    init((size_t)acc);
+    for (int64_t e = 0, n = x.len(); e < n; e++) {
+        int64_t o = 0;
+        for (size_t d = 0; d < nd; d++) o += idx[d] * kept_stride[d];
+        fold((size_t)o, (size_t)e);
+        for (size_t d = nd; d-- > 0;) { if (++idx[d] < x.shape[d]) break; idx[d] = 0; }
+    }
+}
+// ReduceMax / ReduceMin of a host value (shape arithmetic sometimes takes the extreme of a shape vector): NaN propagates, an empty slice gives the identity
+// (src/ops/reduce.rs:876-1044)
+inline HostVal reduce_minmax(const HostVal &x, const std::vector<int> &axes, bool keep_dims, bool min) {
     HostVal y;
     y.is_float = x.is_float;
-    int64_t acc = 1;
-    for (size_t d = nd; d-- > 0;) {
-        const bool red = std::find(axes.begin(), axes.end(), (int)d) != axes.end();
-        if (!red) { kept_stride[d] = acc; acc *= x.shape[d]; }
-    }
-    for (size_t d = 0; d < nd; d++) {
-        const bool red = std::find(axes.begin(), axes.end(), (int)d) != axes.end();
-        if (!red) y.shape.push_back(x.shape[d]);
-        else if (keep_dims) y.shape.push_back(1);
-    }
     const float fid = min ? std::numeric_limits<float>::infinity() : -std::numeric_limits<float>::infinity();
     const int64_t iid = min ? std::numeric_limits<int32_t>::max() : std::numeric_limits<int32_t>::min();
-    if (x.is_float) y.f.assign((size_t)acc, fid); else y.i.assign((size_t)acc, iid);
-    std::vector<int64_t> idx(nd, 0);
-    for (int64_t e = 0, n = x.len(); e < n; e++) {
-        int64_t o = 0;
-        for (size_t d = 0; d < nd; d++) o += idx[d] * kept_stride[d];
+    reduce_walk(x, axes, keep_dims, y, [&](size_t n) { if (x.is_float) y.f.assign(n, fid); else y.i.assign(n, iid); }, [&](size_t o, size_t e) {
         if (x.is_float) {
-            float &a = y.f[(size_t)o];
-            const float b = x.f[(size_t)e];
+            float &a = y.f[o];
+            const float b = x.f[e];
             if (a != a) {} else if (b != b) a = std::numeric_limits<float>::quiet_NaN(); else a = min ? std::min(a, b) : std::max(a, b);
         } else {
-            int64_t &a = y.i[(size_t)o];
-            a = min ? std::min(a, x.i[(size_t)e]) : std::max(a, x.i[(size_t)e]);
+            int64_t &a = y.i[o];
+            a = min ? std::min(a, x.i[e]) : std::max(a, x.i[e]);
         }
-        for (size_t d = nd; d-- > 0;) { if (++idx[d] < x.shape[d]) break; idx[d] = 0; }
-    }
+    });
     return y;
 }
-// int32 ReduceL1 / ReduceSumSquare / ReduceProd of a host value over sorted unique `axes` (dynamic-axes exports take ReduceProd of a Shape): two's complement
-// wrapping arithmetic, as the device kernels and the reference's generic kernels in a release build (src/ops/reduce.rs:782-794,1052-1057,1174-1181); an
-// empty slice gives 0 (Prod: 1).  `kind`: RTEN_HIP_REDUCE_L1 / _SUM_SQUARE / _PROD.
+// int32 ReduceL1 / ReduceSumSquare / ReduceProd of a host value (dynamic-axes exports take ReduceProd of a Shape): two's complement wrapping arithmetic,
+// as the device kernels and the reference's generic kernels in a release build (src/ops/reduce.rs:782-794,1052-1057,1174-1181); an empty slice gives 0
+// (Prod: 1).  `kind`: RTEN_HIP_REDUCE_L1 / _SUM_SQUARE / _PROD.
 inline HostVal reduce_i32(const HostVal &x, const std::vector<int> &axes, bool keep_dims, int kind) {
-    const size_t nd = x.shape.size();
-    std::vector<int64_t> kept_stride(nd, 0);
     HostVal y;
     y.is_float = false;
-    int64_t acc = 1;
-    for (size_t d = nd; d-- > 0;) {
-        const bool red = std::find(axes.begin(), axes.end(), (int)d) != axes.end();
-        if (!red) { kept_stride[d] = acc; acc *= x.shape[d]; }
-    }
-    for (size_t d = 0; d < nd; d++) {
-        const bool red = std::find(axes.begin(), axes.end(), (int)d) != axes.end();
-        if (!red) y.shape.push_back(x.shape[d]);
-        else if (keep_dims) y.shape.push_back(1);
-    }
-    std::vector<uint32_t> r((size_t)acc, kind == RTEN_HIP_REDUCE_PROD ? 1u : 0u);
-    std::vector<int64_t> idx(nd, 0);
-    for (int64_t e = 0, n = x.len(); e < n; e++) {
-        int64_t o = 0;
-        for (size_t d = 0; d < nd; d++) o += idx[d] * kept_stride[d];
-        const uint32_t v = (uint32_t)(int32_t)x.i[(size_t)e];
-        uint32_t &a = r[(size_t)o];
-        if (kind == RTEN_HIP_REDUCE_L1) a += (v & 0x80000000u) ? 0u - v : v;
-        else if (kind == RTEN_HIP_REDUCE_SUM_SQUARE) a += v * v;
-        else a *= v;
-        for (size_t d = nd; d-- > 0;) { if (++idx[d] < x.shape[d]) break; idx[d] = 0; }
-    }
+    std::vector<uint32_t> r;
+    reduce_walk(x, axes, keep_dims, y, [&](size_t n) { r.assign(n, kind == RTEN_HIP_REDUCE_PROD ? 1u : 0u); }, [&](size_t o, size_t e) {
+        const uint32_t v = (uint32_t)(int32_t)x.i[e];
+        if (kind == RTEN_HIP_REDUCE_L1) r[o] += (v & 0x80000000u) ? 0u - v : v;
+        else if (kind == RTEN_HIP_REDUCE_SUM_SQUARE) r[o] += v * v;
+        else r[o] *= v;
+    });
     for (uint32_t v : r) y.i.push_back((int64_t)(int32_t)v);
     return y;
 }
@@ -2390,7 +2378,7 @@ class Graph {
         return true;
     }
     // keepdims / noop_with_empty_axes / axes of a Reduce* node; axes come from the attribute or (ReduceSum: opset >= 13, the others: opset >= 18) from a constant input
-    template <class Op> void read_reduce_attrs(Step &st, const onnx::Node &n, Op &op) {
+    void read_reduce_attrs(Step &st, const onnx::Node &n, ReduceOp &op) {
         op.keep_dims = n.get_int("keepdims", 1) != 0;
         op.noop_with_empty_axes = n.get_int("noop_with_empty_axes", 0) != 0;
         op.axes = n.get_ints("axes", {});
@@ -3001,48 +2989,41 @@ class Graph {
     // shape vector: those run on the host); ReduceL2 / ReduceLogSum / ReduceLogSumExp.  Coupled to the batch exactly when dim 0 is reduced (read_reduce_attrs).
     void make_reduce_step(Step &st, const onnx::Node &n) {
         const std::string kind = n.op_type, nm = st.name;
+        std::shared_ptr<ReduceOp> op;
+        std::function<HostVal(const HostVal &, const std::vector<int> &)> host; // how a host value is reduced on the host, for the kinds shape arithmetic uses
+        bool host_floats = false;                                               // ... float values too, not only int32 ones
         if (kind == "ReduceSum" || kind == "ReduceMean") {
-            auto op = std::make_shared<ReduceSum>();
-            op->mean = kind == "ReduceMean";
-            read_reduce_attrs(st, n, *op);
-            st.run = [this, op, kind, nm](Context &c, const InputList &in) { for (int a : op->axes) note_axis(kind, nm, a, require(in, 0)); return op->run(c, in); };
-            return;
-        }
-        if (const int rk = reduce_family_kind(kind); rk >= 0) {
-            std::shared_ptr<Reduce> op;
+            auto o = std::make_shared<ReduceSum>();
+            o->mean = kind == "ReduceMean";
+            op = o;
+        } else if (const int rk = reduce_family_kind(kind); rk >= 0) {
+            std::shared_ptr<Reduce> o;
             switch (rk) {
-            case RTEN_HIP_REDUCE_L1: op = std::make_shared<ReduceL1>(); break;
-            case RTEN_HIP_REDUCE_SUM_SQUARE: op = std::make_shared<ReduceSumSquare>(); break;
-            case RTEN_HIP_REDUCE_L2: op = std::make_shared<ReduceL2>(); break;
-            case RTEN_HIP_REDUCE_LOG_SUM: op = std::make_shared<ReduceLogSum>(); break;
-            case RTEN_HIP_REDUCE_LOG_SUM_EXP: op = std::make_shared<ReduceLogSumExp>(); break;
-            default: op = std::make_shared<ReduceProd>(); break;
+            case RTEN_HIP_REDUCE_L1: o = std::make_shared<ReduceL1>(); break;
+            case RTEN_HIP_REDUCE_SUM_SQUARE: o = std::make_shared<ReduceSumSquare>(); break;
+            case RTEN_HIP_REDUCE_L2: o = std::make_shared<ReduceL2>(); break;
+            case RTEN_HIP_REDUCE_LOG_SUM: o = std::make_shared<ReduceLogSum>(); break;
+            case RTEN_HIP_REDUCE_LOG_SUM_EXP: o = std::make_shared<ReduceLogSumExp>(); break;
+            default: o = std::make_shared<ReduceProd>(); break;
             }
-            read_reduce_attrs(st, n, *op);
-            auto cache = std::make_shared<HostCache>();
-            st.run = [this, op, kind, nm, rk, cache](Context &c, const InputList &in) {
-                const Tensor &x = require(in, 0);
-                for (int a : op->axes) note_axis(kind, nm, a, x);
-                // shape arithmetic (ReduceProd of a Shape): int32 host values stay on the host
-                if (op->int32 && x.host() && !x.host()->is_float && x.ndim() > 0 && !(op->axes.empty() && op->noop_with_empty_axes)) {
-                    OutputList o;
-                    o.push_back(materialize(c, hostops::reduce_i32(*x.host(), resolve_axes(op->axes, x.ndim()), op->keep_dims, rk), *cache));
-                    return o;
-                }
-                return op->run(c, in);
-            };
-            return;
+            if (o->int32) host = [o, rk](const HostVal &x, const std::vector<int> &ax) { return hostops::reduce_i32(x, ax, o->keep_dims, rk); }; // ReduceProd of a Shape
+            op = o;
+        } else {
+            auto o = std::make_shared<ReduceMax>();
+            o->min = kind == "ReduceMin";
+            host = [o](const HostVal &x, const std::vector<int> &ax) { return hostops::reduce_minmax(x, ax, o->keep_dims, o->min); };
+            host_floats = true;
+            op = o;
         }
-        auto op = std::make_shared<ReduceMax>();
-        op->min = kind == "ReduceMin";
         read_reduce_attrs(st, n, *op);
         auto cache = std::make_shared<HostCache>();
-        st.run = [this, op, kind, nm, cache](Context &c, const InputList &in) {
+        st.run = [this, op, kind, nm, host, host_floats, cache](Context &c, const InputList &in) {
             const Tensor &x = require(in, 0);
             for (int a : op->axes) note_axis(kind, nm, a, x);
-            if (x.host() && x.ndim() > 0 && !(op->axes.empty() && op->noop_with_empty_axes)) { // shape arithmetic: on the host
+            // shape arithmetic stays on the host -- but not a 0-d value and not the no-op form, which are the operator's
+            if (host && x.host() && (host_floats || !x.host()->is_float) && x.ndim() > 0 && !(op->axes.empty() && op->noop_with_empty_axes)) {
                 OutputList o;
-                o.push_back(materialize(c, hostops::reduce_minmax(*x.host(), resolve_axes(op->axes, x.ndim()), op->keep_dims, op->min), *cache));
+                o.push_back(materialize(c, host(*x.host(), resolve_axes(op->axes, x.ndim())), *cache));
                 return o;
             }
             return op->run(c, in);

@@ -2693,21 +2693,34 @@ inline Tensor materialize(Context &ctx, const View &v, DType dt = DType::F32) { 
     return y;
 }
 
+// The dims of `v` outside `axes` (kept: `kshape`) and inside (reduced) as the merged shape + stride lists the strided reductions' ABI takes.  mos[0] and
+// mis[0] are v's own strides; mos[1 + k] are the kept dims' strides in `others[k]`, a full-rank stride list of another view of v's shape (TopK's outputs),
+// and kept dims merge only where every list agrees.  `too_many`: the refusal of more than 6 levels; nullptr leaves that to the caller.
+struct Split { Shape kshape, mo, mi; std::vector<Shape> mos, mis; };
+inline Split split_dims(const View &v, const std::vector<int> &axes, const std::vector<Shape> &others = {},
+                        const char *too_many = "more than 6 non-mergeable dims are not supported by the device path") {
+    Split r;
+    Shape rs, rst;
+    std::vector<Shape> kst(1 + others.size());
+    for (size_t d = 0; d < v.shape.size(); d++) {
+        if (std::find(axes.begin(), axes.end(), (int)d) != axes.end()) { rs.push_back(v.shape[d]); rst.push_back(v.strides[d]); continue; }
+        r.kshape.push_back(v.shape[d]);
+        kst[0].push_back(v.strides[d]);
+        for (size_t k = 0; k < others.size(); k++) kst[k + 1].push_back(others[k][d]);
+    }
+    merge_axes(r.kshape, kst, r.mo, r.mos);
+    merge_axes(rs, {rst}, r.mi, r.mis);
+    if (too_many && (r.mo.size() > 6 || r.mi.size() > 6)) throw OpError(OpError::UnsupportedValue, too_many);
+    return r;
+}
+
 // reduce_sum(view, axes, keep_dims = false): axes sorted and unique
 inline Tensor reduce_sum(Context &ctx, const View &v, const std::vector<int> &axes, bool mean = false) {
-    Shape ks, kst, rs, rst;
-    for (int d = 0; d < v.nd(); d++) {
-        const bool red = std::find(axes.begin(), axes.end(), d) != axes.end();
-        (red ? rs : ks).push_back(v.shape[(size_t)d]);
-        (red ? rst : kst).push_back(v.strides[(size_t)d]);
-    }
-    Tensor y(ctx, ks, DType::F32);
+    const Split d = split_dims(v, axes, {}, nullptr);
+    Tensor y(ctx, d.kshape, DType::F32);
     if (y.len()) {
-        Shape mo, mi; std::vector<Shape> mos, mis;
-        merge_axes(ks, {kst}, mo, mos);
-        merge_axes(rs, {rst}, mi, mis);
-        if (mo.size() > 6 || mi.size() > 6) throw OpError(OpError::UnsupportedValue, "Einsum reduction over more than 6 non-mergeable dims is not supported by the device path");
-        ctx.check((mean ? rten_hip_reduce_mean_strided_f32 : rten_hip_reduce_sum_strided_f32)(ctx.raw(), (int)mo.size(), mo.data(), mos[0].data(), (int)mi.size(), mi.data(), mis[0].data(), v.p, (float *)y.ptr()));
+        if (d.mo.size() > 6 || d.mi.size() > 6) throw OpError(OpError::UnsupportedValue, "Einsum reduction over more than 6 non-mergeable dims is not supported by the device path");
+        ctx.check((mean ? rten_hip_reduce_mean_strided_f32 : rten_hip_reduce_sum_strided_f32)(ctx.raw(), (int)d.mo.size(), d.mo.data(), d.mos[0].data(), (int)d.mi.size(), d.mi.data(), d.mis[0].data(), v.p, (float *)y.ptr()));
     }
     return y;
 }
@@ -2904,36 +2917,10 @@ inline Tensor run_step(Context &ctx, const Step &s, View x, const View *yin) {
 }
 } // namespace einsum_detail
 
-struct ReduceSum : Operator { // src/ops/reduce.rs:1126-1165 (f32); axes as the attribute (or the resolved second input)
-    std::vector<int> axes;
-    bool keep_dims = true, noop_with_empty_axes = false, mean = false;
-    const char *name() const override { return mean ? "ReduceMean" : "ReduceSum"; }
-    int max_inputs() const override { return 2; }
-    OutputList run(Context &ctx, const InputList &in) const override {
-        namespace E = einsum_detail;
-        const Tensor &x = want(require(in, 0), DType::F32, "float32");
-        const int nd = x.ndim();
-        OutputList out;
-        if ((axes.empty() && noop_with_empty_axes) || nd == 0) { out.push_back(E::materialize(ctx, E::View::of(x))); return out; }
-        const std::vector<int> ax = resolve_axes(axes, nd);
-        Tensor y = E::reduce_sum(ctx, E::View::of(x), ax, mean);
-        if (keep_dims) {
-            std::vector<int64_t> s = x.shape();
-            for (int a : ax) s[(size_t)a] = 1;
-            y.reshape(s);
-        }
-        out.push_back(std::move(y));
-        return out;
-    }
-};
-
-struct ReduceMean : ReduceSum { // src/ops/reduce.rs:523-580: Sum / len per slice
-    ReduceMean() { mean = true; }
-};
-
-// ------------------------------------------------------------------------------------------------ selection family
-// ReduceMax / ReduceMin / ArgMax / ArgMin / TopK (src/ops/reduce.rs:64-215, 876-1044, 1236-1356) of float32 and int32 tensors; index outputs are int32.
-// The kernels (rten_amd/csrc/select.hip) read the view in place through its strides and never report back to the host.
+// ------------------------------------------------------------------------------------------------ Reduce* and selection families
+// ReduceSum / ReduceMean (src/ops/reduce.rs:523-580, 1126-1165), ReduceMax / ReduceMin / ArgMax / ArgMin / TopK (:64-215, 876-1044, 1236-1356) and the six
+// kinds of rten_hip_reduce_strided.  ReduceSum is float32; the selection family takes float32 and int32 tensors; index outputs are int32.  The kernels
+// (rten_amd/csrc/reduce.hip, select.hip) read the view in place through its strides and never report back to the host.
 namespace select_detail {
 inline int32_t abi_dtype(const Tensor &x) { // map_value_view!(.., [FloatTensor, Int32Tensor], ..)
     if (x.dtype() == DType::F32) return RTEN_HIP_DT_F32;
@@ -2948,119 +2935,121 @@ inline std::vector<int64_t> host_ints(const Tensor &t) {
     for (int32_t e : t.to_host<int32_t>()) v.push_back(e);
     return v;
 }
-// kept / reduced dims of `v` as the merged shape + stride lists the ABI takes
-struct Split2 { einsum_detail::Shape kshape, mo, mi; std::vector<einsum_detail::Shape> mos, mis; };
-inline Split2 split_dims(const einsum_detail::View &v, const std::vector<int> &axes) {
-    namespace E = einsum_detail;
-    Split2 r;
-    E::Shape kst, rs, rst;
-    for (int d = 0; d < v.nd(); d++) {
-        const bool red = std::find(axes.begin(), axes.end(), d) != axes.end();
-        (red ? rs : r.kshape).push_back(v.shape[(size_t)d]);
-        (red ? rst : kst).push_back(v.strides[(size_t)d]);
-    }
-    E::merge_axes(r.kshape, {kst}, r.mo, r.mos);
-    E::merge_axes(rs, {rst}, r.mi, r.mis);
-    if (r.mo.size() > 6 || r.mi.size() > 6) throw OpError(OpError::UnsupportedValue, "more than 6 non-mergeable dims are not supported by the device path");
-    return r;
+// one value of type `out` per slice of `v` over the sorted unique axes `ax`, shaped as the kept dims; `launch(split, y)` calls the entry point
+template <class Launch>
+inline Tensor reduce_slices(Context &ctx, const einsum_detail::View &v, const std::vector<int> &ax, DType out, Launch launch) {
+    const einsum_detail::Split d = einsum_detail::split_dims(v, ax);
+    Tensor y(ctx, d.kshape, out);
+    if (y.len()) ctx.check(launch(d, y.ptr()));
+    return y;
+}
+// keep_dims: the reduced dims `ax` of `shape` come back with size 1
+inline void restore_kept_dims(Tensor &y, std::vector<int64_t> shape, const std::vector<int> &ax) {
+    for (int a : ax) shape[(size_t)a] = 1;
+    y.reshape(shape);
 }
 } // namespace select_detail
 
-struct ReduceMax : Operator { // src/ops/reduce.rs:977-1044; axes as the attribute or the second input
+// What the operators of reduce() (src/ops/reduce.rs:414-520) do differently around ReduceOp::run, each as the reference has it
+struct ReduceRules {
+    bool axes_input;  // a second input replaces the `axes` attribute.  Not ReduceSum / ReduceMean: theirs is resolved into the attribute by the graph executor
+    bool int32;       // Int32Tensor is taken too (the generic kernels: wrapping arithmetic, or a comparison)
+    bool typed_first; // the operand's type is checked before noop_with_empty_axes is looked at (map_value_view! / require_as outside the test,
+                      // reduce.rs:687,752,827,1215); otherwise only a reduction that runs checks it
+    bool cast_error;  // float32 only through require_as (its cast error) rather than map_value_view! (UnsupportedType)
+    enum Skipped { Copy, Abs, Square, Ln } skipped; // noop_with_empty_axes and no axes: the element map still applies -- x, |x| (reduce.rs:828-830),
+                                                    // x * x (:1216-1218), ln x (:688-690)
+    enum Rank0 { CopyUnchecked, CopyChecked, SliceOfOne } rank0; // a 0-d input: itself, without looking at the axes; itself, after the axes were
+                                                                 // validated (reduce.rs:425-428); the kernel's value for a slice of one element
+};
+
+struct ReduceOp : Operator {
     std::vector<int> axes;
-    bool keep_dims = true, noop_with_empty_axes = false, min = false;
-    const char *name() const override { return min ? "ReduceMin" : "ReduceMax"; }
+    bool keep_dims = true, noop_with_empty_axes = false;
     int max_inputs() const override { return 2; }
+    virtual ReduceRules rules() const = 0;
+    // one value per slice of `v` (a view of all of `x`) over the sorted unique axes `ax`, shaped as the kept dims
+    virtual Tensor reduce(Context &ctx, const Tensor &x, const einsum_detail::View &v, const std::vector<int> &ax) const = 0;
     OutputList run(Context &ctx, const InputList &in) const override {
         namespace E = einsum_detail;
-        namespace S = select_detail;
+        const ReduceRules r = rules();
         const Tensor &x = require(in, 0);
         std::vector<int> given = axes;
-        if (const Tensor *a = get(in, 1)) { given.clear(); for (int64_t e : S::host_ints(*a)) given.push_back((int)e); }
-        const int32_t dt = S::abi_dtype(x);
-        const int nd = x.ndim();
+        if (const Tensor *a = r.axes_input ? get(in, 1) : nullptr) { given.clear(); for (int64_t e : select_detail::host_ints(*a)) given.push_back((int)e); }
+        auto check_type = [&] {
+            if (x.dtype() == DType::F32 || (r.int32 && x.dtype() == DType::I32)) return;
+            if (r.cast_error) want(x, DType::F32, "float32");
+            throw OpError(OpError::UnsupportedType, "");
+        };
+        if (r.typed_first) check_type();
+        const E::View v = E::View::of(x);
         OutputList out;
-        if (given.empty() && noop_with_empty_axes) { out.push_back(E::materialize(ctx, E::View::of(x), x.dtype())); return out; }
-        if (nd == 0) { // a 0-d input returns itself (reduce.rs:425-428)
-            for (int a : given) resolve_axis(a, 0);
-            out.push_back(E::materialize(ctx, E::View::of(x), x.dtype()));
+        if (given.empty() && noop_with_empty_axes) {
+            if (dtype_size(x.dtype()) != 4) throw OpError(OpError::UnsupportedType, "");
+            InputList self{&x};
+            if (r.skipped == ReduceRules::Abs) return Abs().run(ctx, self);
+            if (r.skipped == ReduceRules::Ln) return Log().run(ctx, self);
+            if (r.skipped == ReduceRules::Square) out.push_back(broadcast_binary(ctx, x, x, 1, RTEN_HIP_EW_IMUL));
+            else out.push_back(E::materialize(ctx, v, x.dtype()));
             return out;
         }
-        const std::vector<int> ax = resolve_axes(given, nd);
-        const E::View v = E::View::of(x);
-        const S::Split2 d = S::split_dims(v, ax);
-        Tensor y(ctx, d.kshape, x.dtype());
-        if (y.len())
-            ctx.check(rten_hip_reduce_minmax_strided(ctx.raw(), min ? RTEN_HIP_SELECT_MIN : RTEN_HIP_SELECT_MAX, dt, (int)d.mo.size(), d.mo.data(), d.mos[0].data(),
-                                                     (int)d.mi.size(), d.mi.data(), d.mis[0].data(), v.p, y.ptr()));
-        if (keep_dims) {
-            std::vector<int64_t> s = x.shape();
-            for (int a : ax) s[(size_t)a] = 1;
-            y.reshape(s);
+        check_type();
+        const int nd = x.ndim();
+        if (nd == 0) {
+            if (r.rank0 != ReduceRules::CopyUnchecked) for (int a : given) resolve_axis(a, 0);
+            if (r.rank0 != ReduceRules::SliceOfOne) { out.push_back(E::materialize(ctx, v, x.dtype())); return out; }
         }
+        const std::vector<int> ax = nd ? resolve_axes(given, nd) : std::vector<int>();
+        Tensor y = reduce(ctx, x, v, ax);
+        if (keep_dims) select_detail::restore_kept_dims(y, x.shape(), ax);
         out.push_back(std::move(y));
         return out;
     }
 };
 
+struct ReduceSum : ReduceOp { // src/ops/reduce.rs:1126-1165 (f32)
+    bool mean = false;
+    const char *name() const override { return mean ? "ReduceMean" : "ReduceSum"; }
+    ReduceRules rules() const override { return {false, false, true, true, ReduceRules::Copy, ReduceRules::CopyUnchecked}; }
+    Tensor reduce(Context &ctx, const Tensor &, const einsum_detail::View &v, const std::vector<int> &ax) const override { return einsum_detail::reduce_sum(ctx, v, ax, mean); }
+};
+struct ReduceMean : ReduceSum { // src/ops/reduce.rs:523-580: Sum / len per slice
+    ReduceMean() { mean = true; }
+};
+
+struct ReduceMax : ReduceOp { // src/ops/reduce.rs:977-1044
+    bool min = false;
+    const char *name() const override { return min ? "ReduceMin" : "ReduceMax"; }
+    ReduceRules rules() const override { return {true, true, true, false, ReduceRules::Copy, ReduceRules::CopyChecked}; }
+    Tensor reduce(Context &ctx, const Tensor &x, const einsum_detail::View &v, const std::vector<int> &ax) const override {
+        return select_detail::reduce_slices(ctx, v, ax, x.dtype(), [&](const einsum_detail::Split &d, void *y) {
+            return rten_hip_reduce_minmax_strided(ctx.raw(), min ? RTEN_HIP_SELECT_MIN : RTEN_HIP_SELECT_MAX, select_detail::abi_dtype(x), (int)d.mo.size(), d.mo.data(),
+                                                  d.mos[0].data(), (int)d.mi.size(), d.mi.data(), d.mis[0].data(), v.p, y);
+        });
+    }
+};
 struct ReduceMin : ReduceMax { // src/ops/reduce.rs:907-975
     ReduceMin() { min = true; }
 };
 
 // ReduceL1 / ReduceSumSquare / ReduceL2 / ReduceLogSum / ReduceLogSumExp / ReduceProd (src/ops/reduce.rs:590-845, 1046-1100, 1167-1234) around one kernel
-// of rten_hip_reduce_strided (rten_amd/csrc/reduce.hip): axes as the attribute or the second input; a 0-d input is a slice of one element; an empty slice
-// gives the kernel's value for it.  With noop_with_empty_axes and no axes the reduction is skipped but the operator's element map still applies:
-// L1 |x|, SumSquare x * x, LogSum ln(x), the others a copy.
-struct Reduce : Operator {
+// of rten_hip_reduce_strided (rten_amd/csrc/reduce.hip); an empty slice gives the kernel's value for it.
+struct Reduce : ReduceOp {
     int kind;
     const char *nm;
-    bool int32;       // the reference also takes Int32Tensor (its generic kernels: wrapping arithmetic)
-    bool typed_first; // the operand's type is checked before noop_with_empty_axes is looked at (map_value_view! / require_as outside the test)
-    bool cast_error;  // float32 only through require_as (its cast error) rather than map_value_view! (UnsupportedType)
-    std::vector<int> axes;
-    bool keep_dims = true, noop_with_empty_axes = false;
+    bool int32, typed_first, cast_error; // as ReduceRules has them
     Reduce(int k, const char *n, bool i32, bool tf, bool ce) : kind(k), nm(n), int32(i32), typed_first(tf), cast_error(ce) {}
     const char *name() const override { return nm; }
-    int max_inputs() const override { return 2; }
-    void check_type(const Tensor &x) const {
-        if (x.dtype() == DType::F32 || (int32 && x.dtype() == DType::I32)) return;
-        if (cast_error) want(x, DType::F32, "float32");
-        throw OpError(OpError::UnsupportedType, "");
+    ReduceRules rules() const override {
+        const ReduceRules::Skipped skipped = kind == RTEN_HIP_REDUCE_L1 ? ReduceRules::Abs : kind == RTEN_HIP_REDUCE_SUM_SQUARE ? ReduceRules::Square
+                                             : kind == RTEN_HIP_REDUCE_LOG_SUM ? ReduceRules::Ln : ReduceRules::Copy;
+        return {true, int32, typed_first, cast_error, skipped, ReduceRules::SliceOfOne};
     }
-    OutputList run(Context &ctx, const InputList &in) const override {
-        namespace E = einsum_detail;
-        namespace S = select_detail;
-        const Tensor &x = require(in, 0);
-        std::vector<int> given = axes;
-        if (const Tensor *a = get(in, 1)) { given.clear(); for (int64_t e : S::host_ints(*a)) given.push_back((int)e); }
-        if (typed_first) check_type(x);
-        OutputList out;
-        if (given.empty() && noop_with_empty_axes) {
-            if (dtype_size(x.dtype()) != 4) throw OpError(OpError::UnsupportedType, "");
-            InputList self{&x};
-            if (kind == RTEN_HIP_REDUCE_L1) return Abs().run(ctx, self);
-            if (kind == RTEN_HIP_REDUCE_LOG_SUM) return Log().run(ctx, self);
-            if (kind == RTEN_HIP_REDUCE_SUM_SQUARE) out.push_back(broadcast_binary(ctx, x, x, 1, RTEN_HIP_EW_IMUL));
-            else out.push_back(E::materialize(ctx, E::View::of(x), x.dtype()));
-            return out;
-        }
-        check_type(x);
-        const int nd = x.ndim();
-        if (nd == 0) for (int a : given) resolve_axis(a, 0);
-        const std::vector<int> ax = nd ? resolve_axes(given, nd) : std::vector<int>();
-        const E::View v = E::View::of(x);
-        const S::Split2 d = S::split_dims(v, ax);
-        Tensor y(ctx, d.kshape, x.dtype());
-        if (y.len())
-            ctx.check(rten_hip_reduce_strided(ctx.raw(), kind, S::abi_dtype(x), (int)d.mo.size(), d.mo.data(), d.mos[0].data(), (int)d.mi.size(), d.mi.data(), d.mis[0].data(),
-                                              v.p, y.ptr()));
-        if (keep_dims) {
-            std::vector<int64_t> s = x.shape();
-            for (int a : ax) s[(size_t)a] = 1;
-            y.reshape(s);
-        }
-        out.push_back(std::move(y));
-        return out;
+    Tensor reduce(Context &ctx, const Tensor &x, const einsum_detail::View &v, const std::vector<int> &ax) const override {
+        return select_detail::reduce_slices(ctx, v, ax, x.dtype(), [&](const einsum_detail::Split &d, void *y) {
+            return rten_hip_reduce_strided(ctx.raw(), kind, select_detail::abi_dtype(x), (int)d.mo.size(), d.mo.data(), d.mos[0].data(), (int)d.mi.size(), d.mi.data(),
+                                           d.mis[0].data(), v.p, y);
+        });
     }
 };
 struct ReduceL1 : Reduce { ReduceL1() : Reduce(RTEN_HIP_REDUCE_L1, "ReduceL1", true, true, false) {} };                             // reduce.rs:775-845
@@ -3084,7 +3073,7 @@ struct LpNormalization : Operator {
         Tensor y(ctx, x.shape(), DType::F32);
         if (x.len()) {
             const E::View v = E::View::of(x);
-            const select_detail::Split2 d = select_detail::split_dims(v, {a});
+            const E::Split d = E::split_dims(v, {a});
             ctx.check(rten_hip_lp_normalize_f32(ctx.raw(), p, (int)d.mo.size(), d.mo.data(), d.mos[0].data(), v.shape[(size_t)a], v.strides[(size_t)a], v.p, (float *)y.ptr()));
         }
         OutputList out;
@@ -3104,14 +3093,11 @@ struct GlobalMaxPool : Operator {
         std::vector<int> ax;
         for (int d = 2; d < x.ndim(); d++) ax.push_back(d);
         const E::View v = E::View::of(x);
-        const select_detail::Split2 d = select_detail::split_dims(v, ax);
-        std::vector<int64_t> s(x.shape().size(), 1);
-        s[0] = x.size(0);
-        s[1] = x.size(1);
-        Tensor y(ctx, s, DType::F32);
-        if (y.len())
-            ctx.check(rten_hip_reduce_minmax_strided(ctx.raw(), RTEN_HIP_SELECT_MAX, RTEN_HIP_DT_F32, (int)d.mo.size(), d.mo.data(), d.mos[0].data(), (int)d.mi.size(), d.mi.data(),
-                                                     d.mis[0].data(), v.p, y.ptr()));
+        Tensor y = select_detail::reduce_slices(ctx, v, ax, DType::F32, [&](const E::Split &d, void *yp) {
+            return rten_hip_reduce_minmax_strided(ctx.raw(), RTEN_HIP_SELECT_MAX, RTEN_HIP_DT_F32, (int)d.mo.size(), d.mo.data(), d.mos[0].data(), (int)d.mi.size(), d.mi.data(),
+                                                  d.mis[0].data(), v.p, yp);
+        });
+        select_detail::restore_kept_dims(y, x.shape(), ax);
         OutputList out;
         out.push_back(std::move(y));
         return out;
@@ -3131,16 +3117,11 @@ struct ArgMax : Operator { // src/ops/reduce.rs:64-160: the FIRST NaN of a lane 
         const int a = resolve_axis(axis, x.ndim());
         if (x.size(a) == 0) throw OpError(OpError::InvalidValue, "Cannot select index from empty sequence");
         const E::View v = E::View::of(x);
-        const S::Split2 d = S::split_dims(v, {a});
-        Tensor y(ctx, d.kshape, DType::I32);
-        if (y.len())
-            ctx.check(rten_hip_arg_minmax_strided(ctx.raw(), min ? RTEN_HIP_SELECT_MIN : RTEN_HIP_SELECT_MAX, dt, (int)d.mo.size(), d.mo.data(), d.mos[0].data(),
-                                                  v.shape[(size_t)a], v.strides[(size_t)a], v.p, (int32_t *)y.ptr()));
-        if (keep_dims) {
-            std::vector<int64_t> s = x.shape();
-            s[(size_t)a] = 1;
-            y.reshape(s);
-        }
+        Tensor y = S::reduce_slices(ctx, v, {a}, DType::I32, [&](const E::Split &d, void *yp) {
+            return rten_hip_arg_minmax_strided(ctx.raw(), min ? RTEN_HIP_SELECT_MIN : RTEN_HIP_SELECT_MAX, dt, (int)d.mo.size(), d.mo.data(), d.mos[0].data(),
+                                               v.shape[(size_t)a], v.strides[(size_t)a], v.p, (int32_t *)yp);
+        });
+        if (keep_dims) S::restore_kept_dims(y, x.shape(), {a});
         OutputList out;
         out.push_back(std::move(y));
         return out;
@@ -3177,13 +3158,8 @@ struct TopK : Operator {
         if (k > x.size(a)) throw OpError(OpError::InvalidValue, "k > dimension size");
         if (out[0].len()) {
             const E::View v = E::View::of(x), ov = E::View::of(out[0]);
-            E::Shape ks, kst, kost, mo;
-            std::vector<E::Shape> mos;
-            for (int d = 0; d < v.nd(); d++)
-                if (d != a) { ks.push_back(v.shape[(size_t)d]); kst.push_back(v.strides[(size_t)d]); kost.push_back(ov.strides[(size_t)d]); }
-            E::merge_axes(ks, {kst, kost}, mo, mos);
-            if (mo.size() > 6) throw OpError(OpError::UnsupportedValue, "more than 6 non-mergeable dims are not supported by the device path");
-            ctx.check(rten_hip_topk_strided(ctx.raw(), largest ? 1 : 0, dt, (int)mo.size(), mo.data(), mos[0].data(), mos[1].data(), v.shape[(size_t)a],
+            const E::Split d = E::split_dims(v, {a}, {ov.strides});
+            ctx.check(rten_hip_topk_strided(ctx.raw(), largest ? 1 : 0, dt, (int)d.mo.size(), d.mo.data(), d.mos[0].data(), d.mos[1].data(), v.shape[(size_t)a],
                                             v.strides[(size_t)a], k, v.p, out[0].ptr(), (int32_t *)out[1].ptr(), ov.strides[(size_t)a]));
         }
         return out;

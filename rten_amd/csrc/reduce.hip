@@ -16,6 +16,7 @@
 
 #include "internal.h"
 #include "rowreduce.h" // lane_bcast, simd16_reduce: the reduction order
+#include "slice.h"     // the kept / reduced levels and their addressing
 #include "vecmath.h"
 
 namespace {
@@ -23,48 +24,11 @@ namespace {
 constexpr int ROWS_PER_BLOCK = 4;
 
 struct ReduceArgs {
-    int n_outer, n_inner;
+    SliceLevels<1> kept, red;
     int64_t rows;
     int inner;
     float divisor; // 0: the plain value; slice length: ReduceMean = Sum / len (reduce.rs:532-537)
-    int32_t oshape[6], ishape[6];
-    int64_t ostride[6], istride[6];
 };
-
-// (The outermost kept axis needs no division -- what is left of the row index IS its coordinate -- and a 64-bit division is ~100 instructions on this
-// machine: with one per row the last-axis kernels were division-bound, 10 us for 49152 rows of 128.  32-bit arithmetic whenever the row count allows.)
-__device__ __forceinline__ int64_t reduce_row_base(const ReduceArgs &p, int64_t row) {
-    if (p.n_outer <= 0) return 0;
-    int64_t off = 0;
-    if (p.rows <= 0x7fffffff) {
-        unsigned r = (unsigned)row;
-        for (int d = p.n_outer - 1; d > 0; d--) {
-            const unsigned q = r / (unsigned)p.oshape[d];
-            off += (int64_t)(r - q * (unsigned)p.oshape[d]) * p.ostride[d];
-            r = q;
-        }
-        return off + (int64_t)r * p.ostride[0];
-    }
-    int64_t r = row;
-    for (int d = p.n_outer - 1; d > 0; d--) {
-        const int64_t q = r / p.oshape[d];
-        off += (r - q * p.oshape[d]) * p.ostride[d];
-        r = q;
-    }
-    return off + r * p.ostride[0];
-}
-
-__device__ __forceinline__ int64_t reduce_elem_off(const ReduceArgs &p, int i) {
-    if (p.n_inner == 1) return (int64_t)i * p.istride[0];
-    int r = i;
-    int64_t off = 0;
-    for (int d = p.n_inner - 1; d >= 0; d--) {
-        const int q = r / p.ishape[d];
-        off += (int64_t)(r - q * p.ishape[d]) * p.istride[d];
-        r = q;
-    }
-    return off;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Sum / SumAbs / SumSquare in the fold_unroll<4> order.  MAP is simd16_reduce's KIND (the fold of one element into its accumulator); the accumulators are
@@ -93,8 +57,8 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void reduce_sum_kernel(const R
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (row >= p.rows) return;
-    const float *xr = x + reduce_row_base(p, row);
-    auto get = [&](int i) -> float { return xr[reduce_elem_off(p, i)]; };
+    const float *xr = x + slice_row_base(p.kept, p.rows, row);
+    auto get = [&](int i) -> float { return xr[slice_elem_off(p.red, i)]; };
     const float s = simd16_reduce<MAP>(get, p.inner, 0.f, lane);
     if (lane == 0) y[row] = finish_total<FIN>(s, p.divisor);
 }
@@ -108,10 +72,10 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void reduce_sum_rows16_kernel(
     const int lane = threadIdx.x & 63, l = lane & 15;
     const int64_t row = ((int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6)) * 4 + (lane >> 4);
     const int64_t rr = row < p.rows ? row : p.rows - 1;
-    const float *xr = x + reduce_row_base(p, rr);
+    const float *xr = x + slice_row_base(p.kept, p.rows, rr);
     float v[EPL];
 #pragma unroll
-    for (int q = 0; q < EPL; q++) v[q] = xr[reduce_elem_off(p, l + 16 * q < p.inner ? l + 16 * q : 0)];
+    for (int q = 0; q < EPL; q++) v[q] = xr[slice_elem_off(p.red, l + 16 * q < p.inner ? l + 16 * q : 0)];
     const int unrolled = (p.inner >> 6) * 4;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -135,7 +99,7 @@ template <int MAP, int FIN>
 __global__ __launch_bounds__(1024) void reduce_sum_cols_kernel(const ReduceArgs p, const float *__restrict__ x, float *__restrict__ y) {
     __shared__ float part[16][16];
     const int lane = threadIdx.x & 63, l = threadIdx.x >> 6, u = lane >> 4, j = lane & 15;
-    const int last = p.oshape[p.n_outer - 1];
+    const int last = p.kept.shape[p.kept.n - 1];
     const int groups = (last + 15) >> 4;
     // Two neighbouring column groups read the two 64-byte halves of the same 128-byte lines.  Workgroup ids go round-robin over the eight XCDs, so
     // neighbours in id order never share an L2 and every line is fetched twice; here each XCD gets a CONTIGUOUS run of groups (ids id, id + 8, ...
@@ -149,7 +113,7 @@ __global__ __launch_bounds__(1024) void reduce_sum_cols_kernel(const ReduceArgs 
     const int j0 = (int)(bid - prefix * groups) * 16;
     const int jj = j0 + j < last ? j0 + j : last - 1;
     const int64_t row = prefix * last + jj;
-    const float *xr = x + reduce_row_base(p, row);
+    const float *xr = x + slice_row_base(p.kept, p.rows, row);
     const int n = p.inner, full4 = n >> 6;
     // The chain of adds is the reference's (one accumulator, elements in order); the LOADS are independent, so eight are requested before the
     // first add -- a load per add made this kernel one memory round trip per element (31.5 us for 4096 x 3072 -> 3072: round 3).
@@ -158,25 +122,25 @@ __global__ __launch_bounds__(1024) void reduce_sum_cols_kernel(const ReduceArgs 
     for (; c + 16 <= full4; c += 16) {
         float tv[16];
 #pragma unroll
-        for (int k = 0; k < 16; k++) tv[k] = xr[reduce_elem_off(p, (c + k) * 64 + u * 16 + l)];
+        for (int k = 0; k < 16; k++) tv[k] = xr[slice_elem_off(p.red, (c + k) * 64 + u * 16 + l)];
 #pragma unroll
         for (int k = 0; k < 16; k++) acc = fold_elem<MAP>(acc, tv[k]);
     }
     for (; c + 8 <= full4; c += 8) {
         float tv[8];
 #pragma unroll
-        for (int k = 0; k < 8; k++) tv[k] = xr[reduce_elem_off(p, (c + k) * 64 + u * 16 + l)];
+        for (int k = 0; k < 8; k++) tv[k] = xr[slice_elem_off(p.red, (c + k) * 64 + u * 16 + l)];
 #pragma unroll
         for (int k = 0; k < 8; k++) acc = fold_elem<MAP>(acc, tv[k]);
     }
-    for (; c < full4; c++) acc = fold_elem<MAP>(acc, xr[reduce_elem_off(p, c * 64 + u * 16 + l)]);
+    for (; c < full4; c++) acc = fold_elem<MAP>(acc, xr[slice_elem_off(p.red, c * 64 + u * 16 + l)]);
     float a = lane_bcast(acc, j);
     a = a + lane_bcast(acc, j + 16);
     a = a + lane_bcast(acc, j + 32);
     a = a + lane_bcast(acc, j + 48);
     int i0 = full4 * 64;
-    for (; i0 + 16 <= n; i0 += 16) a = fold_elem<MAP>(a, xr[reduce_elem_off(p, i0 + l)]);
-    if (i0 + l < n) a = fold_elem<MAP>(a, xr[reduce_elem_off(p, i0 + l)]);
+    for (; i0 + 16 <= n; i0 += 16) a = fold_elem<MAP>(a, xr[slice_elem_off(p.red, i0 + l)]);
+    if (i0 + l < n) a = fold_elem<MAP>(a, xr[slice_elem_off(p.red, i0 + l)]);
     if (u == 0) part[l][j] = a;
     __syncthreads();
     if (threadIdx.x < 16 && j0 + (int)threadIdx.x < last) {
@@ -189,15 +153,15 @@ __global__ __launch_bounds__(1024) void reduce_sum_cols_kernel(const ReduceArgs 
 
 // The reduced axes are strided and the innermost kept axis is contiguous, with enough of it for 16 adjacent outputs: the column forms' condition.
 bool column_layout(const ReduceArgs &p) {
-    const int64_t last = p.n_outer ? p.oshape[p.n_outer - 1] : 1;
-    return p.inner > 64 && p.n_outer && p.ostride[p.n_outer - 1] == 1 && last >= 16 && p.istride[p.n_inner - 1] > 1;
+    const int64_t last = p.kept.n ? p.kept.shape[p.kept.n - 1] : 1;
+    return p.inner > 64 && p.kept.n && p.kept.stride[0][p.kept.n - 1] == 1 && last >= 16 && p.red.stride[0][p.red.n - 1] > 1;
 }
 
 template <int MAP, int FIN>
 void launch_sum(rten_hip_ctx *ctx, const ReduceArgs &p, const float *x, float *y) {
     const dim3 block(64 * ROWS_PER_BLOCK);
     const dim3 grid16((unsigned)((p.rows + 4 * ROWS_PER_BLOCK - 1) / (4 * ROWS_PER_BLOCK)));
-    const int64_t last = p.n_outer ? p.oshape[p.n_outer - 1] : 1;
+    const int64_t last = p.kept.n ? p.kept.shape[p.kept.n - 1] : 1;
     if (column_layout(p))
         hipLaunchKernelGGL((reduce_sum_cols_kernel<MAP, FIN>), dim3((unsigned)(p.rows / last * ((last + 15) / 16))), dim3(1024), 0, ctx->stream, p, x, y);
     else if (p.inner <= 64) hipLaunchKernelGGL((reduce_sum_rows16_kernel<4, MAP, FIN>), grid16, block, 0, ctx->stream, p, x, y);
@@ -218,7 +182,7 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void reduce_lse_kernel(const R
     const int lane = threadIdx.x & 63, l = lane & 15;
     const int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (row >= p.rows) return;
-    const float *xr = x + reduce_row_base(p, row);
+    const float *xr = x + slice_row_base(p.kept, p.rows, row);
     const int n = p.inner;
     [[maybe_unused]] float v[CH > 0 ? CH : 1];
     float mx = -__builtin_inff();
@@ -227,14 +191,14 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void reduce_lse_kernel(const R
 #pragma unroll
         for (int k = 0; k < CH; k++) {
             const int i = k * 64 + lane;
-            v[k] = xr[reduce_elem_off(p, i < n ? i : 0)];
+            v[k] = xr[slice_elem_off(p.red, i < n ? i : 0)];
         }
 #pragma unroll
         for (int k = 0; k < CH; k++)
             if (k * 64 + lane < n) { nan = nan || v[k] != v[k]; mx = fmaxf(mx, v[k]); }
     } else {
         for (int i = lane; i < n; i += 64) {
-            const float t = xr[reduce_elem_off(p, i)];
+            const float t = xr[slice_elem_off(p.red, i)];
             nan = nan || t != t;
             mx = fmaxf(mx, t);
         }
@@ -259,7 +223,7 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void reduce_lse_kernel(const R
         const int nch = (n + 63) / 64;
         for (int k = 0; k < nch; k++) {
             const int i = k * 64 + lane;
-            add_chunk(k, vm::exp_full(xr[reduce_elem_off(p, i < n ? i : 0)] - m));
+            add_chunk(k, vm::exp_full(xr[slice_elem_off(p.red, i < n ? i : 0)] - m));
         }
     }
     float s = 0.f;
@@ -279,18 +243,18 @@ constexpr int PROD_BATCH = 16;
 __global__ __launch_bounds__(64) void reduce_prod_cols_kernel(const ReduceArgs p, const float *__restrict__ x, float *__restrict__ y) {
     const int64_t row = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (row >= p.rows) return;
-    const float *xr = x + reduce_row_base(p, row);
+    const float *xr = x + slice_row_base(p.kept, p.rows, row);
     const int n = p.inner;
     float acc = 1.0f;
     int i = 0;
     for (; i + PROD_BATCH <= n; i += PROD_BATCH) {
         float tv[PROD_BATCH];
 #pragma unroll
-        for (int k = 0; k < PROD_BATCH; k++) tv[k] = xr[reduce_elem_off(p, i + k)];
+        for (int k = 0; k < PROD_BATCH; k++) tv[k] = xr[slice_elem_off(p.red, i + k)];
 #pragma unroll
         for (int k = 0; k < PROD_BATCH; k++) acc = acc * tv[k];
     }
-    for (; i < n; i++) acc = acc * xr[reduce_elem_off(p, i)];
+    for (; i < n; i++) acc = acc * xr[slice_elem_off(p.red, i)];
     y[row] = acc;
 }
 
@@ -305,13 +269,13 @@ __global__ __launch_bounds__(64) void reduce_prod_rows_kernel(const ReduceArgs p
     const int n = p.inner;
     float acc = 1.0f;
     for (int i0 = 0; i0 < n; i0 += 64) {
-        const int64_t eo = reduce_elem_off(p, i0 + t < n ? i0 + t : 0);
+        const int64_t eo = slice_elem_off(p.red, i0 + t < n ? i0 + t : 0);
         for (int k0 = 0; k0 < nrows; k0 += 16) {
             float tv[16];
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 const int r = k0 + k < nrows ? k0 + k : nrows - 1;
-                tv[k] = x[reduce_row_base(p, row0 + r) + eo];
+                tv[k] = x[slice_row_base(p.kept, p.rows, row0 + r) + eo];
             }
 #pragma unroll
             for (int k = 0; k < 16; k++) tile[k0 + k][t] = tv[k];
@@ -345,10 +309,10 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void reduce_i32_kernel(const R
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (row >= p.rows) return;
-    const uint32_t *xr = x + reduce_row_base(p, row);
+    const uint32_t *xr = x + slice_row_base(p.kept, p.rows, row);
     uint32_t acc = IOP == IOP_PROD ? 1u : 0u;
     for (int i = lane; i < p.inner; i += 64) {
-        const uint32_t t = xr[reduce_elem_off(p, i)];
+        const uint32_t t = xr[slice_elem_off(p.red, i)];
         if constexpr (IOP == IOP_ABS) acc += (t & 0x80000000u) ? 0u - t : t; // `if x < 0 { -x }`: i32::MIN stays (wrapping)
         else if constexpr (IOP == IOP_SQUARE) acc += t * t;
         else acc *= t;
@@ -370,29 +334,17 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void reduce_i32_kernel(const R
 //            before the wave's first store, and the second pass reads each element before it stores it.
 // ------------------------------------------------------------------------------------------------
 struct LpArgs {
-    int n_outer;
+    SliceLevels<1> kept;
     int64_t rows;
     int64_t len, stride;
-    int32_t oshape[6];
-    int64_t ostride[6];
 };
-
-__device__ __forceinline__ int64_t lp_row_base(const LpArgs &p, int64_t row) {
-    int64_t off = 0, r = row;
-    for (int d = p.n_outer - 1; d > 0; d--) {
-        const int64_t q = r / p.oshape[d];
-        off += (r - q * p.oshape[d]) * p.ostride[d];
-        r = q;
-    }
-    return p.n_outer > 0 ? off + r * p.ostride[0] : 0;
-}
 
 template <int CH, int MAP>
 __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void lp_normalize_kernel(const LpArgs p, const float *x, float *y) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (row >= p.rows) return;
-    const int64_t base = lp_row_base(p, row);
+    const int64_t base = slice_row_base(p.kept, p.rows, row);
     const float *xr = x + base;
     float *yr = y + base;
     const int64_t n = p.len, st = p.stride;
@@ -436,40 +388,11 @@ __global__ __launch_bounds__(64 * ROWS_PER_BLOCK) void lp_normalize_kernel(const
     }
 }
 
-// kept dims / reduced dims of a strided view as the kernels take them; `what` names the entry point in the messages
-int32_t fill_reduce_args(rten_hip_ctx *ctx, const char *what, ReduceArgs &p, int32_t n_outer, const int64_t *outer_shape, const int64_t *outer_strides,
-                         int32_t n_inner, const int64_t *inner_shape, const int64_t *inner_strides) {
-    if (n_outer < 0 || n_outer > 6 || n_inner < 0 || n_inner > 6 || (n_outer && (!outer_shape || !outer_strides)) ||
-        (n_inner && (!inner_shape || !inner_strides)))
-        return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "%s: at most 6 kept and 6 reduced dims", what);
-    p = ReduceArgs();
-    p.n_outer = n_outer;
-    p.n_inner = n_inner > 0 ? n_inner : 1;
-    p.rows = 1;
-    int64_t inner = 1;
-    for (int d = 0; d < n_outer; d++) {
-        if (outer_shape[d] < 0 || outer_shape[d] > 0x7fffffff || outer_strides[d] < 0) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "%s: bad dimension", what);
-        p.oshape[d] = (int32_t)outer_shape[d];
-        p.ostride[d] = outer_strides[d];
-        p.rows *= outer_shape[d];
-    }
-    p.ishape[0] = 1;
-    for (int d = 0; d < n_inner; d++) {
-        if (inner_shape[d] < 0 || inner_strides[d] < 0) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "%s: bad dimension", what);
-        inner *= inner_shape[d];
-        if (inner > 0x7fffffff) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "%s: reduced slice longer than 2^31 - 1", what);
-        p.ishape[d] = (int32_t)inner_shape[d];
-        p.istride[d] = inner_strides[d];
-    }
-    p.inner = (int)inner;
-    return RTEN_HIP_OK;
-}
-
 int32_t reduce_sum_or_mean(rten_hip_ctx *ctx, bool mean, int32_t n_outer, const int64_t *outer_shape, const int64_t *outer_strides, int32_t n_inner,
                            const int64_t *inner_shape, const int64_t *inner_strides, const float *x, float *y) {
     RTEN_CHECK_CTX(ctx);
-    ReduceArgs p;
-    if (int32_t rc = fill_reduce_args(ctx, "reduce_sum", p, n_outer, outer_shape, outer_strides, n_inner, inner_shape, inner_strides)) return rc;
+    ReduceArgs p = {};
+    if (int32_t rc = slice_fill(ctx, "reduce_sum", n_outer, outer_shape, {outer_strides}, p.kept, p.rows, n_inner, inner_shape, inner_strides, &p.red, &p.inner)) return rc;
     p.divisor = mean ? (float)p.inner : 0.f;
     if (p.rows == 0) return RTEN_HIP_OK;
     if (!y) return RTEN_HIP_ERR_INVALID_VALUE;
@@ -507,8 +430,8 @@ RTEN_EXPORT int32_t rten_hip_reduce_strided(rten_hip_ctx *ctx, int32_t kind, int
     const bool i32 = dtype == RTEN_HIP_DT_I32;
     if (i32 && (kind == RTEN_HIP_REDUCE_L2 || kind == RTEN_HIP_REDUCE_LOG_SUM || kind == RTEN_HIP_REDUCE_LOG_SUM_EXP))
         return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "reduce: kind %d takes float32 only", kind);
-    ReduceArgs p;
-    if (int32_t rc = fill_reduce_args(ctx, "reduce", p, n_outer, outer_shape, outer_strides, n_inner, inner_shape, inner_strides)) return rc;
+    ReduceArgs p = {};
+    if (int32_t rc = slice_fill(ctx, "reduce", n_outer, outer_shape, {outer_strides}, p.kept, p.rows, n_inner, inner_shape, inner_strides, &p.red, &p.inner)) return rc;
     if (p.rows == 0) return RTEN_HIP_OK;
     if (!yv) return RTEN_HIP_ERR_INVALID_VALUE;
     if (p.inner == 0) { // the kernel's value for an empty slice (reduce.rs:446-452): sums 0, Prod 1, LogSum ln(0) = -inf, LogSumExp MaxNum's -inf
@@ -551,7 +474,7 @@ RTEN_EXPORT int32_t rten_hip_reduce_strided(rten_hip_ctx *ctx, int32_t kind, int
     }
     default: {
         const dim3 grid((unsigned)((p.rows + 63) / 64));
-        const bool cols = p.n_outer && p.ostride[p.n_outer - 1] == 1 && p.oshape[p.n_outer - 1] >= 16 && p.istride[p.n_inner - 1] > 1;
+        const bool cols = p.kept.n && p.kept.stride[0][p.kept.n - 1] == 1 && p.kept.shape[p.kept.n - 1] >= 16 && p.red.stride[0][p.red.n - 1] > 1;
         if (cols) hipLaunchKernelGGL(reduce_prod_cols_kernel, grid, dim3(64), 0, ctx->stream, p, x, y);
         else hipLaunchKernelGGL(reduce_prod_rows_kernel, grid, dim3(64), 0, ctx->stream, p, x, y);
         break;
@@ -565,20 +488,11 @@ RTEN_EXPORT int32_t rten_hip_lp_normalize_f32(rten_hip_ctx *ctx, int32_t p_norm,
                                               int64_t axis_len, int64_t axis_stride, const float *x, float *y) {
     RTEN_CHECK_CTX(ctx);
     if (p_norm != 1 && p_norm != 2) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "`p` must be 1 or 2");
-    if (n_outer < 0 || n_outer > 6 || (n_outer && (!outer_shape || !outer_strides)))
-        return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "lp_normalize: at most 6 kept dims");
-    if (axis_len < 0 || axis_stride < 0) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "lp_normalize: bad dimension");
     LpArgs p = {};
-    p.n_outer = n_outer;
-    p.rows = 1;
+    if (int32_t rc = slice_fill(ctx, "lp_normalize", n_outer, outer_shape, {outer_strides}, p.kept, p.rows)) return rc;
+    if (axis_len < 0 || axis_stride < 0) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "lp_normalize: bad dimension");
     p.len = axis_len;
     p.stride = axis_stride;
-    for (int d = 0; d < n_outer; d++) {
-        if (outer_shape[d] < 0 || outer_shape[d] > 0x7fffffff || outer_strides[d] < 0) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "lp_normalize: bad dimension");
-        p.oshape[d] = (int32_t)outer_shape[d];
-        p.ostride[d] = outer_strides[d];
-        p.rows *= outer_shape[d];
-    }
     if (p.rows == 0 || axis_len == 0) return RTEN_HIP_OK; // norm.rs:711-713
     if (!x || !y) return RTEN_HIP_ERR_INVALID_VALUE;
     const int64_t blocks = (p.rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;

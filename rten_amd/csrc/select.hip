@@ -12,6 +12,7 @@
 //     input by the selected index, so they keep their bits (sign of zero, NaN payload).
 // Nothing is packed: lanes are read through the view's strides.  No kernel uses scratch registers; every store is a vector store.
 #include "internal.h"
+#include "slice.h" // the kept / reduced levels and their addressing
 
 namespace {
 
@@ -19,48 +20,13 @@ constexpr int WAVES_PER_BLOCK = 4;
 constexpr unsigned NAN_KEY = 0xffffffffu;
 
 struct SelArgs {
-    int n_outer, n_inner;
+    SliceLevels<1> kept, red;
     int64_t rows;  // output elements (lanes)
     int inner;     // reduced slice length, < 2^31
     int chunk;     // two-pass form: elements per partial (a multiple of 4); otherwise == inner
     int nchunks;   // partials per row (1: the kernel writes the decoded result)
     unsigned flip; // 0: max, 0xffffffff: min (xor on the key of a number)
-    int32_t oshape[6], ishape[6];
-    int64_t ostride[6], istride[6];
 };
-
-__device__ __forceinline__ int64_t sel_row_base(const SelArgs &p, int64_t row) {
-    if (p.n_outer <= 0) return 0;
-    int64_t off = 0;
-    if (p.rows <= 0x7fffffff) { // (a 64-bit division is ~100 instructions here: 32-bit arithmetic whenever the row count allows)
-        unsigned r = (unsigned)row;
-        for (int d = p.n_outer - 1; d > 0; d--) {
-            const unsigned q = r / (unsigned)p.oshape[d];
-            off += (int64_t)(r - q * (unsigned)p.oshape[d]) * p.ostride[d];
-            r = q;
-        }
-        return off + (int64_t)r * p.ostride[0];
-    }
-    int64_t r = row;
-    for (int d = p.n_outer - 1; d > 0; d--) {
-        const int64_t q = r / p.oshape[d];
-        off += (r - q * p.oshape[d]) * p.ostride[d];
-        r = q;
-    }
-    return off + r * p.ostride[0];
-}
-
-__device__ __forceinline__ int64_t sel_elem_off(const SelArgs &p, int i) {
-    if (p.n_inner == 1) return (int64_t)i * p.istride[0];
-    int r = i;
-    int64_t off = 0;
-    for (int d = p.n_inner - 1; d >= 0; d--) {
-        const int q = r / p.ishape[d];
-        off += (int64_t)(r - q * p.ishape[d]) * p.istride[d];
-        r = q;
-    }
-    return off;
-}
 
 // ---- keys
 // CANON: -0 takes +0's key (operators whose comparison says the two are equal).  ReduceMax / ReduceMin keep them apart (-0 < +0): either zero is right
@@ -150,7 +116,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void select_rows_kernel(const
     const int64_t row = p.nchunks > 1 ? uu / p.nchunks : uu;
     const int c = p.nchunks > 1 ? (int)(uu - row * p.nchunks) : 0;
     const int i0 = c * p.chunk, i1 = (p.inner - i0 < p.chunk) ? p.inner : i0 + p.chunk;
-    const unsigned *xr = x + sel_row_base(p, row);
+    const unsigned *xr = x + slice_row_base(p.kept, p.rows, row);
     T acc = KT::identity();
     if (VEC) {
         const int v1 = i0 + ((i1 - i0) & ~3);
@@ -181,11 +147,11 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void select_rows_kernel(const
         for (; i + 3 * LPR < i1; i += 4 * LPR) { // four independent loads in flight per lane
             unsigned v[4];
 #pragma unroll
-            for (int q = 0; q < 4; q++) v[q] = xr[sel_elem_off(p, i + q * LPR)];
+            for (int q = 0; q < 4; q++) v[q] = xr[slice_elem_off(p.red, i + q * LPR)];
 #pragma unroll
             for (int q = 0; q < 4; q++) acc = kmax(acc, KT::make(v[q], i + q * LPR, p.flip));
         }
-        for (; i < i1; i += LPR) acc = kmax(acc, KT::make(xr[sel_elem_off(p, i)], i, p.flip));
+        for (; i < i1; i += LPR) acc = kmax(acc, KT::make(xr[slice_elem_off(p.red, i)], i, p.flip));
     }
     acc = group_max<LPR>(acc);
     if (l == 0 && unit < units) {
@@ -214,7 +180,7 @@ template <class KT>
 __global__ __launch_bounds__(1024) void select_cols_kernel(const SelArgs p, int cw, const unsigned *__restrict__ x, unsigned *__restrict__ y) {
     typedef typename KT::T T;
     __shared__ T part[1024];
-    const int last = p.oshape[p.n_outer - 1];
+    const int last = p.kept.shape[p.kept.n - 1];
     const int groups = (last + cw - 1) / cw;
     const int split = (int)blockDim.x / cw;
     const int j = threadIdx.x & (cw - 1), s = threadIdx.x / cw;
@@ -229,24 +195,24 @@ __global__ __launch_bounds__(1024) void select_cols_kernel(const SelArgs p, int 
     const int j0 = (int)(bid - prefix * groups) * cw;
     const bool live = j0 + j < last;
     const int64_t row = prefix * last + (live ? j0 + j : last - 1);
-    const unsigned *xr = x + sel_row_base(p, row);
+    const unsigned *xr = x + slice_row_base(p.kept, p.rows, row);
     T acc = KT::identity();
     int i = s;
     for (; i + 15 * split < p.inner; i += 16 * split) { // sixteen independent loads in flight per lane
         unsigned v[16];
 #pragma unroll
-        for (int q = 0; q < 16; q++) v[q] = xr[sel_elem_off(p, i + q * split)];
+        for (int q = 0; q < 16; q++) v[q] = xr[slice_elem_off(p.red, i + q * split)];
 #pragma unroll
         for (int q = 0; q < 16; q++) acc = kmax(acc, KT::make(v[q], i + q * split, p.flip));
     }
     for (; i + 3 * split < p.inner; i += 4 * split) {
         unsigned v[4];
 #pragma unroll
-        for (int q = 0; q < 4; q++) v[q] = xr[sel_elem_off(p, i + q * split)];
+        for (int q = 0; q < 4; q++) v[q] = xr[slice_elem_off(p.red, i + q * split)];
 #pragma unroll
         for (int q = 0; q < 4; q++) acc = kmax(acc, KT::make(v[q], i + q * split, p.flip));
     }
-    for (; i < p.inner; i += split) acc = kmax(acc, KT::make(xr[sel_elem_off(p, i)], i, p.flip));
+    for (; i < p.inner; i += split) acc = kmax(acc, KT::make(xr[slice_elem_off(p.red, i)], i, p.flip));
     if (split > 1 && cw < 64) { // the thread groups of one wave meet in registers, the waves (at most 16) in LDS
         for (int m = cw; m < 64; m <<= 1) acc = kmax(acc, xor_lane(acc, m));
         const int wave = threadIdx.x >> 6, waves = (int)blockDim.x >> 6;
@@ -267,7 +233,7 @@ __global__ __launch_bounds__(1024) void select_cols_kernel(const SelArgs p, int 
 // A lane of at most P elements is one launch.  A longer lane is cut into chunks of P whose first kk = min(k, P) keys go to a list in global memory
 // (padded with key 0, below every real key since the index word ~i of a real key is >= 2^31); merge launches then sort `per` lists at a time until one is left.
 struct TopkArgs {
-    int n_outer;
+    SliceLevels<2> kept;  // stride lists: 0 the input's, 1 the outputs'
     int64_t lanes;
     int axis_len;
     int64_t axis_stride;  // of the input, in elements
@@ -279,21 +245,7 @@ struct TopkArgs {
     int final;            // 1: write values and indices; 0: write a list of kk keys
     unsigned vflip;       // 0: largest, 0xffffffff: smallest
     int64_t out_axis_stride;
-    int32_t oshape[6];
-    int64_t ostride[6], oostride[6]; // kept dims: input strides, output strides
 };
-
-__device__ __forceinline__ void topk_lane_bases(const TopkArgs &p, int64_t lane_id, int64_t &in_off, int64_t &out_off) {
-    in_off = 0;
-    out_off = 0;
-    int64_t r = lane_id;
-    for (int d = p.n_outer - 1; d >= 0; d--) {
-        const int64_t q = d ? r / p.oshape[d] : 0, c = d ? r - q * p.oshape[d] : r;
-        in_off += c * p.ostride[d];
-        out_off += c * p.oostride[d];
-        r = q;
-    }
-}
 
 template <int DT>
 __global__ __launch_bounds__(1024) void topk_sort_kernel(const TopkArgs p, const unsigned *__restrict__ x, const unsigned long long *__restrict__ lists_in,
@@ -301,9 +253,10 @@ __global__ __launch_bounds__(1024) void topk_sort_kernel(const TopkArgs p, const
     extern __shared__ __attribute__((aligned(16))) unsigned long long keys[];
     const int64_t lane_id = blockIdx.x / p.units;
     const int unit = (int)(blockIdx.x - lane_id * p.units);
-    int64_t in_off, out_off;
-    topk_lane_bases(p, lane_id, in_off, out_off);
-    const unsigned *xl = x + in_off;
+    int64_t base[2]; // of the lane in the input, in the outputs
+    slice_row_bases(p.kept, p.lanes, lane_id, base);
+    const int64_t out_off = base[1];
+    const unsigned *xl = x + base[0];
     if (!p.from_lists) {
         const int64_t i0 = (int64_t)unit * p.P;
         for (int t = threadIdx.x; t < p.P; t += blockDim.x) {
@@ -355,34 +308,14 @@ int next_pow2(int64_t v) {
     return p;
 }
 
-// shared argument checks of the two reductions; fills `p` (without chunking)
-int32_t fill_sel_args(rten_hip_ctx *ctx, const char *what, SelArgs &p, int32_t op, int32_t dtype, int32_t n_outer, const int64_t *outer_shape,
-                      const int64_t *outer_strides, int32_t n_inner, const int64_t *inner_shape, const int64_t *inner_strides) {
+// the checks ReduceMax / ReduceMin and ArgMax / ArgMin share, in their order; fills `p` (without chunking)
+int32_t select_args(rten_hip_ctx *ctx, const char *what, SelArgs &p, int32_t op, int32_t dtype, int32_t n_outer, const int64_t *outer_shape,
+                    const int64_t *outer_strides, int32_t n_inner, const int64_t *inner_shape, const int64_t *inner_strides) {
     if (op != RTEN_HIP_SELECT_MAX && op != RTEN_HIP_SELECT_MIN) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "%s: op must be RTEN_HIP_SELECT_MAX or _MIN", what);
     if (dtype != RTEN_HIP_DT_F32 && dtype != RTEN_HIP_DT_I32) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "%s: element type must be float32 or int32", what);
-    if (n_outer < 0 || n_outer > 6 || n_inner < 0 || n_inner > 6 || (n_outer && (!outer_shape || !outer_strides)) || (n_inner && (!inner_shape || !inner_strides)))
-        return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "%s: at most 6 kept and 6 reduced dims", what);
     p = SelArgs{};
-    p.n_outer = n_outer;
-    p.n_inner = n_inner > 0 ? n_inner : 1;
-    p.rows = 1;
+    if (int32_t rc = slice_fill(ctx, what, n_outer, outer_shape, {outer_strides}, p.kept, p.rows, n_inner, inner_shape, inner_strides, &p.red, &p.inner)) return rc;
     p.flip = op == RTEN_HIP_SELECT_MIN ? 0xffffffffu : 0u;
-    for (int d = 0; d < n_outer; d++) {
-        if (outer_shape[d] < 0 || outer_shape[d] > 0x7fffffff || outer_strides[d] < 0) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "%s: bad dimension", what);
-        p.oshape[d] = (int32_t)outer_shape[d];
-        p.ostride[d] = outer_strides[d];
-        p.rows *= outer_shape[d];
-    }
-    int64_t inner = 1;
-    p.ishape[0] = 1;
-    for (int d = 0; d < n_inner; d++) {
-        if (inner_shape[d] < 0 || inner_strides[d] < 0) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "%s: bad dimension", what);
-        inner *= inner_shape[d];
-        if (inner > 0x7fffffff) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "%s: reduced slice longer than 2^31 - 1", what);
-        p.ishape[d] = (int32_t)inner_shape[d];
-        p.istride[d] = inner_strides[d];
-    }
-    p.inner = (int)inner;
     p.chunk = p.inner;
     p.nchunks = 1;
     return RTEN_HIP_OK;
@@ -394,8 +327,8 @@ int32_t launch_select(rten_hip_ctx *ctx, SelArgs p, const void *xv, void *yv) {
     typedef typename KT::T T;
     const unsigned *x = (const unsigned *)xv;
     unsigned *y = (unsigned *)yv;
-    const int64_t last = p.n_outer ? p.oshape[p.n_outer - 1] : 1;
-    if (p.n_outer && p.ostride[p.n_outer - 1] == 1 && last >= 16 && p.istride[p.n_inner - 1] > 1 && p.rows / last * ((last + 63) / 64) <= 0x7fffffff) {
+    const int64_t last = p.kept.n ? p.kept.shape[p.kept.n - 1] : 1;
+    if (p.kept.n && p.kept.stride[0][p.kept.n - 1] == 1 && last >= 16 && p.red.stride[0][p.red.n - 1] > 1 && p.rows / last * ((last + 63) / 64) <= 0x7fffffff) {
         // thread per output while the outputs alone fill the machine or the slice is short; otherwise the slice is split over the workgroup's thread groups
         const bool flat = p.inner < 64 || p.rows >= (int64_t)64 * 16 * ctx->num_cus;
         const int block = flat ? 256 : 1024;
@@ -405,8 +338,8 @@ int32_t launch_select(rten_hip_ctx *ctx, SelArgs p, const void *xv, void *yv) {
         RTEN_LAUNCH_CHECK(ctx, "select_cols_kernel");
         return RTEN_HIP_OK;
     }
-    bool vec = p.n_inner == 1 && p.istride[0] == 1 && ((uintptr_t)x & 15) == 0;
-    for (int d = 0; d < p.n_outer; d++) vec = vec && (p.ostride[d] & 3) == 0;
+    bool vec = p.red.n == 1 && p.red.stride[0][0] == 1 && ((uintptr_t)x & 15) == 0;
+    for (int d = 0; d < p.kept.n; d++) vec = vec && (p.kept.stride[0][d] & 3) == 0;
     // few rows, long slices: partials first, so that the machine (not rows * 64 lanes) reads the tensor
     T *part = nullptr;
     if (p.rows < (int64_t)8 * ctx->num_cus && p.inner >= 16384) {
@@ -449,7 +382,7 @@ RTEN_EXPORT int32_t rten_hip_reduce_minmax_strided(rten_hip_ctx *ctx, int32_t op
                                                    const void *x, void *y) {
     RTEN_CHECK_CTX(ctx);
     SelArgs p;
-    if (int32_t rc = fill_sel_args(ctx, "reduce_minmax", p, op, dtype, n_outer, outer_shape, outer_strides, n_inner, inner_shape, inner_strides)) return rc;
+    if (int32_t rc = select_args(ctx, "reduce_minmax", p, op, dtype, n_outer, outer_shape, outer_strides, n_inner, inner_shape, inner_strides)) return rc;
     if (p.rows == 0) return RTEN_HIP_OK;
     if (!y) return RTEN_HIP_ERR_INVALID_VALUE;
     if (p.inner == 0) { // an empty slice gives the kernel's identity (reduce.rs:446-452; slice_fold_assoc's initial value / MaxNum's -inf)
@@ -467,7 +400,7 @@ RTEN_EXPORT int32_t rten_hip_arg_minmax_strided(rten_hip_ctx *ctx, int32_t op, i
                                                 const int64_t *outer_strides, int64_t axis_len, int64_t axis_stride, const void *x, int32_t *y) {
     RTEN_CHECK_CTX(ctx);
     SelArgs p;
-    if (int32_t rc = fill_sel_args(ctx, "arg_minmax", p, op, dtype, n_outer, outer_shape, outer_strides, 1, &axis_len, &axis_stride)) return rc;
+    if (int32_t rc = select_args(ctx, "arg_minmax", p, op, dtype, n_outer, outer_shape, outer_strides, 1, &axis_len, &axis_stride)) return rc;
     if (axis_len == 0) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "Cannot select index from empty sequence");
     if (p.rows == 0) return RTEN_HIP_OK;
     if (!x || !y) return RTEN_HIP_ERR_INVALID_VALUE;
@@ -480,6 +413,7 @@ RTEN_EXPORT int32_t rten_hip_topk_strided(rten_hip_ctx *ctx, int32_t largest, in
                                           const void *x, void *values, int32_t *indices, int64_t out_axis_stride) {
     RTEN_CHECK_CTX(ctx);
     if (dtype != RTEN_HIP_DT_F32 && dtype != RTEN_HIP_DT_I32) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "topk: element type must be float32 or int32");
+    // (the level count is refused ahead of the checks on the axis and on k, the levels themselves after them: slice_fill below looks at both)
     if (n_outer < 0 || n_outer > 6 || (n_outer && (!outer_shape || !outer_strides || !outer_out_strides)))
         return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "topk: at most 6 kept dims");
     if (axis_len < 0 || axis_len > 0x7fffffff || axis_stride < 0 || out_axis_stride < 0) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "topk: bad dimension");
@@ -488,15 +422,7 @@ RTEN_EXPORT int32_t rten_hip_topk_strided(rten_hip_ctx *ctx, int32_t largest, in
     if (k > axis_len) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "k > dimension size");
     if (k > 4096) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "topk: k > 4096 is not supported by the device path (a full sort of a long lane is a different kernel)");
     TopkArgs p = {};
-    p.n_outer = n_outer;
-    p.lanes = 1;
-    for (int d = 0; d < n_outer; d++) {
-        if (outer_shape[d] < 0 || outer_shape[d] > 0x7fffffff || outer_strides[d] < 0 || outer_out_strides[d] < 0) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "topk: bad dimension");
-        p.oshape[d] = (int32_t)outer_shape[d];
-        p.ostride[d] = outer_strides[d];
-        p.oostride[d] = outer_out_strides[d];
-        p.lanes *= outer_shape[d];
-    }
+    if (int32_t rc = slice_fill(ctx, "topk", n_outer, outer_shape, {outer_strides, outer_out_strides}, p.kept, p.lanes)) return rc;
     if (p.lanes == 0) return RTEN_HIP_OK;
     if (!x || !values || !indices) return RTEN_HIP_ERR_INVALID_VALUE;
     p.axis_len = (int)axis_len;

@@ -669,10 +669,12 @@ class MatMulNBits(Operator):
 
 
 # ------------------------------------------------------------------------------------------ norm / softmax
-def _resolve_axis(ndim, axis):
-    if axis < -ndim or axis >= ndim:
+def _resolve_axis(nd, axis):
+    """resolve_axis (src/ops/mod.rs): a rank-0 operand has no valid axis."""
+    axis = int(axis)
+    if axis < -nd or axis >= nd:
         raise InvalidValue("Axis is invalid")
-    return axis + ndim if axis < 0 else axis
+    return axis + nd if axis < 0 else axis
 
 
 class Softmax(Operator):
@@ -1644,38 +1646,9 @@ def resolve_axes(nd, axes):
     return sorted(set(out))
 
 
-class ReduceSum(Operator):
-    """src/ops/reduce.rs:1126-1165 (f32): axes attribute or second input already resolved by the caller into `axes`;
-    the slice of every output element is summed in place through the view's strides, 16-lane vecmath::Sum order."""
-    mean = False
-
-    def __init__(self, axes=None, keep_dims=True, noop_with_empty_axes=False):
-        self.axes, self.keep_dims, self.noop_with_empty_axes = axes, keep_dims, noop_with_empty_axes
-
-    def max_inputs(self):
-        return 2
-
-    def run(self, ctx, inputs):
-        from . import einsum as E
-        x = _want(_require(inputs, 0), np.float32)
-        nd = len(x.shape)
-        if not self.axes and self.noop_with_empty_axes:
-            return [E.materialize(ctx, E.View(x))]
-        axes = resolve_axes(nd, self.axes if self.axes else range(nd))
-        y = E.reduce_sum(ctx, E.View(x), axes, mean=self.mean) if nd else E.materialize(ctx, E.View(x))  # rank 0: Sum = Mean = x (slice of one)
-        if self.keep_dims:
-            y = y.reshape([1 if d in axes else x.shape[d] for d in range(nd)])
-        return [y]
-
-
-class ReduceMean(ReduceSum):
-    """src/ops/reduce.rs:523-580: vecmath::Sum(slice) / len(slice) as f32 (an empty slice gives NaN)."""
-    mean = True
-
-
-# ------------------------------------------------------------------------------------------ selection family
 SELECT_MAX, SELECT_MIN = 0, 1  # RTEN_HIP_SELECT_*
 _DT = {np.dtype(np.float32): 0, np.dtype(np.int32): 1}  # RTEN_HIP_DT_F32 / _I32
+REDUCE_L1, REDUCE_SUM_SQUARE, REDUCE_L2, REDUCE_LOG_SUM, REDUCE_LOG_SUM_EXP, REDUCE_PROD = range(6)  # RTEN_HIP_REDUCE_*
 
 
 def _select_view(x):
@@ -1692,67 +1665,36 @@ def _host_ints(v):
     return None if v is None else [int(a) for a in np.asarray(v).reshape(-1)]
 
 
-def _kept_and_reduced(v, axes):
+def _split_dims(v, axes, *others):
+    """The dims of view `v` outside `axes` (kept) and inside (reduced), merged, as the strided reductions' ABI takes them: (kept dims, kept shape, kept
+    stride lists, reduced shape, reduced strides).  The first kept stride list is v's own; each of `others`, a full-rank stride list of another view
+    of v's shape (TopK's outputs), adds one, and kept dims merge only where every list agrees."""
     from . import einsum as E
     keep = [d for d in range(len(v.shape)) if d not in axes]
-    osh, (ost,) = E._merge_axes([v.shape[d] for d in keep], [v.strides[d] for d in keep])
+    osh, ost = E._merge_axes([v.shape[d] for d in keep], *[[st[d] for d in keep] for st in (v.strides,) + others])
     ish, (ist,) = E._merge_axes([v.shape[d] for d in axes], [v.strides[d] for d in axes])
     if len(osh) > 6 or len(ish) > 6:
         raise UnsupportedValue("more than 6 non-mergeable dims are not supported by the device path")
     return keep, osh, ost, ish, ist
 
 
-class ReduceMax(Operator):
-    """src/ops/reduce.rs:977-1044 (float32 and int32): axes attribute or host-side second input; a NaN in a slice gives NaN; an empty slice gives
-    the identity (-inf / i32::MIN; ReduceMin: +inf / i32::MAX).  The slice is read in place through the view's strides."""
-    op = SELECT_MAX
-
-    def __init__(self, axes=None, keep_dims=True, noop_with_empty_axes=False):
-        self.axes, self.keep_dims, self.noop_with_empty_axes = axes, keep_dims, noop_with_empty_axes
-
-    def max_inputs(self):
-        return 2
-
-    def run(self, ctx, inputs):
-        from . import einsum as E
-        v, dt = _select_view(_require(inputs, 0))
-        axes = _host_ints(_get(inputs, 1))
-        axes = list(self.axes) if axes is None and self.axes is not None else axes
-        nd = len(v.shape)
-        copy = lambda: [E.materialize(ctx, v, dtype=v.t.dtype)]
-        if not axes and self.noop_with_empty_axes:
-            return copy()
-        if nd == 0:
-            resolve_axes(0, axes or [])
-            return copy()  # a 0-d input returns itself (reduce.rs:425-428)
-        axes = resolve_axes(nd, axes if axes else range(nd))
-        keep, osh, ost, ish, ist = _kept_and_reduced(v, axes)
-        y = DeviceTensor(ctx, [v.shape[d] for d in keep], v.t.dtype)
-        if y.size:
-            ctx.call("rten_hip_reduce_minmax_strided", self.op, dt, len(osh), E._i64(osh), E._i64(ost), len(ish), E._i64(ish), E._i64(ist), v.t.vp, y.vp)
-        if self.keep_dims:
-            y = y.reshape([1 if d in axes else v.shape[d] for d in range(nd)])
-        return [y]
-
-
-class ReduceMin(ReduceMax):
-    """src/ops/reduce.rs:907-975."""
-    op = SELECT_MIN
-
-
-# ------------------------------------------------------------------------------------------ the rest of the Reduce* family
-REDUCE_L1, REDUCE_SUM_SQUARE, REDUCE_L2, REDUCE_LOG_SUM, REDUCE_LOG_SUM_EXP, REDUCE_PROD = range(6)  # RTEN_HIP_REDUCE_*
-
-
-class _Reduce(Operator):
-    """reduce() (src/ops/reduce.rs:414-520) around one kernel of rten_hip_reduce_strided: axes attribute or host-side second input, resolved, sorted and
-    de-duplicated; a 0-d input is a slice of one element; an empty slice gives the kernel's value for it.  The slice is read in place through the view's
-    strides.  `int32`: the reference also takes Int32Tensor (wrapping arithmetic); `typed_first`: the operand's type is checked before
-    noop_with_empty_axes is looked at (map_value_view! / require_as outside the test, reduce.rs:687,752,827,1215)."""
-    kind = -1
+class _ReduceOp(Operator):
+    """reduce() (src/ops/reduce.rs:414-520) around one strided kernel: axes attribute or host-side second input, resolved, sorted and de-duplicated; an
+    empty slice gives the kernel's value for it.  The slice is read in place through the view's strides.  What the operators do differently, each as
+    the reference has it:
+      axes_input   a second input replaces the `axes` attribute (not ReduceSum / ReduceMean: their caller resolves it into the attribute)
+      int32        the reference also takes Int32Tensor (wrapping arithmetic, or a comparison)
+      typed_first  the operand's type is checked before noop_with_empty_axes is looked at (map_value_view! / require_as outside the test,
+                   reduce.rs:687,752,827,1215); otherwise only a reduction that runs checks it
+      f32_error    falsy: UnsupportedType (map_value_view!); otherwise require_as::<f32>'s cast error
+      rank0_copy   a 0-d input returns itself once its axes are validated (reduce.rs:425-428); otherwise it is a slice of one element for the kernel
+      _noop        what comes back when noop_with_empty_axes skips the reduction
+      _entry       the entry point and its leading arguments"""
+    axes_input = True
     int32 = False
     typed_first = True
-    f32_error = None  # None: UnsupportedType (map_value_view!); otherwise require_as::<f32>'s cast error
+    f32_error = None
+    rank0_copy = False
 
     def __init__(self, axes=None, keep_dims=True, noop_with_empty_axes=False):
         self.axes, self.keep_dims, self.noop_with_empty_axes = axes, keep_dims, noop_with_empty_axes
@@ -1768,14 +1710,22 @@ class _Reduce(Operator):
         raise UnsupportedType
 
     def _noop(self, ctx, t):
-        """What the operator gives when the reduction is skipped: `t` is a fresh contiguous copy of the input."""
+        """`t` is a fresh contiguous copy of the input."""
         return t
+
+    def _reduce(self, ctx, v, axes):
+        from . import einsum as E
+        keep, osh, (ost,), ish, ist = _split_dims(v, axes)
+        y = DeviceTensor(ctx, [v.shape[d] for d in keep], v.t.dtype)
+        if y.size:
+            ctx.call(*self._entry(), _DT[v.t.dtype], len(osh), E._i64(osh), E._i64(ost), len(ish), E._i64(ish), E._i64(ist), v.t.vp, y.vp)
+        return y
 
     def run(self, ctx, inputs):
         from . import einsum as E
         x = _require(inputs, 0)
         v = x if isinstance(x, E.View) else E.View(x)
-        axes = _host_ints(_get(inputs, 1))
+        axes = _host_ints(_get(inputs, 1)) if self.axes_input else None
         axes = list(self.axes) if axes is None and self.axes is not None else axes
         if self.typed_first:
             self._check_type(v)
@@ -1786,13 +1736,50 @@ class _Reduce(Operator):
         self._check_type(v)
         nd = len(v.shape)
         axes = resolve_axes(nd, axes if axes else range(nd))
-        keep, osh, ost, ish, ist = _kept_and_reduced(v, axes)
-        y = DeviceTensor(ctx, [v.shape[d] for d in keep], v.t.dtype)
-        if y.size:
-            ctx.call("rten_hip_reduce_strided", self.kind, _DT[v.t.dtype], len(osh), E._i64(osh), E._i64(ost), len(ish), E._i64(ish), E._i64(ist), v.t.vp, y.vp)
+        if nd == 0 and self.rank0_copy:
+            return [E.materialize(ctx, v, dtype=v.t.dtype)]
+        y = self._reduce(ctx, v, axes)
         if self.keep_dims:
             y = y.reshape([1 if d in axes else v.shape[d] for d in range(nd)])
         return [y]
+
+
+class ReduceSum(_ReduceOp):
+    """src/ops/reduce.rs:1126-1165 (f32): 16-lane vecmath::Sum order."""
+    axes_input, f32_error, rank0_copy = False, True, True
+    mean = False
+
+    def _reduce(self, ctx, v, axes):
+        from . import einsum as E
+        return E.reduce_sum(ctx, v, axes, mean=self.mean)
+
+
+class ReduceMean(ReduceSum):
+    """src/ops/reduce.rs:523-580: vecmath::Sum(slice) / len(slice) as f32 (an empty slice gives NaN)."""
+    mean = True
+
+
+class ReduceMax(_ReduceOp):
+    """src/ops/reduce.rs:977-1044 (float32 and int32): a NaN in a slice gives NaN; an empty slice gives the identity (-inf / i32::MIN; ReduceMin:
+    +inf / i32::MAX)."""
+    int32, rank0_copy = True, True
+    op = SELECT_MAX
+
+    def _entry(self):
+        return "rten_hip_reduce_minmax_strided", self.op
+
+
+class ReduceMin(ReduceMax):
+    """src/ops/reduce.rs:907-975."""
+    op = SELECT_MIN
+
+
+class _Reduce(_ReduceOp):
+    """The six kinds of rten_hip_reduce_strided; a 0-d input is a slice of one element."""
+    kind = -1
+
+    def _entry(self):
+        return "rten_hip_reduce_strided", self.kind
 
 
 class ReduceL1(_Reduce):
@@ -1864,7 +1851,7 @@ class LpNormalization(Operator):
         v = E.View(src)
         if src.size == 0:
             return [y]
-        keep, osh, ost, _, _ = _kept_and_reduced(v, [ax])
+        _, osh, (ost,), _, _ = _split_dims(v, [ax])
         ctx.call("rten_hip_lp_normalize_f32", self.p, len(osh), E._i64(osh), E._i64(ost), v.shape[ax], v.strides[ax], src.vp, y.vp)
         return [y]
 
@@ -1882,7 +1869,7 @@ class GlobalMaxPool(Operator):
         if nd < 2:
             raise InvalidValue("Input must have at least 2 dims")
         v = E.View(x)
-        _, osh, ost, ish, ist = _kept_and_reduced(v, list(range(2, nd)))
+        _, osh, (ost,), ish, ist = _split_dims(v, list(range(2, nd)))
         y = DeviceTensor(ctx, tuple(x.shape[:2]) + (1,) * (nd - 2), np.float32)
         if y.size:
             ctx.call("rten_hip_reduce_minmax_strided", SELECT_MAX, _DT[x.dtype], len(osh), E._i64(osh), E._i64(ost), len(ish), E._i64(ish), E._i64(ist), x.vp, y.vp)
@@ -1906,12 +1893,10 @@ class ArgMax(Operator):
         from . import einsum as E
         v, dt = _select_view(_require(inputs, 0))
         nd = len(v.shape)
-        if self.axis < -nd or self.axis >= nd:
-            raise InvalidValue("Axis is invalid")
-        ax = self.axis + nd if self.axis < 0 else self.axis
+        ax = _resolve_axis(nd, self.axis)
         if v.shape[ax] == 0:
             raise InvalidValue("Cannot select index from empty sequence")
-        keep, osh, ost, _, _ = _kept_and_reduced(v, [ax])
+        keep, osh, (ost,), _, _ = _split_dims(v, [ax])
         y = DeviceTensor(ctx, [v.shape[d] for d in keep], np.int32)
         if y.size:
             ctx.call("rten_hip_arg_minmax_strided", self.op, dt, len(osh), E._i64(osh), E._i64(ost), v.shape[ax], v.strides[ax], v.t.vp, y.vp)
@@ -1946,10 +1931,7 @@ class TopK(Operator):
         if k < 0:
             raise InvalidValue("k must be positive")
         nd = len(v.shape)
-        axis = -1 if self.axis is None else self.axis
-        if axis < -nd or axis >= nd:
-            raise InvalidValue("Axis is invalid")
-        ax = axis + nd if axis < 0 else axis
+        ax = _resolve_axis(nd, -1 if self.axis is None else self.axis)
         out_shape = [k if d == ax else v.shape[d] for d in range(nd)]
         values, indices = DeviceTensor(ctx, out_shape, v.t.dtype), DeviceTensor(ctx, out_shape, np.int32)
         if k == 0:
@@ -1958,10 +1940,7 @@ class TopK(Operator):
             raise InvalidValue("k > dimension size")
         if values.size:
             ov = E.View(values)
-            keep = [d for d in range(nd) if d != ax]
-            osh, (ost, oost) = E._merge_axes([v.shape[d] for d in keep], [v.strides[d] for d in keep], [ov.strides[d] for d in keep])
-            if len(osh) > 6:
-                raise UnsupportedValue("more than 6 non-mergeable dims are not supported by the device path")
+            _, osh, (ost, oost), _, _ = _split_dims(v, [ax], ov.strides)
             try:
                 ctx.call("rten_hip_topk_strided", 1 if self.largest else 0, dt, len(osh), E._i64(osh), E._i64(ost), E._i64(oost), v.shape[ax], v.strides[ax],
                          k, v.t.vp, values.vp, indices.vp, ov.strides[ax])
@@ -2169,14 +2148,6 @@ class DepthToSpace(Operator):
         if y.size:
             ctx.call("rten_hip_transpose_b32", 6, (C.c_int64 * 6)(*view), (C.c_int32 * 6)(*DEPTH_TO_SPACE_PERMS[self.mode]), x.vp, y.vp)
         return [y]
-
-
-def _resolve_axis(nd, axis):
-    """resolve_axis (src/ops/mod.rs): a rank-0 operand has no valid axis."""
-    axis = int(axis)
-    if axis < -nd or axis >= nd:
-        raise InvalidValue("Axis is invalid")
-    return axis + nd if axis < 0 else axis
 
 
 def _scalar_i32(t):

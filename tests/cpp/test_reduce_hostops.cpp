@@ -106,6 +106,40 @@ int main() {
     CHECK(ReduceL2().keep_dims && !ReduceL2().noop_with_empty_axes && ReduceL2().axes.empty() && ReduceProd().max_inputs() == 2);
     CHECK(LpNormalization().axis == -1 && LpNormalization().p == 2 && LpNormalization().max_inputs() == 1 && GlobalMaxPool().max_inputs() == 1);
     CHECK(ReduceL1().int32 && ReduceSumSquare().int32 && ReduceProd().int32 && !ReduceL2().int32 && !ReduceLogSum().int32 && !ReduceLogSumExp().int32);
+
+    // ---- the kept / reduced split every strided reduction hands to the ABI, on the views whose lists tests/test_reduce_ops.py and tests/test_select_ops.py
+    // pin for the Python layer (test_reduce_stride_lists_of_views, test_reduce_stride_lists_of_a_permuted_view): one table for both layers
+    namespace E = einsum_detail;
+    typedef std::vector<V> VV;
+    E::View perm; // [2, 3, 4, 5] permuted by (2, 0, 3, 1)
+    perm.shape = {4, 2, 5, 3};
+    perm.strides = {5, 60, 1, 20};
+    E::Split s = E::split_dims(perm, {1, 3});
+    CHECK(s.kshape == V({4, 5}) && s.mo == V({20}) && s.mos == VV({{1}}) && s.mi == V({6}) && s.mis == VV({{20}})); // 4 x 5 merge, and 2 x 3 (60 = 20 * 3)
+    s = E::split_dims(perm, {0, 2});
+    CHECK(s.kshape == V({2, 3}) && s.mo == V({6}) && s.mos == VV({{20}}) && s.mi == V({20}) && s.mis == VV({{1}})); // the mirror image
+    s = E::split_dims(perm, {2});
+    CHECK(s.kshape == V({4, 2, 3}) && s.mo == V({4, 6}) && s.mos == VV({{5, 20}}) && s.mi == V({5}) && s.mis == VV({{1}})); // 2 x 3 merge, 4 stays apart
+    E::View sliced; // a step-2 slice of the last axis: nothing merges with it
+    sliced.shape = {2, 3, 4, 3};
+    sliced.strides = {60, 20, 5, 2};
+    s = E::split_dims(sliced, {3});
+    CHECK(s.kshape == V({2, 3, 4}) && s.mo == V({24}) && s.mos == VV({{5}}) && s.mi == V({3}) && s.mis == VV({{2}}));
+    // TopK's two stride lists: along dim 2 of the permuted view, k = 2, the outputs are [4, 2, 2, 3] with strides 12, 6, 3, 1 -- kept 2 x 3 would merge
+    // in the view, not in them
+    s = E::split_dims(perm, {2}, {V({12, 6, 3, 1})});
+    CHECK(s.mo == V({4, 2, 3}) && s.mos == VV({{5, 60, 20}, {12, 6, 1}}) && s.mi == V({5}) && s.mis == VV({{1}}));
+    E::View dense; // along the last dim of the contiguous tensor every kept dim merges in both lists
+    dense.shape = {2, 3, 4, 5};
+    dense.strides = {60, 20, 5, 1};
+    s = E::split_dims(dense, {3}, {V({24, 8, 2, 1})});
+    CHECK(s.mo == V({24}) && s.mos == VV({{5}, {2}}) && s.mi == V({5}) && s.mis == VV({{1}}));
+    // more than 6 levels: refused with the family's words, or left to the caller (Einsum's own wording)
+    E::View wide;
+    wide.shape = V(7, 2);
+    wide.strides = {1000000, 100000, 10000, 1000, 100, 10, 1};
+    try { E::split_dims(wide, {}); CHECK(false); } catch (const OpError &e) { CHECK(std::string(e.what()).find("more than 6 non-mergeable dims") != std::string::npos); }
+    CHECK(E::split_dims(wide, {}, {}, nullptr).mo.size() == 7);
     if (failures) { std::printf("%d FAILED\n", failures); return 1; }
     std::printf("ALL OK\n");
     return 0;

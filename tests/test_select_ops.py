@@ -259,6 +259,20 @@ def test_reduce_stride_lists_of_a_permuted_view():
     ops.ReduceMax(axes=[2], keep_dims=False).run(c, [v])
     name, a = c.launches[-1]
     assert a[2] == 2 and list(a[3])[:2] == [4, 6] and list(a[4])[:2] == [5, 20] and (list(a[6])[:1], list(a[7])[:1]) == ([5], [1])
+    # TopK walks the kept dims through two stride lists, the view's and its contiguous outputs' (the table tests/cpp/test_reduce_hostops.cpp holds for C++):
+    # along dim 2 of the view, k = 2, the outputs are [4, 2, 2, 3] with strides 12, 6, 3, 1 -- kept 2 x 3 would merge in the view (60 = 20 * 3), not in them
+    K = np.array([2], np.int32)
+    tv, ti = ops.TopK(axis=2).run(c, [v, K])
+    wv, wi = R.topk(x.transpose(2, 0, 3, 1), 2, 2)
+    same(tv.numpy(), wv)
+    same(ti.numpy(), wi)
+    name, a = c.launches[-1]
+    assert name == "rten_hip_topk_strided" and a[2] == 3 and (list(a[3])[:3], list(a[4])[:3], list(a[5])[:3]) == ([4, 2, 3], [5, 60, 20], [12, 6, 1])
+    assert (a[6], a[7], a[8], a[12]) == (5, 1, 2, 3)
+    # along the last dim of the contiguous tensor every kept dim merges in both lists: 24 lanes, 5 apart in the input and 2 apart in the outputs
+    ops.TopK(axis=3).run(c, [dev(c, x), K])
+    name, a = c.launches[-1]
+    assert a[2] == 1 and (list(a[3])[:1], list(a[4])[:1], list(a[5])[:1]) == ([24], [5], [2]) and (a[6], a[7], a[8], a[12]) == (5, 1, 2, 1)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.int32])
