@@ -86,7 +86,9 @@ __global__ __launch_bounds__(256) void gemv4_kernel(int K, int N, int lbs, const
                 l[2 * q + 1] = (v2f){t.z, t.w};
             }
         }
-        // (q - 8) * s with one rounding: fma(q, s, -8 s) -- -8 s is exact, so the exact sum is (q - 8) s
+        // (q - 8) * s with one rounding: fma(q, s, -8 s).  While 8 |s| is finite (|s| < 2^125) -8 s is exact (a power-of-two multiple stays on the grid,
+        // subnormals included), so the exact sum is (q - 8) s.  From 2^125 on -8 s is +-inf, every weight of the block with it, and the column's sum ends as
+        // inf or NaN whatever follows: that is caught once, behind the fold (see `exact` below), not here.
         const unsigned lo = wv & 0x0F0F0F0Fu, hi = (wv >> 4) & 0x0F0F0F0Fu;
         const v2f s2 = (v2f){s, s}, m8 = (v2f){-8.0f * s, -8.0f * s};
 #pragma unroll
@@ -136,20 +138,41 @@ __global__ __launch_bounds__(256) void gemv4_kernel(int K, int N, int lbs, const
 
     // slot s = SPL * sub + e.  (acc0 + acc1) + (acc2 + acc3) over the four 16-lane accumulators = slots s ^ 16, then s ^ 32; then the
     // halving tree of the horizontal sum (8, 4, 2, 1).  A distance >= SPL is another lane of the column, a smaller one is inside the lane.
-    constexpr int order[6] = {16, 32, 8, 4, 2, 1};
+    auto fold = [&]() __attribute__((always_inline)) {
+        constexpr int order[6] = {16, 32, 8, 4, 2, 1};
 #pragma unroll
-    for (int i = 0; i < 6; i++) {
-        const int w = order[i];
-        if (w >= SPL) {
+        for (int i = 0; i < 6; i++) {
+            const int w = order[i];
+            if (w >= SPL) {
 #pragma unroll
-            for (int e = 0; e < SPL; e++) accs[e] = accs[e] + __shfl_xor(accs[e], w / SPL);
-        } else {
+                for (int e = 0; e < SPL; e++) accs[e] = accs[e] + __shfl_xor(accs[e], w / SPL);
+            } else {
 #pragma unroll
-            for (int e = 0; e < SPL; e++)
-                if (e < w) accs[e] = accs[e] + accs[e + w];
+                for (int e = 0; e < SPL; e++)
+                    if (e < w) accs[e] = accs[e] + accs[e + w];
+            }
         }
-    }
+    };
+    fold();
     float out = accs[0];
+
+    // `exact`: a sum that is not finite is either the true result or the trace of a scale with |s| >= 2^125 (above).  The wave then repeats its columns with
+    // the weight as the reference forms it, (float)(q - 8) * s, which is finite there for |q - 8| <= 4 -- the same slots (lane `sub` owns elements
+    // sub * SPL .. + SPL - 1 of every 64-element step), chains and fold, the LHS read from memory.  Rare, so its speed does not matter; the branch is
+    // uniform over the wave, so the fold's lane exchanges find every partner active.
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!(fabsf(out) <= 3.402823466e+38f)) != 0, 0)) {
+#pragma unroll
+        for (int e = 0; e < SPL; e++) accs[e] = 0.f;
+        for (int k0 = sub * SPL; k0 < kv; k0 += 64) {
+#pragma unroll
+            for (int e = 0; e < SPL; e++) {
+                const int k = k0 + e;
+                accs[e] = __builtin_fmaf(arow[k], nib(qcol[k / 2], k & 1, scol[k >> lbs]), accs[e]);
+            }
+        }
+        fold();
+        out = accs[0];
+    }
 
     if (kv < K && sub == 0) { // scalar tail (block_quant.rs:351-377): separately rounded products
         float tail = 0.f;
