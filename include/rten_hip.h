@@ -633,6 +633,34 @@ int32_t rten_hip_tile_b32(rten_hip_ctx *ctx, int32_t ndim, const int64_t *x_shap
 int32_t rten_hip_non_max_suppression_f32(rten_hip_ctx *ctx, int32_t center_point_box, int64_t n, int64_t c, int64_t b, const float *boxes, const float *scores,
                                          int32_t has_max_per_class, int32_t max_per_class, float iou_threshold, float score_threshold, int32_t *selected,
                                          int64_t *count);
+/* DFT and STFT (src/ops/fft.rs:22-373) on complex float32, one transform core: a Stockham autosort FFT that stays in LDS from load to store
+ * (rten_amd/csrc/fft.hip).  rten_hip_fft_plan factors a length into its passes: radix 4 as often as it divides, then one 2, then 3s, 5s, then every other
+ * prime factor <= RTEN_HIP_FFT_GENERIC_RADIX_MAX as a generic pass; a length with a larger prime factor is ONE direct pass of radix n.  It writes the radices
+ * in pass order and returns their count (0 for n == 1), or a negative code: -RTEN_HIP_ERR_UNSUPPORTED for n > RTEN_HIP_FFT_MAX, -RTEN_HIP_ERR_INVALID_VALUE
+ * for n < 1, a NULL array or a capacity below the count (16 always suffices).  Host only, no context.
+ * Contract: not bit-identity with the reference's FFT library but an error bound against the exact transform, per lane:
+ *   ||got - want||_2 <= eps_f32 * (2 + sum over the passes of (2 r + 6)) * ||want||_2, and a lane whose exact result is zero comes out exactly zero.
+ * Twiddles come from one table w[k] = exp(-/+ 2 pi i k / n), each entry computed in float64 and rounded once, written into the context's auxiliary scratch
+ * by a prologue launch of every call (stateless; capture-safe once the scratch exists, which any eager call ensures).
+ * rten_hip_dft_f32: `lanes` lanes of [n_in][in_components] (1 = real, 2 = interleaved complex), truncated or zero-filled to n_fft points.
+ *   inverse && onesided (IRFFT, complex input only): the conjugate half is rebuilt, X[n_fft - k] = conj(X[k]) for 1 <= k < conj_end, conj_end = min(n_in,
+ *   n_fft) - 1 for even n_fft and min(n_in, n_fft) for odd; the output is [lanes][n_fft] REAL.  Otherwise the output is [lanes][out_len][2], out_len =
+ *   n_fft / 2 + 1 when onesided && !inverse (real input only), else n_fft.  The inverse multiplies by 1.0f / (float)n_fft, one rounding per component.
+ *   n_fft == 0 launches no transform; one-sided forward it zero-fills the single output bin of every lane.  lanes == 0 does nothing.
+ * rten_hip_stft_f32: signal [batch][signal_len][components]; frame f of batch b is signal[b][f * frame_step + k] * window[k] (one rounded f32 multiply;
+ *   window_or_null == NULL: no multiply), k < n_fft, read straight from the signal; y is [batch][n_frames][bins][2], n_frames = (signal_len - n_fft) /
+ *   frame_step + 1, bins = n_fft / 2 + 1 when onesided (real signal only) else n_fft.  batch == 0 or n_fft == 0 does nothing.
+ * Errors (RTEN_HIP_ERR_INVALID_VALUE): "Last dimension of DFT input must have size 1 or 2", "Inverse one-sided DFT (IRFFT) requires complex input",
+ * "DFT cannot be one-sided if input is complex", "Last dimension of signal must have size 1 or 2", "FFT cannot be one-sided if input is complex",
+ * "frame_length must be in range [1, signal_length]", "frame_step must be > 0"; a negative size or a NULL operand.  n_fft above RTEN_HIP_FFT_MAX is
+ * RTEN_HIP_ERR_UNSUPPORTED, the message naming the length and the limit. */
+#define RTEN_HIP_FFT_MAX 8192
+#define RTEN_HIP_FFT_GENERIC_RADIX_MAX 31
+int32_t rten_hip_dft_f32(rten_hip_ctx *ctx, int64_t lanes, int64_t n_in, int64_t n_fft, int32_t in_components, int32_t inverse, int32_t onesided, const float *x,
+                         float *y);
+int32_t rten_hip_stft_f32(rten_hip_ctx *ctx, int64_t batch, int64_t signal_len, int32_t components, int64_t frame_step, int64_t n_fft, int32_t onesided,
+                          const float *window_or_null, const float *signal, float *y);
+int32_t rten_hip_fft_plan(int64_t n, int32_t *radices, int32_t capacity);
 /* 1 while a graph capture is active on `ctx` (rten_hip_graph_begin .. _end): host code must not upload from host memory then -- the copy would be
  * recorded with the host pointer and re-read at every replay. */
 int32_t rten_hip_capture_active(rten_hip_ctx *ctx);

@@ -1338,6 +1338,41 @@ class Graph {
         a.has_score = n.inputs.size() > 4 && !n.inputs[4].empty();
         return a;
     }
+    // What the loader reads from, and refuses about, a DFT / STFT node (make_fft_step; onnx_registry.rs:1063-1079,1991-1994 and the operators' max_inputs).
+    // inverse and onesided default to 0 for DFT, onesided to 1 for STFT.  DFT's axis: the `axis` attribute where the node has one; else 1 before opset 20; else
+    // the optional third input, default -2.  dft_length, axis, frame_step and frame_length are host values at run time -- constants or shape arithmetic -- so
+    // one that is a graph input (device data) is refused here, by node name; any other device-computed one is refused by the step when it runs.  Needs no
+    // device; rten_hip_run --parse-only calls them too.
+    struct DftNode { bool inverse = false, onesided = false, axis_fixed = false; int64_t axis = -2; };
+    static DftNode read_dft_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        const std::string where = "DFT " + label + ": ";
+        DftNode a;
+        a.inverse = n.get_int("inverse", 0) != 0;
+        a.onesided = n.get_int("onesided", 0) != 0;
+        const int64_t none = INT64_MIN;
+        const int64_t attr = n.get_int("axis", none);
+        if (attr != none) { a.axis_fixed = true; a.axis = attr; }
+        else if (m.opset < 20) { a.axis_fixed = true; a.axis = 1; }
+        refuse_extra_inputs(n, 3, where);
+        if (n.inputs.empty() || n.inputs[0].empty()) throw GraphError(where + "the input is missing");
+        refuse_device_operand(m, n, 1, where, "dft_length");
+        refuse_device_operand(m, n, 2, where, "axis");
+        return a;
+    }
+    struct StftNode { bool onesided = true, has_window = false, has_frame_length = false; };
+    static StftNode read_stft_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        const std::string where = "STFT " + label + ": ";
+        StftNode a;
+        a.onesided = n.get_int("onesided", 1) != 0;
+        refuse_extra_inputs(n, 4, where);
+        if (n.inputs.size() < 2 || n.inputs[0].empty() || n.inputs[1].empty()) throw GraphError(where + "the signal or frame_step input is missing");
+        refuse_device_operand(m, n, 1, where, "frame_step");
+        refuse_device_operand(m, n, 3, where, "frame_length");
+        a.has_window = n.inputs.size() > 2 && !n.inputs[2].empty();
+        a.has_frame_length = n.inputs.size() > 3 && !n.inputs[3].empty();
+        if (!a.has_window && !a.has_frame_length) throw GraphError(where + "Either frame_length or window must be set");
+        return a;
+    }
     static bool is_index_kind(const std::string &k) { return k == "CumSum" || k == "GatherElements" || k == "Trilu" || k == "Tile"; }
     static bool is_math_kind(const std::string &k) {
         static const std::set<std::string> kinds = {"Neg", "Abs", "Sign", "Floor", "Ceil", "Round", "Sqrt", "Reciprocal", "Exp", "Log", "Softplus", "Pow", "PRelu", "Min", "Max", "Sum", "Mean"};
@@ -2716,6 +2751,7 @@ class Graph {
             else if (kind == "Pad") make_pad_step(st, n, m);
             else if (is_index_kind(kind)) make_index_step(st, n, m);
             else if (kind == "NonMaxSuppression") make_nms_step(st, n, m);
+            else if (kind == "DFT" || kind == "STFT") make_fft_step(st, n, m);
             else if (kind == "QuantizeLinear" || kind == "DequantizeLinear") make_qdq_step(st, n, m, nodes, out_name);
             else if (kind == "Flatten" || kind == "Reshape" || kind == "Squeeze" || kind == "Unsqueeze" || kind == "Identity" || kind == "Dropout") make_view_step(st, n);
             else if (make_layout_step(st, n)) {
@@ -3124,6 +3160,45 @@ class Graph {
         st.batch_coupled = true;
         st.reads_back = true;
         run_plainly(st, op);
+    }
+
+    // DFT / STFT: read_dft_node's / read_stft_node's checks at load.  dft_length, axis, frame_step and frame_length are host values at run time (constants or
+    // shape arithmetic), read as Pad reads its pads; the window is a constant or a device tensor.  Nothing is read back: a step is the twiddle prologue and one
+    // launch of rten_amd/csrc/fft.hip (plus two transposes for a DFT axis other than ndim - 2) and captures.  A DFT whose axis resolves to dim 0 couples the
+    // batch rows (sub-batch chains split dim 0); STFT transforms within a row and never does.
+    void make_fft_step(Step &st, const onnx::Node &n, const onnx::Model &m) {
+        const std::string nm = st.name;
+        auto one_int = [](const Tensor &t, const std::string &what) {
+            if (t.dtype() != DType::I32) throw OpError(OpError::InputCastFailed, "expected int32 tensor");
+            const std::vector<int64_t> v = host_ints(&t, what);
+            if (v.size() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 0 dims");
+            return v[0];
+        };
+        if (n.op_type == "DFT") {
+            const DftNode a = read_dft_node(m, n, nm);
+            st.batch_coupled = a.axis_fixed && a.axis == 0; // (a negative axis that resolves to dim 0, or an axis input, is a run-time fact: below)
+            st.run = [this, a, nm, one_int](Context &c, const InputList &in) {
+                const Tensor &x = require(in, 0);
+                const Tensor *len = get(in, 1), *ax = a.axis_fixed ? nullptr : get(in, 2);
+                const int64_t dft_length = len ? one_int(*len, "DFT: dft_length") : 0;
+                const int64_t axis = a.axis_fixed ? a.axis : (ax ? one_int(*ax, "DFT: axis") : -2);
+                if (x.ndim() > 0 && (axis == 0 || axis + x.ndim() == 0) && runtime_coupled_.empty()) runtime_coupled_ = "DFT \"" + nm + "\" (transforms along dim 0)";
+                OutputList o;
+                o.push_back(dft_tensor(c, x, len != nullptr, dft_length, axis, a.inverse, a.onesided));
+                return o;
+            };
+        } else {
+            const StftNode a = read_stft_node(m, n, nm);
+            st.run = [a, one_int](Context &c, const InputList &in) {
+                const Tensor &signal = require(in, 0);
+                const int64_t frame_step = one_int(require(in, 1), "STFT: frame_step");
+                const Tensor *fl = get(in, 3);
+                const int64_t frame_length = fl ? one_int(*fl, "STFT: frame_length") : 0;
+                OutputList o;
+                o.push_back(stft_tensor(c, signal, frame_step, get(in, 2), fl != nullptr, frame_length, a.onesided));
+                return o;
+            };
+        }
     }
 
     // CumSum / GatherElements / Trilu / Tile: the read_*_node checks at load.  CumSum's axis, Trilu's k and Tile's repeats are host values at run time (constants

@@ -2440,6 +2440,146 @@ struct NonMaxSuppression : Operator {
     }
 };
 
+// ---- DFT and STFT (src/ops/fft.rs:22-373; rten_amd/csrc/fft.hip): float32, one LDS-resident Stockham FFT behind both.  dft_length, axis, frame_step and
+// frame_length are HOST values -- constants or shape arithmetic -- and a device-valued one is refused.  The contract is an error bound against the exact
+// transform (include/rten_hip.h), not bit-identity with the reference's FFT library.  Lengths above RTEN_HIP_FFT_MAX are UnsupportedValue.
+inline bool fft_host_int(const InputList &in, size_t i, const char *op, const char *what, int64_t *value) {
+    const Tensor *t = get(in, i);
+    if (!t) return false;
+    want(*t, DType::I32, "int32");
+    if (t->len() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 0 dims");
+    if (!t->host() || t->host()->is_float)
+        throw OpError(OpError::UnsupportedValue, std::string(op) + ": " + what + " must be a constant or computable from the input shapes (it depends on device data)");
+    *value = t->host()->i.at(0);
+    return true;
+}
+inline void fft_limit(const char *op, const char *what, int64_t n) {
+    if (n > RTEN_HIP_FFT_MAX)
+        throw OpError(OpError::UnsupportedValue, std::string(op) + " " + what + " of length " + std::to_string(n) + " exceeds the limit of " + std::to_string(RTEN_HIP_FFT_MAX) + " points (RTEN_HIP_FFT_MAX)");
+}
+// the reference's checks, in its order (fft.rs:208-258); returns the resolved axis and n_fft
+inline void check_dft(const std::vector<int64_t> &shape, bool has_length, int64_t dft_length, int64_t axis, bool inverse, bool onesided, int *ax_out, int64_t *n_fft_out) {
+    const int nd = (int)shape.size();
+    if (nd < 2) throw OpError(OpError::InvalidValue, "DFT input must have at least 2 dims");
+    const int64_t comp = shape[(size_t)nd - 1];
+    if (comp != 1 && comp != 2) throw OpError(OpError::InvalidValue, "Last dimension of DFT input must have size 1 or 2");
+    const bool irfft = inverse && onesided;
+    if (irfft && comp != 2) throw OpError(OpError::InvalidValue, "Inverse one-sided DFT (IRFFT) requires complex input");
+    if (onesided && !inverse && comp == 2) throw OpError(OpError::InvalidValue, "DFT cannot be one-sided if input is complex");
+    if (axis < INT32_MIN || axis > INT32_MAX) throw OpError(OpError::InvalidValue, "Axis is invalid");
+    const int ax = resolve_axis((int)axis, nd);
+    if (ax == nd - 1) throw OpError(OpError::InvalidValue, "DFT axis cannot be the complex dimension");
+    const int64_t n_in = shape[(size_t)ax];
+    int64_t n_fft;
+    if (has_length) {
+        if (dft_length < 1) throw OpError(OpError::InvalidValue, "dft_length must be >= 1");
+        n_fft = dft_length;
+    } else {
+        n_fft = irfft ? 2 * std::max<int64_t>(n_in - 1, 0) : n_in;
+    }
+    *ax_out = ax;
+    *n_fft_out = n_fft;
+}
+inline Tensor dft_tensor(Context &ctx, const Tensor &x, bool has_length, int64_t dft_length, int64_t axis, bool inverse, bool onesided) {
+    want(x, DType::F32, "float32");
+    int ax = 0;
+    int64_t n_fft = 0;
+    check_dft(x.shape(), has_length, dft_length, axis, inverse, onesided, &ax, &n_fft);
+    fft_limit("DFT", "transform", n_fft);
+    const int nd = x.ndim();
+    const bool irfft = inverse && onesided;
+    const int64_t n_in = x.size(ax), comp = x.size(nd - 1), out_len = (onesided && !inverse) ? n_fft / 2 + 1 : n_fft, out_comp = irfft ? 1 : 2;
+    std::vector<int32_t> fwd, back((size_t)nd);
+    for (int d = 0; d < nd; d++) if (d != ax && d != nd - 1) fwd.push_back(d);
+    fwd.push_back(ax);
+    fwd.push_back(nd - 1);
+    for (int d = 0; d < nd; d++) back[(size_t)fwd[(size_t)d]] = d;
+    std::vector<int64_t> tshape, oshape_t;
+    for (int d = 0; d < nd; d++) tshape.push_back(x.size(fwd[(size_t)d]));
+    oshape_t = tshape;
+    oshape_t[(size_t)nd - 2] = out_len;
+    oshape_t[(size_t)nd - 1] = out_comp;
+    const int64_t lanes = detail::prod(tshape, 0, (size_t)nd - 2);
+    if (ax == nd - 2) {
+        Tensor y(ctx, oshape_t, DType::F32);
+        if (y.len()) ctx.check(rten_hip_dft_f32(ctx.raw(), lanes, n_in, n_fft, (int32_t)comp, inverse ? 1 : 0, onesided ? 1 : 0, (const float *)x.ptr(), (float *)y.ptr()));
+        return y;
+    }
+    // the reference permutes the axis next to the complex dimension, transforms contiguous lanes, and permutes back (fft.rs:275-283, 360-372)
+    if (nd > 6) throw OpError(OpError::UnsupportedValue, "DFT along an axis other than ndim - 2 of more than 6 dims is not supported by the device path");
+    std::vector<int64_t> oshape((size_t)nd);
+    for (int d = 0; d < nd; d++) oshape[(size_t)d] = oshape_t[(size_t)back[(size_t)d]];
+    Tensor y(ctx, oshape, DType::F32);
+    if (y.len()) {
+        Tensor t(ctx, tshape, DType::F32), u(ctx, oshape_t, DType::F32);
+        if (x.len()) ctx.check(rten_hip_transpose_b32(ctx.raw(), nd, x.shape().data(), fwd.data(), x.ptr(), t.ptr()));
+        ctx.check(rten_hip_dft_f32(ctx.raw(), lanes, n_in, n_fft, (int32_t)comp, inverse ? 1 : 0, onesided ? 1 : 0, (const float *)t.ptr(), (float *)u.ptr()));
+        ctx.check(rten_hip_transpose_b32(ctx.raw(), nd, oshape_t.data(), back.data(), u.ptr(), y.ptr()));
+    }
+    return y;
+}
+struct DFT : Operator {
+    bool inverse = false, onesided = false;
+    const char *name() const override { return "DFT"; }
+    int max_inputs() const override { return 3; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0);
+        int64_t dft_length = 0, axis = -2;
+        const bool has_length = fft_host_int(in, 1, "DFT", "dft_length", &dft_length);
+        fft_host_int(in, 2, "DFT", "axis", &axis);
+        OutputList out;
+        out.push_back(dft_tensor(ctx, x, has_length, dft_length, axis, inverse, onesided));
+        return out;
+    }
+};
+// the reference's checks, in its order (fft.rs:30-93); returns batch, signal_len, components and n_fft.  window_len < 0: no window.
+inline void check_stft(const std::vector<int64_t> &signal, int64_t frame_step, int64_t window_len, bool has_frame_length, int64_t frame_length, bool onesided, int64_t *batch,
+                       int64_t *signal_len, int64_t *comp, int64_t *n_fft) {
+    if (signal.size() != 2 && signal.size() != 3) throw OpError(OpError::InvalidValue, "signal must have 2 or 3 dims");
+    *batch = signal[0];
+    *signal_len = signal[1];
+    *comp = signal.size() == 3 ? signal[2] : 1;
+    if (has_frame_length && (frame_length < 1 || frame_length > *signal_len)) throw OpError(OpError::InvalidValue, "frame_length must be in range [1, signal_length]");
+    if (frame_step <= 0) throw OpError(OpError::InvalidValue, "frame_step must be > 0");
+    if (has_frame_length && window_len >= 0 && frame_length != window_len) throw OpError(OpError::InvalidValue, "window length must equal frame_length");
+    if (!has_frame_length && window_len < 0) throw OpError(OpError::InvalidValue, "Either frame_length or window must be set");
+    *n_fft = has_frame_length ? frame_length : window_len;
+    if (*comp != 1 && *comp != 2) throw OpError(OpError::InvalidValue, "Last dimension of signal must have size 1 or 2");
+    if (*comp == 2 && onesided) throw OpError(OpError::InvalidValue, "FFT cannot be one-sided if input is complex");
+    // (a window that is empty or longer than the signal: the reference's frame count is meaningless there)
+    if (*n_fft < 1 || *n_fft > *signal_len) throw OpError(OpError::InvalidValue, "frame_length must be in range [1, signal_length]");
+}
+inline Tensor stft_tensor(Context &ctx, const Tensor &signal, int64_t frame_step, const Tensor *window, bool has_frame_length, int64_t frame_length, bool onesided) {
+    want(signal, DType::F32, "float32");
+    if (window) {
+        want(*window, DType::F32, "float32");
+        if (window->ndim() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 1 dims");
+    }
+    int64_t batch = 0, signal_len = 0, comp = 0, n_fft = 0;
+    check_stft(signal.shape(), frame_step, window ? window->size(0) : -1, has_frame_length, frame_length, onesided, &batch, &signal_len, &comp, &n_fft);
+    fft_limit("STFT", "frame", n_fft);
+    const int64_t n_frames = (signal_len - n_fft) / frame_step + 1, bins = onesided ? n_fft / 2 + 1 : n_fft;
+    Tensor y(ctx, {batch, n_frames, bins, 2}, DType::F32);
+    if (y.len())
+        ctx.check(rten_hip_stft_f32(ctx.raw(), batch, signal_len, (int32_t)comp, frame_step, n_fft, onesided ? 1 : 0, window ? (const float *)window->ptr() : nullptr,
+                                    (const float *)signal.ptr(), (float *)y.ptr()));
+    return y;
+}
+struct STFT : Operator {
+    bool onesided = true;
+    const char *name() const override { return "STFT"; }
+    int max_inputs() const override { return 4; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &signal = require(in, 0);
+        int64_t frame_step = 0, frame_length = 0;
+        if (!fft_host_int(in, 1, "STFT", "frame_step", &frame_step)) throw OpError(OpError::MissingInputs, "");
+        const bool has_frame_length = fft_host_int(in, 3, "STFT", "frame_length", &frame_length);
+        OutputList out;
+        out.push_back(stft_tensor(ctx, signal, frame_step, get(in, 2), has_frame_length, frame_length, onesided));
+        return out;
+    }
+};
+
 // Split (src/ops/split.rs:34-136) of 4-byte tensors, one strided copy per piece: the sizes of input 1 (the opset < 13 `split` attribute arrives
 // there too), else `num_outputs` (opset 18), else the node's output count, as equal chunks of ceil(dim / n) -- the last piece is smaller, and there
 // may be fewer than n pieces (5 split 4 ways gives 3).
@@ -3365,6 +3505,8 @@ class OpRegistry {
         r.register_op<DepthToSpace>("DepthToSpace");
         r.register_op<CumSum>("CumSum");
         r.register_op<NonMaxSuppression>("NonMaxSuppression");
+        r.register_op<DFT>("DFT");
+        r.register_op<STFT>("STFT");
         r.register_op<GatherElements>("GatherElements");
         r.register_op<Trilu>("Trilu");
         r.register_op<Tile>("Tile");

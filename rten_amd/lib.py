@@ -23,6 +23,16 @@ RNN_PATH_AUTO, RNN_PATH_COMPOSED, RNN_PATH_FUSED = 0, 1, 2  # rten_hip_set_rnn_p
 RNN_FUSED_MAX_HIDDEN = 256
 INSTANCE_NORM_PATH_AUTO, INSTANCE_NORM_PATH_STREAMING, INSTANCE_NORM_PATH_RESIDENT = 0, 1, 2  # rten_hip_set_instance_norm_path
 INSTANCE_NORM_RESIDENT_MAX = 32768  # RTEN_HIP_INSTANCE_NORM_RESIDENT_MAX: longest slice (elements) the resident form holds
+FFT_MAX, FFT_GENERIC_RADIX_MAX = 8192, 31  # RTEN_HIP_FFT_MAX (longest DFT / STFT frame), RTEN_HIP_FFT_GENERIC_RADIX_MAX (largest prime factor with a pass of its own)
+
+
+def fft_plan(n: int):
+    """The pass list (radices in order) of a transform of length n: rten_hip_fft_plan.  Needs no device.  ValueError for n < 1 or n > FFT_MAX."""
+    buf = (C.c_int32 * 16)()
+    cnt = load().rten_hip_fft_plan(int(n), buf, 16)
+    if cnt < 0:
+        raise ValueError(f"no FFT plan for length {n}: " + ("above the limit of %d points" % FFT_MAX if -cnt == ERR_UNSUPPORTED else "invalid length"))
+    return [int(buf[i]) for i in range(cnt)]
 # act_kind of rten_hip_activation_f32 / rten_hip_gemm_f32_act / rten_hip_conv2d_f32_act (which also take the three above)
 ACT_SIGMOID, ACT_SILU, ACT_SWISH, ACT_HARD_SIGMOID, ACT_HARD_SWISH, ACT_CLIP, ACT_LEAKY_RELU, ACT_ELU = 3, 4, 5, 6, 7, 8, 9, 10
 # mode / coord_mode / nearest_mode of rten_hip_resize_f32 (RTEN_HIP_RESIZE_*)
@@ -210,6 +220,9 @@ PROTOTYPES = {
     "rten_hip_trilu_b32": (_I32, [_VP, _I32, _I64, _I64, _I64, _I64, _VP, _VP]),
     "rten_hip_tile_b32": (_I32, [_VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_non_max_suppression_f32": (_I32, [_VP, _I32, _I64, _I64, _I64, _VP, _VP, _I32, _I32, C.c_float, C.c_float, _VP, _VP]),
+    "rten_hip_dft_f32": (_I32, [_VP, _I64, _I64, _I64, _I32, _I32, _I32, _VP, _VP]),
+    "rten_hip_stft_f32": (_I32, [_VP, _I64, _I64, _I32, _I64, _I64, _I32, _VP, _VP, _VP]),
+    "rten_hip_fft_plan": (_I32, [_I64, C.POINTER(_I32), _I32]),
     "rten_hip_reduce_sum_strided_f32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_reduce_mean_strided_f32": (_I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
     "rten_hip_reduce_minmax_strided": (_I32, [_VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),

@@ -738,3 +738,79 @@ def detector_head_graph(seed: int = 31, features: int = 6, classes: int = 3, bat
     if expose_operands:
         outs += [value_info("boxes", FLOAT, [batch, "boxes", 4]), value_info("scores", FLOAT, [batch, classes, "boxes"])]
     return model(nodes, ins, outs, inits, opset=13, name="detector_head"), w
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Audio front ends: a Whisper-style log-mel spectrogram from the waveform (STFT), and a DFT -> spectral filter -> inverse DFT round trip
+# ----------------------------------------------------------------------------------------------------------------
+def mel_filterbank(n_fft: int, n_mels: int, sample_rate: float = 16000.0):
+    """[n_fft / 2 + 1, n_mels] float32: triangular filters evenly spaced on the HTK mel scale from 0 Hz to sample_rate / 2, each with unit peak."""
+    bins = n_fft // 2 + 1
+    mel = lambda f: 2595.0 * np.log10(1.0 + f / 700.0)
+    hz = lambda m: 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+    edges = hz(np.linspace(mel(0.0), mel(sample_rate / 2.0), n_mels + 2))
+    freqs = np.arange(bins) * (sample_rate / n_fft)
+    fb = np.zeros((bins, n_mels), np.float64)
+    for j in range(n_mels):
+        lo, mid, hi = edges[j], edges[j + 1], edges[j + 2]
+        fb[:, j] = np.maximum(0.0, np.minimum((freqs - lo) / (mid - lo), (hi - freqs) / (hi - mid)))
+    return fb.astype(np.float32)
+
+
+def hann_window(n: int):
+    """torch.hann_window(n) (periodic), float32."""
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)).astype(np.float32)
+
+
+def log_mel_graph(n_fft: int = 400, hop: int = 160, n_mels: int = 80, batch="batch", samples="samples", expose_stft: bool = False):
+    """wave [batch, samples] -> reflect Pad of n_fft / 2 on both ends of the sample axis -> STFT "stft" (frame_step = hop, a Hann window initializer, onesided)
+    -> re^2 + im^2 -> MatMul with a mel filterbank [bins, n_mels] -> Clip(min 1e-10) -> Log / ln 10 -> Max(l, ReduceMax(l) - 8) -> (l + 4) / 4: the log-mel
+    front end of a Whisper-style model, `log_mel` [batch, frames, n_mels].  `expose_stft` adds the STFT node's output `spectrum` [batch, frames, bins, 2] to
+    the graph outputs.  -> (model bytes, {"window", "mel"})."""
+    w = {"window": hann_window(n_fft), "mel": mel_filterbank(n_fft, n_mels)}
+    bins = n_fft // 2 + 1
+    inits = [tensor("window", w["window"]), tensor("mel", w["mel"]), tensor("pads", np.asarray([0, n_fft // 2, 0, n_fft // 2], np.int64)),
+             tensor("hop", np.asarray(hop, np.int64)), tensor("component_axis", np.asarray([3], np.int64)), tensor("floor", np.asarray(1e-10, np.float32)),
+             tensor("inv_ln10", np.asarray(1.0 / np.log(10.0), np.float32)), tensor("eight", np.asarray(8.0, np.float32)), tensor("four", np.asarray(4.0, np.float32))]
+    nodes = [node("Pad", ["wave", "pads"], ["padded"], name="center", mode="reflect"),
+             node("STFT", ["padded", "hop", "window"], ["spectrum"], name="stft", onesided=1),
+             node("Mul", ["spectrum", "spectrum"], ["squares"], name="squares"),
+             node("ReduceSum", ["squares", "component_axis"], ["power"], name="power", keepdims=0),
+             node("MatMul", ["power", "mel"], ["mel_power"], name="mel"),
+             node("Clip", ["mel_power", "floor"], ["clamped"], name="clamp"),
+             node("Log", ["clamped"], ["ln"], name="ln"),
+             node("Mul", ["ln", "inv_ln10"], ["log10"], name="log10"),
+             node("ReduceMax", ["log10"], ["peak"], name="peak", keepdims=1),
+             node("Sub", ["peak", "eight"], ["range_floor"], name="range_floor"),
+             node("Max", ["log10", "range_floor"], ["floored"], name="floored"),
+             node("Add", ["floored", "four"], ["shifted"], name="shift"),
+             node("Div", ["shifted", "four"], ["log_mel"], name="scale")]
+    outs = [value_info("log_mel", FLOAT, [batch, "frames", n_mels])]
+    if expose_stft:
+        outs.append(value_info("spectrum", FLOAT, [batch, "frames", bins, 2]))
+    return model(nodes, [value_info("wave", FLOAT, [batch, samples])], outs, inits, opset=17, name="log_mel"), w
+
+
+def dft_graph(opset: int = 17, n: int = 12, dft_length: int | None = None, batch="batch", seed: int = 41):
+    """x [batch, n, 1] (real) -> DFT "forward" along the signal axis -> Mul by a real spectral gain [n_fft, 1] -> DFT "inverse" -> `y` [batch, n_fft, 2]; the
+    forward spectrum is the second output `spectrum`.  opset 17 writes the axis as the `axis` attribute (1); opset 20 as the third INPUT (-2), the form the
+    axis took from opset 20 on.  `dft_length` (a constant second input of the forward node) zero-fills or truncates the signal.  -> (model bytes, {"gain"})."""
+    assert opset in (17, 20), opset
+    n_fft = n if dft_length is None else dft_length
+    rng = np.random.default_rng(seed)
+    w = {"gain": rng.uniform(0.25, 1.5, (n_fft, 1)).astype(np.float32)}
+    inits = [tensor("gain", w["gain"])]
+    length = ""
+    if dft_length is not None:
+        inits.append(tensor("dft_length", np.asarray(dft_length, np.int64)))
+        length = "dft_length"
+    if opset == 17:
+        fwd_in, inv_in, attrs = ["x"] + ([length] if length else []), ["filtered"], {"axis": 1}
+    else:
+        inits.append(tensor("axis", np.asarray(-2, np.int64)))
+        fwd_in, inv_in, attrs = ["x", length, "axis"], ["filtered", "", "axis"], {}
+    nodes = [node("DFT", fwd_in, ["spectrum"], name="forward", **attrs),
+             node("Mul", ["spectrum", "gain"], ["filtered"], name="filter"),
+             node("DFT", inv_in, ["y"], name="inverse", inverse=1, **attrs)]
+    outs = [value_info("y", FLOAT, [batch, n_fft, 2]), value_info("spectrum", FLOAT, [batch, n_fft, 2])]
+    return model(nodes, [value_info("x", FLOAT, [batch, n, 1])], outs, inits, opset=opset, name="dft_round_trip"), w

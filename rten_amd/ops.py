@@ -2407,7 +2407,156 @@ class NonMaxSuppression(Operator):
         return True
 
 
-RNN_DIRECTIONS = {"forward": L.RNN_FORWARD, "reverse": L.RNN_REVERSE, "bidirectional": L.RNN_BIDIRECTIONAL}
+def _fft_host_int(t, index, op, what):
+    """get_as::<i32> of a DFT / STFT size operand: absent -> None; a host value (numpy array or Python int) of one element, of any rank.  A device tensor
+    is refused, worded like Pad's: the graph executor hands constants and shape arithmetic over as host values."""
+    if t is None:
+        return None
+    if isinstance(t, DeviceTensor):
+        raise UnsupportedValue(f"{op}: {what} (input {index}) must be a constant or computable from the input shapes (it depends on device data)")
+    a = np.asarray(t)
+    if a.dtype.kind not in "iu":
+        raise OpError("InputCastFailed", "expected int32 tensor")
+    if a.size != 1:
+        raise OpError("InputCastFailed", "expected tensor with 0 dims")
+    return int(a.reshape(()))
+
+
+def _fft_limit(op, what, n):
+    if n > L.FFT_MAX:
+        raise UnsupportedValue(f"{op} {what} of length {n} exceeds the limit of {L.FFT_MAX} points (RTEN_HIP_FFT_MAX)")
+
+
+class DFT(Operator):
+    """src/ops/fft.rs:200-373 (rten_hip_dft_f32): inputs (x [..., n, 1 | 2], dft_length?, axis?), float32; dft_length and axis are host-side operands
+    (axis default -2, the opset-20 form; an opset < 20 node's `axis` attribute arrives as that input).  The lane is truncated or zero-filled to n_fft =
+    dft_length, else the axis length, else 2 * (len - 1) for IRFFT (inverse and onesided: complex half spectrum in, real signal out).  onesided forward
+    (real input only) keeps n_fft / 2 + 1 bins; the inverse scales by 1.0f / n_fft.  An axis other than ndim - 2 is moved there and back with
+    rten_hip_transpose_b32, as the reference permutes.  Lengths above RTEN_HIP_FFT_MAX are UnsupportedValue.  The contract is an error bound against the
+    exact transform (include/rten_hip.h), not bit-identity with the reference's FFT library."""
+
+    def __init__(self, inverse=False, onesided=False):
+        self.inverse, self.onesided = bool(inverse), bool(onesided)
+
+    def max_inputs(self):
+        return 3
+
+    def run(self, ctx, inputs):
+        x = _want(_require(inputs, 0), np.float32)
+        dft_length = _fft_host_int(_get(inputs, 1), 1, "DFT", "dft_length")
+        axis = _fft_host_int(_get(inputs, 2), 2, "DFT", "axis")
+        axis = -2 if axis is None else axis
+        nd = len(x.shape)
+        if nd < 2:
+            raise InvalidValue("DFT input must have at least 2 dims")
+        comp = x.shape[-1]
+        if comp not in (1, 2):
+            raise InvalidValue("Last dimension of DFT input must have size 1 or 2")
+        irfft = self.inverse and self.onesided
+        if irfft and comp != 2:
+            raise InvalidValue("Inverse one-sided DFT (IRFFT) requires complex input")
+        if self.onesided and not self.inverse and comp == 2:
+            raise InvalidValue("DFT cannot be one-sided if input is complex")
+        ax = _resolve_axis(nd, axis)
+        if ax == nd - 1:
+            raise InvalidValue("DFT axis cannot be the complex dimension")
+        n_in = x.shape[ax]
+        if dft_length is not None:
+            if dft_length < 1:
+                raise InvalidValue("dft_length must be >= 1")
+            n_fft = dft_length
+        else:
+            n_fft = 2 * max(n_in - 1, 0) if irfft else n_in
+        _fft_limit("DFT", "transform", n_fft)
+        out_len = n_fft // 2 + 1 if self.onesided and not self.inverse else n_fft
+        out_comp = 1 if irfft else 2
+        fwd = [d for d in range(nd) if d not in (ax, nd - 1)] + [ax, nd - 1]
+        tshape = [x.shape[d] for d in fwd]
+        lanes = int(np.prod(tshape[:-2], dtype=np.int64))
+        oshape_t = tshape[:-2] + [out_len, out_comp]
+        flags = (1 if self.inverse else 0, 1 if self.onesided else 0)
+        if ax == nd - 2:
+            y = DeviceTensor(ctx, oshape_t, np.float32)
+            if y.size:
+                ctx.call("rten_hip_dft_f32", lanes, n_in, n_fft, comp, *flags, x.vp, y.vp)
+            return [y]
+        if nd > 6:
+            raise UnsupportedValue("DFT along an axis other than ndim - 2 of more than 6 dims is not supported by the device path")
+        back = [fwd.index(d) for d in range(nd)]
+        y = DeviceTensor(ctx, [oshape_t[back[d]] for d in range(nd)], np.float32)
+        if y.size:
+            i64 = lambda v: (C.c_int64 * len(v))(*v)
+            i32 = lambda v: (C.c_int32 * len(v))(*v)
+            t, u = DeviceTensor(ctx, tshape, np.float32), DeviceTensor(ctx, oshape_t, np.float32)
+            if x.size:
+                ctx.call("rten_hip_transpose_b32", nd, i64(list(x.shape)), i32(fwd), x.vp, t.vp)
+            ctx.call("rten_hip_dft_f32", lanes, n_in, n_fft, comp, *flags, t.vp, u.vp)
+            ctx.call("rten_hip_transpose_b32", nd, i64(oshape_t), i32(back), u.vp, y.vp)
+        return [y]
+
+    def batch_coupled(self, x_shape, axis=-2):
+        """Sub-batch chains split dim 0: the rows are coupled when the transform runs along it."""
+        return _resolve_axis(len(x_shape), axis) == 0
+
+
+class STFT(Operator):
+    """src/ops/fft.rs:22-133 (rten_hip_stft_f32): inputs (signal [batch, len] or [batch, len, 1 | 2], frame_step, window?, frame_length?), float32;
+    frame_step and frame_length are host-side operands, the window a device tensor or a host array (uploaded).  n_fft is frame_length, else the window's
+    length; frame f is signal[f * frame_step + k] * window[k], read straight from the signal; the output is [batch, n_frames, bins, 2], n_frames =
+    (len - n_fft) / frame_step + 1, bins = n_fft / 2 + 1 when onesided (real signal only).  Frames above RTEN_HIP_FFT_MAX are UnsupportedValue."""
+
+    def __init__(self, onesided=True):
+        self.onesided = bool(onesided)
+
+    def max_inputs(self):
+        return 4
+
+    def run(self, ctx, inputs):
+        signal = _want(_require(inputs, 0), np.float32)
+        frame_step = _fft_host_int(_require(inputs, 1), 1, "STFT", "frame_step")
+        window = _get(inputs, 2)
+        frame_length = _fft_host_int(_get(inputs, 3), 3, "STFT", "frame_length")
+        if window is not None:
+            if not isinstance(window, DeviceTensor):
+                w = np.asarray(window)
+                if w.dtype != np.dtype(np.float32):
+                    raise OpError("InputCastFailed", "expected float32 tensor")
+                window = DeviceTensor.from_numpy(ctx, w)
+            _want(window, np.float32)
+            if len(window.shape) != 1:
+                raise OpError("InputCastFailed", "expected tensor with 1 dims")
+        if len(signal.shape) == 2:
+            batch, signal_len = signal.shape
+            comp = 1
+        elif len(signal.shape) == 3:
+            batch, signal_len, comp = signal.shape
+        else:
+            raise InvalidValue("signal must have 2 or 3 dims")
+        if frame_length is not None and not 1 <= frame_length <= signal_len:
+            raise InvalidValue("frame_length must be in range [1, signal_length]")
+        if frame_step <= 0:
+            raise InvalidValue("frame_step must be > 0")
+        if frame_length is not None and window is not None and frame_length != window.shape[0]:
+            raise InvalidValue("window length must equal frame_length")
+        n_fft = frame_length if frame_length is not None else (window.shape[0] if window is not None else None)
+        if n_fft is None:
+            raise InvalidValue("Either frame_length or window must be set")
+        if comp not in (1, 2):
+            raise InvalidValue("Last dimension of signal must have size 1 or 2")
+        if comp == 2 and self.onesided:
+            raise InvalidValue("FFT cannot be one-sided if input is complex")
+        if not 1 <= n_fft <= signal_len:  # (a window that is empty or longer than the signal: the reference's frame count is meaningless there)
+            raise InvalidValue("frame_length must be in range [1, signal_length]")
+        _fft_limit("STFT", "frame", n_fft)
+        n_frames = (signal_len - n_fft) // frame_step + 1
+        bins = n_fft // 2 + 1 if self.onesided else n_fft
+        y = DeviceTensor(ctx, (batch, n_frames, bins, 2), np.float32)
+        if y.size:
+            ctx.call("rten_hip_stft_f32", batch, signal_len, comp, frame_step, n_fft, 1 if self.onesided else 0, _vp(window), signal.vp, y.vp)
+        return [y]
+
+
+RNN_DIRECTIONS = {"forward":L.RNN_FORWARD, "reverse": L.RNN_REVERSE, "bidirectional": L.RNN_BIDIRECTIONAL}
 
 
 def _rnn_dims(t, ndim, what, names=None):
@@ -2518,7 +2667,7 @@ class OpRegistry:
                    Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK, GRU, LSTM, Neg, Abs, Sign, Floor, Ceil, Round, Sqrt, Reciprocal, Exp, Log, Softplus,
                    Pow, PRelu, Min, Max, Sum, Mean, Pad, QuantizeLinear, DequantizeLinear, ReduceL1, ReduceL2, ReduceSumSquare, ReduceLogSum, ReduceLogSumExp,
                    ReduceProd, LpNormalization, GlobalMaxPool, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile,
-                   NonMaxSuppression):
+                   NonMaxSuppression, DFT, STFT):
             r.register_op(op)
         return r
 

@@ -586,6 +586,26 @@ def main():
              (lambda: ctx.call("rten_hip_conv2d_int8", C.byref(d), xq.vp, wq.vp, xz.vp, wz.vp, None, None, None, 0, out.vp)),
              2.0 * 32 * o_ * c_ * k_ * k_ * oh * oh, I8_PEAK_TOPS, "TOP/s")
 
+    # ---- DFT / STFT (rten_amd/csrc/fft.hip): one LDS-resident Stockham FFT per lane; a call is the twiddle prologue plus one transform launch.  The HBM bound
+    # is for the bytes the call must move: the signal once, the output once (overlapping STFT frames re-read the signal from cache, not from HBM).
+    if want("fft:"):
+        for b_ in (1, 8):
+            sig, win = dev(rng.standard_normal((b_, 480000), dtype=np.float32)), dev(np.hanning(401)[:400].astype(np.float32))
+            frames = (480000 - 400) // 160 + 1
+            spec = empty((b_, frames, 201, 2))
+            hbm("fft: STFT 30 s of 16 kHz audio, n_fft 400, hop 160, Hann window, onesided", f"{b_}x480000 -> {b_}x{frames}x201x2",
+                (lambda: ctx.call("rten_hip_stft_f32", b_, 480000, 1, 160, 400, 1, win.vp, sig.vp, spec.vp)), 4.0 * b_ * (480000 + frames * 201 * 2))
+            del sig, spec
+        xc_, yc_ = dev(rng.standard_normal((4096, 1024, 2), dtype=np.float32)), empty((4096, 1024, 2))
+        for inv in (0, 1):
+            hbm(f"fft: DFT complex {'inverse' if inv else 'forward'}", "4096 lanes x 1024", (lambda: ctx.call("rten_hip_dft_f32", 4096, 1024, 1024, 2, inv, 0, xc_.vp, yc_.vp)),
+                4.0 * 4096 * 1024 * 4)
+        xr_, yr_ = dev(rng.standard_normal((4096, 400, 1), dtype=np.float32)), empty((4096, 201, 2))
+        hbm("fft: RFFT (real input, onesided)", "4096 lanes x 400 -> 201 bins", (lambda: ctx.call("rten_hip_dft_f32", 4096, 400, 400, 1, 0, 1, xr_.vp, yr_.vp)), 4.0 * 4096 * (400 + 201 * 2))
+        hbm("fft: strided copy of the DFT's bytes (yardstick)", "4096x2048", (lambda: ctx.call("rten_hip_copy_strided_b32", 2, (C.c_int64 * 2)(4096, 2048), (C.c_int64 * 2)(2048, 1), xc_.vp, yc_.vp)),
+            8.0 * 4096 * 2048)
+        del xc_, yc_, xr_, yr_
+
     if args.cpu_baseline:
         sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         import bench  # the oracle is only ever touched through bench.py's cpu_baseline leg

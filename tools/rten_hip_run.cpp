@@ -16,7 +16,7 @@
 //     -t, --timing           per-operator table (each operator followed by a sync)
 //     --tune                 time the candidate launch plans of every f32 convolution at load and keep the fastest
 //     --graph                capture one run into a hipGraph and replay it for the timed runs (refused, by node name, for a graph with a NonMaxSuppression node)
-//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow, Reduce*, LpNormalization, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile, NonMaxSuppression and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
+//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow, Reduce*, LpNormalization, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile, NonMaxSuppression, DFT, STFT and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
 //     --safetensors-info F   list the tensors of a Safetensors file (with --save-outputs: re-write it); no model, no GPU
 //
 // There is no CPU fallback: without an MI355X the tool reports BackendUnavailable and exits 2.
@@ -204,6 +204,22 @@ int main(int argc, char **argv) {
                 std::printf("  nms step \"%s\": %s boxes, max_output_boxes_per_class %s, iou_threshold %s, score_threshold %s; reads the row count back (eager runs only, no capture, no sub-batch chains)\n",
                             n.name.c_str(), a.center_point_box ? "[cx, cy, w, h]" : "[y1, x1, y2, x2]", a.has_max ? "from input 2" : "absent (no limit)", a.has_iou ? "from input 3" : "0",
                             a.has_score ? "from input 4" : "0");
+            }
+        }
+        {
+            const onnx::Model c = Graph::canonical_form(m); // DFT / STFT: the loader's checks
+            for (auto &n : c.nodes) {
+                if (!(n.domain.empty() || n.domain == "ai.onnx") || (n.op_type != "DFT" && n.op_type != "STFT")) continue;
+                const std::string label = n.name.empty() ? n.outputs.at(0) : n.name;
+                if (n.op_type == "DFT") {
+                    const Graph::DftNode a = Graph::read_dft_node(c, n, label);
+                    std::printf("  fft step \"%s\": DFT inverse %d, onesided %d, axis %s\n", n.name.c_str(), a.inverse ? 1 : 0, a.onesided ? 1 : 0,
+                                a.axis_fixed ? std::to_string(a.axis).c_str() : (n.inputs.size() > 2 && !n.inputs[2].empty() ? "from input 2" : "-2"));
+                } else {
+                    const Graph::StftNode a = Graph::read_stft_node(c, n, label);
+                    std::printf("  fft step \"%s\": STFT onesided %d, window %s, frame_length %s\n", n.name.c_str(), a.onesided ? 1 : 0, a.has_window ? "from input 2" : "absent",
+                                a.has_frame_length ? "from input 3" : "the window's length");
+                }
             }
         }
         {

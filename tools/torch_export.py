@@ -80,11 +80,48 @@ def _register_index_symbolics():
     _INDEX_SYMBOLICS_REGISTERED = True
 
 
+_STFT_SYMBOLIC_REGISTERED = False
+
+
+def _register_stft_symbolic():
+    """aten::stft -> STFT, as a custom symbolic.  PyTorch has it in its symbolic_opset17 module, which the exporter does not load on its own (without it
+    torch.stft fails with "ONNX export of stft in opset 9"), and importing that module whole would change how other operators export for the rest of the process
+    (layer_norm becomes a LayerNormalization node, ...): the reason _register_index_symbolics gives.  So only this one is registered, with the body PyTorch
+    gives it for what the builders here use: a [batch, signal] input and a window of n_fft values.  frame_step and frame_length are int64 Constants, the
+    window is Cast to the signal's type, and the [batch, frames, bins, 2] result is transposed to torch.stft's [batch, bins, frames, 2]."""
+    global _STFT_SYMBOLIC_REGISTERED
+    if _STFT_SYMBOLIC_REGISTERED:
+        return
+    import torch
+    from torch.onnx._internal.torchscript_exporter import symbolic_helper as SH
+
+    @SH.parse_args("v", "i", "i", "i", "v", "b", "b", "b", "b")
+    def stft(g, input, n_fft, hop_length=None, win_length=None, window=None, normalized=False, onesided=True, return_complex=False, align_to_window=None):
+        if return_complex:
+            return SH._unimplemented("stft", "complex types")
+        if align_to_window is not None:
+            return SH._unimplemented("stft", "the align_to_window option")
+        if SH._get_tensor_rank(input) != 2 or SH._is_none(window) or SH._get_tensor_dim_size(window, dim=0) != n_fft:
+            return SH._unimplemented("stft", "anything but a [batch, signal] input with a window of n_fft values")
+        frame_step = g.op("Constant", value_t=torch.tensor(hop_length if hop_length is not None else n_fft // 4, dtype=torch.int64))
+        frame_length = g.op("Constant", value_t=torch.tensor(n_fft, dtype=torch.int64))
+        window = g.op("Cast", window, to_i=1)  # (FLOAT: the signal's type)
+        result = g.op("STFT", input, frame_step, window, frame_length, onesided_i=1 if onesided is None or onesided else 0)
+        result = g.op("Transpose", result, perm_i=[0, 2, 1, 3])
+        if normalized:
+            result = g.op("Div", result, g.op("Constant", value_t=torch.sqrt(torch.tensor(n_fft, dtype=torch.float32))))
+        return result
+
+    torch.onnx.register_custom_op_symbolic("aten::stft", stft, 17)
+    _STFT_SYMBOLIC_REGISTERED = True
+
+
 def export_bytes(model, args, input_names, output_names, dynamic_axes=None, opset: int = 17) -> bytes:
     import torch
     import torch.onnx._internal.torchscript_exporter.utils as TU
     import torch.onnx._internal.torchscript_exporter.symbolic_opset16  # noqa: F401  (registers grid_sampler -> GridSample; without it F.grid_sample is UnsupportedOperatorError)
     _register_index_symbolics()
+    _register_stft_symbolic()
     from torch.onnx._internal.torchscript_exporter._globals import GLOBALS
     warnings.filterwarnings("ignore")
     GLOBALS.export_onnx_opset_version = opset
@@ -965,3 +1002,34 @@ if __name__ == "__main__":
         data = bert_onnx(bert_module())
     open(path, "wb").write(data)
     print(f"wrote {path}: {len(data)} bytes")
+
+
+def log_mel_module(n_fft: int = 400, hop: int = 160, n_mels: int = 80):
+    """The log-mel front end of a Whisper-style model: torch.stft(center=True, reflect) -> re^2 + im^2 -> mel MatMul -> clamp -> log10 -> maximum(l, l.max() - 8)
+    -> (l + 4) / 4, with onnx_writer's Hann window and mel filterbank.  wave [batch, samples] -> [batch, frames, n_mels].  -> (module, {"window", "mel"})."""
+    import torch
+    from rten_amd import onnx_writer as ow
+    w = {"window": ow.hann_window(n_fft), "mel": ow.mel_filterbank(n_fft, n_mels)}
+
+    class LogMel(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.register_buffer("window", torch.from_numpy(w["window"]))
+            self.register_buffer("mel", torch.from_numpy(w["mel"]))
+
+        def forward(self, wave):
+            s = torch.stft(wave, n_fft, hop, window=self.window, center=True, pad_mode="reflect", return_complex=False)
+            power = s[..., 0] ** 2 + s[..., 1] ** 2
+            l = torch.clamp(power.transpose(1, 2) @ self.mel, min=1e-10).log10()
+            l = torch.maximum(l, l.max() - 8.0)
+            return (l + 4.0) / 4.0
+
+    return LogMel(), w
+
+
+def log_mel_onnx(n_fft: int = 400, hop: int = 160, n_mels: int = 80, batch: int = 2, samples: int = 2000):
+    """log_mel_module through PyTorch's exporter at opset 17, input `wave` [batch, samples] (both dynamic), output `log_mel`.  -> (model bytes, weights)."""
+    import torch
+    model, w = log_mel_module(n_fft, hop, n_mels)
+    wave = torch.zeros(batch, samples)
+    return export_bytes(model, (wave,), ["wave"], ["log_mel"], {"wave": {0: "batch", 1: "samples"}, "log_mel": {0: "batch", 1: "frames"}}, opset=17), w
