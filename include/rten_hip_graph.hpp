@@ -2168,157 +2168,274 @@ class Graph {
                 m.initializers = std::move(kept);
             }
         }
-        std::map<std::string, size_t> producer, uses;
-        std::map<std::string, const onnx::TensorProto *> inits;
-        auto index = [&] {
-            producer.clear(); uses.clear(); inits.clear();
-            for (size_t i = 0; i < m.nodes.size(); i++) {
-                if (m.nodes[i].op_type.empty()) continue;
-                for (auto &o : m.nodes[i].outputs) if (!o.empty()) producer[o] = i;
-                for (auto &in : m.nodes[i].inputs) if (!in.empty()) uses[in]++;
-            }
-            for (auto &o : m.outputs) uses[o.name] += 2; // a graph output is never an interior value of a pattern
-            for (auto &t : m.initializers) inits[t.name] = &t;
-        };
-        index();
-        auto scalar = [&](const std::string &v, float &out) {
-            auto it = inits.find(v);
-            if (it == inits.end() || it->second->data_type != onnx::FLOAT || it->second->len() != 1 || it->second->raw.size() != 4) return false;
-            std::memcpy(&out, it->second->raw.data(), 4);
-            return true;
-        };
-        auto is_init = [&](const std::string &v) { return inits.count(v) != 0; };
-        auto node_of = [&](const std::string &v, const char *op, bool interior = true) -> onnx::Node * { // producer of v if it is `op` (and v has one use)
-            auto it = producer.find(v);
-            if (it == producer.end() || m.nodes[it->second].op_type != op) return nullptr;
-            if (interior && uses[v] != 1) return nullptr;
-            return &m.nodes[it->second];
-        };
-        // binary node with one operand equal to a scalar constant c (|c - want| tiny); returns the other operand
-        auto with_scalar = [&](onnx::Node *n, float want, bool commutative, std::string &other) {
-            if (!n || n->inputs.size() != 2) return false;
-            for (int k = 0; k < (commutative ? 2 : 1); k++) {
-                float c;
-                const std::string &cs = n->inputs[(size_t)(commutative ? k : 1)], &os = n->inputs[(size_t)(commutative ? 1 - k : 0)];
-                if (scalar(cs, c) && std::fabs(c - want) <= 1e-6f * std::fabs(want)) { other = os; return true; }
-            }
-            return false;
-        };
-        auto last_axis_mean = [&](onnx::Node *n) {
-            if (!n || n->inputs.empty() || n->get_int("keepdims", 1) != 1) return false;
-            std::vector<int> axes = n->get_ints("axes", {});
-            if (axes.empty() && n->inputs.size() > 1 && is_init(n->inputs[1])) { // opset >= 18: axes as a constant input (ReduceMeanAxesFusion)
-                const onnx::TensorProto *t = inits[n->inputs[1]];
-                if (t->data_type == onnx::INT64 && t->len() == 1 && t->raw.size() == 8) { int64_t a; std::memcpy(&a, t->raw.data(), 8); axes = {(int)a}; }
-            }
-            return axes.size() == 1 && axes[0] == -1;
-        };
-        // ---- Silu / Swish: x * Sigmoid(x) -> Silu, x * Sigmoid(alpha * x) -> Swish(alpha), either operand order (SiluFusion / SwishFusion,
-        //      optimize/fusions.rs:567-615, run before GeluFusion).  Silu divides where the pair multiplies by a reciprocal: the bits change.
-        for (size_t i = 0; i < m.nodes.size(); i++) {
-            onnx::Node &mul = m.nodes[i];
-            if (mul.op_type != "Mul" || mul.inputs.size() != 2) continue;
-            for (int k = 0; k < 2; k++) {
-                onnx::Node *sig = node_of(mul.inputs[(size_t)k], "Sigmoid");
-                if (!sig || sig->inputs.size() != 1) continue;
-                const std::string x = mul.inputs[(size_t)(1 - k)];
-                onnx::Node f;
-                onnx::Node *scale = nullptr;
-                if (sig->inputs[0] == x) {
-                    f.op_type = "Silu";
-                } else {
-                    scale = node_of(sig->inputs[0], "Mul");
-                    float alpha = 0.f;
-                    if (!scale || scale->inputs.size() != 2) continue;
-                    const int j = scale->inputs[0] == x ? 0 : (scale->inputs[1] == x ? 1 : -1);
-                    if (j < 0 || !scalar(scale->inputs[(size_t)(1 - j)], alpha)) continue;
-                    f.op_type = "Swish";
-                    onnx::Attr a;
-                    a.name = "alpha"; a.type = 1; a.f = alpha;
-                    f.attrs = {a};
-                }
-                f.name = mul.name.empty() ? (f.op_type == "Silu" ? "silu" : "swish") : mul.name;
-                f.inputs = {x};
-                f.outputs = mul.outputs;
-                sig->op_type.clear();
-                if (scale) scale->op_type.clear();
-                mul = f;
-                index();
-                break;
-            }
+        { // (the nodes taken out above go first: the matcher below indexes the list)
+            std::vector<onnx::Node> live;
+            for (auto &n : m.nodes) if (!n.op_type.empty()) live.push_back(std::move(n));
+            m.nodes = std::move(live);
         }
+        // ---- Silu / Swish / Gelu / LayerNormalization, matched and applied by the reference's own rules (tests/fusion_rules.py restates them with
+        //      their cites and tests/test_fusion_rules.py pins them):
+        //   * operator name and operand count; a commutative binary operator in either order; Add / Mul chains of >= 3 pattern operands as a
+        //     multiset under any bracketing (pattern_matcher.rs:139-197); one symbol, one value; float constants of one element within ABSOLUTE 1e-4;
+        //   * operators visited last to first, the first fusion in list order that matches wins; a fusion whose operators an earlier one of the
+        //     round has claimed is skipped; one whose interior values are read elsewhere or are graph outputs is dropped AFTER claiming its operators
+        //     for the round; rounds repeat while one applied, three at the most (optimize.rs:119-260, 611-660).
+        //   A ReduceMean whose axes are a rank-1 constant input counts as the attribute form from the round after ReduceMeanAxesFusion (fusions.rs:371-404) took it.
+        struct Pat {
+            enum Kind { Op, Const, Sym, Any } kind = Op;
+            std::string name, key;  // Op: operator name and optional key; Sym: the symbol
+            std::vector<Pat> in;    // Op: operand patterns; Any: alternatives, tried left to right
+            float value = 0.f;      // Const, tolerance 1e-4
+            bool constant = false;  // Sym: matches constants only
+            static Pat op(const char *name, std::vector<Pat> in, const char *key = "") { Pat p; p.name = name; p.in = std::move(in); p.key = key; return p; }
+            static Pat c(float v) { Pat p; p.kind = Const; p.value = v; return p; }
+            static Pat sym(const char *name, bool constant = false) { Pat p; p.kind = Sym; p.name = name; p.constant = constant; return p; }
+            static Pat any(std::vector<Pat> alts) { Pat p; p.kind = Any; p.in = std::move(alts); return p; }
+        };
+        typedef std::vector<std::pair<std::string, std::string>> Syms; // symbol or key -> value name (for a key: the output of the operator)
+        struct Matcher {
+            const onnx::Model &m;
+            std::map<std::string, size_t> producer;
+            std::map<std::string, std::vector<size_t>> consumers;
+            std::map<std::string, const onnx::TensorProto *> inits;
+            std::set<std::string> graph_outs;
+            const std::set<std::string> &attr_form; // outputs of the ReduceMean nodes whose constant axes input counts as the attribute
+            Matcher(const onnx::Model &model, const std::set<std::string> &converted) : m(model), attr_form(converted) {
+                for (size_t i = 0; i < m.nodes.size(); i++) {
+                    for (auto &o : m.nodes[i].outputs) if (!o.empty()) producer[o] = i;
+                    for (auto &in : m.nodes[i].inputs) if (!in.empty()) consumers[in].push_back(i);
+                }
+                for (auto &t : m.initializers) inits[t.name] = &t;
+                for (auto &o : m.outputs) graph_outs.insert(o.name);
+            }
+            bool is_const(const std::string &v) const { return inits.count(v) != 0; }
+            long made_by(const std::string &v) const { auto it = producer.find(v); return is_const(v) || it == producer.end() ? -1 : (long)it->second; }
+            bool scalar(const std::string &v, float &out) const { // one element at any rank (TensorView::item)
+                auto it = inits.find(v);
+                if (it == inits.end() || it->second->data_type != onnx::FLOAT || it->second->len() != 1 || it->second->raw.size() != 4) return false;
+                std::memcpy(&out, it->second->raw.data(), 4);
+                return true;
+            }
+            bool axes_of(const onnx::Node &n, std::vector<int64_t> &axes) const { // the attribute, or a rank-1 int64 constant input
+                axes.clear();
+                if (n.inputs.size() == 2 && !n.inputs[1].empty()) {
+                    auto it = inits.find(n.inputs[1]);
+                    if (it == inits.end() || it->second->data_type != onnx::INT64 || it->second->dims.size() != 1 || it->second->raw.size() != 8 * (size_t)it->second->len()) return false;
+                    axes.resize((size_t)it->second->len());
+                    if (!axes.empty()) std::memcpy(axes.data(), it->second->raw.data(), it->second->raw.size());
+                    return true;
+                }
+                const onnx::Attr *a = n.attr("axes");
+                if (!a) return false;
+                axes = a->ints;
+                return true;
+            }
+            // a ReduceMean that an earlier round has turned into the attribute form (ReduceMeanAxesFusion) has one operand for the patterns
+            size_t arity(const onnx::Node &n) const { return n.op_type == "ReduceMean" && n.inputs.size() == 2 && attr_form.count(n.outputs.at(0)) ? 1 : n.inputs.size(); }
+            static bool commutative(const std::string &op) { return op == "Add" || op == "Mul" || op == "And" || op == "Or" || op == "Xor" || op == "Equal"; }
+            static bool associative(const std::string &op) { return op == "Add" || op == "Mul"; }
+            static const std::string *find(const Syms &s, const std::string &name) { for (auto &kv : s) if (kv.first == name) return &kv.second; return nullptr; }
+            static void flatten_pattern(const Pat &p, const std::string &name, std::vector<const Pat *> &out) {
+                if (p.kind == Pat::Op && p.name == name && p.in.size() == 2 && p.key.empty()) for (auto &q : p.in) flatten_pattern(q, name, out);
+                else out.push_back(&p);
+            }
+            void flatten_graph(const std::string &v, const std::string &name, std::vector<std::string> &out) const {
+                const long i = made_by(v);
+                if (i >= 0 && m.nodes[(size_t)i].op_type == name && m.nodes[(size_t)i].inputs.size() == 2 && !m.nodes[(size_t)i].inputs[0].empty() && !m.nodes[(size_t)i].inputs[1].empty())
+                    for (auto &s : m.nodes[(size_t)i].inputs) flatten_graph(s, name, out);
+                else out.push_back(v);
+            }
+            bool match_set(const std::vector<const Pat *> &pats, size_t at, const std::vector<std::string> &vals, std::vector<bool> &used, Syms &syms) const {
+                if (at == pats.size()) return true;
+                for (size_t i = 0; i < vals.size(); i++) {
+                    if (used[i]) continue;
+                    const size_t mark = syms.size();
+                    if (test(*pats[at], vals[i], syms)) {
+                        used[i] = true;
+                        if (match_set(pats, at + 1, vals, used, syms)) return true;
+                        used[i] = false;
+                    }
+                    syms.resize(mark);
+                }
+                return false;
+            }
+            bool match_op(const Pat &p, size_t idx, Syms &syms) const {
+                const onnx::Node &n = m.nodes[idx];
+                if (!(n.domain.empty() || n.domain == "ai.onnx") || n.op_type != p.name || p.in.size() != arity(n)) return false;
+                const bool both = p.in.size() == 2 && !n.inputs[0].empty() && !n.inputs[1].empty();
+                if (associative(p.name) && commutative(p.name) && p.in.size() == 2) {
+                    std::vector<const Pat *> pats;
+                    for (auto &q : p.in) flatten_pattern(q, p.name, pats);
+                    if (pats.size() >= 3) {
+                        std::vector<std::string> vals;
+                        if (both) for (auto &s : n.inputs) flatten_graph(s, p.name, vals);
+                        std::vector<bool> used(vals.size(), false);
+                        if (pats.size() == vals.size() && match_set(pats, 0, vals, used, syms)) return true;
+                    }
+                }
+                if (commutative(p.name) && both) {
+                    const size_t mark = syms.size();
+                    if (test(p.in[0], n.inputs[0], syms) && test(p.in[1], n.inputs[1], syms)) return true;
+                    syms.resize(mark);
+                    return test(p.in[1], n.inputs[0], syms) && test(p.in[0], n.inputs[1], syms);
+                }
+                for (size_t k = 0; k < p.in.size(); k++) if (n.inputs[k].empty() || !test(p.in[k], n.inputs[k], syms)) return false;
+                return true;
+            }
+            bool test(const Pat &p, const std::string &v, Syms &syms) const { // pattern against a value
+                if (p.kind == Pat::Any) {
+                    for (auto &q : p.in) {
+                        const size_t mark = syms.size();
+                        if (test(q, v, syms)) return true;
+                        syms.resize(mark);
+                    }
+                    return false;
+                }
+                if (p.kind == Pat::Op) {
+                    const long i = made_by(v);
+                    if (i < 0 || !match_op(p, (size_t)i, syms)) return false;
+                    if (!p.key.empty()) syms.emplace_back(p.key, v);
+                    return true;
+                }
+                if (p.kind == Pat::Const) { float c; return scalar(v, c) && std::fabs(c - p.value) <= 1e-4f; }
+                if (p.constant && !is_const(v)) return false;
+                if (const std::string *seen = find(syms, p.name)) return *seen == v;
+                syms.emplace_back(p.name, v);
+                return true;
+            }
+            bool match_root(const Pat &p, size_t idx, Syms &syms) const { // pattern against an operator
+                syms.clear();
+                if (p.kind == Pat::Any) {
+                    for (auto &q : p.in) { if (match_root(q, idx, syms)) return true; }
+                    return false;
+                }
+                return p.kind == Pat::Op && match_op(p, idx, syms);
+            }
+            // the rank the reference's shape inference gives a value, as far as the idioms need it: declared for a graph input, carried through broadcasting
+            // binary operators, Sqrt and ReduceMean (binary_elementwise.rs:534,697,949,1120,1184; reduce.rs:579); -1: unknown
+            long rank_of(const std::string &v, int depth = 0) const {
+                if (v.empty() || depth > 16) return -1;
+                auto it = inits.find(v);
+                if (it != inits.end()) return (long)it->second->dims.size();
+                for (auto &in : m.inputs) if (in.name == v) return in.dims.empty() ? -1 : (long)in.dims.size();
+                const long i = made_by(v);
+                if (i < 0) return -1;
+                const onnx::Node &n = m.nodes[(size_t)i];
+                if ((n.op_type == "Add" || n.op_type == "Sub" || n.op_type == "Mul" || n.op_type == "Div" || n.op_type == "Pow") && n.inputs.size() == 2) {
+                    const long a = rank_of(n.inputs[0], depth + 1), b = rank_of(n.inputs[1], depth + 1);
+                    return a < 0 || b < 0 ? -1 : std::max(a, b);
+                }
+                if (n.op_type == "Sqrt" && n.inputs.size() == 1) return rank_of(n.inputs[0], depth + 1);
+                if (n.op_type == "ReduceMean" && !n.inputs.empty()) {
+                    const long r = rank_of(n.inputs[0], depth + 1);
+                    std::vector<int64_t> axes;
+                    if (r < 0 || n.get_int("keepdims", 1) == 1) return r;
+                    return axes_of(n, axes) ? r - (long)axes.size() : -1;
+                }
+                return -1;
+            }
+            bool last_axis_mean(const std::string &mean_out) const { // op_applied_to_last_axis::<ReduceMean> (fusions.rs:643-671)
+                const long i = made_by(mean_out);
+                std::vector<int64_t> axes;
+                if (i < 0 || !axes_of(m.nodes[(size_t)i], axes) || axes.size() != 1) return false;
+                if (axes[0] == -1) return true;
+                const long r = rank_of(m.nodes[(size_t)i].inputs[0]);
+                return r >= 1 && r - 1 == (long)axes[0];
+            }
+        };
         const float sqrt2 = std::sqrt(2.0f);
-        for (size_t i = 0; i < m.nodes.size(); i++) {
-            onnx::Node &last = m.nodes[i];
-            if (last.op_type == "Mul") { // ---- Gelu
-                std::string a, xin, e_plus_1, erf_out, xs, x2;
-                if (!with_scalar(&last, 0.5f, true, a)) continue;
-                onnx::Node *mul = node_of(a, "Mul");
-                if (!mul || mul->inputs.size() != 2) continue;
-                onnx::Node *add = nullptr;
-                for (int k = 0; k < 2 && !add; k++) { add = node_of(mul->inputs[(size_t)k], "Add"); if (add) { e_plus_1 = mul->inputs[(size_t)k]; xin = mul->inputs[(size_t)(1 - k)]; } }
-                if (!add || !with_scalar(add, 1.0f, true, erf_out)) continue;
-                onnx::Node *erf = node_of(erf_out, "Erf");
-                if (!erf || erf->inputs.size() != 1) continue;
-                onnx::Node *scale = node_of(erf->inputs[0], "Div");
-                bool ok = scale && with_scalar(scale, sqrt2, false, x2);
-                if (!ok) { scale = node_of(erf->inputs[0], "Mul"); ok = scale && with_scalar(scale, 1.0f / sqrt2, true, x2); }
-                if (!ok || x2 != xin) continue;
-                onnx::Node g;
-                g.op_type = "Gelu"; g.name = last.name.empty() ? "gelu" : last.name; g.inputs = {xin}; g.outputs = last.outputs;
-                scale->op_type.clear(); erf->op_type.clear(); add->op_type.clear(); mul->op_type.clear();
-                last = g;
-                index();
-            }
-        }
-        for (size_t i = 0; i < m.nodes.size(); i++) { // ---- LayerNormalization: anchored at the scaling Mul
-            onnx::Node &mulnode = m.nodes[i];
-            if (mulnode.op_type != "Mul" || mulnode.inputs.size() != 2) continue;
-            onnx::Node *div = nullptr;
-            std::string scale_name;
-            for (int k = 0; k < 2 && !div; k++)
-                if (is_init(mulnode.inputs[(size_t)(1 - k)])) { div = node_of(mulnode.inputs[(size_t)k], "Div"); scale_name = mulnode.inputs[(size_t)(1 - k)]; }
-            if (!div || div->inputs.size() != 2) continue;
-            onnx::Node *sqrt_n = node_of(div->inputs[1], "Sqrt");
-            auto cit = producer.find(div->inputs[0]);
-            if (!sqrt_n || cit == producer.end() || m.nodes[cit->second].op_type != "Sub" || uses[div->inputs[0]] != 2) continue;
-            onnx::Node *center = &m.nodes[cit->second];
-            onnx::Node *addeps = node_of(sqrt_n->inputs[0], "Add");
-            if (!addeps || addeps->inputs.size() != 2) continue;
-            float eps = 0.f;
-            onnx::Node *mean2 = nullptr;
-            for (int k = 0; k < 2 && !mean2; k++) if (scalar(addeps->inputs[(size_t)k], eps)) mean2 = node_of(addeps->inputs[(size_t)(1 - k)], "ReduceMean");
-            if (!mean2 || !last_axis_mean(mean2)) continue;
-            onnx::Node *pow = node_of(mean2->inputs[0], "Pow");
-            std::string powed;
-            if (!pow || !with_scalar(pow, 2.0f, false, powed) || powed != div->inputs[0]) continue;
-            onnx::Node *mean1 = node_of(center->inputs[1], "ReduceMean");
-            if (!mean1 || !last_axis_mean(mean1) || mean1->inputs[0] != center->inputs[0]) continue;
-            const std::string x = center->inputs[0];
-            onnx::Node ln;
-            ln.op_type = "LayerNormalization";
-            ln.inputs = {x, scale_name};
-            onnx::Node *tail = &mulnode; // optional "+ bias" (a constant): the fused node then takes the Add's place
-            if (uses[mulnode.outputs[0]] == 1)
-                for (size_t j = i + 1; j < m.nodes.size(); j++) {
-                    onnx::Node &c = m.nodes[j];
-                    if (c.op_type != "Add" || c.inputs.size() != 2) continue;
-                    const int k = c.inputs[0] == mulnode.outputs[0] ? 0 : (c.inputs[1] == mulnode.outputs[0] ? 1 : -1);
-                    if (k < 0) continue;
-                    if (is_init(c.inputs[(size_t)(1 - k)])) { ln.inputs.push_back(c.inputs[(size_t)(1 - k)]); tail = &c; }
-                    break;
+        const Pat x = Pat::sym("x");
+        const Pat center = Pat::op("Sub", {x, Pat::op("ReduceMean", {x}, "center_mean")});
+        const Pat normalized = Pat::op("Div", {center, Pat::op("Sqrt", {Pat::op("Add", {Pat::sym("epsilon", true), Pat::op("ReduceMean", {Pat::op("Pow", {center, Pat::c(2.0f)})}, "norm_mean")})})});
+        const Pat scaled = Pat::op("Mul", {normalized, Pat::sym("scale", true)});
+        const std::vector<std::pair<std::string, Pat>> fusions = { // in the reference's list order (optimize.rs:622-629)
+            {"Silu", Pat::op("Mul", {x, Pat::op("Sigmoid", {x})})},
+            {"Swish", Pat::op("Mul", {x, Pat::op("Sigmoid", {Pat::op("Mul", {Pat::sym("alpha", true), x})})})},
+            {"Gelu", Pat::op("Mul", {Pat::op("Mul", {x, Pat::op("Add", {Pat::op("Erf", {Pat::any({Pat::op("Div", {x, Pat::c(sqrt2)}), Pat::op("Mul", {x, Pat::c(1.0f / sqrt2)})})}), Pat::c(1.0f)})}), Pat::c(0.5f)})},
+            {"LayerNormalization", Pat::any({Pat::op("Add", {scaled, Pat::sym("bias", true)}), scaled})},
+        };
+        std::set<std::string> attr_form;
+        for (int round = 0; round < 3; round++) {
+            const Matcher g(m, attr_form);
+            std::set<size_t> claimed, gone;
+            std::set<std::string> converted; // by this round: seen by the patterns from the next round on, as in the reference
+            std::map<size_t, onnx::Node> fused_at;
+            for (size_t idx = m.nodes.size(); idx-- > 0;) {
+                if (claimed.count(idx)) continue;
+                { // ReduceMeanAxesFusion, first in the list: ReduceMean(x, axes constant, a rank-1 integer vector) -> the attribute form.  It spends a round
+                  // and claims the node, as every fusion does; the node itself stays as written (the step builder reads either form).
+                    const onnx::Node &n = m.nodes[idx];
+                    std::vector<int64_t> axes;
+                    if ((n.domain.empty() || n.domain == "ai.onnx") && n.op_type == "ReduceMean" && n.inputs.size() == 2 && n.outputs.size() == 1 && !attr_form.count(n.outputs[0]) && g.axes_of(n, axes)) {
+                        claimed.insert(idx);
+                        converted.insert(n.outputs[0]);
+                        continue;
+                    }
                 }
-            ln.name = tail->name.empty() ? "layer_norm" : tail->name;
-            ln.outputs = tail->outputs;
-            onnx::Attr axis, epsilon;
-            axis.name = "axis"; axis.type = 2; axis.i = -1;
-            epsilon.name = "epsilon"; epsilon.type = 1; epsilon.f = eps;
-            ln.attrs = {axis, epsilon};
-            mean1->op_type.clear(); center->op_type.clear(); pow->op_type.clear(); mean2->op_type.clear(); addeps->op_type.clear(); sqrt_n->op_type.clear();
-            div->op_type.clear();
-            if (tail != &mulnode) mulnode.op_type.clear();
-            *tail = ln;
-            index();
+                for (auto &f : fusions) {
+                    Syms syms;
+                    if (!g.match_root(f.second, idx, syms)) continue;
+                    const onnx::Node &root = m.nodes[idx];
+                    onnx::Node fn;
+                    fn.op_type = f.first;
+                    fn.inputs = {*Matcher::find(syms, "x")};
+                    if (f.first == "Swish") {
+                        onnx::Attr a;
+                        a.name = "alpha"; a.type = 1;
+                        if (!g.scalar(*Matcher::find(syms, "alpha"), a.f)) continue; // "alpha not a scalar"
+                        fn.attrs = {a};
+                    } else if (f.first == "LayerNormalization") {
+                        onnx::Attr axis, epsilon;
+                        axis.name = "axis"; axis.type = 2; axis.i = -1;
+                        epsilon.name = "epsilon"; epsilon.type = 1;
+                        if (!g.last_axis_mean(*Matcher::find(syms, "norm_mean")) || !g.last_axis_mean(*Matcher::find(syms, "center_mean")) || !g.scalar(*Matcher::find(syms, "epsilon"), epsilon.f)) continue;
+                        fn.attrs = {axis, epsilon};
+                        fn.inputs.push_back(*Matcher::find(syms, "scale"));
+                        if (const std::string *bias = Matcher::find(syms, "bias")) fn.inputs.push_back(*bias);
+                    }
+                    std::string lower = f.first == "LayerNormalization" ? "layer_norm" : f.first;
+                    lower[0] = (char)std::tolower(lower[0]);
+                    fn.name = root.name.empty() ? lower : root.name;
+                    fn.outputs = root.outputs;
+                    // the operators between the fused node's inputs and the root
+                    std::vector<size_t> ops, stack = {idx};
+                    while (!stack.empty()) {
+                        const size_t i = stack.back();
+                        stack.pop_back();
+                        if (std::find(ops.begin(), ops.end(), i) != ops.end()) continue;
+                        ops.push_back(i);
+                        for (auto &s : m.nodes[i].inputs)
+                            if (!s.empty() && std::find(fn.inputs.begin(), fn.inputs.end(), s) == fn.inputs.end() && g.made_by(s) >= 0) stack.push_back((size_t)g.made_by(s));
+                    }
+                    std::sort(ops.begin(), ops.end());
+                    bool usable = true;
+                    for (size_t o : ops) { // claimed one by one: what was walked before a clash stays claimed
+                        if (claimed.count(o)) { usable = false; break; }
+                        claimed.insert(o);
+                    }
+                    for (size_t o : ops)
+                        for (auto &v : m.nodes[o].outputs) {
+                            if (!usable || v.empty() || std::find(root.outputs.begin(), root.outputs.end(), v) != root.outputs.end()) continue;
+                            if (g.graph_outs.count(v)) usable = false;
+                            auto us = g.consumers.find(v);
+                            if (us != g.consumers.end()) for (size_t c : us->second) if (!std::binary_search(ops.begin(), ops.end(), c)) usable = false;
+                        }
+                    if (usable) {
+                        for (size_t o : ops) if (o != idx) gone.insert(o);
+                        fused_at[idx] = std::move(fn);
+                    }
+                    break; // the first fusion that matched decides this operator, applied or not
+                }
+            }
+            if (fused_at.empty() && converted.empty()) break;
+            attr_form.insert(converted.begin(), converted.end());
+            std::vector<onnx::Node> next;
+            for (size_t i = 0; i < m.nodes.size(); i++) {
+                auto it = fused_at.find(i);
+                if (it != fused_at.end()) next.push_back(std::move(it->second));
+                else if (!gone.count(i)) next.push_back(std::move(m.nodes[i]));
+            }
+            m.nodes = std::move(next);
         }
         std::vector<onnx::Node> kept;
         for (auto &n : m.nodes) if (!n.op_type.empty()) kept.push_back(std::move(n));
@@ -2549,8 +2666,11 @@ class Graph {
             for (const char *sop : {"Div", "Mul"}) {
                 const long d = nodes.sole_user(cur, sop);
                 float cv = 0.f;
-                if (d < 0 || nodes[d].inputs[0] != cur || at.scale != 1.f || !const_f32_scalar(nodes[d].inputs[1], cv)) continue;
-                at.scale = std::string(sop) == "Div" ? 1.0f / cv : cv;
+                if (d < 0 || at.scale != 1.f || nodes[d].inputs.size() != 2 || nodes[d].inputs[0] == nodes[d].inputs[1]) continue;
+                const bool div = std::string(sop) == "Div";
+                if (nodes[d].inputs[0] != cur && div) continue; // Mul takes the scalar on either side, Div on the right only (MatMulScaleFusion, fusions.rs:884-906)
+                if (!const_f32_scalar(nodes.other_input(nodes[d], cur), cv)) continue;
+                at.scale = div ? 1.0f / cv : cv;
                 covered.push_back((size_t)d);
                 cur = nodes[d].outputs[0];
             }
@@ -2636,16 +2756,53 @@ class Graph {
         st.out = {id_of(at.out)};
         if (!at.lead_check.empty()) st.in.push_back(id_of(at.lead_check)); // (5th operand: the run-time Reshape target, a host value)
         const int lead0 = at.lead0, lead1 = at.lead1;
-        st.run = [op, lead0, lead1](Context &c, const InputList &in) {
+        // A run-time mask with a head axis ([B | 1, H, S, T]: a relative-position or per-head bias fed as an input) is outside the kernel's forms, and the plan
+        // cannot know it: the step then runs the operators it covers plainly, in graph order -- head-split views, Transpose, MatMul with the scale as
+        // FusedMatMul's alpha (MatMulScaleFusion), Add, Softmax, MatMul, Transpose, head-merge view -- which are the interpreter's bits.  Launches only: capture-safe.
+        auto plain = [op](Context &c, const InputList &in) {
+            const Tensor &q = require(in, 0), &k = require(in, 1), &v = require(in, 2);
+            if (q.ndim() != 3 || k.ndim() != 3 || v.ndim() != 3) throw OpError(OpError::InvalidValue, "expected [batch, seq, hidden] projections");
+            const int64_t B = q.size(0), S = q.size(1), T = k.size(1), Hd = op->width ? op->width : q.size(2);
+            const int64_t heads = op->heads > 0 ? op->heads : (op->head_dim > 0 && Hd % op->head_dim == 0 ? Hd / op->head_dim : 0);
+            if (heads <= 0 || Hd % heads != 0) throw OpError(OpError::InvalidValue, "hidden size is not divisible by the number of heads");
+            if (k.size(0) != B || v.size(0) != B || v.size(1) != T || (!op->width && (k.size(2) != Hd || v.size(2) != Hd)))
+                throw OpError(OpError::IncompatibleInputShapes, "q / k / v batch, sequence or hidden sizes do not match");
+            const int64_t d = Hd / heads;
+            auto split = [&](const Tensor &t, int64_t off, std::vector<int> perm) { // a column block of the merged projection is sliced out first
+                Tensor block = op->width ? slice_tensor(c, t, {{0, t.size(0), 1}, {0, t.size(1), 1}, {off, Hd, 1}}) : Tensor::view_of(t, t.shape());
+                const Tensor heads4 = Tensor::view_of(block, {t.size(0), t.size(1), heads, d});
+                Transpose tr;
+                tr.perm = std::move(perm);
+                return tr.run(c, {&heads4});
+            };
+            const OutputList qh = split(q, op->q_off, {0, 2, 1, 3}), kh = split(k, op->k_off, {0, 2, 3, 1}), vh = split(v, op->v_off, {0, 2, 1, 3});
+            FusedMatMul qk;
+            qk.alpha = op->scale;
+            const OutputList scores = qk.run(c, {&qh[0], &kh[0]});
+            const OutputList sum = Add().run(c, {&scores[0], &require(in, 3)});
+            const OutputList probs = Softmax().run(c, {&sum[0]});
+            const OutputList ctx4 = MatMul().run(c, {&probs[0], &vh[0]});
+            Transpose back;
+            back.perm = {0, 2, 1, 3};
+            OutputList out = back.run(c, {&ctx4[0]});
+            out[0].reshape({B, S, Hd});
+            return out;
+        };
+        auto run_attention = [op, plain](Context &c, const InputList &in) {
+            const Tensor *mask = in.size() > 3 ? in[3] : nullptr;
+            const bool head_axis = mask && mask->ndim() >= 3 && mask->ndim() <= 4 && mask->size(mask->ndim() - 3) != 1;
+            return head_axis ? plain(c, in) : op->run(c, in);
+        };
+        st.run = [run_attention, lead0, lead1](Context &c, const InputList &in) {
             if (lead0 && (require(in, 0).ndim() != 3 || require(in, 0).size(0) != lead0 || require(in, 0).size(1) != lead1))
                 throw OpError(OpError::InvalidValue, "fused attention: the graph's Reshape spells out leading dims that differ from the projection's");
             if (in.size() > 4 && in[4]) { // the Reshape target the graph computes at run time must say what the fusion assumed: [B, S, ..] of the projection
                 const std::vector<int64_t> tgt = host_ints(in[4], "fused attention: the head-split Reshape's target");
                 if (require(in, 0).ndim() != 3 || tgt.size() != 4 || tgt[0] != require(in, 0).size(0) || tgt[1] != require(in, 0).size(1))
                     throw OpError(OpError::InvalidValue, "fused attention: the graph's Reshape target differs from the projection's leading dims");
-                return op->run(c, InputList(in.begin(), in.begin() + 4));
+                return run_attention(c, InputList(in.begin(), in.begin() + 4));
             }
-            return op->run(c, in);
+            return run_attention(c, in);
         };
         steps_.push_back(std::move(st));
     }

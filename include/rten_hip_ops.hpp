@@ -1940,7 +1940,9 @@ struct Mean : Variadic {
         if (!divisor_ || divisor_n_ != n || divisor_ctx_ != &ctx) {
             if (rten_hip_capture_active(ctx.raw())) throw OpError(OpError::UnsupportedValue, "Mean: the divisor must be uploaded before the run is captured");
             const float d = (float)n;
-            divisor_ = std::make_shared<Tensor>(Tensor::from_host<float>(ctx, {}, &d));
+            // (unpooled, as Div's reciprocals: a copy kept across runs must not come out of the pool -- taking the 4-byte buffer that an earlier step of the
+            // warm-up run gave back would leave the captured run one buffer short, and an allocation inside a capture is refused)
+            divisor_ = std::make_shared<Tensor>(Tensor::from_host_unpooled<float>(ctx, {}, &d));
             divisor_n_ = n;
             divisor_ctx_ = &ctx;
         }
