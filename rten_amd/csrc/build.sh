@@ -9,7 +9,7 @@ pids=()
 for f in *.hip; do
   o=../_build/${f%.hip}.o
   if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ internal.h -nt "$o" ] || [ vecmath.h -nt "$o" ] || [ rowreduce.h -nt "$o" ] || [ slice.h -nt "$o" ] || [ ../../include/rten_hip.h -nt "$o" ] || \
-     { [ "${f#gemm_f32}" != "$f" ] && [ gemm_f32_common.h -nt "$o" ]; }; then
+     { [ "${f#gemm_f32}" != "$f" ] && [ gemm_f32_common.h -nt "$o" ]; } || { [ "${f#int8}" != "$f" ] && [ int8_fast.h -nt "$o" ]; }; then
     /opt/rocm/bin/hipcc $FLAGS "$@" -c "$f" -o "$o" &
     pids+=($!)
   fi

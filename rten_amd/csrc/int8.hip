@@ -25,7 +25,7 @@
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 
-// int8_fast.hip: k-contiguous staging + LDS-DMA MFMA kernel; RTEN_HIP_ERR_UNSUPPORTED = not covered, use the generic kernel
+// int8_fast_entry.hip: staging (int8_stage.hip) + LDS-DMA MFMA kernel (int8_fast.hip); RTEN_HIP_ERR_UNSUPPORTED = not covered, use the generic kernel
 int32_t rten_i8_fast_gemm(rten_hip_ctx *ctx, const rten_hip_gemm_int8_desc *d, const void *a, const void *b, const void *a_zp,
                           const void *b_zp, const float *scale, void *c);
 int32_t rten_i8_fast_conv(rten_hip_ctx *ctx, const rten_hip_conv2d_int8_desc *di, const void *x, const void *w, const void *x_zp,

@@ -30,9 +30,12 @@
 //     (kernarg_prefetch), index arithmetic by multiply-shift (rten_div), no arithmetic on a loaded value before the main loop (it would drain the
 //     vector-memory counter in front of the first operand request), the launch's single activation zero point through the scalar cache, and the
 //     single-row-term epilogue of the convolution form as a template flag (RT).
+// This unit: the kernel and the dispatch of its launch forms (int8_fast.h: the other two units of the path and what they share).
+#include <array>
+#include <cstdlib>
 #include <cstring>
 
-#include "internal.h"
+#include "int8_fast.h"
 #include "quantize.h"
 #include "vecmath.h"
 
@@ -42,64 +45,9 @@ typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int KT = 64;          // k bytes per tile (4 chunks of 16)
 constexpr unsigned OOB = 0x80000000u;
 
-struct FastArgs {
-    const uint8_t *A;      // [M][Kp] signed rows
-    const uint8_t *B;      // GEMM: [N][Kp] signed rows; conv: padded NHWC image
-    const int *rsum;       // [M] sums of A rows
-    const int *csum;       // [N] sums of B rows (GEMM) or NULL (conv: accumulated in-kernel when needed)
-    void *C;
-    const uint8_t *a_zp, *b_zp;
-    const float *scale, *bias, *res;
-    int M, N, Kp, Kreal;
-    unsigned a_bytes, b_bytes;
-    long long c_rs, c_ns;
-    int Pn;
-    int a_signed, b_signed, a_zp_len, b_zp_len, scale_len, relu, need_csum;
-    int scale_per_row; // conv: scale[m] per output channel instead of scale[0] / scale[n]
-    unsigned *stats;   // optional: min/max of the f32 outputs, accumulated for the DynamicQuantizeLinear that consumes them
-    int tiles_m, tiles_n, n_fastest;
-    // conv geometry (padded image)
-    int conv, OW, sy, sx, Hp, Wp, Cp, KH, KW, dy, dx;
-    // BQ kernels (DynamicQuantizeLinear fused into the B loader of a pointwise conv): the f32 activations, the min/max block their
-    // producer left, the plane size, and where the quantizer's own outputs go
-    const float *xf;
-    const unsigned *in_stats;
-    int HW, Cin;
-    float *xs_out;
-    uint8_t *xz_out;
-    // QO kernels (the DynamicQuantizeLinear that CONSUMES this convolution's output runs in its epilogue, behind a grid-wide min / max):
-    // the barrier block, the consumer's staged image and its geometry, the quantizer's own outputs
-    unsigned *sync;
-    unsigned *fault; // the context's sticky fault word (host-mapped): written only when a grid-wide wait gives up
-    uint8_t *q_out;
-    float *q_scale_out;
-    uint8_t *q_zp_out;
-    const float *q_mul_by;
-    float *q_product;
-    int q_cb, q_Hp, q_Wp, q_pt, q_pl, q_H, q_W, q_pad_mode;
-    unsigned q_bytes;
-    int debug_flags; // RTEN_HIP_DEBUG tuning switches seen by the kernel (bit 0: general zero-point algebra everywhere)
-    // KS kernels (cross-workgroup K split): `ks` workgroups share one output tile, each sums its slice of the k-tiles, parks the raw int32 partial in `slab`
-    // ([tile][part][wave][register quad][lane] x 16 B) and arrives on the tile's counter; the last arrival adds the others' partials to its own registers
-    // (integer addition: any order gives the same bits) and runs the epilogue
-    int ks;
-    int *slab;
-    unsigned *ks_counters;
-    int no_store; // statistics-only launch (pass 1 of the recompute form of a quantized output): the epilogue runs, nothing is stored
-    // exact division by the conv geometry's run-time divisors as multiply + shift (filled by launch_fast): the prologue's per-lane
-    // pixel decode and the chunk table otherwise spend ~40 VALU instructions per division, on every resident wave at once
-    RtenDiv d_pn, d_ow, d_cpc, d_kw, d_hw, d_qw, d_tile;
-};
-
-
-__device__ __forceinline__ int zp_signed(const uint8_t *zp, int idx, int is_signed) {
-    if (!zp) return is_signed ? 0 : -128;
-    return is_signed ? (int)(int8_t)zp[idx] : (int)zp[idx] - 128;
-}
-// The same in two steps: the load (raw byte, -1 = no zero-point input) is issued in the kernel's prologue, the conversion waits until the epilogue --
+// A zero point in the signed domain, in two steps: the load (raw byte, -1 = no zero-point input) is issued in the kernel's prologue, the conversion waits until the epilogue --
 // any arithmetic on the loaded byte makes the compiler drain every outstanding load right there, a full memory round trip before the first operand tile
 // is even requested (tools/debug/i8_trace.py: ~1000 cycles per launch).
 __device__ __forceinline__ int zp_raw(const uint8_t *zp, int idx) { return zp ? (int)zp[idx] : -1; }
@@ -108,334 +56,12 @@ __device__ __forceinline__ int zp_from_raw(int raw, int is_signed) {
     return is_signed ? (int)(int8_t)(uint8_t)raw : raw - 128;
 }
 
-
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 __device__ __forceinline__ constexpr int acc_row(int r) { return (r & 3) + 8 * (r >> 2); }
-
-// ---------------------------------------------------------------------------------------------------------
-// staging kernels
-// ---------------------------------------------------------------------------------------------------------
-
-// rows of a strided u8/i8 matrix -> chunk-major signed operand [Kp/16][rows][16 B] (+ row sums).  With khw > 1 the
-// source k index is (c, tap) (OIHW weights) and the destination k index is (tap, c) with channels padded to Cp.
-// `pk_nch` > 0: the few-channel PACKED destination order (conv_geom, round 6): chunk (ky, j) holds kernel columns j * pk_cpc .. + pk_cpc - 1 of row ky, byte
-// col * C + channel; columns past the kernel's width and the bytes past pk_cpc * C are zero weights.
-__global__ __launch_bounds__(256) void i8_pack_rows_kernel(const uint8_t *__restrict__ src, long long row_stride, long long k_stride, int K,
-                                                          int C, int khw, int Cp, int Kp, int rows, unsigned flip, uint8_t *__restrict__ dst,
-                                                          int *__restrict__ sums, int pk_nch = 0, int pk_cpc = 0, int pk_kw = 0) {
-    const int r = blockIdx.x;
-    const uint8_t *s = src + (long long)r * row_stride;
-    int sum = 0;
-    for (int kq = threadIdx.x * 4; kq < Kp; kq += 1024) {
-        unsigned w = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int kd = kq + b;
-            int tap = kd / Cp, c = kd - tap * Cp;
-            bool ok = tap < khw && c < C;
-            if (pk_nch > 0) { // (Cp == 16 here; `khw` = kernel rows x kernel columns of the REAL kernel)
-                const int vt = kd >> 4, slot = kd & 15, ky = vt / pk_nch, j = vt - ky * pk_nch, col = slot / C, kx = j * pk_cpc + col;
-                c = slot - col * C;
-                ok = ky * pk_kw < khw && col < pk_cpc && kx < pk_kw;
-                tap = ky * pk_kw + kx;
-            }
-            const int ks = c * khw + tap;
-            const unsigned v = ok ? ((unsigned)s[(long long)(ks < K ? ks : 0) * k_stride] ^ flip) & 0xffu : 0u;
-            w |= v << (8 * b);
-        }
-        *reinterpret_cast<unsigned *>(dst + ((long long)(kq >> 4) * rows + r) * 16 + (kq & 15)) = w;
-        sum = __builtin_amdgcn_sdot4((int)w, 0x01010101, sum, false);
-    }
-    __shared__ int red[4];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) sums[r] = red[0] + red[1] + red[2] + red[3];
-}
-
-// Staging of conv activations: NCHW -> padded channel-blocked signed bytes [N][Cp/16][Hp][Wp][16 B]; border = pad
-// value of the selected mode, padded channels 0.  A workgroup takes 256 consecutive SOURCE pixels of one image x one
-// 16-channel block: a thread loads 4 consecutive pixels (one 16-byte load when the plane size allows) of 4 consecutive
-// channels, packs the 4 channel bytes of each pixel into a dword and parks them in LDS ([channel quad][pixel], one
-// conflict-free ds_write_b128); the workgroup then writes the run of PADDED positions that its pixels span -- border
-// pieces included -- as consecutive 16-byte pieces (1 KiB per wave instruction).  `prep()` runs AFTER the loads are in
-// flight (so e.g. the statistics fold of the fused quantizer hides behind them) and returns the mapping: `.fill` =
-// signed-domain border byte, `.byte(v)` = source element -> signed-domain byte.
-template <typename T> struct Vec4;
-template <> struct Vec4<float> { typedef float4 type; };
-template <> struct Vec4<uint8_t> { typedef uchar4 type; };
-
-template <typename T, bool VEC, typename Prep>
-__device__ __forceinline__ void stage_blocked_tile(const T *__restrict__ x, uint8_t *__restrict__ xp, int C, int H, int W, int Hp, int Wp, int Cp, int pt, int pl,
-                                                   Prep prep) {
-    __shared__ __attribute__((aligned(16))) unsigned tile[4][256];
-    const int t = threadIdx.x;
-    const int HW = H * W, npix = Hp * Wp;
-    const int p0 = blockIdx.x * 256, n = blockIdx.y, cb = blockIdx.z;
-    const int px = (t & 63) * 4, cq = (t >> 6) * 4;
-    T raw[4][4]; // [channel][pixel]
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int c = cb * 16 + cq + j;
-        const long long base = ((long long)n * C + (c < C ? c : 0)) * HW + p0 + px;
-        if constexpr (VEC) { // HW % 4 == 0: the 4 pixels are all inside or all outside, and the address is 4-element aligned
-            const typename Vec4<T>::type v = *reinterpret_cast<const typename Vec4<T>::type *>(x + ((c < C && p0 + px < HW) ? base : 0));
-            raw[j][0] = v.x; raw[j][1] = v.y; raw[j][2] = v.z; raw[j][3] = v.w;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; i++) raw[j][i] = x[(c < C && p0 + px + i < HW) ? base + i : 0];
-        }
-    }
-    const auto map = prep();
-    unsigned w[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        w[i] = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const unsigned v = (cb * 16 + cq + j < C) ? map.byte(raw[j][i]) & 0xffu : 0u;
-            w[i] |= v << (8 * j);
-        }
-    }
-    *reinterpret_cast<uint4 *>(&tile[t >> 6][px]) = make_uint4(w[0], w[1], w[2], w[3]);
-    __syncthreads();
-    // border piece of this channel block: pad byte on real channels, 0 on the padding channels
-    unsigned fw[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        fw[q] = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) fw[q] |= (cb * 16 + q * 4 + j < C ? map.fill : 0u) << (8 * j);
-    }
-    auto padded = [&](int sp) { const int y = sp / W; return (y + pt) * Wp + (sp - y * W) + pl; };
-    const int s_end = p0 + 256 < HW ? p0 + 256 : HW;
-    const int begin = p0 == 0 ? 0 : padded(p0);
-    const int end = s_end == HW ? npix : padded(s_end);
-    uint8_t *dst = xp + ((long long)n * (Cp / 16) + cb) * npix * 16;
-    for (int pp = begin + t; pp < end; pp += 256) {
-        const int yp = pp / Wp, xq = pp - yp * Wp;
-        const int y = yp - pt, xs = xq - pl;
-        uint4 v = make_uint4(fw[0], fw[1], fw[2], fw[3]);
-        if ((unsigned)y < (unsigned)H && (unsigned)xs < (unsigned)W) {
-            const int sl = y * W + xs - p0; // in [0, 256): the padded run [begin, end) covers exactly this workgroup's pixels
-            v = make_uint4(tile[0][sl], tile[1][sl], tile[2][sl], tile[3][sl]);
-        }
-        *reinterpret_cast<uint4 *>(dst + (long long)pp * 16) = v;
-    }
-}
-
-// Few-channel PACKED staging (round 6; conv_geom): a convolution with C <= 4 input channels (the 7x7 / stride 2 stem of ResNet-50: C = 3) staged as a 16-channel
-// block moves 16 bytes per pixel for 3 of data and multiplies 13 zeros per tap (K = 49 x 16 = 784 for 147 real terms).  Here a 16-byte chunk holds `cpc` = 16 / C
-// horizontally adjacent kernel COLUMNS x C channels of one kernel row, and every OUTPUT column gets its own `nch` = ceil(KW / cpc) chunks per padded input row
-// (columns ox * stride - pad + j * cpc + col): image [N][Hp][OW * nch][16 B], which the unchanged kernel walks as a convolution with 16 channels, KW = nch and
-// stride nch over "virtual columns" -- K = KH x nch x 16 (224 for the stem).  A thread writes one chunk: all its (clamped) loads first, then `prep()`.
-template <typename T, int C, int NCH, typename Prep>
-__device__ __forceinline__ void stage_packed_chunks(const T *__restrict__ x, uint8_t *__restrict__ xp, int H, int W, int Hp, int OW, int KW, int sx, int dx, int pt, int pl,
-                                                    Prep prep) {
-    // a thread owns one OUTPUT column of one padded input row: the NCH chunks of that column (32 consecutive bytes for the stem); grid = (OW / 128, Hp / 2, N).  The
-    // channel count and the chunk count are compile-time, so the slot -> (kernel column, channel) map costs nothing; every load is issued (clamped) before prep().
-    constexpr int CPC = 16 / C;
-    // (256 threads = two padded rows x 128 output columns: prep()'s statistics fold is written for 256-thread workgroups)
-    const int ox = blockIdx.x * 128 + (threadIdx.x & 127), ypr = blockIdx.y * 2 + (threadIdx.x >> 7), n = blockIdx.z;
-    const int oxc = ox < OW ? ox : OW - 1, yp = ypr < Hp ? ypr : Hp - 1;
-    const int y = yp - pt, x0 = oxc * sx - pl; // kernel column kx reads input column ox * stride - pad + kx * dilation
-    const bool row_in = (unsigned)y < (unsigned)H;
-    const long long plane = (long long)H * W;
-    const T *row = x + (long long)n * C * plane + (long long)(row_in ? y : 0) * W;
-    T raw[NCH * CPC][C];
-#pragma unroll
-    for (int kx = 0; kx < NCH * CPC; kx++) {
-        const int xx = x0 + kx * dx;
-        const bool in = kx < KW && row_in && (unsigned)xx < (unsigned)W;
-#pragma unroll
-        for (int ch = 0; ch < C; ch++) raw[kx][ch] = row[in ? ch * plane + xx : 0];
-    }
-    const auto map = prep();
-#pragma unroll
-    for (int j = 0; j < NCH; j++) {
-        unsigned w[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int col = 0; col < CPC; col++) {
-            const int kx = j * CPC + col, xx = x0 + kx * dx;
-            const bool real = kx < KW;                                        // a kernel column (else: a zero weight multiplies the byte, and the byte is 0)
-            const bool in = real && row_in && (unsigned)xx < (unsigned)W;
-#pragma unroll
-            for (int ch = 0; ch < C; ch++) {
-                constexpr int dummy = 0; (void)dummy;
-                const int slot = col * C + ch;
-                const unsigned v = in ? map.byte(raw[kx][ch]) & 0xffu : (real ? map.fill : 0u);
-                w[slot >> 2] |= v << (8 * (slot & 3));
-            }
-        }
-        if (ox < OW && ypr < Hp) *reinterpret_cast<uint4 *>(xp + ((((long long)n * Hp + yp) * OW + ox) * NCH + j) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-
-// Small feature maps (fewer than 128 pixels per plane, e.g. 7x7): 64 consecutive PADDED positions x 64 channels per
-// workgroup, one pixel per lane, so the lanes stay busy where the 256-pixel tile above would idle.
-template <typename T, typename Prep>
-__device__ __forceinline__ void stage_blocked_tile_small(const T *__restrict__ x, uint8_t *__restrict__ xp, int C, int H, int W, int Hp, int Wp, int Cp, int pt, int pl,
-                                                Prep prep) {
-    __shared__ uint8_t tile[64][64 + 16];
-    const int t = threadIdx.x;
-    const int pp0 = blockIdx.x * 64, n = blockIdx.y;
-    const int npix = Hp * Wp;
-    const int pl_ = t & 63, pp = pp0 + pl_;
-    const int yp = pp / Wp, xq = pp - yp * Wp;
-    const int y = yp - pt, xs = xq - pl;
-    const bool in = pp < npix && (unsigned)y < (unsigned)H && (unsigned)xs < (unsigned)W;
-    const long long src0 = ((long long)n * C * H + (in ? y : 0)) * W + (in ? xs : 0); // + c * H * W
-    const int c0 = blockIdx.z * 64; // one 64-channel slab per workgroup: small feature maps still give thousands of workgroups
-    // thread -> (pixel, 4 consecutive channels) per pass.  All 16 loads are issued first (clamped address, no branch
-    // around a load), then converted and packed: one dword per pass into the LDS tile.
-    T raw[16];
-#pragma unroll
-    for (int pass = 0; pass < 4; pass++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int c = c0 + pass * 16 + (t >> 6) * 4 + b;
-            raw[pass * 4 + b] = x[(in && c < C) ? src0 + (long long)c * H * W : 0];
-        }
-    const auto map = prep();
-    const unsigned fill = map.fill;
-#pragma unroll
-    for (int pass = 0; pass < 4; pass++) {
-        const int cl = pass * 16 + (t >> 6) * 4;
-        unsigned w = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int c = c0 + cl + b;
-            const unsigned v = (in && c < C) ? map.byte(raw[pass * 4 + b]) & 0xffu : (c < C ? fill : 0u);
-            w |= v << (8 * b);
-        }
-        *reinterpret_cast<unsigned *>(&tile[pl_][cl]) = w;
-    }
-    __syncthreads();
-    const int px = t & 63, ch = t >> 6;
-    if (pp0 + px < npix && c0 + ch * 16 < Cp)
-        *reinterpret_cast<uint4 *>(xp + (((long long)n * (Cp / 16) + (c0 / 16 + ch)) * npix + pp0 + px) * 16) = *reinterpret_cast<const uint4 *>(&tile[px][ch * 16]);
-}
-
-struct FlipMap {
-    unsigned fill, flip;
-    __device__ __forceinline__ unsigned byte(uint8_t b) const { return ((unsigned)b ^ flip) & 0xffu; }
-};
-struct QuantMap {
-    unsigned fill;
-    float inv_scale;
-    int zp;
-    __device__ __forceinline__ unsigned byte(float f) const { return dql::quant_u8(f, inv_scale, zp) ^ 0x80u; }
-};
-
-template <int KIND> // 0 = small maps, 1 = 256-pixel tiles with scalar loads, 2 = with 4-pixel vector loads
-__global__ __launch_bounds__(256) void i8_nhwc_pad_kernel(const uint8_t *__restrict__ x, uint8_t *__restrict__ xp, int C, int H, int W, int Hp,
-                                                         int Wp, int Cp, int pt, int pl, unsigned flip, const uint8_t *__restrict__ x_zp,
-                                                         int x_signed, int pad_mode) {
-    auto prep = [&]() {
-        int pad_s = 0;
-        if (pad_mode == RTEN_HIP_PAD_ZERO_POINT) pad_s = zp_signed(x_zp, 0, x_signed);
-        else if (pad_mode == RTEN_HIP_PAD_RAW0_U8) pad_s = -128;
-        return FlipMap{(unsigned)pad_s & 0xffu, flip};
-    };
-    if constexpr (KIND == 0) stage_blocked_tile_small(x, xp, C, H, W, Hp, Wp, Cp, pt, pl, prep);
-    else stage_blocked_tile<uint8_t, KIND == 2>(x, xp, C, H, W, Hp, Wp, Cp, pt, pl, prep);
-}
-
-// DynamicQuantizeLinear's quantize sweep fused with the staging above: f32 NCHW -> u8 codes (bit-identical to
-// quantize.hip: same scale / zero-point algebra, same to_int_round + saturate) written as padded channel-blocked
-// signed bytes.  The min/max fold runs while the tile's loads are in flight.
-// the scalar Mul(x_scale, w_scale) nodes that follow a DynamicQuantizeLinear in ort-quantized graphs (one per convolution that reads the
-// quantized tensor: a stage's shortcut and first 1x1 convolution share one): product[i] = scale * mul_by[i][0]
-constexpr int kMaxProducts = 4;
-struct ScaleProducts {
-    int count;
-    const float *mul_by[kMaxProducts];
-    float *product[kMaxProducts];
-};
-
-template <int C, int NCH>
-__global__ __launch_bounds__(256) void i8_pad_packed_kernel(const uint8_t *__restrict__ x, uint8_t *__restrict__ xp, int H, int W, int Hp, int OW, int KW, int sx, int dx, int pt,
-                                                           int pl, unsigned flip, const uint8_t *__restrict__ x_zp, int x_signed, int pad_mode) {
-    auto prep = [&]() {
-        int pad_s = 0;
-        if (pad_mode == RTEN_HIP_PAD_ZERO_POINT) pad_s = zp_signed(x_zp, 0, x_signed);
-        else if (pad_mode == RTEN_HIP_PAD_RAW0_U8) pad_s = -128;
-        return FlipMap{(unsigned)pad_s & 0xffu, flip};
-    };
-    stage_packed_chunks<uint8_t, C, NCH>(x, xp, H, W, Hp, OW, KW, sx, dx, pt, pl, prep);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void i8_quantize_stage_kernel(const float *__restrict__ x, const float *__restrict__ ws, int nparts, uint8_t *__restrict__ xp,
-                                                               int C, int H, int W, int Hp, int Wp, int Cp, int pt, int pl, int pad_mode,
-                                                               float *scale_out, uint8_t *zp_out, const ScaleProducts sp) {
-    // explicit arguments: 0x58 bytes + ScaleProducts = 160 bytes, three lines (the tail of them is first touched AFTER the tile has arrived: on the critical path)
-    kernarg_prefetch<0x58 + (int)sizeof(ScaleProducts)>();
-    auto prep = [&]() {
-        float x_min, x_max;
-        if (nparts < 0) dql::block_minmax_slots(reinterpret_cast<const unsigned *>(ws), x_min, x_max); // producer-accumulated statistics
-        else dql::block_minmax(ws, nparts, x_min, x_max);
-        const dql::QParams q = dql::dql_params(x_min, x_max);
-        if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
-            *scale_out = q.scale;
-            *zp_out = (uint8_t)q.zp;
-#pragma unroll
-            for (int i = 0; i < kMaxProducts; i++)
-                if (i < sp.count) *sp.product[i] = q.scale * sp.mul_by[i][0];
-        }
-        int pad_s = 0; // signed-domain padding value
-        if (pad_mode == RTEN_HIP_PAD_ZERO_POINT) pad_s = q.zp - 128;
-        else if (pad_mode == RTEN_HIP_PAD_RAW0_U8) pad_s = -128;
-        return QuantMap{(unsigned)pad_s & 0xffu, q.inv_scale, q.zp};
-    };
-    if constexpr (KIND == 0) stage_blocked_tile_small(x, xp, C, H, W, Hp, Wp, Cp, pt, pl, prep);
-    else stage_blocked_tile<float, KIND == 2>(x, xp, C, H, W, Hp, Wp, Cp, pt, pl, prep);
-}
-
-// ... and DynamicQuantizeLinear's quantize sweep into the few-channel packed image (same prep as i8_quantize_stage_kernel: same codes)
-template <int C, int NCH>
-__global__ __launch_bounds__(256) void i8_quantize_packed_kernel(const float *__restrict__ x, const float *__restrict__ ws, int nparts, uint8_t *__restrict__ xp, int H, int W, int Hp,
-                                                                int OW, int KW, int sx, int dx, int pt, int pl, int pad_mode, float *scale_out, uint8_t *zp_out,
-                                                                const ScaleProducts sp) {
-    auto prep = [&]() {
-        float x_min, x_max;
-        if (nparts < 0) dql::block_minmax_slots(reinterpret_cast<const unsigned *>(ws), x_min, x_max);
-        else dql::block_minmax(ws, nparts, x_min, x_max);
-        const dql::QParams q = dql::dql_params(x_min, x_max);
-        if (threadIdx.x == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
-            *scale_out = q.scale;
-            *zp_out = (uint8_t)q.zp;
-#pragma unroll
-            for (int i = 0; i < kMaxProducts; i++)
-                if (i < sp.count) *sp.product[i] = q.scale * sp.mul_by[i][0];
-        }
-        int pad_s = 0;
-        if (pad_mode == RTEN_HIP_PAD_ZERO_POINT) pad_s = q.zp - 128;
-        else if (pad_mode == RTEN_HIP_PAD_RAW0_U8) pad_s = -128;
-        return QuantMap{(unsigned)pad_s & 0xffu, q.inv_scale, q.zp};
-    };
-    stage_packed_chunks<float, C, NCH>(x, xp, H, W, Hp, OW, KW, sx, dx, pt, pl, prep);
-}
-
-// (channel count x chunks per output column: the instantiations conv_geom admits)
-#define RTEN_PACKED_DISPATCH(KERNEL, c, nch, grid, ...)                                                                                  \
-    do {                                                                                                                                 \
-        switch ((c) * 4 + (nch)) {                                                                                                       \
-        case 1 * 4 + 1: hipLaunchKernelGGL((KERNEL<1, 1>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__); break;                         \
-        case 1 * 4 + 2: hipLaunchKernelGGL((KERNEL<1, 2>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__); break;                         \
-        case 2 * 4 + 1: hipLaunchKernelGGL((KERNEL<2, 1>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__); break;                         \
-        case 2 * 4 + 2: hipLaunchKernelGGL((KERNEL<2, 2>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__); break;                         \
-        case 3 * 4 + 1: hipLaunchKernelGGL((KERNEL<3, 1>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__); break;                         \
-        case 3 * 4 + 2: hipLaunchKernelGGL((KERNEL<3, 2>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__); break;                         \
-        case 4 * 4 + 1: hipLaunchKernelGGL((KERNEL<4, 1>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__); break;                         \
-        default: hipLaunchKernelGGL((KERNEL<4, 2>), grid, dim3(256), 0, ctx->stream, __VA_ARGS__); break;                                \
-        }                                                                                                                                \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------------------
 // main kernel
@@ -465,9 +91,7 @@ extern __shared__ __attribute__((aligned(16))) uint8_t i8_smem[];
 // scale / zero point, converts with the same dql::quant_u8 and writes the codes straight into the consumer's staged image
 // (channel-blocked, padded; border pieces included).  The f32 tensor is written only if somebody else needs it (p.C != NULL).
 // Every workgroup of the grid must be resident at once (the host checks the occupancy before it launches this form).
-constexpr unsigned kSyncCtlWords = 16;    // exchange block: word 0 = departures, word 8 = time-out flag, then kSyncGranules 8-byte {min, max} granules
-constexpr unsigned kSyncGranules = 2048;  // >= the workgroups the device holds at once (8 per compute unit x 256)
-constexpr unsigned kSyncWords = kSyncCtlWords + 2 * kSyncGranules;
+// (the exchange block's layout, kSyncCtlWords / kSyncGranules / kSyncWords: int8_fast.h)
 constexpr unsigned long long kGranuleReset = 0x00000000ffffffffull; // {min = 0xffffffff, max = 0}: what a reset leaves, never a real pair
 constexpr unsigned kSyncSpinLimit = 1u << 17;
 // KS = cross-workgroup K split (round 6): the launches of stages 2-3 at batch 32 are 52-392 tiles for 256 compute units with 16-72 k-tiles each -- a
@@ -1193,44 +817,6 @@ __global__ __launch_bounds__(256 * KG, KG == 1 ? 2 : 1) void igemm_i8_fast_kerne
 #undef I8_STAMP
 }
 
-// Transposing variant of the row packer for operands whose rows are NOT k-contiguous (e.g. MatMulInteger weights
-// [K][N]: row n walks k with stride N).  64 x 64 byte tiles through LDS: coalesced reads along the source's
-// contiguous axis, 4-byte writes along k.  Row sums via atomics into a zeroed array.
-__global__ __launch_bounds__(256) void i8_pack_rows_t_kernel(const uint8_t *__restrict__ src, long long row_stride, long long k_stride, int rows,
-                                                            int K, int Kp, unsigned flip, uint8_t *__restrict__ dst, int *__restrict__ sums) {
-    __shared__ uint8_t tile[64][64 + 4];
-    const int t = threadIdx.x;
-    const int r0 = blockIdx.x * 64, k0 = blockIdx.y * 64;
-    // read: consecutive threads walk rows (the source's contiguous axis when row_stride == 1)
-#pragma unroll
-    for (int pass = 0; pass < 16; pass++) {
-        const int rl = t & 63, kl = pass * 4 + (t >> 6);
-        const int r = r0 + rl, k = k0 + kl;
-        unsigned v = 0;
-        if (r < rows && k < K) v = ((unsigned)src[(long long)r * row_stride + (long long)k * k_stride] ^ flip) & 0xffu;
-        tile[rl][kl] = (uint8_t)v;
-    }
-    __syncthreads();
-    // write: thread -> (row, 16-byte group), consecutive lanes on consecutive rows of one chunk plane; k0 + 64 <= Kp
-    // always (Kp is a multiple of 64)
-    const int rl = t & 63, g = t >> 6;
-    const int r = r0 + rl;
-    int sum = 0;
-    if (r < rows) {
-        unsigned w[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            w[q] = (unsigned)tile[rl][g * 16 + q * 4] | ((unsigned)tile[rl][g * 16 + q * 4 + 1] << 8) | ((unsigned)tile[rl][g * 16 + q * 4 + 2] << 16) |
-                   ((unsigned)tile[rl][g * 16 + q * 4 + 3] << 24);
-            sum = __builtin_amdgcn_sdot4((int)w[q], 0x01010101, sum, false);
-        }
-        *reinterpret_cast<uint4 *>(dst + ((long long)(k0 / 16 + g) * rows + r) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    if (r < rows) atomicAdd(&sums[r], sum);
-}
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Workgroups of `kern` (threads, dynamic LDS) the whole device holds at once (the occupancy query is cached per kernel and LDS size).
 int resident_capacity(rten_hip_ctx *ctx, const void *kern, int threads, size_t lds) {
     static std::mutex mu;
@@ -1246,10 +832,31 @@ int resident_capacity(rten_hip_ctx *ctx, const void *kern, int threads, size_t l
     return it->second * ctx->num_cus;
 }
 
-// Returns false (nothing launched) when QO is requested and the grid cannot be resident all at once.
-template <int BM, int BN, int NST, int KTK = 64, int KG = 1, bool BQ = false, int QO = 0, bool KS = false>
-bool launch_fast(rten_hip_ctx *ctx, FastArgs &a, const char *name, double ops, double bytes) {
-    static_assert(KTK == 64 || KG == 1, "k-groups walk 64-byte k-tiles");
+enum Form { PLAIN, LOADQ /* BQ */, EXCHANGE /* QO == 1 */, RECOMPUTE /* QO == 2 */, KSPLIT /* KS */, kForms }; // the launch forms ...
+enum Tile { T128x128, T128x64, T64x128, T64x64, T64x64_KG4, T64x256, kTiles, kNoTile = kTiles }; // ... and the tiles they are launched on
+constexpr int kTileM[kTiles] = {128, 128, 64, 64, 64, 64}, kTileN[kTiles] = {128, 64, 128, 64, 64, 256}, kTileKG[kTiles] = {1, 1, 1, 1, 4, 1};
+
+// The name a launch is profiled under: "igemm_i8_fast_kernel<BM,BN[,kg4][,form]>" (plans, tools and tests match on it)
+const char *fast_label(Form f, Tile t) {
+    static const auto labels = [] {
+        const char *const tile[kTiles] = {"128,128", "128,64", "64,128", "64,64", "64,64,kg4", "64,256"};
+        const char *const form[kForms] = {"", ",bq", ",qo", ",qo2", ",ks"};
+        std::array<std::array<std::string, kTiles>, kForms> l;
+        for (int i = 0; i < kForms; i++)
+            for (int j = 0; j < kTiles; j++) l[i][j] = std::string("igemm_i8_fast_kernel<") + tile[j] + form[i] + ">";
+        return l;
+    }();
+    return labels[f][t].c_str();
+}
+
+// One launch of form F on tile T.  false (nothing launched): an exchange grid that cannot be resident all at once, or a recompute launch outside its form.
+// (256-byte k-tiles were measured and are slower: profiles/r05/int8_notes.md.  Measured again in round 3 and dropped -- profiles/r06/int8_tile_experiments.txt:
+// 128-byte k-tiles on the smaller tiles +5 % on the whole conv time, the next larger tile for the under-filled launches +6 %, four LDS stages +2 %)
+template <Form F, Tile T>
+bool launch_fast(rten_hip_ctx *ctx, FastArgs &a, double ops, double bytes) {
+    constexpr int BM = kTileM[T], BN = kTileN[T], KG = kTileKG[T], NST = 3, KTK = 64;
+    constexpr bool BQ = F == LOADQ, KS = F == KSPLIT;
+    constexpr int QO = F == EXCHANGE ? 1 : F == RECOMPUTE ? 2 : 0;
     a.tiles_m = (a.M + BM - 1) / BM;
     a.tiles_n = (a.N + BN - 1) / BN;
     constexpr size_t ring = (size_t)NST * KG * (BM + BN) * KTK;
@@ -1273,18 +880,18 @@ bool launch_fast(rten_hip_ctx *ctx, FastArgs &a, const char *name, double ops, d
             launched = false;
             return;
         }
-        ProfScope ps(ctx, name, ops, bytes);
+        ProfScope ps(ctx, fast_label(F, T), ops, bytes);
         hipLaunchKernelGGL(kern, dim3((unsigned)(a.tiles_m * a.tiles_n * (KS ? a.ks : 1))), dim3(256 * KG), lds, ctx->stream, a);
     };
-    // RT: the single-row-term zero-point algebra of the convolution form (weight zero point 0 in the signed domain, one activation zero point)
-    const bool rt = a.conv && !(a.debug_flags & 1) && a.a_zp == nullptr && a.a_signed && a.b_zp_len <= 1 && !a.need_csum;
+    const bool rt = single_row_term(a);
+    // (statements, not an `else`, follow the two early-return forms: the RES x RT kernels of their tile are compiled for them too and never launched -- for
+    // K split they are the plain form's own, for the recompute form they belong to the library's kernel set as it stands)
     if constexpr (QO == 2) { // the recompute form is built for the single-row-term convolution without a residual (the single-consumer edges of a bottleneck block)
         if (!rt || (a.res && a.scale)) { launched = false; return launched; }
         go(igemm_i8_fast_kernel<BM, BN, NST, false, KTK, KG, BQ, 2, true>);
         return launched;
     }
     if constexpr (KS) { // (the dispatcher checked: RT form, no residual)
-        a.d_tile = rten_make_div((long long)a.tiles_m * a.tiles_n, a.n_fastest ? a.tiles_n : a.tiles_m);
         go(igemm_i8_fast_kernel<BM, BN, NST, false, KTK, KG, BQ, QO, true, true>);
         return launched;
     }
@@ -1298,583 +905,80 @@ bool launch_fast(rten_hip_ctx *ctx, FastArgs &a, const char *name, double ops, d
     return launched;
 }
 
-int32_t dispatch_fast(rten_hip_ctx *ctx, FastArgs &a, double ops, double bytes) {
-    // tile choice: the largest tile that still gives every CU a workgroup (the tile DMA of a workgroup tops out far
-    // below what the MFMAs could consume, so an idle CU costs more than the extra operand re-reads of a smaller tile)
-    const long long t128 = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-    const long long t12864 = (long long)((a.M + 127) / 128) * ((a.N + 63) / 64);
+// The tile switch of every form.  A form is compiled for the tiles it has always had: 64x256 for the exchange form only, four k-groups for the forms that take
+// the plain tile choice, no 64x128 for K split.  false: nothing launched (launch_fast), or a tile the form is not built for -- which no caller below asks for.
+template <Form F>
+bool launch_tile(rten_hip_ctx *ctx, FastArgs &a, Tile t, double ops, double bytes) {
+    switch (t) {
+    case T128x128: return launch_fast<F, T128x128>(ctx, a, ops, bytes);
+    case T128x64: return launch_fast<F, T128x64>(ctx, a, ops, bytes);
+    case T64x64: return launch_fast<F, T64x64>(ctx, a, ops, bytes);
+    case T64x128: if constexpr (F != KSPLIT) return launch_fast<F, T64x128>(ctx, a, ops, bytes); else break;
+    case T64x64_KG4: if constexpr (F == PLAIN || F == EXCHANGE || F == RECOMPUTE) return launch_fast<F, T64x64_KG4>(ctx, a, ops, bytes); else break;
+    case T64x256: if constexpr (F == EXCHANGE) return launch_fast<F, T64x256>(ctx, a, ops, bytes); else break;
+    default: break;
+    }
+    return false;
+}
+
+// tile setting (0 = 128x128, 1 = 128x64, 2 = 64x128, anything else = 64x64) -> tile; `kg4`: the 64x64 tile with four k-groups
+Tile tile_of(int setting, bool kg4) { return setting == 0 ? T128x128 : setting == 1 ? T128x64 : setting == 2 ? T64x128 : kg4 ? T64x64_KG4 : T64x64; }
+// the next larger tile an exchange launch tries when its grid does not fit the chip at once
+Tile next_larger(Tile t) { return t == T128x64 ? T128x128 : t == T64x128 ? T64x256 : t == T64x64 ? T128x64 : kNoTile; }
+long long tile_count(const FastArgs &a, Tile t) { return (long long)((a.M + kTileM[t] - 1) / kTileM[t]) * ((a.N + kTileN[t] - 1) / kTileN[t]); }
+
+// K-group rule: under-filled launches (fewer than ~2 workgroups per CU) of the 64x64 tile split K over 4 k-groups inside the workgroup: more waves per SIMD to
+// hide the k-loop's latencies behind each other (RTEN_HIP_DEBUG bit 0x800 turns this off).  Measured (profiles/r05/int8_per_layer.txt): 4 groups pay off below
+// ~1.25 workgroups per CU with K >= 1024 bytes (stage-4 3x3: 20.8 -> 14.8 us); 2 groups on the 1.5-workgroup launches of stage 3 do not (10.3 -> 11.5 us)
+bool four_k_groups(const rten_hip_ctx *ctx, const FastArgs &a) { return !(ctx->debug & 0x800) && tile_count(a, T64x64) * 4 <= 5 * ctx->num_cus && (a.Kp + 63) / 64 >= 16; }
+
+// Cross-workgroup K split (KS kernels): under-filled long-K launches of the single-row-term convolution form without a residual.  `a.ks` = the largest
+// split the caller's slab holds (0: none); RTEN_I8_KS = "<parts>[,<tile>]" selects it (a measurement knob: tile 0 = 128x128, 1 = 128x64, else 64x64).
+// Returns the tile to split on, with a.ks = the parts; or kNoTile, with a.ks = 0.
+Tile k_split_tile(const rten_hip_ctx *ctx, FastArgs &a) {
+    static const char *env_ks = getenv("RTEN_I8_KS");
+    static const int env_parts = env_ks ? atoi(env_ks) : -1, env_kst = (env_ks && strchr(env_ks, ',')) ? atoi(strchr(env_ks, ',') + 1) : -1;
+    int parts = 0;
+    if (single_row_term(a) && !a.res && a.ks >= 2 && a.slab && a.ks_counters && !(ctx->debug & 0x1000)) {
+        // MEASURED AND NOT USED BY DEFAULT (profiles/r09/int8_cross_workgroup_k_split.txt): every split loses -- s2 3x3 13.7 -> 17.1 us (2 parts, 64x64),
+        // 16.9 (2 parts, 128x64), 19.0 (128x128), 20.8 (4 parts); s3 3x3 12.6 -> 15.7; K = 1024 1x1 9.1 -> 13.6; the int8 step 1.48 -> 1.53 ms (one
+        // replica), 0.89 -> 0.97 (four).  The hand-off (16-64 KB of write-through partials per workgroup, the counter, the L2-bypassing reload) costs 4-7 us
+        // against a k-loop of ~6 us that it can shorten by half at best; the in-workgroup form (k-groups through LDS) stays the rule for stage 3.
+        if (env_parts >= 0) parts = env_parts;
+        if (parts > a.ks) parts = a.ks;
+        if (parts > (a.Kp + 63) / 64) parts = (a.Kp + 63) / 64;
+    }
+    const Tile t = tile_of(env_kst == 0 || env_kst == 1 ? env_kst : 3, false);
+    a.ks = parts >= 2 && tile_count(a, t) <= rten_hip_ctx::kSplitCounters ? parts : 0;
+    return a.ks ? t : kNoTile;
+}
+
+} // namespace
+
+int32_t rten_i8_dispatch_fast(rten_hip_ctx *ctx, void *args, double ops, double bytes) {
+    FastArgs &a = *static_cast<FastArgs *>(args);
+    // tile choice: the largest tile that still gives every CU a workgroup (the tile DMA of a workgroup tops out far below what the MFMAs could consume, so an
+    // idle CU costs more than the extra operand re-reads of a smaller tile); tile order: consecutive workgroup ids (one XCD's share) walk the axis of the
+    // SMALLER operand, so that the larger one is fetched into as few of the eight L2s as possible
     static const int env_tile = getenv("RTEN_I8_TILE") ? atoi(getenv("RTEN_I8_TILE")) : -1; // (tuning: 0 = 128x128, 1 = 128x64, 2 = 64x128, 3 = 64x64)
-    const int tile = env_tile >= 0 ? env_tile : (ctx->int8_tile >= 0 ? ctx->int8_tile : (a.M <= 64 ? 2 : (t128 >= ctx->num_cus ? 0 : (t12864 >= ctx->num_cus ? 1 : 3))));
-    // tile order: consecutive workgroup ids (one XCD's share) walk the axis of the SMALLER operand, so that the larger
-    // one is fetched into as few of the eight L2s as possible
+    const int setting = env_tile >= 0 ? env_tile : ctx->int8_tile >= 0 ? ctx->int8_tile : a.M <= 64 ? 2 : tile_count(a, T128x128) >= ctx->num_cus ? 0 : tile_count(a, T128x64) >= ctx->num_cus ? 1 : 3;
+    const Tile tile = tile_of(setting, four_k_groups(ctx, a)); // (the plain kernels' choice)
     a.n_fastest = (double)a.a_bytes > (double)a.b_bytes ? 1 : 0;
-    // (256-byte k-tiles were measured and are slower: profiles/r05/int8_notes.md)
+    bool ok; // false: a quantized-output launch that was refused (the other forms always launch)
     if (a.q_out && a.in_stats) { // recompute form of a quantized output (QO == 2): the plain kernels' tile choice, nothing to fit
-        const long long t64 = (long long)((a.M + 63) / 64) * ((a.N + 63) / 64);
-        const int nkt = (a.Kp + 63) / 64;
-        const bool kg4 = !(ctx->debug & 0x800) && t64 * 4 <= 5 * ctx->num_cus && nkt >= 16;
-        bool ok;
-        if (tile == 0) ok = launch_fast<128, 128, 3, 64, 1, false, 2>(ctx, a, "igemm_i8_fast_kernel<128,128,qo2>", ops, bytes);
-        else if (tile == 1) ok = launch_fast<128, 64, 3, 64, 1, false, 2>(ctx, a, "igemm_i8_fast_kernel<128,64,qo2>", ops, bytes);
-        else if (tile == 2) ok = launch_fast<64, 128, 3, 64, 1, false, 2>(ctx, a, "igemm_i8_fast_kernel<64,128,qo2>", ops, bytes);
-        else if (kg4) ok = launch_fast<64, 64, 3, 64, 4, false, 2>(ctx, a, "igemm_i8_fast_kernel<64,64,kg4,qo2>", ops, bytes);
-        else ok = launch_fast<64, 64, 3, 64, 1, false, 2>(ctx, a, "igemm_i8_fast_kernel<64,64,qo2>", ops, bytes);
-        if (!ok) return RTEN_HIP_ERR_UNSUPPORTED;
-        RTEN_LAUNCH_CHECK(ctx, "igemm_i8_fast_kernel launch");
-        return RTEN_HIP_OK;
-    }
-    if (a.q_out) { // quantized-output form (rten_hip_conv2d_int8_qout): the same tile choice, or the next larger one that fits the chip at once
-        const long long t64 = (long long)((a.M + 63) / 64) * ((a.N + 63) / 64);
-        const int nkt = (a.Kp + 63) / 64;
-        const bool kg4 = !(ctx->debug & 0x800) && t64 * 4 <= 5 * ctx->num_cus && nkt >= 16;
-        bool ok = false;
-        if (tile == 0) ok = launch_fast<128, 128, 3, 64, 1, false, true>(ctx, a, "igemm_i8_fast_kernel<128,128,qo>", ops, bytes);
-        else if (tile == 1) ok = launch_fast<128, 64, 3, 64, 1, false, true>(ctx, a, "igemm_i8_fast_kernel<128,64,qo>", ops, bytes) ||
-                                 launch_fast<128, 128, 3, 64, 1, false, true>(ctx, a, "igemm_i8_fast_kernel<128,128,qo>", ops, bytes);
-        else if (tile == 2) ok = launch_fast<64, 128, 3, 64, 1, false, true>(ctx, a, "igemm_i8_fast_kernel<64,128,qo>", ops, bytes) ||
-                                 launch_fast<64, 256, 3, 64, 1, false, true>(ctx, a, "igemm_i8_fast_kernel<64,256,qo>", ops, bytes);
-        else if (kg4) ok = launch_fast<64, 64, 3, 64, 4, false, true>(ctx, a, "igemm_i8_fast_kernel<64,64,kg4,qo>", ops, bytes);
-        else ok = launch_fast<64, 64, 3, 64, 1, false, true>(ctx, a, "igemm_i8_fast_kernel<64,64,qo>", ops, bytes) ||
-                  launch_fast<128, 64, 3, 64, 1, false, true>(ctx, a, "igemm_i8_fast_kernel<128,64,qo>", ops, bytes);
-        if (!ok) return RTEN_HIP_ERR_UNSUPPORTED; // more workgroups than the device holds at once: run the two-launch sequence
-        RTEN_LAUNCH_CHECK(ctx, "igemm_i8_fast_kernel launch");
-        return RTEN_HIP_OK;
-    }
-    if (a.xf) { // quantize-on-load form (rten_hip_conv2d_int8_dql)
-        if (tile == 0) launch_fast<128, 128, 3, 64, 1, true>(ctx, a, "igemm_i8_fast_kernel<128,128,bq>", ops, bytes);
-        else if (tile == 1) launch_fast<128, 64, 3, 64, 1, true>(ctx, a, "igemm_i8_fast_kernel<128,64,bq>", ops, bytes);
-        else if (tile == 2) launch_fast<64, 128, 3, 64, 1, true>(ctx, a, "igemm_i8_fast_kernel<64,128,bq>", ops, bytes);
-        else launch_fast<64, 64, 3, 64, 1, true>(ctx, a, "igemm_i8_fast_kernel<64,64,bq>", ops, bytes);
-        RTEN_LAUNCH_CHECK(ctx, "igemm_i8_fast_kernel launch");
-        return RTEN_HIP_OK;
-    }
-    // Cross-workgroup K split (KS kernels): under-filled long-K launches of the single-row-term convolution form without a residual.  `a.ks` = the largest
-    // split the caller's slab holds (0: none); RTEN_I8_KS = "<parts>[,<tile>]" selects it (a measurement knob: tile 0 = 128x128, 1 = 128x64, 3 = 64x64).
-    {
-        const bool rt = a.conv && !(a.debug_flags & 1) && a.a_zp == nullptr && a.a_signed && a.b_zp_len <= 1 && !a.need_csum;
-        static const char *env_ks = getenv("RTEN_I8_KS");
-        static const int env_parts = env_ks ? atoi(env_ks) : -1, env_kst = (env_ks && strchr(env_ks, ',')) ? atoi(strchr(env_ks, ',') + 1) : -1;
-        const int nkt = (a.Kp + 63) / 64;
-        const long long t64 = (long long)((a.M + 63) / 64) * ((a.N + 63) / 64);
-        int parts = 0, kst = 3;
-        if (rt && !a.res && a.ks >= 2 && a.slab && a.ks_counters && !(ctx->debug & 0x1000)) {
-            // MEASURED AND NOT USED BY DEFAULT (profiles/r09/int8_cross_workgroup_k_split.txt): every split loses -- s2 3x3 13.7 -> 17.1 us (2 parts, 64x64),
-            // 16.9 (2 parts, 128x64), 19.0 (128x128), 20.8 (4 parts); s3 3x3 12.6 -> 15.7; K = 1024 1x1 9.1 -> 13.6; the int8 step 1.48 -> 1.53 ms (one
-            // replica), 0.89 -> 0.97 (four).  The hand-off (16-64 KB of write-through partials per workgroup, the counter, the L2-bypassing reload) costs 4-7 us
-            // against a k-loop of ~6 us that it can shorten by half at best; the in-workgroup form (k-groups through LDS) stays the rule for stage 3.
-            if (env_parts >= 0) { parts = env_parts; kst = env_kst >= 0 ? env_kst : 3; }
-            if (parts > a.ks) parts = a.ks;
-            if (parts > nkt) parts = nkt;
-        }
-        if (parts >= 2) {
-            a.ks = parts;
-            const long long tiles = kst == 0 ? t128 : kst == 1 ? t12864 : t64;
-            if (tiles <= rten_hip_ctx::kSplitCounters) {
-                if (kst == 0) launch_fast<128, 128, 3, 64, 1, false, false, true>(ctx, a, "igemm_i8_fast_kernel<128,128,ks>", ops, bytes);
-                else if (kst == 1) launch_fast<128, 64, 3, 64, 1, false, false, true>(ctx, a, "igemm_i8_fast_kernel<128,64,ks>", ops, bytes);
-                else launch_fast<64, 64, 3, 64, 1, false, false, true>(ctx, a, "igemm_i8_fast_kernel<64,64,ks>", ops, bytes);
-                RTEN_LAUNCH_CHECK(ctx, "igemm_i8_fast_kernel launch");
-                return RTEN_HIP_OK;
-            }
-        }
-        a.ks = 0;
-    }
-    // (measured again in round 3 and dropped -- profiles/r06/int8_tile_experiments.txt: 128-byte k-tiles on the 128x64 / 64x128 / 64x64 tiles
-    // +5 % on the whole conv time, the next larger tile for the under-filled launches +6 %, four LDS stages +2 %; no layer gains more than 5 %)
-    if (tile == 0) {
-        launch_fast<128, 128, 3>(ctx, a, "igemm_i8_fast_kernel<128,128>", ops, bytes);
-    } else if (tile == 1) {
-        launch_fast<128, 64, 3>(ctx, a, "igemm_i8_fast_kernel<128,64>", ops, bytes);
-    } else if (tile == 2) {
-        launch_fast<64, 128, 3>(ctx, a, "igemm_i8_fast_kernel<64,128>", ops, bytes);
+        ok = launch_tile<RECOMPUTE>(ctx, a, tile, ops, bytes);
+    } else if (a.q_out) { // exchange form (QO == 1): the same tile choice, or the next larger one that fits the chip at once; else the caller runs the two-launch sequence
+        const Tile larger = next_larger(tile);
+        ok = launch_tile<EXCHANGE>(ctx, a, tile, ops, bytes) || (larger != kNoTile && launch_tile<EXCHANGE>(ctx, a, larger, ops, bytes));
+    } else if (a.xf) { // quantize-on-load form (rten_hip_conv2d_int8_dql): one k-group on every tile
+        ok = launch_tile<LOADQ>(ctx, a, tile_of(setting, false), ops, bytes);
+    } else if (const Tile split = k_split_tile(ctx, a); split != kNoTile) {
+        ok = launch_tile<KSPLIT>(ctx, a, split, ops, bytes);
     } else {
-        // under-filled launches (fewer than ~2 workgroups per CU) split K over 2 or 4 k-groups inside the workgroup: more waves
-        // per SIMD to hide the k-loop's latencies behind each other (RTEN_HIP_DEBUG bit 0x800 turns this off)
-        const long long t64 = (long long)((a.M + 63) / 64) * ((a.N + 63) / 64);
-        const int nkt = (a.Kp + 63) / 64;
-        // measured (profiles/r05/int8_per_layer.txt): 4 groups pay off below ~1.25 workgroups per CU with K >= 1024 bytes (stage-4 3x3:
-        // 20.8 -> 14.8 us); 2 groups on the 1.5-workgroup launches of stage 3 do not (10.3 -> 11.5 us) and are not used
-        const int kgs = (ctx->debug & 0x800) ? 1 : (t64 * 4 <= 5 * ctx->num_cus && nkt >= 16 ? 4 : 1);
-        if (kgs == 4) launch_fast<64, 64, 3, 64, 4>(ctx, a, "igemm_i8_fast_kernel<64,64,kg4>", ops, bytes);
-        else launch_fast<64, 64, 3>(ctx, a, "igemm_i8_fast_kernel<64,64>", ops, bytes);
+        ok = launch_tile<PLAIN>(ctx, a, tile, ops, bytes);
     }
+    if (!ok) return RTEN_HIP_ERR_UNSUPPORTED;
     RTEN_LAUNCH_CHECK(ctx, "igemm_i8_fast_kernel launch");
     return RTEN_HIP_OK;
 }
 
-} // namespace
-
-namespace {
-inline int gemm_kp(int k) { return (k + KT - 1) / KT * KT; }
-inline bool gemm_b_covered(int k, int n) { return k > 0 && n > 0 && k <= (1 << 18) && (long long)n * gemm_kp(k) < (1ll << 31); } // K bound: the kernel's chunk table lives in LDS
-
-// rows of a strided u8 / i8 matrix -> chunk-major signed operand + row sums (both packers; see the kernels)
-void pack_rows(rten_hip_ctx *ctx, const void *src, long long row_stride, long long k_stride, int rows, int k, int Kp, unsigned flip, char *dst, char *sums) {
-    if (k_stride == 1) {
-        hipLaunchKernelGGL(i8_pack_rows_kernel, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const uint8_t *)src, row_stride, k_stride, k, k, 1, Kp, Kp, rows, flip,
-                           (uint8_t *)dst, (int *)sums);
-    } else {
-        hipMemsetAsync(sums, 0, (size_t)rows * 4, ctx->stream);
-        hipLaunchKernelGGL(i8_pack_rows_t_kernel, dim3((unsigned)((rows + 63) / 64), (unsigned)(Kp / 64)), dim3(256), 0, ctx->stream, (const uint8_t *)src, row_stride, k_stride,
-                           rows, k, Kp, flip, (uint8_t *)dst, (int *)sums);
-    }
-}
-} // namespace
-
-// Load-time staging of a constant MatMulInteger RHS (PackedBMatrix, rten-gemm/src/prepack.rs:19-120; packing/int8.rs:80-249
-// keeps the column sums inside the packed image, as here).  Layout: [Kp/16][n][16] signed bytes, then int32[n] column sums.
-RTEN_EXPORT size_t rten_hip_gemm_int8_packed_bytes(int32_t k, int32_t n) {
-    if (!gemm_b_covered(k, n)) return 0;
-    return up256((size_t)n * gemm_kp(k)) + up256((size_t)n * 4);
-}
-
-RTEN_EXPORT int32_t rten_hip_gemm_int8_prepack(rten_hip_ctx *ctx, int32_t k, int32_t n, const void *b, int64_t b_rs, int64_t b_cs, int32_t b_signed, void *packed) {
-    RTEN_CHECK_CTX(ctx);
-    if (!b || !packed) return RTEN_HIP_ERR_INVALID_VALUE;
-    if (!gemm_b_covered(k, n)) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "gemm_int8 prepack: shape not covered by the staged kernel (packed_bytes == 0)");
-    if (b_rs < 0 || b_cs < 0) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "gemm_int8 prepack: negative strides are not supported");
-    const int Kp = gemm_kp(k);
-    pack_rows(ctx, b, b_cs, b_rs, n, k, Kp, b_signed ? 0u : 0x80u, (char *)packed, (char *)packed + up256((size_t)n * Kp));
-    RTEN_LAUNCH_CHECK(ctx, "i8_pack_rows_kernel launch");
-    return RTEN_HIP_OK;
-}
-
-// Entry points used by int8.hip: return RTEN_HIP_ERR_UNSUPPORTED when the fast path does not cover the call
-// (the caller then falls back to the generic kernel).
-int32_t rten_i8_fast_gemm(rten_hip_ctx *ctx, const rten_hip_gemm_int8_desc *d, const void *a, const void *b, const void *a_zp,
-                          const void *b_zp, const float *scale, void *c) {
-    const int Kp = gemm_kp(d->k);
-    if (d->k <= 0 || (long long)d->m * Kp >= (1ll << 31) || !gemm_b_covered(d->k, d->n) || (long long)d->m * d->ldc >= (1ll << 29))
-        return RTEN_HIP_ERR_UNSUPPORTED;
-    // per call: the activation side (A) is staged; B too unless the caller prepacked it at load (MatMulInteger weights)
-    const size_t b_img = up256((size_t)d->n * Kp);
-    const size_t offA = 4096, offRs = offA + up256((size_t)d->m * Kp), offB = offRs + up256((size_t)d->m * 4),
-                 offCs = offB + (d->b_prepacked ? 0 : b_img), total = offCs + (d->b_prepacked ? 0 : up256((size_t)d->n * 4));
-    char *sc = (char *)rten_scratch(ctx, total);
-    if (!sc) return rten_set_error(ctx, RTEN_HIP_ERR_HIP, "int8 staging allocation failed (or attempted during graph capture)");
-    pack_rows(ctx, a, d->a_rs, d->a_cs, d->m, d->k, Kp, d->a_signed ? 0u : 0x80u, sc + offA, sc + offRs);
-    if (!d->b_prepacked) pack_rows(ctx, b, d->b_cs, d->b_rs, d->n, d->k, Kp, d->b_signed ? 0u : 0x80u, sc + offB, sc + offCs);
-    RTEN_LAUNCH_CHECK(ctx, "i8_pack_rows_kernel launch");
-    FastArgs g = {};
-    g.A = (const uint8_t *)(sc + offA);
-    g.B = d->b_prepacked ? (const uint8_t *)b : (const uint8_t *)(sc + offB);
-    g.rsum = (const int *)(sc + offRs);
-    g.csum = d->b_prepacked ? (const int *)((const char *)b + b_img) : (const int *)(sc + offCs);
-    g.C = c;
-    g.a_zp = d->a_zp_len ? (const uint8_t *)a_zp : nullptr;
-    g.b_zp = d->b_zp_len ? (const uint8_t *)b_zp : nullptr;
-    g.scale = d->scale_len ? scale : nullptr;
-    g.M = d->m; g.N = d->n; g.Kp = Kp; g.Kreal = d->k;
-    g.a_bytes = (unsigned)((size_t)d->m * Kp); g.b_bytes = (unsigned)((size_t)d->n * Kp);
-    g.c_rs = d->ldc; g.c_ns = 0; g.Pn = d->n;
-    g.a_signed = d->a_signed; g.b_signed = d->b_signed;
-    g.a_zp_len = d->a_zp_len; g.b_zp_len = d->b_zp_len; g.scale_len = d->scale_len;
-    return dispatch_fast(ctx, g, 2.0 * d->m * (double)d->n * d->k, (double)d->m * d->k + (double)d->k * d->n + 4.0 * d->m * d->n);
-}
-
-namespace {
-// `packed` (round 6): the few-channel form of stage_packed_chunks -- C <= 4 input channels and a kernel at least two columns wide.  The choice depends on C, KW
-// and the group count ONLY: weights are prepacked from a descriptor that knows nothing else (ConvInteger::prepack), and every zero-point form stays exact -- the
-// unused bytes of a chunk are 0 in the signed domain on BOTH operands, like the padded channels of the 16-channel-block form, so they add nothing to the product,
-// the row sums or the column sums.  Cp / Wp / taps / Kp / img then describe the VIRTUAL convolution the kernel walks (16 channels, KW = nch, stride nch over
-// OW * nch virtual columns); sx / kw / dx say so to the launch.
-struct ConvGeom { int Cp, Hp, Wp, taps, Kreal, Kp, P; size_t img; bool ok; bool packed; int nch, cpc, sx, kw, dx; };
-ConvGeom conv_geom(const rten_hip_conv2d_int8_desc *di) {
-    const rten_hip_conv2d_desc *d = &di->conv;
-    ConvGeom g = {};
-    g.Cp = (d->c + 15) / 16 * 16;
-    g.Hp = d->h + d->pads[0] + d->pads[2];
-    g.Wp = d->w + d->pads[1] + d->pads[3];
-    g.taps = d->kh * d->kw;
-    g.Kreal = d->c * g.taps;
-    g.P = d->out_h * d->out_w;
-    g.sx = d->stride_w; g.kw = d->kw; g.dx = d->dil_w;
-    static const bool no_pack = getenv("RTEN_I8_NO_PACK") != nullptr; // (A/B switch: the 16-channel-block form for every geometry)
-    if (!no_pack && d->groups == 1 && d->c >= 1 && d->c <= 4 && d->kw >= 2 && d->out_w > 0) {
-        g.cpc = 16 / d->c;
-        g.nch = (d->kw + g.cpc - 1) / g.cpc;
-        if (g.nch < d->kw && g.nch <= 2) { // fewer chunks per kernel row than taps: the smaller product (one or two chunks per output column are instantiated)
-            g.packed = true;
-            g.Cp = 16;
-            g.Wp = d->out_w * g.nch;
-            g.taps = d->kh * g.nch;
-            g.sx = g.nch; g.kw = g.nch; g.dx = 1;
-        }
-    }
-    g.Kp = (g.taps * g.Cp + KT - 1) / KT * KT;
-    g.img = (size_t)d->n * g.Hp * g.Wp * g.Cp;
-    g.ok = d->groups == 1 && d->c > 0 && d->o > 0 && g.Kp <= (1 << 18) && // (the kernel's chunk -> offset table lives in LDS)
-           // the chunk walk addresses taps on the padded image: the window must fit (true for valid conv geometry)
-           (d->out_h - 1) * d->stride_h + (d->kh - 1) * d->dil_h < g.Hp && (d->out_w - 1) * g.sx + (g.kw - 1) * g.dx < g.Wp &&
-           g.img < (1ull << 31) && (size_t)d->o * g.Kp < (1ull << 31) && (long long)d->n * d->o * g.P < (1ll << 29);
-    return g;
-}
-} // namespace
-
-namespace {
-ScaleProducts one_product(const float *mul_by, float *product) {
-    ScaleProducts sp = {};
-    if (mul_by) { sp.count = 1; sp.mul_by[0] = mul_by; sp.product[0] = product; }
-    return sp;
-}
-
-void launch_quantize_stage(rten_hip_ctx *ctx, const rten_hip_conv2d_desc *d, const ConvGeom &g, const float *x, const float *ws, int nparts, void *staged,
-                           int pad_mode, float *scale, uint8_t *zero_point, const ScaleProducts &sp) {
-    if (g.packed) {
-        const dim3 pgrid((unsigned)((d->out_w + 127) / 128), (unsigned)((g.Hp + 1) / 2), (unsigned)d->n);
-        RTEN_PACKED_DISPATCH(i8_quantize_packed_kernel, d->c, g.nch, pgrid, x, ws, nparts, (uint8_t *)staged, d->h, d->w, g.Hp, d->out_w, d->kw, d->stride_w, d->dil_w, d->pads[0],
-                             d->pads[1], pad_mode, scale, zero_point, sp);
-        return;
-    }
-    const dim3 grid((unsigned)((d->h * d->w + 255) / 256), (unsigned)d->n, (unsigned)(g.Cp / 16));
-    const dim3 grid_small((unsigned)((g.Hp * g.Wp + 63) / 64), (unsigned)d->n, (unsigned)((g.Cp + 63) / 64));
-    const bool vec = (d->h * d->w) % 4 == 0 && ((uintptr_t)x & 15) == 0;
-#define QS_ARGS x, ws, nparts, (uint8_t *)staged, d->c, d->h, d->w, g.Hp, g.Wp, g.Cp, d->pads[0], d->pads[1], pad_mode, scale, zero_point, sp
-    if (d->h * d->w < 128) hipLaunchKernelGGL(i8_quantize_stage_kernel<0>, grid_small, dim3(256), 0, ctx->stream, QS_ARGS);
-    else if (vec) hipLaunchKernelGGL(i8_quantize_stage_kernel<2>, grid, dim3(256), 0, ctx->stream, QS_ARGS);
-    else hipLaunchKernelGGL(i8_quantize_stage_kernel<1>, grid, dim3(256), 0, ctx->stream, QS_ARGS);
-#undef QS_ARGS
-}
-} // namespace
-
-RTEN_EXPORT size_t rten_hip_conv2d_int8_packed_bytes(const rten_hip_conv2d_int8_desc *di) {
-    if (!di) return 0;
-    const ConvGeom g = conv_geom(di);
-    return g.ok ? up256((size_t)di->conv.o * g.Kp) + (size_t)di->conv.o * 4 : 0;
-}
-
-RTEN_EXPORT int32_t rten_hip_conv2d_int8_prepack(rten_hip_ctx *ctx, const rten_hip_conv2d_int8_desc *di, const void *w, void *packed) {
-    RTEN_CHECK_CTX(ctx);
-    if (!di || !w || !packed) return RTEN_HIP_ERR_INVALID_VALUE;
-    const ConvGeom g = conv_geom(di);
-    if (!g.ok) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "conv_int8 prepack: geometry not covered by the staged kernel (packed_bytes == 0)");
-    const rten_hip_conv2d_desc *d = &di->conv;
-    hipLaunchKernelGGL(i8_pack_rows_kernel, dim3((unsigned)d->o), dim3(256), 0, ctx->stream, (const uint8_t *)w, (long long)g.Kreal, 1ll, g.Kreal, d->c, d->kh * d->kw,
-                       g.Cp, g.Kp, d->o, di->w_signed ? 0u : 0x80u, (uint8_t *)packed, (int *)((char *)packed + up256((size_t)d->o * g.Kp)), g.packed ? g.nch : 0, g.cpc,
-                       d->kw);
-    RTEN_LAUNCH_CHECK(ctx, "i8_pack_rows_kernel launch");
-    return RTEN_HIP_OK;
-}
-
-RTEN_EXPORT size_t rten_hip_conv2d_int8_staged_bytes(const rten_hip_conv2d_int8_desc *di) {
-    if (!di || di->x_signed) return 0;
-    const ConvGeom g = conv_geom(di);
-    return g.ok ? up256(g.img) : 0;
-}
-
-RTEN_EXPORT int32_t rten_hip_dynamic_quantize_linear_staged(rten_hip_ctx *ctx, const rten_hip_conv2d_int8_desc *di, const float *x, void *staged,
-                                                            float *scale, uint8_t *zero_point, const float *mul_by, float *product) {
-    RTEN_CHECK_CTX(ctx);
-    if (!di || !x || !staged || !scale || !zero_point || (mul_by && !product)) return RTEN_HIP_ERR_INVALID_VALUE;
-    const ConvGeom g = conv_geom(di);
-    if (!g.ok || di->x_signed) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "quantize_staged: geometry not covered by the staged kernel (staged_bytes == 0)");
-    const rten_hip_conv2d_desc *d = &di->conv;
-    const int64_t n = (int64_t)d->n * d->c * d->h * d->w;
-    ProfScope ps(ctx, "dynamic_quantize_linear_staged", 0.0, 8.0 * n + (double)g.img);
-    int nparts = 0;
-    const float *ws = rten_dql_minmax(ctx, n, x, &nparts);
-    if (!ws) return rten_set_error(ctx, RTEN_HIP_ERR_HIP, "dql: scratch allocation failed");
-    launch_quantize_stage(ctx, d, g, x, ws, nparts, staged, rten_effective_pad_mode(di), scale, zero_point, one_product(mul_by, product));
-    RTEN_LAUNCH_CHECK(ctx, "i8_quantize_stage_kernel launch");
-    return RTEN_HIP_OK;
-}
-
-RTEN_EXPORT size_t rten_hip_minmax_stats_bytes(void) { return 2 * dql::kStatSlots * sizeof(unsigned); }
-
-namespace {
-__global__ void stats_reset_kernel(unsigned *stats, int count) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x; // one thread per slot word
-    if (i < count * 2 * dql::kStatSlots) stats[i] = (i % (2 * dql::kStatSlots)) < dql::kStatSlots ? 0xffffffffu : 0u; // minima | maxima
-}
-} // namespace
-
-RTEN_EXPORT int32_t rten_hip_minmax_stats_reset(rten_hip_ctx *ctx, void *stats, int32_t count) {
-    RTEN_CHECK_CTX(ctx);
-    if (!stats || count < 1) return RTEN_HIP_ERR_INVALID_VALUE;
-    const int n = count * 2 * dql::kStatSlots;
-    hipLaunchKernelGGL(stats_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (unsigned *)stats, count);
-    RTEN_LAUNCH_CHECK(ctx, "stats_reset_kernel launch");
-    return RTEN_HIP_OK;
-}
-
-RTEN_EXPORT int32_t rten_hip_dynamic_quantize_linear_staged_stats(rten_hip_ctx *ctx, const rten_hip_conv2d_int8_desc *di, const float *x, const void *stats,
-                                                                  void *staged, float *scale, uint8_t *zero_point, const float *mul_by, float *product) {
-    RTEN_CHECK_CTX(ctx);
-    if (!di || !x || !stats || !staged || !scale || !zero_point || (mul_by && !product)) return RTEN_HIP_ERR_INVALID_VALUE;
-    const ConvGeom g = conv_geom(di);
-    if (!g.ok || di->x_signed) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "quantize_staged: geometry not covered by the staged kernel (staged_bytes == 0)");
-    const rten_hip_conv2d_desc *d = &di->conv;
-    ProfScope ps(ctx, "dynamic_quantize_linear_staged_stats", 0.0, 4.0 * d->n * d->c * (double)d->h * d->w + (double)g.img);
-    launch_quantize_stage(ctx, d, g, x, (const float *)stats, -1, staged, rten_effective_pad_mode(di), scale, zero_point, one_product(mul_by, product));
-    RTEN_LAUNCH_CHECK(ctx, "i8_quantize_stage_kernel launch");
-    return RTEN_HIP_OK;
-}
-
-RTEN_EXPORT int32_t rten_hip_dynamic_quantize_linear_staged_products(rten_hip_ctx *ctx, const rten_hip_conv2d_int8_desc *di, const float *x, const void *stats,
-                                                                     void *staged, float *scale, uint8_t *zero_point, int32_t count,
-                                                                     const float *const *mul_by, float *const *product) {
-    RTEN_CHECK_CTX(ctx);
-    if (!di || !x || !staged || !scale || !zero_point || count < 0 || (count > 0 && (!mul_by || !product))) return RTEN_HIP_ERR_INVALID_VALUE;
-    if (count > kMaxProducts) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "quantize_staged_products: at most 4 scale products per launch");
-    ScaleProducts sp = {};
-    sp.count = count;
-    for (int i = 0; i < count; i++) {
-        if (!mul_by[i] || !product[i]) return RTEN_HIP_ERR_INVALID_VALUE;
-        sp.mul_by[i] = mul_by[i];
-        sp.product[i] = product[i];
-    }
-    const ConvGeom g = conv_geom(di);
-    if (!g.ok || di->x_signed) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "quantize_staged: geometry not covered by the staged kernel (staged_bytes == 0)");
-    const rten_hip_conv2d_desc *d = &di->conv;
-    const int64_t n = (int64_t)d->n * d->c * d->h * d->w;
-    if (stats) {
-        ProfScope ps(ctx, "dynamic_quantize_linear_staged_stats", 0.0, 4.0 * n + (double)g.img);
-        launch_quantize_stage(ctx, d, g, x, (const float *)stats, -1, staged, rten_effective_pad_mode(di), scale, zero_point, sp);
-    } else {
-        ProfScope ps(ctx, "dynamic_quantize_linear_staged", 0.0, 8.0 * n + (double)g.img);
-        int nparts = 0;
-        const float *ws = rten_dql_minmax(ctx, n, x, &nparts);
-        if (!ws) return rten_set_error(ctx, RTEN_HIP_ERR_HIP, "dql: scratch allocation failed");
-        launch_quantize_stage(ctx, d, g, x, ws, nparts, staged, rten_effective_pad_mode(di), scale, zero_point, sp);
-    }
-    RTEN_LAUNCH_CHECK(ctx, "i8_quantize_stage_kernel launch");
-    return RTEN_HIP_OK;
-}
-
-namespace {
-struct QOutArgs { // the consumer side of rten_hip_conv2d_int8_qout
-    const rten_hip_conv2d_int8_desc *next;
-    void *sync, *staged;
-    float *scale;
-    uint8_t *zp;
-    const float *mul_by;
-    float *product;
-};
-int32_t i8_fast_conv_impl(rten_hip_ctx *ctx, const rten_hip_conv2d_int8_desc *di, const void *x, const void *w, const void *x_zp, const void *w_zp,
-                          const float *scale, const float *bias, const float *residual, uint32_t flags, void *y, void *stats, const QOutArgs *qo);
-} // namespace
-
-int32_t rten_i8_fast_conv(rten_hip_ctx *ctx, const rten_hip_conv2d_int8_desc *di, const void *x, const void *w, const void *x_zp,
-                          const void *w_zp, const float *scale, const float *bias, const float *residual, uint32_t flags, void *y, void *stats) {
-    return i8_fast_conv_impl(ctx, di, x, w, x_zp, w_zp, scale, bias, residual, flags, y, stats, nullptr);
-}
-
-namespace {
-int32_t i8_fast_conv_impl(rten_hip_ctx *ctx, const rten_hip_conv2d_int8_desc *di, const void *x, const void *w, const void *x_zp, const void *w_zp,
-                          const float *scale, const float *bias, const float *residual, uint32_t flags, void *y, void *stats, const QOutArgs *qo) {
-    const rten_hip_conv2d_desc *d = &di->conv;
-    const ConvGeom cg = conv_geom(di);
-    if (!cg.ok)
-        return (di->weights_packed || di->x_staged) ? rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "conv_int8: staged operands for an unsupported geometry")
-                                                    : RTEN_HIP_ERR_UNSUPPORTED;
-    const size_t wbytes = di->weights_packed ? 0 : up256((size_t)d->o * cg.Kp) + up256((size_t)d->o * 4);
-    // cross-workgroup K split (KS kernels): a slab for up to kKsMax int32 partials of the (tile-padded) output, for the launches the dispatcher may split
-    constexpr int kKsMax = 4;
-    const long long n_cols = (long long)d->n * cg.P;
-    const long long t64 = (long long)((d->o + 63) / 64) * ((n_cols + 63) / 64);
-    static const bool ks_knob = getenv("RTEN_I8_KS") != nullptr && atoi(getenv("RTEN_I8_KS")) >= 2; // (no slab, no scratch growth, unless the measurement knob is set)
-    const bool ks_candidate = ks_knob && !qo && scale && !(flags & RTEN_HIP_CONV_RESIDUAL) && cg.Kp >= 16 * 64 && t64 <= 3 * (long long)ctx->num_cus && ctx->split_counters;
-    const size_t slab_bytes = ks_candidate ? (size_t)kKsMax * (size_t)((d->o + 127) / 128 * 128) * (size_t)((n_cols + 127) / 128 * 128) * 4 : 0;
-    const size_t offA = 4096, offB = offA + wbytes, offS = offB + (di->x_staged ? 0 : up256(cg.img)), total = offS + slab_bytes;
-    char *sc = (char *)rten_scratch(ctx, total);
-    if (!sc) return rten_set_error(ctx, RTEN_HIP_ERR_HIP, "int8 staging allocation failed (or attempted during graph capture)");
-    const uint8_t *Ap;
-    const int *rsum;
-    if (di->weights_packed) {
-        Ap = (const uint8_t *)w;
-        rsum = (const int *)((const char *)w + up256((size_t)d->o * cg.Kp));
-    } else {
-        Ap = (const uint8_t *)(sc + offA);
-        rsum = (const int *)(sc + offA + up256((size_t)d->o * cg.Kp));
-        hipLaunchKernelGGL(i8_pack_rows_kernel, dim3((unsigned)d->o), dim3(256), 0, ctx->stream, (const uint8_t *)w, (long long)cg.Kreal, 1ll, cg.Kreal, d->c,
-                           d->kh * d->kw, cg.Cp, cg.Kp, d->o, di->w_signed ? 0u : 0x80u, (uint8_t *)Ap, (int *)rsum, cg.packed ? cg.nch : 0, cg.cpc, d->kw);
-    }
-    if (!di->x_staged && cg.packed) {
-        const dim3 pgrid((unsigned)((d->out_w + 127) / 128), (unsigned)((cg.Hp + 1) / 2), (unsigned)d->n);
-        RTEN_PACKED_DISPATCH(i8_pad_packed_kernel, d->c, cg.nch, pgrid, (const uint8_t *)x, (uint8_t *)(sc + offB), d->h, d->w, cg.Hp, d->out_w, d->kw, d->stride_w, d->dil_w,
-                             d->pads[0], d->pads[1], di->x_signed ? 0u : 0x80u, (const uint8_t *)x_zp, di->x_signed, rten_effective_pad_mode(di));
-    } else if (!di->x_staged)
-    {
-        const dim3 grid((unsigned)((d->h * d->w + 255) / 256), (unsigned)d->n, (unsigned)(cg.Cp / 16));
-        const dim3 grid_small((unsigned)((cg.Hp * cg.Wp + 63) / 64), (unsigned)d->n, (unsigned)((cg.Cp + 63) / 64));
-        const bool vec = (d->h * d->w) % 4 == 0 && ((uintptr_t)x & 3) == 0;
-#define PAD_ARGS (const uint8_t *)x, (uint8_t *)(sc + offB), d->c, d->h, d->w, cg.Hp, cg.Wp, cg.Cp, d->pads[0], d->pads[1], di->x_signed ? 0u : 0x80u, (const uint8_t *)x_zp, di->x_signed, rten_effective_pad_mode(di)
-        if (d->h * d->w < 128) hipLaunchKernelGGL(i8_nhwc_pad_kernel<0>, grid_small, dim3(256), 0, ctx->stream, PAD_ARGS);
-        else if (vec) hipLaunchKernelGGL(i8_nhwc_pad_kernel<2>, grid, dim3(256), 0, ctx->stream, PAD_ARGS);
-        else hipLaunchKernelGGL(i8_nhwc_pad_kernel<1>, grid, dim3(256), 0, ctx->stream, PAD_ARGS);
-#undef PAD_ARGS
-    }
-    RTEN_LAUNCH_CHECK(ctx, "int8 staging launch");
-    FastArgs g = {};
-    g.A = Ap; g.B = di->x_staged ? (const uint8_t *)x : (const uint8_t *)(sc + offB);
-    g.rsum = rsum; g.csum = nullptr;
-    g.C = y;
-    g.a_zp = di->w_zp_len ? (const uint8_t *)w_zp : nullptr;
-    g.b_zp = (const uint8_t *)x_zp;
-    g.scale = scale; g.bias = bias;
-    g.res = (flags & RTEN_HIP_CONV_RESIDUAL) ? residual : nullptr;
-    g.relu = (flags & RTEN_HIP_CONV_RELU) ? 1 : 0;
-    g.M = d->o; g.N = d->n * cg.P; g.Kp = cg.Kp; g.Kreal = cg.Kreal;
-    g.a_bytes = (unsigned)((size_t)d->o * cg.Kp); g.b_bytes = (unsigned)cg.img;
-    g.c_rs = cg.P; g.c_ns = (long long)d->o * cg.P; g.Pn = cg.P;
-    g.a_signed = di->w_signed; g.b_signed = di->x_signed;
-    g.a_zp_len = di->w_zp_len; g.b_zp_len = x_zp ? 1 : 0;
-    g.scale_len = scale ? 1 : 0;
-    g.scale_per_row = (scale && di->scale_len > 1) ? 1 : 0;
-    g.stats = scale ? (unsigned *)stats : nullptr;
-    g.need_csum = (di->w_zp_len != 0 || !di->w_signed) ? 1 : 0; // weight zero point may be non-zero in the signed domain
-    g.debug_flags = (ctx->debug & 0x200000) ? 1 : 0;
-    g.conv = 1; g.OW = d->out_w; g.sy = d->stride_h; g.sx = cg.sx; g.Hp = cg.Hp; g.Wp = cg.Wp; g.Cp = cg.Cp;
-    g.KH = d->kh; g.KW = cg.kw; g.dy = d->dil_h; g.dx = cg.dx; // (cg.sx / kw / dx: the virtual geometry of a few-channel packed image, else the convolution's own)
-    if (slab_bytes) { g.ks = kKsMax; g.slab = (int *)(sc + offS); g.ks_counters = ctx->split_counters; }
-    double out_bytes = 4.0 * d->o * g.N;
-    if (qo && !qo->sync) {
-        // Recompute form (no exchange block): launch 1 = this convolution, statistics only (nothing stored); launch 2 = the same convolution again, which
-        // folds those statistics, quantizes in its epilogue and writes the consumer's staged image (+ the f32 tensor when `y` is wanted)
-        if (!stats) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "conv2d_int8_qout (recompute form): a statistics block is required");
-        const bool rt = !(g.debug_flags & 1) && g.a_zp == nullptr && g.a_signed && !g.need_csum;
-        if (!rt || g.res) return RTEN_HIP_ERR_UNSUPPORTED; // (built for the single-row-term form without a residual: the caller runs the two operators)
-        FastArgs g1 = g;
-        g1.no_store = 1;
-        const int32_t rc1 = dispatch_fast(ctx, g1, 2.0 * d->o * (double)g.N * cg.Kreal, (double)d->o * cg.Kreal + (double)d->n * d->c * d->h * d->w);
-        if (rc1 != RTEN_HIP_OK) return rc1;
-        const ConvGeom ng = conv_geom(qo->next);
-        g.in_stats = (const unsigned *)stats;
-        g.stats = nullptr;
-        g.q_out = (uint8_t *)qo->staged;
-        g.q_scale_out = qo->scale; g.q_zp_out = qo->zp; g.q_mul_by = qo->mul_by; g.q_product = qo->product;
-        g.q_cb = ng.Cp / 16; g.q_Hp = ng.Hp; g.q_Wp = ng.Wp; g.q_pt = qo->next->conv.pads[0]; g.q_pl = qo->next->conv.pads[1];
-        g.q_H = d->out_h; g.q_W = d->out_w; g.q_pad_mode = rten_effective_pad_mode(qo->next);
-        g.q_bytes = (unsigned)ng.img;
-        g.ks = 0; g.slab = nullptr;
-        return dispatch_fast(ctx, g, 2.0 * d->o * (double)g.N * cg.Kreal,
-                             (double)d->o * cg.Kreal + (double)d->n * d->c * d->h * d->w + (y ? out_bytes : 0.0) + (double)ng.img);
-    }
-    if (qo) {
-        const ConvGeom ng = conv_geom(qo->next);
-        g.sync = (unsigned *)qo->sync;
-        g.fault = ctx->fault_dev;
-        g.q_out = (uint8_t *)qo->staged;
-        g.q_scale_out = qo->scale; g.q_zp_out = qo->zp; g.q_mul_by = qo->mul_by; g.q_product = qo->product;
-        g.q_cb = ng.Cp / 16; g.q_Hp = ng.Hp; g.q_Wp = ng.Wp; g.q_pt = qo->next->conv.pads[0]; g.q_pl = qo->next->conv.pads[1];
-        g.q_H = d->out_h; g.q_W = d->out_w; g.q_pad_mode = rten_effective_pad_mode(qo->next);
-        g.q_bytes = (unsigned)ng.img;
-        out_bytes = (y ? out_bytes : 0.0) + (double)ng.img;
-    }
-    // algorithmic bytes: i8 weights + u8 activations (once) + f32 output (+ f32 residual when the epilogue adds one); quantized-output form:
-    // the consumer's staged u8 image instead of (or, when y is wanted too, besides) the f32 output
-    return dispatch_fast(ctx, g, 2.0 * d->o * (double)g.N * cg.Kreal,
-                         (double)d->o * cg.Kreal + (double)d->n * d->c * d->h * d->w + out_bytes + (g.res ? 4.0 * d->o * g.N : 0.0));
-}
-} // namespace
-
-// ConvIntegerToFloat [+ bias] [+ residual] [+ Relu] AND the DynamicQuantizeLinear of the one convolution that consumes its output, in ONE
-// launch (igemm_i8_fast_kernel, QO): see rten_hip.h.  RTEN_HIP_ERR_UNSUPPORTED when the geometry is not covered or the launch's
-// workgroups cannot all be resident at once -- run rten_hip_conv2d_int8_stats + rten_hip_dynamic_quantize_linear_staged_stats then.
-RTEN_EXPORT size_t rten_hip_grid_sync_bytes(void) { return kSyncWords * sizeof(unsigned); }
-
-RTEN_EXPORT int32_t rten_hip_conv2d_int8_qout(rten_hip_ctx *ctx, const rten_hip_conv2d_int8_desc *di, const void *x, const void *w, const void *x_zp,
-                                              const void *w_zp, const float *scale, const float *bias, const float *residual, uint32_t flags, float *y,
-                                              void *stats, void *sync, const rten_hip_conv2d_int8_desc *next, void *next_staged, float *next_scale,
-                                              uint8_t *next_zero_point, const float *mul_by, float *product) {
-    RTEN_CHECK_CTX(ctx);
-    if (!di || !x || !w || !scale || !stats || !next || !next_staged || !next_scale || !next_zero_point || (mul_by && !product))
-        return RTEN_HIP_ERR_INVALID_VALUE; // (sync == NULL: the recompute form -- two launches, no grid-wide exchange, no residency requirement)
-    const rten_hip_conv2d_desc *d = &di->conv, *nd = &next->conv;
-    if (di->scale_len != 0 && di->scale_len != 1 && di->scale_len != d->o)
-        return rten_set_error(ctx, RTEN_HIP_ERR_INCOMPATIBLE_SHAPES, "conv_int8: scale must be a scalar or have one value per output channel");
-    if (di->w_zp_len != 0 && di->w_zp_len != 1 && di->w_zp_len != d->o) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "Zero point has incorrect size");
-    if (nd->n != d->n || nd->c != d->o || nd->h != d->out_h || nd->w != d->out_w)
-        return rten_set_error(ctx, RTEN_HIP_ERR_INCOMPATIBLE_SHAPES, "conv2d_int8_qout: the consumer's input is not this convolution's output");
-    const ConvGeom cg = conv_geom(di), ng = conv_geom(next);
-    if (!cg.ok || !ng.ok || ng.packed || next->x_signed || !di->weights_packed || !di->x_staged || d->o % 16 != 0)
-        return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "conv2d_int8_qout: staged operands, O % 16 == 0 and a consumer covered by the staged kernel only");
-    if (d->n == 0 || d->out_h == 0 || d->out_w == 0) return RTEN_HIP_OK;
-    const QOutArgs qo = {next, sync, next_staged, next_scale, next_zero_point, mul_by, product};
-    return i8_fast_conv_impl(ctx, di, x, w, x_zp, w_zp, scale, bias, residual, flags, y, stats, &qo);
-}
-
-namespace {
-__global__ void grid_sync_reset_kernel(unsigned *sync, int count) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; // one thread per word
-    if (i >= (long long)count * kSyncWords) return;
-    const unsigned w = (unsigned)(i % kSyncWords);
-    sync[i] = (w >= kSyncCtlWords && ((w - kSyncCtlWords) & 1u) == 0u) ? 0xffffffffu : 0u; // granule = {lo = 0xffffffff, hi = 0}
-}
-} // namespace
-
-// Initialises `count` consecutive exchange blocks (once, when they are allocated; every launch leaves its block in this state).
-RTEN_EXPORT int32_t rten_hip_grid_sync_reset(rten_hip_ctx *ctx, void *sync, int32_t count) {
-    RTEN_CHECK_CTX(ctx);
-    if (!sync || count < 1) return RTEN_HIP_ERR_INVALID_VALUE;
-    // the reset ends with a stream synchronise (the sticky fault is cleared after what is in flight has drained): inside a capture that would
-    // invalidate the capture instead of resetting anything -- refused, not attempted
-    if (ctx->capturing) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "grid_sync_reset: not while a graph capture is active on this context");
-    const long long n = (long long)count * kSyncWords;
-    hipLaunchKernelGGL(grid_sync_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (unsigned *)sync, count);
-    RTEN_LAUNCH_CHECK(ctx, "grid_sync_reset_kernel launch");
-    if (ctx->fault_host) { // the caller starts over: the context's sticky fault goes with the blocks' flags (after what is in flight has drained)
-        RTEN_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        *ctx->fault_host = 0u;
-    }
-    return RTEN_HIP_OK;
-}
-
-// Time-out flags of `count` consecutive barrier blocks (non-zero: a quantized-output launch gave up waiting for its grid and its results are void).
-RTEN_EXPORT int32_t rten_hip_grid_sync_timeouts(rten_hip_ctx *ctx, const void *sync, int32_t count, int32_t *timeouts) {
-    RTEN_CHECK_CTX(ctx);
-    if (!sync || count < 1 || !timeouts) return RTEN_HIP_ERR_INVALID_VALUE;
-    std::vector<unsigned> host((size_t)count * kSyncWords);
-    RTEN_HIP_TRY(ctx, hipMemcpyAsync(host.data(), sync, host.size() * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    RTEN_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    int n = 0;
-    for (int i = 0; i < count; i++) n += host[(size_t)i * kSyncWords + 8] != 0;
-    *timeouts = n;
-    return RTEN_HIP_OK;
-}
-
-
-// DynamicQuantizeLinear -> ConvInteger -> Cast -> Mul(x_scale, w_scale) [-> Add(bias)] [-> Add(residual)] [-> Relu] of a dynamically
-// quantized graph in ONE launch, for pointwise (1x1, stride 1, no padding, groups 1) convolutions whose input statistics were
-// accumulated by the producing kernel (rten_hip_conv2d_int8_stats / this function): the quantizer runs inside the B loader of the
-// integer GEMM (igemm_i8_fast_kernel, BQ).  `w` must be prepacked (rten_hip_conv2d_int8_prepack), `w_scale` is the scalar or
-// per-output-channel weight scale (di->scale_len), `x_scale_out` / `x_zero_point_out` receive DynamicQuantizeLinear's own outputs
-// (optional).  RTEN_HIP_ERR_UNSUPPORTED for any other geometry: run the staged sequence instead.
-RTEN_EXPORT int32_t rten_hip_conv2d_int8_dql(rten_hip_ctx *ctx, const rten_hip_conv2d_int8_desc *di, const float *x, const void *in_stats, const void *w,
-                                             const float *w_scale, const float *bias, const float *residual, uint32_t flags, float *y, void *out_stats,
-                                             float *x_scale_out, uint8_t *x_zero_point_out) {
-    RTEN_CHECK_CTX(ctx);
-    if (!di || !x || !in_stats || !w || !w_scale || !y) return RTEN_HIP_ERR_INVALID_VALUE;
-    const rten_hip_conv2d_desc *d = &di->conv;
-    const ConvGeom cg = conv_geom(di);
-    const bool pointwise = d->kh == 1 && d->kw == 1 && d->stride_h == 1 && d->stride_w == 1 && d->groups == 1 && d->pads[0] == 0 && d->pads[1] == 0 &&
-                           d->pads[2] == 0 && d->pads[3] == 0;
-    if (!cg.ok || !pointwise || !di->weights_packed || di->x_signed || di->w_zp_len != 0 || d->c % 64 != 0 ||
-        (long long)d->n * d->c * d->h * d->w * 4 >= (1ll << 31))
-        return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "conv2d_int8_dql: pointwise stride-1 unpadded convolutions with prepacked weights and C % 64 == 0 only");
-    if (di->scale_len != 0 && di->scale_len != 1 && di->scale_len != d->o)
-        return rten_set_error(ctx, RTEN_HIP_ERR_INCOMPATIBLE_SHAPES, "conv_int8: scale must be a scalar or have one value per output channel");
-    if (d->n == 0 || d->out_h == 0 || d->out_w == 0) return RTEN_HIP_OK;
-    FastArgs g = {};
-    g.A = (const uint8_t *)w;
-    g.rsum = (const int *)((const char *)w + up256((size_t)d->o * cg.Kp));
-    g.C = y;
-    g.xf = x; g.in_stats = (const unsigned *)in_stats; g.HW = d->h * d->w; g.Cin = d->c;
-    g.xs_out = x_scale_out; g.xz_out = x_zero_point_out;
-    g.scale = w_scale; g.bias = bias;
-    g.res = (flags & RTEN_HIP_CONV_RESIDUAL) ? residual : nullptr;
-    g.relu = (flags & RTEN_HIP_CONV_RELU) ? 1 : 0;
-    g.M = d->o; g.N = d->n * cg.P; g.Kp = cg.Kp; g.Kreal = cg.Kreal;
-    g.a_bytes = (unsigned)((size_t)d->o * cg.Kp); g.b_bytes = (unsigned)((size_t)d->n * d->c * d->h * d->w * 4);
-    g.c_rs = cg.P; g.c_ns = (long long)d->o * cg.P; g.Pn = cg.P;
-    g.a_signed = di->w_signed; g.b_signed = 0;
-    g.a_zp_len = 0; g.b_zp_len = 1;
-    g.scale_len = 1;
-    g.scale_per_row = di->scale_len > 1 ? 1 : 0;
-    g.stats = (unsigned *)out_stats;
-    g.need_csum = di->w_signed ? 0 : 1;
-    g.conv = 1; g.OW = d->out_w; g.sy = 1; g.sx = 1; g.Hp = d->h; g.Wp = d->w; g.Cp = cg.Cp; g.KH = 1; g.KW = 1; g.dy = 1; g.dx = 1;
-    // algorithmic bytes: i8 weights + f32 activations (read once) + f32 output (+ f32 residual)
-    return dispatch_fast(ctx, g, 2.0 * d->o * (double)g.N * cg.Kreal,
-                         (double)d->o * cg.Kreal + 4.0 * d->n * d->c * d->h * d->w + 4.0 * d->o * g.N + (g.res ? 4.0 * d->o * g.N : 0.0));
-}

@@ -1,5 +1,5 @@
-// Device pieces of DynamicQuantizeLinear shared by quantize.hip and the fused quantize-and-stage kernel of
-// int8_fast.hip (src/ops/quantize.rs:352-436, rten-vecmath/src/min_max.rs:20-44, quantize.rs:39-79).
+// Device pieces of DynamicQuantizeLinear shared by quantize.hip, the fused quantize-and-stage kernels of int8_stage.hip and
+// the quantizing loader / epilogue of int8_fast.hip (src/ops/quantize.rs:352-436, rten-vecmath/src/min_max.rs:20-44, quantize.rs:39-79).
 #pragma once
 #include "internal.h"
 

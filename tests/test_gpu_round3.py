@@ -39,7 +39,7 @@ def _conv_desc(n, c, h, w, o, k, stride, pad, pad_mode=L.PAD_RAW0_I8, packed=1, 
 
 
 def staged_image(codes_u8, zero_point, pads, pad_mode):
-    """numpy restatement of the staged int8 activation layout the fast kernels read (csrc/int8_fast.hip `ConvGeom`):
+    """numpy restatement of the staged int8 activation layout the fast kernels read (csrc/int8_fast.h `ConvGeom`):
     [N][ceil(C / 16)][H + pad_top + pad_bottom][W + pad_left + pad_right][16 B] of SIGNED bytes (u8 code ^ 0x80); the border holds the padded-tap
     value of the pad mode -- zero point (in the signed domain), raw 0 after the u8 -> i8 shift, or raw u8 0; channels past C are 0
     everywhere (border included).

@@ -318,7 +318,7 @@ def test_co_run_measurement_on_borrowed_contexts():
 
 @pytest.mark.parametrize("pm", [L.PAD_ZERO_POINT, L.PAD_RAW0_I8, L.PAD_RAW0_U8])
 def test_few_channel_packed_int8_convolution_is_bit_exact(ctx, pm):
-    """Convolutions with C <= 4 input channels take the PACKED staging form (int8_fast.hip, conv_geom: a 16-byte chunk = 16 / C kernel columns x C channels of one
+    """Convolutions with C <= 4 input channels take the PACKED staging form (int8_stage.hip, rten_i8_conv_geom: a 16-byte chunk = 16 / C kernel columns x C channels of one
     kernel row, per output column; the stem of ResNet-50 goes from K = 784 to 224): every channel count, kernel widths that fill a chunk exactly / partly / need
     several, strides 1-3, dilation, asymmetric padding on both axes, both signednesses of both operands with no / a scalar / a per-channel weight zero point on the
     plain path (the unused bytes of a chunk are zero on both operands, so every term of the zero-point algebra is exact), and DynamicQuantizeLinear's staged image +
