@@ -420,6 +420,40 @@ int32_t rten_hip_layer_norm_f32(rten_hip_ctx *ctx, int64_t rows, int32_t cols, c
 int32_t rten_hip_add_layer_norm_f32(rten_hip_ctx *ctx, int64_t rows, int32_t cols, const float *x, const float *addend,
                                     const float *gamma, const float *beta, float gamma_scalar, float beta_scalar,
                                     float epsilon, float *y);
+/* ---- RMSNormalization / SimplifiedLayerNormalization: src/ops/norm.rs:419-435,571-608, src/ops/norm/contrib.rs:86-115 ----
+ * ms = SumSquare(row) / cols in the reference's fold order, r = gamma_scalar / sqrt(ms + epsilon); gamma given: y = x * (gamma[i] * r) and gamma_scalar is
+ * taken as 1; gamma NULL (a one-element scale): y = mul_add(x, r, 0), so a -0 product comes out +0 (normalize.rs:112-146).  A row whose squares overflow has
+ * r = 0 as in the reference.  y may alias x up to 8192 columns (a row is read whole before it is stored); not above. */
+int32_t rten_hip_rms_norm_f32(rten_hip_ctx *ctx, int64_t rows, int32_t cols, const float *x, const float *gamma, float gamma_scalar, float epsilon,
+                              float *y);
+/* ---- SkipLayerNormalization / SkipSimplifiedLayerNormalization: src/ops/norm/contrib.rs:22-77,123-238 ----
+ * sum = (x + skip) + bias (two rounded adds; bias [cols] optional), y = the normalisation of sum over the row with gamma [cols] and, mode LAYER only, the
+ * optional beta [cols]; sum_out (optional) receives sum from the same launch.  Row r reads skip row r % skip_rows (skip_rows divides rows: a skip that
+ * broadcasts over the batch).  Bit-identical to Add, Add and the normalisation run one after the other.
+ * Aliasing, up to 8192 columns: y and sum_out may alias x, and may alias skip when skip_rows == rows (the rows of a broadcast skip are read by other
+ * workgroups); y and sum_out must differ from each other.  Above 8192 columns (the two-pass form) no output may alias an input. */
+#define RTEN_HIP_SKIP_NORM_LAYER 0
+#define RTEN_HIP_SKIP_NORM_RMS 1
+int32_t rten_hip_skip_norm_f32(rten_hip_ctx *ctx, int32_t mode, int64_t rows, int32_t cols, const float *x, const float *skip, int64_t skip_rows,
+                               const float *bias, const float *gamma, const float *beta, float epsilon, float *sum_out, float *y);
+/* ---- RotaryEmbedding: src/ops/embedding.rs:144-194 (ai.onnx) and src/ops/embedding/contrib.rs:53-73 (com.microsoft position forms) ----
+ * Rows are (b, s, h); row (b, s, h) of x starts at x + b * x_stride_b + s * x_stride_s + h * x_stride_h (element strides; unit stride along the head), so
+ * [B, S, H * D], [B, H, S, D] and a q or k column block of a fused [B, S, 3 * H * D] projection are all read in place.  y likewise (y == x with equal
+ * strides is allowed: a thread reads what it writes).  The first rotary_dim elements (even, <= head_size; 0 = none) are rotated, in halves
+ * (y[i] = x[i] c[i] - x[half + i] s[i], y[half + i] = x[i] s[i] + x[half + i] c[i]) or, interleaved, in pairs (2i, 2i + 1); the rest is copied.  Every
+ * product and every sum is rounded on its own (no FMA).
+ * position_mode NONE: the cache row of (b, s) is cos + b * cos_stride_b + s * cos_stride_s (a stride of 0 broadcasts), sin likewise.
+ * position_mode IDS: position_ids is int32 [B, S] on the device and the caches are [max_pos, rotary_dim / 2]; OFFSET: position_ids is ONE int32 k on the
+ * device and token s uses position k + s.  The kernel gathers the cache row itself; nothing is read back.  An id outside the cache follows Gather on device
+ * data: a negative id counts from the end, then the id is clamped into [0, max_pos). */
+#define RTEN_HIP_ROTARY_POS_NONE 0
+#define RTEN_HIP_ROTARY_POS_IDS 1
+#define RTEN_HIP_ROTARY_POS_OFFSET 2
+int32_t rten_hip_rotary_embedding_f32(rten_hip_ctx *ctx, int32_t batch, int32_t seq, int32_t heads, int32_t head_size, int32_t rotary_dim,
+                                      int32_t interleaved, const float *x, int64_t x_stride_b, int64_t x_stride_s, int64_t x_stride_h,
+                                      const float *cos, int64_t cos_stride_b, int64_t cos_stride_s, const float *sin, int64_t sin_stride_b,
+                                      int64_t sin_stride_s, const int32_t *position_ids, int32_t position_mode, int32_t max_pos, float *y,
+                                      int64_t y_stride_b, int64_t y_stride_s, int64_t y_stride_h);
 /* BatchNormalization (inference), src/ops/norm.rs:194-224 */
 int32_t rten_hip_batch_norm_f32(rten_hip_ctx *ctx, int32_t n, int32_t c, int64_t inner, const float *x,
                                 const float *scale, const float *bias, const float *mean, const float *var,

@@ -1242,6 +1242,109 @@ class Graph {
         a.p = (int)p;
         return a;
     }
+    // What the loader reads from, and refuses about, the decoder-block nodes (make_decoder_step): RMSNormalization and SimplifiedLayerNormalization in ai.onnx
+    // (onnx_registry.rs:1584-1590,1905-1911: axis defaults to -1, epsilon to the operator's 1e-5, stash_type must be 1), SkipLayerNormalization and
+    // SkipSimplifiedLayerNormalization in com.microsoft (onnx_registry.rs:1918-1933: epsilon is required) and the two RotaryEmbedding operators
+    // (onnx_registry.rs:1815-1847).  The skip forms compute output 0 and output 3 (the sum): the reference fills outputs 1 and 2 (mean, inv_std_var:
+    // training outputs) with scalar zeros, here a node whose output 1 or 2 is READ -- by a node or as a graph output -- is refused; named but unread is fine.
+    // An input whose element type the model states (an initializer or a graph input) must be float32 (position_ids: int32 / int64).  Needs no device;
+    // rten_hip_run --parse-only calls it too.
+    static bool is_decoder_node(const onnx::Node &n) {
+        const bool std_domain = n.domain.empty() || n.domain == "ai.onnx";
+        if (std_domain) return n.op_type == "RMSNormalization" || n.op_type == "SimplifiedLayerNormalization" || n.op_type == "RotaryEmbedding";
+        return n.domain == "com.microsoft" && (n.op_type == "SkipLayerNormalization" || n.op_type == "SkipSimplifiedLayerNormalization" || n.op_type == "RotaryEmbedding");
+    }
+    static bool value_is_read(const onnx::Model &m, const std::string &v) {
+        if (v.empty()) return false;
+        for (auto &o : m.outputs) if (o.name == v) return true;
+        for (auto &nd : m.nodes) for (auto &s : nd.inputs) if (s == v) return true;
+        return false;
+    }
+    // The RMSNormalization / SimplifiedLayerNormalization node that the Add at `add` fuses with (make_add_norm_step; off under --no-fuse): it reads the sum as
+    // its input, normalises the last axis (axis -1), and its scale exists before the Add runs.  -1: none.  From the model alone, so --parse-only can say it.
+    static long add_rms_consumer(const onnx::Model &m, size_t add) {
+        const onnx::Node &a = m.nodes[add];
+        if (a.op_type != "Add" || !(a.domain.empty() || a.domain == "ai.onnx") || a.inputs.size() != 2 || a.outputs.empty()) return -1;
+        const std::string &sum = a.outputs[0];
+        for (size_t u = 0; u < m.nodes.size(); u++) {
+            const onnx::Node &c = m.nodes[u];
+            if (!(c.domain.empty() || c.domain == "ai.onnx") || (c.op_type != "RMSNormalization" && c.op_type != "SimplifiedLayerNormalization")) continue;
+            if (c.inputs.size() != 2 || c.inputs[0] != sum || c.inputs[1] == sum || c.get_int("axis", -1) != -1 || c.get_int("stash_type", 1) != 1) continue;
+            bool ready = true;
+            for (size_t q = add; q < m.nodes.size(); q++) for (auto &o : m.nodes[q].outputs) if (o == c.inputs[1]) ready = false;
+            if (ready) return (long)u;
+        }
+        return -1;
+    }
+    struct DecoderNode {
+        bool contrib = false, rotary = false, skip = false, rms = false; // rms: the root-mean-square statistic (every normalisation here but SkipLayerNormalization)
+        int axis = -1;
+        std::optional<float> epsilon;
+        bool want_sum = false; // a skip form whose output 3 is read
+        bool interleaved = false;
+        int64_t num_heads = 0, rotary_embedding_dim = 0;
+    };
+    static DecoderNode read_decoder_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        DecoderNode a;
+        a.contrib = n.domain == "com.microsoft";
+        a.rotary = n.op_type == "RotaryEmbedding";
+        a.skip = a.contrib && !a.rotary;
+        a.rms = !a.rotary && n.op_type != "SkipLayerNormalization";
+        const std::string where = (a.contrib ? "com.microsoft." : "") + n.op_type + " " + label + ": ";
+        auto stated = [&](const std::string &v) {
+            if (const onnx::TensorProto *t = initializer_named(m, v)) return t->data_type;
+            if (const onnx::ValueInfo *gi = graph_input_named(m, v)) return gi->elem_type;
+            return 0;
+        };
+        auto floats = [&](std::initializer_list<size_t> which) {
+            for (size_t i : which) {
+                if (i >= n.inputs.size() || n.inputs[i].empty()) continue;
+                const int et = stated(n.inputs[i]);
+                if (et != 0 && et != onnx::FLOAT) throw GraphError(where + "input " + std::to_string(i) + " (\"" + n.inputs[i] + "\") has element type " + std::to_string(et) + ": float32 only");
+            }
+        };
+        auto needs = [&](size_t count, const char *what) {
+            for (size_t i = 0; i < count; i++) if (i >= n.inputs.size() || n.inputs[i].empty()) throw GraphError(where + "the " + what + " inputs are required");
+        };
+        if (a.rotary) {
+            a.interleaved = n.get_int("interleaved", 0) != 0;
+            a.num_heads = n.get_int("num_heads", 0);
+            a.rotary_embedding_dim = n.get_int("rotary_embedding_dim", 0);
+            if (a.num_heads < 0 || a.rotary_embedding_dim < 0) throw GraphError(where + "num_heads and rotary_embedding_dim must not be negative");
+            refuse_extra_inputs(n, 4, where);
+            needs(a.contrib ? 4 : 3, a.contrib ? "input, position_ids, cos_cache and sin_cache" : "X, cos_cache and sin_cache");
+            if (a.contrib) floats({0, 2, 3}); else floats({0, 1, 2});
+            const size_t ids = a.contrib ? 1 : 3;
+            if (ids < n.inputs.size() && !n.inputs[ids].empty()) {
+                const int et = stated(n.inputs[ids]);
+                if (et != 0 && et != onnx::INT32 && et != onnx::INT64) throw GraphError(where + "position_ids (\"" + n.inputs[ids] + "\") has element type " + std::to_string(et) + ": int32 / int64 only");
+            }
+            return a;
+        }
+        if (a.skip) {
+            const onnx::Attr *eps = n.attr("epsilon");
+            if (!eps) throw GraphError(where + "the epsilon attribute is missing");
+            a.epsilon = eps->f;
+            refuse_extra_inputs(n, a.rms ? 4 : 5, where);
+            needs(3, "input, skip and gamma");
+            floats({0, 1, 2, 3, 4});
+            static const char *slot[] = {"", "mean", "inv_std_var"};
+            for (size_t k = 1; k <= 2; k++)
+                if (k < n.outputs.size() && value_is_read(m, n.outputs[k]))
+                    throw GraphError(where + "output " + std::to_string(k) + " (" + slot[k] + ", \"" + n.outputs[k] + "\") is read, but only output 0 and output 3 (the sum) are computed");
+            if (n.outputs.size() > 4) throw GraphError(where + "has at most 4 outputs (it names " + std::to_string(n.outputs.size()) + ")");
+            a.want_sum = n.outputs.size() > 3 && value_is_read(m, n.outputs[3]);
+            return a;
+        }
+        a.axis = (int)n.get_int("axis", -1);
+        if (const onnx::Attr *eps = n.attr("epsilon")) a.epsilon = eps->f;
+        const int64_t stash = n.get_int("stash_type", 1);
+        if (stash != 1) throw GraphError(where + "stash_type = " + std::to_string(stash) + " is not supported (the statistic is computed in float32: stash_type must be 1)");
+        refuse_extra_inputs(n, 2, where);
+        needs(2, "X and scale");
+        floats({0, 1});
+        return a;
+    }
     // What the loader refuses about a Reduce* node of reduce_family_kind: axes that are neither an attribute nor a constant input are found when the plan
     // is built (read_reduce_attrs); here, without a device, an axes input that is a graph input (device data at run time).
     static void check_reduce_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
@@ -1536,6 +1639,7 @@ class Graph {
         bool batch_coupled = false; // the result for one dim-0 row depends on other rows (no sub-batch chains for such a graph)
         bool reads_back = false;    // the step reads a count back from the device to shape its output (NonMaxSuppression): it synchronises and cannot be captured
         size_t pos = 0; // index of the LAST graph node folded into this step: the step runs where that node stood
+        int extra_out = -1; // a value the step produces besides its node's outputs, appended to `out` (the sum of a fused Add -> RMSNormalization that has other readers)
     };
 
     Context &ctx_;
@@ -2824,7 +2928,7 @@ class Graph {
             if (nodes.dead[i]) continue;
             const onnx::Node &n = m.nodes[i];
             // contrib operators this backend carries live in com.microsoft (onnx_registry.rs registers them under that domain)
-            const bool contrib = n.domain == "com.microsoft" && n.op_type == "MatMulNBits";
+            const bool contrib = n.domain == "com.microsoft" && (n.op_type == "MatMulNBits" || is_decoder_node(n));
             if (!n.domain.empty() && n.domain != "ai.onnx" && !contrib) throw GraphError("node " + n.name + ": operator domain " + n.domain + " is not supported");
             Step st;
             st.name = label_of(n);
@@ -2861,6 +2965,7 @@ class Graph {
                 st.run = [op, plan](Context &c, const InputList &in) { PlanScope scope(c, *plan); return op->run(c, in); };
             } else if (kind == "MatMul") make_matmul_step(st, n, nodes, out_name);
             else if (kind == "Add" && opt_.fuse && make_add_norm_step(st, n, nodes, out_name)) {} // (any other Add takes the generic path below)
+            else if (is_decoder_node(n)) make_decoder_step(st, n, m); // (RotaryEmbedding dispatches on its domain, the skip forms exist in com.microsoft only)
             else if (kind == "LayerNormalization") {
                 auto op = std::make_shared<LayerNormalization>();
                 op->axis = (int)n.get_int("axis", -1);
@@ -2921,6 +3026,7 @@ class Graph {
             }
             st.out.push_back(id_of(out_name));
             for (size_t k = 1; k < n.outputs.size(); k++) st.out.push_back(n.outputs[k].empty() ? -1 : id_of(n.outputs[k]));
+            if (st.extra_out >= 0) st.out.push_back(st.extra_out);
             steps_.push_back(std::move(st));
         }
         for (auto &o : m.outputs)
@@ -3137,6 +3243,29 @@ class Graph {
             };
             return true;
         }
+        // Add(residual) -> RMSNormalization / SimplifiedLayerNormalization(last axis) as one skip launch.  The sum usually has other readers (it is the
+        // residual stream), so the step runs where the Add stood and produces both values; the scale must exist by then.
+        {
+            const size_t at = st.pos;
+            const std::string sum = out_name;
+            auto us = nodes.users.find(sum);
+            long rn = add_rms_consumer(nodes.m, at);
+            if (rn >= 0 && nodes.dead[(size_t)rn]) rn = -1;
+            if (rn >= 0) {
+                const onnx::Node &c = nodes[rn];
+                auto op = std::make_shared<AddRMSNormalization>();
+                op->epsilon = c.get_float("epsilon", 1e-5f);
+                op->want_sum = nodes.graph_outs.count(sum) != 0 || us->second.size() > 1;
+                nodes.dead[(size_t)rn] = true; // (not absorb(): the step keeps the Add's position, the other readers of the sum come before the normalisation node)
+                fused_away_++;
+                out_name = c.outputs.at(0);
+                st.in.push_back(id_of(c.inputs[1]));
+                if (op->want_sum) st.extra_out = id_of(sum);
+                st.kind_name = "Add+" + c.op_type;
+                run_plainly(st, op);
+                return true;
+            }
+        }
         const long sm = nodes.sole_user(out_name, "Softmax");
         if (sm >= 0 && nodes[sm].get_int("axis", -1) == -1) {
             // Add -> Softmax(last axis) = AddSoftmax (src/ops/attention.rs:94-156)
@@ -3159,6 +3288,43 @@ class Graph {
             return true;
         }
         return false;
+    }
+    // RMSNormalization / SimplifiedLayerNormalization, the skip forms and the two RotaryEmbedding operators: the read_decoder_node checks at load, one
+    // launch per step, nothing read back (a position offset on the device is read by the kernel), so every one of them captures.  Rows of the batch are
+    // independent unless a normalisation's axis resolves to dim 0; a skip form with a [1, S, H] or [S, H] skip reads the same skip rows for every batch row.
+    void make_decoder_step(Step &st, const onnx::Node &n, const onnx::Model &m) {
+        const DecoderNode a = read_decoder_node(m, n, st.name);
+        const std::string nm = st.name;
+        if (a.rotary) {
+            if (a.contrib) {
+                auto op = std::make_shared<RotaryEmbeddingMicrosoft>();
+                op->interleaved = a.interleaved; op->num_heads = a.num_heads; op->rotary_embedding_dim = a.rotary_embedding_dim;
+                st.kind_name = "com.microsoft.RotaryEmbedding";
+                run_plainly(st, op);
+            } else {
+                auto op = std::make_shared<RotaryEmbedding>();
+                op->interleaved = a.interleaved; op->num_heads = a.num_heads; op->rotary_embedding_dim = a.rotary_embedding_dim;
+                run_plainly(st, op);
+            }
+        } else if (a.skip) {
+            std::shared_ptr<SkipNormBase> op;
+            if (a.rms) op = std::make_shared<SkipSimplifiedLayerNormalization>(); else op = std::make_shared<SkipLayerNormalization>();
+            op->epsilon = *a.epsilon;
+            op->want_sum = a.want_sum;
+            st.run = [op](Context &c, const InputList &in) {
+                OutputList o = op->run(c, in);
+                while (o.size() < 4) o.emplace_back(); // outputs the graph names but nothing reads
+                return o;
+            };
+        } else {
+            std::shared_ptr<RMSNormalization> op;
+            if (n.op_type == "RMSNormalization") op = std::make_shared<RMSNormalization>(); else op = std::make_shared<SimplifiedLayerNormalization>();
+            op->axis = a.axis;
+            op->epsilon = a.epsilon;
+            st.batch_coupled = a.axis == 0;
+            const std::string kind = n.op_type;
+            st.run = [this, op, kind, nm](Context &c, const InputList &in) { note_axis(kind, nm, op->axis, require(in, 0)); return op->run(c, in); };
+        }
     }
     void make_activation_step(Step &st, const onnx::Node &n) {
         Activation act;

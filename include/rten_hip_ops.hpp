@@ -3405,6 +3405,260 @@ struct LSTM : Operator {
     }
 };
 
+// ------------------------------------------------------------------------------------------------ decoder blocks: RMS / skip normalisation, rotary embedding
+namespace decoder_detail {
+// `scale.item()` of layer_normalization_impl (src/ops/norm.rs:470): the value of a tensor of exactly one element, whatever its rank.  A constant carries a
+// host copy (nothing is read back); a one-element scale that only the device knows is read back, which synchronises.
+inline bool one_element(const Tensor &t, float &v) {
+    if (t.len() != 1) return false;
+    if (t.host() && t.host()->is_float && t.host()->f.size() == 1) v = t.host()->f[0];
+    else v = t.to_host<float>()[0];
+    return true;
+}
+// try_broadcast(shape -> target) of rten-tensor: right-aligned, every dim equal or 1, rank not above the target's
+inline bool broadcastable(const std::vector<int64_t> &shape, const std::vector<int64_t> &target) {
+    if (shape.size() > target.size()) return false;
+    for (size_t i = 0; i < shape.size(); i++) {
+        const int64_t s = shape[shape.size() - 1 - i], t = target[target.size() - 1 - i];
+        if (s != t && s != 1) return false;
+    }
+    return true;
+}
+// rotary_cache_dims (src/ops/embedding.rs:20-44): a cos / sin cache is [1 | batch, 1 | seq_len, rotary_embedding_dim / 2]
+inline std::pair<int64_t, int64_t> rotary_cache_dims(const std::vector<int64_t> &cache, int64_t batch, int64_t seq_len, int64_t half, const char *bad_last_dim) {
+    if (cache.size() != 3) throw OpError(OpError::InvalidValue, "cos/sin cache must be a 3D tensor");
+    if (cache[2] != half) throw OpError(OpError::InvalidValue, bad_last_dim);
+    if (cache[1] != 1 && cache[1] != seq_len) throw OpError(OpError::InvalidValue, "cos/sin cache sequence length must be 1 or match the input");
+    if (cache[0] != 1 && cache[0] != batch) throw OpError(OpError::InvalidValue, "cos/sin cache batch size must be 1 or match the input");
+    return {cache[0], cache[1]};
+}
+// rotary_embedding (src/ops/embedding.rs:46-207) on rten_hip_rotary_embedding_f32.  `ids`: int32 [batch, seq] positions or, with `offset`, the contrib
+// operator's one-element offset k (token i uses position k + i).  The kernel gathers the cache rows and reads the offset itself: nothing is read back, no
+// intermediate [B, S, half] tensor exists.  Ids the host knows are checked here and refused with Gather's message; ids only the device knows are clamped.
+inline Tensor rotary_embedding(Context &ctx, const Tensor &x_in, const Tensor &cos_in, const Tensor &sin_in, const Tensor *ids, bool offset, bool interleaved,
+                               int64_t num_heads, int64_t rotary_embedding_dim) {
+    const Tensor &x = want(x_in, DType::F32, "float32");
+    const Tensor &cos = want(cos_in, DType::F32, "float32"), &sin = want(sin_in, DType::F32, "float32");
+    int64_t batch, seq, heads, head_size, st[3];
+    if (x.ndim() == 3) {
+        if (num_heads == 0) throw OpError(OpError::InvalidValue, "num_heads must not be 0 for 3 dimensioned input");
+        if (x.size(2) % num_heads != 0) throw OpError(OpError::InvalidValue, "hidden_size must be divisible by num_heads");
+        batch = x.size(0); seq = x.size(1); heads = num_heads; head_size = x.size(2) / num_heads;
+        st[0] = seq * x.size(2); st[1] = x.size(2); st[2] = head_size;
+    } else if (x.ndim() == 4) {
+        batch = x.size(0); heads = x.size(1); seq = x.size(2); head_size = x.size(3);
+        st[0] = heads * seq * head_size; st[1] = head_size; st[2] = seq * head_size;
+    } else throw OpError(OpError::IncompatibleInputShapes, "Input processed needs 3-4 dimensions");
+    const int64_t rot = rotary_embedding_dim == 0 ? head_size : rotary_embedding_dim;
+    if (rot == 0 || rot % 2 != 0) throw OpError(OpError::InvalidValue, "rotary_embedding_dim must be a positive even number");
+    if (rot > head_size) throw OpError(OpError::InvalidValue, "rotary_embedding_dim must not exceed head size");
+    const int64_t half = rot / 2;
+    const char *bad_cos = "Last dimension of cos cache does not match rotary_embedding_dim/2", *bad_sin = "Last dimension of sin cache does not match rotary_embedding_dim/2";
+    int32_t mode = RTEN_HIP_ROTARY_POS_NONE;
+    int64_t max_pos = 0, cst[2] = {0, 0}, sst[2] = {0, 0};
+    if (ids) {
+        want(*ids, DType::I32, "int32");
+        // gather(cache, 0, ids) has the shape ids.shape + cache.shape[1..]
+        const std::vector<int64_t> id_shape = offset ? std::vector<int64_t>{batch, seq} : ids->shape();
+        for (const Tensor *cache : {&cos, &sin}) {
+            if (cache->ndim() == 0) throw OpError(OpError::InvalidValue, "Cannot gather from a scalar");
+            std::vector<int64_t> g = id_shape;
+            g.insert(g.end(), cache->shape().begin() + 1, cache->shape().end());
+            rotary_cache_dims(g, batch, seq, half, cache == &cos ? bad_cos : bad_sin);
+        }
+        if (cos.size(0) != sin.size(0)) throw OpError(OpError::UnsupportedValue, "device path needs cos and sin caches of one length");
+        if (!offset && (ids->size(0) != batch || ids->size(1) != seq)) throw OpError(OpError::UnsupportedValue, "device path needs position_ids of the input's [batch, seq] shape");
+        max_pos = cos.size(0);
+        if (const HostVal *h = ids->host()) {
+            if (!h->is_float)
+                for (size_t i = 0; i < h->i.size(); i++) {
+                    const int64_t lo = h->i[i], hi = offset ? lo + seq - 1 : lo;
+                    if (lo < -max_pos || hi >= max_pos) throw OpError(OpError::InvalidValue, "Entry in `indices` is out of range");
+                }
+        }
+        mode = offset ? RTEN_HIP_ROTARY_POS_OFFSET : RTEN_HIP_ROTARY_POS_IDS;
+    } else {
+        const auto c = rotary_cache_dims(cos.shape(), batch, seq, half, bad_cos), s = rotary_cache_dims(sin.shape(), batch, seq, half, bad_sin);
+        cst[0] = c.first == 1 ? 0 : c.second * half; cst[1] = c.second == 1 ? 0 : half;
+        sst[0] = s.first == 1 ? 0 : s.second * half; sst[1] = s.second == 1 ? 0 : half;
+    }
+    Tensor y(ctx, x.shape(), DType::F32);
+    if (x.len())
+        ctx.check(rten_hip_rotary_embedding_f32(ctx.raw(), (int32_t)batch, (int32_t)seq, (int32_t)heads, (int32_t)head_size, (int32_t)rot, interleaved ? 1 : 0,
+                                                (const float *)x.ptr(), st[0], st[1], st[2], (const float *)cos.ptr(), cst[0], cst[1], (const float *)sin.ptr(), sst[0], sst[1],
+                                                (const int32_t *)vp(ids), mode, (int32_t)max_pos, (float *)y.ptr(), st[0], st[1], st[2]));
+    return y;
+}
+} // namespace decoder_detail
+
+// RMSNormalization (src/ops/norm.rs:419-435,571-608; loader defaults onnx_registry.rs:1584-1590: axis -1, epsilon absent = 1e-5, stash_type must be 1).
+// inputs X, scale: shape[axis..] is normalised by its root mean square; a one-element scale is the reference's scalar form.
+struct RMSNormalization : Operator {
+    int axis = -1;
+    std::optional<float> epsilon;
+    const char *name() const override { return "RMSNormalization"; }
+    int max_inputs() const override { return 2; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = want(require(in, 0), DType::F32, "float32");
+        const Tensor &scale = want(require(in, 1), DType::F32, "float32");
+        const int a = resolve_axis(axis, x.ndim());
+        const std::vector<int64_t> norm_shape(x.shape().begin() + a, x.shape().end());
+        const int64_t cols = detail::prod(x.shape(), (size_t)a, x.shape().size()), rows = cols ? x.len() / cols : 0;
+        float gs = 1.f;
+        const bool one = decoder_detail::one_element(scale, gs);
+        if (!one) {
+            if (!decoder_detail::broadcastable(scale.shape(), norm_shape)) throw OpError(OpError::InvalidValue, "`scale` is not broadcastable to normalized axes of input");
+            if (scale.len() != cols) throw OpError(OpError::UnsupportedValue, "device path needs scale already expanded to the normalized shape");
+        }
+        Tensor y(ctx, x.shape(), DType::F32);
+        if (x.len())
+            ctx.check(rten_hip_rms_norm_f32(ctx.raw(), rows, (int32_t)cols, (const float *)x.ptr(), one ? nullptr : (const float *)scale.ptr(), gs, epsilon.value_or(1e-5f),
+                                            (float *)y.ptr()));
+        OutputList out;
+        out.push_back(std::move(y));
+        return out;
+    }
+};
+// SimplifiedLayerNormalization (src/ops/norm/contrib.rs:86-115): the contrib spelling, registered in ai.onnx (onnx_registry.rs:275,1905)
+struct SimplifiedLayerNormalization : RMSNormalization {
+    const char *name() const override { return "SimplifiedLayerNormalization"; }
+};
+
+// skip_layer_normalization (src/ops/norm/contrib.rs:22-77) on rten_hip_skip_norm_f32: sum = (input + skip) + bias, normalised over the last axis; `want_sum`
+// also returns the sum (output 3, the residual stream), written by the same launch.  Outputs: [output] or [output, {}, {}, sum] -- the mean and
+// inv_std_var slots (training outputs the reference fills with zeros) stay empty, the loader refuses a graph that reads them.
+struct SkipNormBase : Operator {
+    float epsilon = 1e-5f;
+    bool want_sum = false;
+    OutputList run_skip(Context &ctx, bool rms, const Tensor &x_in, const Tensor &skip_in, const Tensor &gamma, const Tensor *beta, const Tensor *bias) const {
+        const Tensor &x = want(x_in, DType::F32, "float32"), &skip = want(skip_in, DType::F32, "float32");
+        for (const Tensor *t : {&gamma, beta, bias}) {
+            if (!t) continue;
+            want(*t, DType::F32, "float32");
+            if (t->ndim() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 1 dims");
+        }
+        if (x.ndim() != 2 && x.ndim() != 3) throw OpError(OpError::InvalidValue, "input must be 2 or 3 dimensioned");
+        if (skip.ndim() != 2 && skip.ndim() != 3) throw OpError(OpError::InvalidValue, "skip must be 2 or 3 dimensioned");
+        const bool tail = skip.size(skip.ndim() - 1) == x.size(x.ndim() - 1) && skip.size(skip.ndim() - 2) == x.size(x.ndim() - 2);
+        if (!tail || skip.ndim() > x.ndim() || (skip.ndim() == 3 && skip.size(0) != 1 && skip.size(0) != x.size(0)))
+            throw OpError(OpError::IncompatibleInputShapes, "skip must broadcast to input over the batch dimension");
+        const int64_t cols = x.size(x.ndim() - 1), rows = cols ? x.len() / cols : 0;
+        if (bias && bias->len() != 1 && bias->len() != cols) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs");
+        float gs = 1.f, bs = 0.f;
+        const bool one = decoder_detail::one_element(gamma, gs);
+        if (!one && gamma.len() != cols) throw OpError(OpError::InvalidValue, "`scale` is not broadcastable to normalized axes of input");
+        if (beta && beta->len() != 1 && beta->len() != cols) throw OpError(OpError::InvalidValue, "`bias` is not broadcastable to normalized axes of input");
+        const bool beta_one = beta && decoder_detail::one_element(*beta, bs);
+        OutputList out;
+        out.emplace_back(ctx, x.shape(), DType::F32);
+        if (want_sum) { out.emplace_back(); out.emplace_back(); }
+        if (one || beta_one || (bias && bias->len() != cols)) {
+            // a one-element gamma / beta is the reference's scalar form (other bits than a vector of equal values), a one-element bias a broadcast: the
+            // operators one after the other, on the entry points that take a scalar
+            OutputList sum = Add().run(ctx, {&x, &skip});
+            if (bias) sum = Add().run(ctx, {&sum[0], bias});
+            if (x.len()) {
+                if (rms) ctx.check(rten_hip_rms_norm_f32(ctx.raw(), rows, (int32_t)cols, (const float *)sum[0].ptr(), one ? nullptr : (const float *)gamma.ptr(), gs, epsilon, (float *)out[0].ptr()));
+                else ctx.check(rten_hip_layer_norm_f32(ctx.raw(), rows, (int32_t)cols, (const float *)sum[0].ptr(), one ? nullptr : (const float *)gamma.ptr(),
+                                                       beta && !beta_one ? (const float *)beta->ptr() : nullptr, gs, bs, epsilon, (float *)out[0].ptr()));
+            }
+            if (want_sum) out.push_back(std::move(sum[0]));
+            return out;
+        }
+        if (want_sum) out.emplace_back(ctx, x.shape(), DType::F32);
+        if (x.len())
+            ctx.check(rten_hip_skip_norm_f32(ctx.raw(), rms ? RTEN_HIP_SKIP_NORM_RMS : RTEN_HIP_SKIP_NORM_LAYER, rows, (int32_t)cols, (const float *)x.ptr(), (const float *)skip.ptr(),
+                                             skip.len() / cols, (const float *)vp(bias), (const float *)gamma.ptr(), (const float *)vp(beta), epsilon,
+                                             want_sum ? (float *)out[3].ptr() : nullptr, (float *)out[0].ptr()));
+        return out;
+    }
+};
+// SkipLayerNormalization (com.microsoft, src/ops/norm/contrib.rs:123-177): inputs input, skip, gamma, beta?, bias?; epsilon is a required attribute
+struct SkipLayerNormalization : SkipNormBase {
+    const char *name() const override { return "SkipLayerNormalization"; }
+    int max_inputs() const override { return 5; }
+    OutputList run(Context &ctx, const InputList &in) const override { return run_skip(ctx, false, require(in, 0), require(in, 1), require(in, 2), get(in, 3), get(in, 4)); }
+};
+// SkipSimplifiedLayerNormalization (com.microsoft, src/ops/norm/contrib.rs:186-238): the RMS form; inputs input, skip, gamma, bias?
+struct SkipSimplifiedLayerNormalization : SkipNormBase {
+    const char *name() const override { return "SkipSimplifiedLayerNormalisation"; } // (sic, contrib.rs:192)
+    int max_inputs() const override { return 4; }
+    OutputList run(Context &ctx, const InputList &in) const override { return run_skip(ctx, true, require(in, 0), require(in, 1), require(in, 2), nullptr, get(in, 3)); }
+};
+
+// Add(residual) -> RMSNormalization / SimplifiedLayerNormalization over the last axis as one skip launch (the executor's fusion): the sum is x + r, the
+// one f32 add the Add node makes, so the result has the bits of the two operators.  `want_sum`: the sum has other readers (the residual stream) and is
+// written by the same launch as a second output.  A one-element scale, or operands of different shapes, run the two operators one after the other.
+struct AddRMSNormalization : Operator {
+    float epsilon = 1e-5f;
+    bool want_sum = false;
+    const char *name() const override { return "AddRMSNormalization"; }
+    int max_inputs() const override { return 3; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0), &r = require(in, 1), &scale = require(in, 2);
+        const int64_t cols = x.ndim() ? x.size(x.ndim() - 1) : 1, rows = cols ? x.len() / cols : 0;
+        OutputList out;
+        if (x.dtype() != DType::F32 || r.dtype() != DType::F32 || scale.dtype() != DType::F32 || x.shape() != r.shape() || x.ndim() == 0 || scale.len() != cols || cols == 1) {
+            OutputList sum = Add().run(ctx, {&x, &r});
+            RMSNormalization norm;
+            norm.epsilon = epsilon;
+            out = norm.run(ctx, {&sum[0], &scale});
+            if (want_sum) out.push_back(std::move(sum[0]));
+            return out;
+        }
+        out.emplace_back(ctx, x.shape(), DType::F32);
+        if (want_sum) out.emplace_back(ctx, x.shape(), DType::F32);
+        if (x.len())
+            ctx.check(rten_hip_skip_norm_f32(ctx.raw(), RTEN_HIP_SKIP_NORM_RMS, rows, (int32_t)cols, (const float *)x.ptr(), (const float *)r.ptr(), rows, nullptr,
+                                             (const float *)scale.ptr(), nullptr, epsilon, want_sum ? (float *)out[1].ptr() : nullptr, (float *)out[0].ptr()));
+        return out;
+    }
+};
+
+// RotaryEmbedding (ai.onnx, src/ops/embedding.rs:209-252; loader defaults onnx_registry.rs:1832-1847): inputs X [B, S, H * D] (needs num_heads) or
+// [B, H, S, D], cos, sin, position_ids [B, S]?
+struct RotaryEmbedding : Operator {
+    bool interleaved = false;
+    int64_t num_heads = 0, rotary_embedding_dim = 0;
+    const char *name() const override { return "RotaryEmbedding"; }
+    int max_inputs() const override { return 4; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor *ids = get(in, 3);
+        if (ids && ids->ndim() != 2) throw OpError(OpError::InputCastFailed, "expected tensor with 2 dims");
+        OutputList out;
+        out.push_back(decoder_detail::rotary_embedding(ctx, require(in, 0), require(in, 1), require(in, 2), ids, false, interleaved, num_heads, rotary_embedding_dim));
+        return out;
+    }
+};
+// com.microsoft RotaryEmbedding (src/ops/embedding/contrib.rs:17-135): inputs X, position_ids, cos [max_pos, half], sin.  position_ids is [B, S], or a
+// scalar / one-element vector holding an offset; num_heads 0 (the attribute's default, or absent) is inferred from the cache for a 3-D input.
+struct RotaryEmbeddingMicrosoft : Operator {
+    bool interleaved = false;
+    int64_t num_heads = 0, rotary_embedding_dim = 0;
+    const char *name() const override { return "com.microsoft.RotaryEmbedding"; }
+    int max_inputs() const override { return 4; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &x = require(in, 0), &ids = require(in, 1), &cos = require(in, 2), &sin = require(in, 3);
+        if (x.ndim() != 3 && x.ndim() != 4) throw OpError(OpError::IncompatibleInputShapes, "Input processed needs 3-4 dimensions");
+        bool offset;
+        if (ids.ndim() <= 1 && ids.len() == 1) offset = true;
+        else if (ids.ndim() == 2) offset = false;
+        else throw OpError(OpError::InvalidValue, "position_ids must be a scalar, a 1-element vector or have 2 dims");
+        int64_t heads = num_heads;
+        if (x.ndim() == 3 && heads == 0) {
+            if (rotary_embedding_dim != 0) throw OpError(OpError::InvalidValue, "num_heads must be specified when rotary_embedding_dim is set");
+            if (cos.ndim() == 0) throw OpError(OpError::InvalidValue, "cos cache must not be scalar");
+            const int64_t half = cos.size(cos.ndim() - 1);
+            if (half == 0) throw OpError(OpError::InvalidValue, "Last dimension of cos cache must not be 0");
+            if (x.size(2) % (2 * half) != 0) throw OpError(OpError::InvalidValue, "hidden_size must be divisible by head size");
+            heads = x.size(2) / (2 * half);
+        }
+        OutputList out;
+        out.push_back(decoder_detail::rotary_embedding(ctx, x, cos, sin, &ids, offset, interleaved, heads, rotary_embedding_dim));
+        return out;
+    }
+};
+
 // ------------------------------------------------------------------------------------------------ registry (src/op_registry.rs:25-72)
 class OpRegistry {
   public:
@@ -3512,6 +3766,13 @@ class OpRegistry {
         r.register_op<GatherElements>("GatherElements");
         r.register_op<Trilu>("Trilu");
         r.register_op<Tile>("Tile");
+        r.register_op<RMSNormalization>("RMSNormalization");
+        r.register_op<SimplifiedLayerNormalization>("SimplifiedLayerNormalization"); // ai.onnx (sic, onnx_registry.rs:275)
+        r.register_op<RotaryEmbedding>("RotaryEmbedding");
+        // the contrib operators (onnx_registry.rs:285-296) under their domain: the loader dispatches on it, as the reference's OpId does
+        r.register_op<SkipLayerNormalization>("com.microsoft.SkipLayerNormalization");
+        r.register_op<SkipSimplifiedLayerNormalization>("com.microsoft.SkipSimplifiedLayerNormalization");
+        r.register_op<RotaryEmbeddingMicrosoft>("com.microsoft.RotaryEmbedding");
         return r;
     }
 

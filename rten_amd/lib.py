@@ -187,6 +187,10 @@ PROTOTYPES = {
     "rten_hip_softmax_f32": (_I32, [_VP, _I64, _I32, _VP, _VP, _I64, _I64, _I32, _VP]),
     "rten_hip_layer_norm_f32": (_I32, [_VP, _I64, _I32, _VP, _VP, _VP, _F32, _F32, _F32, _VP]),
     "rten_hip_add_layer_norm_f32": (_I32, [_VP, _I64, _I32, _VP, _VP, _VP, _VP, _F32, _F32, _F32, _VP]),
+    "rten_hip_rms_norm_f32": (_I32, [_VP, _I64, _I32, _VP, _VP, _F32, _F32, _VP]),
+    "rten_hip_skip_norm_f32": (_I32, [_VP, _I32, _I64, _I32, _VP, _VP, _I64, _VP, _VP, _VP, _F32, _VP, _VP]),
+    "rten_hip_rotary_embedding_f32": (_I32, [_VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I64, _I64, _I64, _VP, _I64, _I64, _VP, _I64, _I64, _VP, _I32, _I32,
+                                            _VP, _I64, _I64, _I64]),
     "rten_hip_batch_norm_f32": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _F32, _VP]),
     "rten_hip_batch_norm_f32_act": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _F32, _I32, _F32, _F32, _VP]),
     "rten_hip_instance_norm_f32": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _F32, _I32, _F32, _F32, _VP]),

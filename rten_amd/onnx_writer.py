@@ -814,3 +814,142 @@ def dft_graph(opset: int = 17, n: int = 12, dft_length: int | None = None, batch
              node("DFT", inv_in, ["y"], name="inverse", inverse=1, **attrs)]
     outs = [value_info("y", FLOAT, [batch, n_fft, 2]), value_info("spectrum", FLOAT, [batch, n_fft, 2])]
     return model(nodes, [value_info("x", FLOAT, [batch, n, 1])], outs, inits, opset=opset, name="dft_round_trip"), w
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Decoder blocks: RMS / skip normalisation and rotary embedding, one graph per operator form, and a genai-builder-style block
+# ----------------------------------------------------------------------------------------------------------------
+MS = "com.microsoft"
+NORM_ROTARY_FORMS = ("rms", "rms_two_axes", "rms_one_element_scale", "simplified", "skip_layer", "skip_layer_plain", "skip_simplified", "skip_simplified_batch_skip",
+                     "add_rms", "add_simplified_sole", "rotary", "rotary_ids_4d", "rotary_interleaved_partial", "ms_rotary_offset", "ms_rotary_ids")
+NORM_ROTARY_BAD = ("stash_type_0", "skip_mean_read", "skip_inv_std_var_output", "skip_no_epsilon", "rms_int_scale", "rotary_int_cache", "ms_rotary_no_ids")
+
+
+def rotary_caches(max_pos: int, half: int, base: float = 10000.0):
+    """cos / sin caches [max_pos, half] of the usual rotary frequencies, float32."""
+    inv = base ** (-np.arange(half, dtype=np.float64) / half)
+    ang = np.arange(max_pos, dtype=np.float64)[:, None] * inv[None, :]
+    return np.cos(ang).astype(np.float32), np.sin(ang).astype(np.float32)
+
+
+def norm_rotary_graph(form: str, batch="batch", seq: int = 3, heads: int = 2, head_size: int = 8, max_pos: int = 16, seed: int = 51):
+    """One operator form per graph (NORM_ROTARY_FORMS; NORM_ROTARY_BAD are the forms the loader refuses by node name).  The hidden size is heads * head_size.
+    Inputs: `x` [batch, seq, hidden] ([batch, heads, seq, head_size] for rotary_ids_4d), `skip` for the skip and Add forms ([1, seq, hidden] for
+    skip_simplified_batch_skip), `position_ids` int64 [batch, seq] or `offset` int64 [1] for the position forms.  Outputs: `y`, and `sum` where the form
+    exposes the sum.  -> (model bytes, weights)."""
+    assert form in NORM_ROTARY_FORMS + NORM_ROTARY_BAD, form
+    rng = np.random.default_rng(seed)
+    hidden, half = heads * head_size, head_size // 2
+    f = lambda *s: rng.standard_normal(s).astype(np.float32)
+    w = {"gamma": f(hidden), "beta": f(hidden), "bias": f(hidden), "gamma2": f(seq, hidden), "one": np.asarray([0.75], np.float32)}
+    w["cos"], w["sin"] = rotary_caches(max_pos, half)
+    w["cos_part"], w["sin_part"] = rotary_caches(max_pos, (head_size - 2) // 2)
+    x_info = value_info("x", FLOAT, [batch, seq, hidden])
+    skip_info = value_info("skip", FLOAT, [batch, seq, hidden])
+    ins, outs, used = [x_info], [value_info("y", FLOAT, [batch, seq, hidden])], []
+    sum_info = value_info("sum", FLOAT, [batch, seq, hidden])
+    if form in ("rms", "simplified", "stash_type_0", "rms_int_scale"):
+        attrs = {"stash_type": 0} if form == "stash_type_0" else {}
+        if form == "rms_int_scale":
+            w["gamma"] = np.arange(hidden, dtype=np.int32)
+        nodes = [node("SimplifiedLayerNormalization" if form == "simplified" else "RMSNormalization", ["x", "gamma"], ["y"], name="norm", axis=-1, epsilon=1e-6, **attrs)]
+        used = ["gamma"]
+    elif form == "rms_two_axes":
+        nodes, used = [node("RMSNormalization", ["x", "gamma2"], ["y"], name="norm", axis=-2)], ["gamma2"]
+    elif form == "rms_one_element_scale":
+        nodes, used = [node("RMSNormalization", ["x", "one"], ["y"], name="norm")], ["one"]
+    elif form in ("skip_layer", "skip_layer_plain", "skip_mean_read", "skip_inv_std_var_output", "skip_no_epsilon"):
+        attrs = {} if form == "skip_no_epsilon" else {"epsilon": 1e-5}
+        if form == "skip_layer_plain":
+            nodes, used = [node("SkipLayerNormalization", ["x", "skip", "gamma"], ["y"], name="skip_norm", domain=MS, **attrs)], ["gamma"]
+        else:
+            nodes = [node("SkipLayerNormalization", ["x", "skip", "gamma", "beta", "bias"], ["y", "mean", "inv_std_var", "sum"], name="skip_norm", domain=MS, **attrs)]
+            used, outs = ["gamma", "beta", "bias"], outs + [sum_info]
+        if form == "skip_mean_read":
+            nodes.append(node("Identity", ["mean"], ["mean_copy"], name="reads_mean"))
+        if form == "skip_inv_std_var_output":
+            outs.append(value_info("inv_std_var", FLOAT, []))
+        ins.append(skip_info)
+    elif form in ("skip_simplified", "skip_simplified_batch_skip"):
+        nodes = [node("SkipSimplifiedLayerNormalization", ["x", "skip", "gamma", "bias"], ["y", "", "", "sum"], name="skip_norm", domain=MS, epsilon=1e-6)]
+        used, outs = ["gamma", "bias"], outs + [sum_info]
+        ins.append(value_info("skip", FLOAT, [1, seq, hidden]) if form == "skip_simplified_batch_skip" else skip_info)
+    elif form == "add_rms":  # the residual stream: the sum is read by the normalisation and is a graph output
+        nodes = [node("Add", ["x", "skip"], ["sum"], name="residual"), node("RMSNormalization", ["sum", "gamma"], ["y"], name="norm", epsilon=1e-6)]
+        used, outs = ["gamma"], outs + [sum_info]
+        ins.append(skip_info)
+    elif form == "add_simplified_sole":  # the sum has no other reader
+        nodes = [node("Add", ["x", "skip"], ["sum"], name="residual"), node("SimplifiedLayerNormalization", ["sum", "gamma"], ["y"], name="norm")]
+        used = ["gamma"]
+        ins.append(skip_info)
+    elif form in ("rotary", "rotary_int_cache"):
+        w["cos3"], w["sin3"] = w["cos"][None, :seq], w["sin"][None, :seq]
+        if form == "rotary_int_cache":
+            w["cos3"] = np.zeros((1, seq, half), np.int32)
+        nodes, used = [node("RotaryEmbedding", ["x", "cos3", "sin3"], ["y"], name="rope", num_heads=heads)], ["cos3", "sin3"]
+    elif form == "rotary_ids_4d":
+        nodes, used = [node("RotaryEmbedding", ["x", "cos", "sin", "position_ids"], ["y"], name="rope")], ["cos", "sin"]
+        ins = [value_info("x", FLOAT, [batch, heads, seq, head_size]), value_info("position_ids", INT64, [batch, seq])]
+        outs = [value_info("y", FLOAT, [batch, heads, seq, head_size])]
+    elif form == "rotary_interleaved_partial":
+        nodes = [node("RotaryEmbedding", ["x", "cos_part", "sin_part", "position_ids"], ["y"], name="rope", num_heads=heads, interleaved=1, rotary_embedding_dim=head_size - 2)]
+        used = ["cos_part", "sin_part"]
+        ins.append(value_info("position_ids", INT64, [batch, seq]))
+    elif form == "ms_rotary_offset":
+        nodes, used = [node("RotaryEmbedding", ["x", "offset", "cos", "sin"], ["y"], name="rope", domain=MS, num_heads=heads)], ["cos", "sin"]
+        ins.append(value_info("offset", INT64, [1]))
+    elif form == "ms_rotary_ids":  # num_heads absent: inferred from the cache
+        nodes, used = [node("RotaryEmbedding", ["x", "position_ids", "cos", "sin"], ["y"], name="rope", domain=MS)], ["cos", "sin"]
+        ins.append(value_info("position_ids", INT64, [batch, seq]))
+    else:  # ms_rotary_no_ids
+        nodes, used = [node("RotaryEmbedding", ["x", "", "cos", "sin"], ["y"], name="rope", domain=MS, num_heads=heads)], ["cos", "sin"]
+    return model(nodes, ins, outs, [tensor(k, w[k]) for k in used], opset=23, name="norm_rotary_" + form), {k: w[k] for k in used}
+
+
+DECODER_BLOCK_OUTPUTS = ["mlp_out", "residual_out", "present_k", "present_v"]
+
+
+def decoder_block_graph(hidden: int = 64, heads: int = 4, kv_heads: int = 2, head_size: int = 16, ffn: int = 96, max_pos: int = 32, batch="batch", seq="seq",
+                        past="past", seed: int = 61):
+    """One decoder block as onnxruntime-genai's builder lays it out, its attention composed from plain operators:
+    SkipSimplifiedLayerNormalization(hidden_in, residual_in) -> q / k / v MatMul -> com.microsoft RotaryEmbedding on q and k from the one-element `offset` ->
+    head split (Reshape, Transpose) -> Concat with past_k / past_v [batch, kv_heads, past, head_size] (= present_k / present_v) -> KV heads repeated by Unsqueeze,
+    Expand, Reshape -> MatMul, Mul by 1 / sqrt(head_size), Softmax, MatMul -> head merge -> output projection -> SkipSimplifiedLayerNormalization with the
+    first sum -> gated MLP (gate and up MatMul, Silu, Mul, down MatMul).  Outputs DECODER_BLOCK_OUTPUTS: the MLP output and the second sum (the next block's
+    input and skip), present_k, present_v.  -> (model bytes, weights)."""
+    assert hidden == heads * head_size and heads % kv_heads == 0
+    rng = np.random.default_rng(seed)
+    f = lambda *s: (rng.standard_normal(s) / np.sqrt(s[0])).astype(np.float32)
+    w = {"ln1_g": (1.0 + 0.1 * rng.standard_normal(hidden)).astype(np.float32), "ln2_g": (1.0 + 0.1 * rng.standard_normal(hidden)).astype(np.float32),
+         "wq": f(hidden, heads * head_size), "wk": f(hidden, kv_heads * head_size), "wv": f(hidden, kv_heads * head_size), "wo": f(hidden, hidden),
+         "w_gate": f(hidden, ffn), "w_up": f(hidden, ffn), "w_down": f(ffn, hidden)}
+    w["cos"], w["sin"] = rotary_caches(max_pos, head_size // 2)
+    rep = heads // kv_heads
+    i64 = lambda *v: np.asarray(v, np.int64)
+    shapes = {"q_split": i64(0, 0, heads, head_size), "kv_split": i64(0, 0, kv_heads, head_size), "rep_axes": i64(2), "rep_shape": i64(1, 1, rep, 1, 1),
+              "rep_merge": i64(0, heads, -1, head_size), "merge": i64(0, 0, hidden), "scale": np.asarray(1.0 / np.sqrt(head_size), np.float32)}
+    nodes = [node("SkipSimplifiedLayerNormalization", ["hidden_in", "residual_in", "ln1_g"], ["n1", "", "", "res1"], name="input_norm", domain=MS, epsilon=1e-6),
+             node("MatMul", ["n1", "wq"], ["q"], name="q_proj"), node("MatMul", ["n1", "wk"], ["k"], name="k_proj"), node("MatMul", ["n1", "wv"], ["v"], name="v_proj"),
+             node("RotaryEmbedding", ["q", "offset", "cos", "sin"], ["q_rot"], name="q_rope", domain=MS, num_heads=heads),
+             node("RotaryEmbedding", ["k", "offset", "cos", "sin"], ["k_rot"], name="k_rope", domain=MS, num_heads=kv_heads),
+             node("Reshape", ["q_rot", "q_split"], ["q4"], name="q_split"), node("Transpose", ["q4"], ["q_heads"], name="q_heads", perm=[0, 2, 1, 3]),
+             node("Reshape", ["k_rot", "kv_split"], ["k4"], name="k_split"), node("Transpose", ["k4"], ["k_new"], name="k_heads", perm=[0, 2, 1, 3]),
+             node("Reshape", ["v", "kv_split"], ["v4"], name="v_split"), node("Transpose", ["v4"], ["v_new"], name="v_heads", perm=[0, 2, 1, 3]),
+             node("Concat", ["past_k", "k_new"], ["present_k"], name="k_cache", axis=2), node("Concat", ["past_v", "v_new"], ["present_v"], name="v_cache", axis=2)]
+    for t in ("k", "v"):
+        nodes += [node("Unsqueeze", [f"present_{t}", "rep_axes"], [f"{t}_5d"], name=f"{t}_rep_axis"), node("Expand", [f"{t}_5d", "rep_shape"], [f"{t}_rep"], name=f"{t}_repeat"),
+                  node("Reshape", [f"{t}_rep", "rep_merge"], [f"{t}_all"], name=f"{t}_rep_merge")]
+    nodes += [node("Transpose", ["k_all"], ["k_t"], name="k_transpose", perm=[0, 1, 3, 2]), node("MatMul", ["q_heads", "k_t"], ["scores"], name="qk"),
+              node("Mul", ["scores", "scale"], ["scaled"], name="qk_scale"), node("Softmax", ["scaled"], ["probs"], name="softmax", axis=-1),
+              node("MatMul", ["probs", "v_all"], ["ctx4"], name="pv"), node("Transpose", ["ctx4"], ["ctx_t"], name="merge_heads", perm=[0, 2, 1, 3]),
+              node("Reshape", ["ctx_t", "merge"], ["ctx"], name="merge"), node("MatMul", ["ctx", "wo"], ["attn_out"], name="o_proj"),
+              node("SkipSimplifiedLayerNormalization", ["attn_out", "res1", "ln2_g"], ["n2", "", "", "residual_out"], name="post_attention_norm", domain=MS, epsilon=1e-6),
+              node("MatMul", ["n2", "w_gate"], ["gate"], name="gate_proj"), node("MatMul", ["n2", "w_up"], ["up"], name="up_proj"),
+              node("Silu", ["gate"], ["gate_act"], name="act"), node("Mul", ["gate_act", "up"], ["gated"], name="gated"),
+              node("MatMul", ["gated", "w_down"], ["mlp_out"], name="down_proj")]
+    ins = [value_info("hidden_in", FLOAT, [batch, seq, hidden]), value_info("residual_in", FLOAT, [batch, seq, hidden]),
+           value_info("past_k", FLOAT, [batch, kv_heads, past, head_size]), value_info("past_v", FLOAT, [batch, kv_heads, past, head_size]), value_info("offset", INT64, [1])]
+    outs = [value_info("mlp_out", FLOAT, [batch, seq, hidden]), value_info("residual_out", FLOAT, [batch, seq, hidden]),
+            value_info("present_k", FLOAT, [batch, kv_heads, "total", head_size]), value_info("present_v", FLOAT, [batch, kv_heads, "total", head_size])]
+    inits = [tensor(k, v) for k, v in w.items()] + [tensor(k, v) for k, v in shapes.items()]
+    return model(nodes, ins, outs, inits, opset=21, name="decoder_block"), w

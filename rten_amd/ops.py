@@ -2652,6 +2652,306 @@ class LSTM(_Recurrent):
         return self._launch(ctx, "rten_hip_lstm_f32", x, [w, r, b, h0, c0], 3, outputs)
 
 
+# ------------------------------------------------------------------------------------------ decoder blocks: RMS / skip normalisation, rotary embedding
+SKIP_NORM_LAYER, SKIP_NORM_RMS = 0, 1  # RTEN_HIP_SKIP_NORM_*
+ROTARY_POS_NONE, ROTARY_POS_IDS, ROTARY_POS_OFFSET = 0, 1, 2  # RTEN_HIP_ROTARY_POS_*
+
+
+def _dense(ctx, x):
+    """A contiguous DeviceTensor of a DeviceTensor or an einsum.View (re-laid when it is strided)."""
+    from . import einsum as E
+    return E.materialize(ctx, x) if isinstance(x, E.View) else x
+
+
+def _one_element(t):
+    """`scale.item()` of layer_normalization_impl (norm.rs:470): the value of a tensor of exactly one element, any rank; None otherwise.  A host array costs
+    nothing; a device tensor is read back (constants of a graph are host values in the executor)."""
+    if isinstance(t, DeviceTensor):
+        return float(t.numpy().reshape(())) if t.size == 1 else None
+    a = np.asarray(t)
+    return float(a.reshape(())) if a.size == 1 else None
+
+
+class RMSNormalization(Operator):
+    """src/ops/norm.rs:419-435,571-608 (rten_hip_rms_norm_f32).  inputs: X, scale.  The slice shape[axis..] is normalised by its root mean square:
+    y = x * (scale[i] * r), r = 1 / sqrt(SumSquare / n + epsilon); a one-element scale gives y = mul_add(x, scale / sqrt(..), 0).  Loader defaults
+    (onnx_registry.rs:1584-1590): axis -1, epsilon absent = 1e-5, stash_type must be 1."""
+
+    def __init__(self, axis=-1, epsilon=None):
+        self.axis, self.epsilon = axis, epsilon
+
+    def max_inputs(self):
+        return 2
+
+    def run(self, ctx, inputs):
+        from . import einsum as E
+        x = _require(inputs, 0)
+        _want(x.t if isinstance(x, E.View) else x, np.float32)
+        scale = _want(_require(inputs, 1), np.float32)
+        x = _dense(ctx, x)  # (to_contiguous_in, norm.rs:497)
+        ax = _resolve_axis(len(x.shape), self.axis)
+        norm_shape = tuple(x.shape[ax:])
+        cols = int(np.prod(norm_shape, dtype=np.int64))
+        gamma, gs = None, _one_element(scale)
+        if gs is None:
+            if _broadcast_shapes(tuple(scale.shape), norm_shape) != norm_shape:
+                raise InvalidValue("`scale` is not broadcastable to normalized axes of input")
+            if scale.size != cols:
+                raise UnsupportedValue("device path needs scale already expanded to the normalized shape")
+            gamma = scale if isinstance(scale, DeviceTensor) else DeviceTensor.from_numpy(ctx, scale)
+        y = DeviceTensor(ctx, x.shape, np.float32)
+        if x.size:
+            ctx.call("rten_hip_rms_norm_f32", x.size // cols, cols, x.vp, _vp(gamma), 1.0 if gs is None else gs, 1e-5 if self.epsilon is None else self.epsilon, y.vp)
+        return [y]
+
+
+class SimplifiedLayerNormalization(RMSNormalization):
+    """src/ops/norm/contrib.rs:86-115: the contrib spelling of RMSNormalization, registered in ai.onnx (onnx_registry.rs:275,1905)."""
+
+
+class _SkipNorm(Operator):
+    """skip_layer_normalization, src/ops/norm/contrib.rs:22-77 (rten_hip_skip_norm_f32): sum = (input + skip) + bias, normalised over the last axis.
+    `outputs` says which of (output, mean, inv_std_var, input_skip_bias_sum) a caller reads: the sum comes from the same launch when entry 3 is set; mean and
+    inv_std_var are training outputs the reference fills with zeros, and asking for them here is UnsupportedValue.  Returns [output] or
+    [output, None, None, sum]."""
+
+    MODE = SKIP_NORM_LAYER
+
+    def __init__(self, epsilon):
+        self.epsilon = epsilon
+
+    def max_outputs(self):
+        return 4
+
+    def _operands(self, inputs):
+        raise NotImplementedError
+
+    def run(self, ctx, inputs, outputs=None):
+        x = _dense(ctx, _require(inputs, 0))
+        skip = _dense(ctx, _require(inputs, 1))
+        _want(x, np.float32), _want(skip, np.float32)
+        gamma, beta, bias = self._operands(inputs)
+        for t in (gamma, beta, bias):
+            if t is not None:
+                _want(t, np.float32)
+                if len(t.shape) != 1:
+                    raise OpError("InputCastFailed", "expected tensor with 1 dims")
+        want = list(outputs) + [False] * (4 - len(outputs)) if outputs is not None else [True, False, False, False]
+        if want[1] or want[2]:
+            raise UnsupportedValue("the mean and inv_std_var outputs are not computed")
+        if len(x.shape) not in (2, 3):
+            raise InvalidValue("input must be 2 or 3 dimensioned")
+        if len(skip.shape) not in (2, 3):
+            raise InvalidValue("skip must be 2 or 3 dimensioned")
+        if tuple(skip.shape[-2:]) != tuple(x.shape[-2:]) or (len(skip.shape) == 3 and skip.shape[0] not in (1, x.shape[0])) or len(skip.shape) > len(x.shape):
+            raise IncompatibleInputShapes("skip must broadcast to input over the batch dimension")
+        cols = x.shape[-1]
+        if bias is not None and bias.shape[0] not in (1, cols):
+            raise IncompatibleInputShapes("Cannot broadcast inputs")  # (add_in_place, binary_elementwise.rs)
+        one = _one_element(gamma) is not None
+        if not one and gamma.shape[0] != cols:
+            raise InvalidValue("`scale` is not broadcastable to normalized axes of input")
+        if beta is not None and beta.shape[0] not in (1, cols):
+            raise InvalidValue("`bias` is not broadcastable to normalized axes of input")
+        y = DeviceTensor(ctx, x.shape, np.float32)
+        total = DeviceTensor(ctx, x.shape, np.float32) if want[3] else None
+        if x.size:
+            if one or (bias is not None and bias.shape[0] != cols) or (beta is not None and beta.shape[0] != cols):
+                # a one-element gamma is the reference's scalar scale (other bits than a vector of equal values), a one-element bias / beta a broadcast: the
+                # operators one after the other, on the entry points that take a scalar
+                s = Add().run(ctx, [x, skip])[0]
+                if bias is not None:
+                    s = Add().run(ctx, [s, bias])[0]
+                norm = RMSNormalization(-1, self.epsilon) if self.MODE == SKIP_NORM_RMS else LayerNormalization(-1, self.epsilon)
+                scale = gamma.reshape(()) if one else gamma
+                y = norm.run(ctx, [s, scale] + ([beta.reshape(()) if beta.shape[0] == 1 else beta] if beta is not None else []))[0]
+                total = s if want[3] else None
+            else:
+                ctx.call("rten_hip_skip_norm_f32", self.MODE, x.size // cols, cols, x.vp, skip.vp, skip.size // cols, _vp(bias), gamma.vp, _vp(beta), self.epsilon,
+                         _vp(total), y.vp)
+        return [y, None, None, total] if want[3] else [y]
+
+
+class SkipLayerNormalization(_SkipNorm):
+    """com.microsoft, src/ops/norm/contrib.rs:123-177.  inputs: input, skip, gamma, beta?, bias?; `epsilon` is required (onnx_registry.rs:1918-1922)."""
+
+    def max_inputs(self):
+        return 5
+
+    def _operands(self, inputs):
+        return _require(inputs, 2), _get(inputs, 3), _get(inputs, 4)
+
+
+class SkipSimplifiedLayerNormalization(_SkipNorm):
+    """com.microsoft, src/ops/norm/contrib.rs:186-238: the RMS form.  inputs: input, skip, gamma, bias?."""
+
+    MODE = SKIP_NORM_RMS
+
+    def name(self):
+        return "SkipSimplifiedLayerNormalisation"  # (sic, contrib.rs:192)
+
+    def max_inputs(self):
+        return 4
+
+    def _operands(self, inputs):
+        return _require(inputs, 2), None, _get(inputs, 3)
+
+
+def rotary_cache_dims(cache_shape, batch, seq_len, half, bad_last_dim):
+    """src/ops/embedding.rs:20-44: a cos / sin cache is [1 | batch, 1 | seq_len, rotary_embedding_dim / 2]; returns its (batch, seq_len) dims."""
+    if len(cache_shape) != 3:
+        raise InvalidValue("cos/sin cache must be a 3D tensor")
+    cache_batch, cache_seq, cache_half = cache_shape
+    if cache_half != half:
+        raise InvalidValue(bad_last_dim)
+    if cache_seq != 1 and cache_seq != seq_len:
+        raise InvalidValue("cos/sin cache sequence length must be 1 or match the input")
+    if cache_batch != 1 and cache_batch != batch:
+        raise InvalidValue("cos/sin cache batch size must be 1 or match the input")
+    return cache_batch, cache_seq
+
+
+def _host_ids(t):
+    """position_ids known on the host (a numpy array or a Python int; the loader narrows int64 to int32) as an int32 array; None for device data."""
+    if isinstance(t, DeviceTensor):
+        return None
+    a = np.asarray(t)
+    if a.dtype.kind not in "iu":
+        raise OpError("InputCastFailed", "expected int32 tensor")
+    return a.astype(np.int32)
+
+
+def rotary_embedding(ctx, x, cos, sin, position_ids, offset, interleaved, num_heads, rotary_embedding_dim):
+    """rotary_embedding, src/ops/embedding.rs:46-207 (rten_hip_rotary_embedding_f32).  `x` may be an einsum.View with a unit stride along its last axis --
+    a q or k column block of a fused projection -- and is then read in place.  `position_ids`: int32 [batch, seq] ids, or, with `offset`, the contrib
+    operator's one-element offset k (token i uses position k + i); a DeviceTensor is gathered by the kernel (an id outside the cache is clamped as Gather on
+    device data is), a host array is checked here."""
+    from . import einsum as E
+    _want(x.t if isinstance(x, E.View) else x, np.float32)
+    v = x if isinstance(x, E.View) else E.View(x)
+    if len(v.shape) in (3, 4) and v.shape[-1] > 1 and v.strides[-1] != 1:
+        v = E.View(E.materialize(ctx, v))  # (to_contiguous_in, embedding.rs:128-131)
+    if len(v.shape) == 3:
+        batch, seq_len, hidden = v.shape
+        if num_heads == 0:
+            raise InvalidValue("num_heads must not be 0 for 3 dimensioned input")
+        if hidden % num_heads != 0:
+            raise InvalidValue("hidden_size must be divisible by num_heads")
+        heads, head_size = num_heads, hidden // num_heads
+        xst = (v.strides[0], v.strides[1], head_size)
+        yst = (seq_len * hidden, hidden, head_size)
+    elif len(v.shape) == 4:
+        batch, heads, seq_len, head_size = v.shape
+        xst = (v.strides[0], v.strides[2], v.strides[1])
+        yst = (heads * seq_len * head_size, head_size, seq_len * head_size)
+    else:
+        raise IncompatibleInputShapes("Input processed needs 3-4 dimensions")
+    rot = head_size if rotary_embedding_dim == 0 else rotary_embedding_dim
+    if rot == 0 or rot % 2 != 0:
+        raise InvalidValue("rotary_embedding_dim must be a positive even number")
+    if rot > head_size:
+        raise InvalidValue("rotary_embedding_dim must not exceed head size")
+    half = rot // 2
+    cos, sin = _dense(ctx, cos), _dense(ctx, sin)
+    _want(cos, np.float32), _want(sin, np.float32)
+    mode, max_pos, ids, cst, sst = ROTARY_POS_NONE, 0, None, (0, 0), (0, 0)
+    if position_ids is not None:
+        host = _host_ids(position_ids)
+        if host is None:
+            _want(position_ids, np.int32)
+        id_shape = (batch, seq_len) if offset else tuple(position_ids.shape if host is None else host.shape)
+        # gather(cos, 0, ids) has shape ids.shape + cos.shape[1..]
+        for cache, msg in ((cos, "Last dimension of cos cache does not match rotary_embedding_dim/2"), (sin, "Last dimension of sin cache does not match rotary_embedding_dim/2")):
+            if len(cache.shape) == 0:
+                raise InvalidValue("Cannot gather from a scalar")  # (gather.rs)
+            rotary_cache_dims(id_shape + tuple(cache.shape[1:]), batch, seq_len, half, msg)
+        if cos.shape[0] != sin.shape[0]:
+            raise UnsupportedValue("device path needs cos and sin caches of one length")
+        max_pos = cos.shape[0]
+        if host is not None:
+            pos = host.reshape(-1)[:1].astype(np.int64) + np.arange(seq_len) if offset else host.astype(np.int64)
+            if pos.size and (pos.min() < -max_pos or pos.max() >= max_pos):
+                raise InvalidValue("Entry in `indices` is out of range")
+            if not offset:
+                host = np.ascontiguousarray(np.broadcast_to(host, (batch, seq_len)))
+            ids = DeviceTensor.from_numpy(ctx, host.reshape(-1)[:1] if offset else host)
+        else:
+            if not offset and id_shape != (batch, seq_len):
+                raise UnsupportedValue("device position_ids must have the input's [batch, seq] shape")
+            ids = position_ids
+        mode = ROTARY_POS_OFFSET if offset else ROTARY_POS_IDS
+    else:
+        cb, cs = rotary_cache_dims(tuple(cos.shape), batch, seq_len, half, "Last dimension of cos cache does not match rotary_embedding_dim/2")
+        sb, ss = rotary_cache_dims(tuple(sin.shape), batch, seq_len, half, "Last dimension of sin cache does not match rotary_embedding_dim/2")
+        cst = (0 if cb == 1 else cs * half, 0 if cs == 1 else half)
+        sst = (0 if sb == 1 else ss * half, 0 if ss == 1 else half)
+    y = DeviceTensor(ctx, v.shape, np.float32)
+    if y.size:
+        ctx.call("rten_hip_rotary_embedding_f32", batch, seq_len, heads, head_size, rot, 1 if interleaved else 0, v.t.vp, *xst, cos.vp, *cst, sin.vp, *sst,
+                 _vp(ids), mode, max_pos, y.vp, *yst)
+    return y
+
+
+class RotaryEmbedding(Operator):
+    """ai.onnx, src/ops/embedding.rs:209-252.  inputs: X [B, S, H * D] (needs num_heads) or [B, H, S, D], cos, sin, position_ids [B, S]?.  Loader defaults
+    (onnx_registry.rs:1832-1847): interleaved false, num_heads 0, rotary_embedding_dim 0 (= head size)."""
+
+    def __init__(self, interleaved=False, num_heads=0, rotary_embedding_dim=0):
+        self.interleaved, self.num_heads, self.rotary_embedding_dim = bool(interleaved), num_heads, rotary_embedding_dim
+
+    def max_inputs(self):
+        return 4
+
+    def run(self, ctx, inputs):
+        x, cos, sin, ids = _require(inputs, 0), _require(inputs, 1), _require(inputs, 2), _get(inputs, 3)
+        if ids is not None and len(np.shape(ids) if not isinstance(ids, DeviceTensor) else ids.shape) != 2:
+            raise OpError("InputCastFailed", "expected tensor with 2 dims")
+        return [rotary_embedding(ctx, x, cos, sin, ids, False, self.interleaved, self.num_heads, self.rotary_embedding_dim)]
+
+
+class RotaryEmbeddingMicrosoft(Operator):
+    """com.microsoft RotaryEmbedding, src/ops/embedding/contrib.rs:17-135.  inputs: X, position_ids, cos [max_pos, half], sin.  position_ids is [B, S], or a
+    scalar / one-element vector holding an offset k (token i uses position k + i).  num_heads 0 or None is inferred from the cache for a 3-D input, which
+    rotary_embedding_dim != 0 rules out."""
+
+    def __init__(self, interleaved=False, num_heads=None, rotary_embedding_dim=0):
+        self.interleaved, self.num_heads, self.rotary_embedding_dim = bool(interleaved), num_heads, rotary_embedding_dim
+
+    def name(self):
+        return "com.microsoft.RotaryEmbedding"
+
+    def max_inputs(self):
+        return 4
+
+    def run(self, ctx, inputs):
+        from . import einsum as E
+        x, ids, cos, sin = (_require(inputs, i) for i in range(4))
+        xs = tuple(x.shape)
+        if len(xs) not in (3, 4):
+            raise IncompatibleInputShapes("Input processed needs 3-4 dimensions")
+        ids_shape = tuple(ids.shape) if isinstance(ids, DeviceTensor) else np.shape(ids)
+        n_ids = int(np.prod(ids_shape, dtype=np.int64))
+        if len(ids_shape) in (0, 1) and n_ids == 1:
+            offset = True
+        elif len(ids_shape) == 2:
+            offset = False
+        else:
+            raise InvalidValue("position_ids must be a scalar, a 1-element vector or have 2 dims")
+        num_heads = self.num_heads or 0
+        if len(xs) == 3 and num_heads == 0:
+            if self.rotary_embedding_dim != 0:
+                raise InvalidValue("num_heads must be specified when rotary_embedding_dim is set")
+            if len(cos.shape) == 0:
+                raise InvalidValue("cos cache must not be scalar")
+            if cos.shape[-1] == 0:
+                raise InvalidValue("Last dimension of cos cache must not be 0")
+            head_size = cos.shape[-1] * 2
+            if xs[2] % head_size != 0:
+                raise InvalidValue("hidden_size must be divisible by head size")
+            num_heads = xs[2] // head_size
+        return [rotary_embedding(ctx, x, cos, sin, ids, offset, self.interleaved, num_heads, self.rotary_embedding_dim)]
+
+
 class OpRegistry:
     """Mirror of OpRegistry (src/op_registry.rs:25-72): op_type -> operator class for the hot path."""
 
@@ -2667,7 +2967,8 @@ class OpRegistry:
                    Split, ReduceMax, ReduceMin, ArgMax, ArgMin, TopK, GRU, LSTM, Neg, Abs, Sign, Floor, Ceil, Round, Sqrt, Reciprocal, Exp, Log, Softplus,
                    Pow, PRelu, Min, Max, Sum, Mean, Pad, QuantizeLinear, DequantizeLinear, ReduceL1, ReduceL2, ReduceSumSquare, ReduceLogSum, ReduceLogSumExp,
                    ReduceProd, LpNormalization, GlobalMaxPool, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile,
-                   NonMaxSuppression, DFT, STFT):
+                   NonMaxSuppression, DFT, STFT, RMSNormalization, SimplifiedLayerNormalization, SkipLayerNormalization,
+                   SkipSimplifiedLayerNormalization, RotaryEmbedding, RotaryEmbeddingMicrosoft):
             r.register_op(op)
         return r
 

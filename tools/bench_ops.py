@@ -606,6 +606,41 @@ def main():
             8.0 * 4096 * 2048)
         del xc_, yc_, xr_, yr_
 
+    # ---- decoder blocks (rten_amd/csrc/decoder.hip): RMS normalisation, the skip form with its sum written, rotary embedding.  Each norm row is followed by
+    # the same shape through rten_hip_layer_norm_f32 (up to 1024 columns its register forms, above that its generic one-wave-per-row form: what these rows
+    # ran on before) and by a strided copy of the same bytes, the yardstick.  RTEN_NORM_WPR=4 in the environment forces the workgroup-per-row form at 1024
+    # columns and below: the two runs side by side are the numbers behind the launch rule's 1024 boundary (docs/KERNELS.md 4.17).
+    if want("decoder:"):
+        form = os.environ.get("RTEN_NORM_WPR", "rule")
+        for r_, c_ in ((1, 4096), (32, 4096), (4096, 4096), (2048, 8192), (32, 1024), (4096, 1024), (4096, 512)):
+            xd, sd, yd, td = dev(rng.standard_normal((r_, c_), dtype=np.float32)), dev(rng.standard_normal((r_, c_), dtype=np.float32)), empty((r_, c_)), empty((r_, c_))
+            gd, bd = dev(rng.standard_normal(c_, dtype=np.float32)), dev(rng.standard_normal(c_, dtype=np.float32))
+            shape = f"rows={r_} cols={c_} form={form}"
+            hbm("decoder: RMSNormalization", shape, (lambda: ctx.call("rten_hip_rms_norm_f32", r_, c_, xd.vp, gd.vp, 1.0, 1e-6, yd.vp)), 8.0 * r_ * c_)
+            hbm("decoder: LayerNormalization entry point, same shape (what the rows ran on before)", shape,
+                (lambda: ctx.call("rten_hip_layer_norm_f32", r_, c_, xd.vp, gd.vp, bd.vp, C.c_float(1.0), C.c_float(0.0), C.c_float(1e-6), yd.vp)), 8.0 * r_ * c_)
+            hbm("decoder: strided copy of the norm's bytes (yardstick)", shape,
+                (lambda: ctx.call("rten_hip_copy_strided_b32", 2, (C.c_int64 * 2)(r_, c_), (C.c_int64 * 2)(c_, 1), xd.vp, yd.vp)), 8.0 * r_ * c_)
+            hbm("decoder: SkipSimplifiedLayerNormalization with the sum written", shape,
+                (lambda: ctx.call("rten_hip_skip_norm_f32", 1, r_, c_, xd.vp, sd.vp, r_, None, gd.vp, None, 1e-6, td.vp, yd.vp)), 16.0 * r_ * c_)
+            def two_copies():  # the skip form reads two tensors and writes two: the same bytes as two copies, which are two launches
+                ctx.call("rten_hip_copy_strided_b32", 2, (C.c_int64 * 2)(r_, c_), (C.c_int64 * 2)(c_, 1), xd.vp, yd.vp)
+                ctx.call("rten_hip_copy_strided_b32", 2, (C.c_int64 * 2)(r_, c_), (C.c_int64 * 2)(c_, 1), sd.vp, td.vp)
+            hbm("decoder: two strided copies of the skip form's bytes (yardstick)", shape, two_copies, 16.0 * r_ * c_)
+            del xd, sd, yd, td
+        cos_, sin_ = dev(rng.standard_normal((4096, 64), dtype=np.float32)), dev(rng.standard_normal((4096, 64), dtype=np.float32))
+        off_ = dev(np.array([100], np.int32))
+        for b_, s_, h_ in ((32, 1, 32), (1, 2048, 32)):
+            d_ = 128
+            xq, yq = dev(rng.standard_normal((b_, s_, h_ * d_), dtype=np.float32)), empty((b_, s_, h_ * d_))
+            shape = f"batch={b_} seq={s_} heads={h_} head_size={d_}"
+            hbm("decoder: RotaryEmbedding, positions from a one-element device offset", shape,
+                (lambda: ctx.call("rten_hip_rotary_embedding_f32", b_, s_, h_, d_, d_, 0, xq.vp, s_ * h_ * d_, h_ * d_, d_, cos_.vp, 0, 0, sin_.vp, 0, 0, off_.vp, 2, 4096,
+                                  yq.vp, s_ * h_ * d_, h_ * d_, d_)), 8.0 * b_ * s_ * h_ * d_)
+            hbm("decoder: strided copy of the rotary rows' bytes (yardstick)", shape,
+                (lambda: ctx.call("rten_hip_copy_strided_b32", 2, (C.c_int64 * 2)(b_ * s_, h_ * d_), (C.c_int64 * 2)(h_ * d_, 1), xq.vp, yq.vp)), 8.0 * b_ * s_ * h_ * d_)
+            del xq, yq
+
     if args.cpu_baseline:
         sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         import bench  # the oracle is only ever touched through bench.py's cpu_baseline leg

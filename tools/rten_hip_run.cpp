@@ -16,7 +16,7 @@
 //     -t, --timing           per-operator table (each operator followed by a sync)
 //     --tune                 time the candidate launch plans of every f32 convolution at load and keep the fastest
 //     --graph                capture one run into a hipGraph and replay it for the timed runs (refused, by node name, for a graph with a NonMaxSuppression node)
-//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow, Reduce*, LpNormalization, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile, NonMaxSuppression, DFT, STFT and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
+//     --parse-only           print the model summary (and check GRU / LSTM, normalisation, Pad, Pow, Reduce*, LpNormalization, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile, NonMaxSuppression, DFT, STFT, RMS / skip normalisation, RotaryEmbedding and QuantizeLinear / DequantizeLinear nodes as the loader does) and exit (needs no GPU)
 //     --safetensors-info F   list the tensors of a Safetensors file (with --save-outputs: re-write it); no model, no GPU
 //
 // There is no CPU fallback: without an MI355X the tool reports BackendUnavailable and exits 2.
@@ -220,6 +220,32 @@ int main(int argc, char **argv) {
                     std::printf("  fft step \"%s\": STFT onesided %d, window %s, frame_length %s\n", n.name.c_str(), a.onesided ? 1 : 0, a.has_window ? "from input 2" : "absent",
                                 a.has_frame_length ? "from input 3" : "the window's length");
                 }
+            }
+        }
+        {
+            const onnx::Model c = Graph::canonical_form(m); // RMS / skip normalisation and RotaryEmbedding: the loader's checks, and the Add each RMS node takes in with fusion on
+            std::map<size_t, size_t> add_of;
+            if (fuse)
+                for (size_t i = 0; i < c.nodes.size(); i++) {
+                    const long r = Graph::add_rms_consumer(c, i);
+                    if (r >= 0 && !add_of.count((size_t)r)) add_of[(size_t)r] = i;
+                }
+            for (size_t i = 0; i < c.nodes.size(); i++) {
+                const onnx::Node &n = c.nodes[i];
+                if (!Graph::is_decoder_node(n)) continue;
+                const Graph::DecoderNode a = Graph::read_decoder_node(c, n, n.name.empty() ? n.outputs.at(0) : n.name);
+                const std::string kind = (a.contrib ? "com.microsoft." : "") + n.op_type;
+                if (a.rotary)
+                    std::printf("  decoder step %s \"%s\": interleaved %d, num_heads %" PRId64 ", rotary_embedding_dim %" PRId64 ", positions %s\n", kind.c_str(), n.name.c_str(),
+                                a.interleaved ? 1 : 0, a.num_heads, a.rotary_embedding_dim,
+                                a.contrib ? "from input 1 (ids or a one-element offset, gathered by the kernel)" : n.inputs.size() > 3 && !n.inputs[3].empty() ? "from input 3 (gathered by the kernel)" : "absent");
+                else if (a.skip)
+                    std::printf("  decoder step %s \"%s\": epsilon %g, bias %s, sum %s\n", kind.c_str(), n.name.c_str(), (double)*a.epsilon,
+                                n.inputs.size() > (a.rms ? 3u : 4u) && !n.inputs[a.rms ? 3 : 4].empty() ? "yes" : "no", a.want_sum ? "written by the same launch" : "not read");
+                else if (add_of.count(i))
+                    std::printf("  decoder step Add+%s \"%s\" + \"%s\": one skip launch, epsilon %g\n", n.op_type.c_str(), c.nodes[add_of[i]].name.c_str(), n.name.c_str(), (double)a.epsilon.value_or(1e-5f));
+                else
+                    std::printf("  decoder step %s \"%s\": axis %d, epsilon %g\n", kind.c_str(), n.name.c_str(), a.axis, (double)a.epsilon.value_or(1e-5f));
             }
         }
         {
