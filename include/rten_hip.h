@@ -50,7 +50,8 @@
 extern "C" {
 #endif
 
-/* v8 (round 6, third part): + rten_hip_conv2d_f32_pair / _pair_supported (an expand layer and the next block's reduce layer in one launch; a launch plan
+/* v8, later additions without a bump: + rten_hip_gqa_f32, rten_hip_set_gqa_path (GroupQueryAttention with a KV cache; dims and strides as host arrays).
+ * v8 (round 6, third part): + rten_hip_conv2d_f32_pair / _pair_supported (an expand layer and the next block's reduce layer in one launch; a launch plan
  * lists the pairs: "pairs"), rten_hip_conv2d_f32_pair_shortcut / _supported (the same with the block's shortcut convolution computed in the launch: "pair_shortcuts");
  * GEMM variant 32 (the direct stem kernel); rten_hip_model_plan_json also names the load-time lists.
  * v7 (round 6, second part): + rten_hip_set_int8_tile (the int8 kernels' workgroup tile as a context knob: a launch plan may carry a per-layer entry for an int8
@@ -454,6 +455,31 @@ int32_t rten_hip_rotary_embedding_f32(rten_hip_ctx *ctx, int32_t batch, int32_t 
                                       const float *cos, int64_t cos_stride_b, int64_t cos_stride_s, const float *sin, int64_t sin_stride_b,
                                       int64_t sin_stride_s, const int32_t *position_ids, int32_t position_mode, int32_t max_pos, float *y,
                                       int64_t y_stride_b, int64_t y_stride_s, int64_t y_stride_h);
+/* ---- GroupQueryAttention with a KV cache: src/ops/attention/contrib.rs:359-878 (com.microsoft) ----
+ * One call = rotary on Q and K (optional), both present caches, attention.  Nothing is read back: seqlens_k (int32 [B]) and total_sequence_length (ONE
+ * int32) stay on the device, so the call captures and a replay follows new values.
+ * dims (host, RTEN_HIP_GQA_NDIMS int32): batch, seq S, num_heads H, kv_num_heads KV (divides H), head_size D, past_seq P, rotary_dim (even, <= D; 0 = no
+ * rotary), rotary_interleaved, max_pos (rows of cos / sin, [max_pos, rotary_dim / 2]), local_window_size (<= 0: none).
+ * strides (host, RTEN_HIP_GQA_NSTRIDES int64, elements): batch / token / head strides of q, k and v (unit stride along the head, so separate [B, S, H * D]
+ * tensors, one packed [B, S, (H + 2 KV) * D] buffer and a fused projection's column blocks are read in place), then batch / head / row strides of
+ * attention_bias (0 broadcasts; its columns are contiguous and there are at least P + S of them).
+ * past_key / past_value: [B, KV, P, D] contiguous, NULL when P == 0.  present_key / present_value: [B, KV, P + S, D] contiguous, always written (a caller
+ * that does not want them passes temporaries); they may not alias the past.  out: [B, S, H * D] contiguous.
+ * Per batch item: kv_len = seqlens_k + 1, past_len = 0 when S == total else kv_len - S.  present = zeros, then rows [0, past_len) of past, then the S new
+ * rows at past_len (K rotated at position_ids [B, S], or past_len + s when that is NULL).  Query row s of head h attends keys [start, past_len + s + 1) of
+ * KV head h / (H / KV), start = max(0, past_len + s + 1 - local_window_size); the bias is added inside the window, everything else is -inf; softmax flushes
+ * NaN to 0.  Device values are clamped so that no access leaves a buffer (kv_len into [1, P + S], past_len into [0, P]; a position as in
+ * rten_hip_rotary_embedding_f32); a host that knows the values validates them itself (contrib.rs:582-639).
+ * One query row with the gemv order on, D 64 or 128 and 4 * ((H / KV) * (P + 1 + D) + 8192) bytes of LDS <= 160 KiB takes the one-launch decode kernel (a
+ * workgroup per (batch, KV head) that reads each K and V row once for the whole group); everything else takes GEMM, score kernel, GEMM with the group as
+ * the inner batch level, in passes of at most 64 MiB of scores (one query row in the gemv order with D > 512: RTEN_HIP_ERR_UNSUPPORTED).  rten_hip_set_gqa_path: 0 that rule, 1 the composed path only, 2 the decode kernel or RTEN_HIP_ERR_UNSUPPORTED. */
+#define RTEN_HIP_GQA_NDIMS 10
+#define RTEN_HIP_GQA_NSTRIDES 12
+int32_t rten_hip_gqa_f32(rten_hip_ctx *ctx, const int32_t *dims, const int64_t *strides, float scale, const float *q, const float *k, const float *v,
+                         const float *past_key, const float *past_value, const int32_t *seqlens_k, const int32_t *total_sequence_length,
+                         const float *cos, const float *sin, const int32_t *position_ids, const float *attention_bias, float *out,
+                         float *present_key, float *present_value);
+int32_t rten_hip_set_gqa_path(rten_hip_ctx *ctx, int32_t mode);
 /* BatchNormalization (inference), src/ops/norm.rs:194-224 */
 int32_t rten_hip_batch_norm_f32(rten_hip_ctx *ctx, int32_t n, int32_t c, int64_t inner, const float *x,
                                 const float *scale, const float *bias, const float *mean, const float *var,

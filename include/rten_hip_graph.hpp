@@ -1345,6 +1345,59 @@ class Graph {
         floats({0, 1});
         return a;
     }
+    // What the loader reads from, and refuses about, a com.microsoft GroupQueryAttention node (make_gqa_step; attributes and their defaults:
+    // onnx_registry.rs:1467-1492 -- num_heads and kv_num_heads are required, a non-positive local_window_size disables the window).  Refused by node name:
+    // smooth_softmax, a head_sink input, softcap != 0 (the reference calls libm's tanh there: not reproducible), inputs 12-15 (quantisation scales, q / k
+    // norm weights), output 3 (output_qk), and an input whose stated element type is not float32 (seqlens_k, total_sequence_length, position_ids: int32 /
+    // int64).  Needs no device; rten_hip_run --parse-only calls it too.
+    static bool is_gqa_node(const onnx::Node &n) { return n.domain == "com.microsoft" && n.op_type == "GroupQueryAttention"; }
+    struct GqaNode {
+        int64_t num_heads = 0, kv_num_heads = 0, local_window_size = -1;
+        std::optional<float> scale;
+        bool do_rotary = false, rotary_interleaved = false, packed = false, want_present = false;
+    };
+    static GqaNode read_gqa_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        const std::string where = "com.microsoft.GroupQueryAttention " + label + ": ";
+        GqaNode a;
+        if (!n.attr("num_heads") || !n.attr("kv_num_heads")) throw GraphError(where + "the num_heads and kv_num_heads attributes are required");
+        a.num_heads = n.get_int("num_heads", 0);
+        a.kv_num_heads = n.get_int("kv_num_heads", 0);
+        if (a.num_heads <= 0 || a.kv_num_heads <= 0) throw GraphError(where + "num_heads and kv_num_heads must be positive");
+        if (a.num_heads % a.kv_num_heads != 0) throw GraphError(where + "num_heads must be a multiple of kv_num_heads");
+        if (const onnx::Attr *sc = n.attr("scale")) a.scale = sc->f;
+        a.do_rotary = n.get_int("do_rotary", 0) != 0;
+        a.rotary_interleaved = n.get_int("rotary_interleaved", 0) != 0;
+        a.local_window_size = n.get_int("local_window_size", -1);
+        if (n.get_int("smooth_softmax", 0) != 0) throw GraphError(where + "smooth_softmax is not supported");
+        if (n.get_float("softcap", 0.f) != 0.f) throw GraphError(where + "softcap != 0 is not supported");
+        auto present = [&](size_t i) { return i < n.inputs.size() && !n.inputs[i].empty(); };
+        if (present(11)) throw GraphError(where + "the head_sink input (\"" + n.inputs[11] + "\") is not supported");
+        for (size_t i = 12; i < n.inputs.size(); i++)
+            if (present(i)) throw GraphError(where + "input " + std::to_string(i) + " (\"" + n.inputs[i] + "\") is not supported (inputs 12-15: quantisation scales and q / k norm weights)");
+        if (n.outputs.size() > 3 && !n.outputs[3].empty()) throw GraphError(where + "output 3 (output_qk, \"" + n.outputs[3] + "\") is not supported");
+        if (!present(0) || !present(5) || !present(6)) throw GraphError(where + "the query, seqlens_k and total_sequence_length inputs are required");
+        if (present(1) != present(2)) throw GraphError(where + "key and value must both be present or both absent");
+        if (present(3) != present(4)) throw GraphError(where + "past_key and past_value must both be present or both absent");
+        if (a.do_rotary && (!present(7) || !present(8))) throw GraphError(where + "cos_cache and sin_cache are required when do_rotary is set");
+        a.packed = !present(1);
+        auto stated = [&](const std::string &v) {
+            if (const onnx::TensorProto *t = initializer_named(m, v)) return t->data_type;
+            if (const onnx::ValueInfo *gi = graph_input_named(m, v)) return gi->elem_type;
+            return 0;
+        };
+        for (size_t i : {0, 1, 2, 3, 4, 7, 8, 10}) {
+            if (!present(i)) continue;
+            const int et = stated(n.inputs[i]);
+            if (et != 0 && et != onnx::FLOAT) throw GraphError(where + "input " + std::to_string(i) + " (\"" + n.inputs[i] + "\") has element type " + std::to_string(et) + ": float32 only");
+        }
+        for (size_t i : {5, 6, 9}) {
+            if (!present(i)) continue;
+            const int et = stated(n.inputs[i]);
+            if (et != 0 && et != onnx::INT32 && et != onnx::INT64) throw GraphError(where + "input " + std::to_string(i) + " (\"" + n.inputs[i] + "\") has element type " + std::to_string(et) + ": int32 / int64 only");
+        }
+        for (size_t k = 1; k <= 2; k++) a.want_present = a.want_present || (k < n.outputs.size() && value_is_read(m, n.outputs[k]));
+        return a;
+    }
     // What the loader refuses about a Reduce* node of reduce_family_kind: axes that are neither an attribute nor a constant input are found when the plan
     // is built (read_reduce_attrs); here, without a device, an axes input that is a graph input (device data at run time).
     static void check_reduce_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
@@ -2928,7 +2981,7 @@ class Graph {
             if (nodes.dead[i]) continue;
             const onnx::Node &n = m.nodes[i];
             // contrib operators this backend carries live in com.microsoft (onnx_registry.rs registers them under that domain)
-            const bool contrib = n.domain == "com.microsoft" && (n.op_type == "MatMulNBits" || is_decoder_node(n));
+            const bool contrib = n.domain == "com.microsoft" && (n.op_type == "MatMulNBits" || is_decoder_node(n) || is_gqa_node(n));
             if (!n.domain.empty() && n.domain != "ai.onnx" && !contrib) throw GraphError("node " + n.name + ": operator domain " + n.domain + " is not supported");
             Step st;
             st.name = label_of(n);
@@ -2965,6 +3018,7 @@ class Graph {
                 st.run = [op, plan](Context &c, const InputList &in) { PlanScope scope(c, *plan); return op->run(c, in); };
             } else if (kind == "MatMul") make_matmul_step(st, n, nodes, out_name);
             else if (kind == "Add" && opt_.fuse && make_add_norm_step(st, n, nodes, out_name)) {} // (any other Add takes the generic path below)
+            else if (is_gqa_node(n)) make_gqa_step(st, n, m);
             else if (is_decoder_node(n)) make_decoder_step(st, n, m); // (RotaryEmbedding dispatches on its domain, the skip forms exist in com.microsoft only)
             else if (kind == "LayerNormalization") {
                 auto op = std::make_shared<LayerNormalization>();
@@ -3325,6 +3379,23 @@ class Graph {
             const std::string kind = n.op_type;
             st.run = [this, op, kind, nm](Context &c, const InputList &in) { note_axis(kind, nm, op->axis, require(in, 0)); return op->run(c, in); };
         }
+    }
+    // com.microsoft GroupQueryAttention: the read_gqa_node checks at load, then rten_hip_gqa_f32 per run.  seqlens_k and total_sequence_length stay on the
+    // device and nothing is read back, so the step captures and a replayed plan follows new lengths; every batch item attends to its own cache only, so
+    // the step is not batch_coupled.  The present outputs are handed on only when the graph reads them.
+    void make_gqa_step(Step &st, const onnx::Node &n, const onnx::Model &m) {
+        const GqaNode a = read_gqa_node(m, n, st.name);
+        auto op = std::make_shared<GroupQueryAttention>();
+        op->num_heads = a.num_heads; op->kv_num_heads = a.kv_num_heads; op->scale = a.scale;
+        op->do_rotary = a.do_rotary; op->rotary_interleaved = a.rotary_interleaved; op->local_window_size = a.local_window_size;
+        op->want_present = a.want_present;
+        st.kind_name = "com.microsoft.GroupQueryAttention";
+        const size_t named = n.outputs.size();
+        st.run = [op, named](Context &c, const InputList &in) {
+            OutputList o = op->run(c, in);
+            while (o.size() < named) o.emplace_back(); // outputs the graph names but nothing reads
+            return o;
+        };
     }
     void make_activation_step(Step &st, const onnx::Node &n) {
         Activation act;

@@ -3659,6 +3659,135 @@ struct RotaryEmbeddingMicrosoft : Operator {
     }
 };
 
+// GroupQueryAttention with a KV cache (com.microsoft, src/ops/attention/contrib.rs:419-878; loader defaults onnx_registry.rs:1467-1492) on rten_hip_gqa_f32:
+// inputs query [B, S, H * D] (packed [B, S, (H + 2 KV) * D] with key and value absent), key, value [B, S, KV * D], past_key, past_value [B, KV, P, D],
+// seqlens_k int32 [B] or [B, 1], total_sequence_length int32 scalar, cos_cache, sin_cache [max, rot / 2], position_ids int32 [B, S], attention_bias
+// [B | 1, H | 1, >= S, >= P + S], head_sink (refused).  seqlens_k and total_sequence_length that carry a host copy (constants) are validated with the
+// reference's errors (contrib.rs:582-639); values only the device knows stay there -- nothing is read back, the step captures -- and the kernels clamp
+// kv_len into [1, P + S] and past_len into [0, P].  `want_present`: outputs 1 / 2 are requested (contrib.rs:803-807); the caches are computed either way,
+// because the attention kernels read K and V out of them.
+struct GroupQueryAttention : Operator {
+    int64_t num_heads = 0, kv_num_heads = 0;
+    std::optional<float> scale;
+    bool do_rotary = false, rotary_interleaved = false, smooth_softmax = false, want_present = true;
+    int64_t local_window_size = -1; // non-positive: no window
+    float softcap = 0.f;
+    const char *name() const override { return "com.microsoft.GroupQueryAttention"; }
+    int max_inputs() const override { return 12; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &query = want(require(in, 0), DType::F32, "float32");
+        if (query.ndim() != 3) throw OpError(OpError::InputCastFailed, "expected tensor with 3 dims");
+        const Tensor *key = get(in, 1), *value = get(in, 2), *past_key = get(in, 3), *past_value = get(in, 4);
+        const Tensor &seqlens = want(require(in, 5), DType::I32, "int32"), &total = want(require(in, 6), DType::I32, "int32");
+        const Tensor *cos = get(in, 7), *sin = get(in, 8), *position_ids = get(in, 9), *bias = get(in, 10), *head_sink = get(in, 11);
+        for (const Tensor *t : {key, value}) {
+            if (!t) continue;
+            want(*t, DType::F32, "float32");
+            if (t->ndim() != 3) throw OpError(OpError::InputCastFailed, "expected tensor with 3 dims");
+        }
+        std::vector<int64_t> sl = seqlens.shape();
+        while (sl.size() > 1 && sl.back() == 1) sl.pop_back();
+        if (sl.size() != 1) throw OpError(OpError::UnsupportedValue, "seqlens_k must be a vector");
+        if (total.len() != 1) throw OpError(OpError::InputCastFailed, "expected tensor with 0 dims");
+        if (head_sink) throw OpError(OpError::UnsupportedValue, "head_sink is not supported");
+        if (smooth_softmax) throw OpError(OpError::UnsupportedValue, "smooth_softmax is not supported");
+        const int64_t H = num_heads, KV = kv_num_heads;
+        if (H <= 0 || KV <= 0) throw OpError(OpError::InvalidValue, "num_heads and kv_num_heads must be positive");
+        if (H % KV != 0) throw OpError(OpError::InvalidValue, "num_heads must be a multiple of kv_num_heads");
+        const int64_t batch = query.size(0), seq = query.size(1), q_hidden = query.size(2);
+        int64_t D, st[RTEN_HIP_GQA_NSTRIDES] = {};
+        const float *qp = (const float *)query.ptr(), *kp, *vp_;
+        if (key && value) {
+            if (q_hidden % H != 0) throw OpError(OpError::IncompatibleInputShapes, "query hidden size must be divisible by num_heads");
+            D = q_hidden / H;
+            if (key->size(0) != batch || value->size(0) != batch) throw OpError(OpError::IncompatibleInputShapes, "key and value batch size must match query");
+            if (key->size(1) != value->size(1) || key->size(2) != value->size(2)) throw OpError(OpError::IncompatibleInputShapes, "key and value must have the same shape");
+            if (key->size(2) != KV * D) throw OpError(OpError::IncompatibleInputShapes, "key hidden size must equal kv_num_heads * head_size");
+            if (key->size(1) != seq) throw OpError(OpError::UnsupportedValue, "key sequence length must match query sequence length");
+            kp = (const float *)key->ptr(); vp_ = (const float *)value->ptr();
+            st[0] = seq * H * D; st[1] = H * D; st[2] = D;
+            st[3] = st[6] = seq * KV * D; st[4] = st[7] = KV * D; st[5] = st[8] = D;
+        } else if (!key && !value) {
+            const int64_t heads = H + 2 * KV;
+            if (q_hidden % heads != 0) throw OpError(OpError::IncompatibleInputShapes, "packed query hidden size must be divisible by num_heads + 2 * kv_num_heads");
+            D = q_hidden / heads;
+            kp = qp + H * D; vp_ = qp + (H + KV) * D;
+            for (int i = 0; i < 3; i++) { st[3 * i] = seq * q_hidden; st[3 * i + 1] = q_hidden; st[3 * i + 2] = D; }
+        } else throw OpError(OpError::InvalidValue, "key and value must both be present or both absent");
+        if (sl[0] != batch) throw OpError(OpError::IncompatibleInputShapes, "seqlens_k must have batch_size elements");
+        const HostVal *total_h = total.host(), *seqlens_h = seqlens.host();
+        if (total_h && total_h->is_float) total_h = nullptr;
+        if (seqlens_h && seqlens_h->is_float) seqlens_h = nullptr;
+        if (total_h && total_h->i.size() == 1 && total_h->i[0] <= 0) throw OpError(OpError::InvalidValue, "total_sequence_length must be positive");
+        int64_t P = 0;
+        if (past_key && past_value) {
+            want(*past_key, DType::F32, "float32"); want(*past_value, DType::F32, "float32");
+            if (past_key->ndim() != 4 || past_value->ndim() != 4) throw OpError(OpError::InputCastFailed, "expected tensor with 4 dims");
+            if (past_key->shape() != past_value->shape() || past_key->size(0) != batch || past_key->size(1) != KV || past_key->size(3) != D)
+                throw OpError(OpError::IncompatibleInputShapes, "past_key/past_value shape does not match");
+            P = past_key->size(2);
+        } else if (past_key || past_value) throw OpError(OpError::InvalidValue, "past_key and past_value must both be present or both absent");
+        const int64_t present_seq = P + seq;
+        if (total_h && total_h->i.size() == 1) {
+            const int64_t tot = total_h->i[0];
+            const bool first = seq == tot, subsequent = seq > 1 && seq != tot;
+            if (subsequent && batch != 1) throw OpError(OpError::UnsupportedValue, "batch size must be 1 when sequence_length > 1 and a past context is given");
+            if (!first && !subsequent && seq != 1) throw OpError(OpError::InvalidValue, "sequence_length must be 1 when query is not a prompt");
+        }
+        if (seqlens_h)
+            for (int64_t v : seqlens_h->i) {
+                if (v < 0 || v >= present_seq) throw OpError(OpError::InvalidValue, "seqlens_k entry is out of range");
+                if (v + 1 < seq) throw OpError(OpError::InvalidValue, "seqlens_k entry is too small for the query sequence length");
+            }
+        if (bias) {
+            want(*bias, DType::F32, "float32");
+            if (bias->ndim() != 4) throw OpError(OpError::InputCastFailed, "expected tensor with 4 dims");
+            const int64_t bb = bias->size(0), bh = bias->size(1), bs = bias->size(2), bt = bias->size(3);
+            if ((bb != 1 && bb != batch) || (bh != 1 && bh != H) || bs < seq || bt < present_seq)
+                throw OpError(OpError::IncompatibleInputShapes, "attention_bias shape is incompatible with query/key shapes");
+            st[9] = bb == 1 ? 0 : bh * bs * bt; st[10] = bh == 1 ? 0 : bs * bt; st[11] = bt;
+        }
+        const float sc = scale ? *scale : (D ? 1.0f / std::sqrt((float)D) : 0.f);
+        int64_t rot = 0, max_pos = 0;
+        if (do_rotary) {
+            if (!cos || !sin) throw OpError(OpError::InvalidValue, "cos_cache and sin_cache are required when do_rotary is set");
+            want(*cos, DType::F32, "float32"); want(*sin, DType::F32, "float32");
+            if (cos->ndim() != 2 || sin->ndim() != 2) throw OpError(OpError::InputCastFailed, "expected tensor with 2 dims");
+            rot = 2 * cos->size(1);
+            if (rot == 0) throw OpError(OpError::InvalidValue, "rotary_embedding_dim must be a positive even number");
+            if (rot > D) throw OpError(OpError::InvalidValue, "rotary_embedding_dim must not exceed head size");
+            if (sin->size(1) != cos->size(1)) throw OpError(OpError::InvalidValue, "Last dimension of sin cache does not match rotary_embedding_dim/2");
+            if (cos->size(0) != sin->size(0)) throw OpError(OpError::UnsupportedValue, "device path needs cos and sin caches of one length");
+            max_pos = cos->size(0);
+            if (position_ids) {
+                want(*position_ids, DType::I32, "int32");
+                if (position_ids->ndim() != 2) throw OpError(OpError::InputCastFailed, "expected tensor with 2 dims");
+                if (position_ids->size(0) != batch || position_ids->size(1) != seq)
+                    throw OpError(OpError::UnsupportedValue, "device path needs position_ids of the input's [batch, seq] shape");
+                if (const HostVal *h = position_ids->host())
+                    if (!h->is_float)
+                        for (int64_t v : h->i)
+                            if (v < -max_pos || v >= max_pos) throw OpError(OpError::InvalidValue, "Entry in `indices` is out of range");
+            }
+        }
+        if (softcap != 0.f) throw OpError(OpError::UnsupportedValue, "softcap is not supported");
+        OutputList out;
+        out.emplace_back(ctx, std::vector<int64_t>{batch, seq, H * D}, DType::F32);
+        out.emplace_back(ctx, std::vector<int64_t>{batch, KV, present_seq, D}, DType::F32);
+        out.emplace_back(ctx, std::vector<int64_t>{batch, KV, present_seq, D}, DType::F32);
+        if (out[0].len() && out[1].len()) {
+            const int32_t dims[RTEN_HIP_GQA_NDIMS] = {(int32_t)batch, (int32_t)seq, (int32_t)H, (int32_t)KV, (int32_t)D, (int32_t)P, (int32_t)rot, rotary_interleaved ? 1 : 0,
+                                                      (int32_t)max_pos, (int32_t)(local_window_size > 0 ? local_window_size : 0)};
+            ctx.check(rten_hip_gqa_f32(ctx.raw(), dims, st, sc, qp, kp, vp_, (const float *)vp(past_key), (const float *)vp(past_value), (const int32_t *)seqlens.ptr(),
+                                       (const int32_t *)total.ptr(), do_rotary ? (const float *)cos->ptr() : nullptr, do_rotary ? (const float *)sin->ptr() : nullptr,
+                                       do_rotary ? (const int32_t *)vp(position_ids) : nullptr, (const float *)vp(bias), (float *)out[0].ptr(), (float *)out[1].ptr(),
+                                       (float *)out[2].ptr()));
+        }
+        if (!want_present) out.resize(1);
+        return out;
+    }
+};
+
 // ------------------------------------------------------------------------------------------------ registry (src/op_registry.rs:25-72)
 class OpRegistry {
   public:
@@ -3773,6 +3902,7 @@ class OpRegistry {
         r.register_op<SkipLayerNormalization>("com.microsoft.SkipLayerNormalization");
         r.register_op<SkipSimplifiedLayerNormalization>("com.microsoft.SkipSimplifiedLayerNormalization");
         r.register_op<RotaryEmbeddingMicrosoft>("com.microsoft.RotaryEmbedding");
+        r.register_op<GroupQueryAttention>("com.microsoft.GroupQueryAttention");
         return r;
     }
 

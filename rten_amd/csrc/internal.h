@@ -54,6 +54,7 @@ struct rten_hip_ctx {
     int wave_flavour = 0; // pipeline 6: 0 = k-tiles of 16 x 2 LDS stages, 1 = 8 x 4, 2 = 16 x 3
     int num_cus = 256;
     int sdpa_path = 0;  // 0 automatic (fused attention kernel when it covers the shape), 1 composed path only
+    int gqa_path = 0;   // GroupQueryAttention: 0 automatic, 1 composed path only, 2 the one-launch decode kernel or an error (gqa.hip)
     int rnn_path = 0;   // GRU / LSTM: 0 automatic, 1 composed path only (per-step GEMM + gate kernel), 2 the time-persistent fused kernel or an error (rnn.hip)
     int instance_norm_path = 0; // InstanceNormalization: 0 automatic, 1 streaming form, 2 LDS-resident form where the slice fits, else streaming (norm.hip)
     int int8_path = 0;  // 0 automatic (fast staging path when it covers the call), 1 generic kernel only

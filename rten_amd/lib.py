@@ -119,6 +119,8 @@ class Pool2dDesc(C.Structure):
                 ("count_include_pad", C.c_int32)]
 
 
+GQA_NDIMS, GQA_NSTRIDES = 10, 12  # RTEN_HIP_GQA_NDIMS / _NSTRIDES: the host arrays of rten_hip_gqa_f32
+
 # every symbol include/rten_hip.h declares (checked by tests/test_abi.py against the header)
 _VP, _I32, _I64, _F32, _U32, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint32, C.c_size_t
 PROTOTYPES = {
@@ -191,6 +193,8 @@ PROTOTYPES = {
     "rten_hip_skip_norm_f32": (_I32, [_VP, _I32, _I64, _I32, _VP, _VP, _I64, _VP, _VP, _VP, _F32, _VP, _VP]),
     "rten_hip_rotary_embedding_f32": (_I32, [_VP, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I64, _I64, _I64, _VP, _I64, _I64, _VP, _I64, _I64, _VP, _I32, _I32,
                                             _VP, _I64, _I64, _I64]),
+    "rten_hip_gqa_f32": (_I32, [_VP, C.POINTER(_I32), C.POINTER(_I64), _F32] + [_VP] * 14),
+    "rten_hip_set_gqa_path": (_I32, [_VP, _I32]),
     "rten_hip_batch_norm_f32": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _F32, _VP]),
     "rten_hip_batch_norm_f32_act": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _F32, _I32, _F32, _F32, _VP]),
     "rten_hip_instance_norm_f32": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _F32, _I32, _F32, _F32, _VP]),

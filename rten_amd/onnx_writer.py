@@ -953,3 +953,49 @@ def decoder_block_graph(hidden: int = 64, heads: int = 4, kv_heads: int = 2, hea
             value_info("present_k", FLOAT, [batch, kv_heads, "total", head_size]), value_info("present_v", FLOAT, [batch, kv_heads, "total", head_size])]
     inits = [tensor(k, v) for k, v in w.items()] + [tensor(k, v) for k, v in shapes.items()]
     return model(nodes, ins, outs, inits, opset=21, name="decoder_block"), w
+
+
+GQA_BLOCK_FORMS = ("rotary_nodes", "do_rotary", "packed")
+
+
+def decoder_block_gqa_graph(form: str = "do_rotary", hidden: int = 64, heads: int = 4, kv_heads: int = 2, head_size: int = 16, ffn: int = 96, max_pos: int = 32,
+                            batch="batch", seq="seq", past="past", seed: int = 61, local_window_size: int = -1, **extra_attrs):
+    """decoder_block_graph with the same weights and outputs, its attention ONE com.microsoft GroupQueryAttention node, as onnxruntime-genai's builder writes
+    it: q / k / v MatMul -> GroupQueryAttention(q, k, v, past_k, past_v, seqlens_k, total_sequence_length[, cos, sin]) -> output projection -> ... (the rest as
+    decoder_block_graph).  Forms: "rotary_nodes" -- q and k go through the separate com.microsoft RotaryEmbedding nodes (one-element `offset` input) and
+    the node has do_rotary = 0; "do_rotary" -- the node rotates (do_rotary = 1, cos / sin inputs); "packed" -- q, k and v are concatenated into one
+    [batch, seq, (heads + 2 kv_heads) * head_size] tensor, key and value are absent, do_rotary = 1.  Inputs: hidden_in, residual_in, past_k, past_v, seqlens_k int32
+    [batch], total_sequence_length int32 scalar (and offset).  -> (model bytes, weights)."""
+    assert form in GQA_BLOCK_FORMS and hidden == heads * head_size and heads % kv_heads == 0
+    rng = np.random.default_rng(seed)
+    f = lambda *s: (rng.standard_normal(s) / np.sqrt(s[0])).astype(np.float32)
+    w = {"ln1_g": (1.0 + 0.1 * rng.standard_normal(hidden)).astype(np.float32), "ln2_g": (1.0 + 0.1 * rng.standard_normal(hidden)).astype(np.float32),
+         "wq": f(hidden, heads * head_size), "wk": f(hidden, kv_heads * head_size), "wv": f(hidden, kv_heads * head_size), "wo": f(hidden, hidden),
+         "w_gate": f(hidden, ffn), "w_up": f(hidden, ffn), "w_down": f(ffn, hidden)}
+    w["cos"], w["sin"] = rotary_caches(max_pos, head_size // 2)
+    nodes = [node("SkipSimplifiedLayerNormalization", ["hidden_in", "residual_in", "ln1_g"], ["n1", "", "", "res1"], name="input_norm", domain=MS, epsilon=1e-6),
+             node("MatMul", ["n1", "wq"], ["q"], name="q_proj"), node("MatMul", ["n1", "wk"], ["k"], name="k_proj"), node("MatMul", ["n1", "wv"], ["v"], name="v_proj")]
+    attrs = dict(num_heads=heads, kv_num_heads=kv_heads, local_window_size=local_window_size, **extra_attrs)  # extra_attrs: e.g. smooth_softmax=1 for a refusal
+    tail = ["past_k", "past_v", "seqlens_k", "total_sequence_length"]
+    if form == "rotary_nodes":
+        nodes += [node("RotaryEmbedding", ["q", "offset", "cos", "sin"], ["q_rot"], name="q_rope", domain=MS, num_heads=heads),
+                  node("RotaryEmbedding", ["k", "offset", "cos", "sin"], ["k_rot"], name="k_rope", domain=MS, num_heads=kv_heads),
+                  node("GroupQueryAttention", ["q_rot", "k_rot", "v"] + tail, ["ctx", "present_k", "present_v"], name="attention", domain=MS, **attrs)]
+    elif form == "do_rotary":
+        nodes += [node("GroupQueryAttention", ["q", "k", "v"] + tail + ["cos", "sin"], ["ctx", "present_k", "present_v"], name="attention", domain=MS, do_rotary=1, **attrs)]
+    else:
+        nodes += [node("Concat", ["q", "k", "v"], ["qkv"], name="pack_qkv", axis=2),
+                  node("GroupQueryAttention", ["qkv", "", ""] + tail + ["cos", "sin"], ["ctx", "present_k", "present_v"], name="attention", domain=MS, do_rotary=1, **attrs)]
+    nodes += [node("MatMul", ["ctx", "wo"], ["attn_out"], name="o_proj"),
+              node("SkipSimplifiedLayerNormalization", ["attn_out", "res1", "ln2_g"], ["n2", "", "", "residual_out"], name="post_attention_norm", domain=MS, epsilon=1e-6),
+              node("MatMul", ["n2", "w_gate"], ["gate"], name="gate_proj"), node("MatMul", ["n2", "w_up"], ["up"], name="up_proj"),
+              node("Silu", ["gate"], ["gate_act"], name="act"), node("Mul", ["gate_act", "up"], ["gated"], name="gated"),
+              node("MatMul", ["gated", "w_down"], ["mlp_out"], name="down_proj")]
+    ins = [value_info("hidden_in", FLOAT, [batch, seq, hidden]), value_info("residual_in", FLOAT, [batch, seq, hidden]),
+           value_info("past_k", FLOAT, [batch, kv_heads, past, head_size]), value_info("past_v", FLOAT, [batch, kv_heads, past, head_size]),
+           value_info("seqlens_k", INT32, [batch]), value_info("total_sequence_length", INT32, [])]
+    if form == "rotary_nodes":
+        ins.append(value_info("offset", INT64, [1]))
+    outs = [value_info("mlp_out", FLOAT, [batch, seq, hidden]), value_info("residual_out", FLOAT, [batch, seq, hidden]),
+            value_info("present_k", FLOAT, [batch, kv_heads, "total", head_size]), value_info("present_v", FLOAT, [batch, kv_heads, "total", head_size])]
+    return model(nodes, ins, outs, [tensor(k, v) for k, v in w.items()], opset=21, name="decoder_block_gqa"), w

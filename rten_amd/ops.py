@@ -2952,6 +2952,207 @@ class RotaryEmbeddingMicrosoft(Operator):
         return [rotary_embedding(ctx, x, cos, sin, ids, offset, self.interleaved, num_heads, self.rotary_embedding_dim)]
 
 
+def _shape_of(t):
+    return tuple(t.shape) if isinstance(t, DeviceTensor) else tuple(np.shape(t))
+
+
+def _int32_operand(ctx, t):
+    """An int32 input that may arrive as a host value (numpy / int: validated by the caller, then uploaded) or as device data -> (host array | None, DeviceTensor)."""
+    if isinstance(t, DeviceTensor):
+        return None, _want(t, np.int32)
+    a = np.asarray(t)
+    if a.dtype.kind not in "iu":
+        raise OpError("InputCastFailed", "expected int32 tensor")
+    a = np.ascontiguousarray(a.astype(np.int32))
+    return a, DeviceTensor.from_numpy(ctx, a.reshape(-1))
+
+
+class GroupQueryAttention(Operator):
+    """com.microsoft.GroupQueryAttention with a KV cache, src/ops/attention/contrib.rs:419-878 (rten_hip_gqa_f32: one prepare-and-append launch, then the
+    one-launch decode kernel or GEMM, score kernel, GEMM).  inputs: query [B, S, H * D] (packed [B, S, (H + 2 KV) * D] with key and value absent), key,
+    value [B, S, KV * D], past_key, past_value [B, KV, P, D], seqlens_k int32 [B] or [B, 1], total_sequence_length int32 scalar, cos_cache, sin_cache
+    [max, rot / 2], position_ids int32 [B, S], attention_bias [B | 1, H | 1, >= S, >= P + S], head_sink (refused).  query may be an einsum.View with a unit
+    stride along its last axis (a fused projection's column block), read in place.
+    Loader defaults (onnx_registry.rs:1467-1492): scale None (1 / sqrt(D)), do_rotary, rotary_interleaved and smooth_softmax false, local_window_size -1 (a
+    non-positive size disables the window), softcap 0.
+    seqlens_k and total_sequence_length that arrive as host values are validated here with the reference's errors (contrib.rs:582-639); DeviceTensors stay on
+    the device, where the kernels clamp kv_len into [1, P + S] and past_len into [0, P] instead.  `outputs`: the requested output indices; present_key /
+    present_value are RETURNED only when 1 or 2 is among them (contrib.rs:803-807) -- they are always computed, because the attention kernels read K and V
+    out of them.
+    Not built: softcap != 0 (the reference calls libm's tanh there), smooth_softmax, head_sink."""
+
+    def __init__(self, num_heads, kv_num_heads, scale=None, do_rotary=False, rotary_interleaved=False, local_window_size=-1, softcap=0.0, smooth_softmax=False):
+        self.num_heads, self.kv_num_heads, self.scale = int(num_heads), int(kv_num_heads), scale
+        self.do_rotary, self.rotary_interleaved = bool(do_rotary), bool(rotary_interleaved)
+        lw = -1 if local_window_size is None else int(local_window_size)
+        self.local_window_size = lw if lw > 0 else None
+        self.softcap, self.smooth_softmax = float(softcap), bool(smooth_softmax)
+
+    def name(self):
+        return "com.microsoft.GroupQueryAttention"
+
+    def max_inputs(self):
+        return 12
+
+    def max_outputs(self):
+        return 3
+
+    def run(self, ctx, inputs, outputs=(0, 1, 2)):
+        from . import einsum as E
+        query = _require(inputs, 0)
+        qv = query if isinstance(query, E.View) else E.View(query)
+        _want(qv.t, np.float32)
+        if len(qv.shape) != 3:
+            raise OpError("InputCastFailed", "expected tensor with 3 dims")
+        if qv.shape[-1] > 1 and qv.strides[-1] != 1:
+            qv = E.View(E.materialize(ctx, qv))
+        key, value = _get(inputs, 1), _get(inputs, 2)
+        past_key, past_value = _get(inputs, 3), _get(inputs, 4)
+        seqlens, total = _require(inputs, 5), _require(inputs, 6)
+        cos, sin, position_ids, bias, head_sink = (_get(inputs, i) for i in range(7, 12))
+        for t in (key, value):
+            if t is not None:
+                _want(t, np.float32)
+                if len(t.shape) != 3:
+                    raise OpError("InputCastFailed", "expected tensor with 3 dims")
+        sl_shape = list(_shape_of(seqlens))
+        while len(sl_shape) > 1 and sl_shape[-1] == 1:
+            sl_shape.pop()
+        if len(sl_shape) != 1:
+            raise UnsupportedValue("seqlens_k must be a vector")
+        if len(_shape_of(total)) != 0 and not (isinstance(total, DeviceTensor) and total.size == 1):
+            raise OpError("InputCastFailed", "expected tensor with 0 dims")
+        if head_sink is not None:
+            raise UnsupportedValue("head_sink is not supported")
+        if self.smooth_softmax:
+            raise UnsupportedValue("smooth_softmax is not supported")
+        H, KV = self.num_heads, self.kv_num_heads
+        if H <= 0 or KV <= 0:
+            raise InvalidValue("num_heads and kv_num_heads must be positive")
+        if H % KV != 0:
+            raise InvalidValue("num_heads must be a multiple of kv_num_heads")
+        batch, seq, q_hidden = qv.shape
+        qb = qv.t.ptr
+        if key is not None and value is not None:
+            if q_hidden % H != 0:
+                raise IncompatibleInputShapes("query hidden size must be divisible by num_heads")
+            D = q_hidden // H
+            key, value = _dense(ctx, key), _dense(ctx, value)
+            if key.shape[0] != batch or value.shape[0] != batch:
+                raise IncompatibleInputShapes("key and value batch size must match query")
+            if tuple(key.shape[1:]) != tuple(value.shape[1:]):
+                raise IncompatibleInputShapes("key and value must have the same shape")
+            if key.shape[2] != KV * D:
+                raise IncompatibleInputShapes("key hidden size must equal kv_num_heads * head_size")
+            if key.shape[1] != seq:
+                raise UnsupportedValue("key sequence length must match query sequence length")
+            ptrs = (qb, key.ptr, value.ptr)
+            kvst = (seq * KV * D, KV * D, D)
+            strides = [qv.strides[0], qv.strides[1], D, *kvst, *kvst]
+        elif key is None and value is None:
+            if q_hidden % (H + 2 * KV) != 0:
+                raise IncompatibleInputShapes("packed query hidden size must be divisible by num_heads + 2 * kv_num_heads")
+            D = q_hidden // (H + 2 * KV)
+            ptrs = (qb, qb + 4 * H * D, qb + 4 * (H + KV) * D)
+            strides = [qv.strides[0], qv.strides[1], D] * 3
+        else:
+            raise InvalidValue("key and value must both be present or both absent")
+        if sl_shape[0] != batch:
+            raise IncompatibleInputShapes("seqlens_k must have batch_size elements")
+        total_host, total_dev = _int32_operand(ctx, total)
+        if total_host is not None and int(total_host.reshape(())) <= 0:
+            raise InvalidValue("total_sequence_length must be positive")
+        if past_key is not None and past_value is not None:
+            past_key, past_value = _dense(ctx, _want(past_key, np.float32)), _dense(ctx, _want(past_value, np.float32))
+            if len(past_key.shape) != 4 or len(past_value.shape) != 4:
+                raise OpError("InputCastFailed", "expected tensor with 4 dims")
+            if tuple(past_key.shape) != tuple(past_value.shape) or tuple(past_key.shape[:2]) != (batch, KV) or past_key.shape[3] != D:
+                raise IncompatibleInputShapes("past_key/past_value shape does not match")
+            past_seq = past_key.shape[2]
+        elif past_key is None and past_value is None:
+            past_seq = 0
+        else:
+            raise InvalidValue("past_key and past_value must both be present or both absent")
+        present_seq = past_seq + seq
+        seqlens_host, seqlens_dev = _int32_operand(ctx, seqlens)
+        if total_host is not None:
+            tot = int(total_host.reshape(()))
+            first, subsequent = seq == tot, seq > 1 and seq != tot
+            if subsequent and batch != 1:
+                raise UnsupportedValue("batch size must be 1 when sequence_length > 1 and a past context is given")
+            if not first and not subsequent and seq != 1:
+                raise InvalidValue("sequence_length must be 1 when query is not a prompt")
+        if seqlens_host is not None:
+            for n in seqlens_host.reshape(-1):
+                if n < 0 or n >= present_seq:
+                    raise InvalidValue("seqlens_k entry is out of range")
+                if n + 1 < seq:
+                    raise InvalidValue("seqlens_k entry is too small for the query sequence length")
+        bias_strides = [0, 0, 0]
+        if bias is not None:
+            bias = _dense(ctx, _want(bias, np.float32))
+            if len(bias.shape) != 4:
+                raise OpError("InputCastFailed", "expected tensor with 4 dims")
+            bb, bh, bs, bt = bias.shape
+            if (bb != 1 and bb != batch) or (bh != 1 and bh != H) or bs < seq or bt < present_seq:
+                raise IncompatibleInputShapes("attention_bias shape is incompatible with query/key shapes")
+            bias_strides = [0 if bb == 1 else bh * bs * bt, 0 if bh == 1 else bs * bt, bt]
+        scale = self.scale
+        if scale is None:
+            scale = float(np.float32(1.0) / np.sqrt(np.float32(D))) if D else 0.0
+        rot, max_pos = 0, 0
+        if self.do_rotary:
+            if cos is None or sin is None:
+                raise InvalidValue("cos_cache and sin_cache are required when do_rotary is set")
+            cos, sin = _dense(ctx, _want(cos, np.float32)), _dense(ctx, _want(sin, np.float32))
+            if len(cos.shape) != 2 or len(sin.shape) != 2:
+                raise OpError("InputCastFailed", "expected tensor with 2 dims")
+            rot = 2 * cos.shape[1]
+            if rot == 0 or rot % 2 != 0:
+                raise InvalidValue("rotary_embedding_dim must be a positive even number")
+            if rot > D:
+                raise InvalidValue("rotary_embedding_dim must not exceed head size")
+            if sin.shape[1] != cos.shape[1]:
+                raise InvalidValue("Last dimension of sin cache does not match rotary_embedding_dim/2")
+            if cos.shape[0] != sin.shape[0]:
+                raise UnsupportedValue("device path needs cos and sin caches of one length")
+            max_pos = cos.shape[0]
+            if position_ids is not None:
+                ids_host, position_ids = _int32_operand(ctx, position_ids)
+                if ids_host is not None:
+                    if ids_host.ndim != 2:
+                        raise OpError("InputCastFailed", "expected tensor with 2 dims")
+                    if ids_host.shape[1] not in (1, seq):
+                        raise InvalidValue("cos/sin cache sequence length must be 1 or match the input")
+                    if ids_host.shape[0] not in (1, batch):
+                        raise InvalidValue("cos/sin cache batch size must be 1 or match the input")
+                    if ids_host.size and (ids_host.min() < -max_pos or ids_host.max() >= max_pos):
+                        raise InvalidValue("Entry in `indices` is out of range")
+                    position_ids = DeviceTensor.from_numpy(ctx, np.ascontiguousarray(np.broadcast_to(ids_host, (batch, seq))))
+                elif tuple(position_ids.shape) != (batch, seq):
+                    raise UnsupportedValue("device position_ids must have the input's [batch, seq] shape")
+            elif seqlens_host is not None and total_host is not None and max_pos > 0:
+                tot = int(total_host.reshape(()))
+                last = seq - 1 if seq == tot else int(seqlens_host.max(initial=0))
+                if last >= max_pos:
+                    raise InvalidValue("Entry in `indices` is out of range")
+        else:
+            cos = sin = position_ids = None
+        if self.softcap != 0.0:
+            raise UnsupportedValue("softcap is not supported")
+        out = DeviceTensor(ctx, (batch, seq, H * D), np.float32)
+        present_key = DeviceTensor(ctx, (batch, KV, present_seq, D), np.float32)
+        present_value = DeviceTensor(ctx, (batch, KV, present_seq, D), np.float32)
+        if out.size and KV * D:
+            dims = (C.c_int32 * L.GQA_NDIMS)(batch, seq, H, KV, D, past_seq, rot, 1 if self.rotary_interleaved else 0, max_pos, self.local_window_size or 0)
+            st = (C.c_int64 * L.GQA_NSTRIDES)(*strides, *bias_strides)
+            ctx.call("rten_hip_gqa_f32", dims, st, scale, *(C.c_void_p(p) for p in ptrs), _vp(past_key), _vp(past_value), seqlens_dev.vp, total_dev.vp,
+                     _vp(cos), _vp(sin), _vp(position_ids) if self.do_rotary else None, _vp(bias), out.vp, present_key.vp, present_value.vp)
+        if 1 in outputs or 2 in outputs:
+            return [out, present_key, present_value]
+        return [out]
+
+
 class OpRegistry:
     """Mirror of OpRegistry (src/op_registry.rs:25-72): op_type -> operator class for the hot path."""
 
@@ -2968,7 +3169,7 @@ class OpRegistry:
                    Pow, PRelu, Min, Max, Sum, Mean, Pad, QuantizeLinear, DequantizeLinear, ReduceL1, ReduceL2, ReduceSumSquare, ReduceLogSum, ReduceLogSumExp,
                    ReduceProd, LpNormalization, GlobalMaxPool, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile,
                    NonMaxSuppression, DFT, STFT, RMSNormalization, SimplifiedLayerNormalization, SkipLayerNormalization,
-                   SkipSimplifiedLayerNormalization, RotaryEmbedding, RotaryEmbeddingMicrosoft):
+                   SkipSimplifiedLayerNormalization, RotaryEmbedding, RotaryEmbeddingMicrosoft, GroupQueryAttention):
             r.register_op(op)
         return r
 

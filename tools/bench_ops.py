@@ -641,6 +641,77 @@ def main():
                 (lambda: ctx.call("rten_hip_copy_strided_b32", 2, (C.c_int64 * 2)(b_ * s_, h_ * d_), (C.c_int64 * 2)(h_ * d_, 1), xq.vp, yq.vp)), 8.0 * b_ * s_ * h_ * d_)
             del xq, yq
 
+    # ---- GroupQueryAttention with a KV cache (rten_amd/csrc/gqa.hip; --only gqa: selects these rows): decode at H 32 / KV 8 / D 128 on a cache of
+    # kv_len - 1 rows, the whole call (prepare-and-append launch + attention) on the decode kernel and on the composed path, beside (a) what such a
+    # graph ran on before -- two strided copies for the concatenation, then rten_hip_sdpa_f32 with one query row on K and V expanded to 32 heads -- and
+    # (b) one strided copy of the K and V bytes, the yardstick.  Then one first prompt of 2048 tokens.  Operands are zeros: the timing does not read values.
+    if want("gqa:"):
+        h_, kv_, d_ = 32, 8, 128
+
+        def zeros(*shape, dt=np.float32):
+            t_ = empty(shape, dt)
+            ctx.call("rten_hip_memset", t_.vp, 0, C.c_size_t(t_.size * 4))
+            return t_
+
+        for b_ in (1, 32):
+            for kvl in (512, 2048, 4096):
+                p_ = kvl - 1
+                q_, k_, v_ = zeros(b_, 1, h_ * d_), zeros(b_, 1, kv_ * d_), zeros(b_, 1, kv_ * d_)
+                pk_, pv_, ok_, ov_ = zeros(b_, kv_, p_, d_), zeros(b_, kv_, p_, d_), zeros(b_, kv_, kvl, d_), zeros(b_, kv_, kvl, d_)
+                o_ = zeros(b_, 1, h_ * d_)
+                sl_, tot_ = dev(np.full(b_, kvl - 1, np.int32)), dev(np.array([kvl], np.int32))
+                dims = (C.c_int32 * L.GQA_NDIMS)(b_, 1, h_, kv_, d_, p_, 0, 0, 0, 0)
+                st_ = (C.c_int64 * L.GQA_NSTRIDES)(h_ * d_, h_ * d_, d_, kv_ * d_, kv_ * d_, d_, kv_ * d_, kv_ * d_, d_, 0, 0, 0)
+                shape = f"batch={b_} kv_len={kvl} heads={h_} kv_heads={kv_} head_size={d_}"
+                kv_bytes = 8.0 * b_ * kv_ * kvl * d_
+                call = (lambda: ctx.call("rten_hip_gqa_f32", dims, st_, 0.0883883461, q_.vp, k_.vp, v_.vp, pk_.vp, pv_.vp, sl_.vp, tot_.vp, None, None, None, None,
+                                         o_.vp, ok_.vp, ov_.vp))
+                for pname, path in (("decode kernel", 2), ("composed path", 1), ("dispatch rule", 0)):
+                    ctx.call("rten_hip_set_gqa_path", path)
+                    hbm(f"gqa: decode, whole call ({pname})", shape, call, 3 * kv_bytes)
+                ctx.call("rten_hip_set_gqa_path", 0)
+                ke_, ve_ = zeros(b_, h_, kvl, d_), zeros(b_, h_, kvl, d_)
+                sd_ = L.SdpaDesc(b_, h_, 1, kvl, d_, d_, h_ * d_, d_, h_ * d_, h_ * kvl * d_, kvl * d_, d_, h_ * kvl * d_, kvl * d_, d_, h_ * d_, d_, h_ * d_, 0, 0,
+                                 0.0883883461, 1)
+                csh, cst = (C.c_int64 * 2)(b_ * kv_ * p_, d_), (C.c_int64 * 2)(d_, 1)
+
+                def parent_route():
+                    ctx.call("rten_hip_copy_strided_b32", 2, csh, cst, pk_.vp, ok_.vp)
+                    ctx.call("rten_hip_copy_strided_b32", 2, csh, cst, pv_.vp, ov_.vp)
+                    ctx.call("rten_hip_sdpa_f32", C.byref(sd_), q_.vp, ke_.vp, ve_.vp, None, o_.vp)
+                hbm("gqa: (a) two concatenation copies + rten_hip_sdpa_f32 on K, V expanded to 32 heads (what ran before)", shape, parent_route, 3 * kv_bytes)
+                bsh = (C.c_int64 * 2)(2 * b_ * kv_ * p_, d_)
+                hbm("gqa: (b) one strided copy of the K and V bytes (yardstick)", shape,
+                    (lambda: ctx.call("rten_hip_copy_strided_b32", 2, bsh, cst, ke_.vp, ve_.vp)), 2 * kv_bytes)
+                del q_, k_, v_, pk_, pv_, ok_, ov_, o_, ke_, ve_
+        # first prompts of 128 / 512 / 2048 tokens: the whole call (prepare launch + GEMM, score kernel, GEMM) beside rten_hip_sdpa_f32 on the same queries with
+        # K and V expanded to 32 heads and a causal [1, 1, S, S] mask -- its automatic choice (the one-kernel form up to 128 keys, else its own GEMM, softmax,
+        # GEMM) and, where it covers the shape (<= 512 keys), the one-kernel form forced.  This is the comparison behind NOT extending the fused kernels here.
+        for s_ in (128, 512, 2048):
+            q_, k_, v_, o_ = zeros(1, s_, h_ * d_), zeros(1, s_, kv_ * d_), zeros(1, s_, kv_ * d_), zeros(1, s_, h_ * d_)
+            ok_, ov_ = zeros(1, kv_, s_, d_), zeros(1, kv_, s_, d_)
+            sl_, tot_ = dev(np.array([s_ - 1], np.int32)), dev(np.array([s_], np.int32))
+            dims = (C.c_int32 * L.GQA_NDIMS)(1, s_, h_, kv_, d_, 0, 0, 0, 0, 0)
+            st_ = (C.c_int64 * L.GQA_NSTRIDES)(s_ * h_ * d_, h_ * d_, d_, s_ * kv_ * d_, kv_ * d_, d_, s_ * kv_ * d_, kv_ * d_, d_, 0, 0, 0)
+            shape = f"batch=1 seq={s_} heads={h_} kv_heads={kv_} head_size={d_}"
+            flops = 4.0 * h_ * s_ * s_ * d_
+            mfma("gqa: first prompt, whole call (composed path)", shape,
+                 (lambda: ctx.call("rten_hip_gqa_f32", dims, st_, 0.0883883461, q_.vp, k_.vp, v_.vp, None, None, sl_.vp, tot_.vp, None, None, None, None, o_.vp, ok_.vp,
+                                   ov_.vp)), flops, F32_PEAK_TF, "TFLOP/s")
+            ke_, ve_ = zeros(1, h_, s_, d_), zeros(1, h_, s_, d_)
+            mask_ = dev(np.triu(np.full((s_, s_), -np.inf, np.float32), 1).reshape(1, 1, s_, s_))
+            sd_ = L.SdpaDesc(1, h_, s_, s_, d_, d_, s_ * h_ * d_, d_, h_ * d_, h_ * s_ * d_, s_ * d_, d_, h_ * s_ * d_, s_ * d_, d_, s_ * h_ * d_, d_, h_ * d_, s_ * s_, s_,
+                             0.0883883461, 1)
+            for pname, path in (("automatic", 0), ("one-kernel form forced", 2)):
+                if path == 2 and s_ > 512:
+                    continue
+                if want("gqa:"):
+                    ctx.call("rten_hip_set_sdpa_path", path)
+                mfma(f"gqa: rten_hip_sdpa_f32 on 32 expanded heads with a causal mask ({pname})", shape,
+                     (lambda: ctx.call("rten_hip_sdpa_f32", C.byref(sd_), q_.vp, ke_.vp, ve_.vp, mask_.vp, o_.vp)), flops, F32_PEAK_TF, "TFLOP/s")
+            ctx.call("rten_hip_set_sdpa_path", 0)
+            del q_, k_, v_, o_, ok_, ov_, ke_, ve_, mask_
+
     if args.cpu_baseline:
         sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         import bench  # the oracle is only ever touched through bench.py's cpu_baseline leg

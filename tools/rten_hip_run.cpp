@@ -249,6 +249,17 @@ int main(int argc, char **argv) {
             }
         }
         {
+            const onnx::Model c = Graph::canonical_form(m); // GroupQueryAttention: the loader's checks and what the step will be handed
+            for (const onnx::Node &n : c.nodes) {
+                if (!Graph::is_gqa_node(n)) continue;
+                const Graph::GqaNode a = Graph::read_gqa_node(c, n, n.name.empty() ? n.outputs.at(0) : n.name);
+                std::printf("  attention step com.microsoft.GroupQueryAttention \"%s\": num_heads %" PRId64 ", kv_num_heads %" PRId64 ", %s, rotary %s, window %s, present caches %s\n",
+                            n.name.c_str(), a.num_heads, a.kv_num_heads, a.packed ? "packed QKV" : "separate q / k / v",
+                            a.do_rotary ? (a.rotary_interleaved ? "interleaved" : "in halves") : "off", a.local_window_size > 0 ? std::to_string(a.local_window_size).c_str() : "none",
+                            a.want_present ? "read" : "not read");
+            }
+        }
+        {
             const onnx::Model c = Graph::canonical_form(m); // QuantizeLinear / DequantizeLinear: the loader's checks, and the pairs that become one round-trip step
             std::vector<bool> taken(c.nodes.size(), false);
             for (size_t i = 0; i < c.nodes.size(); i++) {
