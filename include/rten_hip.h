@@ -50,7 +50,8 @@
 extern "C" {
 #endif
 
-/* v8, later additions without a bump: + rten_hip_gqa_f32, rten_hip_set_gqa_path (GroupQueryAttention with a KV cache; dims and strides as host arrays).
+/* v8, later additions without a bump: + rten_hip_gqa_f32, rten_hip_set_gqa_path (GroupQueryAttention with a KV cache; dims and strides as host arrays);
+ * + rten_hip_set_gqa_split and mode 3 of rten_hip_set_gqa_path (the decode form that spreads the key range over workgroups).
  * v8 (round 6, third part): + rten_hip_conv2d_f32_pair / _pair_supported (an expand layer and the next block's reduce layer in one launch; a launch plan
  * lists the pairs: "pairs"), rten_hip_conv2d_f32_pair_shortcut / _supported (the same with the block's shortcut convolution computed in the launch: "pair_shortcuts");
  * GEMM variant 32 (the direct stem kernel); rten_hip_model_plan_json also names the load-time lists.
@@ -472,7 +473,13 @@ int32_t rten_hip_rotary_embedding_f32(rten_hip_ctx *ctx, int32_t batch, int32_t 
  * rten_hip_rotary_embedding_f32); a host that knows the values validates them itself (contrib.rs:582-639).
  * One query row with the gemv order on, D 64 or 128 and 4 * ((H / KV) * (P + 1 + D) + 8192) bytes of LDS <= 160 KiB takes the one-launch decode kernel (a
  * workgroup per (batch, KV head) that reads each K and V row once for the whole group); everything else takes GEMM, score kernel, GEMM with the group as
- * the inner batch level, in passes of at most 64 MiB of scores (one query row in the gemv order with D > 512: RTEN_HIP_ERR_UNSUPPORTED).  rten_hip_set_gqa_path: 0 that rule, 1 the composed path only, 2 the decode kernel or RTEN_HIP_ERR_UNSUPPORTED. */
+ * the inner batch level, in passes of at most 64 MiB of scores (one query row in the gemv order with D > 512: RTEN_HIP_ERR_UNSUPPORTED).
+ * The split decode form covers the same calls without the LDS bound: the key range of a (batch, KV head) is spread over workgroups of keys_per_workgroup
+ * keys, score rows and 8-key block sums live in scratch (at most 64 MiB per pass over the (batch, KV head) pairs, or one pair's rows), and the result has the
+ * same bits for every split.  The rule takes it where the decode kernel's LDS does not fit, and where B * KV workgroups under-fill the device at a cache long
+ * enough to pay for its extra launches.  rten_hip_set_gqa_path: 0 that rule, 1 the composed path only, 2 the decode kernel or RTEN_HIP_ERR_UNSUPPORTED, 3 the
+ * split decode form or RTEN_HIP_ERR_UNSUPPORTED (it takes one query row in the gemv order and head size 64 or 128).  rten_hip_set_gqa_split: the split
+ * form's keys per workgroup, 0 (the rule, from B, KV and P) or a positive multiple of 8; anything else is RTEN_HIP_ERR_INVALID_VALUE. */
 #define RTEN_HIP_GQA_NDIMS 10
 #define RTEN_HIP_GQA_NSTRIDES 12
 int32_t rten_hip_gqa_f32(rten_hip_ctx *ctx, const int32_t *dims, const int64_t *strides, float scale, const float *q, const float *k, const float *v,
@@ -480,6 +487,7 @@ int32_t rten_hip_gqa_f32(rten_hip_ctx *ctx, const int32_t *dims, const int64_t *
                          const float *cos, const float *sin, const int32_t *position_ids, const float *attention_bias, float *out,
                          float *present_key, float *present_value);
 int32_t rten_hip_set_gqa_path(rten_hip_ctx *ctx, int32_t mode);
+int32_t rten_hip_set_gqa_split(rten_hip_ctx *ctx, int32_t keys_per_workgroup);
 /* BatchNormalization (inference), src/ops/norm.rs:194-224 */
 int32_t rten_hip_batch_norm_f32(rten_hip_ctx *ctx, int32_t n, int32_t c, int64_t inner, const float *x,
                                 const float *scale, const float *bias, const float *mean, const float *var,

@@ -10,7 +10,7 @@
 // seqlens_k and total are read on the device by every kernel here (lens()), clamped so that no access leaves a buffer: kv_len into [1, P + S], past_len
 // into [0, P].  Nothing is read back, so a call captures and a replay follows new device values.
 //
-// Three kernels:
+// The kernels of this unit (gqa_split.hip holds the second decode form):
 //   * gqa_prepare_kernel: one launch writes both present caches (zero rows included) and, with rotary, the rotated Q into scratch; K is rotated while it
 //     is written.  Rotary is rot1 of decoder.hip: every product and sum rounded on its own; the cache row is gathered as RotaryEmbedding gathers it.
 //   * gqa_decode_kernel<D> (S == 1, gemv order on, D 64 / 128): one workgroup of 1024 threads per (batch, KV head) serves the G query heads of the group, so
@@ -27,6 +27,12 @@
 //       read.
 //     LDS: 4 * (G * D [q] + 8192 [block sums: 1024 / D slots x 8 heads x D] + G * (P + 1) [score rows]) bytes, which must fit the 160 KiB a single
 //     workgroup may declare on this part.  G = 4, D = 128: P + 1 <= 8064 keys.
+//   * the split decode form (gqa_split.hip; same coverage without the LDS bound): the key range of one (batch, KV head) spread over workgroups of
+//     keys_per_workgroup keys, score rows and 8-key block sums in scratch, four dependent launches (scores, softmax sums, PV block sums, ordered fold) in
+//     the orders above, so the bits do not depend on the split.  Mode 0 takes it when the one-workgroup kernel's LDS does not fit, and when B * KV
+//     workgroups under-fill the device at a cache long enough to pay for the extra launches (rten_gqa_split_pays).  Its scratch follows the rotated Q in
+//     rten_aux_scratch: with Tp = T rounded up to 64, NB = ceil(T / 8) and U = clamp(64 MiB / (4 G (Tp + NB D)), 1, B KV) units per pass,
+//     round_up(U G, 64) + U G Tp + U G NB D floats.
 //   * gqa_scores_kernel: the score modification and softmax for the composed path (GEMM, this kernel, GEMM; the group is the GEMMs' inner batch level with
 //     stride 0 on K and V, so nothing is expanded).  It works on all P + S columns: columns at or beyond lim are -inf, contribute exp = 0 to the lane sums
 //     and probability 0 to PV, which walks the zero rows of present beyond kv_len: x + 0 and fmaf(0, 0, x) change nothing but the sign of a zero.  The
@@ -36,46 +42,11 @@
 //     gemv entry on P + 1 columns: which keys are a column block's left-overs follows the DEVICE kv_len, as in the reference, so a right-padded item keeps the
 //     reference's bits.  PV is the gemv entry over P + 1 keys; the keys beyond kv_len have probability 0 and zero rows, and a chain that starts at +0
 //     cannot be moved by +-0 addends.  (Head sizes above 512 would need the depth-block beta step: refused.)
-#include "internal.h"
+#include "gqa_common.h"
 #include "rowreduce.h"
 #include "vecmath.h"
 
 namespace {
-
-struct GqaArgs {
-    int B, S, H, KV, D, P, T, G; // T = P + S
-    int rot, interleaved, max_pos, local;
-    int s0, SC; // composed path: the query rows [s0, s0 + SC) of this pass; scores is [B, H, SC, T]
-    long long gemv_threads;
-    int64_t q_sb, q_ss, q_sh, k_sb, k_ss, k_sh, v_sb, v_ss, v_sh, bias_sb, bias_sh, bias_sr;
-    const float *q, *k, *v, *past_k, *past_v, *cos, *sin, *bias;
-    const int32_t *seqlens, *total, *pos;
-    float *qr;       // rotated Q [B, S, H, D] (rotary only)
-    float *pk, *pv;  // present [B, KV, T, D]
-    float *scores;   // composed path: [B, H, S, T]
-    float *out;      // [B, S, H * D]
-    float scale;
-};
-
-__device__ __forceinline__ void lens(const GqaArgs &p, int b, int &kv_len, int &past_len) {
-    long long kv = (long long)p.seqlens[b] + 1;
-    kv = kv < 1 ? 1 : (kv > p.T ? p.T : kv);
-    long long pl = p.total[0] == p.S ? 0 : kv - p.S;
-    pl = pl < 0 ? 0 : (pl > p.P ? p.P : pl);
-    kv_len = (int)kv;
-    past_len = (int)pl;
-}
-
-__device__ __forceinline__ int past_len_of(const GqaArgs &p, int b) {
-    int kv_len, past_len;
-    lens(p, b, kv_len, past_len);
-    return past_len;
-}
-
-__device__ __forceinline__ void window(const GqaArgs &p, int past_len, int s, int &start, int &lim) {
-    lim = past_len + s + 1;
-    start = (p.local > 0 && lim > p.local) ? lim - p.local : 0;
-}
 
 // element i of token (b, s), head h of x after rotary (embedding.rs:144-194; rot1 of decoder.hip)
 __device__ __forceinline__ float rotated(const GqaArgs &p, const float *xr, int b, int s, int past_len, int i) {
@@ -373,8 +344,16 @@ int32_t launch_decode(rten_hip_ctx *ctx, const GqaArgs &a, size_t lds) {
 
 RTEN_EXPORT int32_t rten_hip_set_gqa_path(rten_hip_ctx *ctx, int32_t mode) {
     RTEN_CHECK_CTX(ctx);
-    if (mode < 0 || mode > 2) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "set_gqa_path: mode must be 0, 1 or 2");
+    if (mode < 0 || mode > 3) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "set_gqa_path: mode must be 0, 1, 2 or 3");
     ctx->gqa_path = mode;
+    return RTEN_HIP_OK;
+}
+
+RTEN_EXPORT int32_t rten_hip_set_gqa_split(rten_hip_ctx *ctx, int32_t keys_per_workgroup) {
+    RTEN_CHECK_CTX(ctx);
+    if (keys_per_workgroup < 0 || keys_per_workgroup % 8 != 0)
+        return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "set_gqa_split: keys_per_workgroup must be 0 (the rule) or a positive multiple of 8");
+    ctx->gqa_split = keys_per_workgroup;
     return RTEN_HIP_OK;
 }
 
@@ -411,9 +390,13 @@ RTEN_EXPORT int32_t rten_hip_gqa_f32(rten_hip_ctx *ctx, const int32_t *dims, con
     const bool covered = one_row && (a.D == 64 || a.D == 128) && lds <= LDS_PER_WORKGROUP;
     if (ctx->gqa_path == 2 && !covered)
         return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "gqa: the decode kernel takes one query row in the gemv order, head size 64 or 128 and rows that fit LDS");
-    const bool fused = covered && ctx->gqa_path != 1;
+    const bool splittable = one_row && (a.D == 64 || a.D == 128);
+    if (ctx->gqa_path == 3 && !splittable)
+        return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "gqa: the split decode form takes one query row in the gemv order and head size 64 or 128");
+    const bool split = splittable && (ctx->gqa_path == 3 || (ctx->gqa_path == 0 && (!covered || rten_gqa_split_pays(ctx, a))));
+    const bool fused = covered && ctx->gqa_path != 1 && !split;
 
-    // scratch: [rotated Q | scores], the auxiliary buffer (the GEMMs called below own `scratch`).  The composed path works through the query rows in passes
+    // scratch: [rotated Q | scores, or the split form's rows and block sums], the auxiliary buffer (the GEMMs called below own `scratch`).  The composed path works through the query rows in passes
     // of SC rows so that the score buffer [B, H, SC, T] stays within SCORE_PASS_BYTES whatever the prompt length (rows are independent of one another).
     const size_t q_elems = a.rot > 0 ? (size_t)a.B * a.S * a.H * a.D : 0;
     const size_t q_pad = (q_elems + 63) / 64 * 64;
@@ -421,7 +404,7 @@ RTEN_EXPORT int32_t rten_hip_gqa_f32(rten_hip_ctx *ctx, const int32_t *dims, con
     size_t sc_rows = SCORE_PASS_BYTES / sizeof(float) / row_elems;
     sc_rows = sc_rows < 1 ? 1 : (sc_rows > (size_t)a.S ? (size_t)a.S : sc_rows);
     a.SC = (int)sc_rows;
-    const size_t score_elems = fused ? 0 : row_elems * sc_rows;
+    const size_t score_elems = fused ? 0 : split ? rten_gqa_split_scratch_elems(a) : row_elems * sc_rows;
     float *aux = nullptr;
     if (q_pad + score_elems > 0) {
         aux = (float *)rten_aux_scratch(ctx, (q_pad + score_elems) * sizeof(float) + 256);
@@ -441,6 +424,7 @@ RTEN_EXPORT int32_t rten_hip_gqa_f32(rten_hip_ctx *ctx, const int32_t *dims, con
         a.q_sb = (int64_t)a.S * a.H * a.D; a.q_ss = (int64_t)a.H * a.D; a.q_sh = a.D;
     }
     if (fused) return a.D == 64 ? launch_decode<64>(ctx, a, lds) : launch_decode<128>(ctx, a, lds);
+    if (split) return rten_gqa_split_launch(ctx, a, ctx->gqa_split, a.scores);
 
     // ---- composed path.  Batch levels: outer = (b, KV head), inner = the G query heads of the group, K and V with inner stride 0.  (b, KV head) is
     // one stride of Q and out only for one batch item, or one token whose batch stride is H heads; otherwise one launch per batch item.

@@ -645,16 +645,19 @@ def main():
     # kv_len - 1 rows, the whole call (prepare-and-append launch + attention) on the decode kernel and on the composed path, beside (a) what such a
     # graph ran on before -- two strided copies for the concatenation, then rten_hip_sdpa_f32 with one query row on K and V expanded to 32 heads -- and
     # (b) one strided copy of the K and V bytes, the yardstick.  Then one first prompt of 2048 tokens.  Operands are zeros: the timing does not read values.
+    # The split decode form (gqa_split.hip) is a fourth path on every row, with a sweep of its keys per workgroup at batch 1; kv_len 16384 is past the
+    # one-workgroup kernel's LDS bound at G 4.  A library without rten_hip_set_gqa_split (the parent's, when the two are timed alternately) skips those rows.
     if want("gqa:"):
         h_, kv_, d_ = 32, 8, 128
+        has_split = hasattr(ctx.lib, "rten_hip_set_gqa_split")
 
         def zeros(*shape, dt=np.float32):
             t_ = empty(shape, dt)
             ctx.call("rten_hip_memset", t_.vp, 0, C.c_size_t(t_.size * 4))
             return t_
 
-        for b_ in (1, 32):
-            for kvl in (512, 2048, 4096):
+        for b_ in (1, 4, 32):
+            for kvl in (512, 2048, 4096, 16384):
                 p_ = kvl - 1
                 q_, k_, v_ = zeros(b_, 1, h_ * d_), zeros(b_, 1, kv_ * d_), zeros(b_, 1, kv_ * d_)
                 pk_, pv_, ok_, ov_ = zeros(b_, kv_, p_, d_), zeros(b_, kv_, p_, d_), zeros(b_, kv_, kvl, d_), zeros(b_, kv_, kvl, d_)
@@ -666,9 +669,17 @@ def main():
                 kv_bytes = 8.0 * b_ * kv_ * kvl * d_
                 call = (lambda: ctx.call("rten_hip_gqa_f32", dims, st_, 0.0883883461, q_.vp, k_.vp, v_.vp, pk_.vp, pv_.vp, sl_.vp, tot_.vp, None, None, None, None,
                                          o_.vp, ok_.vp, ov_.vp))
-                for pname, path in (("decode kernel", 2), ("composed path", 1), ("dispatch rule", 0)):
+                for pname, path in (("decode kernel", 2), ("composed path", 1), ("split kernel", 3), ("dispatch rule", 0)):
+                    if (path == 2 and kvl > 8064) or (path == 3 and not has_split):
+                        continue
                     ctx.call("rten_hip_set_gqa_path", path)
                     hbm(f"gqa: decode, whole call ({pname})", shape, call, 3 * kv_bytes)
+                if has_split and b_ == 1:
+                    ctx.call("rten_hip_set_gqa_path", 3)
+                    for ck in (16, 32, 64, 128, 256, 1024):
+                        ctx.call("rten_hip_set_gqa_split", ck)
+                        hbm(f"gqa: decode, whole call (split kernel, {ck} keys per workgroup)", shape, call, 3 * kv_bytes)
+                    ctx.call("rten_hip_set_gqa_split", 0)
                 ctx.call("rten_hip_set_gqa_path", 0)
                 ke_, ve_ = zeros(b_, h_, kvl, d_), zeros(b_, h_, kvl, d_)
                 sd_ = L.SdpaDesc(b_, h_, 1, kvl, d_, d_, h_ * d_, d_, h_ * d_, h_ * kvl * d_, kvl * d_, d_, h_ * kvl * d_, kvl * d_, d_, h_ * d_, d_, h_ * d_, 0, 0,
