@@ -50,7 +50,8 @@
 extern "C" {
 #endif
 
-/* v8, later additions without a bump: + rten_hip_gqa_f32, rten_hip_set_gqa_path (GroupQueryAttention with a KV cache; dims and strides as host arrays);
+/* v8, later additions without a bump: + rten_hip_attention_f32, rten_hip_set_attention_path (opset-23 Attention with past / present caches);
+ * + rten_hip_gqa_f32, rten_hip_set_gqa_path (GroupQueryAttention with a KV cache; dims and strides as host arrays);
  * + rten_hip_set_gqa_split and mode 3 of rten_hip_set_gqa_path (the decode form that spreads the key range over workgroups).
  * v8 (round 6, third part): + rten_hip_conv2d_f32_pair / _pair_supported (an expand layer and the next block's reduce layer in one launch; a launch plan
  * lists the pairs: "pairs"), rten_hip_conv2d_f32_pair_shortcut / _supported (the same with the block's shortcut convolution computed in the launch: "pair_shortcuts");
@@ -488,6 +489,30 @@ int32_t rten_hip_gqa_f32(rten_hip_ctx *ctx, const int32_t *dims, const int64_t *
                          float *present_key, float *present_value);
 int32_t rten_hip_set_gqa_path(rten_hip_ctx *ctx, int32_t mode);
 int32_t rten_hip_set_gqa_split(rten_hip_ctx *ctx, int32_t keys_per_workgroup);
+/* ---- Attention (ai.onnx, opset 23) with past_key / past_value and present outputs: src/ops/attention.rs:579-973 ----
+ * dims (host, RTEN_HIP_ATTENTION_NDIMS int32): batch, q_num_heads Hq, kv_num_heads Hkv (divides Hq), q_seq Sq, kv_seq Skv, past_seq P, head_size D,
+ * v_head_size Dv, is_causal, mask kind (RTEN_HIP_ATTN_MASK_*).  Every length is a shape: total_seq T = P + Skv.
+ * strides (host, RTEN_HIP_ATTENTION_NSTRIDES int64, elements): batch / head / row strides of q, k, v and out (unit stride along the head, so the
+ * (B, H, S, D) and the (B, S, H * D) layouts are both read and written in place), then the batch / head / row / column strides of attn_mask broadcast to
+ * (B, Hq, Sq, T) (0 broadcasts).  attn_mask: float (added) or int32 (0 = -inf), by the mask kind; NULL for none.
+ * past_key [B, Hkv, P, D], past_value [B, Hkv, P, Dv]: contiguous, NULL when P == 0.  present_key [B, Hkv, T, D], present_value [B, Hkv, T, Dv]:
+ * contiguous, both NULL when the caller does not want them (nothing is stored then); they may not alias the inputs.
+ * nonpad_kv_seqlen: int32 [B] on the device or NULL; it only masks (with is_causal it anchors the causal window at nonpad - Sq, otherwise columns from
+ * nonpad on are -inf), is clamped into [0, T] where it is read and never read back, so the call captures and a replay follows new values.  The
+ * reference refuses it together with a past; a host that knows the values validates them itself (attention.rs:801-820).
+ * One query row with the gemv order on, D == Dv in {64, 128}, Hq / Hkv <= 32 and 4 * ((Hq / Hkv) * (T + D) + 8192) bytes of LDS <= 160 KiB takes the
+ * cache-appending decode kernel: one launch that reads past and the new rows directly and stores present from the registers it holds.  Everything else
+ * takes a concatenation launch, GEMM, score kernel, GEMM in passes of at most 64 MiB of scores.  rten_hip_set_attention_path: 0 that rule, 1 the
+ * composed path only, 2 the decode kernel or RTEN_HIP_ERR_UNSUPPORTED. */
+#define RTEN_HIP_ATTENTION_NDIMS 10
+#define RTEN_HIP_ATTENTION_NSTRIDES 16
+#define RTEN_HIP_ATTN_MASK_NONE 0
+#define RTEN_HIP_ATTN_MASK_FLOAT 1
+#define RTEN_HIP_ATTN_MASK_BOOL 2
+int32_t rten_hip_attention_f32(rten_hip_ctx *ctx, const int32_t *dims, const int64_t *strides, float scale, const float *q, const float *k, const float *v,
+                               const void *attn_mask, const float *past_key, const float *past_value, const int32_t *nonpad_kv_seqlen, float *out,
+                               float *present_key, float *present_value);
+int32_t rten_hip_set_attention_path(rten_hip_ctx *ctx, int32_t mode);
 /* BatchNormalization (inference), src/ops/norm.rs:194-224 */
 int32_t rten_hip_batch_norm_f32(rten_hip_ctx *ctx, int32_t n, int32_t c, int64_t inner, const float *x,
                                 const float *scale, const float *bias, const float *mean, const float *var,

@@ -1398,6 +1398,46 @@ class Graph {
         for (size_t k = 1; k <= 2; k++) a.want_present = a.want_present || (k < n.outputs.size() && value_is_read(m, n.outputs[k]));
         return a;
     }
+    // What the loader reads from, and refuses about, an opset-23 Attention node (make_attention_step; attributes onnx_registry.rs:791-810).  Refused by node
+    // name: softcap != 0 (the reference calls libm's tanh there: not reproducible), a stated qk_matmul_output_mode or softmax_precision, a used fourth output
+    // (qk_matmul_output), and an input whose stated element type is not float32 (attn_mask: float32 / int32 / bool; nonpad_kv_seqlen: int32).  Needs no
+    // device; rten_hip_run --parse-only calls it too.
+    static bool is_attention_node(const onnx::Node &n) { return (n.domain.empty() || n.domain == "ai.onnx") && n.op_type == "Attention"; }
+    struct AttentionNode {
+        bool is_causal = false, want_present = false;
+        std::optional<int64_t> q_num_heads, kv_num_heads;
+        std::optional<float> scale;
+    };
+    static AttentionNode read_attention_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
+        const std::string where = "Attention " + label + ": ";
+        AttentionNode a;
+        a.is_causal = n.get_int("is_causal", 0) != 0;
+        if (n.attr("q_num_heads")) a.q_num_heads = n.get_int("q_num_heads", 0);
+        if (n.attr("kv_num_heads")) a.kv_num_heads = n.get_int("kv_num_heads", 0);
+        if (const onnx::Attr *sc = n.attr("scale")) a.scale = sc->f;
+        if (n.get_float("softcap", 0.f) != 0.f) throw GraphError(where + "softcap != 0 is not supported");
+        for (const char *unused : {"qk_matmul_output_mode", "softmax_precision"})
+            if (n.attr(unused)) throw GraphError(where + "the " + unused + " attribute is not supported");
+        if (n.outputs.size() > 3 && value_is_read(m, n.outputs[3])) throw GraphError(where + "output 3 (qk_matmul_output, \"" + n.outputs[3] + "\") is read: not supported");
+        auto present = [&](size_t i) { return i < n.inputs.size() && !n.inputs[i].empty(); };
+        if (!present(0) || !present(1) || !present(2)) throw GraphError(where + "the Q, K and V inputs are required");
+        if (present(4) != present(5)) throw GraphError(where + "past_key and past_value must either both be present or both be absent");
+        if (n.inputs.size() > 7) throw GraphError(where + "at most 7 inputs");
+        auto stated = [&](const std::string &v) {
+            if (const onnx::TensorProto *t = initializer_named(m, v)) return t->data_type;
+            if (const onnx::ValueInfo *gi = graph_input_named(m, v)) return gi->elem_type;
+            return 0;
+        };
+        for (size_t i = 0; i < 7; i++) {
+            if (!present(i)) continue;
+            const int et = stated(n.inputs[i]);
+            const bool ok = et == 0 || (i == 3 ? et == onnx::FLOAT || et == onnx::INT32 || et == onnx::BOOL : i == 6 ? et == onnx::INT32 : et == onnx::FLOAT);
+            if (!ok) throw GraphError(where + "input " + std::to_string(i) + " (\"" + n.inputs[i] + "\") has element type " + std::to_string(et) +
+                                      (i == 3 ? ": float32 or int32 (bool) only" : i == 6 ? ": int32 only" : ": float32 only"));
+        }
+        for (size_t k = 1; k <= 2; k++) a.want_present = a.want_present || (k < n.outputs.size() && value_is_read(m, n.outputs[k]));
+        return a;
+    }
     // What the loader refuses about a Reduce* node of reduce_family_kind: axes that are neither an attribute nor a constant input are found when the plan
     // is built (read_reduce_attrs); here, without a device, an axes input that is a graph input (device data at run time).
     static void check_reduce_node(const onnx::Model &m, const onnx::Node &n, const std::string &label) {
@@ -3019,6 +3059,7 @@ class Graph {
             } else if (kind == "MatMul") make_matmul_step(st, n, nodes, out_name);
             else if (kind == "Add" && opt_.fuse && make_add_norm_step(st, n, nodes, out_name)) {} // (any other Add takes the generic path below)
             else if (is_gqa_node(n)) make_gqa_step(st, n, m);
+            else if (is_attention_node(n)) make_attention_step(st, n, m);
             else if (is_decoder_node(n)) make_decoder_step(st, n, m); // (RotaryEmbedding dispatches on its domain, the skip forms exist in com.microsoft only)
             else if (kind == "LayerNormalization") {
                 auto op = std::make_shared<LayerNormalization>();
@@ -3390,6 +3431,20 @@ class Graph {
         op->do_rotary = a.do_rotary; op->rotary_interleaved = a.rotary_interleaved; op->local_window_size = a.local_window_size;
         op->want_present = a.want_present;
         st.kind_name = "com.microsoft.GroupQueryAttention";
+        const size_t named = n.outputs.size();
+        st.run = [op, named](Context &c, const InputList &in) {
+            OutputList o = op->run(c, in);
+            while (o.size() < named) o.emplace_back(); // outputs the graph names but nothing reads
+            return o;
+        };
+    }
+    // Attention (opset 23): the read_attention_node checks at load, then rten_hip_attention_f32 per run.  Every length is a shape and nonpad_kv_seqlen
+    // stays on the device, so the step captures; every batch item attends to its own keys only, so it is not batch_coupled.  Present is computed only
+    // when the graph reads it.
+    void make_attention_step(Step &st, const onnx::Node &n, const onnx::Model &m) {
+        const AttentionNode a = read_attention_node(m, n, st.name);
+        auto op = std::make_shared<Attention>();
+        op->is_causal = a.is_causal; op->q_num_heads = a.q_num_heads; op->kv_num_heads = a.kv_num_heads; op->scale = a.scale; op->want_present = a.want_present;
         const size_t named = n.outputs.size();
         st.run = [op, named](Context &c, const InputList &in) {
             OutputList o = op->run(c, in);

@@ -3788,6 +3788,107 @@ struct GroupQueryAttention : Operator {
     }
 };
 
+// Attention (ai.onnx, opset 23; src/ops/attention.rs:579-973, attributes onnx_registry.rs:791-810) on rten_hip_attention_f32: inputs Q (B, Hq, Sq, D) or
+// (B, Sq, Hq * D), K, V, attn_mask (float32 added / int32 0 = -inf, broadcast to (B, Hq, Sq, T)), past_key, past_value (B, Hkv, P, D | Dv), nonpad_kv_seqlen
+// int32 [B].  A nonpad_kv_seqlen that carries a host copy is validated with the reference's errors; device values stay there (nothing is read back, the
+// step captures) and the kernels clamp them into [0, T].  `want_present`: outputs 1 / 2 are requested; `want_qk`: output 3 is (refused).
+struct Attention : Operator {
+    bool is_causal = false, want_present = false, want_qk = false;
+    std::optional<int64_t> q_num_heads, kv_num_heads;
+    std::optional<float> scale;
+    float softcap = 0.f;
+    const char *name() const override { return "Attention"; }
+    int max_inputs() const override { return 7; }
+    OutputList run(Context &ctx, const InputList &in) const override {
+        const Tensor &query = want(require(in, 0), DType::F32, "float32"), &key = want(require(in, 1), DType::F32, "float32"),
+                     &value = want(require(in, 2), DType::F32, "float32");
+        const Tensor *mask = get(in, 3), *past_key = get(in, 4), *past_value = get(in, 5), *nonpad = get(in, 6);
+        if (want_qk) throw OpError(OpError::UnsupportedValue, "qk_matmul_output output is not supported");
+        const int nd = query.ndim();
+        if (nd != 3 && nd != 4) throw OpError(OpError::InvalidValue, "query must have 3 or 4 dimensions");
+        if (key.ndim() != nd || value.ndim() != nd) throw OpError(OpError::IncompatibleInputShapes, "query, key and value must have the same rank");
+        int64_t batch = query.size(0), Hq, Hkv, Sq, Skv, D, Dv;
+        if (nd == 3) {
+            if (!q_num_heads) throw OpError(OpError::InvalidValue, "q_num_heads is required for 3D inputs");
+            if (!kv_num_heads) throw OpError(OpError::InvalidValue, "kv_num_heads is required for 3D inputs");
+            Hq = *q_num_heads; Hkv = *kv_num_heads;
+            if (Hq == 0 || Hkv == 0) throw OpError(OpError::InvalidValue, "q_num_heads and kv_num_heads must be positive");
+            if (key.size(0) != batch || value.size(0) != batch) throw OpError(OpError::IncompatibleInputShapes, "query, key and value must have the same batch size");
+            if (key.size(1) != value.size(1)) throw OpError(OpError::IncompatibleInputShapes, "key and value must have the same sequence length");
+            if (query.size(2) % Hq != 0) throw OpError(OpError::IncompatibleInputShapes, "query hidden size must be divisible by q_num_heads");
+            D = query.size(2) / Hq;
+            if (key.size(2) % Hkv != 0 || value.size(2) % Hkv != 0) throw OpError(OpError::IncompatibleInputShapes, "key/value hidden size must be divisible by kv_num_heads");
+            if (key.size(2) / Hkv != D) throw OpError(OpError::IncompatibleInputShapes, "key head size must match query head size");
+            Sq = query.size(1); Skv = key.size(1); Dv = value.size(2) / Hkv;
+        } else {
+            Hq = query.size(1); Sq = query.size(2); D = query.size(3);
+            if (key.size(0) != batch || value.size(0) != batch) throw OpError(OpError::IncompatibleInputShapes, "query, key and value must have the same batch size");
+            if (key.size(1) != value.size(1) || key.size(2) != value.size(2))
+                throw OpError(OpError::IncompatibleInputShapes, "key and value must have the same number of heads and sequence length");
+            if (key.size(3) != D) throw OpError(OpError::IncompatibleInputShapes, "key head size must match query head size");
+            Hkv = key.size(1); Skv = key.size(2); Dv = value.size(3);
+        }
+        if (Hq == 0 || Hkv == 0 || Hq % Hkv != 0) throw OpError(OpError::IncompatibleInputShapes, "q_num_heads must be a positive multiple of kv_num_heads");
+        int64_t P = 0;
+        if (past_key && past_value) {
+            want(*past_key, DType::F32, "float32"); want(*past_value, DType::F32, "float32");
+            if (past_key->ndim() != 4 || past_value->ndim() != 4) throw OpError(OpError::InputCastFailed, "expected tensor with 4 dims");
+            if (past_key->size(0) != batch || past_value->size(0) != batch || past_key->size(1) != Hkv || past_value->size(1) != Hkv || past_key->size(3) != D ||
+                past_value->size(3) != Dv || past_key->size(2) != past_value->size(2))
+                throw OpError(OpError::IncompatibleInputShapes, "past_key/past_value shape does not match key/value shape");
+            P = past_key->size(2);
+        } else if (past_key || past_value) throw OpError(OpError::InvalidValue, "past_key and past_value must either both be present or both be absent");
+        const int64_t T = P + Skv;
+        if (nonpad) {
+            want(*nonpad, DType::I32, "int32");
+            if (past_key) throw OpError(OpError::InvalidValue, "nonpad_kv_seqlen cannot be combined with past_key/past_value");
+            if (nonpad->ndim() != 1 || nonpad->size(0) != batch) throw OpError(OpError::IncompatibleInputShapes, "nonpad_kv_seqlen must have batch_size elements");
+            if (const HostVal *h = nonpad->host())
+                if (!h->is_float)
+                    for (int64_t v : h->i)
+                        if (v < 0 || v > T) throw OpError(OpError::InvalidValue, "nonpad_kv_seqlen entry is out of range");
+        }
+        const float sc = scale ? *scale : (D ? 1.0f / std::sqrt((float)D) : 0.f);
+        // batch / head / row strides of a (B, S, H * w) or a (B, H, S, w) tensor
+        auto layout = [&](int64_t *st, int64_t seq, int64_t heads, int64_t w) {
+            if (nd == 3) { st[0] = seq * heads * w; st[1] = w; st[2] = heads * w; }
+            else { st[0] = heads * seq * w; st[1] = seq * w; st[2] = w; }
+        };
+        int64_t st[RTEN_HIP_ATTENTION_NSTRIDES] = {};
+        layout(st, Sq, Hq, D); layout(st + 3, Skv, Hkv, D); layout(st + 6, Skv, Hkv, Dv); layout(st + 9, Sq, Hq, Dv);
+        int32_t mask_kind = RTEN_HIP_ATTN_MASK_NONE;
+        if (mask) {
+            if (mask->dtype() != DType::F32 && mask->dtype() != DType::I32) throw OpError(OpError::InvalidValue, "attn_mask must have a float or bool (int32) type");
+            mask_kind = mask->dtype() == DType::F32 ? RTEN_HIP_ATTN_MASK_FLOAT : RTEN_HIP_ATTN_MASK_BOOL;
+            if (mask->ndim() > 4) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs");
+            const int64_t target[4] = {batch, Hq, Sq, T};
+            int64_t shape[4] = {1, 1, 1, 1};
+            for (int i = 0; i < mask->ndim(); i++) shape[4 - mask->ndim() + i] = mask->size(i);
+            int64_t dense = 1;
+            for (int i = 3; i >= 0; i--) {
+                if (shape[i] != 1 && shape[i] != target[i]) throw OpError(OpError::IncompatibleInputShapes, "Cannot broadcast inputs");
+                st[12 + i] = shape[i] == 1 ? 0 : dense;
+                dense *= shape[i];
+            }
+        }
+        if (softcap > 0.f) throw OpError(OpError::UnsupportedValue, "softcap is not supported");
+        OutputList out;
+        out.emplace_back(ctx, nd == 3 ? std::vector<int64_t>{batch, Sq, Hq * Dv} : std::vector<int64_t>{batch, Hq, Sq, Dv}, DType::F32);
+        if (want_present) {
+            out.emplace_back(ctx, std::vector<int64_t>{batch, Hkv, T, D}, DType::F32);
+            out.emplace_back(ctx, std::vector<int64_t>{batch, Hkv, T, Dv}, DType::F32);
+        }
+        if (out[0].len() && T > 0 && D > 0) {
+            const int32_t dims[RTEN_HIP_ATTENTION_NDIMS] = {(int32_t)batch, (int32_t)Hq, (int32_t)Hkv, (int32_t)Sq, (int32_t)Skv, (int32_t)P, (int32_t)D, (int32_t)Dv,
+                                                            is_causal ? 1 : 0, mask_kind};
+            ctx.check(rten_hip_attention_f32(ctx.raw(), dims, st, sc, (const float *)query.ptr(), (const float *)key.ptr(), (const float *)value.ptr(), vp(mask),
+                                             (const float *)vp(past_key), (const float *)vp(past_value), (const int32_t *)vp(nonpad), (float *)out[0].ptr(),
+                                             want_present ? (float *)out[1].ptr() : nullptr, want_present ? (float *)out[2].ptr() : nullptr));
+        }
+        return out;
+    }
+};
+
 // ------------------------------------------------------------------------------------------------ registry (src/op_registry.rs:25-72)
 class OpRegistry {
   public:
@@ -3903,6 +4004,7 @@ class OpRegistry {
         r.register_op<SkipSimplifiedLayerNormalization>("com.microsoft.SkipSimplifiedLayerNormalization");
         r.register_op<RotaryEmbeddingMicrosoft>("com.microsoft.RotaryEmbedding");
         r.register_op<GroupQueryAttention>("com.microsoft.GroupQueryAttention");
+        r.register_op<Attention>("Attention");
         return r;
     }
 

@@ -43,8 +43,7 @@
 //     reference's bits.  PV is the gemv entry over P + 1 keys; the keys beyond kv_len have probability 0 and zero rows, and a chain that starts at +0
 //     cannot be moved by +-0 addends.  (Head sizes above 512 would need the depth-block beta step: refused.)
 #include "gqa_common.h"
-#include "rowreduce.h"
-#include "vecmath.h"
+#include "softmax_row.h"
 
 namespace {
 
@@ -104,39 +103,6 @@ __global__ __launch_bounds__(256) void gqa_prepare_kernel(const GqaArgs p) {
 constexpr int DEC_THREADS = 1024;
 constexpr int DEC_HC = 8; // heads whose block sums are parked at a time
 constexpr float NEG_INF = -__builtin_inff();
-
-// the softmax of rowwise.hip (softmax_long_kernel) on a row one wave owns, in place
-__device__ __forceinline__ void softmax_row(float *row, int cols, int lane) {
-    float mx = -3.40282347e+38f; // f32::MIN (softmax.rs:181)
-    for (int i = lane; i < cols; i += 64) mx = fmaxf(mx, row[i]);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    float a = 0.f;
-    const int l = lane & 15;
-    const int nch = (cols + 63) / 64;
-    for (int c = 0; c < nch; c++) {
-        const int i = c * 64 + lane;
-        float e = 0.f;
-        if (i < cols) {
-            e = vm::exp_reduced(row[i] - mx);
-            row[i] = e;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const float eq = lane_bcast(e, l + 16 * q);
-            if (c * 64 + l + 16 * q < cols) a = a + eq;
-        }
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; k++) s = s + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), k));
-    const float inv = 1.0f / s;
-    for (int i = lane; i < cols; i += 64) {
-        float r = row[i] * inv;
-        if (!(r == r)) r = 0.f; // flush_nans_to_zero (attention.rs:551)
-        row[i] = r;
-    }
-}
 
 template <int D>
 __global__ __launch_bounds__(DEC_THREADS) void gqa_decode_kernel(const GqaArgs p) {

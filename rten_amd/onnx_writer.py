@@ -999,3 +999,32 @@ def decoder_block_gqa_graph(form: str = "do_rotary", hidden: int = 64, heads: in
     outs = [value_info("mlp_out", FLOAT, [batch, seq, hidden]), value_info("residual_out", FLOAT, [batch, seq, hidden]),
             value_info("present_k", FLOAT, [batch, kv_heads, "total", head_size]), value_info("present_v", FLOAT, [batch, kv_heads, "total", head_size])]
     return model(nodes, ins, outs, [tensor(k, v) for k, v in w.items()], opset=21, name="decoder_block_gqa"), w
+
+
+def attention_graph(heads: int = 8, kv_heads: int = 2, head_size: int = 64, rank: int = 3, past: bool = True, mask=None, nonpad: bool = False, qk_output: bool = False,
+                    batch="batch", seq="seq", past_seq="past", input_type=None, **attrs):
+    """One opset-23 Attention node as PyTorch's exporter writes scaled_dot_product_attention: Attention(q, k, v[, attn_mask, past_k, past_v, nonpad]) ->
+    y, present_k, present_v (all graph outputs).  rank 3: (batch, seq, heads * head_size) inputs with q_num_heads / kv_num_heads; rank 4: (batch, heads,
+    seq, head_size).  mask: None, FLOAT or INT32 -- a (batch, 1, seq, "total") graph input.  qk_output: the fourth output is named and a graph output (a
+    refusal); attrs: further node attributes (is_causal, scale, softcap, ...); input_type: the stated type of q (a refusal when not FLOAT).  -> model bytes."""
+    shape = (lambda s, h: [batch, s, h * head_size]) if rank == 3 else (lambda s, h: [batch, h, s, head_size])
+    ins = [value_info("q", input_type or FLOAT, shape(seq, heads)), value_info("k", FLOAT, shape(seq, kv_heads)), value_info("v", FLOAT, shape(seq, kv_heads))]
+    names = ["q", "k", "v", "", "", "", ""]
+    if mask is not None:
+        names[3] = "attn_mask"
+        ins.append(value_info("attn_mask", mask, [batch, 1, seq, "total"]))
+    if past:
+        names[4:6] = ["past_k", "past_v"]
+        ins += [value_info(nm, FLOAT, [batch, kv_heads, past_seq, head_size]) for nm in ("past_k", "past_v")]
+    if nonpad:
+        names[6] = "nonpad"
+        ins.append(value_info("nonpad", INT32, [batch]))
+    while names and not names[-1]:
+        names.pop()
+    if rank == 3:
+        attrs = dict(q_num_heads=heads, kv_num_heads=kv_heads, **attrs)
+    out_names = ["y", "present_k", "present_v"] + (["qk"] if qk_output else [])
+    outs = [value_info("y", FLOAT, shape(seq, heads))] + [value_info(nm, FLOAT, [batch, kv_heads, "total", head_size]) for nm in ("present_k", "present_v")]
+    if qk_output:
+        outs.append(value_info("qk", FLOAT, [batch, heads, seq, "total"]))
+    return model([node("Attention", names, out_names, name="attention", **attrs)], ins, outs, [], opset=23, name="attention")

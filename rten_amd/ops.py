@@ -1576,47 +1576,7 @@ class DequantizeLinear(Operator):
         return [y]
 
 
-# ------------------------------------------------------------------------------------------ attention
-class Attention(Operator):
-    """ONNX Attention restricted to the BERT path (src/ops/attention.rs:645-905): 4-D Q/K/V
-    [B,H,S,D], optional additive float mask [B,1,1,T] or [B,1,S,T]; no KV cache / GQA / causal."""
-
-    def __init__(self, scale=None):
-        self.scale = scale
-
-    def max_inputs(self):
-        return 4
-
-    def run(self, ctx, inputs):
-        q = _want(_require(inputs, 0), np.float32)
-        k = _want(_require(inputs, 1), np.float32)
-        v = _want(_require(inputs, 2), np.float32)
-        mask = _get(inputs, 3)
-        if len(q.shape) != 4 or len(k.shape) != 4 or len(v.shape) != 4:
-            raise UnsupportedValue("device Attention needs 4-D Q/K/V")
-        B, H, S, D = q.shape
-        T, Dv = k.shape[2], v.shape[3]
-        if k.shape[:2] != (B, H) or v.shape[:3] != (B, H, T) or k.shape[3] != D:
-            raise IncompatibleInputShapes("Q/K/V shapes are inconsistent")
-        # `1.0 / (head_size as f32).sqrt()` in f32 arithmetic (attention.rs:659-670)
-        scale = self.scale if self.scale is not None else float(np.float32(1.0) / np.sqrt(np.float32(D)))
-        mbs, mrs = 0, 0
-        if mask is not None:
-            if mask.dtype != np.float32:
-                raise UnsupportedValue("device Attention supports additive float masks")
-            if tuple(mask.shape) == (B, 1, 1, T):
-                mbs, mrs = T, 0
-            elif tuple(mask.shape) == (B, 1, S, T):
-                mbs, mrs = S * T, T
-            else:
-                raise UnsupportedValue("mask must be [B,1,1,T] or [B,1,S,T]")
-        out = DeviceTensor(ctx, (B, H, S, Dv), np.float32)
-        d = L.SdpaDesc(B, H, S, T, D, Dv, H * S * D, S * D, D, H * T * D, T * D, D, H * T * Dv, T * Dv, Dv,
-                       H * S * Dv, S * Dv, Dv, mbs, mrs, scale, 1)
-        ctx.call("rten_hip_sdpa_f32", C.byref(d), q.vp, k.vp, v.vp, _vp(mask), out.vp)
-        return [out]
-
-
+# ------------------------------------------------------------------------------------------ attention: class Attention, below GroupQueryAttention
 class Gather(Operator):
     """Gather along axis 0 of a 2-D f32 table (embedding lookup; src/ops/gather.rs).  inputs: table [R,W], ids i32."""
 
@@ -3153,6 +3113,133 @@ class GroupQueryAttention(Operator):
         return [out]
 
 
+class Attention(Operator):
+    """Attention (ai.onnx, opset 23) with past / present caches, src/ops/attention.rs:579-973 (rten_hip_attention_f32: the cache-appending decode kernel, or a
+    concatenation launch, GEMM, score kernel, GEMM).  inputs: Q (B, Hq, Sq, D) or (B, Sq, Hq * D), K, V (B, Hkv, Skv, D | Dv) or 3-D, attn_mask float32
+    (added) or int32 (0 = -inf) broadcastable to (B, Hq, Sq, T), past_key, past_value (B, Hkv, P, D | Dv), nonpad_kv_seqlen int32 [B].  A nonpad_kv_seqlen
+    that arrives as a host value is validated with the reference's errors (attention.rs:801-820); a DeviceTensor stays on the device, where the kernels
+    clamp it into [0, T].  `outputs`: the requested output indices; present (always 4-D) is computed and returned only when 1 or 2 is among them, 3
+    (qk_matmul_output) is refused.  The encoder form (4-D, Hq == Hkv, no cache, not causal, no mask or a float [B, 1, 1 | Sq, T] mask, output 0 only) runs
+    rten_hip_sdpa_f32 as before.  Not built: softcap > 0 (the reference calls libm's tanh there)."""
+
+    def __init__(self, is_causal=False, q_num_heads=None, kv_num_heads=None, scale=None, softcap=0.0):
+        self.is_causal, self.scale, self.softcap = bool(is_causal), scale, float(softcap)
+        self.q_num_heads = None if q_num_heads is None else int(q_num_heads)
+        self.kv_num_heads = None if kv_num_heads is None else int(kv_num_heads)
+
+    def name(self):
+        return "Attention"
+
+    def max_inputs(self):
+        return 7
+
+    def max_outputs(self):
+        return 4
+
+    def run(self, ctx, inputs, outputs=(0,)):
+        query, key, value = (_dense(ctx, _want(_require(inputs, i), np.float32)) for i in range(3))
+        mask, past_key, past_value, nonpad = (_get(inputs, i) for i in range(3, 7))
+        if 3 in outputs:
+            raise UnsupportedValue("qk_matmul_output output is not supported")
+        nd = len(query.shape)
+        if nd not in (3, 4):
+            raise InvalidValue("query must have 3 or 4 dimensions")
+        if len(key.shape) != nd or len(value.shape) != nd:
+            raise IncompatibleInputShapes("query, key and value must have the same rank")
+        if nd == 3:
+            Hq, Hkv = self.q_num_heads, self.kv_num_heads
+            if Hq is None:
+                raise InvalidValue("q_num_heads is required for 3D inputs")
+            if Hkv is None:
+                raise InvalidValue("kv_num_heads is required for 3D inputs")
+            if Hq == 0 or Hkv == 0:
+                raise InvalidValue("q_num_heads and kv_num_heads must be positive")
+            batch, Sq, q_hidden = query.shape
+            if key.shape[0] != batch or value.shape[0] != batch:
+                raise IncompatibleInputShapes("query, key and value must have the same batch size")
+            if key.shape[1] != value.shape[1]:
+                raise IncompatibleInputShapes("key and value must have the same sequence length")
+            if q_hidden % Hq != 0:
+                raise IncompatibleInputShapes("query hidden size must be divisible by q_num_heads")
+            D = q_hidden // Hq
+            if key.shape[2] % Hkv != 0 or value.shape[2] % Hkv != 0:
+                raise IncompatibleInputShapes("key/value hidden size must be divisible by kv_num_heads")
+            if key.shape[2] // Hkv != D:
+                raise IncompatibleInputShapes("key head size must match query head size")
+            Skv, Dv = key.shape[1], value.shape[2] // Hkv
+            layout = lambda seq, heads, w: [seq * heads * w, w, heads * w]  # batch / head / row strides of (B, S, H * w)
+        else:
+            batch, Hq, Sq, D = query.shape
+            if key.shape[0] != batch or value.shape[0] != batch:
+                raise IncompatibleInputShapes("query, key and value must have the same batch size")
+            if key.shape[1] != value.shape[1] or key.shape[2] != value.shape[2]:
+                raise IncompatibleInputShapes("key and value must have the same number of heads and sequence length")
+            if key.shape[3] != D:
+                raise IncompatibleInputShapes("key head size must match query head size")
+            Hkv, Skv, Dv = key.shape[1], key.shape[2], value.shape[3]
+            layout = lambda seq, heads, w: [heads * seq * w, seq * w, w]
+        if Hq == 0 or Hkv == 0 or Hq % Hkv != 0:
+            raise IncompatibleInputShapes("q_num_heads must be a positive multiple of kv_num_heads")
+        if past_key is not None and past_value is not None:
+            past_key, past_value = _dense(ctx, _want(past_key, np.float32)), _dense(ctx, _want(past_value, np.float32))
+            if len(past_key.shape) != 4 or len(past_value.shape) != 4:
+                raise OpError("InputCastFailed", "expected tensor with 4 dims")
+            if tuple(past_key.shape[:2]) != (batch, Hkv) or tuple(past_value.shape[:2]) != (batch, Hkv) or past_key.shape[3] != D or \
+                    past_value.shape[3] != Dv or past_key.shape[2] != past_value.shape[2]:
+                raise IncompatibleInputShapes("past_key/past_value shape does not match key/value shape")
+            P = past_key.shape[2]
+        elif past_key is None and past_value is None:
+            P = 0
+        else:
+            raise InvalidValue("past_key and past_value must either both be present or both be absent")
+        T = P + Skv
+        nonpad_dev = None
+        if nonpad is not None:
+            if P or past_key is not None:
+                raise InvalidValue("nonpad_kv_seqlen cannot be combined with past_key/past_value")
+            if _shape_of(nonpad) != (batch,):
+                raise IncompatibleInputShapes("nonpad_kv_seqlen must have batch_size elements")
+            nonpad_host, nonpad_dev = _int32_operand(ctx, nonpad)
+            if nonpad_host is not None and any(n < 0 or n > T for n in nonpad_host):
+                raise InvalidValue("nonpad_kv_seqlen entry is out of range")
+        scale = self.scale
+        if scale is None:
+            scale = float(np.float32(1.0) / np.sqrt(np.float32(D))) if D else 0.0
+        mask_kind, mask_strides = L.ATTN_MASK_NONE, [0, 0, 0, 0]
+        if mask is not None:
+            mask = _dense(ctx, mask)
+            if mask.dtype not in (np.dtype(np.float32), np.dtype(np.int32)):
+                raise InvalidValue("attn_mask must have a float or bool (int32) type")
+            mask_kind = L.ATTN_MASK_FLOAT if mask.dtype == np.dtype(np.float32) else L.ATTN_MASK_BOOL
+            shape = tuple(mask.shape)
+            if len(shape) > 4:
+                raise IncompatibleInputShapes("Cannot broadcast inputs")
+            shape = (1,) * (4 - len(shape)) + shape
+            if any(m not in (1, t) for m, t in zip(shape, (batch, Hq, Sq, T))):
+                raise IncompatibleInputShapes("Cannot broadcast inputs")
+            dense = [shape[1] * shape[2] * shape[3], shape[2] * shape[3], shape[3], 1]
+            mask_strides = [0 if m == 1 else st for m, st in zip(shape, dense)]
+        if self.softcap > 0.0:
+            raise UnsupportedValue("softcap is not supported")
+        out = DeviceTensor(ctx, (batch, Sq, Hq * Dv) if nd == 3 else (batch, Hq, Sq, Dv), np.float32)
+        want_present = 1 in outputs or 2 in outputs
+        bert = nd == 4 and Hq == Hkv and P == 0 and nonpad is None and not self.is_causal and not want_present and \
+            (mask is None or (mask_kind == L.ATTN_MASK_FLOAT and tuple(mask.shape) in ((batch, 1, 1, T), (batch, 1, Sq, T))))
+        if bert:  # the encoder form keeps its route: rten_hip_sdpa_f32 (the fused attention kernel where it covers the shape)
+            mbs, mrs = (0, 0) if mask is None else ((T, 0) if mask.shape[2] == 1 else (Sq * T, T))
+            d = L.SdpaDesc(batch, Hq, Sq, T, D, Dv, Hq * Sq * D, Sq * D, D, Hq * T * D, T * D, D, Hq * T * Dv, T * Dv, Dv, Hq * Sq * Dv, Sq * Dv, Dv, mbs, mrs, scale, 1)
+            ctx.call("rten_hip_sdpa_f32", C.byref(d), query.vp, key.vp, value.vp, _vp(mask), out.vp)
+            return [out]
+        present_key = DeviceTensor(ctx, (batch, Hkv, T, D), np.float32) if want_present else None
+        present_value = DeviceTensor(ctx, (batch, Hkv, T, Dv), np.float32) if want_present else None
+        if out.size and T * D:
+            dims = (C.c_int32 * L.ATTENTION_NDIMS)(batch, Hq, Hkv, Sq, Skv, P, D, Dv, int(self.is_causal), mask_kind)
+            st = (C.c_int64 * L.ATTENTION_NSTRIDES)(*layout(Sq, Hq, D), *layout(Skv, Hkv, D), *layout(Skv, Hkv, Dv), *layout(Sq, Hq, Dv), *mask_strides)
+            ctx.call("rten_hip_attention_f32", dims, st, scale, query.vp, key.vp, value.vp, _vp(mask), _vp(past_key), _vp(past_value), _vp(nonpad_dev), out.vp,
+                     _vp(present_key), _vp(present_value))
+        return [out, present_key, present_value] if want_present else [out]
+
+
 class OpRegistry:
     """Mirror of OpRegistry (src/op_registry.rs:25-72): op_type -> operator class for the hot path."""
 
@@ -3169,7 +3256,7 @@ class OpRegistry:
                    Pow, PRelu, Min, Max, Sum, Mean, Pad, QuantizeLinear, DequantizeLinear, ReduceL1, ReduceL2, ReduceSumSquare, ReduceLogSum, ReduceLogSumExp,
                    ReduceProd, LpNormalization, GlobalMaxPool, GridSample, DepthToSpace, CumSum, GatherElements, Trilu, Tile,
                    NonMaxSuppression, DFT, STFT, RMSNormalization, SimplifiedLayerNormalization, SkipLayerNormalization,
-                   SkipSimplifiedLayerNormalization, RotaryEmbedding, RotaryEmbeddingMicrosoft, GroupQueryAttention):
+                   SkipSimplifiedLayerNormalization, RotaryEmbedding, RotaryEmbeddingMicrosoft, GroupQueryAttention, Attention):
             r.register_op(op)
         return r
 

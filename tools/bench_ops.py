@@ -723,6 +723,44 @@ def main():
             ctx.call("rten_hip_set_sdpa_path", 0)
             del q_, k_, v_, o_, ok_, ov_, ke_, ve_, mask_
 
+    # ---- Attention (opset 23) with past / present caches (rten_amd/csrc/attention_kv.hip; --only attention_kv: selects these rows): decode at Hq 32 / Hkv 8 /
+    # D 128, one new row appended to a cache of kv_len - 1 rows, present written: the cache-appending decode kernel (mode 2: one launch) against the composed
+    # path of the same library (mode 1: concatenation launch, gemv, score kernel, gemv), beside the yardstick -- rten_hip_gqa_f32 on the same shape on its
+    # one-workgroup decode kernel (rten_hip_set_gqa_path 2), its prepare-and-append launch included.  The three are measured alternately, three runs each.
+    if want("attention_kv:"):
+        hq_, hkv_, d_ = 32, 8, 128
+
+        def zeros_(*shape, dt=np.float32):
+            t_ = empty(shape, dt)
+            ctx.call("rten_hip_memset", t_.vp, 0, C.c_size_t(t_.size * 4))
+            return t_
+
+        for b_ in (1, 32):
+            for kvl in (512, 2048, 4096):
+                p_ = kvl - 1
+                q_, k_, v_, o_ = zeros_(b_, 1, hq_ * d_), zeros_(b_, 1, hkv_ * d_), zeros_(b_, 1, hkv_ * d_), zeros_(b_, 1, hq_ * d_)
+                pk_, pv_, ok_, ov_ = zeros_(b_, hkv_, p_, d_), zeros_(b_, hkv_, p_, d_), zeros_(b_, hkv_, kvl, d_), zeros_(b_, hkv_, kvl, d_)
+                adims = (C.c_int32 * L.ATTENTION_NDIMS)(b_, hq_, hkv_, 1, 1, p_, d_, d_, 1, L.ATTN_MASK_NONE)
+                ast = (C.c_int64 * L.ATTENTION_NSTRIDES)(hq_ * d_, d_, hq_ * d_, hkv_ * d_, d_, hkv_ * d_, hkv_ * d_, d_, hkv_ * d_, hq_ * d_, d_, hq_ * d_, 0, 0, 0, 0)
+                attn = (lambda: ctx.call("rten_hip_attention_f32", adims, ast, 0.0883883461, q_.vp, k_.vp, v_.vp, None, pk_.vp, pv_.vp, None, o_.vp, ok_.vp, ov_.vp))
+                sl_, tot_ = dev(np.full(b_, kvl - 1, np.int32)), dev(np.array([kvl], np.int32))
+                gdims = (C.c_int32 * L.GQA_NDIMS)(b_, 1, hq_, hkv_, d_, p_, 0, 0, 0, 0)
+                gst = (C.c_int64 * L.GQA_NSTRIDES)(hq_ * d_, hq_ * d_, d_, hkv_ * d_, hkv_ * d_, d_, hkv_ * d_, hkv_ * d_, d_, 0, 0, 0)
+                gqa = (lambda: ctx.call("rten_hip_gqa_f32", gdims, gst, 0.0883883461, q_.vp, k_.vp, v_.vp, pk_.vp, pv_.vp, sl_.vp, tot_.vp, None, None, None, None,
+                                        o_.vp, ok_.vp, ov_.vp))
+                shape = f"batch={b_} kv_len={kvl} heads={hq_} kv_heads={hkv_} head_size={d_}"
+                kv_bytes = 8.0 * b_ * hkv_ * kvl * d_
+                for run in (1, 2, 3):
+                    ctx.call("rten_hip_set_attention_path", 2)
+                    hbm(f"attention_kv: decode, cache-appending kernel (mode 2), run {run}", shape, attn, 2 * kv_bytes)
+                    ctx.call("rten_hip_set_attention_path", 1)
+                    hbm(f"attention_kv: decode, composed path (mode 1), run {run}", shape, attn, 2 * kv_bytes)
+                    ctx.call("rten_hip_set_attention_path", 0)
+                    ctx.call("rten_hip_set_gqa_path", 2)
+                    hbm(f"attention_kv: yardstick, rten_hip_gqa_f32 one-workgroup decode with its prepare launch, run {run}", shape, gqa, 2 * kv_bytes)
+                    ctx.call("rten_hip_set_gqa_path", 0)
+                del q_, k_, v_, o_, pk_, pv_, ok_, ov_, sl_, tot_
+
     if args.cpu_baseline:
         sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         import bench  # the oracle is only ever touched through bench.py's cpu_baseline leg

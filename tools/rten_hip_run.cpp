@@ -260,6 +260,16 @@ int main(int argc, char **argv) {
             }
         }
         {
+            const onnx::Model c = Graph::canonical_form(m); // Attention (opset 23): the loader's checks and what the step will be handed
+            for (const onnx::Node &n : c.nodes) {
+                if (!Graph::is_attention_node(n)) continue;
+                const Graph::AttentionNode a = Graph::read_attention_node(c, n, n.name.empty() ? n.outputs.at(0) : n.name);
+                std::printf("  attention step Attention \"%s\": q_num_heads %s, kv_num_heads %s, %s, present caches %s\n", n.name.c_str(),
+                            a.q_num_heads ? std::to_string(*a.q_num_heads).c_str() : "from the shape", a.kv_num_heads ? std::to_string(*a.kv_num_heads).c_str() : "from the shape",
+                            a.is_causal ? "causal" : "not causal", a.want_present ? "read" : "not read");
+            }
+        }
+        {
             const onnx::Model c = Graph::canonical_form(m); // QuantizeLinear / DequantizeLinear: the loader's checks, and the pairs that become one round-trip step
             std::vector<bool> taken(c.nodes.size(), false);
             for (size_t i = 0; i < c.nodes.size(); i++) {
