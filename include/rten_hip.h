@@ -50,7 +50,8 @@
 extern "C" {
 #endif
 
-/* v8, later additions without a bump: + rten_hip_attention_f32, rten_hip_set_attention_path (opset-23 Attention with past / present caches);
+/* v8, later additions without a bump: + rten_hip_set_attention_split and mode 3 of rten_hip_set_attention_path (Attention's decode form that spreads the
+ * key range over workgroups); + rten_hip_attention_f32, rten_hip_set_attention_path (opset-23 Attention with past / present caches);
  * + rten_hip_gqa_f32, rten_hip_set_gqa_path (GroupQueryAttention with a KV cache; dims and strides as host arrays);
  * + rten_hip_set_gqa_split and mode 3 of rten_hip_set_gqa_path (the decode form that spreads the key range over workgroups).
  * v8 (round 6, third part): + rten_hip_conv2d_f32_pair / _pair_supported (an expand layer and the next block's reduce layer in one launch; a launch plan
@@ -502,8 +503,14 @@ int32_t rten_hip_set_gqa_split(rten_hip_ctx *ctx, int32_t keys_per_workgroup);
  * reference refuses it together with a past; a host that knows the values validates them itself (attention.rs:801-820).
  * One query row with the gemv order on, D == Dv in {64, 128}, Hq / Hkv <= 32 and 4 * ((Hq / Hkv) * (T + D) + 8192) bytes of LDS <= 160 KiB takes the
  * cache-appending decode kernel: one launch that reads past and the new rows directly and stores present from the registers it holds.  Everything else
- * takes a concatenation launch, GEMM, score kernel, GEMM in passes of at most 64 MiB of scores.  rten_hip_set_attention_path: 0 that rule, 1 the
- * composed path only, 2 the decode kernel or RTEN_HIP_ERR_UNSUPPORTED. */
+ * takes a concatenation launch, GEMM, score kernel, GEMM in passes of at most 64 MiB of scores.
+ * The split decode form takes one query row with the gemv order on, D and Dv each 64 or 128 (independently) and Hq / Hkv <= 512, whatever T: the key range
+ * of a (batch, KV head) is spread over workgroups of keys_per_workgroup keys in four dependent launches that read past and the new rows directly and store
+ * present while they do; score rows and 8-key block sums live in scratch (at most 64 MiB per pass over the (batch, KV head) pairs, or one pair's rows), and
+ * the result has the same bits for every split.  The rule takes it where the decode kernel does not cover such a call, and where B * Hkv workgroups
+ * under-fill the device at a cache long enough to pay for its extra launches.  rten_hip_set_attention_path: 0 that rule, 1 the composed path only, 2 the
+ * decode kernel or RTEN_HIP_ERR_UNSUPPORTED, 3 the split decode form or RTEN_HIP_ERR_UNSUPPORTED.  rten_hip_set_attention_split: the split form's keys
+ * per workgroup, 0 (the rule, from B, Hkv and T) or a positive multiple of 8; anything else is RTEN_HIP_ERR_INVALID_VALUE. */
 #define RTEN_HIP_ATTENTION_NDIMS 10
 #define RTEN_HIP_ATTENTION_NSTRIDES 16
 #define RTEN_HIP_ATTN_MASK_NONE 0
@@ -513,6 +520,7 @@ int32_t rten_hip_attention_f32(rten_hip_ctx *ctx, const int32_t *dims, const int
                                const void *attn_mask, const float *past_key, const float *past_value, const int32_t *nonpad_kv_seqlen, float *out,
                                float *present_key, float *present_value);
 int32_t rten_hip_set_attention_path(rten_hip_ctx *ctx, int32_t mode);
+int32_t rten_hip_set_attention_split(rten_hip_ctx *ctx, int32_t keys_per_workgroup);
 /* BatchNormalization (inference), src/ops/norm.rs:194-224 */
 int32_t rten_hip_batch_norm_f32(rten_hip_ctx *ctx, int32_t n, int32_t c, int64_t inner, const float *x,
                                 const float *scale, const float *bias, const float *mean, const float *var,

@@ -24,62 +24,22 @@
 //         of its block ONCE, stores them to present_value, and chains them for every head of the group, 8 heads parked in LDS at a time; the thread that
 //         owns (head, column) folds the parked sums in block order (first block stored, the rest added).  D is 64 or 128: no left-over columns.
 //     LDS: 4 * (G * D [q] + 8192 [block sums: 1024 / D slots x 8 heads x D] + G * T [score rows]) bytes <= 160 KiB, the formula of gqa_decode_kernel.
+//   * the split decode form (attention_split.hip; Sq == 1, gemv order on, D and Dv each 64 or 128, G <= 512, no LDS bound): the key range of one (batch, KV
+//     head) spread over workgroups in four dependent launches, same arithmetic.  The rule takes it where the kernel above does not cover such a call, and where
+//     B * Hkv workgroups under-fill the device at a cache long enough to pay for the extra launches (rten_attn_split_pays).
 //   * attn_concat_kernel: present_key and present_value of the composed path in one launch (into scratch when the caller does not want them and the
 //     GEMMs cannot read the inputs in place).
 //   * attn_scores_kernel: the score modification and softmax_row on a scratch row, one wave per row, between the two GEMMs of the composed path (any D,
 //     Dv, Sq): the group is the GEMMs' inner batch level with stride 0 on K and V; one query row takes the gemv entry on T columns (T is a shape here, so
 //     which keys are a column block's left-overs is host-known), more rows rten_gemm_f32_blocked; the query rows are worked in passes of <= 64 MiB of scores.
-#include "internal.h"
+#include "attention_common.h"
 #include "softmax_row.h"
 
 namespace {
 
-struct AttnArgs {
-    int B, Hq, Hkv, G, Sq, Skv, P, T, D, Dv; // T = P + Skv
-    int causal, mask_kind;                   // mask_kind: RTEN_HIP_ATTN_MASK_*
-    int s0, SC;                              // composed path: the query rows [s0, s0 + SC) of this pass; scores is [B, Hq, SC, T]
-    long long gemv_threads;
-    int64_t q_sb, q_sh, q_ss, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_sh, o_ss, m_sb, m_sh, m_sq, m_st;
-    const float *q, *k, *v, *past_k, *past_v;
-    const void *mask;      // float or int32, by mask_kind
-    const int32_t *nonpad; // [B] or NULL
-    float *pk, *pv;        // present [B, Hkv, T, D] / [B, Hkv, T, Dv]; NULL in the decode kernel: not stored
-    float *scores, *out;
-    float scale;
-};
-
 constexpr int DEC_THREADS = 1024;
 constexpr int DEC_HC = 8;    // heads whose block sums are parked at a time
 constexpr int DEC_MAXCH = 4; // chunks of DEC_HC heads whose output an owner thread carries: G <= 32
-constexpr float NEG_INF = -__builtin_inff();
-
-// nonpad_kv_seqlen[b] clamped into [0, T], or -1 when the input is absent
-__device__ __forceinline__ int nonpad_of(const AttnArgs &p, int b) {
-    if (!p.nonpad) return -1;
-    const int n = p.nonpad[b];
-    return n < 0 ? 0 : (n > p.T ? p.T : n);
-}
-
-// the first masked column of row s by steps 2 and 3 of the score modification (T: none)
-__device__ __forceinline__ int masked_from(const AttnArgs &p, int np, int s) {
-    if (p.causal) {
-        const long long from = (long long)(np >= 0 ? np - p.Sq : p.P) + s + 1;
-        return (int)(from < 0 ? 0 : (from > p.T ? p.T : from));
-    }
-    return np >= 0 ? np : p.T;
-}
-
-// steps 1-3 on one score; mrow = the mask's row (b, h, s), already offset
-__device__ __forceinline__ float modified(const AttnArgs &p, float o, const void *mrow, int t, int from) {
-    if (p.mask_kind == RTEN_HIP_ATTN_MASK_FLOAT) o = o + ((const float *)mrow)[t * p.m_st];
-    else if (p.mask_kind == RTEN_HIP_ATTN_MASK_BOOL && ((const int32_t *)mrow)[t * p.m_st] == 0) o = NEG_INF;
-    return t >= from ? NEG_INF : o;
-}
-
-__device__ __forceinline__ const void *mask_row(const AttnArgs &p, int b, int h, int s) {
-    const int64_t at = b * p.m_sb + h * p.m_sh + s * p.m_sq;
-    return p.mask_kind == RTEN_HIP_ATTN_MASK_FLOAT ? (const void *)((const float *)p.mask + at) : (const void *)((const int32_t *)p.mask + at);
-}
 
 template <int D>
 __global__ __launch_bounds__(DEC_THREADS) void attn_decode_kernel(const AttnArgs p) {
@@ -266,8 +226,16 @@ int32_t launch_decode(rten_hip_ctx *ctx, const AttnArgs &a, size_t lds) {
 
 RTEN_EXPORT int32_t rten_hip_set_attention_path(rten_hip_ctx *ctx, int32_t mode) {
     RTEN_CHECK_CTX(ctx);
-    if (mode < 0 || mode > 2) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "set_attention_path: mode must be 0, 1 or 2");
+    if (mode < 0 || mode > 3) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "set_attention_path: mode must be 0, 1, 2 or 3");
     ctx->attention_path = mode;
+    return RTEN_HIP_OK;
+}
+
+RTEN_EXPORT int32_t rten_hip_set_attention_split(rten_hip_ctx *ctx, int32_t keys_per_workgroup) {
+    RTEN_CHECK_CTX(ctx);
+    if (keys_per_workgroup < 0 || keys_per_workgroup % 8 != 0)
+        return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "set_attention_split: keys_per_workgroup must be 0 (the rule) or a positive multiple of 8");
+    ctx->attention_split = keys_per_workgroup;
     return RTEN_HIP_OK;
 }
 
@@ -306,6 +274,11 @@ RTEN_EXPORT int32_t rten_hip_attention_f32(rten_hip_ctx *ctx, const int32_t *dim
     const bool covered = one_row && a.D == a.Dv && (a.D == 64 || a.D == 128) && a.G <= DEC_HC * DEC_MAXCH && lds <= LDS_PER_WORKGROUP;
     if (ctx->attention_path == 2 && !covered)
         return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "attention: the decode kernel takes one query row in the gemv order, equal K and V head sizes of 64 or 128, at most 32 query heads per KV head and rows that fit LDS");
+    const bool splittable = one_row && rten_attn_split_covers(a);
+    if (ctx->attention_path == 3 && !splittable)
+        return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "attention: the split decode form takes one query row in the gemv order, K and V head sizes of 64 or 128 and at most 512 query heads per KV head");
+    if (splittable && (ctx->attention_path == 3 || (ctx->attention_path == 0 && (!covered || rten_attn_split_pays(ctx, a)))))
+        return rten_attn_split_launch(ctx, a, ctx->attention_split);
     if (covered && ctx->attention_path != 1) return a.D == 64 ? launch_decode<64>(ctx, a, lds) : launch_decode<128>(ctx, a, lds);
 
     // ---- composed path.  K and V are read in place when there is no past and the inputs are contiguous (B, Hkv, T, *); otherwise out of present, or out

@@ -18,21 +18,20 @@
 //      are never read.
 //   4. gqa_split_fold_kernel, one workgroup of 256 threads per (row, 32 output columns): 128 blocks x 32 columns are staged into LDS with 16-byte loads
 //      (the next tile is in flight while this one is folded), and 32 threads fold them in block order: block 0 stored, the rest added left to right.
-// Workgroups whose chunk lies at or beyond the device kv_len exit at once; every kernel derives the lengths through lens().
+// Workgroups whose chunk lies at or beyond the device kv_len exit at once; every kernel derives the lengths through lens().  Stages 2 and 4 are device
+// functions of split_rows.h, shared with attention_split.hip.
 //
 // Scratch (floats, after the rotated Q in rten_aux_scratch), a function of host-known dims only.  With Tp = T rounded up to 64 and NB = ceil(T / 8), one
 // unit needs G * (Tp + NB * D) floats (score rows, block sums; the block sums cost G / 8 of the V bytes in traffic).  The units are worked through in
 // passes of U = clamp(64 MiB / unit bytes, 1, B * KV) units, and the buffer is  round_up(U * G, 64) [1 / sum]  +  U * G * Tp  +  U * G * NB * D.
 #include "gqa_common.h"
-#include "vecmath.h"
+#include "split_rows.h"
 
 namespace {
 
 constexpr int SPL_THREADS = 256;
 constexpr int SPL_QH = 16;       // query heads parked in LDS at a time
-constexpr int SM_THREADS = 1024, SM_TILE = 4096;
 constexpr int PV_TILE = 4096;    // probabilities parked in LDS at a time (floats): 8-key blocks of the G heads
-constexpr int FOLD_COLS = 32, FOLD_TILE = 128;
 constexpr size_t SPLIT_PASS_BYTES = 64u << 20;
 constexpr float NEG_INF = -__builtin_inff();
 
@@ -122,60 +121,10 @@ __global__ __launch_bounds__(SPL_THREADS) void gqa_split_scores_kernel(const Spl
     }
 }
 
-// the softmax of rowwise.hip (softmax_long_kernel) on one score row in scratch, up to the division: e over x, 1 / sum to inv
+// stage 2 (split_rows.h) on one score row in scratch: e over x, 1 / sum to inv
 __global__ __launch_bounds__(SM_THREADS) void gqa_split_softmax_kernel(const SplitArgs s) {
-    __shared__ float tile[2][SM_TILE];
-    __shared__ float red[SM_THREADS / 64];
-    const int tid = threadIdx.x, row = blockIdx.x;
-    const int kv_len = unit_of(s, row / s.p.G).kv_len;
-    float *x = s.e + (int64_t)row * s.Tp;
-    float mx = -3.40282347e+38f; // f32::MIN (softmax.rs:181)
-    for (int i = tid; i < kv_len; i += SM_THREADS) mx = fmaxf(mx, x[i]);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if ((tid & 63) == 0) red[tid >> 6] = mx;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < SM_THREADS / 64; w++) mx = fmaxf(mx, red[w]);
-    float a = 0.f;
-    for (int t0 = 0, it = 0; t0 < kv_len; t0 += SM_TILE, it++) {
-        float *buf = tile[it & 1];
-        float xv[SM_TILE / SM_THREADS];
-#pragma unroll
-        for (int j = 0; j < SM_TILE / SM_THREADS; j++) {
-            const int i = t0 + j * SM_THREADS + tid;
-            xv[j] = i < kv_len ? x[i] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < SM_TILE / SM_THREADS; j++) {
-            const int i = t0 + j * SM_THREADS + tid;
-            if (i < kv_len) {
-                const float e = vm::exp_reduced(xv[j] - mx);
-                x[i] = e;
-                buf[j * SM_THREADS + tid] = e;
-            }
-        }
-        __syncthreads();
-        // the 16 ordered chains; the other waves go on to fill the other tile, and meet this wave again at the next barrier before they come back to this one
-        if (tid < 16) {
-            const int n = kv_len - t0 < SM_TILE ? kv_len - t0 : SM_TILE;
-            int i = tid;
-            for (; i + 16 * 7 < n; i += 16 * 8) { // eight reads in flight, then the eight adds in index order
-                float v[8];
-#pragma unroll
-                for (int j = 0; j < 8; j++) v[j] = buf[i + 16 * j];
-#pragma unroll
-                for (int j = 0; j < 8; j++) a = a + v[j];
-            }
-            for (; i < n; i += 16) a = a + buf[i];
-        }
-    }
-    if (tid < 64) {
-        float sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; k++) sum = sum + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a), k));
-        if (tid == 0) s.inv[row] = 1.0f / sum;
-    }
+    const int row = blockIdx.x;
+    split_softmax_row(s.e + (int64_t)row * s.Tp, unit_of(s, row / s.p.G).kv_len, s.inv + row);
 }
 
 // one 8-key depth block of column n for the G heads: the fmaf chains from zero over `depth` keys, probabilities from LDS (row stride kt)
@@ -231,47 +180,13 @@ __global__ __launch_bounds__(SPL_THREADS) void gqa_split_pv_kernel(const SplitAr
     }
 }
 
+// stage 4 (split_rows.h) on 32 output columns of one row
 __global__ __launch_bounds__(256) void gqa_split_fold_kernel(const SplitArgs s) {
-    __shared__ float4 tile[FOLD_TILE][FOLD_COLS / 4];
     const GqaArgs &p = s.p;
-    const int tid = threadIdx.x, D = p.D, slices = D / FOLD_COLS;
+    const int D = p.D, slices = D / FOLD_COLS;
     const int row = blockIdx.x / slices, cs = blockIdx.x % slices * FOLD_COLS;
     const Unit u = unit_of(s, row / p.G);
-    const int nblk = (u.kv_len + 7) / 8;
-    const float *src = s.bs + (int64_t)row * s.NB * D + cs;
-    const int rr = tid >> 3, c4 = tid & 7;
-    float4 reg[4];
-    auto load = [&](int b0) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int blk = b0 + rr + 32 * i;
-            reg[i] = blk < nblk ? *reinterpret_cast<const float4 *>(src + (int64_t)blk * D + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    load(0);
-    float o = 0.f;
-    for (int b0 = 0; b0 < nblk; b0 += FOLD_TILE) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) tile[rr + 32 * i][c4] = reg[i];
-        __syncthreads();
-        if (b0 + FOLD_TILE < nblk) load(b0 + FOLD_TILE);
-        if (tid < FOLD_COLS) {
-            const float *tf = reinterpret_cast<const float *>(&tile[0][0]);
-            const int cnt = nblk - b0 < FOLD_TILE ? nblk - b0 : FOLD_TILE;
-            int j = 0;
-            if (b0 == 0) o = tf[tid], j = 1; // the first block is stored, the rest are added
-            for (; j + 7 < cnt; j += 8) {
-                float v[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) v[i] = tf[(j + i) * FOLD_COLS + tid];
-#pragma unroll
-                for (int i = 0; i < 8; i++) o = o + v[i];
-            }
-            for (; j < cnt; j++) o = o + tf[j * FOLD_COLS + tid];
-        }
-        __syncthreads();
-    }
-    if (tid < FOLD_COLS) p.out[(int64_t)u.b * p.H * D + ((int64_t)u.g * p.G + row % p.G) * D + cs + tid] = o;
+    split_fold_row(s.bs + (int64_t)row * s.NB * D + cs, (u.kv_len + 7) / 8, D, p.out + (int64_t)u.b * p.H * D + ((int64_t)u.g * p.G + row % p.G) * D + cs);
 }
 
 struct SplitPlan {

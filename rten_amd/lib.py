@@ -200,6 +200,7 @@ PROTOTYPES = {
     "rten_hip_set_gqa_split": (_I32, [_VP, _I32]),
     "rten_hip_attention_f32": (_I32, [_VP, C.POINTER(_I32), C.POINTER(_I64), _F32] + [_VP] * 10),
     "rten_hip_set_attention_path": (_I32, [_VP, _I32]),
+    "rten_hip_set_attention_split": (_I32, [_VP, _I32]),
     "rten_hip_batch_norm_f32": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _F32, _VP]),
     "rten_hip_batch_norm_f32_act": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _VP, _VP, _F32, _I32, _F32, _F32, _VP]),
     "rten_hip_instance_norm_f32": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _F32, _I32, _F32, _F32, _VP]),

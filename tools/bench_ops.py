@@ -726,17 +726,21 @@ def main():
     # ---- Attention (opset 23) with past / present caches (rten_amd/csrc/attention_kv.hip; --only attention_kv: selects these rows): decode at Hq 32 / Hkv 8 /
     # D 128, one new row appended to a cache of kv_len - 1 rows, present written: the cache-appending decode kernel (mode 2: one launch) against the composed
     # path of the same library (mode 1: concatenation launch, gemv, score kernel, gemv), beside the yardstick -- rten_hip_gqa_f32 on the same shape on its
-    # one-workgroup decode kernel (rten_hip_set_gqa_path 2), its prepare-and-append launch included.  The three are measured alternately, three runs each.
+    # one-workgroup decode kernel (rten_hip_set_gqa_path 2) and on its dispatch rule, the prepare-and-append launch included.  They are measured alternately,
+    # three runs each.  The split decode form (attention_split.hip, mode 3) and the dispatch rule (mode 0) are further rows, with a sweep of the keys per
+    # workgroup at batch 1; kv_len 16384 is past the one-workgroup kernels' LDS bound at G 4.  A library without rten_hip_set_attention_split (the parent's,
+    # when the two are timed alternately) skips the split rows.
     if want("attention_kv:"):
         hq_, hkv_, d_ = 32, 8, 128
+        has_split = hasattr(ctx.lib, "rten_hip_set_attention_split")
 
         def zeros_(*shape, dt=np.float32):
             t_ = empty(shape, dt)
             ctx.call("rten_hip_memset", t_.vp, 0, C.c_size_t(t_.size * 4))
             return t_
 
-        for b_ in (1, 32):
-            for kvl in (512, 2048, 4096):
+        for b_ in (1, 4, 32):
+            for kvl in (512, 2048, 4096, 16384):
                 p_ = kvl - 1
                 q_, k_, v_, o_ = zeros_(b_, 1, hq_ * d_), zeros_(b_, 1, hkv_ * d_), zeros_(b_, 1, hkv_ * d_), zeros_(b_, 1, hq_ * d_)
                 pk_, pv_, ok_, ov_ = zeros_(b_, hkv_, p_, d_), zeros_(b_, hkv_, p_, d_), zeros_(b_, hkv_, kvl, d_), zeros_(b_, hkv_, kvl, d_)
@@ -751,14 +755,28 @@ def main():
                 shape = f"batch={b_} kv_len={kvl} heads={hq_} kv_heads={hkv_} head_size={d_}"
                 kv_bytes = 8.0 * b_ * hkv_ * kvl * d_
                 for run in (1, 2, 3):
-                    ctx.call("rten_hip_set_attention_path", 2)
-                    hbm(f"attention_kv: decode, cache-appending kernel (mode 2), run {run}", shape, attn, 2 * kv_bytes)
+                    if kvl <= 8064:
+                        ctx.call("rten_hip_set_attention_path", 2)
+                        hbm(f"attention_kv: decode, cache-appending kernel (mode 2), run {run}", shape, attn, 2 * kv_bytes)
                     ctx.call("rten_hip_set_attention_path", 1)
                     hbm(f"attention_kv: decode, composed path (mode 1), run {run}", shape, attn, 2 * kv_bytes)
+                    if has_split:
+                        ctx.call("rten_hip_set_attention_path", 3)
+                        hbm(f"attention_kv: decode, split form (mode 3), run {run}", shape, attn, 2 * kv_bytes)
                     ctx.call("rten_hip_set_attention_path", 0)
-                    ctx.call("rten_hip_set_gqa_path", 2)
-                    hbm(f"attention_kv: yardstick, rten_hip_gqa_f32 one-workgroup decode with its prepare launch, run {run}", shape, gqa, 2 * kv_bytes)
+                    hbm(f"attention_kv: decode, dispatch rule (mode 0), run {run}", shape, attn, 2 * kv_bytes)
+                    if kvl <= 8064:
+                        ctx.call("rten_hip_set_gqa_path", 2)
+                        hbm(f"attention_kv: yardstick, rten_hip_gqa_f32 one-workgroup decode with its prepare launch, run {run}", shape, gqa, 2 * kv_bytes)
                     ctx.call("rten_hip_set_gqa_path", 0)
+                    hbm(f"attention_kv: yardstick, rten_hip_gqa_f32 dispatch rule with its prepare launch, run {run}", shape, gqa, 2 * kv_bytes)
+                if has_split and b_ == 1:
+                    ctx.call("rten_hip_set_attention_path", 3)
+                    for ck in (16, 32, 64, 128, 256, 1024):
+                        ctx.call("rten_hip_set_attention_split", ck)
+                        hbm(f"attention_kv: decode, split form (mode 3), {ck} keys per workgroup", shape, attn, 2 * kv_bytes)
+                    ctx.call("rten_hip_set_attention_split", 0)
+                    ctx.call("rten_hip_set_attention_path", 0)
                 del q_, k_, v_, o_, pk_, pv_, ok_, ov_, sl_, tot_
 
     if args.cpu_baseline:
