@@ -50,7 +50,8 @@
 extern "C" {
 #endif
 
-/* v8, later additions without a bump: + rten_hip_set_attention_split and mode 3 of rten_hip_set_attention_path (Attention's decode form that spreads the
+/* v8, later additions without a bump: + rten_hip_set_nbits_path (MatMulNBits with more than one row: the fused dequantising MFMA kernel or expand + GEMM);
+ * + rten_hip_set_attention_split and mode 3 of rten_hip_set_attention_path (Attention's decode form that spreads the
  * key range over workgroups); + rten_hip_attention_f32, rten_hip_set_attention_path (opset-23 Attention with past / present caches);
  * + rten_hip_gqa_f32, rten_hip_set_gqa_path (GroupQueryAttention with a KV cache; dims and strides as host arrays);
  * + rten_hip_set_gqa_split and mode 3 of rten_hip_set_gqa_path (the decode form that spreads the key range over workgroups).
@@ -871,6 +872,13 @@ int32_t rten_hip_set_rnn_path(rten_hip_ctx *ctx, int32_t mode);
  * rows == 1 reproduces the reference's 64-slot accumulation order, rows > 1 its f32 GEMM on the dequantised matrix. */
 int32_t rten_hip_matmul_nbits_f32(rten_hip_ctx *ctx, int64_t batch, int32_t rows, int32_t k, int32_t n, int32_t block_size, const float *a,
                                   const uint8_t *b_quant, const float *scales, float *y);
+/* More than one row (batch * rows >= 2 with rows > 1) runs on one of two routes with the same bits.  The fused kernel dequantises the packed weights on
+ * the way into LDS and multiplies with MFMA chains: no f32 copy of the weights, no scratch, nothing allocated -- legal inside a capture with no warm-up
+ * call; block sizes up to 256.  The older route expands the weights to f32 in the auxiliary scratch and calls the f32 GEMM.
+ * rten_hip_set_nbits_path: 0 the rule (the fused kernel up to the row count at which it was measured ahead, docs/KERNELS.md 4.20), 1 expand + GEMM only,
+ * 2 the fused kernel or RTEN_HIP_ERR_UNSUPPORTED where it does not cover the call (block_size > 256); any other mode is RTEN_HIP_ERR_INVALID_VALUE.
+ * rows == 1 takes the vector kernel in every mode. */
+int32_t rten_hip_set_nbits_path(rten_hip_ctx *ctx, int32_t mode);
 
 /* ---- pooling: src/ops/pooling.rs:174-389,392-417,516-521,581-600 ---- */
 typedef struct {

@@ -58,6 +58,7 @@ struct rten_hip_ctx {
     int gqa_split = 0;  // keys per workgroup of the split decode form: 0 = the rule, else a positive multiple of 8 (gqa_split.hip)
     int attention_path = 0; // Attention (opset 23): 0 automatic, 1 composed path only, 2 the cache-appending decode kernel or an error, 3 the split decode form or an error (attention_kv.hip)
     int attention_split = 0; // keys per workgroup of that split decode form: 0 = the rule, else a positive multiple of 8 (attention_split.hip)
+    int nbits_path = 0; // MatMulNBits with more than one row: 0 automatic, 1 expand + GEMM only, 2 the fused dequantising MFMA kernel or an error (matmul_nbits_gemm.hip)
     int rnn_path = 0;   // GRU / LSTM: 0 automatic, 1 composed path only (per-step GEMM + gate kernel), 2 the time-persistent fused kernel or an error (rnn.hip)
     int instance_norm_path = 0; // InstanceNormalization: 0 automatic, 1 streaming form, 2 LDS-resident form where the slice fits, else streaming (norm.hip)
     int int8_path = 0;  // 0 automatic (fast staging path when it covers the call), 1 generic kernel only
@@ -102,6 +103,12 @@ int32_t rten_gemv_f32(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const floa
 // gemm_f32.hip: rten_hip_gemm_f32 without the gemv dispatch (operators whose reference form is not a gemm_impl call on unpacked operands)
 int32_t rten_gemm_f32_blocked(rten_hip_ctx *ctx, const rten_hip_gemm_desc *d, const float *a, const float *b, const float *bias, float *c);
 void *rten_aux_scratch(rten_hip_ctx *ctx, size_t bytes);
+// matmul_nbits_gemm.hip: MatMulNBits on m = batch * rows >= 2 rows with the 4-bit weights dequantised into LDS (no scratch, nothing allocated).
+// covers: the calls it takes (block sizes <= 256), which the launcher expects checked; pays: the automatic rule of rten_hip_matmul_nbits_f32 (measured,
+// docs/KERNELS.md 4.20).
+bool rten_nbits_gemm_covers(long long m, int block_size);
+bool rten_nbits_gemm_pays(long long m, int n);
+int32_t rten_launch_nbits_gemm(rten_hip_ctx *ctx, long long m, int k, int n, int block_size, const float *a, const uint8_t *q, const float *sc, float *y);
 // The f32 GEMM kernel families, one translation unit each (gemm_f32_<family>.hip), launched by the plans of gemm_f32.hip.  `args` = the caller's
 // GemmArgs (gemm_f32_common.h); bm x bn = tile shape, al / bl = operand layouts (ALoad / BLoad), mode = 0 one depth block, 1 several, 2 split-K
 // producer; flops / bytes = the launch's share of the call for the profiler.  Each launcher names, brackets (ProfScope) and checks its launch.

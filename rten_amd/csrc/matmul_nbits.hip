@@ -2,9 +2,10 @@
 // quant [N][K/bs][bs/2] bytes (element 2j low nibble, 2j+1 high nibble of byte j), scales [N][K/bs], zero point 8;
 // a weight is (float)(q - 8) * scale, one rounded multiply (packing.rs:300-312, block_quant.rs:243-262).
 //
-//  rows > 1 (contrib.rs:86-100): the reference dequantises while packing and runs its ordinary f32 GEMM.  Here one kernel
-//      expands the weights to f32 [N][K] in the auxiliary scratch and the MFMA GEMM reads them through strides (B[k][n] at
-//      n*K + k) -- the same k-ordered FMA chain in 256-deep blocks, so results are bit-identical for block sizes <= 256.
+//  rows > 1 (contrib.rs:86-100): the reference dequantises while packing and runs its ordinary f32 GEMM.  Two routes (rten_hip_set_nbits_path):
+//      the fused kernel of matmul_nbits_gemm.hip dequantises on the way into LDS (block sizes <= 256); the older route expands the weights to
+//      f32 [N][K] in the auxiliary scratch with one kernel and the MFMA GEMM reads them through strides (B[k][n] at n*K + k).  Both are the
+//      same k-ordered FMA chain in 256-deep blocks, so results are bit-identical for block sizes <= 256.
 //  rows == 1 (block_quant.rs:166-389, the AVX-512 instantiation): 64 accumulator slots per column, slot s owning
 //      k = s, s + 64, ... with one FMA per element; slots are then folded (s ^ 16, s ^ 32, then halves 8, 4, 2, 1) and a
 //      scalar tail handles K % 128.  64 / SPL lanes share a column, each owning SPL adjacent slots (SPL / 2 bytes of every
@@ -199,6 +200,13 @@ void launch_gemv4(rten_hip_ctx *ctx, int u, int64_t batch, int k, int n, int bs,
 
 } // namespace
 
+RTEN_EXPORT int32_t rten_hip_set_nbits_path(rten_hip_ctx *ctx, int32_t mode) {
+    RTEN_CHECK_CTX(ctx);
+    if (mode < 0 || mode > 2) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "set_nbits_path: mode must be 0, 1 or 2");
+    ctx->nbits_path = mode;
+    return RTEN_HIP_OK;
+}
+
 // a [batch][rows][k]; b_quant [n][k / block_size][block_size / 2]; scales [n][k / block_size]; y [batch][rows][n].
 RTEN_EXPORT int32_t rten_hip_matmul_nbits_f32(rten_hip_ctx *ctx, int64_t batch, int32_t rows, int32_t k, int32_t n, int32_t block_size, const float *a,
                                               const uint8_t *b_quant, const float *scales, float *y) {
@@ -229,6 +237,12 @@ RTEN_EXPORT int32_t rten_hip_matmul_nbits_f32(rten_hip_ctx *ctx, int64_t batch, 
         return RTEN_HIP_OK;
     }
     if (batch * rows > 0x7fffffffLL) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "matmul_nbits: too many rows");
+    // rows > 1: the fused dequantise-into-LDS MFMA kernel (matmul_nbits_gemm.hip) where it covers the call and the rule sends it there, else expand + GEMM
+    const bool covered = rten_nbits_gemm_covers(batch * rows, block_size);
+    if (ctx->nbits_path == 2 && !covered)
+        return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "matmul_nbits: the fused kernel takes block sizes up to 256 and 16 * 65535 rows (rten_hip_set_nbits_path 2)");
+    if (covered && (ctx->nbits_path == 2 || (ctx->nbits_path == 0 && rten_nbits_gemm_pays(batch * rows, n))))
+        return rten_launch_nbits_gemm(ctx, batch * rows, k, n, block_size, a, b_quant, scales, y);
     const long long words = (long long)n * k / 8;
     float *bm = (float *)rten_aux_scratch(ctx, (size_t)n * k * sizeof(float));
     if (!bm) return rten_set_error(ctx, RTEN_HIP_ERR_HIP, "matmul_nbits: weight expansion buffer allocation failed (or attempted during graph capture)");

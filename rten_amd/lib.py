@@ -247,6 +247,7 @@ PROTOTYPES = {
     "rten_hip_conv_transpose_output_size": (_I32, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP]),
     "rten_hip_conv_transpose2d_f32": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "rten_hip_matmul_nbits_f32": (_I32, [_VP, _I64, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "rten_hip_set_nbits_path": (_I32, [_VP, _I32]),
     "rten_hip_add_channel_bias_f32": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP]),
     "rten_hip_max_pool2d_f32": (_I32, [_VP, C.POINTER(Pool2dDesc), _VP, _VP]),
     "rten_hip_max_pool2d_f32_stats": (_I32, [_VP, C.POINTER(Pool2dDesc), _VP, _VP, _VP]),

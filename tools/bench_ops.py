@@ -246,17 +246,31 @@ def main():
          2.0 * 32 * 64 * 28 * 28 * 32 * 16, F32_PEAK_TF, "TFLOP/s")
 
     # ---- MatMulNBits on LLM-decoder projections (4-bit blocks of 32): decode (1 row, bound by streaming the packed weights) on a
-    # 4096 x 4096 attention projection and a 4096 x 14336 FFN up-projection, and a 128-row prefill
-    for (kq, nq, rows_list) in ((4096, 4096, (1, 128)), (4096, 14336, (1,))):
+    # 4096 x 4096 attention projection and a 4096 x 14336 FFN up-projection, and M = 2 .. 2048 rows (verify steps, prompt chunks, prefill) on both routes
+    # of rten_hip_set_nbits_path -- expand + GEMM (1), the fused dequantising MFMA kernel (2) -- and on the rule (0).  A library without the setter (an
+    # older build under RTEN_HIP_LIBRARY) gets one row per shape.
+    nbits_modes = ((1, "expand + GEMM"), (2, "fused"), (0, "rule")) if hasattr(ctx.lib, "rten_hip_set_nbits_path") else ((None, "no setter"),)
+    # (4096 x 1024, the K / V projection of a grouped-query model, is the narrow matrix: its 64-wide column tiles leave compute units without a workgroup)
+    for (kq, nq) in ((4096, 4096), (4096, 14336), (4096, 1024)):
         bsq = 32
+        if not any(want(o) for o in ["MatMulNBits decode"] + [f"MatMulNBits prefill ({label})" for _, label in nbits_modes]):
+            break  # (no weights uploaded for a run that wants none of these rows)
         wq, wsc = dev(rng.integers(0, 256, (nq, kq // bsq, bsq // 2)).astype(np.uint8)), dev(rng.random((nq, kq // bsq), dtype=np.float32) * 0.01)
-        for rows_q in rows_list:
+        for rows_q in (1, 2, 4, 8, 16, 32, 48, 64, 128, 192, 256, 384, 512, 2048):
             xq, yq = dev(rng.standard_normal((rows_q, kq), dtype=np.float32)), empty((rows_q, nq))
             fn = (lambda xq=xq, yq=yq, rows_q=rows_q, kq=kq, nq=nq, wq=wq, wsc=wsc: ctx.call("rten_hip_matmul_nbits_f32", 1, rows_q, kq, nq, bsq, xq.vp, wq.vp, wsc.vp, yq.vp))
             if rows_q == 1:
                 hbm("MatMulNBits decode", f"1x{kq}x{nq} q4/{bsq}", fn, nq * kq / 2 + 4.0 * (nq * kq // bsq + kq + nq))
-            else:
-                mfma("MatMulNBits prefill", f"{rows_q}x{kq}x{nq} q4/{bsq}", fn, 2.0 * rows_q * kq * nq, F32_PEAK_TF, "TFLOP/s")
+                continue
+            for mode, label in nbits_modes:
+                if mode is not None:
+                    ctx.call("rten_hip_set_nbits_path", mode)
+                if not want(f"MatMulNBits prefill ({label})"):
+                    continue
+                mfma(f"MatMulNBits prefill ({label})", f"{rows_q}x{kq}x{nq} q4/{bsq}", fn, 2.0 * rows_q * kq * nq, F32_PEAK_TF, "TFLOP/s")
+                rows[-1]["packed_weight_stream_us"] = round((nq * kq / 2 + 4.0 * (nq * kq // bsq)) / HBM_PEAK_GBS / 1e3, 2)  # the packed weights and scales once at the HBM peak
+            if nbits_modes[0][0] is not None:
+                ctx.call("rten_hip_set_nbits_path", 0)
 
     # ---- ReduceSum through strides and Einsum (src/ops/reduce.rs, src/ops/einsum.rs): a contiguous last-axis sum, a column sum over
     # the strided axis (nothing packed), and the two attention products written as Einsum on un-transposed [B, S, H, D]
