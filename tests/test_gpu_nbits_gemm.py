@@ -1,6 +1,6 @@
 """MatMulNBits with more than one row on the fused kernel (rten_amd/csrc/matmul_nbits_gemm.hip, rten_hip_set_nbits_path 2): bit for bit against the oracle at
-every tile edge, inside the forward error bound of an f32 FMA chain against float64, on scales whose eightfold overflows, on every mode of the setter, and
-captured into a hipGraph on a context that never ran the shape eagerly."""
+every tile edge, between guards (tests/confine.py) on both tiles and with non-finite rows and columns, inside the forward error bound of an f32 FMA chain
+against float64, on scales whose eightfold overflows, on every mode of the setter, and captured into a hipGraph on a context that never ran the shape eagerly."""
 import functools
 
 import numpy as np
@@ -9,6 +9,8 @@ import pytest
 from oracle import ref
 from rten_amd import lib as L
 from rten_amd.tensor import DeviceTensor
+from tests import attention_cases as AC
+from tests import confine as K
 from tests import range_cases as RC
 from tests.reduce_rules import same_bits
 
@@ -17,11 +19,7 @@ pytestmark = pytest.mark.gpu
 AUTO, EXPAND, FUSED = 0, 1, 2  # rten_hip_set_nbits_path
 
 
-def draw(lead, k, n, bs, seed=1234):
-    """Operands as tests/test_gpu_parity.py::test_matmul_nbits draws them: lhs [*lead, k] in [-0.5, 0.5), every code, scales in [0, 1)."""
-    rng = ref.XorShiftRng(seed)
-    lhs = (rng.f32(int(np.prod(lead)) * k) - F(0.5)).reshape(*lead, k)
-    return lhs, rng.u8(n * (k // 2)).reshape(n, k // bs, bs // 2), rng.f32(n * (k // bs)).reshape(n, k // bs)
+draw = AC.nbits_operands  # lhs [*lead, k] in [-0.5, 0.5), every code, scales in [0, 1), as tests/test_gpu_parity.py::test_matmul_nbits draws them
 
 
 def shifted(ctx, arr, nbytes):  # `arr` on the device, `nbytes` past the start of an allocation of its own
@@ -66,6 +64,46 @@ def test_bits_equal_the_oracle(ctx, tile, m, k, bs):
     for n in (1, 24, 65, 130):  # partial column tiles of 16 and of 64
         operands, want = case(m if isinstance(m, tuple) else (m,), k, n, bs)
         same_bits(run(ctx, *operands), want, f"tile {tile} M {m} N {n} K {k} block {bs}")
+
+
+def run_guarded(ctx, lhs, quant, scales, mode=FUSED, quant_fill=K.FILL):
+    """`run` with lhs, quant, scales and y each in a tests/confine.py allocation: y one element off its 16 bytes with a full 128 x 128 tile of guard past
+    the matrix, the inputs' guards NaN (quant's: `quant_fill` in every byte) -> y, confined."""
+    n, bs = quant.shape[0], 2 * quant.shape[2]
+    rows = int(np.prod(lhs.shape[:-1], dtype=np.int64))
+    ld, qd, sd = K.Guarded(ctx, lhs), K.Guarded(ctx, quant, fill=quant_fill), K.Guarded(ctx, scales)
+    guard = K.gemm_guard(n)
+    yd = K.Guarded(ctx, rows * n * 4, lead=1, front=guard, back=guard)
+    ctx.call("rten_hip_set_nbits_path", mode)
+    try:
+        ctx.call("rten_hip_matmul_nbits_f32", int(np.prod(lhs.shape[:-2], dtype=np.int64)), lhs.shape[-2], lhs.shape[-1], n, bs, ld.vp, qd.vp, sd.vp, yd.vp)
+        ctx.sync()
+    finally:
+        ctx.call("rten_hip_set_nbits_path", AUTO)
+    y = yd.check(yd.raw(), (rows, n), (n, 1), F, f"matmul_nbits rows {lhs.shape[:-1]} N {n} K {lhs.shape[-1]} block {bs}", axes=("row", "column"))
+    return y.reshape(*lhs.shape[:-1], n)
+
+
+@pytest.mark.parametrize("k,bs", [(16, 16), (272, 16), (768, 128)])
+@pytest.mark.parametrize("m", [2, 17, 65, (3, 5)])
+def test_writes_only_its_matrix(ctx, tile, m, k, bs):
+    for n in (1, 24, 65, 130):
+        operands, want = case(m if isinstance(m, tuple) else (m,), k, n, bs)
+        for fill in K.FILLS_8BIT:  # 0xFF nibbles dequantise to a finite 7 s: a stray load of packed weights cannot hide in both fills
+            same_bits(run_guarded(ctx, *operands, quant_fill=fill), want, f"tile {tile} M {m} N {n} K {k} block {bs} quant guard 0x{fill:02x}")
+
+
+def test_nan_row_and_nan_scale_column_stay_put(ctx, tile):
+    """A NaN row and an Inf in lhs, a NaN column and an Inf in the scales, on a shape ragged in both directions with a 16-deep tail (tile "1": the four-wave
+    fold): bits against the oracle, whose result tests/test_attention_cases.py shows to differ from the finite one on exactly those rows and columns."""
+    m, k, n, bs = AC.NBITS_NONFINITE_SHAPE
+    (lhs, quant, scales), fin = case((m,), k, n, bs)
+    bad_lhs, bad_scales, dep = AC.nbits_nonfinite(lhs, scales)
+    with np.errstate(all="ignore"):
+        want = ref.matmul_nbits_f32(bad_lhs, quant, bad_scales)
+    got = run_guarded(ctx, bad_lhs, quant, bad_scales)
+    same_bits(got, want, f"tile {tile}: non-finite rows and columns")
+    same_bits(got[~dep], fin[~dep], f"tile {tile}: outside the dependency set against the finite run")
 
 
 @pytest.mark.parametrize("shift", [(4, 0), (0, 1), (8, 4), (12, 7)])  # lhs off 16 bytes: dword loads; packed weights off 8 bytes: byte loads
