@@ -510,7 +510,12 @@ int32_t rten_hip_set_gqa_split(rten_hip_ctx *ctx, int32_t keys_per_workgroup);
  * present while they do; score rows and 8-key block sums live in scratch (at most 64 MiB per pass over the (batch, KV head) pairs, or one pair's rows), and
  * the result has the same bits for every split.  The rule takes it where the decode kernel does not cover such a call, and where B * Hkv workgroups
  * under-fill the device at a cache long enough to pay for its extra launches.  rten_hip_set_attention_path: 0 that rule, 1 the composed path only, 2 the
- * decode kernel or RTEN_HIP_ERR_UNSUPPORTED, 3 the split decode form or RTEN_HIP_ERR_UNSUPPORTED.  rten_hip_set_attention_split: the split form's keys
+ * decode kernel or RTEN_HIP_ERR_UNSUPPORTED, 3 the split decode form or RTEN_HIP_ERR_UNSUPPORTED, 4 the fused prefill kernel or RTEN_HIP_ERR_UNSUPPORTED;
+ * any other mode is RTEN_HIP_ERR_INVALID_VALUE.  The fused prefill kernel (attention_prefill.hip) takes more than one query row, or one row with the gemv
+ * order off, D == Dv in {64, 128} and 16-byte aligned K and V: one launch per call after the concatenation launch (none when K and V are contiguous 4-D
+ * with no past and present is not wanted), no score buffer, the composed path's bits; it needs scratch only when present is not wanted and K / V cannot be
+ * read in place.  The rule takes it on causal first prompts without a mask from 8192 keys at D 128 and from 2048 keys at D 64, on at least 1024 strips of
+ * 64 rows over all (batch, head) pairs.  rten_hip_set_attention_split: the split form's keys
  * per workgroup, 0 (the rule, from B, Hkv and T) or a positive multiple of 8; anything else is RTEN_HIP_ERR_INVALID_VALUE. */
 #define RTEN_HIP_ATTENTION_NDIMS 10
 #define RTEN_HIP_ATTENTION_NSTRIDES 16

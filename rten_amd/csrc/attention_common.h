@@ -36,10 +36,13 @@ static __device__ __forceinline__ int masked_from(const AttnArgs &p, int np, int
 }
 
 // steps 1-3 on one score; mrow = the mask's row (b, h, s), already offset
-static __device__ __forceinline__ float modified(const AttnArgs &p, float o, const void *mrow, int t, int from) {
-    if (p.mask_kind == RTEN_HIP_ATTN_MASK_FLOAT) o = o + ((const float *)mrow)[t * p.m_st];
-    else if (p.mask_kind == RTEN_HIP_ATTN_MASK_BOOL && ((const int32_t *)mrow)[t * p.m_st] == 0) o = NEG_INF;
+static __device__ __forceinline__ float modified_at(const AttnArgs &p, float o, const void *mrow, int64_t at, int t, int from) {
+    if (p.mask_kind == RTEN_HIP_ATTN_MASK_FLOAT) o = o + ((const float *)mrow)[at];
+    else if (p.mask_kind == RTEN_HIP_ATTN_MASK_BOOL && ((const int32_t *)mrow)[at] == 0) o = NEG_INF;
     return t >= from ? NEG_INF : o;
+}
+static __device__ __forceinline__ float modified(const AttnArgs &p, float o, const void *mrow, int t, int from) {
+    return modified_at(p, o, mrow, t * p.m_st, t, from); // (`at` apart: attention_prefill.hip forms the element offset itself)
 }
 
 static __device__ __forceinline__ const void *mask_row(const AttnArgs &p, int b, int h, int s) {
@@ -55,3 +58,9 @@ int32_t rten_attn_split_launch(rten_hip_ctx *ctx, const AttnArgs &a, int keys_pe
 // the rule's chunk length for a call's dims, and whether mode 0 prefers the split form to a one-workgroup kernel that covers the call
 int rten_attn_split_keys(const rten_hip_ctx *ctx, const AttnArgs &a);
 bool rten_attn_split_pays(const rten_hip_ctx *ctx, const AttnArgs &a);
+
+// attention_prefill.hip.  Whether the fused prefill kernel takes a call's shapes (the caller has checked that the call is not a one-row call in the gemv
+// order): D == Dv in {64, 128}.  Its launch: kc and vc are K and V as contiguous [B, Hkv, T, D], 16-byte aligned (the inputs read in place, present or
+// scratch, as on the composed path).  It allocates nothing.
+bool rten_attn_prefill_covers(const AttnArgs &a);
+int32_t rten_attn_prefill_launch(rten_hip_ctx *ctx, const AttnArgs &a, const float *kc, const float *vc);

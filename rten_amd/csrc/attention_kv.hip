@@ -27,6 +27,8 @@
 //   * the split decode form (attention_split.hip; Sq == 1, gemv order on, D and Dv each 64 or 128, G <= 512, no LDS bound): the key range of one (batch, KV
 //     head) spread over workgroups in four dependent launches, same arithmetic.  The rule takes it where the kernel above does not cover such a call, and where
 //     B * Hkv workgroups under-fill the device at a cache long enough to pay for the extra launches (rten_attn_split_pays).
+//   * the fused prefill kernel (attention_prefill.hip; more than one query row, or one row in the blocked order, D == Dv in {64, 128}): the composed path's
+//     two products and its score kernel in one launch with no score buffer, same bits.  Mode 4, and mode 0 where prefill_pays() holds.
 //   * attn_concat_kernel: present_key and present_value of the composed path in one launch (into scratch when the caller does not want them and the
 //     GEMMs cannot read the inputs in place).
 //   * attn_scores_kernel: the score modification and softmax_row on a scratch row, one wave per row, between the two GEMMs of the composed path (any D,
@@ -205,6 +207,16 @@ size_t decode_lds_bytes(int G, int D, int T) { return sizeof(float) * ((size_t)G
 constexpr size_t LDS_PER_WORKGROUP = 160 * 1024;
 constexpr size_t SCORE_PASS_BYTES = 64u << 20; // the composed path's score buffer per pass over the query rows
 
+// Whether mode 0 prefers the fused prefill kernel (attention_prefill.hip) to the composed path for a call that kernel covers: the measured range of
+// docs/KERNELS.md 4.19.  Causal first prompts (no past, as many rows as keys) without a mask, from 8192 keys at head size 128 (20.1 against 35.0 ms at
+// Hq 32 / Hkv 8) and from 2048 keys at head size 64 (0.96 against 1.07 ms), on at least the 1024 workgroups of the smaller of those two rows.  It loses
+// at 128 .. 2048 keys at head size 128, on the chunked prompt and on the non-causal one: those stay on the composed path.
+bool prefill_pays(const AttnArgs &a) {
+    if (!a.causal || a.P != 0 || a.Sq != a.T || a.mask_kind != RTEN_HIP_ATTN_MASK_NONE) return false;
+    if ((int64_t)a.B * a.Hq * ((a.Sq + 63) / 64) < 1024) return false;
+    return a.D == 128 ? a.T >= 8192 : a.T >= 2048;
+}
+
 template <int D>
 int32_t launch_decode(rten_hip_ctx *ctx, const AttnArgs &a, size_t lds) {
     // the kernel's dynamic LDS ceiling, raised once per device (not a stream operation: nothing lands in a capture)
@@ -226,7 +238,7 @@ int32_t launch_decode(rten_hip_ctx *ctx, const AttnArgs &a, size_t lds) {
 
 RTEN_EXPORT int32_t rten_hip_set_attention_path(rten_hip_ctx *ctx, int32_t mode) {
     RTEN_CHECK_CTX(ctx);
-    if (mode < 0 || mode > 3) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "set_attention_path: mode must be 0, 1, 2 or 3");
+    if (mode < 0 || mode > 4) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "set_attention_path: mode must be 0 .. 4");
     ctx->attention_path = mode;
     return RTEN_HIP_OK;
 }
@@ -270,6 +282,8 @@ RTEN_EXPORT int32_t rten_hip_attention_f32(rten_hip_ctx *ctx, const int32_t *dim
     a.gemv_threads = ctx->gemv_threads;
 
     const bool one_row = a.Sq == 1 && ctx->gemv_order != 0;
+    const char *const prefill_cover = "attention: the fused prefill kernel takes more than one query row, or one row with the gemv order off, equal K and V head sizes of 64 or 128, and 16-byte aligned K and V";
+    if (ctx->attention_path == 4 && (one_row || !rten_attn_prefill_covers(a))) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, prefill_cover);
     const size_t lds = decode_lds_bytes(a.G, a.D, a.T);
     const bool covered = one_row && a.D == a.Dv && (a.D == 64 || a.D == 128) && a.G <= DEC_HC * DEC_MAXCH && lds <= LDS_PER_WORKGROUP;
     if (ctx->attention_path == 2 && !covered)
@@ -281,13 +295,32 @@ RTEN_EXPORT int32_t rten_hip_attention_f32(rten_hip_ctx *ctx, const int32_t *dim
         return rten_attn_split_launch(ctx, a, ctx->attention_split);
     if (covered && ctx->attention_path != 1) return a.D == 64 ? launch_decode<64>(ctx, a, lds) : launch_decode<128>(ctx, a, lds);
 
-    // ---- composed path.  K and V are read in place when there is no past and the inputs are contiguous (B, Hkv, T, *); otherwise out of present, or out
-    // of scratch when the caller does not want present.  Scratch (the auxiliary buffer: the GEMMs called below own `scratch`): [K | V | scores].
+    // ---- the fused prefill kernel and the composed path.  K and V are read in place when there is no past and the inputs are contiguous (B, Hkv, T, *);
+    // otherwise out of present, or out of scratch when the caller does not want present.  Scratch (the auxiliary buffer: the GEMMs called below own
+    // `scratch`): [K | V | scores]; the prefill kernel has no scores and needs none when K and V are read in place or present is supplied.
     const bool in_place = a.P == 0 && a.k_ss == a.D && a.k_sh == (int64_t)a.T * a.D && a.k_sb == (int64_t)a.Hkv * a.T * a.D && a.v_ss == a.Dv &&
                           a.v_sh == (int64_t)a.T * a.Dv && a.v_sb == (int64_t)a.Hkv * a.T * a.Dv;
     const size_t nk = (size_t)a.B * a.Hkv * a.T * a.D, nv = (size_t)a.B * a.Hkv * a.T * a.Dv;
     const bool own_kv = !in_place && !a.pk;
     const size_t kv_pad = own_kv ? (nk + 63) / 64 * 64 + (nv + 63) / 64 * 64 : 0;
+    auto al16 = [](const void *ptr) { return ((uintptr_t)ptr & 15u) == 0; };
+    const bool kv_al16 = in_place ? al16(a.k) && al16(a.v) : (own_kv || (al16(a.pk) && al16(a.pv)));
+    const bool fusable = !one_row && rten_attn_prefill_covers(a) && kv_al16;
+    if (ctx->attention_path == 4 && !fusable) return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, prefill_cover);
+    if (fusable && (ctx->attention_path == 4 || (ctx->attention_path == 0 && prefill_pays(a)))) {
+        if (own_kv) {
+            float *aux = (float *)rten_aux_scratch(ctx, kv_pad * sizeof(float) + 256);
+            if (!aux) return rten_set_error(ctx, RTEN_HIP_ERR_HIP, "attention: scratch allocation failed (warm up before capture)");
+            a.pk = aux + 64;
+            a.pv = a.pk + (nk + 63) / 64 * 64;
+        }
+        if (a.pk) {
+            ProfScope ps(ctx, "attn_concat_kernel", 0.0, 8.0 * (double)(nk + nv));
+            hipLaunchKernelGGL(attn_concat_kernel, dim3((unsigned)ceil_div64((int64_t)(nk + nv), 256)), dim3(256), 0, ctx->stream, a);
+            RTEN_LAUNCH_CHECK(ctx, "attn_concat_kernel");
+        }
+        return rten_attn_prefill_launch(ctx, a, in_place ? a.k : a.pk, in_place ? a.v : a.pv);
+    }
     const size_t row_elems = (size_t)a.B * a.Hq * (size_t)a.T; // one query row of every (batch, head)
     size_t sc_rows = SCORE_PASS_BYTES / sizeof(float) / row_elems;
     sc_rows = sc_rows < 1 ? 1 : (sc_rows > (size_t)a.Sq ? (size_t)a.Sq : sc_rows);

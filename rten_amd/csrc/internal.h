@@ -56,7 +56,7 @@ struct rten_hip_ctx {
     int sdpa_path = 0;  // 0 automatic (fused attention kernel when it covers the shape), 1 composed path only
     int gqa_path = 0;   // GroupQueryAttention: 0 automatic, 1 composed path only, 2 the one-launch decode kernel or an error, 3 the split decode form or an error (gqa.hip)
     int gqa_split = 0;  // keys per workgroup of the split decode form: 0 = the rule, else a positive multiple of 8 (gqa_split.hip)
-    int attention_path = 0; // Attention (opset 23): 0 automatic, 1 composed path only, 2 the cache-appending decode kernel or an error, 3 the split decode form or an error (attention_kv.hip)
+    int attention_path = 0; // Attention (opset 23): 0 automatic, 1 composed path only, 2 the cache-appending decode kernel or an error, 3 the split decode form or an error, 4 the fused prefill kernel or an error (attention_kv.hip)
     int attention_split = 0; // keys per workgroup of that split decode form: 0 = the rule, else a positive multiple of 8 (attention_split.hip)
     int nbits_path = 0; // MatMulNBits with more than one row: 0 automatic, 1 expand + GEMM only, 2 the fused dequantising MFMA kernel or an error (matmul_nbits_gemm.hip)
     int rnn_path = 0;   // GRU / LSTM: 0 automatic, 1 composed path only (per-step GEMM + gate kernel), 2 the time-persistent fused kernel or an error (rnn.hip)

@@ -793,6 +793,34 @@ def main():
                     ctx.call("rten_hip_set_attention_path", 0)
                 del q_, k_, v_, o_, pk_, pv_, ok_, ov_, sl_, tot_
 
+    # ---- Attention (opset 23) prefill (--only "attention_kv: prefill" selects these rows alone): the whole call with present written, 4-D inputs, on the
+    # composed path (mode 1), the fused prefill kernel (attention_prefill.hip, mode 4) and the dispatch rule (mode 0), measured alternately, three runs each.
+    # A library without mode 4 (the parent's, when the two are timed alternately) skips that row.
+    if want("attention_kv: prefill rows"):
+        for b_, sq_, p_, d_, causal_ in ((1, 128, 0, 128, 1), (1, 512, 0, 128, 1), (1, 2048, 0, 128, 1), (1, 8192, 0, 128, 1), (4, 2048, 0, 128, 1),
+                                         (1, 512, 2048, 128, 1), (1, 2048, 0, 128, 0), (1, 2048, 0, 64, 1)):
+            hq_, hkv_, t_ = 32, 8, p_ + sq_
+            q_, o_ = dev(rng.standard_normal((b_, hq_, sq_, d_), np.float32)), empty((b_, hq_, sq_, d_))
+            k_, v_ = dev(rng.standard_normal((b_, hkv_, sq_, d_), np.float32)), dev(rng.standard_normal((b_, hkv_, sq_, d_), np.float32))
+            pk_, pv_ = (dev(rng.standard_normal((b_, hkv_, p_, d_), np.float32)) for _ in range(2)) if p_ else (None, None)
+            ok_, ov_ = empty((b_, hkv_, t_, d_)), empty((b_, hkv_, t_, d_))
+            adims = (C.c_int32 * L.ATTENTION_NDIMS)(b_, hq_, hkv_, sq_, sq_, p_, d_, d_, causal_, L.ATTN_MASK_NONE)
+            ast = (C.c_int64 * L.ATTENTION_NSTRIDES)(hq_ * sq_ * d_, sq_ * d_, d_, hkv_ * sq_ * d_, sq_ * d_, d_, hkv_ * sq_ * d_, sq_ * d_, d_,
+                                                     hq_ * sq_ * d_, sq_ * d_, d_, 0, 0, 0, 0)
+            attn = (lambda: ctx.call("rten_hip_attention_f32", adims, ast, float(d_) ** -0.5, q_.vp, k_.vp, v_.vp, None, pk_ and pk_.vp, pv_ and pv_.vp, None,
+                                     o_.vp, ok_.vp, ov_.vp))
+            shape = f"batch={b_} rows={sq_} past={p_} heads={hq_} kv_heads={hkv_} head_size={d_} causal={causal_}"
+            flops = 4.0 * b_ * hq_ * sq_ * t_ * d_  # both products over the full rectangle, masked or not
+            for run in (1, 2, 3):
+                for pname, path in (("composed path (mode 1)", 1), ("fused kernel (mode 4)", 4), ("dispatch rule (mode 0)", 0)):
+                    try:
+                        ctx.call("rten_hip_set_attention_path", path)
+                    except L.HipError:
+                        continue
+                    mfma(f"attention_kv: prefill, {pname}, run {run}", shape, attn, flops, F32_PEAK_TF, "TFLOP/s")
+            ctx.call("rten_hip_set_attention_path", 0)
+            del q_, k_, v_, o_, pk_, pv_, ok_, ov_
+
     if args.cpu_baseline:
         sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         import bench  # the oracle is only ever touched through bench.py's cpu_baseline leg
