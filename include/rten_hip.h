@@ -481,7 +481,10 @@ int32_t rten_hip_rotary_embedding_f32(rten_hip_ctx *ctx, int32_t batch, int32_t 
  * keys, score rows and 8-key block sums live in scratch (at most 64 MiB per pass over the (batch, KV head) pairs, or one pair's rows), and the result has the
  * same bits for every split.  The rule takes it where the decode kernel's LDS does not fit, and where B * KV workgroups under-fill the device at a cache long
  * enough to pay for its extra launches.  rten_hip_set_gqa_path: 0 that rule, 1 the composed path only, 2 the decode kernel or RTEN_HIP_ERR_UNSUPPORTED, 3 the
- * split decode form or RTEN_HIP_ERR_UNSUPPORTED (it takes one query row in the gemv order and head size 64 or 128).  rten_hip_set_gqa_split: the split
+ * split decode form or RTEN_HIP_ERR_UNSUPPORTED (it takes one query row in the gemv order and head size 64 or 128), 4 the fused prefill kernel or
+ * RTEN_HIP_ERR_UNSUPPORTED.  That kernel covers what would take the blocked-order composed path (more than one query row, or one row with the gemv order
+ * off) at head size 64 or 128 on at most 2^31 - 1 workgroups (B * H * ceil(S / 64)): a strip of 64 query rows per workgroup in one launch after the prepare
+ * launch, no score scratch, key tiles outside the strip's causal / window band skipped, the composed path's bits.  rten_hip_set_gqa_split: the split
  * form's keys per workgroup, 0 (the rule, from B, KV and P) or a positive multiple of 8; anything else is RTEN_HIP_ERR_INVALID_VALUE. */
 #define RTEN_HIP_GQA_NDIMS 10
 #define RTEN_HIP_GQA_NSTRIDES 12

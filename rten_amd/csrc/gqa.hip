@@ -42,6 +42,8 @@
 //     gemv entry on P + 1 columns: which keys are a column block's left-overs follows the DEVICE kv_len, as in the reference, so a right-padded item keeps the
 //     reference's bits.  PV is the gemv entry over P + 1 keys; the keys beyond kv_len have probability 0 and zero rows, and a chain that starts at +0
 //     cannot be moved by +-0 addends.  (Head sizes above 512 would need the depth-block beta step: refused.)
+//   * the fused prefill kernel (gqa_prefill.hip; D 64 / 128, every call that would take the composed path in the blocked order): GEMM, gqa_scores_kernel and
+//     GEMM in one launch with no score scratch, key tiles outside a strip's causal / window band skipped, same bits.  Mode 4, and mode 0 where prefill_pays().
 #include "gqa_common.h"
 #include "softmax_row.h"
 
@@ -289,6 +291,16 @@ size_t decode_lds_bytes(int G, int D, int T) { return sizeof(float) * ((size_t)G
 constexpr size_t LDS_PER_WORKGROUP = 160 * 1024;
 constexpr size_t SCORE_PASS_BYTES = 64u << 20; // the composed path's score buffer per pass over the query rows
 
+// Whether mode 0 prefers the fused prefill kernel (gqa_prefill.hip) to the composed path for a call that kernel covers: the measured range of
+// docs/KERNELS.md 4.18 at H 32 / KV 8.  First prompts (no past buffer, so past_len is 0 whatever the device says) of at least 2048 rows on at least the 1024
+// workgroups of the smallest winning row: 1.36 against 1.38 ms at head size 128 (4.44 against 6.86 ms at batch 4, 14.6 against 30.3 ms at 8192 rows) and
+// 0.74 against 1.03 ms at head size 64.  A window only shortens the band the kernel walks and leaves the composed path's GEMMs as they are (4.9 against
+// 29.0 ms at 8192 rows, window 1024).  It loses at 128 and 512 rows and on 512 rows appended to a past of 2048; with a bias nothing was measured.
+bool prefill_pays(const GqaArgs &a) {
+    if (a.P != 0 || a.S < 2048 || a.bias) return false;
+    return (int64_t)a.B * a.H * ((a.S + 63) / 64) >= 1024;
+}
+
 template <int D>
 int32_t launch_decode(rten_hip_ctx *ctx, const GqaArgs &a, size_t lds) {
     // the kernel's dynamic LDS ceiling, raised once per device (not a stream operation: nothing lands in a capture)
@@ -310,7 +322,7 @@ int32_t launch_decode(rten_hip_ctx *ctx, const GqaArgs &a, size_t lds) {
 
 RTEN_EXPORT int32_t rten_hip_set_gqa_path(rten_hip_ctx *ctx, int32_t mode) {
     RTEN_CHECK_CTX(ctx);
-    if (mode < 0 || mode > 3) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "set_gqa_path: mode must be 0, 1, 2 or 3");
+    if (mode < 0 || mode > 4) return rten_set_error(ctx, RTEN_HIP_ERR_INVALID_VALUE, "set_gqa_path: mode must be 0, 1, 2, 3 or 4");
     ctx->gqa_path = mode;
     return RTEN_HIP_OK;
 }
@@ -361,6 +373,10 @@ RTEN_EXPORT int32_t rten_hip_gqa_f32(rten_hip_ctx *ctx, const int32_t *dims, con
         return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "gqa: the split decode form takes one query row in the gemv order and head size 64 or 128");
     const bool split = splittable && (ctx->gqa_path == 3 || (ctx->gqa_path == 0 && (!covered || rten_gqa_split_pays(ctx, a))));
     const bool fused = covered && ctx->gqa_path != 1 && !split;
+    const bool prefillable = !one_row && rten_gqa_prefill_covers(a);
+    if (ctx->gqa_path == 4 && !prefillable)
+        return rten_set_error(ctx, RTEN_HIP_ERR_UNSUPPORTED, "gqa: the fused prefill kernel takes more than one query row, or one row with the gemv order off, and head size 64 or 128");
+    const bool prefill = prefillable && (ctx->gqa_path == 4 || (ctx->gqa_path == 0 && prefill_pays(a)));
 
     // scratch: [rotated Q | scores, or the split form's rows and block sums], the auxiliary buffer (the GEMMs called below own `scratch`).  The composed path works through the query rows in passes
     // of SC rows so that the score buffer [B, H, SC, T] stays within SCORE_PASS_BYTES whatever the prompt length (rows are independent of one another).
@@ -370,7 +386,7 @@ RTEN_EXPORT int32_t rten_hip_gqa_f32(rten_hip_ctx *ctx, const int32_t *dims, con
     size_t sc_rows = SCORE_PASS_BYTES / sizeof(float) / row_elems;
     sc_rows = sc_rows < 1 ? 1 : (sc_rows > (size_t)a.S ? (size_t)a.S : sc_rows);
     a.SC = (int)sc_rows;
-    const size_t score_elems = fused ? 0 : split ? rten_gqa_split_scratch_elems(a) : row_elems * sc_rows;
+    const size_t score_elems = fused || prefill ? 0 : split ? rten_gqa_split_scratch_elems(a) : row_elems * sc_rows;
     float *aux = nullptr;
     if (q_pad + score_elems > 0) {
         aux = (float *)rten_aux_scratch(ctx, (q_pad + score_elems) * sizeof(float) + 256);
@@ -391,6 +407,7 @@ RTEN_EXPORT int32_t rten_hip_gqa_f32(rten_hip_ctx *ctx, const int32_t *dims, con
     }
     if (fused) return a.D == 64 ? launch_decode<64>(ctx, a, lds) : launch_decode<128>(ctx, a, lds);
     if (split) return rten_gqa_split_launch(ctx, a, ctx->gqa_split, a.scores);
+    if (prefill) return rten_gqa_prefill_launch(ctx, a);
 
     // ---- composed path.  Batch levels: outer = (b, KV head), inner = the G query heads of the group, K and V with inner stride 0.  (b, KV head) is
     // one stride of Q and out only for one batch item, or one token whose batch stride is H heads; otherwise one launch per batch item.

@@ -45,3 +45,8 @@ int32_t rten_gqa_split_launch(rten_hip_ctx *ctx, const GqaArgs &a, int keys_per_
 // the rule's chunk length for a call's host-known dims, and whether mode 0 prefers the split form to a one-workgroup kernel that fits
 int rten_gqa_split_keys(const rten_hip_ctx *ctx, const GqaArgs &a);
 bool rten_gqa_split_pays(const rten_hip_ctx *ctx, const GqaArgs &a);
+
+// gqa_prefill.hip.  Whether the fused prefill kernel covers a call's head size and grid (the caller checks that the call is in the blocked order), and its
+// launch after gqa_prepare_kernel, with a.q already the rotated copy where there is one.  It needs no scratch.
+bool rten_gqa_prefill_covers(const GqaArgs &a);
+int32_t rten_gqa_prefill_launch(rten_hip_ctx *ctx, const GqaArgs &a);

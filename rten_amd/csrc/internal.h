@@ -54,7 +54,7 @@ struct rten_hip_ctx {
     int wave_flavour = 0; // pipeline 6: 0 = k-tiles of 16 x 2 LDS stages, 1 = 8 x 4, 2 = 16 x 3
     int num_cus = 256;
     int sdpa_path = 0;  // 0 automatic (fused attention kernel when it covers the shape), 1 composed path only
-    int gqa_path = 0;   // GroupQueryAttention: 0 automatic, 1 composed path only, 2 the one-launch decode kernel or an error, 3 the split decode form or an error (gqa.hip)
+    int gqa_path = 0;   // GroupQueryAttention: 0 automatic, 1 composed path only, 2 the one-launch decode kernel or an error, 3 the split decode form or an error, 4 the fused prefill kernel or an error (gqa.hip)
     int gqa_split = 0;  // keys per workgroup of the split decode form: 0 = the rule, else a positive multiple of 8 (gqa_split.hip)
     int attention_path = 0; // Attention (opset 23): 0 automatic, 1 composed path only, 2 the cache-appending decode kernel or an error, 3 the split decode form or an error, 4 the fused prefill kernel or an error (attention_kv.hip)
     int attention_split = 0; // keys per workgroup of that split decode form: 0 = the rule, else a positive multiple of 8 (attention_split.hip)

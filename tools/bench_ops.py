@@ -821,6 +821,34 @@ def main():
             ctx.call("rten_hip_set_attention_path", 0)
             del q_, k_, v_, o_, pk_, pv_, ok_, ov_
 
+    # ---- GroupQueryAttention prefill (--only "gqa: prefill" selects these rows alone): the whole call, prepare launch included, at H 32 / KV 8 on the
+    # composed path (mode 1), the fused prefill kernel (gqa_prefill.hip, mode 4) and the dispatch rule (mode 0), measured alternately, three runs each.
+    # A library without mode 4 (the parent's, when the two are timed alternately) skips that row.
+    if want("gqa: prefill rows"):
+        for b_, s_, p_, d_, win_ in ((1, 128, 0, 128, 0), (1, 512, 0, 128, 0), (1, 2048, 0, 128, 0), (1, 8192, 0, 128, 0), (4, 2048, 0, 128, 0),
+                                     (1, 512, 2048, 128, 0), (1, 8192, 0, 128, 1024), (1, 2048, 0, 64, 0)):
+            h_, kv_, t_ = 32, 8, p_ + s_
+            q_, o_ = dev(rng.standard_normal((b_, s_, h_ * d_), np.float32)), empty((b_, s_, h_ * d_))
+            k_, v_ = dev(rng.standard_normal((b_, s_, kv_ * d_), np.float32)), dev(rng.standard_normal((b_, s_, kv_ * d_), np.float32))
+            pk_, pv_ = (dev(rng.standard_normal((b_, kv_, p_, d_), np.float32)) for _ in range(2)) if p_ else (None, None)
+            ok_, ov_ = empty((b_, kv_, t_, d_)), empty((b_, kv_, t_, d_))
+            sl_, tot_ = dev(np.full(b_, t_ - 1, np.int32)), dev(np.array([t_], np.int32))
+            gdims = (C.c_int32 * L.GQA_NDIMS)(b_, s_, h_, kv_, d_, p_, 0, 0, 0, win_)
+            gst = (C.c_int64 * L.GQA_NSTRIDES)(s_ * h_ * d_, h_ * d_, d_, s_ * kv_ * d_, kv_ * d_, d_, s_ * kv_ * d_, kv_ * d_, d_, 0, 0, 0)
+            call = (lambda: ctx.call("rten_hip_gqa_f32", gdims, gst, float(d_) ** -0.5, q_.vp, k_.vp, v_.vp, pk_ and pk_.vp, pv_ and pv_.vp, sl_.vp, tot_.vp,
+                                     None, None, None, None, o_.vp, ok_.vp, ov_.vp))
+            shape = f"batch={b_} rows={s_} past={p_} heads={h_} kv_heads={kv_} head_size={d_} window={win_}"
+            flops = 4.0 * b_ * h_ * s_ * t_ * d_  # both products over the full rectangle, masked or not
+            for run in (1, 2, 3):
+                for pname, path in (("composed path (mode 1)", 1), ("fused kernel (mode 4)", 4), ("dispatch rule (mode 0)", 0)):
+                    try:
+                        ctx.call("rten_hip_set_gqa_path", path)
+                    except L.HipError:
+                        continue
+                    mfma(f"gqa: prefill, {pname}, run {run}", shape, call, flops, F32_PEAK_TF, "TFLOP/s")
+            ctx.call("rten_hip_set_gqa_path", 0)
+            del q_, k_, v_, o_, pk_, pv_, ok_, ov_, sl_, tot_
+
     if args.cpu_baseline:
         sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
         import bench  # the oracle is only ever touched through bench.py's cpu_baseline leg
